@@ -48,6 +48,10 @@ timings (RCCL).  Rank 0 prints ONE JSON line:
   cpu_baseline          the CPU oracle (torch-CPU port of the reference path) timed on this host on garment 0 OF THE BENCHMARK BATCH; its WNF
                         volume, NOCS bins and occupied cells are compared with slot 0 of the timed HIP result (oracle_check)
 
+--dump-outputs DIR: after the headline pass, rank 0 writes what its last timed step returned (every result tensor of its garments) as
+DIR/<name>.npy in float32 / float64, at most DUMP_LIMIT bytes in all, the largest arrays as a fixed seeded sample (dump_outputs).  The
+inputs below are seeded, so two builds run with the same arguments can be compared output for output.
+
 INPUT (--input planted, the default): the seeded global batch of synthetic.synthetic_cloud(colour="position") clouds and the seeded
 synthetic checkpoint with synthetic.plant_nocs_path -- the NOCS head decodes the clouds' colour channels (:= the garment's normalised,
 64-bin quantised positions), so the predicted NOCS coordinates spread over the garment's own shape: ~4900 occupied cells of the 128^3
@@ -65,6 +69,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -77,6 +82,8 @@ PEAK_16BIT_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 / f16 (v_mfma
 SPLIT_PRODUCTS = {"f16x2": 3, "bf16x3": 6, "bf16x2": 3}     # matrix-core products per fp32 product (csrc/unet_split.hip)
 PEAK_HBM_GBS = 8000.0
 CLOUD_SEED = 20260928
+DUMP_LIMIT = 64 * 10**6         # bytes: --dump-outputs writes at most this much, headers and manifest included
+DUMP_SEED = 1234
 
 
 def parse():
@@ -124,7 +131,12 @@ def parse():
     ap.add_argument("--no-latency-b1", action="store_true", help="skip the single-garment latency at the reference's shipped predict configuration (latency_b1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-garments", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline pass, write what its last timed step returned (rank 0's garments) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_LIMIT // 10**6} MB in all (dump_outputs): two builds run with the same arguments can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch is None:
         a.batch = 32 if a.workload == "pointnet2" else 16
     return a
@@ -772,6 +784,82 @@ def emit(full):
     print(text, flush=True)
 
 
+def _tensor_leaves(obj, prefix=""):
+    """(name, tensor) for every tensor of a result: dict keys and Batch fields joined with '.'"""
+    from garmentnets_amd.batch import Batch
+    if torch.is_tensor(obj):
+        yield prefix, obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _tensor_leaves(v, f"{prefix}.{k}" if prefix else str(k))
+    elif isinstance(obj, Batch):
+        for k in obj.keys:
+            yield from _tensor_leaves(getattr(obj, k), f"{prefix}.{k}")
+
+
+def _host_array(t):
+    """float32 / float64 numpy copy: floating tensors keep fp64 or become fp32, bool -> fp32, integers -> fp64 (exact below 2^53)"""
+    t = t.detach()
+    if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool):
+        return t.to(torch.float64).cpu().numpy()
+    return t.to(torch.float32).cpu().numpy()
+
+
+def _sample_indices(n, k, name):
+    """k distinct sorted indices of [0, n): one per equal stratum, drawn by a generator seeded with DUMP_SEED and the array's name"""
+    rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+    lo = (np.arange(k, dtype=np.int64) * n) // k
+    hi = (np.arange(1, k + 1, dtype=np.int64) * n) // k
+    return lo + (rng.random(k) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the arrays the timed path returned in its last step, as out_dir/<name>.npy.
+    Full workload (a list of per-garment dicts): one file per result key, the garments stacked on a new first axis; where their sizes
+    differ (the meshes) concatenated along the first axis instead, with <name>.rows.npy holding each garment's row count.  pointnet2: one
+    file per tensor of the result dict (aliases of a tensor already written are skipped).  Within DUMP_LIMIT the smallest arrays are
+    written whole and the rest share what is left: an array larger than its share is written as a fixed sample of its flattened
+    elements (_sample_indices: the same shape gives the same indices in every run).  dump_manifest.json gives every array's full shape and
+    whether it was sampled.  -> (files, bytes)"""
+    garments = res if isinstance(res, list) else [res]
+    per_name = {}
+    for g in garments:
+        seen = set()
+        for name, t in _tensor_leaves(g):
+            alias = (t.data_ptr(), tuple(t.shape), t.stride(), t.dtype)
+            if t.numel() and alias in seen:
+                continue
+            seen.add(alias)
+            per_name.setdefault(name, []).append(_host_array(t))
+    arrays, manifest = {}, {}
+    for name, a in per_name.items():
+        if len(a) != len(garments):
+            manifest[name] = {"skipped": f"present in {len(a)} of {len(garments)} garments"}
+        elif not isinstance(res, list):
+            arrays[name] = a[0]
+        elif all(x.shape == a[0].shape for x in a):
+            arrays[name] = np.stack(a)
+        else:
+            arrays[name] = np.concatenate(a)
+            arrays[name + ".rows"] = np.array([x.shape[0] for x in a], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                           # bytes of an .npy header
+    left = DUMP_LIMIT - 2 * 10**5                          # (the manifest)
+    order = sorted(arrays, key=lambda n: (arrays[n].nbytes, n))
+    files = total = 0
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i) - header
+        out = a if a.nbytes <= share else a.reshape(-1)[_sample_indices(a.size, max(share, 0) // a.itemsize, name)]
+        np.save(os.path.join(out_dir, name + ".npy"), out)
+        manifest[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": out is not a, "elements_written": int(out.size)}
+        left -= out.nbytes + header
+        files, total = files + 1, total + out.nbytes + header
+    with open(os.path.join(out_dir, "dump_manifest.json"), "w") as f:
+        json.dump({"sample": f"flattened elements, one per equal stratum, numpy default_rng([{DUMP_SEED}, crc32(name)])", "arrays": manifest}, f, indent=1)
+    return files, total
+
+
 def bench_inputs(batch, points, grid, reduce, input_kind, rank=0, world=1):
     """the benchmark's model inputs: (hparams, state dict, this rank's shard of the seeded global batch on the host, (lo, hi)).
     tests/test_gpu_fullsize.py::test_bench_batch_against_oracle calls this to check THE batch the number is quoted on."""
@@ -1021,6 +1109,9 @@ def main():
     # cached or paid a 17 GB hipMalloc -- ~0.5 s on these boxes -- came down to which cross-stream frees of the probe had been polled as
     # complete: the same build measured 59 or 143 garments/s depending on it, profiles/r05_ab_experiments.txt section 17.)
     dt, res, groups = timed(step, args.steps, max(2, args.warmup) if pipelined[0] else max(1, args.warmup), hw_name="headline")
+    if args.dump_outputs and rank == 0:                 # (outside every timed region)
+        n_files, n_bytes = dump_outputs(res, args.dump_outputs)
+        print(f"bench.py: --dump-outputs: {n_files} arrays, {n_bytes / 1e6:.1f} MB -> {args.dump_outputs}", file=sys.stderr, flush=True)
     verts_total = None
     checksums = []                                   # per local garment: fp64 sum of its WNF volume (full) / logits (pointnet2), last timed step
     probe = None                                     # slot 0 of the timed result, kept for the oracle check of the cpu_baseline leg

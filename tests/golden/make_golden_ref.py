@@ -17,6 +17,7 @@ ImplicitWNFDecoder, the 64^3-chunk decode loop -- is the reference's code execut
 
 Only DATA (inputs, expected outputs) is written to tests/golden/*.npz; no reference source is copied.
 """
+import copy
 import os
 import sys
 import types
@@ -153,6 +154,26 @@ def ref_pipeline(hp, sd):
     return model
 
 
+FP64_QUANTUM = 2.0 ** -22
+
+
+def write_fp64(name, volumes, **arrays):
+    """ref_<name>_fp64.npz: the reference's UNet run in fp64 -- fp32 conv3d on the CPU sums in an order that differs from machine to
+    machine (by up to ~2e-5 on these volumes, more than the tests' 1e-5), fp64 does not at that tolerance; tests/test_oracle_golden.py
+    compares the oracle's fp64 UNet with these.  volumes: {key of ref_<name>.npz: (fp64 volume, that fp32 volume)}, stored as <key>_to64 =
+    the int16 number of FP64_QUANTUM steps from the fp32 golden to the fp64 result (rounding error <= 1.2e-7; a fraction of the bytes of
+    the volume itself).  arrays: stored as they are"""
+    out = {"quantum": np.float64(FP64_QUANTUM)}
+    for key, (v64, v32) in volumes.items():
+        q = torch.round((v64 - v32.double()) / FP64_QUANTUM)
+        assert float(q.abs().max()) < 2 ** 15, key
+        out[key + "_to64"] = q.numpy().astype(np.int16)
+    out.update(arrays)
+    path = os.path.join(REPO, "tests", "golden", f"ref_{name}_fp64.npz")
+    np.savez_compressed(path, **out)
+    print(name, "fp64 ->", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def run_case(name, B, n_points, grid, reduce_method, Q, seed, store_full=True, stride=1):
     from components.gridding import VirtualGrid, ArraySlicer
     hp = S.default_hparams(grid=grid, reduce_method=reduce_method)
@@ -167,23 +188,30 @@ def run_case(name, B, n_points, grid, reduce_method, Q, seed, store_full=True, s
         u3 = model.unet3d_forward(p2)
         vol_in = model.volume_agg(nd)
         vol = u3["out_feature_volume"]
-        # chunked volume decode exactly as predict.py:145-157, garment 0
-        vg = VirtualGrid(grid_shape=(Q,) * 3)
-        gp = vg.get_grid_points(include_batch=False)
-        slicer = ArraySlicer(gp.shape, (64, 64, 64))
-        wnf = torch.zeros(gp.shape[:-1])
-        for i in range(len(slicer)):
-            sl = tuple(slicer[i])
-            q = gp[sl]
-            r = model.volume_decoder_forward({"out_feature_volume": vol[0:1]}, q.reshape(1, -1, 3))
-            wnf[sl] = r["pred_volume_value"].view(*q.shape[:-1])
         g = torch.Generator().manual_seed(seed + 77)
         sq = torch.rand(B, 257, 3, generator=g)
         sq[:, 0] = 0.0
         sq[:, 1] = 1.0
         sq[:, 2] = torch.tensor([0.0, 1.0, 0.5])
-        surf = model.surface_decoder_forward(u3, sq)["out_features"]
-        volq = model.volume_decoder_forward(u3, sq)
+
+        def decoders(vol):
+            """chunked volume decode exactly as predict.py:145-157 (garment 0), the surface and volume decoders at sq"""
+            vg = VirtualGrid(grid_shape=(Q,) * 3)
+            gp = vg.get_grid_points(include_batch=False)
+            slicer = ArraySlicer(gp.shape, (64, 64, 64))
+            wnf = torch.zeros(gp.shape[:-1])
+            for i in range(len(slicer)):
+                sl = tuple(slicer[i])
+                q = gp[sl]
+                r = model.volume_decoder_forward({"out_feature_volume": vol[0:1]}, q.reshape(1, -1, 3))
+                wnf[sl] = r["pred_volume_value"].view(*q.shape[:-1])
+            u = {"out_feature_volume": vol}
+            return wnf, model.surface_decoder_forward(u, sq)["out_features"], model.volume_decoder_forward(u, sq)["pred_volume_value"]
+
+        wnf, surf, volq = decoders(vol)
+        # the reference's UNet in fp64 on the same input (see write_fp64), its decoders on that volume rounded to fp32
+        vol64 = copy.deepcopy(model.unet_3d).double()(vol_in.double())
+        wnf_u64, surf_u64, volq_u64 = decoders(vol64.float())
     sl = slice(None, None, stride)
     out.update(
         meta=np.array([B, n_points, grid, Q, seed, stride], np.int64), reduce_method=np.array(reduce_method),
@@ -191,15 +219,19 @@ def run_case(name, B, n_points, grid, reduce_method, Q, seed, store_full=True, s
         pred_nocs=nd.pos.numpy()[sl], pred_confidence=nd.pred_confidence.numpy()[sl],
         per_point_features=p2["per_point_features"].numpy()[sl], per_point_logits=p2["per_point_logits"].numpy()[sl],
         global_logits=p2["global_logits"].numpy(), global_feature=p2["global_feature"].numpy(),
-        surf_query=sq.numpy(), surf_out=surf.numpy(), volq_out=volq["pred_volume_value"].numpy(),
+        surf_query=sq.numpy(), surf_out=surf.numpy(), volq_out=volq.numpy(),
         wnf_volume=wnf.numpy(),
         in_volume_sum=vol_in.double().sum(dim=(2, 3, 4)).numpy(), in_volume_abs=vol_in.double().abs().sum().numpy(),
         out_volume_sum=vol.double().sum(dim=(2, 3, 4)).numpy(), out_volume_abs=vol.double().abs().sum().numpy(),
     )
     if store_full:
         out.update(in_feature_volume=vol_in.numpy(), out_feature_volume=vol.numpy())
+        key, pick = "out_feature_volume", lambda v: v
     else:
         out.update(out_volume_probe=vol.numpy()[:, ::16, ::3, ::3, ::3], in_volume_probe=vol_in.numpy()[:, ::16, ::3, ::3, ::3])
+        key, pick = "out_volume_probe", lambda v: v[:, ::16, ::3, ::3, ::3]
+    write_fp64(name, {key: (pick(vol64), pick(vol))}, out_volume_sum64=vol64.sum(dim=(2, 3, 4)).numpy(), wnf_volume_u64=wnf_u64.numpy(),
+               surf_out_u64=surf_u64.numpy(), volq_out_u64=volq_u64.numpy())
     path = os.path.join(REPO, "tests", "golden", f"ref_{name}.npz")
     np.savez_compressed(path, **out)
     print(name, "->", path, os.path.getsize(path) // 1024, "KiB",
@@ -220,9 +252,11 @@ def unet_case(name, G, B, seed):
     x = torch.randn(B, 128, G, G, G, generator=g)
     with torch.no_grad():
         y = net(x)
+        y64 = copy.deepcopy(net).double()(x.double())
     path = os.path.join(REPO, "tests", "golden", f"ref_{name}.npz")
     np.savez_compressed(path, meta=np.array([G, B, seed], np.int64), y=y.numpy())
     print(name, "->", path, os.path.getsize(path) // 1024, "KiB")
+    write_fp64(name, {"y": (y64, y)})
 
 
 def grid_case():

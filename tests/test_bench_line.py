@@ -86,3 +86,31 @@ def test_pick_roofline_names_the_group_with_the_most_time():
     rl = bench.pick_roofline(args, groups, "f16x2", "f16x2")
     assert rl["kernel"] == "conv3d_split_wino_kernel<true>" and rl["peak"] == pytest.approx(2500.0 / 2)       # 3 x 36/54 executed products
     assert set(rl["all_conv_instances"]) == {"conv3d_split_wino_kernel<true>", "conv3d_split_strip_kernel<true>"}
+
+
+def test_dump_outputs_is_reproducible_typed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: every result key of every garment, float32 / float64 only, ragged mesh arrays concatenated with their row counts,
+    within DUMP_LIMIT (the largest array sampled at seeded indices), the same files from the same result"""
+    import numpy as np
+    import torch
+    bench = _bench()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 400_000)
+    g = torch.Generator().manual_seed(0)
+    res = [dict(wnf_volume=torch.randn(32, 32, 32, generator=g), verts=torch.rand(100 + b, 3, dtype=torch.float64),
+                faces=torch.randint(0, 100, (150 + b, 3), dtype=torch.int32), global_feature=torch.randn(64, generator=g)) for b in range(4)]
+    for d in ("a", "b"):
+        bench.dump_outputs(res, str(tmp_path / d))
+    names = sorted(f for f in os.listdir(tmp_path / "a") if f.endswith(".npy"))
+    assert names == ["faces.npy", "faces.rows.npy", "global_feature.npy", "verts.npy", "verts.rows.npy", "wnf_volume.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 400_000
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    assert np.array_equal(np.load(tmp_path / "a" / "faces.npy"), np.concatenate([r["faces"].numpy() for r in res]).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "verts.rows.npy"), [100, 101, 102, 103])
+    assert np.array_equal(np.load(tmp_path / "a" / "global_feature.npy"), np.stack([r["global_feature"].numpy() for r in res]))
+    wnf = np.stack([r["wnf_volume"].numpy() for r in res]).reshape(-1)
+    got = np.load(tmp_path / "a" / "wnf_volume.npy")
+    assert 0 < got.size < wnf.size and np.array_equal(got, wnf[bench._sample_indices(wnf.size, got.size, "wnf_volume")])
+    manifest = json.load(open(tmp_path / "a" / "dump_manifest.json"))["arrays"]
+    assert manifest["wnf_volume"]["sampled"] and manifest["wnf_volume"]["shape"] == [4, 32, 32, 32] and not manifest["faces"]["sampled"]

@@ -24,7 +24,9 @@ def _libasan():
 def test_oracle_goldens_under_address_and_ub_sanitizers():
     subprocess.check_call(["make", "-C", os.path.join(REPO, "oracle"), "asan"], stdout=subprocess.DEVNULL)
     so = os.path.join(REPO, "oracle", "libgn_oracle_asan.so")
-    env = dict(os.environ, LD_PRELOAD=_libasan(), GN_ORACLE_LIB=so, PYTHONPATH=REPO,
+    # (libasan first, as ASan requires; whatever the environment already preloads stays loaded behind it)
+    preload = " ".join(p for p in (_libasan(), os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, GN_ORACLE_LIB=so, PYTHONPATH=REPO,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:allocator_may_return_null=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     # the child must really be running the sanitized library
     probe = subprocess.run([sys.executable, "-c", "import oracle, numpy as np; L = oracle.lib(); print(L._name); "
