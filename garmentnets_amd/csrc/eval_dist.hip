@@ -1,0 +1,188 @@
+// eval_dist.hip -- the all-pairs searches of the evaluation metrics (eval.py), fp64, brute force.
+//
+//   gn_nearest_neighbor_f64_batch  exact 1-NN (scipy cKDTree.query(k=1)) -- chamfer, hybrid chamfer, gradient threshold
+//   gn_point_mesh_sqdist_batch     unsigned squared point-to-triangle-mesh distance (libigl point_mesh_squared_distance,
+//                                  what igl.hausdorff calls in both directions)
+//
+// Both take a pairs table so that one launch serves every (query set, reference set) pair of a sample: blockIdx.y = pair,
+// blockIdx.x = a block of 256 queries (one per thread), blocks past the pair's query count leave at once.  The reference set
+// streams through LDS in SoA tiles; every lane reads the same LDS element at a time (a broadcast).  The library is built with
+// -ffp-contract=off and the per-pair arithmetic below has no fma: every distance is the plain-rounded expression written here.
+#include <math.h>
+
+#include "common.h"
+
+#define ED_BLOCK 256
+#define NN64_TILE 256
+#define PM_TILE 128
+
+// ((dx*dx + dy*dy) + dz*dz): the summation order of cKDTree's squared Euclidean distance (4-way accumulators, all zero for 3-D,
+// then the scalar tail), so the distances are the ones scipy returns before its sqrt
+__device__ __forceinline__ double ed_sqdist3(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
+    double s = __dmul_rn(dx, dx);
+    s = __dadd_rn(s, __dmul_rn(dy, dy));
+    return __dadd_rn(s, __dmul_rn(dz, dz));
+}
+
+__device__ __forceinline__ double ed_dot3(double ax, double ay, double az, double bx, double by, double bz) {
+    return __dadd_rn(__dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)), __dmul_rn(az, bz));
+}
+
+__global__ __launch_bounds__(ED_BLOCK) void nn_f64_batch_kernel(const double *__restrict__ q, const double *__restrict__ ref,
+                                                                const int64_t *__restrict__ pairs, int32_t *__restrict__ idx,
+                                                                double *__restrict__ d2) {
+    __shared__ double sx[NN64_TILE], sy[NN64_TILE], sz[NN64_TILE];
+    const int64_t *pr = pairs + 4 * (int64_t)blockIdx.y;
+    const int64_t q_off = pr[0], nq = pr[1], r_off = pr[2], nr = pr[3];
+    const int64_t i0 = (int64_t)blockIdx.x * ED_BLOCK;
+    if (i0 >= nq) return;                                   // block-uniform: no barrier is skipped by part of the block
+    const int64_t i = i0 + threadIdx.x;
+    const bool live = i < nq;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (live) { const double *p = q + 3 * (q_off + i); qx = p[0]; qy = p[1]; qz = p[2]; }
+    double best = __longlong_as_double(0x7ff0000000000000LL);    // +inf
+    int bi = -1;
+    const double *r = ref + 3 * r_off;
+    for (int64_t t0 = 0; t0 < nr; t0 += NN64_TILE) {
+        const int n = (int)((nr - t0) < NN64_TILE ? (nr - t0) : NN64_TILE);
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += ED_BLOCK) {
+            const double *p = r + 3 * (t0 + j);
+            sx[j] = p[0]; sy[j] = p[1]; sz[j] = p[2];
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const double d = ed_sqdist3(qx, qy, qz, sx[j], sy[j], sz[j]);
+            if (d < best) { best = d; bi = (int)(t0 + j); }          // strict: ties keep the lowest index
+        }
+    }
+    if (live) { idx[q_off + i] = bi; d2[q_off + i] = best; }
+}
+
+extern "C" int gn_nearest_neighbor_f64_batch(const double *query, const double *ref, const int64_t *pairs, int P, int64_t max_nq, int32_t *idx,
+                                             double *d2, void *stream) {
+    GN_REQUIRE(P >= 0 && P <= 65535 && max_nq >= 0 && max_nq < INT32_MAX, "gn_nearest_neighbor_f64_batch: bad sizes (P=%d, max_nq=%lld)", P,
+               (long long)max_nq);
+    if (P == 0 || max_nq == 0) return GN_OK;
+    GN_REQUIRE(query && pairs && idx && d2, "gn_nearest_neighbor_f64_batch: null pointer");
+    hipLaunchKernelGGL(nn_f64_batch_kernel, dim3((unsigned)gn_cdiv(max_nq, ED_BLOCK), (unsigned)P), dim3(ED_BLOCK), 0, gn_stream(stream), query, ref,
+                       pairs, idx, d2);
+    GN_LAUNCH_CHECK("gn_nearest_neighbor_f64_batch");
+    return GN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- point -> mesh
+// Per staged triangle (v0, v1, v2): v0, e0 = v1 - v0, e1 = v2 - v0, v1, e2 = v2 - v1, the Gram entries a = e0.e0, b = e0.e1,
+// c = e1.e1, 1 / det (det = a c - b b; 0 when det <= 0) and the reciprocal squared lengths of the three edges (0 for a zero-length edge).
+enum { PM_V0X, PM_V0Y, PM_V0Z, PM_E0X, PM_E0Y, PM_E0Z, PM_E1X, PM_E1Y, PM_E1Z, PM_V1X, PM_V1Y, PM_V1Z, PM_E2X, PM_E2Y, PM_E2Z,
+       PM_A, PM_B, PM_C, PM_IDET, PM_IA, PM_IC, PM_IE2, PM_NCONST };
+
+__device__ __forceinline__ double pm_rcp_or_zero(double x) { return x > 0.0 ? 1.0 / x : 0.0; }
+
+// squared distance from w (the query relative to the segment's start) to the segment start + t dir, t = clamp(w.dir / |dir|^2, 0, 1)
+__device__ __forceinline__ double pm_seg(double wx, double wy, double wz, double dx, double dy, double dz, double wd, double inv_len2) {
+    const double t = fmin(fmax(__dmul_rn(wd, inv_len2), 0.0), 1.0);
+    const double rx = __dsub_rn(wx, __dmul_rn(t, dx)), ry = __dsub_rn(wy, __dmul_rn(t, dy)), rz = __dsub_rn(wz, __dmul_rn(t, dz));
+    return ed_dot3(rx, ry, rz, rx, ry, rz);
+}
+
+__global__ __launch_bounds__(ED_BLOCK) void point_mesh_sqdist_batch_kernel(const double *__restrict__ q, const double *__restrict__ verts,
+                                                                           const int32_t *__restrict__ faces, const int64_t *__restrict__ pairs,
+                                                                           int32_t *__restrict__ face_idx, double *__restrict__ d2,
+                                                                           int64_t *__restrict__ bad) {
+    __shared__ double tri[PM_NCONST][PM_TILE];
+    const int64_t *pr = pairs + 6 * (int64_t)blockIdx.y;
+    const int64_t q_off = pr[0], nq = pr[1], v_off = pr[2], nv = pr[3], f_off = pr[4], nf = pr[5];
+    const int32_t *F = faces + 3 * f_off;
+    const double *V = verts + 3 * v_off;
+    const int64_t i0 = (int64_t)blockIdx.x * ED_BLOCK;
+    if (i0 >= nq) {
+        // a pair without queries still has its faces checked (once, by its first block): the wrapper raises on any bad index
+        if (blockIdx.x == 0)
+            for (int64_t f = threadIdx.x; f < nf; f += ED_BLOCK)
+                for (int k = 0; k < 3; ++k)
+                    if (F[3 * f + k] < 0 || F[3 * f + k] >= nv) *bad = 1;
+        return;
+    }
+    const int64_t i = i0 + threadIdx.x;
+    const bool live = i < nq;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (live) { const double *p = q + 3 * (q_off + i); qx = p[0]; qy = p[1]; qz = p[2]; }
+    double best = __longlong_as_double(0x7ff0000000000000LL);    // +inf
+    int bi = -1;
+    for (int64_t t0 = 0; t0 < nf; t0 += PM_TILE) {
+        const int n = (int)((nf - t0) < PM_TILE ? (nf - t0) : PM_TILE);
+        __syncthreads();
+        for (int j = threadIdx.x; j < n; j += ED_BLOCK) {
+            double p[3][3];
+            for (int k = 0; k < 3; ++k) {
+                const int32_t vi = F[3 * (t0 + j) + k];
+                p[k][0] = p[k][1] = p[k][2] = 0.0;
+                if (vi >= 0 && vi < nv) {
+                    p[k][0] = V[3 * (int64_t)vi]; p[k][1] = V[3 * (int64_t)vi + 1]; p[k][2] = V[3 * (int64_t)vi + 2];
+                } else {
+                    *bad = 1;                               // out of range: flagged, never read (a zero vertex stands in)
+                }
+            }
+            const double e0x = __dsub_rn(p[1][0], p[0][0]), e0y = __dsub_rn(p[1][1], p[0][1]), e0z = __dsub_rn(p[1][2], p[0][2]);
+            const double e1x = __dsub_rn(p[2][0], p[0][0]), e1y = __dsub_rn(p[2][1], p[0][1]), e1z = __dsub_rn(p[2][2], p[0][2]);
+            const double e2x = __dsub_rn(p[2][0], p[1][0]), e2y = __dsub_rn(p[2][1], p[1][1]), e2z = __dsub_rn(p[2][2], p[1][2]);
+            const double a = ed_dot3(e0x, e0y, e0z, e0x, e0y, e0z), b = ed_dot3(e0x, e0y, e0z, e1x, e1y, e1z);
+            const double c = ed_dot3(e1x, e1y, e1z, e1x, e1y, e1z), l2 = ed_dot3(e2x, e2y, e2z, e2x, e2y, e2z);
+            const double det = __dsub_rn(__dmul_rn(a, c), __dmul_rn(b, b));
+            tri[PM_V0X][j] = p[0][0]; tri[PM_V0Y][j] = p[0][1]; tri[PM_V0Z][j] = p[0][2];
+            tri[PM_E0X][j] = e0x; tri[PM_E0Y][j] = e0y; tri[PM_E0Z][j] = e0z;
+            tri[PM_E1X][j] = e1x; tri[PM_E1Y][j] = e1y; tri[PM_E1Z][j] = e1z;
+            tri[PM_V1X][j] = p[1][0]; tri[PM_V1Y][j] = p[1][1]; tri[PM_V1Z][j] = p[1][2];
+            tri[PM_E2X][j] = e2x; tri[PM_E2Y][j] = e2y; tri[PM_E2Z][j] = e2z;
+            tri[PM_A][j] = a; tri[PM_B][j] = b; tri[PM_C][j] = c;
+            tri[PM_IDET][j] = pm_rcp_or_zero(det);
+            tri[PM_IA][j] = pm_rcp_or_zero(a); tri[PM_IC][j] = pm_rcp_or_zero(c); tri[PM_IE2][j] = pm_rcp_or_zero(l2);
+        }
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const double wx = __dsub_rn(qx, tri[PM_V0X][j]), wy = __dsub_rn(qy, tri[PM_V0Y][j]), wz = __dsub_rn(qz, tri[PM_V0Z][j]);
+            const double e0x = tri[PM_E0X][j], e0y = tri[PM_E0Y][j], e0z = tri[PM_E0Z][j];
+            const double e1x = tri[PM_E1X][j], e1y = tri[PM_E1Y][j], e1z = tri[PM_E1Z][j];
+            const double d0 = ed_dot3(wx, wy, wz, e0x, e0y, e0z), d1 = ed_dot3(wx, wy, wz, e1x, e1y, e1z);
+            // the three clamped segment distances (a zero-length edge clamps to its start point: degenerate triangles land here)
+            const double s0 = pm_seg(wx, wy, wz, e0x, e0y, e0z, d0, tri[PM_IA][j]);
+            const double s1 = pm_seg(wx, wy, wz, e1x, e1y, e1z, d1, tri[PM_IC][j]);
+            const double ux = __dsub_rn(qx, tri[PM_V1X][j]), uy = __dsub_rn(qy, tri[PM_V1Y][j]), uz = __dsub_rn(qz, tri[PM_V1Z][j]);
+            const double e2x = tri[PM_E2X][j], e2y = tri[PM_E2Y][j], e2z = tri[PM_E2Z][j];
+            const double s2 = pm_seg(ux, uy, uz, e2x, e2y, e2z, ed_dot3(ux, uy, uz, e2x, e2y, e2z), tri[PM_IE2][j]);
+            // the projection onto the plane in barycentric form: w = s e0 + t e1 + (normal part)
+            const double a = tri[PM_A][j], b = tri[PM_B][j], c = tri[PM_C][j], idet = tri[PM_IDET][j];
+            const double s = __dmul_rn(__dsub_rn(__dmul_rn(c, d0), __dmul_rn(b, d1)), idet);
+            const double t = __dmul_rn(__dsub_rn(__dmul_rn(a, d1), __dmul_rn(b, d0)), idet);
+            const double rx = __dsub_rn(__dsub_rn(wx, __dmul_rn(s, e0x)), __dmul_rn(t, e1x));
+            const double ry = __dsub_rn(__dsub_rn(wy, __dmul_rn(s, e0y)), __dmul_rn(t, e1y));
+            const double rz = __dsub_rn(__dsub_rn(wz, __dmul_rn(s, e0z)), __dmul_rn(t, e1z));
+            const double plane = ed_dot3(rx, ry, rz, rx, ry, rz);
+            const bool inside = idet > 0.0 && s >= 0.0 && t >= 0.0 && __dadd_rn(s, t) <= 1.0;
+            // the segment distances stay in the minimum when the projection is inside: on a sliver (det nearly cancelled) s and t are
+            // noise, `plane` is then only an upper bound and an edge can be closer
+            const double seg = fmin(fmin(s0, s1), s2);
+            const double d = inside ? fmin(plane, seg) : seg;
+            if (d < best) { best = d; bi = (int)(t0 + j); }          // strict: ties keep the lowest face index
+        }
+    }
+    if (live) {
+        if (isnan(qx) || isnan(qy) || isnan(qz)) best = __longlong_as_double(0x7ff8000000000000LL);   // a NaN query has no distance
+        face_idx[q_off + i] = bi;
+        d2[q_off + i] = best;
+    }
+}
+
+extern "C" int gn_point_mesh_sqdist_batch(const double *query, const double *verts, const int32_t *faces, const int64_t *pairs, int P, int64_t max_nq,
+                                          int32_t *face_idx, double *d2, int64_t *bad, void *stream) {
+    GN_REQUIRE(P >= 0 && P <= 65535 && max_nq >= 0 && max_nq < INT32_MAX, "gn_point_mesh_sqdist_batch: bad sizes (P=%d, max_nq=%lld)", P,
+               (long long)max_nq);
+    if (P == 0) return GN_OK;
+    GN_REQUIRE(pairs && bad, "gn_point_mesh_sqdist_batch: null pointer");
+    hipLaunchKernelGGL(point_mesh_sqdist_batch_kernel, dim3((unsigned)(max_nq > 0 ? gn_cdiv(max_nq, ED_BLOCK) : 1), (unsigned)P), dim3(ED_BLOCK), 0,
+                       gn_stream(stream), query, verts, faces, pairs, face_idx, d2, bad);
+    GN_LAUNCH_CHECK("gn_point_mesh_sqdist_batch");
+    return GN_OK;
+}

@@ -116,13 +116,13 @@ class Group:
         """C-order Zarr v2 array; chunks=None -> one chunk (chunks == data.shape: what the reference's prediction.zarr uses), else a
         chunk grid with full-size (fill-padded) edge chunks; compressor: None, ("zlib", level) or a Zarr v2 codec config dict
         (e.g. REFERENCE_COMPRESSOR; anything but zlib needs numcodecs)"""
-        data = np.ascontiguousarray(data)
+        data = np.ascontiguousarray(data) if np.ndim(data) else np.asarray(data)     # (ascontiguousarray makes a 0-d array 1-d)
         apath = os.path.join(self.path, name)
         comp = _codec_config(compressor)
         codec = _Codec(comp, apath)
         os.makedirs(apath, exist_ok=True)
         shape = list(data.shape)
-        cshape = shape if chunks is None else [int(c) for c in chunks]
+        cshape = [max(1, n) for n in shape] if chunks is None else [int(c) for c in chunks]      # an empty axis still has a chunk size
         assert len(cshape) == len(shape)
         fill = 0.0 if data.dtype.kind == "f" else 0
         meta = {"chunks": cshape, "compressor": comp, "dtype": data.dtype.str, "fill_value": fill,

@@ -987,3 +987,105 @@ def nearest_neighbor(query, ref):
     d2 = torch.empty(nq, dtype=torch.float32, device=query.device)
     _lib.call("gn_nearest_neighbor", _p(query), nq, _p(ref), ref.shape[0], _p(idx), _p(d2), _stream())
     return idx, d2
+
+
+def _rows3_f64(t, name):
+    t = t.to(torch.float64).contiguous()
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected an (N, 3) tensor, got {tuple(t.shape)}")
+    return t
+
+
+def _cat_sets(tensors, name, dtype=torch.float64, width=3, dedup=True):
+    """concatenate point / face sets -> (joint tensor, row offset of each entry); dedup: a tensor passed more than once is stored once (for
+    the READ-ONLY sets: query rows are also output rows and must not share them)"""
+    uniq, offs, seen, n = [], [], {}, 0
+    for k, t in enumerate(tensors):
+        key = id(t) if dedup else k
+        if key not in seen:
+            seen[key] = n
+            uniq.append(t)
+            n += t.shape[0]
+        offs.append(seen[key])
+    if not uniq:
+        return None, offs
+    joint = torch.cat([u.reshape(-1, width) for u in uniq]) if len(uniq) > 1 else uniq[0]
+    return _chk(joint.to(dtype).contiguous(), dtype, name), offs
+
+
+def _pairs_table(rows, device):
+    if len(rows) > 65535:
+        raise ValueError(f"at most 65535 pairs per launch, got {len(rows)}")
+    return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), -1).to(device, non_blocking=False)
+
+
+def nearest_neighbor_f64_batch(queries, refs):
+    """fp64 exact 1-NN for every (queries[k], refs[k]) pair in ONE launch (gn_nearest_neighbor_f64_batch) -> list of (idx int32 [nq_k],
+    d2 float64 [nq_k]).  d2 in cKDTree's summation order; ties -> lowest index; an empty reference set gives (+inf, -1)."""
+    if len(queries) != len(refs):
+        raise ValueError("nearest_neighbor_f64_batch: one reference set per query set")
+    if not queries:
+        return []
+    queries = [_rows3_f64(q, "query") for q in queries]
+    refs = [_rows3_f64(r, "ref") for r in refs]
+    dev = queries[0].device
+    q, qo = _cat_sets(queries, "query", dedup=False)
+    r, ro = _cat_sets(refs, "ref")
+    if r.shape[0] >= 2 ** 31:
+        raise ValueError("nearest_neighbor_f64_batch: more than 2^31 reference points")
+    rows = [(qo[k], queries[k].shape[0], ro[k], refs[k].shape[0]) for k in range(len(queries))]
+    pairs = _pairs_table(rows, dev)
+    max_nq = max(n for _, n, _, _ in rows)
+    idx = torch.empty(q.shape[0], dtype=_i32, device=dev)
+    d2 = torch.empty(q.shape[0], dtype=torch.float64, device=dev)
+    _lib.call("gn_nearest_neighbor_f64_batch", _p(q), _p(r), _p(pairs), len(rows), max_nq, _p(idx), _p(d2), _stream())
+    return [(idx[o:o + n], d2[o:o + n]) for o, n, _, _ in rows]
+
+
+def nearest_neighbor_f64(query, ref):
+    """-> (idx int32 [Nq], d2 float64 [Nq]): exact fp64 1-NN of every query point in `ref` (cKDTree.query(k=1) before its sqrt)"""
+    return nearest_neighbor_f64_batch([query], [ref])[0]
+
+
+def point_mesh_sqdist_batch(queries, meshes):
+    """fp64 unsigned squared distance of every query to the nearest triangle of its mesh, every (queries[k], meshes[k] = (verts, faces))
+    pair in ONE launch (gn_point_mesh_sqdist_batch) -> list of (face_idx int32 [nq_k], d2 float64 [nq_k]).  libigl's
+    point_mesh_squared_distance; ties -> lowest face index; an empty mesh gives (+inf, -1).  A face index outside [0, V) raises IndexError
+    (after the launch: one host synchronisation)."""
+    if len(queries) != len(meshes):
+        raise ValueError("point_mesh_sqdist_batch: one mesh per query set")
+    if not queries:
+        return []
+    queries = [_rows3_f64(q, "query") for q in queries]
+    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
+    faces = []
+    for _, f in meshes:
+        if f.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"faces: expected an integer tensor, got {f.dtype}")
+        if f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError(f"faces: expected an (F, 3) tensor, got {tuple(f.shape)}")
+        if f.dtype == torch.int64:          # int32 on the device; an index that does not fit is out of range: keep it so
+            f = f.clamp(min=-1, max=2 ** 31 - 1)
+        faces.append(f)
+    dev = queries[0].device
+    q, qo = _cat_sets(queries, "query", dedup=False)
+    v, vo = _cat_sets(verts, "verts")
+    f, fo = _cat_sets(faces, "faces", dtype=_i32)
+    if v.shape[0] >= 2 ** 31 or (f is not None and f.shape[0] >= 2 ** 31):
+        raise ValueError("point_mesh_sqdist_batch: more than 2^31 vertices or faces")
+    rows = [(qo[k], queries[k].shape[0], vo[k], verts[k].shape[0], fo[k], faces[k].shape[0]) for k in range(len(queries))]
+    pairs = _pairs_table(rows, dev)
+    max_nq = max(r[1] for r in rows)
+    face_idx = torch.empty(q.shape[0], dtype=_i32, device=dev)
+    d2 = torch.empty(q.shape[0], dtype=torch.float64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.call("gn_point_mesh_sqdist_batch", _p(q), _p(v), _p(f) if f is not None else None, _p(pairs), len(rows), max_nq, _p(face_idx), _p(d2),
+              _p(bad), _stream())
+    if int(bad.item()):
+        raise IndexError("point_mesh_sqdist: a face index is out of bounds for its mesh's vertices")
+    return [(face_idx[r[0]:r[0] + r[1]], d2[r[0]:r[0] + r[1]]) for r in rows]
+
+
+def point_mesh_sqdist(query, verts, faces):
+    """-> (face_idx int32 [Nq], d2 float64 [Nq]): squared distance of every query to the nearest triangle of (verts, faces)"""
+    return point_mesh_sqdist_batch([query], [(verts, faces)])[0]

@@ -12,7 +12,8 @@
  *   - all pointers are DEVICE pointers into caller-owned memory unless the name ends in _host.
  *   - stream is a hipStream_t passed as void* (NULL = default stream); all work is stream-ordered, no
  *     allocation, no host synchronisation, no global mutable state (LUTs are immutable).
- *   - dense float tensors are fp32, row-major with an explicit leading dimension (ld*) in elements.
+ *   - dense float tensors are fp32, row-major with an explicit leading dimension (ld*) in elements.  Exception: the two
+ *     evaluation distances (gn_nearest_neighbor_f64_batch, gn_point_mesh_sqdist_batch) take and return fp64 tensors.
  *   - volumes are CHANNEL-LAST: [B][D][H][W][C]  (the reference's NCDHW is a host-side view of this).
  *   - indices: point / vertex indices int32 on device (int64 only where the reference API exposes them).
  */
@@ -450,6 +451,23 @@ int gn_decoder_input_scale(const double *sumsq, int64_t V, int B, int C, float s
  * replaces the scipy cKDTree.query(k=1) calls of the Chamfer metrics -- eval.py:259-263,381-385.
  * idx [nq] int32, d2 [nq] squared distance. */
 int gn_nearest_neighbor(const float *query, int64_t nq, const float *ref, int64_t nr, int32_t *idx, float *d2, void *stream);
+
+/* fp64 exact 1-nearest-neighbour for P (query set, reference set) pairs in one launch -- the cKDTree.query(k=1) calls of
+ * eval.py:79-80,259-263,381-385 (gradient threshold, chamfer, hybrid chamfer).  query / ref: [*][3] fp64 rows; pairs [P][4] int64 on the
+ * device = {q_off, nq, r_off, nr} (rows of query / ref); max_nq = the largest nq.  idx [*] int32 (relative to r_off) and d2 [*] fp64 are
+ * written at rows q_off .. q_off + nq - 1.  d2 = (dx*dx + dy*dy) + dz*dz (cKDTree's order); ties -> lowest index; empty reference set ->
+ * d2 = +inf, idx = -1.  P <= 65535. */
+int gn_nearest_neighbor_f64_batch(const double *query, const double *ref, const int64_t *pairs, int P, int64_t max_nq, int32_t *idx, double *d2,
+                                  void *stream);
+
+/* fp64 unsigned squared distance from every query to the nearest triangle of its mesh, P (query set, mesh) pairs in one launch -- libigl's
+ * point_mesh_squared_distance, which igl.hausdorff calls in both directions (eval.py:564-567).  verts [*][3] fp64, faces [*][3] int32
+ * RELATIVE to the pair's v_off; pairs [P][6] int64 = {q_off, nq, v_off, nv, f_off, nf}.  face_idx [*] int32 (relative to f_off) and d2 [*]
+ * fp64 at the query rows.  Ties -> lowest face index; empty mesh -> +inf, -1; a NaN query -> d2 = NaN.  Degenerate triangles (zero area,
+ * repeated vertices) are measured as their edges.  A face index outside [0, nv) sets *bad = 1 (caller zeroes it; the distances are then
+ * meaningless).  P <= 65535. */
+int gn_point_mesh_sqdist_batch(const double *query, const double *verts, const int32_t *faces, const int64_t *pairs, int P, int64_t max_nq,
+                               int32_t *face_idx, double *d2, int64_t *bad, void *stream);
 
 #ifdef __cplusplus
 }
