@@ -21,8 +21,9 @@ global mutable state except immutable LUTs).  ``DEFAULT`` is read from the envir
                        run in Winograd F(2,3) form along x: 36 instead of 54 matrix-core tap products per output pair (csrc/unet_wino.hip); the transforms
                        are exact in the operands' zero pattern, error against fp64 stays within the f16x2 contract (tests/test_gpu_parity.py)
     winograd32         (f16x2, with winograd) the same form for the 32- / 64-wide layers at the two finest levels -- the encoder's second convolution 128 -> 32 at
-                       128^3, the last decoders' convolutions -- through the 32-wide column-block kernel (csrc/unet_wino32.hip, round 6; the polyphase partial
-                       of a decoder's first convolution is added in its epilogue).  Off: those layers take the direct x-strip kernel (csrc/unet_split.hip)
+                       128^3, the last decoders' convolutions -- through the 32-wide column-block kernel (csrc/unet_wino32.hip, round 6: one kernel, its
+                       waves specialised into multiplying and staging ones; the polyphase partial of a decoder's first convolution is added in its
+                       epilogue).  Off: those layers take the direct x-strip kernel (csrc/unet_split.hip)
     polyphase_upconv   polyphase form of the decoders' first convolutions (csrc/upconv.hip)
     fold_final_conv    the decoders absorb the UNet's final 1x1x1 convolution into their first layer (conv_implicit_wnf.UNetResult)
     fused_lattice      lattice queries sampled INSIDE the decoder-MLP kernel (gn_implicit_decode_lattice_split, no sampled-row buffer in

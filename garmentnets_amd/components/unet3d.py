@@ -158,108 +158,91 @@ class SingleConv(PackedModule, nn.Sequential):
         st1 = None
         if src1 is not None:
             st1 = stats1 if stats1 is not None else ops.channel_stats(src1)
-        if (sparse is not None and arith.affine_in_weights and arith.conv_mode == ops.SPLIT_F16X2 and src1 is None
-                and src0.shape[-1] % 16 == 0 and self.conv.out_channels % 32 == 0
-                and (sparse["reach"] == 1 or sparse.get("rest_in") is not None)):
-            return self._run_at_rest(src0, st0, with_stats, sparse, arith, gamma, beta)
-        if arith.conv_mode != ops.CONV_FP32:      # split-operand path on the 16-bit matrix cores (csrc/unet_split.hip)
-            mode = arith.conv_mode
-            # fp16 planes: the sample's activations are range-normalised by a power of two (exact, undone in the epilogue)
-            a, d, act_inv = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta, with_act_scale=True) \
-                if mode == ops.SPLIT_F16X2 else ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta) + (None,)
-            cache, gen = param_cache(self, "_split_packs"), (self.conv.weight.device, self.conv.weight._version)
-            wpack = cache.get(gen, mode, lambda: ops.pack_conv_weight_split(self.conv.weight, mode).to(self.conv.weight.device))
-            cout, sp = self.conv.out_channels, {}
-            wino = src1 is None and _wino_ok(arith, src0, cout)
-            wwino = cache.get(gen, "wino", lambda: ops.pack_conv_weight_split_wino(self.conv.weight).to(self.conv.weight.device)) if wino else None
-            if (sparse is not None and arith.sparse_first_conv and src1 is None and mode != ops.SPLIT_BF16X3 and src0.shape[-1] <= 384
-                    and (cout % 128 == 0 or cout % 64 != 0) and min(src0.shape[1:4]) > 2 * sparse["reach"]
-                    and (sparse["reach"] == 1 or sparse.get("small_in") is not None)
-                    # (the class constants must come from the kernel the real launch takes: a Winograd layer handed a small volume it cannot take
-                    #  -- 5^3, from a layer that ran in the direct form -- simply runs dense)
-                    and (not wino or sparse.get("small_in") is None or ops.wino_supported(src0.shape[-1], cout, sparse["small_in"].shape[1:4]))):
-                B, reach = src0.shape[0], int(sparse["reach"])
-                small_in = sparse.get("small_in")
-                if small_in is None:
-                    n = 8 if wino else 5          # the Winograd kernel takes whole 4 x 8 x 8 tiles
-                    small_in = torch.zeros((B, n, n, n, src0.shape[-1]), dtype=torch.float32, device=src0.device)
-                # (a plain dense launch of the kernel the real launch takes)
-                if wino:
-                    small_out = ops.conv3d_gcr_split_wino(small_in, a, d, wwino, cout, relu=True, act_inv=act_inv)
-                else:
-                    small_out = ops.conv3d_gcr_split(small_in, None, a, d, wpack, cout, relu=True, act_inv=act_inv)
-                sp = dict(tile_active=ops.grid_tile_flags(sparse["flat"], B, src0.shape[1:4], reach), kconst=_class_constants(small_out, reach, cout), kreach=reach)
-                sparse["small_out"] = small_out
-            if src1 is not None and arith.polyphase_upconv and mode != ops.SPLIT_BF16X3 and src1.shape[-1] <= 384:
-                # polyphase form: the nearest-upsampled channels as a 2x2x2-tap convolution per output parity class on the COARSE volume
-                # (8/27 of their MACs, the coarse halo staged once for all classes: csrc/upconv.hip), added in the fine launch's epilogue
-                c0 = src0.shape[-1]
+        if arith.conv_mode == ops.CONV_FP32:
+            a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta)
+            r = ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels, relu=True, with_stats=with_stats)
+        else:
+            r = self._run_split(src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0)
+        return r if with_stats else (r, None)
+
+    def _run_split(self, src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0):
+        """run() on the split-operand kernels (16-bit matrix cores: csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip) in one of two operand forms:
+        literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack)"""
+        gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, arith.conv_mode, src0.shape[-1]
+        aiw = arith.affine_in_weights and mode == ops.SPLIT_F16X2 and c0 % 16 == 0 and cout % 32 == 0
+        # polyphase form of a decoder's first convolution: the nearest-upsampled channels as a 2x2x2-tap convolution per output parity class on the
+        # COARSE volume (8/27 of their MACs, the coarse halo staged once for all classes: csrc/upconv.hip), added in the fine launch's epilogue
+        poly = src1 is not None and arith.polyphase_upconv and mode != ops.SPLIT_BF16X3 and src1.shape[-1] <= 384
+        # (of a polyphase layer the full-resolution part may run in Winograd form on the 32- / 64-wide layers: csrc/unet_wino32.hip takes the partial
+        #  in its epilogue)
+        wino = (src1 is None or (poly and cout % 128 != 0)) and _wino_ok(arith, src0, cout)
+        cache, gen = param_cache(self, "_split_packs"), (weight.device, weight._version)
+        part = prep = None
+        if src1 is None and aiw and sparse is not None and (sparse["reach"] == 1 or sparse.get("rest_in") is not None):
+            # affine-in-weights form of a layer whose input is at rest (0 for the scattered volume, sparse['rest_in'] behind it) almost everywhere
+            a, d = ops.groupnorm_affine(st0, None, gn.num_groups, gn.eps, gamma, beta)
+            rest = sparse.get("rest_in") if sparse["reach"] > 1 else None
+            prep = ops.conv_affine_pack(weight if weight.is_contiguous() else weight.contiguous(), a, d, st0, rest, wino=wino)
+            # away from the cells the operand is zero: the output is ReLU(0 * scale + K[interior]) = ReLU(K[63]) -- the next layer's rest value
+            sparse["rest_out"] = torch.relu(prep.kbias[:, 63]).contiguous()
+        else:
+            # literal form.  fp16 planes: the sample's activations are range-normalised by a power of two (exact, undone in the epilogue)
+            if mode == ops.SPLIT_F16X2:
+                a, d, act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True)
+            else:
+                (a, d), act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta), None
+            if poly:
                 def build_poly():
-                    w0, wm, _ = ops.polyphase_weights(self.conv.weight, c0)
-                    dev = self.conv.weight.device
-                    return (ops.pack_conv_weight_split(w0, mode).to(dev), ops.pack_upconv_weight(wm, cout, mode).to(dev))
+                    w0, wm, _ = ops.polyphase_weights(weight, c0)
+                    return (ops.pack_conv_weight_split(w0, mode).to(weight.device), ops.pack_upconv_weight(wm, cout, mode).to(weight.device))
                 pk0, pkm = cache.get(gen, ("poly", mode, c0), build_poly)
                 part = ops.upconv_partial(src1, a[:, c0:].contiguous(), d[:, c0:].contiguous(), pkm, cout, act_inv=act_inv)
-                # the full-resolution part in Winograd form (32- / 64-wide layers: csrc/unet_wino32.hip takes the partial in its epilogue)
-                wino0 = mode == ops.SPLIT_F16X2 and cout % 128 != 0 and _wino_ok(arith, src0, cout)
-                if rest0 is not None and arith.affine_in_weights and mode == ops.SPLIT_F16X2 and c0 % 16 == 0 and cout % 32 == 0:
+                if rest0 is not None and aiw:
+                    # the full-resolution part in the affine-in-weights form: the skip connection src0 is at rest away from the cells
                     # (a, d carry the sample's power-of-two activation scale: exact to undo)
                     a0 = (a[:, :c0] * act_inv[:, None]).contiguous()
                     d0 = (d[:, :c0] * act_inv[:, None]).contiguous()
-                    w0c = cache.get(gen, ("w0", c0), lambda: self.conv.weight.detach()[:, :c0].contiguous())
-                    prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=wino0)
-                    r = ops.conv3d_gcr_split_persample(src0, prep, relu=True, with_stats=with_stats, partial=part)
-                    return r if with_stats else (r, None)
-                if wino0:
-                    pkw = cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(self.conv.weight, c0)[0]).to(self.conv.weight.device))
-                    r = ops.conv3d_gcr_split_wino(src0, a[:, :c0].contiguous(), d[:, :c0].contiguous(), pkw, cout, relu=True, with_stats=with_stats,
-                                                  act_inv=act_inv, partial=part)
-                    return r if with_stats else (r, None)
-                r = ops.conv3d_gcr_split(src0, None, a[:, :c0].contiguous(), d[:, :c0].contiguous(), pk0, cout, relu=True, with_stats=with_stats,
-                                         act_inv=act_inv, partial=part)
-                return r if with_stats else (r, None)
-            if wino:
-                r = ops.conv3d_gcr_split_wino(src0, a, d, wwino, cout, relu=True, with_stats=with_stats, act_inv=act_inv, **sp)
-                return r if with_stats else (r, None)
-            r = ops.conv3d_gcr_split(src0, src1, a, d, wpack, cout, relu=True, with_stats=with_stats, act_inv=act_inv, **sp)
-            return r if with_stats else (r, None)
-        a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta)
-        if with_stats:
-            return ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels, relu=True, with_stats=True)
-        return ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels, relu=True), None
+                    w0c = cache.get(gen, ("w0", c0), lambda: weight.detach()[:, :c0].contiguous())
+                    prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=wino)
+                else:
+                    a, d = a[:, :c0].contiguous(), d[:, :c0].contiguous()
+                    pack = (cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(weight, c0)[0]).to(weight.device))
+                            if wino else pk0)
+            elif wino:
+                pack = cache.get(gen, "wino", lambda: ops.pack_conv_weight_split_wino(weight).to(weight.device))
+            else:
+                pack = cache.get(gen, mode, lambda: ops.pack_conv_weight_split(weight, mode).to(weight.device))
+        # the one launch tail of each form (a polyphase launch reads the full-resolution source alone: the upsampled channels arrive as the partial)
+        if prep is not None:
+            launch = lambda x, **kw: ops.conv3d_gcr_split_persample(x, prep, relu=True, **kw)
+        elif wino:
+            launch = lambda x, **kw: ops.conv3d_gcr_split_wino(x, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
+        else:
+            launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if poly else src1, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
+        sp = self._occupancy_aware(src0, src1, sparse, arith, wino, launch)
+        return launch(src0, with_stats=with_stats, partial=part, **sp)
 
-
-    def _run_at_rest(self, src0, st0, with_stats, sparse, arith, gamma, beta):
-        """the affine-in-weights form of run() for an input that is at rest (0 for the scattered volume, sparse['rest_in'] behind it) almost
-        everywhere"""
-        B, cout, reach = src0.shape[0], self.conv.out_channels, int(sparse["reach"])
-        a, d = ops.groupnorm_affine(st0, None, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta)
-        w = self.conv.weight
-        if not w.is_contiguous():
-            w = w.contiguous()
-        rest = sparse.get("rest_in") if reach > 1 else None
-        wino = _wino_ok(arith, src0, cout)
-        prep = ops.conv_affine_pack(w, a, d, st0, rest, wino=wino)
-        # away from the cells the operand is zero: the output is ReLU(0 * scale + K[interior]) = ReLU(K[63]) -- the next layer's rest value
-        sparse["rest_out"] = torch.relu(prep.kbias[:, 63]).contiguous()
-        sp = {}
-        small_in = sparse.get("small_in")
-        if (arith.sparse_first_conv and src0.shape[-1] <= 384 and (cout % 128 == 0 or cout % 64 != 0) and min(src0.shape[1:4]) > 2 * reach
-                and (reach == 1 or small_in is not None)
-                # (the class constants must come from the kernel -- and the pack -- the real launch takes: a Winograd layer handed a small volume it cannot
-                #  take, 5^3 from a layer that ran in the direct form, simply runs dense, as in run().  At reach 2 the small volume holds the previous
-                #  layer's face values, the operand is NOT zero there and the two forms round differently: constants from the direct pack would break
-                #  "occupancy-aware == dense, bit for bit" for such mixed configurations)
-                and (not wino or small_in is None or ops.wino_supported(src0.shape[-1], cout, small_in.shape[1:4]))):
-            if small_in is None:
-                n = 8 if wino else 5              # the Winograd kernels take whole tiles (4 x 8 x 8 / 8 x 8 x 8)
-                small_in = torch.zeros((B, n, n, n, src0.shape[-1]), dtype=torch.float32, device=src0.device)
-            # a plain dense launch of the same kernel with the same pack over the small all-at-rest volume
-            small_out = ops.conv3d_gcr_split_persample(small_in, prep, relu=True)
-            sp = dict(tile_active=ops.grid_tile_flags(sparse["flat"], B, src0.shape[1:4], reach), kconst=_class_constants(small_out, reach, cout), kreach=reach)
-            sparse["small_out"] = small_out
-        r = ops.conv3d_gcr_split_persample(src0, prep, relu=True, with_stats=with_stats, **sp)
-        return r if with_stats else (r, None)
+    def _occupancy_aware(self, src0, src1, sparse, arith, wino, launch):
+        """arith.sparse_first_conv: {} (a dense launch), or the keyword arguments of the occupancy-aware launch of a layer behind the scattered
+        volume (tile_active, kconst, kreach).  Its border-class constants come from `launch` -- the kernel AND the pack the real launch takes --
+        over a small all-at-rest volume; this layer's output there goes to sparse['small_out'] for the next layer."""
+        cin, cout = src0.shape[-1], self.conv.out_channels
+        if sparse is None or not arith.sparse_first_conv or src1 is not None or arith.conv_mode == ops.SPLIT_BF16X3:
+            return {}
+        B, reach, small_in = src0.shape[0], int(sparse["reach"]), sparse.get("small_in")
+        if not (cin <= 384 and (cout % 128 == 0 or cout % 64 != 0) and min(src0.shape[1:4]) > 2 * reach and (reach == 1 or small_in is not None)
+                # (a Winograd layer handed a small volume it cannot take -- 5^3, from a layer that ran in the direct form -- simply runs dense.  At reach 2
+                #  the small volume holds the previous layer's face values, the operand is NOT zero there and the two forms round differently: constants
+                #  from the direct pack would break "occupancy-aware == dense, bit for bit" for such mixed configurations)
+                and (not wino or small_in is None or ops.wino_supported(cin, cout, small_in.shape[1:4]))):
+            return {}
+        if small_in is None:
+            n = 8 if wino else 5                  # the Winograd kernels take whole tiles (4 x 8 x 8 / 8 x 8 x 8)
+            small_in = torch.zeros((B, n, n, n, cin), dtype=torch.float32, device=src0.device)
+        small_out = launch(small_in)              # (a plain dense launch)
+        sp = dict(tile_active=ops.grid_tile_flags(sparse["flat"], B, src0.shape[1:4], reach), kconst=_class_constants(small_out, reach, cout), kreach=reach)
+        sparse["small_out"] = small_out
+        return sp
 
 
 class DoubleConv(nn.Sequential):

@@ -81,12 +81,12 @@ template <int P, int HZ = SP_HZ> struct HaloLayout {
     __device__ static constexpr __forceinline__ int at(int hz, int hy, int hx) { return (hz * SP_HY + hy) * ROWP + hx * VB; }
 };
 
-// MT = z-slices per wave: 1 -> tile 4 x 8 x 8; 2 -> tile 8 x 8 x 8 (wave w takes slices w and w+4).  The tall tile is for the 32-wide
-// (NT = 1) layers: twice the MFMAs per barrier, per staged voxel (halo 1000 instead of 2 x 600) and per B fragment.
-template <int NT, int P, bool F16, int MT>
+// tile 4 x 8 x 8: wave w takes z-slice w, as two 32-row fragments (y halves).  (A tall 8 x 8 x 8 tile, two z-slices per wave, was measured on the
+// 32-wide layers: 327-347 TFLOP/s against 340 -- its synchronous staging phase is 29 % of the kernel -- and dropped.)
+template <int NT, int P, bool F16>
 __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     constexpr int CT = NT * 32;
-    constexpr int TZ = SP_TZ * MT, HZ = TZ + 2, HVOX = HZ * SP_HY * SP_HX, NF = 2 * MT;   // NF: 32-row fragments per wave
+    constexpr int TZ = SP_TZ, HZ = TZ + 2, HVOX = HZ * SP_HY * SP_HX, NF = 2;            // NF: 32-row fragments per wave
     // LDS (ONE array: a second __shared__ object makes hipcc drain the LDS-DMA queue before every ds_read):
     //   halo : HaloLayout<P> (600 voxels, P planes of 16 halfs each)
     //   ring : DEPTH x (NT*P) B fragments of 1 KB in lane order, filled by global_load_lds_dwordx4 DEPTH taps ahead
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     const int n0 = cb * CT;
     const int D1 = p.D >> 1, H1 = p.H >> 1, W1 = p.W >> 1;
 
-    f32x16s acc[NF][NT], tot[NF][NT];               // fragment f = 2 m + t: z-slice wave + 4 m, y half t
+    f32x16s acc[NF][NT], tot[NF][NT];               // fragment t: y half t
 #pragma unroll
     for (int t = 0; t < NF; ++t)
 #pragma unroll
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
 
     {
     const int abase = HL::at(wave, r >> 3, r & 7) + 16 * h;                          // bytes; plane pl at +32*pl
-    constexpr int AF1 = 4 * HL::ROWP, AFZ = 4 * SP_HY * HL::ROWP;                       // y half, second z-slice
+    constexpr int AF1 = 4 * HL::ROWP;                                                   // y half
     const int nslices = Cin / SP_KS;
     // B operands: the pack is in fragment order [slice][tap][Cout/32][plane][lane] (16 B per lane), so the NT*P fragments a
     // workgroup needs for one (slice, tap) step are NT*P contiguous KB.  They are DMA'd into the ring DEPTH steps ahead (no VGPRs;
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     // VALU work.  goff0 / goff1: index of the voxel within the sample in src0 / the half-resolution src1 (-1 = outside the volume or
     // past the last item; voxel indices, not element offsets: 256^3 x 128 channels does not fit 32 bits); loff: its byte offset in
     // the LDS halo.
-    constexpr bool PRE = (NT == 1 && MT == 1);
+    constexpr bool PRE = NT == 1;
     constexpr int NITP = (HVOX * 4 + 255) / 256;
     int goff0[PRE ? NITP : 1], goff1[PRE ? NITP : 1], loff[PRE ? NITP : 1];
     if (PRE) {
@@ -209,15 +209,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
             const int c4 = (tid & 3) * 4;                                  // 256 % 4 == 0: the same channel quad every iteration
             const float4 av = *reinterpret_cast<const float4 *>(ab + c4);
             const float4 dv = *reinterpret_cast<const float4 *>(db + c4);
-            // in batches of NB rows per thread (all of a batch's loads in flight before its first use; the tall tile takes two
-            // batches: 16 rows would not fit beside its 128 accumulator registers)
-            constexpr int NB = NIT <= 10 ? NIT : (NIT + 1) / 2;
-            for (int it0 = 0; it0 < NIT; it0 += NB) {
-            float4 raw[NB];
-            bool inb[NB];
+            float4 raw[NIT];
+            bool inb[NIT];
 #pragma unroll
-            for (int itb = 0; itb < NB; ++itb) {
-                const int it = itb, idx = tid + (it0 + itb) * 256;
+            for (int it = 0; it < NIT; ++it) {
+                const int idx = tid + it * 256;
                 const int hv = idx >> 2;
                 const int hx = hv % SP_HX, hy = (hv / SP_HX) % SP_HY, hz = hv / (SP_HX * SP_HY);
                 const int gz = z0 + hz - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
@@ -231,8 +227,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
                 }
             }
 #pragma unroll
-            for (int itb = 0; itb < NB; ++itb) {
-                const int it = itb, idx = tid + (it0 + itb) * 256;
+            for (int it = 0; it < NIT; ++it) {
+                const int idx = tid + it * 256;
                 if (idx < HVOX * 4) {
                     const int hv = idx >> 2;
                     float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
@@ -248,7 +244,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
                     for (int i = 0; i < P; ++i) *reinterpret_cast<uint2 *>(halo + HL::at(hv / (SP_HX * SP_HY), (hv / SP_HX) % SP_HY, hv % SP_HX) + i * 32 + c4 * 2) = pl[i];
                 }
             }
-            }
         }
         __syncthreads();                            // halo visible (and this wave's outstanding ring DMAs have landed)
         // step j = s*27 + tap lives in ring slot j % DEPTH
@@ -258,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-            for (int i = 0; i < P; ++i) naf[f][i] = *reinterpret_cast<const uint4 *>(halo + abase + (f >> 1) * AFZ + (f & 1) * AF1 + i * 32);
+            for (int i = 0; i < P; ++i) naf[f][i] = *reinterpret_cast<const uint4 *>(halo + abase + f * AF1 + i * 32);
 #pragma unroll
         for (int u = 0; u < NT; ++u)
 #pragma unroll
@@ -283,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
 #pragma unroll
                 for (int f = 0; f < NF; ++f)
 #pragma unroll
-                    for (int i = 0; i < P; ++i) naf[f][i] = *reinterpret_cast<const uint4 *>(halo + abase + (f >> 1) * AFZ + (f & 1) * AF1 + toff + i * 32);
+                    for (int i = 0; i < P; ++i) naf[f][i] = *reinterpret_cast<const uint4 *>(halo + abase + f * AF1 + toff + i * 32);
 #pragma unroll
                 for (int u = 0; u < NT; ++u)
 #pragma unroll
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     for (int f = 0; f < NF; ++f)
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
-            const int t = f & 1, gz = z0 + wave + 4 * (f >> 1);
+            const int t = f, gz = z0 + wave;
             const int n = n0 + u * 32 + r;
             const float osn = p.out_scale[(int64_t)b * p.osc_bstride + n];
             const float osc = p.act_inv ? __fmul_rn(osn, p.act_inv[b]) : osn;
@@ -1034,13 +1029,11 @@ static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, i
     const int tiles8 = (int)gn_cdiv(D, 8) * p.tiles_y * p.tiles_x;
     const bool strip = !wino && mode != GN_SPLIT_BF16X3 && !wide128 && C1 == 0 && (int64_t)tiles8 * (Cout / 32) * B >= 512;
     const bool wide = !wino && !wide128 && !strip && (Cout % 64 == 0) && ((int64_t)tiles * (Cout / 64) * B >= 1024);
-    // (MT = 2, the tall 8 x 8 x 8 tile, was measured on the 32-wide layers: 327-347 TFLOP/s vs 340 for MT = 1 -- its synchronous
-    //  staging phase is 29 % of the kernel -- so it is not dispatched)
 #define SP_LAUNCH(P_, F16_)                                                                                                    \
     do {                                                                                                                       \
-        if (wide) hipLaunchKernelGGL((conv3d_split_kernel<2, P_, F16_, 1>), dim3(tiles * (Cout / 64), B), dim3(256), 0, st, p); \
-        else hipLaunchKernelGGL((conv3d_split_kernel<1, P_, F16_, 1>), dim3(tiles * (Cout / 32), B), dim3(256), 0, st, p);     \
-        gn_note_kernel(wide ? "conv3d_split_kernel<2, " #P_ ", " #F16_ ", 1>" : "conv3d_split_kernel<1, " #P_ ", " #F16_ ", 1>"); \
+        if (wide) hipLaunchKernelGGL((conv3d_split_kernel<2, P_, F16_>), dim3(tiles * (Cout / 64), B), dim3(256), 0, st, p);    \
+        else hipLaunchKernelGGL((conv3d_split_kernel<1, P_, F16_>), dim3(tiles * (Cout / 32), B), dim3(256), 0, st, p);        \
+        gn_note_kernel(wide ? "conv3d_split_kernel<2, " #P_ ", " #F16_ ">" : "conv3d_split_kernel<1, " #P_ ", " #F16_ ">");     \
     } while (0)
     // The variant is chosen from the SHAPE alone -- an occupancy-aware launch (tile_active) takes the kernel the dense launch of the same
     // shape takes, so the two give bit-identical outputs AND the same per-tile fp32 partials of the epilogue statistics.  (Outputs are
@@ -1064,8 +1057,8 @@ static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, i
         p.active_count = count;
     }
     if (wino32) {
-        const bool pc = gn_launch_conv3d_wino32(p, tiles8, st);
-        gn_note_kernel(pc ? "conv3d_split_wino32pc_kernel<true>" : "conv3d_split_wino32_kernel<true>");
+        gn_launch_conv3d_wino32(p, tiles8, st);
+        gn_note_kernel("conv3d_split_wino32pc_kernel<true>");
     } else if (wino) {
         gn_launch_conv3d_wino(p, tiles, st);
         gn_note_kernel("conv3d_split_wino_kernel<true>");

@@ -385,18 +385,25 @@ def pack_conv_weight_split_wino(w):
 def conv3d_gcr_split_wino(src, a, d, pack, cout, relu=True, with_stats=False, act_inv=None, tile_active=None, kconst=None, kreach=1, partial=None):
     """the literal form through the Winograd kernels (pack = pack_conv_weight_split_wino); partial: the polyphase partial of a decoder's first
     convolution (upconv_partial), 32- / 64-wide layers only"""
+    return _conv3d_wino("conv3d_gcr_split_wino", src, a, d, pack.tensor, pack.out_scale, act_inv, None, cout, relu, with_stats, tile_active, kconst, kreach,
+                        partial)
+
+
+def _conv3d_wino(who, src, a, d, pack, out_scale, act_inv, kbias, cout, relu, with_stats, tile_active, kconst, kreach, partial):
+    """both operand forms through the Winograd kernels (kbias None: literal, else affine-in-weights): gn_conv3d_gcr_split_wino, or its _partial entry
+    when a polyphase partial is added (never occupancy-aware)"""
     B, D, H, W, C0 = src.shape
     out = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=src.device)
     s, q = _stats_buffers(B, cout, src.device, with_stats)
     if partial is not None:
         if tile_active is not None:
-            raise ValueError("conv3d_gcr_split_wino: the occupancy-aware launch cannot take a polyphase partial")
-        _lib.call("gn_conv3d_gcr_split_wino_partial", _p(src), C0, _p(a), _p(d), _p(pack.tensor), _p(pack.out_scale), _p(act_inv), None, B, D, H, W, cout,
+            raise ValueError(f"{who}: the occupancy-aware launch cannot take a polyphase partial")
+        _lib.call("gn_conv3d_gcr_split_wino_partial", _p(src), C0, _p(a), _p(d), _p(pack), _p(out_scale), _p(act_inv), _p(kbias), B, D, H, W, cout,
                   1 if relu else 0, _p(out), _p(s), _p(q), _p(_chk(partial, torch.float32, "partial")), _stream())
-        return (out, (s, q, D * H * W)) if with_stats else out
-    ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src.device)
-    _lib.call("gn_conv3d_gcr_split_wino", _p(src), C0, _p(a), _p(d), _p(pack.tensor), _p(pack.out_scale), _p(act_inv), None, B, D, H, W, cout,
-              1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(ows), ows_bytes, _stream())
+    else:
+        ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src.device)
+        _lib.call("gn_conv3d_gcr_split_wino", _p(src), C0, _p(a), _p(d), _p(pack), _p(out_scale), _p(act_inv), _p(kbias), B, D, H, W, cout,
+                  1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(ows), ows_bytes, _stream())
     return (out, (s, q, D * H * W)) if with_stats else out
 
 
@@ -522,19 +529,12 @@ def conv3d_gcr_split_persample(src, prep, relu=True, with_stats=False, tile_acti
     """the 'gcr' layer from an AffinePack (GN_SPLIT_F16X2 arithmetic; the operand is exactly zero wherever the input is at rest)"""
     B, D, H, W, C = src.shape
     assert C == prep.cin and B == prep.stage_a.shape[0]
+    if prep.wino:
+        return _conv3d_wino("conv3d_gcr_split_persample", src, prep.stage_a, prep.stage_d, prep.pack, prep.out_scale, None, prep.kbias, prep.cout, relu,
+                            with_stats, tile_active, kconst, kreach, partial)
     out = torch.empty((B, D, H, W, prep.cout), dtype=torch.float32, device=src.device)
     s, q = _stats_buffers(B, prep.cout, src.device, with_stats)
     ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src.device)
-    if prep.wino:
-        if partial is not None:
-            if tile_active is not None:
-                raise ValueError("conv3d_gcr_split_persample: the occupancy-aware launch cannot take a polyphase partial")
-            _lib.call("gn_conv3d_gcr_split_wino_partial", _p(src), C, _p(prep.stage_a), _p(prep.stage_d), _p(prep.pack), _p(prep.out_scale), None, _p(prep.kbias),
-                      B, D, H, W, prep.cout, 1 if relu else 0, _p(out), _p(s), _p(q), _p(_chk(partial, torch.float32, "partial")), _stream())
-            return (out, (s, q, D * H * W)) if with_stats else out
-        _lib.call("gn_conv3d_gcr_split_wino", _p(src), C, _p(prep.stage_a), _p(prep.stage_d), _p(prep.pack), _p(prep.out_scale), None, _p(prep.kbias),
-                  B, D, H, W, prep.cout, 1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(ows), ows_bytes, _stream())
-        return (out, (s, q, D * H * W)) if with_stats else out
     _lib.call("gn_conv3d_gcr_split_persample", _p(src), C, _p(prep.stage_a), _p(prep.stage_d), _p(prep.pack), _p(prep.out_scale), _p(prep.kbias),
               B, D, H, W, prep.cout, 1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(partial), _p(ows), ows_bytes,
               _stream())

@@ -265,8 +265,9 @@ int gn_conv3d_gcr_split_persample(const float *src, int Cin, const float *stage_
  *                  (same contract as gn_conv_affine_pack, 36 steps per slice: gn_conv_affine_pack_wino_bytes); act_inv_scale NULL.
  * Requirements (GN_EINVAL otherwise): one source, Cin % 16 == 0, D*H*W <= 2^27, D*H*W*Cin*4 < 2^32 and
  *   Cout % 128 == 0 (csrc/unet_wino.hip: 4 x 8 x 8 tiles x 128 channels): Cin <= 256, D % 4 == H % 8 == W % 8 == 0;
- *   any other Cout % 32 == 0 (csrc/unet_wino32.hip, round 6: 8 x 8 x 8 tiles x one 32-wide column block -- the encoder's second convolution 128 -> 32 at
- *   full resolution, components/unet3d.py:127-144, and the last decoder's convolutions, :291,330): Cin <= 128, D % 8 == H % 8 == W % 8 == 0.
+ *   any other Cout % 32 == 0 (csrc/unet_wino32.hip, round 6: one kernel, 8 x 8 x 8 tiles x one 32-wide column block, four waves multiplying and four
+ *   staging -- the encoder's second convolution 128 -> 32 at full resolution, components/unet3d.py:127-144, and the last decoder's convolutions,
+ *   :291,330): Cin <= 128, D % 8 == H % 8 == W % 8 == 0.
  * tile_active / kconst / kreach / occ_ws as gn_conv3d_gcr_split (tile granularity of the occupancy-aware list: the kernel's own).
  * gn_conv3d_gcr_split_wino_partial: the same layer with the polyphase partial of gn_upconv_partial added before the ReLU (Cout % 128 != 0 only; dense). */
 size_t gn_conv_affine_pack_wino_bytes(int B, int Cin, int Cout);
