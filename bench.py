@@ -2,6 +2,7 @@
 """bench.py -- GarmentNets inference throughput on MI355X (BASELINE.json metric: garments/s end to end).
 
     python bench.py --gpus N --steps K --warmup W                       # default = BASELINE config[2]: full pipeline, B=16/GPU, G=128, Q=128
+    python bench.py --gpus N --steps K --warmup W --full                # the same headline + every side pass, check and figure listed below
     python bench.py --workload full --volume-size 256 --batch 8         # config[4]: 256^3 WNF + marching cubes
     python bench.py --workload pointnet2 --batch 32                     # config[1]: PointNet++ NOCS forward only
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
@@ -10,7 +11,9 @@ One "step" = one pass of the hot path (predict.py:138-209: PointNet++ -> griddin
 gradient magnitude -> Lewiner marching cubes -> surface decode) over one batch of synthetic garments.  The GLOBAL batch
 (batch x world garments, one seed) is sharded contiguously over the ranks with parallel.shard_range: config[3] (128 garments over 8
 GPUs) is literally what runs under --gpus 8.  Garments never move between GPUs; the only collective is an all-gather of per-rank
-timings (RCCL).  Rank 0 prints ONE JSON line:
+timings (RCCL).  Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: it sets up, warms up, times the K
+steps, writes --dump-outputs and prints the line -- `value` / `ms_per_step`, and the `roofline` of the HIP events and hwmon clock taken
+during those steps (`traffic` null).  Every other entry below, `roofline.traffic` and the throttle residencies are measured under --full only:
 
   value / ms_per_step   K timed steps, inputs resident in HBM, results left on the device (barrier + synchronize on both sides, MAX
                         over ranks) -- the default arithmetic (f16x2 operand split for the 3x3x3 convs and the decoder MLPs)
@@ -118,6 +121,11 @@ def parse():
                     help="1 (default): one batch at a time (predict.predict_batch, the reference's loop); 2: every timed pass keeps two batches in "
                          "flight -- batch k+1's dense path is queued before batch k's host-synchronising tail is finished (predict.PredictJob).  "
                          "Either way a timed pass begins and finishes all its K batches")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the strict-fp32, host-I/O, occupancy-aware, literal-affine and two-in-flight "
+                         "passes, stages_ms / hbm_members / fp32_twin, validation, latency_b1, the rocprofv3 traffic passes, the throttle residencies and "
+                         "the CPU baseline with its oracle check.  Off (default): set up, warm up, time the K steps, write --dump-outputs, print the "
+                         "line.  The --no-* options below trim a --full run")
     ap.add_argument("--no-in-flight-pass", action="store_true", help="skip the extra timed pass with two batches in flight (reported as two_in_flight)")
     ap.add_argument("--no-strict-pass", action="store_true", help="skip the second timed pass in strict fp32 arithmetic")
     ap.add_argument("--no-host-io-pass", action="store_true", help="skip the timed pass that includes H2D of the clouds / D2H of the meshes")
@@ -1059,7 +1067,7 @@ def main():
     hw_passes = {}
 
     def timed(fn, steps, warmup, hw_name=None):
-        thr0 = throttle_read(dev_index) if (hw_name and rank == 0) else None     # (before the warm-up: the GPU goes into the timed steps warm)
+        thr0 = throttle_read(dev_index) if (hw_name and rank == 0 and args.full) else None     # (before the warm-up: the GPU goes into the timed steps warm)
         run_steps(fn, warmup)
         torch.cuda.synchronize()
         parallel.barrier()
@@ -1090,7 +1098,8 @@ def main():
             sampler.__exit__(None, None, None)
             hw_passes[hw_name] = sampler.summary()
             # why the clock is what it is: share of the pass (warm-up + timed steps: the same workload) the firmware spent limiting it, per limiter
-            hw_passes[hw_name]["throttle"] = throttle_window(thr0, throttle_read(dev_index))
+            hw_passes[hw_name]["throttle"] = (throttle_window(thr0, throttle_read(dev_index)) if args.full else
+                                              {"available": False, "why_not": "read under --full only"})
         timer.enabled = False
         return dt, res, timer.summary()
 
@@ -1119,7 +1128,7 @@ def main():
         checksums = torch.stack([r["wnf_volume"].double().sum() for r in res]).cpu().tolist()
         verts_total = sum(int(r["verts"].shape[0]) for r in res)
         assert not any(bool(torch.isnan(r["verts"]).any()) for r in res), "marching cubes produced a placeholder mesh"
-        if rank == 0:
+        if rank == 0 and args.full:
             r0 = res[0]
             w0 = r0["wnf_volume"]
             level0 = 0.5 * (float(w0.min()) + float(w0.max())) if auto_level[0] else 0.5
@@ -1127,27 +1136,27 @@ def main():
             probe = dict(wnf0=w0.cpu(), level0=level0, bins0=bins0, verts0=int(r0["verts"].shape[0]), faces0=int(r0["faces"].shape[0]))
     else:
         checksums = res["per_point_logits"].double().view(hi - lo, -1).sum(dim=1).cpu().tolist()
-    if args.workload != "full" and rank == 0:
+    if args.workload != "full" and rank == 0 and args.full:
         n = args.points
         bins0, _, _ = ops.nocs_head(res["per_point_logits"][:n].contiguous(), model.pointnet2_nocs.nocs_bins)
         probe = dict(bins0=bins0.cpu(), feat0=res["per_point_features"][:n].cpu())
     del res
 
     strict = None
-    if not args.no_strict_pass and (args.conv_mode, args.decode_mode) != ("fp32", "fp32") and args.workload == "full":
+    if args.full and not args.no_strict_pass and (args.conv_mode, args.decode_mode) != ("fp32", "fp32") and args.workload == "full":
         model.arith = headline.strict_fp32()
         dt_s, res_s, groups_s = timed(step, args.steps, 1, hw_name="strict_fp32")
         del res_s
         strict = (dt_s, groups_s)
         model.arith = headline
     hostio = None
-    if not args.no_host_io_pass:
+    if args.full and not args.no_host_io_pass:
         dt_h, res_h, _ = timed(step_host_io, args.steps, 1)
         del res_h
         hostio = dt_h
 
     occupancy = None
-    if not args.no_occupancy_pass and args.workload == "full" and args.conv_mode in ("f16x2", "bf16x2"):
+    if args.full and not args.no_occupancy_pass and args.workload == "full" and args.conv_mode in ("f16x2", "bf16x2"):
         model.arith = headline.replace(sparse_first_conv=True)
         dt_a, _, _ = timed(step, args.steps, 1)
         model.arith = headline
@@ -1166,7 +1175,7 @@ def main():
             del vin
     groups_l = None
     literal = None          # the same steps with the GroupNorm shift inside the MFMA operand (Arith.affine_in_weights off): the A/B of DESIGN.md 4.3 on THIS box
-    if not args.no_occupancy_pass and args.workload == "full" and args.conv_mode == "f16x2" and headline.affine_in_weights:
+    if args.full and not args.no_occupancy_pass and args.workload == "full" and args.conv_mode == "f16x2" and headline.affine_in_weights:
         model.arith = headline.replace(affine_in_weights=False)
         literal, _, groups_l = timed(step, args.steps, 1, hw_name="literal_affine")
         model.arith = headline
@@ -1174,7 +1183,7 @@ def main():
     # per-stage HIP-event times of ONE extra, untimed step; the stages are the reference's own stage methods.  The same
     # step carries the HIP-event brackets of the HBM-bound members (hbm_members)
     stages_ms = hbm_members = None
-    if rank == 0 and args.workload == "full":
+    if rank == 0 and args.full and args.workload == "full":
         from garmentnets_amd.common import marching_cubes_util as mcu
         hbm = HbmMembers()
         hbm.install()
@@ -1213,15 +1222,15 @@ def main():
         del p2, u3, wnf_all, job, meshes
 
     fp32_twin = None
-    if rank == 0 and args.workload == "full" and args.decode_mode == "f16x2":
+    if rank == 0 and args.full and args.workload == "full" and args.decode_mode == "f16x2":
         fp32_twin = fp32_twin_accounting(step)
 
     validation = None
-    if rank == 0 and not args.no_validate:
+    if rank == 0 and args.full and not args.no_validate:
         validation = validate(model, args, dev, auto_level[0])
 
     in_flight = in_flight_io = None
-    if args.workload == "full" and not pipelined[0] and not auto_level[0] and not args.no_in_flight_pass:
+    if args.full and args.workload == "full" and not pipelined[0] and not auto_level[0] and not args.no_in_flight_pass:
         # the same K batches with two in flight (predict.PredictJob).  Last of the GPU passes, behind its own warm-up: a second batch's
         # buffers (tens of GB; hipMalloc of such blocks takes tens of ms each) have to exist in the caching allocator first, and they
         # are released again afterwards
@@ -1240,7 +1249,7 @@ def main():
         torch.cuda.empty_cache()
 
     lat_b1 = None
-    if rank == 0 and world == 1 and args.workload == "full" and not args.no_latency_b1:
+    if rank == 0 and args.full and world == 1 and args.workload == "full" and not args.no_latency_b1:
         lat_b1 = latency_b1(args, dev)
 
     # the only collective: per-rank (garments, seconds of each timed pass) over RCCL/xGMI
@@ -1273,8 +1282,9 @@ def main():
             workload = (f"full conv_implicit_wnf pipeline, batch={args.batch}/GPU, {args.points}-pt clouds, {args.grid}^3 feature volume ({args.reduce}), "
                         f"{args.volume_size}^3 WNF + GGM + MC33 + surface decode; input: {input_note}"
                         + (f" ({occupancy['occupied_cells_per_garment']:.0f} occupied cells per garment)" if occupancy else ""))
-            if args.no_pmc or world > 1:          # (the counter passes are a single-GPU measurement: at N > 1 the line carries null)
-                traffic = (None, "--no-pmc" if args.no_pmc else "not collected at N > 1 (single-GPU measurement: run bench.py --gpus 1)")
+            if not args.full or args.no_pmc or world > 1:          # (the counter passes are a single-GPU measurement: at N > 1 the line carries null)
+                traffic = (None, "measured under --full only" if not args.full else "--no-pmc" if args.no_pmc else
+                           "not collected at N > 1 (single-GPU measurement: run bench.py --gpus 1 --full)")
             else:
                 traffic = measure_traffic(args)
             roofline = pick_roofline(args, groups, args.conv_mode, args.decode_mode, hw_passes.get("headline"), traffic)
@@ -1363,7 +1373,7 @@ def main():
                 "roofline": pick_roofline(args, groups_l, args.conv_mode, args.decode_mode, hw_passes.get("literal_affine"))}
         if validation is not None:
             line["validation"] = validation
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if full_mask is not None:
                 os.sched_setaffinity(0, full_mask)          # the CPU baseline may use every core of the host
             line["cpu_baseline"], check = cpu_baseline(args, hp, sd, shard, probe)

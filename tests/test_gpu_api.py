@@ -684,3 +684,35 @@ def test_two_process_bench_over_rccl():
     """the same launch with the production backend: init_process_group("nccl", device_id=cuda:LOCAL_RANK), rank 1's whole data path on
     device ordinal 1 (gn_stream's device binding), the metrics all-gather over RCCL; checksums against in-process runs on the same devices"""
     _two_rank_bench("nccl")
+
+
+def _one_rank_bench(*extra):
+    """bench.py --gpus 1 on a small configuration in a fresh process -> (compact line, detail dict)"""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--points", "2000",
+           "--grid", "32", "--volume-size", "32", *extra]
+    out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    det = [l for l in out.stderr.splitlines() if l.startswith("[bench detail] ")]
+    assert len(lines) == 1 and len(det) == 1, out.stdout[-2000:]
+    return json.loads(lines[0]), json.loads(det[0][len("[bench detail] "):])
+
+
+SIDE_ENTRIES = ("strict_fp32", "with_host_io", "occupancy_aware", "literal_affine", "hbm_members", "fp32_twin", "validation", "latency_b1",
+                "cpu_baseline", "oracle_check")
+
+
+def test_plain_bench_run_times_the_headline_only_and_full_keeps_the_side_passes():
+    """a plain run sets up, warms up, times the K steps and prints the line: no side pass, check or counter run; --full adds them back"""
+    import bench
+    compact, line = _one_rank_bench()
+    assert tuple(compact) == bench.COMPACT_KEYS and compact["value"] > 0 and compact["ms_per_step"] > 0 and compact["roofline"]["kernel"]
+    assert line["value"] == pytest.approx(2 * 2 / (line["ms_per_step"] * 1e-3 * 2), rel=1e-6)
+    assert not any(k in line for k in SIDE_ENTRIES + ("two_in_flight", "two_in_flight_with_host_io")), sorted(line)
+    assert line["stages_ms"] is None and line["roofline"].get("traffic") is None
+    assert compact["with_host_io"] is None and compact["cpu_baseline"] is None and compact["validation_ok"] is None
+    compact_f, line_f = _one_rank_bench("--full", "--no-pmc")
+    assert all(line_f.get(k) for k in SIDE_ENTRIES), [k for k in SIDE_ENTRIES if not line_f.get(k)]
+    assert line_f["stages_ms"] and line_f["validation"]["ok"] and line_f["oracle_check"]["ok"] and compact_f["with_host_io"]["value"] > 0
+    assert line_f["garment_checksums"] == pytest.approx(line["garment_checksums"], rel=1e-6)        # the same headline computation

@@ -5,7 +5,7 @@ TAG=${1:-ov}; shift || true
 REPO=$(cd "$(dirname "$0")/../.." && pwd)
 RAW=/tmp/ov_$TAG; OUT=$REPO/gpurun_out/ov_$TAG; mkdir -p $RAW $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $RAW -o ov -- python $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-strict-pass --no-host-io-pass --no-validate --no-occupancy-pass --no-latency-b1 --no-pmc $* > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $RAW -o ov -- python $REPO/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-strict-pass --no-host-io-pass --no-validate --no-occupancy-pass --no-latency-b1 --no-pmc $* > $OUT/run.log 2>&1
 F=$(find $RAW -name "*kernel_trace.csv" | head -1)
 python - "$F" > $OUT/overlap.txt <<'PY'
 import csv, sys

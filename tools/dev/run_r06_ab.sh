@@ -6,7 +6,7 @@
 #   dec       same-box bench A/B of two libraries: the tree's and tools/dev/_build/lib_old.so
 #   batchdec  same-box bench A/B of the batched surface queries against the garment loop (GARMENTNETS_DECODE_BATCH_BYTES=0)
 CASE=${1:-tail}; O=gpurun_out/r06_$CASE; mkdir -p $O
-SHORT="--no-cpu-baseline --no-in-flight-pass --no-pmc --no-occupancy-pass --no-strict-pass --no-host-io-pass --no-validate --steps 10 --warmup 3"
+SHORT="--full --no-cpu-baseline --no-in-flight-pass --no-pmc --no-occupancy-pass --no-strict-pass --no-host-io-pass --no-validate --steps 10 --warmup 3"
 line() { python - "$1" <<'PY'
 import json,sys; d=json.load(open("gpurun_out/bench_detail.json")); b1=d.get("latency_b1") or {}
 print(sys.argv[1], round(d["value"],2), round(d["ms_per_step"],2), {k[:12]:round(v,2) for k,v in d["stages_ms"].items()}, "b1", b1.get("ms_median"))

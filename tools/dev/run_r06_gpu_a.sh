@@ -3,7 +3,7 @@
 O=gpurun_out/r06_a; mkdir -p $O
 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "winograd or unet or conv" 2>&1 | tail -5
 python -m pytest tests/test_gpu_fullsize.py -x -q -m gpu -k "bench_batch or dense_unet or realistic" 2>&1 | tail -5
-F="--no-strict-pass --no-latency-b1 --no-cpu-baseline --no-in-flight-pass --no-pmc --steps 10 --warmup 3"
+F="--full --no-strict-pass --no-latency-b1 --no-cpu-baseline --no-in-flight-pass --no-pmc --steps 10 --warmup 3"
 python bench.py $F --winograd32 off > $O/w32off.json 2> $O/w32off.err; python - <<PY
 import json; d=json.load(open("gpurun_out/bench_detail.json")); print("off", d["value"], d["literal_affine"]["value"], {k:(round(v["ms"]/10,2), round(v["tflops"])) for k,v in d["roofline"]["all_conv_instances"].items()})
 PY
