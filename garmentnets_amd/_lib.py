@@ -38,6 +38,8 @@ PROTOTYPES = {
     "gn_grid_scatter": [_vp, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _i32, _vp],
     "gn_channel_stats": [_vp, _i32, _i64, _i32, _vp, _vp, _vp],
     "gn_groupnorm_affine": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_channel_stats_any": [_vp, _i32, _i64, _i32, _vp, _vp, _vp],
+    "gn_groupnorm_affine_map": [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_conv3d_gcr": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "gn_conv3d_gcr_split": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp],
     "gn_conv3d_occupancy_workspace_bytes": [_i32, _i32, _i32, _i32],

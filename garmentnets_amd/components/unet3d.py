@@ -22,6 +22,37 @@ def number_of_features_per_level(init_channel_number, num_levels):
     return [init_channel_number * 2 ** k for k in range(num_levels)]
 
 
+# Channel padding.  The conv kernels take Cout % 32 == 0 (and Cin % 16 == 0 per source), so a layer of c output channels is STORED with
+# round_up(c, 32): its weights get zero rows / columns for the pad channels, its normalisation a zero affine (a = d = 0) and its conv bias a
+# zero there, so the pads hold exact zeros through every layer (ReLU / LeakyReLU / ELU of 0 is 0, and so is every border-class constant of
+# the occupancy-aware launch).  A layer whose channels need no padding runs exactly the unpadded code.
+CHANNEL_GRANULE = 32
+
+
+def stored_channels(c):
+    """the stored width of a UNet activation with c real channels"""
+    return -(-int(c) // CHANNEL_GRANULE) * CHANNEL_GRANULE
+
+
+class _Layout(tuple):
+    """(real, stored, cout): the real and stored channel count of each source of one SingleConv call and its stored output width"""
+    real = property(lambda self: self[0])
+    stored = property(lambda self: self[1])
+    cout = property(lambda self: self[2])
+
+
+def to_stored(v, real, stored):
+    """[..., sum(real)] -> [..., sum(stored)]: each source's real channels at the head of its stored block, zeros on the pads"""
+    if tuple(real) == tuple(stored):
+        return v
+    out = v.new_zeros(tuple(v.shape[:-1]) + (sum(stored),))
+    o = k = 0
+    for r, st in zip(real, stored):
+        out[..., o:o + r] = v[..., k:k + r]
+        o, k = o + st, k + r
+    return out
+
+
 def _wino_ok(arith, src0, cout):
     """the layer fits a Winograd F(2,3)-along-x kernel (arith.winograd: csrc/unet_wino.hip for Cout % 128 == 0; arith.winograd32: csrc/unet_wino32.hip for the
     32- / 64-wide layers).  Decided from the SAMPLE's shape alone, never
@@ -75,6 +106,8 @@ class SingleConv(PackedModule, nn.Sequential):
         if any(ch in "rle" for ch in order[:order.index("c")]) or sum(ch in "gb" for ch in order[:order.index("c")]) > 1:
             raise NotImplementedError(f"layer order {order!r}: at most one normalisation and no non-linearity in front of the convolution")
         self.order = order
+        # real channel count of each source when the inputs are stored channel-padded (set by DoubleConv / Decoder); None: as stored
+        self.in_real = None
         for i, ch in enumerate(order):
             before = i < order.index("c")
             nch = in_channels if before else out_channels
@@ -90,26 +123,58 @@ class SingleConv(PackedModule, nn.Sequential):
                 self.add_module("batchnorm", nn.BatchNorm3d(nch))
 
     def _pack(self):
-        wp = ops.pack_conv_weight(self.conv.weight)                # [tap][Cin/16][Cout][16]
+        # [tap][Cin/16][Cout][16] (a layer of other widths runs channel-padded: _padded_weight)
+        wp = ops.pack_conv_weight(self.conv.weight) if self.conv.in_channels % 16 == 0 else None
         gn = getattr(self, "groupnorm", None)
         return wp, (None if gn is None else gn.weight.detach().float().contiguous()), (None if gn is None else gn.bias.detach().float().contiguous())
 
-    def _norm_affine(self, ch, B, st0, st1):
-        """per-(sample, channel) affine of one normalisation layer from the statistics of what it normalises"""
+    def _layout(self, src0, src1):
+        """the channel layout of a call (_Layout), or None when nothing is padded: the unpadded code runs"""
+        stored = (src0.shape[-1],) if src1 is None else (src0.shape[-1], src1.shape[-1])
+        real = stored if self.in_real is None else tuple(self.in_real)
+        cout = self.conv.out_channels
+        if self.in_real is not None and (len(real) != len(stored) or any(r > st for r, st in zip(real, stored))):
+            raise ValueError(f"SingleConv: inputs of {stored} stored channels for {real} real ones")
+        if real == stored and cout % CHANNEL_GRANULE == 0:
+            return None
+        return _Layout((real, stored, stored_channels(cout)))
+
+    def _padded_weight(self, lay):
+        """the Conv3d weight in the stored layout (lay.cout, sum(lay.stored), 3, 3, 3): zero rows and columns for the pad channels"""
+        def build():
+            w = self.conv.weight.detach()
+            wp = w.new_zeros((lay.cout, sum(lay.stored)) + tuple(w.shape[2:]))
+            wp[:w.shape[0]] = to_stored(w.transpose(1, -1), lay.real, lay.stored).transpose(1, -1)
+            return wp.contiguous()
+        return param_cache(self, "_split_packs").get(self._gen(lay), "padded_weight", build)
+
+    def _gen(self, lay):
+        """the ParamCache generation of this layer's packs: parameter state and (when padded) channel layout"""
+        w = self.conv.weight
+        return (w.device, w._version) if lay is None else (w.device, w._version, lay)
+
+    def _norm_affine(self, ch, B, st0, st1, real=None, stored=None):
+        """per-(sample, channel) affine of one normalisation layer from the statistics of what it normalises (real / stored: the channel
+        layout of channel-padded sources, None: unpadded)"""
         if ch == "g":
             return ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, self.groupnorm.weight.detach().float().contiguous(),
-                                        self.groupnorm.bias.detach().float().contiguous())
+                                        self.groupnorm.bias.detach().float().contiguous(), real=real)
         bn = self.batchnorm                       # eval BatchNorm3d: running statistics
         sc = (bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps))
         sh = bn.bias.detach().double() - bn.running_mean.double() * sc
+        if real is not None:                      # (zero scale and shift on the pads)
+            sc, sh = to_stored(sc, real, stored), to_stored(sh, real, stored)
         return sc.float().expand(B, -1).contiguous(), sh.float().expand(B, -1).contiguous()
 
-    def _run_generic(self, src0, src1, stats0, stats1, with_stats):
+    def _run_generic(self, src0, src1, stats0, stats1, with_stats, lay=None):
         """every layer order but 'gcr' (see the class docstring)"""
         order, ic = self.order, self.order.index("c")
-        B, cout = src0.shape[0], self.conv.out_channels
+        B, cout = src0.shape[0], self.conv.out_channels if lay is None else lay.cout
         cin = src0.shape[-1] + (0 if src1 is None else src1.shape[-1])
-        wp, _, _ = self.packed()
+        if lay is None:
+            wp, _, _ = self.packed()
+        else:
+            wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
         if ic == 0:
             a = torch.ones((B, cin), dtype=torch.float32, device=src0.device)
             d = torch.zeros_like(a)
@@ -118,9 +183,12 @@ class SingleConv(PackedModule, nn.Sequential):
             if order[0] == "g":
                 st0 = stats0 if stats0 is not None else ops.channel_stats(src0)
                 st1 = None if src1 is None else (stats1 if stats1 is not None else ops.channel_stats(src1))
-            a, d = self._norm_affine(order[0], B, st0, st1)
+            a, d = self._norm_affine(order[0], B, st0, st1, *((None, None) if lay is None else (lay.real, lay.stored)))
         post = order[ic + 1:]
         bias = None if self.conv.bias is None else self.conv.bias.detach().float().contiguous()
+        if bias is not None and lay is not None:
+            bias = to_stored(bias, (self.conv.out_channels,), (cout,)).contiguous()
+        out_lay = (None, None) if lay is None else ((self.conv.out_channels,), (cout,))
         fuse_relu = bias is None and post[:1] == "r"
         y = ops.conv3d_gcr(src0, src1, a, d, wp, cout, relu=fuse_relu)
         k = 1 if fuse_relu else 0
@@ -132,7 +200,7 @@ class SingleConv(PackedModule, nn.Sequential):
             if ch in _ACT:
                 ops.affine_act(y, act=_ACT[ch][2], out=y)
             else:
-                na, nd = self._norm_affine(ch, B, ops.channel_stats(y) if ch == "g" else None, None)
+                na, nd = self._norm_affine(ch, B, ops.channel_stats(y) if ch == "g" else None, None, *out_lay)
                 ops.affine_act(y, a=na, d=nd, out=y)
         return y, (ops.channel_stats(y) if with_stats else None)
 
@@ -151,24 +219,31 @@ class SingleConv(PackedModule, nn.Sequential):
         rest0 [B][C0]: (polyphase form of a decoder layer) the value the skip connection src0 holds away from the cells: its full-resolution
         launch takes the affine-in-weights form as well."""
         arith = arith or AR.DEFAULT
+        lay = self._layout(src0, src1)
         if self.order != "gcr":
-            return self._run_generic(src0, src1, stats0, stats1, with_stats)
+            return self._run_generic(src0, src1, stats0, stats1, with_stats, lay)
         wp, gamma, beta = self.packed()
         st0 = stats0 if stats0 is not None else ops.channel_stats(src0)
         st1 = None
         if src1 is not None:
             st1 = stats1 if stats1 is not None else ops.channel_stats(src1)
         if arith.conv_mode == ops.CONV_FP32:
-            a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta)
-            r = ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels, relu=True, with_stats=with_stats)
+            a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta, real=None if lay is None else lay.real)
+            if lay is not None:
+                wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
+            r = ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels if lay is None else lay.cout, relu=True, with_stats=with_stats)
         else:
-            r = self._run_split(src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0)
+            r = self._run_split(src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0, lay)
         return r if with_stats else (r, None)
 
-    def _run_split(self, src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0):
+    def _run_split(self, src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0, lay=None):
         """run() on the split-operand kernels (16-bit matrix cores: csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip) in one of two operand forms:
-        literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack)"""
+        literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack).
+        lay: channel-padded storage (_Layout) -- the padded weight and stored widths in every pack, the GroupNorm over the real channels"""
         gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, arith.conv_mode, src0.shape[-1]
+        real = None
+        if lay is not None:
+            weight, cout, real = self._padded_weight(lay), lay.cout, lay.real
         aiw = arith.affine_in_weights and mode == ops.SPLIT_F16X2 and c0 % 16 == 0 and cout % 32 == 0
         # polyphase form of a decoder's first convolution: the nearest-upsampled channels as a 2x2x2-tap convolution per output parity class on the
         # COARSE volume (8/27 of their MACs, the coarse halo staged once for all classes: csrc/upconv.hip), added in the fine launch's epilogue
@@ -176,11 +251,11 @@ class SingleConv(PackedModule, nn.Sequential):
         # (of a polyphase layer the full-resolution part may run in Winograd form on the 32- / 64-wide layers: csrc/unet_wino32.hip takes the partial
         #  in its epilogue)
         wino = (src1 is None or (poly and cout % 128 != 0)) and _wino_ok(arith, src0, cout)
-        cache, gen = param_cache(self, "_split_packs"), (weight.device, weight._version)
+        cache, gen = param_cache(self, "_split_packs"), self._gen(lay)
         part = prep = None
         if src1 is None and aiw and sparse is not None and (sparse["reach"] == 1 or sparse.get("rest_in") is not None):
             # affine-in-weights form of a layer whose input is at rest (0 for the scattered volume, sparse['rest_in'] behind it) almost everywhere
-            a, d = ops.groupnorm_affine(st0, None, gn.num_groups, gn.eps, gamma, beta)
+            a, d = ops.groupnorm_affine(st0, None, gn.num_groups, gn.eps, gamma, beta, real=real)
             rest = sparse.get("rest_in") if sparse["reach"] > 1 else None
             prep = ops.conv_affine_pack(weight if weight.is_contiguous() else weight.contiguous(), a, d, st0, rest, wino=wino)
             # away from the cells the operand is zero: the output is ReLU(0 * scale + K[interior]) = ReLU(K[63]) -- the next layer's rest value
@@ -188,9 +263,9 @@ class SingleConv(PackedModule, nn.Sequential):
         else:
             # literal form.  fp16 planes: the sample's activations are range-normalised by a power of two (exact, undone in the epilogue)
             if mode == ops.SPLIT_F16X2:
-                a, d, act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True)
+                a, d, act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True, real=real)
             else:
-                (a, d), act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta), None
+                (a, d), act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real), None
             if poly:
                 def build_poly():
                     w0, wm, _ = ops.polyphase_weights(weight, c0)
@@ -219,14 +294,14 @@ class SingleConv(PackedModule, nn.Sequential):
             launch = lambda x, **kw: ops.conv3d_gcr_split_wino(x, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
         else:
             launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if poly else src1, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
-        sp = self._occupancy_aware(src0, src1, sparse, arith, wino, launch)
+        sp = self._occupancy_aware(src0, src1, sparse, arith, wino, launch, cout)
         return launch(src0, with_stats=with_stats, partial=part, **sp)
 
-    def _occupancy_aware(self, src0, src1, sparse, arith, wino, launch):
+    def _occupancy_aware(self, src0, src1, sparse, arith, wino, launch, cout):
         """arith.sparse_first_conv: {} (a dense launch), or the keyword arguments of the occupancy-aware launch of a layer behind the scattered
         volume (tile_active, kconst, kreach).  Its border-class constants come from `launch` -- the kernel AND the pack the real launch takes --
         over a small all-at-rest volume; this layer's output there goes to sparse['small_out'] for the next layer."""
-        cin, cout = src0.shape[-1], self.conv.out_channels
+        cin = src0.shape[-1]
         if sparse is None or not arith.sparse_first_conv or src1 is not None or arith.conv_mode == ops.SPLIT_BF16X3:
             return {}
         B, reach, small_in = src0.shape[0], int(sparse["reach"]), sparse.get("small_in")
@@ -256,6 +331,9 @@ class DoubleConv(nn.Sequential):
             c2_in, c2_out = out_channels, out_channels
         self.add_module("SingleConv1", SingleConv(c1_in, c1_out, kernel_size, order, num_groups))
         self.add_module("SingleConv2", SingleConv(c2_in, c2_out, kernel_size, order, num_groups))
+        if encoder:              # (a decoder's first layer reads two sources: Decoder states their split)
+            self.SingleConv1.in_real = (c1_in,)
+        self.SingleConv2.in_real = (c2_in,)
 
     def run(self, src0, src1=None, stats0=None, stats1=None, sparse_flat=None, arith=None, info=None, rest0=None):
         """sparse_flat: src0 is gn_grid_scatter's volume (flat cell index of every scattered point): both convolutions run occupancy-aware /
@@ -293,6 +371,8 @@ class Decoder(nn.Module):
     def __init__(self, in_channels, out_channels, conv_layer_order="gcr", num_groups=8):
         super().__init__()
         self.basic_module = DoubleConv(in_channels, out_channels, encoder=False, order=conv_layer_order, num_groups=num_groups)
+        # cat((encoder_features [out_channels], x [in_channels - out_channels])): the split of Abstract3DUNet's decoders
+        self.basic_module.SingleConv1.in_real = (out_channels, in_channels - out_channels)
 
     def run(self, encoder_features, x, stats_skip=None, stats_x=None, arith=None, skip_rest=None):
         # cat((encoder_features, upsample_nearest(x)), dim=channel) is never materialised
@@ -300,12 +380,21 @@ class Decoder(nn.Module):
 
 
 class FinalConv1x1(PackedModule, nn.Conv3d):
+    in_stored = None         # the stored width of its channel-padded input (Abstract3DUNet); None: in_channels
+
+    def stored_weight(self):
+        """the weight as (out_channels, stored input channels): zero columns for the pad channels of the input"""
+        w = self.weight.detach().reshape(self.out_channels, self.in_channels)
+        return to_stored(w, (self.in_channels,), (self.in_stored or self.in_channels,))
+
     def _pack(self):
-        return pack_wb(self.weight.detach().reshape(self.out_channels, self.in_channels), self.bias)
+        return pack_wb(self.stored_weight(), self.bias)
 
     def run(self, x):
         wp, b, k = self.packed()
         shp = x.shape
+        if shp[-1] != k:
+            raise ValueError(f"FinalConv1x1: input of {shp[-1]} channels, expected {k}")
         y = ops.linear(x.reshape(-1, shp[-1]), wp, b, None, None, relu=False, K=k)
         return y.reshape(*shp[:-1], self.out_channels)
 
@@ -326,13 +415,28 @@ class Abstract3DUNet(nn.Module):
         self.decoders = nn.ModuleList([
             Decoder(rf[i] + rf[i + 1], rf[i + 1], conv_layer_order=layer_order, num_groups=num_groups) for i in range(len(rf) - 1)])
         self.final_conv = FinalConv1x1(f_maps[0], out_channels, 1)
+        self.final_conv.in_stored = stored_channels(f_maps[0])
         self.final_activation = None
+        self.in_channels = in_channels
         self.arith = None        # arithmetic of forward(x) (None: arith.DEFAULT); run() takes it per call
+
+    def check_input(self, x):
+        """refuse, by name, the shapes this UNet does not run: NotImplementedError"""
+        if self.in_channels % 16 != 0:
+            raise NotImplementedError(f"Abstract3DUNet: in_channels={self.in_channels} is not a multiple of 16 (the first convolution reads its "
+                                      "input unpadded, 16 channels at a time)")
+        k = 2 ** (len(self.encoders) - 1)
+        if any(int(n) % k != 0 for n in x.shape[1:4]):
+            raise NotImplementedError(f"Abstract3DUNet: grid {tuple(x.shape[1:4])} does not halve evenly through {len(self.encoders)} levels "
+                                      f"(every dimension must be a multiple of {k}: only x2 nearest upsampling is implemented)")
 
     def run(self, x, stats=None, pre_final=False, return_stats=False, sparse_flat=None, arith=None):
         """channel-last in, channel-last out (pre_final: stop before the final 1x1x1 convolution -- it is linear, so the decoders can
         fold it into their first layer and sample the f_maps[0]-channel volume instead: networks/conv_implicit_wnf.py UNetResult).  Every kernel that produces a tensor also emits the per-channel statistics the
-        next GroupNorm needs (conv / max-pool epilogues), so no activation is re-read for normalisation."""
+        next GroupNorm needs (conv / max-pool epilogues), so no activation is re-read for normalisation.
+        Widths that are not multiples of 32 run channel-padded (stored_channels): the pre-final volume then holds stored_channels(f_maps[0])
+        channels, the pads exactly zero; the final convolution's output has out_channels."""
+        self.check_input(x)
         feats = []
         for i, enc in enumerate(self.encoders):
             info = {}

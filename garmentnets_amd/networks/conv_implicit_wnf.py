@@ -172,15 +172,18 @@ class ImplicitWNFDecoder(PackedModule):
         W1' = W1 Wf, b1' = b1 + W1 bf (fp64 on the host).  It runs on rows sampled from the PRE-final feature volume (f_maps[0] = 32
         channels instead of 128): trilinear interpolation is linear and its weights sum to one, so sample(Wf x + bf) = Wf sample(x) +
         bf up to rounding.  The 128-channel volume is then never written or read (17 GB per 16-garment batch at 128^3), the
-        sampler moves a quarter of the bytes and layer 1 does a quarter of the FLOPs.  -> packed() layout, or None when not foldable."""
+        sampler moves a quarter of the bytes and layer 1 does a quarter of the FLOPs.  -> packed() layout, or None when not foldable.
+        A channel-padded pre-final volume (f_maps[0] not a multiple of 32: components/unet3d.py stored_channels) gets zero weight columns
+        for its pad channels."""
         ch = self.nn_channels
-        if not (self.fused and len(ch) == 4 and ch[0] == final_conv.out_channels and final_conv.in_channels % 32 == 0 and ch[1] % 256 == 0
+        cin = final_conv.in_stored or final_conv.in_channels
+        if not (self.fused and len(ch) == 4 and ch[0] == final_conv.out_channels and cin % 32 == 0 and ch[1] % 256 == 0
                 and ch[2] % 256 == 0 and ch[3] <= 4 and final_conv.kernel_size == (1, 1, 1)):
             return None
-        key = (id(final_conv), final_conv.weight._version, final_conv.bias._version, final_conv.weight.device) + tuple(p._version for p in self.parameters())
+        key = (id(final_conv), cin, final_conv.weight._version, final_conv.bias._version, final_conv.weight.device) + tuple(p._version for p in self.parameters())
 
         def build():
-            wf = final_conv.weight.detach().double().reshape(final_conv.out_channels, final_conv.in_channels)
+            wf = final_conv.stored_weight().double()
             bf = final_conv.bias.detach().double()
             layers, raw = [], []
             for i, block in enumerate(self.mlp):
@@ -194,7 +197,7 @@ class ImplicitWNFDecoder(PackedModule):
                 layers.append((ops.pack_kpair(w) if i < 2 else w.contiguous(), b, sc, sh, ch[i + 1]))
                 raw.append((w, b, sc, sh))
             # the split-operand pack: the shipped hidden width 256 and the class default 512 (conv_implicit_wnf.py:122), csrc/decode_split.hip
-            split = ops.pack_decode_split(raw).to(w.device) if (final_conv.in_channels, ch[1], ch[2]) in ((32, 256, 256), (32, 512, 512)) else None
+            split = ops.pack_decode_split(raw).to(w.device) if (cin, ch[1], ch[2]) in ((32, 256, 256), (32, 512, 512)) else None
             return tuple(layers) + (split,)
         return param_cache(self, "_folded").get(key, "folded", build)
 
@@ -331,7 +334,7 @@ class UNetResult(dict):
 
     def __init__(self, pre_final, final_conv, pre_stats=None):
         super().__init__()
-        self.pre_final, self.final_conv = pre_final, final_conv          # [B][D][H][W][f_maps[0]] channel-last
+        self.pre_final, self.final_conv = pre_final, final_conv          # [B][D][H][W][f_maps[0]] channel-last (channel-padded: pads 0)
         self.pre_stats = pre_stats                                       # (sum, sumsq, V) of pre_final from the last conv's epilogue, or None
         self._scales = {}                                                # smax -> (B, 2) decoder input scales
 

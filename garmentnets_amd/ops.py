@@ -277,13 +277,17 @@ def channel_stats(x):
     B, C = x.shape[0], x.shape[-1]
     V = x.numel() // (B * C)
     s, q = _stats_buffers(B, C, x.device, True)
-    _lib.call("gn_channel_stats", _p(x), B, V, C, _p(s), _p(q), _stream())
+    # (gn_channel_stats_any: the channel counts gn_channel_stats does not take -- the UNet's channel-padded widths 96, 160, 384 ...)
+    narrow = (C <= 256 and 256 % C == 0) or C % 256 == 0
+    _lib.call("gn_channel_stats" if narrow else "gn_channel_stats_any", _p(x), B, V, C, _p(s), _p(q), _stream())
     return s, q, V
 
 
-def groupnorm_affine(st0, st1, groups, eps, gamma, beta, with_act_scale=False):
+def groupnorm_affine(st0, st1, groups, eps, gamma, beta, with_act_scale=False, real=None):
     """-> (a, d) [B][C0+C1]; with_act_scale: -> (a, d, act_inv_scale [B]) with the sample's power-of-two range normalisation folded
-    into a and d (split-operand convs: conv3d_gcr_split undoes it in the epilogue)"""
+    into a and d (split-operand convs: conv3d_gcr_split undoes it in the epilogue).
+    real: the real channel count of each source when the statistics cover channel-padded storage (C0, C1 stored): the groups are formed over
+    the real channels (gamma / beta hold those), a = d = 0 on the pads (gn_groupnorm_affine_map, which also takes more than 1024 channels)"""
     s0, q0, V0 = st0
     B, C0 = s0.shape
     if st1 is not None:
@@ -296,9 +300,17 @@ def groupnorm_affine(st0, st1, groups, eps, gamma, beta, with_act_scale=False):
     a = torch.empty((B, C0 + C1), dtype=torch.float32, device=s0.device)
     d = torch.empty_like(a)
     inv = torch.empty(B, dtype=torch.float32, device=s0.device) if with_act_scale else None
-    _lib.call("gn_groupnorm_affine", _p(s0), _p(q0), C0, V0, _p(s1), _p(q1), C1, V1, rep, B, groups, float(eps), _p(gamma), _p(beta),
-              _p(a), _p(d), _p(inv), _stream())
+    r0, r1 = (C0, C1) if real is None else (int(real[0]), int(real[1]) if len(real) > 1 else 0)
+    if (r0, r1) == (C0, C1) and C0 + C1 <= GNA_MAXC:
+        _lib.call("gn_groupnorm_affine", _p(s0), _p(q0), C0, V0, _p(s1), _p(q1), C1, V1, rep, B, groups, float(eps), _p(gamma), _p(beta),
+                  _p(a), _p(d), _p(inv), _stream())
+    else:
+        _lib.call("gn_groupnorm_affine_map", _p(s0), _p(q0), r0, C0, V0, _p(s1), _p(q1), r1, C1, V1, rep, B, groups, float(eps), _p(gamma),
+                  _p(beta), _p(a), _p(d), _p(inv), _stream())
     return (a, d, inv) if with_act_scale else (a, d)
+
+
+GNA_MAXC = 1024        # gn_groupnorm_affine's channel limit (static LDS tables); gn_groupnorm_affine_map sizes its tables from C
 
 
 def pack_conv_weight(w):
@@ -584,8 +596,12 @@ def affine_act(x, a=None, d=None, bias=None, act=ACT_NONE, out=None):
 def maxpool3d_2(x, with_stats=False):
     B, D, H, W, C = x.shape
     out = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-    s, q = _stats_buffers(B, C, x.device, with_stats)
+    # the kernel's statistics epilogue takes C / 4 | 256; other widths get their statistics from one gn_channel_stats(_any) pass
+    epilogue = with_stats and 0 < C <= 256 and C % 4 == 0 and 256 % (C // 4) == 0
+    s, q = _stats_buffers(B, C, x.device, epilogue)
     _lib.call("gn_maxpool3d_2", _p(x), B, D, H, W, C, _p(out), _p(s), _p(q), _stream())
+    if with_stats and not epilogue:
+        return out, channel_stats(out)
     return (out, (s, q, (D // 2) * (H // 2) * (W // 2))) if with_stats else out
 
 

@@ -1,0 +1,308 @@
+"""GPU (-m gpu): the UNet at every width and depth the reference's UNet3D accepts.
+
+Kernels: gn_groupnorm_affine_map (any channel count, channel-padded storage) and gn_channel_stats_any against fp64 numpy, and
+bit for bit against gn_groupnorm_affine where that one runs.  Abstract3DUNet at widths that are not multiples of 32 (channel-padded
+storage, pads exactly zero), deeper and wider than the shipped f_maps=32 / 4 levels, against oracle/pipeline.py in fp64.  The whole
+pipeline with f_maps 16 and 128 from a saved checkpoint against the oracle.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import pipeline as P  # noqa: E402
+from garmentnets_amd import _lib, ops, synthetic as S  # noqa: E402
+from garmentnets_amd.arith import Arith  # noqa: E402
+from garmentnets_amd.components import unet3d as U  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def _threads():
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+
+
+def _stats(B, C, V, seed):
+    """plausible GroupNorm statistics: per-channel mean m and spread s over V voxels -> (sum, sumsq) fp64"""
+    g = torch.Generator().manual_seed(seed)
+    m = torch.randn(B, C, generator=g, dtype=torch.float64)
+    s = torch.rand(B, C, generator=g, dtype=torch.float64) * 2 + 0.1
+    return (m * V), ((s * s + m * m) * V)
+
+
+def _affine_ref(sums, sqs, Vs, reps, groups, eps, gamma, beta):
+    """numpy fp64 restatement of nn.GroupNorm's affine over the concatenated sources -> (a, d) [B][C]"""
+    s = np.concatenate([np.asarray(x) * r for x, r in zip(sums, reps)], axis=1)
+    q = np.concatenate([np.asarray(x) * r for x, r in zip(sqs, reps)], axis=1)
+    B, C = s.shape
+    cpg = C // groups
+    n = cpg * Vs
+    gs, gq = s.reshape(B, groups, cpg).sum(2), q.reshape(B, groups, cpg).sum(2)
+    mean = gs / n
+    var = np.maximum(gq / n - mean * mean, 0)
+    rstd = 1 / np.sqrt(var + eps)
+    a = gamma[None] * np.repeat(rstd, cpg, axis=1)
+    d = beta[None] - np.repeat(mean, cpg, axis=1) * a
+    return a, d
+
+
+def _affine_case(C0, C1, groups, seed, V0=4096):
+    B = 3
+    rep = 8 if C1 else 1
+    s0, q0 = _stats(B, C0, V0, seed)
+    s1, q1 = _stats(B, C1, V0 // rep, seed + 1) if C1 else (None, None)
+    g = torch.Generator().manual_seed(seed + 2)
+    gamma = (1 + 0.2 * torch.randn(C0 + C1, generator=g)).float()
+    beta = (0.3 * torch.randn(C0 + C1, generator=g)).float()
+    return B, V0, rep, (s0, q0), (s1, q1), gamma, beta
+
+
+def _map_call(st0, st1, real, stored, V0, rep, B, groups, gamma, beta, with_scale):
+    (s0, q0), (s1, q1) = st0, st1
+    S = sum(stored)
+    a = torch.empty((B, S), dtype=torch.float32, device=DEV)
+    d = torch.empty_like(a)
+    a.fill_(7.0)
+    d.fill_(7.0)
+    inv = torch.empty(B, dtype=torch.float32, device=DEV) if with_scale else None
+    p = lambda t: None if t is None else t.to(DEV).contiguous()
+    s0, q0, s1, q1, gamma, beta = p(s0), p(q0), p(s1), p(q1), p(gamma), p(beta)
+    C1, S1 = (real[1], stored[1]) if len(real) > 1 else (0, 0)
+    _lib.call("gn_groupnorm_affine_map", ops._p(s0), ops._p(q0), real[0], stored[0], V0, ops._p(s1), ops._p(q1), C1, S1, V0 // rep if C1 else 0, rep,
+              B, groups, 1e-5, ops._p(gamma), ops._p(beta), ops._p(a), ops._p(d), ops._p(inv), ops._stream())
+    torch.cuda.synchronize()
+    return a.cpu(), d.cpu(), None if inv is None else inv.cpu()
+
+
+@pytest.mark.parametrize("C,two", [(1536, False), (1536, True), (3072, False), (3072, True)])
+def test_groupnorm_affine_beyond_1024_channels(C, two):
+    """the decoder concatenations of f_maps 128 / levels 4, 64 / 5, 32 / 6 (512 + 1024) and wider: gn_groupnorm_affine refuses them"""
+    C0, C1 = (C // 3, C - C // 3) if two else (C, 0)
+    groups = 8
+    B, V0, rep, st0, st1, gamma, beta = _affine_case(C0, C1, groups, C)
+    real = (C0, C1) if two else (C0,)
+    a, d, _ = _map_call(st0, st1, real, real, V0, rep, B, groups, gamma, beta, False)
+    ra, rd = _affine_ref([st0[0]] + ([st1[0]] if two else []), [st0[1]] + ([st1[1]] if two else []), V0, [1] + ([rep] if two else []), groups,
+                         1e-5, gamma.double().numpy(), beta.double().numpy())
+    np.testing.assert_allclose(a.numpy(), ra, rtol=2e-6, atol=1e-6)
+    np.testing.assert_allclose(d.numpy(), rd, rtol=2e-6, atol=1e-6 * np.abs(rd).max())
+    # the ops wrapper takes the new entry for these widths
+    s0, q0 = (t.to(DEV) for t in st0)
+    o1 = None if not two else (st1[0].to(DEV), st1[1].to(DEV), V0 // rep)
+    a2, d2, inv = ops.groupnorm_affine((s0, q0, V0), o1, groups, 1e-5, gamma.to(DEV), beta.to(DEV), with_act_scale=True)
+    inv = inv.cpu().numpy()
+    assert np.all(np.frexp(inv)[0] == 0.5)                                  # exact powers of two
+    np.testing.assert_allclose(a2.cpu().numpy() * inv[:, None], ra, rtol=2e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize("C0,C1,groups", [(32, 0, 8), (96, 0, 8), (256, 512, 8), (512, 512, 16), (384, 192, 4), (1024, 0, 32), (48, 16, 1)])
+@pytest.mark.parametrize("with_scale", [False, True])
+def test_groupnorm_affine_map_is_bit_identical_to_the_narrow_kernel(C0, C1, groups, with_scale):
+    B, V0, rep, st0, st1, gamma, beta = _affine_case(C0, C1, groups, C0 + 3 * C1 + groups)
+    real = (C0, C1) if C1 else (C0,)
+    a, d, inv = _map_call(st0, st1, real, real, V0, rep, B, groups, gamma, beta, with_scale)
+    o1 = None if not C1 else (st1[0].to(DEV), st1[1].to(DEV), V0 // rep)
+    r = ops.groupnorm_affine((st0[0].to(DEV), st0[1].to(DEV), V0), o1, groups, 1e-5, gamma.to(DEV), beta.to(DEV), with_act_scale=with_scale)
+    assert torch.equal(a, r[0].cpu()) and torch.equal(d, r[1].cpu())
+    if with_scale:
+        assert torch.equal(inv, r[2].cpu())
+
+
+@pytest.mark.parametrize("real,stored,groups", [((16,), (32,), 8), ((48,), (64,), 16), ((96, 48), (96, 64), 8), ((24, 48), (32, 64), 4),
+                                                ((16, 8), (32, 32), 8), ((1040, 520), (1056, 544), 8)])
+@pytest.mark.parametrize("with_scale", [False, True])
+def test_groupnorm_affine_channel_map(real, stored, groups, with_scale):
+    """channel-padded storage: on the real channels the bits of the unpadded call, a = d = 0 on the pads whatever their statistics hold"""
+    C0, C1 = real[0], (real[1] if len(real) > 1 else 0)
+    B, V0, rep, st0, st1, gamma, beta = _affine_case(C0, C1, groups, sum(stored) + groups)
+    a, d, inv = _map_call(st0, st1, real, real, V0, rep, B, groups, gamma, beta, with_scale)
+
+    def pad(st, r, s):
+        if st[0] is None:
+            return st
+        g = torch.Generator().manual_seed(s)
+        out = []
+        for t in st:
+            z = torch.rand(B, s, generator=g, dtype=torch.float64) * 1e3 + 1   # garbage on the pads: the kernel must not read them
+            z[:, :r] = t
+            out.append(z)
+        return tuple(out)
+    pst0 = pad(st0, C0, stored[0])
+    pst1 = pad(st1, C1, stored[1]) if C1 else st1
+    pa, pd, pinv = _map_call(pst0, pst1, real, stored, V0, rep, B, groups, gamma, beta, with_scale)
+    idx = list(range(C0)) + [stored[0] + i for i in range(C1)]
+    pads = [i for i in range(sum(stored)) if i not in set(idx)]
+    assert torch.equal(pa[:, idx], a) and torch.equal(pd[:, idx], d)
+    assert torch.equal(pa[:, pads], torch.zeros(B, len(pads))) and torch.equal(pd[:, pads], torch.zeros(B, len(pads)))
+    if with_scale:
+        assert torch.equal(pinv, inv)
+
+
+@pytest.mark.parametrize("C", [96, 160, 384, 1056])
+def test_channel_and_maxpool_statistics_at_any_width(C):
+    g = torch.Generator().manual_seed(C)
+    x = (torch.randn(2, 8, 6, 10, C, generator=g) * 2 + 0.5).to(DEV)
+    s, q, V = ops.channel_stats(x)
+    xd = x.cpu().double().reshape(2, -1, C).numpy()
+    assert V == 480
+    np.testing.assert_allclose(s.cpu().numpy(), xd.sum(1), rtol=1e-6, atol=1e-4)
+    np.testing.assert_allclose(q.cpu().numpy(), (xd * xd).sum(1), rtol=1e-6)
+    pooled, (ps, pq, pv) = ops.maxpool3d_2(x, with_stats=True)
+    ref = torch.nn.functional.max_pool3d(x.cpu().permute(0, 4, 1, 2, 3), 2).permute(0, 2, 3, 4, 1)
+    assert torch.equal(pooled.cpu(), ref) and pv == 60
+    rd = ref.double().reshape(2, -1, C).numpy()
+    np.testing.assert_allclose(ps.cpu().numpy(), rd.sum(1), rtol=1e-6, atol=1e-4)
+    np.testing.assert_allclose(pq.cpu().numpy(), (rd * rd).sum(1), rtol=1e-6)
+
+
+# ---------------------------------------------------------------------------------------------------- UNet against the oracle
+def _unet(in_channels, f_maps, levels, groups, order="gcr", seed=5):
+    torch.manual_seed(seed)
+    net = U.Abstract3DUNet(in_channels=in_channels, out_channels=16, f_maps=f_maps, layer_order=order, num_groups=groups, num_levels=levels)
+    g = torch.Generator().manual_seed(seed + 6)
+    with torch.no_grad():
+        for name, prm in net.named_parameters():
+            if prm.dim() > 1:
+                fan_in = prm[0].numel()
+                prm.copy_((torch.rand(prm.shape, generator=g) * 2 - 1) * (3.0 / fan_in) ** 0.5)
+            else:
+                prm.copy_(torch.randn(prm.shape, generator=g) * 0.3 + (1.0 if name.endswith("norm.weight") else 0.0))
+        for name, buf in net.named_buffers():
+            if name.endswith("running_var"):
+                buf.copy_(torch.rand(buf.shape, generator=g) + 0.5)
+            elif name.endswith("running_mean"):
+                buf.copy_(torch.randn(buf.shape, generator=g) * 0.2)
+    return net.eval()
+
+
+class _PadProbe:
+    """records every SingleConv output and the real channel count it carries"""
+
+    def __init__(self, monkeypatch):
+        self.seen = []
+        orig = U.SingleConv.run
+
+        def run(conv, *args, **kwargs):
+            r = orig(conv, *args, **kwargs)
+            self.seen.append((conv.conv.out_channels, r[0]))
+            return r
+        monkeypatch.setattr(U.SingleConv, "run", run)
+
+    def assert_pads_zero(self):
+        padded = 0
+        for cout, y in self.seen:
+            assert y.shape[-1] == -(-cout // 32) * 32
+            if y.shape[-1] > cout:
+                padded += 1
+                assert int(torch.count_nonzero(y[..., cout:])) == 0
+        return padded
+
+
+UNET_CASES = [
+    # (in_channels, f_maps, levels, groups, G, arith, order)
+    (32, 16, 4, 8, 16, None, "gcr"),
+    (32, 48, 3, 8, 16, None, "gcr"),
+    (32, 96, 3, 8, 16, None, "gcr"),
+    (32, 64, 4, 8, 16, None, "gcr"),
+    (32, 64, 5, 8, 16, None, "gcr"),
+    (32, 128, 4, 8, 16, None, "gcr"),
+    (32, 32, 6, 8, 32, None, "gcr"),
+    (16, [24, 48, 96], None, 8, 16, None, "gcr"),
+    (32, 16, 4, 4, 16, None, "gcr"),
+    (32, 48, 3, 16, 16, None, "gcr"),
+    (32, 96, 3, 4, 16, None, "gcr"),
+    (32, 16, 4, 8, 16, "fp32", "gcr"),
+    (32, 96, 3, 16, 16, "fp32", "gcr"),
+    (32, 128, 4, 8, 16, "fp32", "gcr"),
+    (16, [24, 48, 96], None, 8, 16, "fp32", "gcr"),
+    (32, 16, 3, 8, 16, None, "crg"),
+    (32, 48, 3, 8, 16, None, "cbr"),
+]
+
+
+@pytest.mark.parametrize("cin,f_maps,levels,groups,G,arith,order", UNET_CASES)
+def test_unet_widths_against_oracle(cin, f_maps, levels, groups, G, arith, order, monkeypatch):
+    """Abstract3DUNet at widths the conv kernels do not take directly (channel-padded) and depths / widths past gn_groupnorm_affine's
+    1024 channels, against the oracle in fp64 at the bound of test_unet_other_layer_orders_against_oracle; every pad channel of every
+    layer's output is exactly zero"""
+    _threads()
+    net = _unet(cin, f_maps, levels if levels else 4, groups, order)
+    if arith == "fp32":
+        net.arith = Arith.named("fp32", "fp32")
+    sd = {"u." + k: v.clone().double() if v.is_floating_point() else v.clone() for k, v in net.state_dict().items()}
+    x = torch.randn(2, cin, G, G, G, generator=torch.Generator().manual_seed(G + cin))
+    hp = dict(f_maps=f_maps, layer_order=order, num_groups=groups)
+    if levels:
+        hp["num_levels"] = levels
+    with torch.no_grad():
+        ref = P.unet3d(sd, hp, x.double(), prefix="u").numpy()
+    probe = _PadProbe(monkeypatch)
+    with torch.no_grad():
+        y = net.to(DEV)(x.to(DEV)).cpu().numpy()
+    assert y.shape == ref.shape
+    np.testing.assert_allclose(y, ref, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(ref).max())))
+    padded = probe.assert_pads_zero()
+    assert (padded > 0) == any(cout % 32 for cout, _ in probe.seen)
+
+
+@pytest.mark.parametrize("f_maps", [16, 24])
+def test_padded_unet_pre_final_and_folded_decoder(f_maps):
+    """the pre-final volume of a padded f_maps[0] has zero pad channels, the folded first decoder layer takes the fused kernels on it and
+    gives what the materialised out_feature_volume gives"""
+    from garmentnets_amd.networks.conv_implicit_wnf import ImplicitWNFDecoder, UNetResult
+    net = _unet(32, f_maps, 3, 8).to(DEV)
+    x = torch.randn(2, 16, 16, 16, 32, generator=torch.Generator().manual_seed(3)).to(DEV)
+    pre, st = net.run(x, pre_final=True, return_stats=True)
+    assert pre.shape[-1] == 32 and int(torch.count_nonzero(pre[..., f_maps:])) == 0
+    dec = ImplicitWNFDecoder((16, 256, 256, 1)).to(DEV).eval()
+    layers = dec.folded_pack(net.final_conv)
+    assert layers is not None and layers[3] is not None                       # the fused split-operand decoder on 32 stored channels
+    res = UNetResult(pre, net.final_conv, st)
+    out = res["out_feature_volume"]
+    assert out.shape == (2, 16, 16, 16, 16)
+    q = torch.rand(2, 500, 3, generator=torch.Generator().manual_seed(4)).to(DEV)
+    folded = dec.run_on(UNetResult(pre, net.final_conv, st), q)
+    plain = dec(out, q)
+    np.testing.assert_allclose(folded.cpu().numpy(), plain.cpu().numpy(), rtol=1e-4, atol=1e-4 * max(1.0, float(plain.abs().max())))
+
+
+# ---------------------------------------------------------------------------------------------------- whole pipeline
+@pytest.mark.parametrize("f_maps", [16, 128])
+def test_pipeline_at_other_unet_widths_against_oracle(f_maps, tmp_path):
+    """a checkpoint of another unet3d_params width loads (load_from_checkpoint) and runs through predict_batch at the library-default
+    arithmetic (occupancy-aware first convolution on) -- against oracle.pipeline.predict"""
+    from garmentnets_amd import parallel
+    from garmentnets_amd.networks.conv_implicit_wnf import ConvImplicitWNFPipeline
+    from garmentnets_amd.predict import predict_batch
+    _threads()
+    G, Q, B, NPTS, TOL = 32, 64, 2, 3000, 1e-4
+    hp = S.default_hparams(grid=G)
+    hp["unet3d_params"] = dict(hp["unet3d_params"], f_maps=f_maps)
+    sd = S.synthetic_state_dict(hp, 0, planted_nocs=True)
+    m = ConvImplicitWNFPipeline(**hp)
+    m.load_state_dict(sd)
+    ck = str(tmp_path / "model.ckpt")
+    m.save_checkpoint(ck)
+    model = ConvImplicitWNFPipeline.load_from_checkpoint(ck).to(DEV).eval().requires_grad_(False)
+    assert model.arith.sparse_first_conv
+    shard, _ = parallel.shard_batch(B, NPTS, 1234, 0, 1, colour="position")
+    res = predict_batch(model, shard.to(DEV), volume_size=Q, auto_level=True)
+    with torch.no_grad():
+        ref = P.predict(sd, hp, shard.x, shard.pos, shard.batch, Q=Q, auto_level=True)
+        vin = model.volume_agg(model.pointnet2_forward(shard.to(DEV))["nocs_data"]).cpu()
+    ref_bins = ref["pointnet2_result"]["nocs_data"]["nocs_bin_idx"]
+    bins = torch.cat([torch.round(r["pred_nocs"] * 63).to(torch.int64) for r in res]).cpu()
+    assert torch.equal(bins, ref_bins)
+    assert torch.equal(vin != 0, ref["in_feature_volume"] != 0)
+    for b in range(B):
+        wnf = res[b]["wnf_volume"].cpu().numpy()
+        ref_wnf = ref["garments"][b]["wnf_volume"]
+        assert float(np.abs(wnf - ref_wnf).max()) <= TOL
+        level = float(res[b]["level"]) if "level" in res[b] else 0.5 * (float(wnf.min()) + float(wnf.max()))
+        iso = P.isosurface(wnf, level, 0.5)
+        assert np.array_equal(res[b]["faces"].cpu().numpy(), iso["faces"]) and np.array_equal(res[b]["verts"].cpu().numpy(), iso["verts"])
+        far = np.abs(ref_wnf - level) > TOL
+        assert np.array_equal((wnf > level)[far], (ref_wnf > level)[far])
