@@ -22,6 +22,8 @@ PROTOTYPES = {
     "gn_segment_ptr": [_vp, _i64, _i32, _vp, _vp],
     "gn_fps": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "gn_fps_nested": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "gn_fps_workspace_bytes": [_i32, _i32],
+    "gn_fps_nested_ws": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
     "gn_ball_query": [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp],
     "gn_sa_gather": [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp],
     "gn_segment_max": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
@@ -31,11 +33,13 @@ PROTOTYPES = {
     "gn_sa_gather_scoped": [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "gn_global_max_pool": [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp],
     "gn_knn_interpolate": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
+    "gn_knn_interpolate_any": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "gn_linear": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _vp],
     "gn_nocs_head": [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp],
     "gn_grid_features": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],
     "gn_grid_scatter_workspace_bytes": [_i64, _i32, _i32],
     "gn_grid_scatter": [_vp, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _i32, _vp],
+    "gn_grid_scatter_ex": [_vp, _i32, _vp, _i64, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _i32, _vp],
     "gn_channel_stats": [_vp, _i32, _i64, _i32, _vp, _vp, _vp],
     "gn_groupnorm_affine": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_channel_stats_any": [_vp, _i32, _i64, _i32, _vp, _vp, _vp],
@@ -86,7 +90,7 @@ PROTOTYPES = {
     "gn_nearest_neighbor_f64_batch": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "gn_point_mesh_sqdist_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz}
+_RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz}
 
 _lib = None
 

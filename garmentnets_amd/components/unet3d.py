@@ -422,9 +422,9 @@ class Abstract3DUNet(nn.Module):
 
     def check_input(self, x):
         """refuse, by name, the shapes this UNet does not run: NotImplementedError"""
-        if self.in_channels % 16 != 0:
-            raise NotImplementedError(f"Abstract3DUNet: in_channels={self.in_channels} is not a multiple of 16 (the first convolution reads its "
-                                      "input unpadded, 16 channels at a time)")
+        if x.shape[-1] % 16 != 0:
+            raise NotImplementedError(f"Abstract3DUNet.run: an input stored with {x.shape[-1]} channels is not a multiple of 16 (the first convolution "
+                                      "reads 16 channels at a time): hand it channel-padded (stored_channels), as forward() and the volume aggregator do")
         k = 2 ** (len(self.encoders) - 1)
         if any(int(n) % k != 0 for n in x.shape[1:4]):
             raise NotImplementedError(f"Abstract3DUNet: grid {tuple(x.shape[1:4])} does not halve evenly through {len(self.encoders)} levels "
@@ -451,7 +451,17 @@ class Abstract3DUNet(nn.Module):
     def forward(self, x):
         """x: (B, C, D, H, W) as in the reference; returns (B, C', D, H, W) (a view over channel-last storage)."""
         stats = getattr(x, "_gn_stats", None)
-        return self.run(to_channel_last(x), stats, arith=self.arith).permute(0, 4, 1, 2, 3)
+        v = stored_volume(x)
+        if v.shape[-1] % 16 != 0:                 # an input width the first convolution does not read as it is: channel-padded, pads 0
+            v, stats = to_stored(v, (v.shape[-1],), (stored_channels(v.shape[-1]),)), None
+        return self.run(v, stats, arith=self.arith).permute(0, 4, 1, 2, 3)
+
+
+def stored_volume(x):
+    """(B,C,D,H,W) -> the channel-last storage the UNet reads: the channel-padded volume a scattered (B,C,D,H,W) view carries
+    (VolumeFeatureAggregator, C not a multiple of 16), else to_channel_last(x)"""
+    v = getattr(x, "_gn_stored", None)
+    return to_channel_last(x) if v is None else v
 
 
 def to_channel_last(x):

@@ -1,7 +1,10 @@
-// grid.hip -- VolumeFeatureAggregator: per-point cell index + aggregation features, scatter (max | mean) into a
+// grid.hip -- VolumeFeatureAggregator: per-point cell index + aggregation features, scatter (max | mean | sum | min | mul) into a
 // channel-last feature volume.  Reference: /root/reference/networks/conv_implicit_wnf.py:43-100,
 // components/gridding.py:161-256 (VirtualGrid index maths, fp32, truncation toward zero).
 #include "common.h"
+
+// gn_grid_scatter's reduce codes (include/garmentnets_hip.h)
+enum { GN_REDUCE_MAX = 0, GN_REDUCE_MEAN = 1, GN_REDUCE_SUM = 2, GN_REDUCE_MIN = 3, GN_REDUCE_MUL = 4 };
 
 struct GridParams {
     float lower[3], upper[3];
@@ -75,7 +78,14 @@ __device__ __forceinline__ float dec_f32(unsigned e) {
     return __uint_as_float(u);
 }
 
-// max: order-independent by construction (atomicMax on the encoding).
+// dec_f32(~e), written out: (e's top bit clear: ~e has it set)
+__device__ __forceinline__ float dec_inv_f32(unsigned e) {
+    return __uint_as_float((e & 0x80000000u) ? e : (~e & 0x7fffffffu));
+}
+
+// max: order-independent by construction (atomicMax on the encoding).  INV (min): atomicMax on ~enc(x), also > 0 for every non-NaN float, so a
+// zero-filled cell still reads as empty and the finalize pass still leaves untouched cells at 0.
+template <bool INV>
 __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__restrict__ src, int lds, const int32_t *__restrict__ flat_idx,
                                                                 int64_t N, int C, float *__restrict__ vol, int32_t *__restrict__ count) {
     const int lane = threadIdx.x & 63;
@@ -84,10 +94,14 @@ __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__r
     const int64_t cell = flat_idx[p];
     if (lane == 0) atomicAdd(&count[cell], 1);
     float *v = vol + cell * C;
-    for (int ch = lane; ch < C; ch += 64) atomicMax(reinterpret_cast<unsigned *>(v) + ch, enc_f32(src[p * lds + ch]));
+    for (int ch = lane; ch < C; ch += 64) {
+        const unsigned e = enc_f32(src[p * lds + ch]);
+        atomicMax(reinterpret_cast<unsigned *>(v) + ch, INV ? ~e : e);
+    }
 }
 
 // the first point that reaches a cell here finalises it (decode the max)
+template <bool INV>
 __global__ __launch_bounds__(256) void scatter_max_finalize_kernel(const int32_t *__restrict__ flat_idx, int64_t N, int C,
                                                                    float *__restrict__ vol, int32_t *__restrict__ count) {
     const int lane = threadIdx.x & 63;
@@ -99,7 +113,10 @@ __global__ __launch_bounds__(256) void scatter_max_finalize_kernel(const int32_t
     c = __shfl(c, 0);
     if (c <= 0) return;
     float *v = vol + cell * C;
-    for (int ch = lane; ch < C; ch += 64) v[ch] = dec_f32(__float_as_uint(v[ch]));
+    for (int ch = lane; ch < C; ch += 64) {
+        const unsigned e = __float_as_uint(v[ch]);
+        v[ch] = INV ? dec_inv_f32(e) : dec_f32(e);
+    }
 }
 
 // mean: DETERMINISTIC.  A float atomicAdd into the volume would make the sum depend on the arrival order of a cell's points (with
@@ -130,6 +147,8 @@ __global__ __launch_bounds__(256) void scatter_mean_accum_kernel(const float *__
     for (int ch = lane; ch < C; ch += 64) atomicAdd(a + ch, (double)src[p * lds + ch]);
 }
 
+// DIV = false (sum / add): the same fp64 sums stored as fp32(sum)
+template <bool DIV>
 __global__ __launch_bounds__(256) void scatter_mean_finalize_kernel(const int32_t *__restrict__ flat_idx, int64_t N, int C,
                                                                     const int32_t *__restrict__ owner_of, const int32_t *__restrict__ npts,
                                                                     const double *__restrict__ acc, float *__restrict__ vol,
@@ -140,41 +159,130 @@ __global__ __launch_bounds__(256) void scatter_mean_finalize_kernel(const int32_
     const int64_t cell = flat_idx[p];
     const float c = (float)npts[p];
     float *v = vol + cell * C;
-    for (int ch = lane; ch < C; ch += 64) v[ch] = __fdiv_rn((float)acc[p * C + ch], c);
+    for (int ch = lane; ch < C; ch += 64) v[ch] = DIV ? __fdiv_rn((float)acc[p * C + ch], c) : (float)acc[p * C + ch];
     if (lane == 0) count[cell] = 0;                 // gn_grid_stats expects the count workspace zeroed
 }
 
-extern "C" size_t gn_grid_scatter_workspace_bytes(int64_t N, int C, int reduce) {
-    if (reduce != 1 || N <= 0) return 0;
-    return (size_t)N * C * sizeof(double) + 2 * (size_t)N * sizeof(int32_t);
+// mul: the product of a cell's points in ascending point index -- the order of torch_scatter's CPU loop; a float atomic product would depend on the
+// arrival order.  Owners as for mean; each owner gets a range of a point list (counting sort keyed by the owner: a range per owner from one counter,
+// then the points in arrival order), every point finds its rank in its cell's range (how many of the cell's points have a lower index: O(k) per point,
+// k = the cell's points) and moves to that slot of a second list, and the owner multiplies its cell's rows in that order, starting from the identity 1.
+struct MulWs {
+    int32_t *owner_of, *npts, *start, *cursor, *lst, *sorted, *total;
+};
+__host__ __device__ inline MulWs mul_ws(void *ws, int64_t N) {
+    int32_t *w = reinterpret_cast<int32_t *>(ws);
+    return MulWs{w, w + N, w + 2 * N, w + 3 * N, w + 4 * N, w + 5 * N, w + 6 * N};
 }
 
-extern "C" int gn_grid_scatter(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int64_t cells, int reduce,
-                               float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream) {
-    GN_REQUIRE(N >= 0 && C > 0 && cells >= 0 && (reduce == 0 || reduce == 1), "gn_grid_scatter: bad arguments");
+__global__ __launch_bounds__(256) void scatter_mul_start_kernel(int64_t N, MulWs w) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N || w.owner_of[p] != (int)p) return;
+    w.start[p] = atomicAdd(w.total, w.npts[p]);
+}
+
+__global__ __launch_bounds__(256) void scatter_mul_list_kernel(int64_t N, MulWs w) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    const int o = w.owner_of[p];
+    w.lst[w.start[o] + atomicAdd(&w.cursor[o], 1)] = (int)p;
+}
+
+__global__ __launch_bounds__(256) void scatter_mul_rank_kernel(int64_t N, MulWs w) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    const int o = w.owner_of[p], base = w.start[o], k = w.npts[o];
+    int rank = 0;
+    for (int i = 0; i < k; ++i) rank += w.lst[base + i] < (int)p;
+    w.sorted[base + rank] = (int)p;
+}
+
+// every cell: 1 on the real channels (the identity an empty cell keeps), 0 on the pads [c_real, C)
+__global__ __launch_bounds__(256) void scatter_mul_fill_kernel(int64_t n, int C, int c_real, float *__restrict__ vol) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    vol[t] = (int)(t % C) < c_real ? 1.f : 0.f;
+}
+
+__global__ __launch_bounds__(256) void scatter_mul_finalize_kernel(const float *__restrict__ src, int lds, const int32_t *__restrict__ flat_idx, int64_t N,
+                                                                   int C, MulWs w, float *__restrict__ vol, int32_t *__restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (p >= N || w.owner_of[p] != (int)p) return;
+    const int64_t cell = flat_idx[p];
+    const int32_t *list = w.sorted + w.start[p];
+    const int k = w.npts[p];
+    float *v = vol + cell * C;
+    for (int ch = lane; ch < C; ch += 64) {
+        float prod = 1.f;
+        for (int i = 0; i < k; ++i) prod = __fmul_rn(prod, src[(int64_t)list[i] * lds + ch]);
+        v[ch] = prod;
+    }
+    if (lane == 0) count[cell] = 0;                 // the count workspace leaves zeroed, as after the other reductions
+}
+
+extern "C" size_t gn_grid_scatter_workspace_bytes(int64_t N, int C, int reduce) {
+    if (N <= 0) return 0;
+    if (reduce == GN_REDUCE_MEAN || reduce == GN_REDUCE_SUM) return (size_t)N * C * sizeof(double) + 2 * (size_t)N * sizeof(int32_t);
+    if (reduce == GN_REDUCE_MUL) return (6 * (size_t)N + 1) * sizeof(int32_t);
+    return 0;
+}
+
+extern "C" int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int c_real, int64_t cells, int reduce,
+                                  float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream) {
+    GN_REQUIRE(N >= 0 && C > 0 && cells >= 0 && reduce >= GN_REDUCE_MAX && reduce <= GN_REDUCE_MUL, "gn_grid_scatter: bad arguments");
+    GN_REQUIRE(c_real > 0 && c_real <= C, "gn_grid_scatter: c_real must be in [1, C]");
     GN_REQUIRE(N < (int64_t)0x7fffffff, "gn_grid_scatter: more than 2^31-2 points");
     GN_REQUIRE(ws_bytes >= gn_grid_scatter_workspace_bytes(N, C, reduce) && (ws || !gn_grid_scatter_workspace_bytes(N, C, reduce)),
                "gn_grid_scatter: workspace too small (gn_grid_scatter_workspace_bytes)");
     hipStream_t st = gn_stream(stream);
     if (!vol_is_zeroed) {       // (the caller may have zeroed both ahead of time, e.g. on a side stream next to the serial FPS kernels)
-        GN_HIP(hipMemsetAsync(vol, 0, sizeof(float) * (size_t)cells * C, st), "gn_grid_scatter(memset vol)");
+        if (reduce != GN_REDUCE_MUL) GN_HIP(hipMemsetAsync(vol, 0, sizeof(float) * (size_t)cells * C, st), "gn_grid_scatter(memset vol)");
         GN_HIP(hipMemsetAsync(count_ws, 0, sizeof(int32_t) * (size_t)cells, st), "gn_grid_scatter(memset count)");
     }
-    if (N == 0) return GN_OK;
-    dim3 grid((unsigned)gn_cdiv(N, 4)), block(256);
-    if (reduce == 0) {
-        hipLaunchKernelGGL(scatter_max_accum_kernel, grid, block, 0, st, src, lds, flat_idx, N, C, vol, count_ws);
-        hipLaunchKernelGGL(scatter_max_finalize_kernel, grid, block, 0, st, flat_idx, N, C, vol, count_ws);
+    if (reduce == GN_REDUCE_MUL && cells > 0) {
+        const int64_t n = cells * C;
+        hipLaunchKernelGGL(scatter_mul_fill_kernel, dim3((unsigned)gn_cdiv(n, 256)), dim3(256), 0, st, n, C, c_real, vol);
+    }
+    if (N == 0) {
+        GN_LAUNCH_CHECK("gn_grid_scatter");
+        return GN_OK;
+    }
+    dim3 grid((unsigned)gn_cdiv(N, 4)), block(256), pts((unsigned)gn_cdiv(N, 256));
+    if (reduce == GN_REDUCE_MAX || reduce == GN_REDUCE_MIN) {
+        if (reduce == GN_REDUCE_MAX) {
+            hipLaunchKernelGGL(scatter_max_accum_kernel<false>, grid, block, 0, st, src, lds, flat_idx, N, C, vol, count_ws);
+            hipLaunchKernelGGL(scatter_max_finalize_kernel<false>, grid, block, 0, st, flat_idx, N, C, vol, count_ws);
+        } else {
+            hipLaunchKernelGGL(scatter_max_accum_kernel<true>, grid, block, 0, st, src, lds, flat_idx, N, C, vol, count_ws);
+            hipLaunchKernelGGL(scatter_max_finalize_kernel<true>, grid, block, 0, st, flat_idx, N, C, vol, count_ws);
+        }
+    } else if (reduce == GN_REDUCE_MUL) {
+        const MulWs w = mul_ws(ws, N);
+        GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
+        hipLaunchKernelGGL(scatter_mean_owner_kernel, pts, block, 0, st, flat_idx, N, count_ws, w.owner_of, w.npts);
+        hipLaunchKernelGGL(scatter_mul_start_kernel, pts, block, 0, st, N, w);
+        hipLaunchKernelGGL(scatter_mul_list_kernel, pts, block, 0, st, N, w);
+        hipLaunchKernelGGL(scatter_mul_rank_kernel, pts, block, 0, st, N, w);
+        hipLaunchKernelGGL(scatter_mul_finalize_kernel, grid, block, 0, st, src, lds, flat_idx, N, C, w, vol, count_ws);
     } else {
         double *acc = reinterpret_cast<double *>(ws);
         int32_t *owner_of = reinterpret_cast<int32_t *>(acc + (size_t)N * C), *npts = owner_of + N;
         GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
-        hipLaunchKernelGGL(scatter_mean_owner_kernel, dim3((unsigned)gn_cdiv(N, 256)), block, 0, st, flat_idx, N, count_ws, owner_of, npts);
+        hipLaunchKernelGGL(scatter_mean_owner_kernel, pts, block, 0, st, flat_idx, N, count_ws, owner_of, npts);
         hipLaunchKernelGGL(scatter_mean_accum_kernel, grid, block, 0, st, src, lds, N, C, owner_of, acc);
-        hipLaunchKernelGGL(scatter_mean_finalize_kernel, grid, block, 0, st, flat_idx, N, C, owner_of, npts, acc, vol, count_ws);
+        if (reduce == GN_REDUCE_MEAN)
+            hipLaunchKernelGGL(scatter_mean_finalize_kernel<true>, grid, block, 0, st, flat_idx, N, C, owner_of, npts, acc, vol, count_ws);
+        else
+            hipLaunchKernelGGL(scatter_mean_finalize_kernel<false>, grid, block, 0, st, flat_idx, N, C, owner_of, npts, acc, vol, count_ws);
     }
     GN_LAUNCH_CHECK("gn_grid_scatter");
     return GN_OK;
+}
+
+extern "C" int gn_grid_scatter(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int64_t cells, int reduce,
+                               float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream) {
+    return gn_grid_scatter_ex(src, lds, flat_idx, N, C, C, cells, reduce, vol, count_ws, ws, ws_bytes, vol_is_zeroed, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ sparse statistics

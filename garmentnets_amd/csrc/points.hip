@@ -1,6 +1,6 @@
 // points.hip -- PointNet++ point-set operators for gfx950 (wave64).
 //   gn_segment_ptr, gn_fps, gn_ball_query, gn_sa_gather, gn_segment_max, gn_global_max_pool,
-//   gn_knn_interpolate, gn_nocs_head
+//   gn_knn_interpolate(_any), gn_nocs_head
 // Reference call sites: /root/reference/components/pointnet2.py:22-76, networks/conv_implicit_wnf.py:220-231.
 #include <stdarg.h>
 #include <limits.h>
@@ -286,7 +286,7 @@ extern "C" int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t
     GN_REQUIRE(nested_gap == nullptr || start_idx == nullptr, "gn_fps_nested: a nested sample starts at the example's first point (start_idx must be NULL)");
     if (B == 0 || max_points_per_example == 0) return GN_OK;
     const int n = max_points_per_example;
-    GN_REQUIRE(n <= FPS_LDS_MAX, "gn_fps: more than %d points per example is not supported (got %d)", FPS_LDS_MAX, n);
+    GN_REQUIRE(n <= FPS_LDS_MAX, "gn_fps: more than %d points per example needs a workspace: gn_fps_nested_ws (got %d)", FPS_LDS_MAX, n);
     if (n > 16 * FPS_THREADS) {                     // beyond the register-resident kernels: running distances in LDS (fps_lds_kernel)
         const size_t shl = sizeof(float) * (4 * FPS_WAVES + (size_t)n);
         GN_HIP(hipFuncSetAttribute((const void *)fps_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shl), "gn_fps");
@@ -324,6 +324,83 @@ extern "C" int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t
     else FPS_LAUNCH(16, false, FPS_THREADS);
 #undef FPS_BY_PPT
 #undef FPS_LAUNCH
+    GN_LAUNCH_CHECK("gn_fps");
+    return GN_OK;
+}
+
+// Examples of more points than fps_lds_kernel holds: the running distances live in a device workspace, one 16-byte record (x, y, z, d) per point written
+// once at the start, so that a step is one dwordx4 load and one dword store per point (L2-resident: 1.6 MB per 100 000 points).  One workgroup per example as
+// above -- never one example over several workgroups, which would pay a device-scope fence and a spin barrier per step.  Every thread reads and writes only
+// its own records (points tid, tid + FPS_THREADS, ...), so the workspace needs no barrier; same arithmetic, same walk in ascending index and the same
+// reductions as fps_lds_kernel, hence the same index list.  A correctness path for the clouds the reference takes without limit, not a tuned one.
+__global__ __launch_bounds__(FPS_THREADS) void fps_ws_kernel(const float *__restrict__ pos, const int32_t *__restrict__ ptr, const int32_t *__restrict__ out_ptr,
+                                                            const int32_t *__restrict__ start_idx, int32_t *__restrict__ out_idx, float *__restrict__ gap_out,
+                                                            const float *__restrict__ nested_gap, float4 *__restrict__ ws, int max_points) {
+    constexpr int WAVES = FPS_WAVES;
+    __shared__ float pv[2 * WAVES];
+    __shared__ int pi[2 * WAVES];
+    const int b = blockIdx.x;
+    const int s = ptr[b], n = ptr[b + 1] - s;
+    const int o0 = out_ptr[b], m = out_ptr[b + 1] - o0;
+    if (n <= 0 || m <= 0 || n > max_points) return;   // (an example larger than the caller's max_points would run past its workspace rows)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (nested_gap && nested_gap[b] > 0.f && m <= n) {
+        for (int k = tid; k < m; k += FPS_THREADS) out_idx[o0 + k] = s + k;
+        if (gap_out && tid == 0) gap_out[b] = nested_gap[b];
+        return;
+    }
+    const float *gp = pos + 3 * (size_t)s;
+    float4 *rec = ws + (size_t)b * max_points;
+    for (int i = tid; i < n; i += FPS_THREADS) rec[i] = make_float4(gp[3 * i], gp[3 * i + 1], gp[3 * i + 2], 3.0e38f);
+    float gmin = 3.0e38f;
+    int last = start_idx ? start_idx[b] : 0;
+    if (last < 0 || last >= n) last = 0;
+    if (tid == 0) out_idx[o0] = s + last;
+    for (int k = 1; k < m; ++k) {
+        const float qx = gp[3 * last], qy = gp[3 * last + 1], qz = gp[3 * last + 2];
+        float bv = -1.f;
+        int bi = INT_MAX;
+        for (int i = tid; i < n; i += FPS_THREADS) {
+            const float4 r = rec[i];
+            const float d = fps_min(r.w, gn_sqdist3(r.x, r.y, r.z, qx, qy, qz));
+            reinterpret_cast<float *>(rec + i)[3] = d;
+            if (d > bv) { bv = d; bi = i; }          // ascending index: ties keep the lowest
+        }
+        const float wv = wave_max_f(bv);
+        const int wi = wave_min_i(bv == wv ? bi : INT_MAX);
+        const int par = (k & 1) * WAVES;
+        if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
+        __syncthreads();
+        float fv = pv[par + (lane & (WAVES - 1))];
+        int fi = pi[par + (lane & (WAVES - 1))];
+        const float gv = part_max_f<WAVES>(fv);
+        fi = part_min_i<WAVES>(fv == gv ? fi : INT_MAX);
+        last = __builtin_amdgcn_readfirstlane(fi);
+        gmin = fps_min(gmin, gv);
+        if (tid == 0) out_idx[o0 + k] = s + last;
+    }
+    if (gap_out && tid == 0) gap_out[b] = gmin;
+}
+
+extern "C" size_t gn_fps_workspace_bytes(int B, int max_points_per_example) {
+    if (B <= 0 || max_points_per_example <= FPS_LDS_MAX) return 0;
+    return (size_t)B * (size_t)max_points_per_example * sizeof(float4);
+}
+
+extern "C" int gn_fps_nested_ws(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
+                                int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *ws, size_t ws_bytes,
+                                void *stream) {
+    GN_REQUIRE(B >= 0 && max_points_per_example >= 0, "gn_fps: bad sizes");
+    GN_REQUIRE(nested_gap == nullptr || start_idx == nullptr, "gn_fps_nested: a nested sample starts at the example's first point (start_idx must be NULL)");
+    const int n = max_points_per_example;
+    if (B == 0 || n == 0 || n <= FPS_LDS_MAX)
+        return gn_fps_nested(pos, ptr, out_ptr, start_idx, B, n, out_idx, gap_out, nested_gap, stream);
+    const size_t need = gn_fps_workspace_bytes(B, n);
+    GN_REQUIRE(ws != nullptr && ws_bytes >= need, "gn_fps_nested_ws: %d points per example need a workspace of %zu bytes (gn_fps_workspace_bytes), got %zu",
+               n, need, ws ? ws_bytes : (size_t)0);
+    GN_REQUIRE(((uintptr_t)ws & 15) == 0, "gn_fps_nested_ws: the workspace must be 16-byte aligned");
+    hipLaunchKernelGGL(fps_ws_kernel, dim3(B), dim3(FPS_THREADS), 0, gn_stream(stream), pos, ptr, out_ptr, start_idx, out_idx, gap_out, nested_gap,
+                       reinterpret_cast<float4 *>(ws), n);
     GN_LAUNCH_CHECK("gn_fps");
     return GN_OK;
 }
@@ -570,7 +647,7 @@ __global__ __launch_bounds__(256) void knn_interp_kernel(const float *__restrict
 
 extern "C" int gn_knn_interpolate(const float *xs, int ldx, const float *ps, const int32_t *ptr_s, const float *pq,
                                   const int32_t *ptr_q, int B, int Nq, int C, int k, float *out, int ldo, void *stream) {
-    GN_REQUIRE(k >= 1 && k <= KNN_MAXK, "gn_knn_interpolate: k must be in [1,%d]", KNN_MAXK);
+    GN_REQUIRE(k >= 1 && k <= KNN_MAXK, "gn_knn_interpolate: k must be in [1,%d] (gn_knn_interpolate_any takes any k)", KNN_MAXK);
     GN_REQUIRE(B >= 0 && Nq >= 0 && C > 0, "gn_knn_interpolate: bad sizes");
     if (Nq == 0) return GN_OK;
     dim3 grid((unsigned)gn_cdiv(Nq, 4)), block(256);
@@ -587,6 +664,66 @@ extern "C" int gn_knn_interpolate(const float *xs, int ldx, const float *ps, con
     }
 #undef KNN_LAUNCH
     GN_LAUNCH_CHECK("gn_knn_interpolate");
+    return GN_OK;
+}
+
+// Any k (the k > 8 that knn_interp_kernel's register lists do not hold): one wavefront per query and one pass per neighbour.  Pass r finds the smallest
+// (d2, index) key strictly greater than pass r-1's -- the oracle's ascending (d2, index) order, O(k n) distance evaluations, nothing stored per query --
+// and adds that neighbour's weight to the running sum and its weighted features to the output row at once (each lane owns its channels of the row: the
+// sums run in the oracle's order, neighbour by neighbour).  An example with fewer than k sources stops when a pass finds none: all of them are used.
+__global__ __launch_bounds__(256) void knn_interp_any_kernel(const float *__restrict__ xs, int ldx, const float *__restrict__ ps,
+                                                             const int32_t *__restrict__ ptr_s, const float *__restrict__ pq,
+                                                             const int32_t *__restrict__ ptr_q, int B, int Nq, int C, int k,
+                                                             float *__restrict__ out, int ldo) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (q >= Nq) return;
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        int mid = (lo + hi) >> 1;
+        if (ptr_q[mid] <= q) lo = mid; else hi = mid;
+    }
+    const int s = ptr_s[lo], e = ptr_s[lo + 1];
+    const float qx = pq[3 * (size_t)q], qy = pq[3 * (size_t)q + 1], qz = pq[3 * (size_t)q + 2];
+    float *o = out + (size_t)q * ldo;
+    for (int ch = lane; ch < C; ch += 64) o[ch] = 0.f;
+    float pd = -1.f;                               // the previous pass's key (d2 >= 0 > -1: the first pass takes any source)
+    int pj = -1;
+    float wsum = 0.f;
+    for (int r = 0; r < k; ++r) {
+        float v = 3.4e38f;
+        int i = INT_MAX;
+        for (int j = s + lane; j < e; j += 64) {
+            const float d = gn_sqdist3(ps[3 * (size_t)j], ps[3 * (size_t)j + 1], ps[3 * (size_t)j + 2], qx, qy, qz);
+            // j ascends within a lane: strict '<' keeps the lower index among equal distances
+            if ((d > pd || (d == pd && j > pj)) && d < v) { v = d; i = j; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(v, off);
+            const int oi = __shfl_xor(i, off);
+            if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+        }
+        if (i == INT_MAX) break;                   // fewer than k sources
+        pd = v;
+        pj = i;
+        const float w = __fdiv_rn(1.0f, v < 1e-16f ? 1e-16f : v);
+        wsum = __fadd_rn(wsum, w);
+        const float *xr = xs + (size_t)i * ldx;
+        for (int ch = lane; ch < C; ch += 64) o[ch] = __fadd_rn(o[ch], __fmul_rn(xr[ch], w));
+    }
+    for (int ch = lane; ch < C; ch += 64) o[ch] = __fdiv_rn(o[ch], wsum);
+}
+
+extern "C" int gn_knn_interpolate_any(const float *xs, int ldx, const float *ps, const int32_t *ptr_s, const float *pq,
+                                      const int32_t *ptr_q, int B, int Nq, int C, int k, float *out, int ldo, void *stream) {
+    GN_REQUIRE(k >= 1, "gn_knn_interpolate_any: k must be >= 1");
+    GN_REQUIRE(B >= 0 && Nq >= 0 && C > 0, "gn_knn_interpolate_any: bad sizes");
+    if (Nq == 0) return GN_OK;
+    if (k <= KNN_MAXK) return gn_knn_interpolate(xs, ldx, ps, ptr_s, pq, ptr_q, B, Nq, C, k, out, ldo, stream);
+    hipLaunchKernelGGL(knn_interp_any_kernel, dim3((unsigned)gn_cdiv(Nq, 4)), dim3(256), 0, gn_stream(stream), xs, ldx, ps, ptr_s, pq, ptr_q, B, Nq, C, k,
+                       out, ldo);
+    GN_LAUNCH_CHECK("gn_knn_interpolate_any");
     return GN_OK;
 }
 

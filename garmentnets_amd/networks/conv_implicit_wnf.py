@@ -17,13 +17,20 @@ from .. import arith as AR
 from .. import ops
 from ..batch import Batch
 from ..components.mlp import MLP, PackedModule, fold_batchnorm, param_cache
-from ..components.unet3d import Abstract3DUNet, DoubleConv, to_channel_last
+from ..components.unet3d import Abstract3DUNet, DoubleConv, stored_channels, stored_volume, to_channel_last
 from ..components.pointnet2 import Segments
 from .pointnet2_nocs import PointNet2NOCS
 
 
+def agg_stored_channels(c):
+    """the stored width of the scattered volume with c real channels: c when the first convolution reads it as it is (a multiple of 16), else
+    rounded up as the UNet stores its activations (components/unet3d.py stored_channels), the pads exact zeros"""
+    return int(c) if int(c) % 16 == 0 else stored_channels(c)
+
+
 class VolumeFeatureAggregator(nn.Module):
-    """per-point MLP -> scatter (max | mean) into a (B,C,G,G,G) volume -- conv_implicit_wnf.py:23-100."""
+    """per-point MLP -> scatter (any torch_scatter reduction: max | mean | sum | add | min | mul) into a (B,C,G,G,G) volume -- conv_implicit_wnf.py:23-100.
+    Empty cells hold what torch_scatter 2.0.8 leaves there: 0, and 1 under 'mul'."""
 
     def __init__(self, nn_channels=[1024, 1024, 128], batch_norm=True, lower_corner=(0, 0, 0), upper_corner=(1, 1, 1),
                  grid_shape=(32, 32, 32), reduce_method="mean", include_point_feature=True, include_confidence_feature=False):
@@ -32,6 +39,8 @@ class VolumeFeatureAggregator(nn.Module):
         self.lower_corner = tuple(lower_corner)
         self.upper_corner = tuple(upper_corner)
         self.grid_shape = tuple(grid_shape)
+        if reduce_method not in ops.REDUCE_CODES:
+            raise ValueError(f"VolumeFeatureAggregator: reduce_method={reduce_method!r} is not a torch_scatter reduction ({sorted(ops.REDUCE_CODES)})")
         self.reduce_method = reduce_method
         self.include_point_feature = include_point_feature
         self.include_confidence_feature = include_confidence_feature
@@ -46,6 +55,7 @@ class VolumeFeatureAggregator(nn.Module):
         C = self.local_nn[-1][0].out_features if self.local_nn is not None else None
         if C is None:
             return
+        C = agg_stored_channels(C)
         dev = _normalise_device(device)
         state = _THREAD_STATE.of(self)
         pre = state.get("prezero")
@@ -78,6 +88,12 @@ class VolumeFeatureAggregator(nn.Module):
                                         self.include_point_feature, self.include_confidence_feature)
         if self.local_nn is not None:
             feats = self.local_nn(feats)
+        C = feats.shape[1]
+        Cs = agg_stored_channels(C)
+        if Cs != C:                                   # channel-padded rows: zeros on the pads, which every reduction keeps at zero
+            padded = torch.zeros((feats.shape[0], Cs), dtype=torch.float32, device=feats.device)
+            padded[:, :C] = feats
+            feats = padded
         pre = _THREAD_STATE.of(self).pop("prezero", None)
         prezeroed = None
         if pre is not None and torch.cuda.is_current_stream_capturing():
@@ -88,10 +104,19 @@ class VolumeFeatureAggregator(nn.Module):
             pre[1].record_stream(cur)                 # filled on the side stream, consumed (and outlived) by work on this one: the allocator
             pre[2].record_stream(cur)                 # must not hand the block to the side stream's NEXT fill while that work is in flight
             prezeroed = (pre[1], pre[2])
-        vol, stats = ops.grid_scatter(feats, flat, B, self.grid_shape, self.reduce_method, with_stats=True, prezeroed=prezeroed)   # [B][G][G][G][C]
-        out = vol.permute(0, 4, 1, 2, 3)
-        out._gn_stats = stats      # GroupNorm statistics of the (mostly empty) volume, from its occupied cells only
-        out._gn_flat = flat        # the occupied cells: the first UNet convolution only visits the tiles that can see one
+        if self.reduce_method == "mul":
+            # a 'mul' volume is 1 wherever no point landed: no statistics from the occupied cells alone and no occupancy-aware convolution behind it
+            # (both assume empty cells are 0) -- the UNet takes the dense launch with whole-volume statistics
+            vol = ops.grid_scatter(feats, flat, B, self.grid_shape, "mul", prezeroed=prezeroed, c_real=C)
+            stats = flat = None
+        else:
+            vol, stats = ops.grid_scatter(feats, flat, B, self.grid_shape, self.reduce_method, with_stats=True, prezeroed=prezeroed, c_real=C)   # [B][G][G][G][Cs]
+        out = vol.permute(0, 4, 1, 2, 3) if Cs == C else vol[..., :C].permute(0, 4, 1, 2, 3)
+        if Cs != C:
+            out._gn_stored = vol   # the channel-padded storage: the UNet reads it without a copy
+        if stats is not None:
+            out._gn_stats = stats  # GroupNorm statistics of the (mostly empty) volume, from its occupied cells only
+            out._gn_flat = flat    # the occupied cells: the first UNet convolution only visits the tiles that can see one
         return out
 
 
@@ -462,7 +487,7 @@ class ConvImplicitWNFPipeline(nn.Module):
         arith = arith or self.arith
         in_feature_volume = self.volume_agg(pointnet2_result["nocs_data"])
         net = self.unet_3d.abstract_3d_unet
-        pre, st = net.run(to_channel_last(in_feature_volume), getattr(in_feature_volume, "_gn_stats", None), pre_final=True, return_stats=True,
+        pre, st = net.run(stored_volume(in_feature_volume), getattr(in_feature_volume, "_gn_stats", None), pre_final=True, return_stats=True,
                           sparse_flat=getattr(in_feature_volume, "_gn_flat", None), arith=arith)
         return UNetResult(pre, net.final_conv, st)   # ['out_feature_volume'] materialises the reference's tensor on demand
 

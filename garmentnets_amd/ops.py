@@ -89,7 +89,17 @@ def fps(pos, ptr, out_ptr, max_points, m_total, start_idx=None, gap_out=None, ne
     gets the prefix 0..m-1 of every example whose first-level running maximum stayed positive -- the same indices without the serial steps."""
     _chk(pos, torch.float32, "pos")
     idx = torch.empty(m_total, dtype=_i32, device=pos.device)
-    if gap_out is None and nested_gap is None:
+    B = ptr.numel() - 1
+    nbytes = _lib.load().gn_fps_workspace_bytes(B, int(max_points))
+    if nbytes:
+        # more points per example than the LDS-resident kernels hold: running distances in a device workspace (gn_fps_nested_ws)
+        for t, name in ((gap_out, "gap_out"), (nested_gap, "nested_gap")):
+            if t is not None:
+                _chk(t, torch.float32, name)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
+        _lib.call("gn_fps_nested_ws", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), B, int(max_points), _p(idx), _p(gap_out), _p(nested_gap),
+                  _p(ws), nbytes, _stream())
+    elif gap_out is None and nested_gap is None:
         _lib.call("gn_fps", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), ptr.numel() - 1, int(max_points), _p(idx), _stream())
     else:
         if gap_out is not None:
@@ -188,12 +198,16 @@ def global_max_pool(h, ptr, B):
     return out
 
 
+KNN_MAXK = 8          # gn_knn_interpolate's largest k
+
+
 def knn_interpolate(xs, ps, ptr_s, pq, ptr_q, k, out=None):
     Nq, C = pq.shape[0], xs.shape[1]
     if out is None:
         out = new_rows(Nq, C, xs.device)
-    _lib.call("gn_knn_interpolate", _p(xs), rows_view(xs)[1], _p(ps), _p(ptr_s), _p(pq), _p(ptr_q), ptr_s.numel() - 1, Nq, C,
-              int(k), _p(out), rows_view(out)[1], _stream())
+    # k <= 8: the register-list kernel; larger k: one pass per neighbour (gn_knn_interpolate_any)
+    _lib.call("gn_knn_interpolate" if int(k) <= KNN_MAXK else "gn_knn_interpolate_any", _p(xs), rows_view(xs)[1], _p(ps), _p(ptr_s), _p(pq), _p(ptr_q),
+              ptr_s.numel() - 1, Nq, C, int(k), _p(out), rows_view(out)[1], _stream())
     return out
 
 
@@ -247,10 +261,19 @@ def zeroed_volume(B, grid_shape, C, device):
     return vol, cnt
 
 
-def grid_scatter(src, flat_idx, B, grid_shape, reduce, with_stats=False, prezeroed=None):
+# torch_scatter.scatter's reductions (networks/conv_implicit_wnf.py:92-94) -> gn_grid_scatter's reduce codes
+REDUCE_CODES = {"max": 0, "mean": 1, "sum": 2, "add": 2, "min": 3, "mul": 4}
+
+
+def grid_scatter(src, flat_idx, B, grid_shape, reduce, with_stats=False, prezeroed=None, c_real=None):
     """-> channel-last volume [B][G0][G1][G2][C] (and its per-channel statistics, from the occupied cells only).
-    prezeroed: (vol, cnt) from zeroed_volume that the caller has already ordered before this call"""
+    prezeroed: (vol, cnt) from zeroed_volume that the caller has already ordered before this call.
+    c_real: channels [c_real, C) of src are pads (zeros): they stay 0 in every cell, also under 'mul', whose empty cells are 1 elsewhere"""
     N, C = src.shape
+    if reduce not in REDUCE_CODES:
+        raise ValueError(f"grid_scatter: reduce={reduce!r} is not one of {sorted(REDUCE_CODES)}")
+    if with_stats and reduce == "mul":
+        raise ValueError("grid_scatter: the occupied-cell statistics assume empty cells are 0, which 'mul' leaves at 1")
     cps = int(np.prod(grid_shape))
     cells = B * cps
     if prezeroed is not None:
@@ -259,11 +282,11 @@ def grid_scatter(src, flat_idx, B, grid_shape, reduce, with_stats=False, prezero
     else:
         vol = torch.empty((B,) + tuple(grid_shape) + (C,), dtype=torch.float32, device=src.device)
         cnt = torch.empty(cells, dtype=_i32, device=src.device)
-    code = {"max": 0, "mean": 1}[reduce]
+    code = REDUCE_CODES[reduce]
     nbytes = _lib.load().gn_grid_scatter_workspace_bytes(N, C, code)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if nbytes else None
-    _lib.call("gn_grid_scatter", _p(src), rows_view(src)[1], _p(flat_idx), N, C, cells, code, _p(vol), _p(cnt), _p(ws), nbytes,
-              0 if prezeroed is None else 1, _stream())
+    _lib.call("gn_grid_scatter_ex", _p(src), rows_view(src)[1], _p(flat_idx), N, C, C if c_real is None else int(c_real), cells, code, _p(vol), _p(cnt),
+              _p(ws), nbytes, 0 if prezeroed is None else 1, _stream())
     if not with_stats:
         return vol
     s, q = _stats_buffers(B, C, src.device, True)

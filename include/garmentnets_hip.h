@@ -67,6 +67,13 @@ int gn_fps(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const i
  *            the others (duplicate-ridden clouds) are sampled as gn_fps samples them.  Same output as gn_fps, bit for bit, either way. */
 int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
                   int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *stream);
+/* gn_fps and gn_fps_nested take at most 36 864 points per example.  gn_fps_nested_ws takes any number: an example of more points keeps its
+ * running distances in `ws`, one 16-byte record (x, y, z, d) per point, gn_fps_workspace_bytes(B, max_points_per_example) bytes (0 up to
+ * 36 864 points: ws may then be NULL), 16-byte aligned.  Same arguments and the same output as gn_fps_nested otherwise, bit for bit. */
+size_t gn_fps_workspace_bytes(int B, int max_points_per_example);
+int gn_fps_nested_ws(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
+                     int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *ws, size_t ws_bytes,
+                     void *stream);
 
 /* Ball query.  replaces torch_cluster.radius(max_num_neighbors=K) -- components/pointnet2.py:28-29.
  * For every centre c (a point index centre_idx[c], example b): the first K points j of example b in ascending
@@ -118,6 +125,10 @@ int gn_global_max_pool(const float *in, int ldi, const int32_t *ptr, int B, int 
  * k <= 8; neighbours ordered by ascending (d2, index); w = 1/max(d2,1e-16); out = sum(w x)/sum(w). */
 int gn_knn_interpolate(const float *xs, int ldx, const float *ps, const int32_t *ptr_s, const float *pq,
                        const int32_t *ptr_q, int B, int Nq, int C, int k, float *out, int ldo, void *stream);
+/* The same for any k >= 1 (k <= 8: gn_knn_interpolate itself).  One pass per neighbour over the example's sources, in ascending (d2, index);
+ * an example with fewer than k sources uses all of them. */
+int gn_knn_interpolate_any(const float *xs, int ldx, const float *ps, const int32_t *ptr_s, const float *pq,
+                           const int32_t *ptr_q, int B, int Nq, int C, int k, float *out, int ldo, void *stream);
 
 /* Dense layer:  Y = bn( act( X W^T + bias ) ),  X [M][K] (ldx), W [N][K] (ldw), Y [M][N] (ldy).
  * relu != 0 applies ReLU; bn_scale/bn_shift (may be NULL) apply y*scale[n]+shift[n] AFTER the ReLU
@@ -144,14 +155,21 @@ int gn_grid_features(const float *feat, int ldf, int Cf, const float *nocs, cons
                      int include_point, int include_conf, float *out, int ldo, int32_t *flat_idx, void *stream);
 
 /* Scatter point features into a zero-filled channel-last volume.  replaces torch_scatter.scatter(reduce) --
- * networks/conv_implicit_wnf.py:92-94.  reduce: 0 = max, 1 = mean.  vol [cells][C] must be zeroed by this
- * call (it does the memset); count_ws: [cells] int32 workspace.  Empty cells stay 0.  Both reductions are
- * deterministic (run-to-run bit-identical): max by construction, mean through order-independent fp64 partial sums
- * kept in `ws` (gn_grid_scatter_workspace_bytes(N, C, reduce) bytes; 0 / NULL for max).  vol_is_zeroed != 0: the caller has already
- * zero-filled vol and count_ws (e.g. on a side stream, overlapped with the serial FPS kernels) and the memsets are skipped. */
+ * networks/conv_implicit_wnf.py:92-94.  reduce: 0 = max, 1 = mean, 2 = sum (torch_scatter's 'sum' and 'add'), 3 = min, 4 = mul.
+ * vol [cells][C] is filled by this call (it does the memset); count_ws: [cells] int32 workspace, left zeroed.  Empty cells hold
+ * the torch_scatter 2.0.8 value: 0 for max / mean / sum / min, 1 for mul.  Every reduction is deterministic (run-to-run
+ * bit-identical): max / min by construction (atomicMax on an order-preserving encoding, bit-inverted for min), mean / sum
+ * through order-independent fp64 partial sums, mul as a sequential fp32 product in ascending point index; the workspace `ws`
+ * holds gn_grid_scatter_workspace_bytes(N, C, reduce) bytes (0 / NULL for max and min).  vol_is_zeroed != 0: the caller has already
+ * zero-filled vol and count_ws (e.g. on a side stream, overlapped with the serial FPS kernels) and the memsets are skipped (mul
+ * still writes its identity into every cell). */
 size_t gn_grid_scatter_workspace_bytes(int64_t N, int C, int reduce);
 int gn_grid_scatter(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int64_t cells, int reduce,
                     float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream);
+/* gn_grid_scatter over channel-padded rows: channels [c_real, C) are pads (src holds zeros there), which mul's identity fill leaves at 0, so
+ * the pads of every cell hold exact zeros under every reduction.  gn_grid_scatter = gn_grid_scatter_ex with c_real = C. */
+int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int c_real, int64_t cells, int reduce,
+                       float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream);
 
 /* Output tiles (4 x 8 x 8 voxels, the tiling of gn_conv3d_gcr_split) of a 3x3x3 convolution over the scattered volume that can see an
  * occupied cell: flags [B][tiles_y * tiles_x * tiles_z] bytes (zeroed inside), index (ty * tiles_x + tx) * tiles_z + tz.  reach = 1 for the
