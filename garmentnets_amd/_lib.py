@@ -89,8 +89,27 @@ PROTOTYPES = {
     "gn_nearest_neighbor": [_vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "gn_nearest_neighbor_f64_batch": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "gn_point_mesh_sqdist_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "gn_nocs_bin_metrics_workspace_bytes": [_vp, _i32],
+    "gn_nocs_bin_metrics": [_vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
+    "gn_value_losses_workspace_bytes": [_vp, _i32],
+    "gn_value_losses": [_vp, _i32, _vp, _sz, _vp, _vp],
 }
-_RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz}
+_RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
+             "gn_nocs_bin_metrics_workspace_bytes": _sz, "gn_value_losses_workspace_bytes": _sz}
+
+LOSS_MAX_SETS = 8                               # GN_LOSS_MAX_SETS
+LOSS_KINDS = {"l2": 0, "smooth_l1": 1, "bce_logits": 2, "row_norm": 3}
+
+
+class NocsBinSet(ctypes.Structure):
+    """GnNocsBinSet (host table entry of gn_nocs_bin_metrics)"""
+    _fields_ = [("logits", _vp), ("gt", _vp), ("n", _i64), ("ldl", _i32), ("pad", _i32)]
+
+
+class LossSegment(ctypes.Structure):
+    """GnLossSegment (host table entry of gn_value_losses)"""
+    _fields_ = [("pred", _vp), ("target", _vp), ("count", _i64), ("kind", _i32), ("mirror", _i32)]
+
 
 _lib = None
 

@@ -11,7 +11,10 @@ data module does to pick the samples of a subset (prepare_data 478-529), re-buil
   visible_points     view sub-sampling as index arithmetic (np.repeat owner table + np.isin), no per-view loop.
   FIELD tables       which stored arrays feed which output fields, and which fields a rotation touches, as data.
 
-Training-only targets (volume / surface / marching-cubes-surface query sampling) are not on the inference path and are not here.
+The training / validation targets (get_volume_sample 231-281, get_surface_sample 283-334, get_mc_surface_sample 336-368) are drawn when
+their sample counts are > 0 (all 0 by default: the inference samples above are unchanged), with the same random contract: each stage a
+fresh RandomState(idx if static_epoch_seed else None), in the reference's order [volume]; [surface]; [mc surface] between the base data and the
+noise.  Their fields come out (1, M), (1, M, 3) and (1, M, 1) per sample, (B, M, ...) after collate(), as PyG batches them.
 Stores are read through garmentnets_amd.io.zarr_store (Zarr v2; uncompressed / zlib natively, anything else through numcodecs
 when that package is importable).
 """
@@ -20,6 +23,7 @@ import torch
 from scipy.spatial.transform import Rotation
 
 from ..batch import Batch
+from ..common.metrics import barycentric_interpolation, mesh_sample_barycentric
 from . import zarr_store
 
 # stored array (group, name) -> key of the raw sample dict
@@ -41,6 +45,10 @@ TASK_SPACE_SIM_FIELDS = ("pos", "sim_grip_point")
 TASK_SPACE_QUERY_FIELDS = ("volume_query_points", "surf_query_points")
 TASK_SPACE_PIVOT = np.array([0.5, 0.5, 0.0], dtype=np.float32)
 SUBSETS = ("train", "val", "test")
+# the target fields of the three samplers, float32 after collate()
+TARGET_FIELDS = ("volume_query_points", "gt_volume_value", "surf_query_points", "gt_sim_points", "mc_surf_query_points", "is_query_point_on_surf")
+# the volume group whose queries live in task space (the reference's dataset derives volume_task_space from it)
+TASK_SPACE_VOLUME_GROUP = "sim_nocs_winding_number_field"
 
 
 class SeededDraws:
@@ -85,6 +93,129 @@ def data_io(sample_group):
     attrs = sample_group.attrs
     raw.update({k: attrs[k] for k in RAW_ATTRS})
     return raw
+
+
+def read_volume(sample_group, volume_group="nocs_winding_number_field", volume_size=128, tsdf_clip_value=None, volume_absolute_value=False):
+    """samples/<key>/volume/<volume_group>/<volume_size> -> (1, 1, D, H, W) float32 (data_io: 163-179): divided by tsdf_clip_value and clipped
+    to [-1, 1] when that is set, then absolute values when volume_absolute_value"""
+    volume = np.expand_dims(sample_group["volume"][volume_group][str(volume_size)][:], (0, 1)).astype(np.float32)
+    if tsdf_clip_value is not None:
+        volume = np.clip(volume / tsdf_clip_value, -1, 1)
+    if volume_absolute_value:
+        volume = np.abs(volume)
+    return volume
+
+
+def read_mc_mesh(sample_group):
+    """the marching-cubes mesh of a sample and its per-vertex on-surface flags (data_io: 156-161)"""
+    g = sample_group["marching_cube_mesh"]
+    return {k: g[k][:] for k in ("marching_cube_verts", "marching_cube_faces", "is_vertex_on_surface")}
+
+
+def nocs_grid_sample(volume, query_points):
+    """trilinear sample of a (D, H, W) volume (any leading 1-axes) at (M, 3) points of the unit cube -> (M,) float32: the reference's
+    nocs_grid_sample (components/gridding.py:45-98) = grid_sample(align_corners=True, padding_mode='border') with the zyx flip, i.e. point
+    (x, y, z) reads volume[x * (D-1), y * (H-1), z * (W-1)].  fp32 in ATen's CPU order: coordinate ((2q - 1) + 1) / 2 * (size - 1) clipped
+    to [0, size - 1]; corner weight (w_W * w_H) * w_D; the eight corners added to 0 in (D, H, W) bit order, those past the far face skipped."""
+    vol = np.asarray(volume, dtype=np.float32)
+    vol = vol.reshape(vol.shape[-3:])
+    q = np.asarray(query_points, dtype=np.float32)
+    one, two = np.float32(1), np.float32(2)
+    lo, frac = [], []
+    for ax in range(3):
+        n = vol.shape[ax]
+        c = np.minimum(np.float32(n - 1), np.maximum((((two * q[:, ax] - one) + one) / two) * np.float32(n - 1), np.float32(0)))
+        f0 = np.floor(c)
+        lo.append(f0)
+        frac.append(((f0 + one) - c, c - f0))                                # weights of the low and the high corner
+    out = np.zeros(len(q), dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        for corner in range(8):
+            bit = [(corner >> 2) & 1, (corner >> 1) & 1, corner & 1]
+            w = (frac[2][bit[2]] * frac[1][bit[1]]) * frac[0][bit[0]]
+            idx = [lo[ax] + np.float32(bit[ax]) for ax in range(3)]
+            inb = np.ones(len(q), dtype=bool)
+            for ax in range(3):
+                inb &= (idx[ax] >= 0) & (idx[ax] <= vol.shape[ax] - 1)
+            ii = [np.where(inb, idx[ax], 0).astype(np.int64) for ax in range(3)]
+            out = np.where(inb, out + vol[ii[0], ii[1], ii[2]] * w, out)
+    return out
+
+
+class AABBGripNormalizer:
+    """task-space normaliser (common/geometry_util.py:100-123): the simulation-space box (2, 3) into the unit NOCS cube, x / y centred on 0.5,
+    the top of z at 1 - padding; the same numpy operations in the same order"""
+
+    def __init__(self, aabb, padding=0.05):
+        nocs_radius = 0.5 - padding
+        radius = np.max(np.abs(aabb), axis=0)[:2]
+        radius_scale = np.min(nocs_radius / radius)
+        z_scale = (nocs_radius * 2) / (aabb[1, 2] - aabb[0, 2])
+        self.scale = min(radius_scale, z_scale)
+        self.offset = np.array([0.5, 0.5, 1 - padding - aabb[1, 2] * self.scale], dtype=aabb.dtype)
+
+    def __call__(self, data):
+        return (data * self.scale) + self.offset
+
+
+def _for_batching(data):
+    return {k: v.reshape((1,) + v.shape) for k, v in data.items()}
+
+
+def get_volume_sample(idx, data_in, volume, num_volume_sample, surface_sample_ratio=0, surface_sample_std=0.05, static_epoch_seed=False,
+                      volume_group="nocs_winding_number_field"):
+    """volume query points and the volume's values there (get_volume_sample: 231-281).  surface_sample_ratio == 0: uniform points of the unit
+    cube; otherwise int(num_volume_sample * surface_sample_ratio) UNIFORM points (the reference sizes the uniform part by the ratio) followed
+    by points of the NOCS mesh plus N(0, surface_sample_std) noise, all clipped to [0, 1].  Occupancy grids threshold the value at > 0.1."""
+    draws = SeededDraws(idx, static_epoch_seed)
+    rs = draws.fresh()
+    if surface_sample_ratio == 0:
+        query = rs.uniform(low=0, high=1, size=(num_volume_sample, 3)).astype(np.float32)
+    else:
+        n_uniform = int(num_volume_sample * surface_sample_ratio)
+        n_surface = num_volume_sample - n_uniform
+        uniform = rs.uniform(low=0, high=1, size=(n_uniform, 3)).astype(np.float32)
+        verts, faces = data_in["cloth_nocs_verts"], data_in["cloth_faces_tri"]
+        bc, face_idx = mesh_sample_barycentric(verts, faces, n_surface, seed=draws.seed)
+        on_mesh = barycentric_interpolation(bc, verts, faces[face_idx])
+        noise = rs.normal(loc=(0,) * 3, scale=(surface_sample_std,) * 3, size=(n_surface, 3))
+        query = np.clip(np.concatenate([uniform, on_mesh + noise], axis=0).astype(np.float32), 0, 1)
+    values = nocs_grid_sample(volume, query)
+    if volume_group == "nocs_occupancy_grid":
+        values = (values > 0.1).astype(np.float32)
+    return _for_batching({"volume_query_points": query, "gt_volume_value": values})
+
+
+def check_surface_normal_noise(surface_normal_noise_ratio):
+    if surface_normal_noise_ratio != 0:
+        raise NotImplementedError("surface_normal_noise_ratio != 0 needs libigl's per-vertex normals, which this package does not carry "
+                                  "(the shipped configs set surface_normal_noise_ratio: 0)")
+
+
+def get_surface_sample(idx, data_in, num_surface_sample, static_epoch_seed=False, volume_task_space=False, cloth_sim_aabb=None,
+                       surface_normal_noise_ratio=0):
+    """points of the garment mesh in the decoder's query space and their simulation-space positions (get_surface_sample: 283-334); in
+    task space the roles swap: queries are the AABBGripNormalizer'd simulation vertices' points, targets the NOCS ones"""
+    check_surface_normal_noise(surface_normal_noise_ratio)
+    nocs_verts, sim_verts, faces = data_in["cloth_nocs_verts"], data_in["cloth_sim_verts"], data_in["cloth_faces_tri"]
+    if volume_task_space:
+        nocs_verts, sim_verts = AABBGripNormalizer(cloth_sim_aabb)(sim_verts), nocs_verts
+    bc, face_idx = mesh_sample_barycentric(nocs_verts, faces, num_surface_sample, seed=SeededDraws(idx, static_epoch_seed).seed)
+    sampled_faces = faces[face_idx]
+    return _for_batching({"surf_query_points": barycentric_interpolation(bc, nocs_verts, sampled_faces),
+                          "gt_sim_points": barycentric_interpolation(bc, sim_verts, sampled_faces)})
+
+
+def get_mc_surface_sample(idx, data_in, num_surface_sample, static_epoch_seed=False):
+    """points of the marching-cubes mesh and whether each lies on the garment's surface (get_mc_surface_sample: 336-368): the interpolated
+    per-vertex flag > 0.5.  The reference draws num_surface_sample points here, not num_mc_surface_sample; so does this."""
+    verts, faces = data_in["marching_cube_verts"], data_in["marching_cube_faces"]
+    flags = np.expand_dims(data_in["is_vertex_on_surface"].astype(np.float32), axis=-1)
+    bc, face_idx = mesh_sample_barycentric(verts, faces, num_surface_sample, seed=SeededDraws(idx, static_epoch_seed).seed)
+    sampled_faces = faces[face_idx]
+    on_surface = barycentric_interpolation(bc, flags, sampled_faces)
+    return _for_batching({"mc_surf_query_points": barycentric_interpolation(bc, verts, sampled_faces),
+                          "is_query_point_on_surf": (on_surface > 0.5).astype(np.float32)})
 
 
 def get_base_data(idx, data_in, num_pc_sample=6000, num_views=4, static_epoch_seed=False, cloth_sim_aabb=None):
@@ -154,9 +285,22 @@ class GarmentInputDataset:
     dataset indices predict iterates for ``prediction.subset = name``."""
 
     def __init__(self, zarr_path, num_pc_sample=6000, enable_augumentation=True, random_rot_range=(-90, 90), num_views=4,
-                 pc_noise_std=0, static_epoch_seed=False, volume_task_space=False, dataset_split=(8, 1, 1), split_seed=0, **kwargs):
+                 pc_noise_std=0, static_epoch_seed=False, volume_task_space=False, dataset_split=(8, 1, 1), split_seed=0,
+                 num_volume_sample=0, num_surface_sample=0, num_mc_surface_sample=0, surface_sample_ratio=0, surface_sample_std=0.05,
+                 surface_normal_noise_ratio=0, surface_normal_std=0, volume_size=128, volume_group="nocs_winding_number_field",
+                 tsdf_clip_value=None, volume_absolute_value=False, **kwargs):
         if num_views <= 0:
             raise AssertionError("num_views > 0")
+        if num_surface_sample > 0:
+            check_surface_normal_noise(surface_normal_noise_ratio)
+        if volume_group == TASK_SPACE_VOLUME_GROUP:
+            volume_task_space = True
+            if num_mc_surface_sample != 0:
+                raise AssertionError("num_mc_surface_sample must be 0 for task-space volumes")
+        self.num_volume_sample, self.num_surface_sample, self.num_mc_surface_sample = num_volume_sample, num_surface_sample, num_mc_surface_sample
+        self.surface_sample_ratio, self.surface_sample_std = surface_sample_ratio, surface_sample_std
+        self.surface_normal_noise_ratio, self.surface_normal_std = surface_normal_noise_ratio, surface_normal_std
+        self.volume_size, self.volume_group, self.tsdf_clip_value, self.volume_absolute_value = volume_size, volume_group, tsdf_clip_value, volume_absolute_value
         root = zarr_store.open_group(zarr_path, create=False)
         self.samples_group = root["samples"]
         self.keys = sorted(self.samples_group.keys())
@@ -182,8 +326,18 @@ class GarmentInputDataset:
 
     def __getitem__(self, idx):
         idx = int(idx)
-        sample = get_base_data(idx, data_io(self.samples_group[self.keys[idx]]), self.num_pc_sample, self.num_views,
-                               self.static_epoch_seed, self.cloth_sim_aabb)
+        group = self.samples_group[self.keys[idx]]
+        data_in = data_io(group)
+        sample = get_base_data(idx, data_in, self.num_pc_sample, self.num_views, self.static_epoch_seed, self.cloth_sim_aabb)
+        if self.num_volume_sample > 0:
+            volume = read_volume(group, self.volume_group, self.volume_size, self.tsdf_clip_value, self.volume_absolute_value)
+            sample.update(get_volume_sample(idx, data_in, volume, self.num_volume_sample, self.surface_sample_ratio, self.surface_sample_std,
+                                            self.static_epoch_seed, self.volume_group))
+        if self.num_surface_sample > 0:
+            sample.update(get_surface_sample(idx, data_in, self.num_surface_sample, self.static_epoch_seed, self.volume_task_space,
+                                             self.cloth_sim_aabb, self.surface_normal_noise_ratio))
+        if self.num_mc_surface_sample > 0:
+            sample.update(get_mc_surface_sample(idx, {**data_in, **read_mc_mesh(group)}, self.num_surface_sample, self.static_epoch_seed))
         sample["input_aug_rot_mat"] = np.eye(3, dtype=np.float32)[None]
         if self.pc_noise_std > 0:
             sample = noise_augmentation(idx, sample, self.pc_noise_std, self.static_epoch_seed)
@@ -193,9 +347,11 @@ class GarmentInputDataset:
 
     @staticmethod
     def collate(samples):
-        """PyG-style batching: every field concatenated along dim 0, plus the `batch` vector of the per-point fields"""
+        """PyG-style batching: every field concatenated along dim 0, plus the `batch` vector of the per-point fields; the target fields
+        (1, M[, C]) per sample -> (B, M[, C]) float32"""
         sizes = [len(s["pos"]) for s in samples]
         cat = {k: torch.from_numpy(np.concatenate([np.asarray(s[k]) for s in samples], axis=0)) for k in samples[0]}
         cat["pos"], cat["x"] = cat["pos"].float(), cat["x"].float()
+        cat.update({k: cat[k].float() for k in TARGET_FIELDS if k in cat})
         batch = torch.repeat_interleave(torch.arange(len(samples)), torch.tensor(sizes))
         return Batch(sizes=sizes, batch=batch, **cat)

@@ -3,8 +3,8 @@
 Keeps the reference's class names, constructor kwargs, sub-module names (= checkpoint schema: ``pointnet2_nocs``,
 ``volume_agg.local_nn``, ``unet_3d.abstract_3d_unet``, ``volume_decoder.mlp`` ...), stage methods
 (``pointnet2_forward``, ``unet3d_forward``, ``volume_decoder_forward``, ``surface_decoder_forward``,
-``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  Training code
-(:340-452) is out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
+``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  ``validation_metrics`` gives the
+losses of the reference's infer (:405-452); optimisers, training steps and visualisation are out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
 """
 import os
 import threading
@@ -437,7 +437,9 @@ class ConvImplicitWNFPipeline(nn.Module):
                             unet3d_params=dict(unet3d_params), volume_decoder_params=dict(volume_decoder_params),
                             surface_decoder_params=dict(surface_decoder_params),
                             mc_surface_decoder_params=None if mc_surface_decoder_params is None else dict(mc_surface_decoder_params),
-                            mc_surface_loss_weight=mc_surface_loss_weight, volume_task_space=volume_task_space)
+                            mc_surface_loss_weight=mc_surface_loss_weight, volume_task_space=volume_task_space,
+                            learning_rate=learning_rate, loss_type=loss_type, volume_loss_weight=volume_loss_weight,
+                            surface_loss_weight=surface_loss_weight, volume_classification=volume_classification)
         self.pointnet2_nocs = PointNet2NOCS(**pointnet2_params)
         self.volume_agg = VolumeFeatureAggregator(**volume_agg_params)
         self.unet_3d = UNet3D(**unet3d_params)
@@ -448,6 +450,12 @@ class ConvImplicitWNFPipeline(nn.Module):
             self.mc_surface_decoder = ImplicitWNFDecoder(**mc_surface_decoder_params)
         self.volume_task_space = volume_task_space
         self.batch_size = batch_size
+        self.learning_rate = learning_rate
+        self.loss_type = loss_type
+        self.volume_loss_weight = volume_loss_weight
+        self.surface_loss_weight = surface_loss_weight
+        self.mc_surface_loss_weight = mc_surface_loss_weight
+        self.volume_classification = volume_classification
         self.arith = AR.DEFAULT      # this model's arithmetic (an immutable arith.Arith); every stage method also takes arith= per call
 
     # -- checkpoint ------------------------------------------------------------------------------------------
@@ -548,3 +556,34 @@ class ConvImplicitWNFPipeline(nn.Module):
         if self.mc_surface_decoder is not None:
             result["mc_surface_decoder_result"] = self.mc_surface_decoder_forward(u3, data.mc_surf_query_points, arith)
         return result
+
+    # -- validation ------------------------------------------------------------------------------------------
+    LOSS_TYPES = ("l2", "smooth_l1")
+
+    def validation_metrics(self, data, arith=None):
+        """the loss dict of the reference's infer (conv_implicit_wnf.py:405-452) as python floats: volume_loss, surface_loss[, mc_surface_loss
+        when mc_surface_loss_weight > 0] (each its weight times the mean criterion) and loss, their sum.  data: the network input plus the
+        targets io.dataset draws (volume_query_points / gt_volume_value, surf_query_points / gt_sim_points[, mc_surf_query_points /
+        is_query_point_on_surf]).  Criterion: loss_type (l2 = MSE, smooth_l1 with beta 1); the volume takes BCE-with-logits when
+        volume_classification, the mc surface always.  forward() runs the decoders, ONE gn_value_losses launch the three losses."""
+        self._check_loss_type()
+        return self.losses_from(self.forward(data, arith), data)
+
+    def _check_loss_type(self):
+        if self.loss_type not in self.LOSS_TYPES:
+            raise ValueError(f"Invalid loss_type: {self.loss_type!r} (expected one of {self.LOSS_TYPES})")
+
+    def losses_from(self, result, data):
+        """validation_metrics' loss dict from a forward() result dict and the batch's targets"""
+        self._check_loss_type()
+        segs = [(result["volume_decoder_result"]["pred_volume_value"], data.gt_volume_value, "bce_logits" if self.volume_classification else self.loss_type),
+                (result["surface_decoder_result"]["out_features"], data.gt_sim_points, self.loss_type)]
+        names, weights = ["volume_loss", "surface_loss"], [self.volume_loss_weight, self.surface_loss_weight]
+        if self.mc_surface_loss_weight > 0:
+            segs.append((result["mc_surface_decoder_result"]["out_features"], data.is_query_point_on_surf, "bce_logits"))
+            names.append("mc_surface_loss")
+            weights.append(self.mc_surface_loss_weight)
+        sums = ops.value_losses(segs)[:, 0].cpu().tolist()
+        metrics = {k: w * (s / seg[1].numel()) for k, w, s, seg in zip(names, weights, sums, segs)}
+        metrics["loss"] = sum(metrics.values())
+        return metrics

@@ -1,8 +1,9 @@
 """PointNet2NOCS (inference) -- API twin of /root/reference/networks/pointnet2_nocs.py:58-195.
 
 Same constructor kwargs, sub-module names (``sa1_module`` ... ``global_lin2``: the checkpoint schema), ``forward(data)``
-result keys and ``logits_to_nocs`` / ``get_virtual_grid`` helpers; training code (losses, Lightning steps,
-visualisation, :197-448) is out of scope.  All arithmetic runs in HIP kernels (garmentnets_amd.ops).
+result keys and ``logits_to_nocs`` / ``get_virtual_grid`` helpers, and ``validation_metrics`` (the metric dict of the
+reference's ``infer``, :257-440, without its logging).  Optimisers, training steps and visualisation are out of scope.  All
+arithmetic runs in HIP kernels (garmentnets_amd.ops).
 """
 import torch
 from torch import nn
@@ -20,7 +21,8 @@ class PointNet2NOCS(nn.Module):
         super().__init__()
         self.hparams = dict(feature_dim=feature_dim, batch_norm=batch_norm, dropout=dropout, sa1_ratio=sa1_ratio, sa1_r=sa1_r,
                             sa2_ratio=sa2_ratio, sa2_r=sa2_r, fp3_k=fp3_k, fp2_k=fp2_k, fp1_k=fp1_k, symmetry_axis=symmetry_axis,
-                            nocs_bins=nocs_bins)
+                            nocs_bins=nocs_bins, learning_rate=learning_rate, nocs_loss_weight=nocs_loss_weight,
+                            grip_point_loss_weight=grip_point_loss_weight)
         self.sa1_module = SAModule(sa1_ratio, sa1_r, MLP([3 + 3, 64, 64, 128], batch_norm=batch_norm))
         self.sa2_module = SAModule(sa2_ratio, sa2_r, MLP([128 + 3, 128, 128, 256], batch_norm=batch_norm))
         self.sa3_module = GlobalSAModule(nn=MLP([256 + 3, 256, 512, 1024], batch_norm=batch_norm))
@@ -36,6 +38,22 @@ class PointNet2NOCS(nn.Module):
         self.nocs_bins = nocs_bins
         self.symmetry_axis = symmetry_axis
         self.batch_size = batch_size
+        self.learning_rate = learning_rate
+        self.nocs_loss_weight = nocs_loss_weight
+        self.grip_point_loss_weight = grip_point_loss_weight
+
+    @classmethod
+    def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", **overrides):
+        """a standalone PointNet2NOCS checkpoint {'state_dict', 'hyper_parameters'} (train_pointnet2.py's), without Lightning"""
+        ckpt = torch.load(checkpoint_path, map_location=map_location, weights_only=False)
+        hp = dict(ckpt["hyper_parameters"])
+        hp.update(overrides)
+        model = cls(**hp)
+        model.load_state_dict(ckpt["state_dict"])
+        return model
+
+    def save_checkpoint(self, path):
+        torch.save({"state_dict": self.state_dict(), "hyper_parameters": self.hparams}, path)
 
     @property
     def device(self):
@@ -89,3 +107,42 @@ class PointNet2NOCS(nn.Module):
     def get_virtual_grid(self):
         return VirtualGrid(lower_corner=(0, 0, 0), upper_corner=(1, 1, 1), grid_shape=(self.nocs_bins,) * 3, batch_size=1,
                            device=self.device, int_dtype=torch.int64, float_dtype=torch.float32)
+
+    # -- validation ----------------------------------------------------------------------------------------
+    def validation_metrics(self, batch, result=None):
+        """the metric dict of the reference's infer (pointnet2_nocs.py:257-440) as python floats: loss, nocs_loss, grip_point_loss,
+        nocs_err_dist, grip_point_err_dist.  batch: .x, .pos, .batch, .y (N, 3) NOCS targets, .nocs_grip_point (B, 3).  result: this model's
+        forward(batch) when the caller already has it.
+          regression (nocs_bins None): MSE of the logits, MirrorMSELoss (min of the plain and the x-mirrored MSE) when symmetry_axis is set;
+          bins, no symmetry axis: cross entropy at VirtualGrid's target bins, arg-max coordinates for the distances;
+          bins and symmetry_axis: the same against the plain and the mirrored targets; the WHOLE batch takes the branch with the smaller
+          weighted loss (plain when equal) and loss = that minimum."""
+        if result is None:
+            result = self(batch)
+        logits, glogits = result["per_point_logits"], result["global_logits"]
+        gt, ggt = batch.y, batch.nocs_grip_point
+        n, b = gt.shape[0], ggt.shape[0]
+        wn, wg = self.nocs_loss_weight, self.grip_point_loss_weight
+        if self.nocs_bins is None:
+            mirror = self.symmetry_axis is not None
+            s = ops.value_losses([(logits, gt, "l2", mirror), (glogits, ggt, "l2", mirror), (logits, gt, "row_norm"), (glogits, ggt, "row_norm")])
+            s = s.cpu().tolist()
+            nocs = min(s[0][0], s[0][1]) if mirror else s[0][0]
+            grip = min(s[1][0], s[1][1]) if mirror else s[1][0]
+            nocs_loss, grip_loss = nocs / (n * 3), grip / (b * 3)
+            return {"loss": wn * nocs_loss + wg * grip_loss, "nocs_loss": nocs_loss, "grip_point_loss": grip_loss,
+                    "nocs_err_dist": s[2][0] / n, "grip_point_err_dist": s[3][0] / b}
+        sums = ops.nocs_bin_metrics([(logits, gt), (glogits, ggt)], self.nocs_bins, self.symmetry_axis).cpu().tolist()
+
+        def branch(ce, dist):
+            nocs_loss, grip_loss = sums[0][ce] / (n * 3), sums[1][ce] / (b * 3)
+            return {"loss": wn * nocs_loss + wg * grip_loss, "nocs_loss": nocs_loss, "grip_point_loss": grip_loss,
+                    "nocs_err_dist": sums[0][dist] / n, "grip_point_err_dist": sums[1][dist] / b}
+
+        plain = branch(0, 2)
+        if self.symmetry_axis is None:
+            return plain
+        mirrored = branch(1, 3)
+        final = dict(plain if plain["loss"] <= mirrored["loss"] else mirrored)
+        final["loss"] = min(plain["loss"], mirrored["loss"])
+        return final

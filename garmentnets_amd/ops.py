@@ -1128,3 +1128,70 @@ def point_mesh_sqdist_batch(queries, meshes):
 def point_mesh_sqdist(query, verts, faces):
     """-> (face_idx int32 [Nq], d2 float64 [Nq]): squared distance of every query to the nearest triangle of (verts, faces)"""
     return point_mesh_sqdist_batch([query], [(verts, faces)])[0]
+
+
+# ------------------------------------------------------------------------------------------------ validation losses
+def _check_sets(n):
+    if not 1 <= n <= _lib.LOSS_MAX_SETS:
+        raise ValueError(f"1..{_lib.LOSS_MAX_SETS} sets per launch, got {n}")
+
+
+def _table(cls, rows):
+    return (cls * len(rows))(*[cls(*r) for r in rows])
+
+
+def nocs_bin_metrics(sets, bins, mirror_axis=None):
+    """binned NOCS head metrics of 1..8 row sets in ONE launch (gn_nocs_bin_metrics).  sets: [(logits (N, >= bins*3) fp32 rows laid out
+    (bins, 3), gt (N, 3))], N >= 1.  -> (nsets, 4) fp64 on the device: the sums over the set of CE at the target bin, CE at the mirrored
+    target bin, |arg-max coordinate - gt| and |arg-max coordinate - mirrored gt| (mirror_axis None: the mirrored columns repeat the plain ones)"""
+    _check_sets(len(sets))
+    keep = []
+    for logits, gt in sets:
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] < bins * 3:
+            raise ValueError(f"logits: expected (N, >= {bins * 3}) float32 rows, got {tuple(logits.shape)} {logits.dtype}")
+        if logits.shape[1] > 1 and logits.stride(1) != 1:
+            logits = logits.contiguous()
+        n, ldl = rows_view(logits)
+        gt = gt.float().contiguous()
+        if n < 1 or gt.shape != (n, 3):
+            raise ValueError(f"gt: expected ({n}, 3) with at least one row, got {tuple(gt.shape)}")
+        keep.append((logits, gt, n, ldl))
+    rows = [(_p(lg).value, _p(gt).value, n, ldl, 0) for lg, gt, n, ldl in keep]
+    tab = _table(_lib.NocsBinSet, rows)
+    dev = keep[0][1].device
+    nws = _lib.load().gn_nocs_bin_metrics_workspace_bytes(tab, len(rows))
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
+    out = torch.empty((len(rows), 4), dtype=torch.float64, device=dev)
+    _lib.call("gn_nocs_bin_metrics", tab, len(rows), int(bins), -1 if mirror_axis is None else int(mirror_axis), _p(ws), nws, _p(out), _stream())
+    return out
+
+
+def value_losses(segments):
+    """element-wise loss sums of 1..8 segments in ONE launch (gn_value_losses).  segments: [(pred, target, kind[, mirror])], kind one of
+    "l2" | "smooth_l1" | "bce_logits" (per element) | "row_norm" (|pred - target| per (M, 3) row); pred and target of the same number of
+    elements (any shape, read flat); mirror: also the sum against the x-mirrored target of (M, 3) rows.  -> (nsegs, 2) fp64 on the device:
+    (sum, mirrored sum; 0 without mirror)"""
+    _check_sets(len(segments))
+    keep = []
+    for seg in segments:
+        pred, target, kind = seg[:3]
+        mirror = bool(seg[3]) if len(seg) > 3 else False
+        if kind not in _lib.LOSS_KINDS:
+            raise ValueError(f"loss kind {kind!r}: expected one of {sorted(_lib.LOSS_KINDS)}")
+        pred, target = pred.float().contiguous(), target.float().contiguous()
+        if pred.numel() != target.numel():
+            raise ValueError(f"pred ({pred.numel()} elements) and target ({target.numel()}) differ in size")
+        count = pred.numel()
+        if kind == "row_norm" or mirror:
+            if count % 3:
+                raise ValueError(f"{kind} {'(mirrored) ' if mirror else ''}needs (M, 3) rows, got {count} elements")
+            count = count // 3 if kind == "row_norm" else count
+        keep.append((pred, target, count, _lib.LOSS_KINDS[kind], int(mirror)))
+    rows = [(_p(pr).value, _p(tg).value, n, k, m) for pr, tg, n, k, m in keep]
+    tab = _table(_lib.LossSegment, rows)
+    dev = keep[0][0].device
+    nws = _lib.load().gn_value_losses_workspace_bytes(tab, len(rows))
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
+    out = torch.empty((len(rows), 2), dtype=torch.float64, device=dev)
+    _lib.call("gn_value_losses", tab, len(rows), _p(ws), nws, _p(out), _stream())
+    return out

@@ -500,6 +500,48 @@ int gn_nearest_neighbor_f64_batch(const double *query, const double *ref, const 
 int gn_point_mesh_sqdist_batch(const double *query, const double *verts, const int32_t *faces, const int64_t *pairs, int P, int64_t max_nq,
                                int32_t *face_idx, double *d2, int64_t *bad, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Validation losses (networks/pointnet2_nocs.py:257-440, networks/conv_implicit_wnf.py:405-452).
+ * Per-element terms in fp32 as torch computes them; sums in fp64.  Deterministic: one plain store of a partial per workgroup into ws,
+ * then a fold launch in a fixed order (no atomics: two identical calls give identical bits).  The set / segment tables are HOST arrays
+ * (the `_host` suffix); the pointers in them are device pointers.
+ * ------------------------------------------------------------------------------------------------------- */
+#define GN_LOSS_MAX_SETS 8
+#define GN_LOSS_L2 0
+#define GN_LOSS_SMOOTH_L1 1
+#define GN_LOSS_BCE_LOGITS 2
+#define GN_LOSS_ROW_NORM 3   /* |pred - target| of (count, 3) rows: the regression head's error distance */
+
+typedef struct {
+    const float *logits;   /* [n][ldl] rows, the first bins * 3 laid out (bins, 3) as gn_nocs_head reads them */
+    const float *gt;       /* [n][3] target NOCS coordinates */
+    int64_t n;             /* rows, >= 1 */
+    int ldl;               /* >= bins * 3 */
+    int pad;
+} GnNocsBinSet;
+
+typedef struct {
+    const float *pred;     /* [count] ([count][3] for GN_LOSS_ROW_NORM) */
+    const float *target;   /* same size as pred */
+    int64_t count;         /* >= 0 elements (rows for GN_LOSS_ROW_NORM); a multiple of 3 when mirror is set on an element-wise kind */
+    int kind;              /* GN_LOSS_L2 | GN_LOSS_SMOOTH_L1 (beta 1) | GN_LOSS_BCE_LOGITS (max(x,0) - x*y + log1p(exp(-|x|))) | GN_LOSS_ROW_NORM
+                              (fp32 sqrt((dx*dx + dy*dy) + dz*dz)) */
+    int mirror;            /* 1: also sum against the x-mirrored target of (count/3, 3) rows (components/loss.py MirrorMSELoss) */
+} GnLossSegment;
+
+/* Binned NOCS head metrics for 1..GN_LOSS_MAX_SETS row sets in one launch (the per-point logits and the global grip-point logits).
+ * Per (row, axis): max-subtracted log-sum-exp over the bins; cross entropy at the target bin of gt and at the target bin of the mirrored gt
+ * (mirror_axis 0..2: (p - 0.5) * -1 + 0.5 on that axis in fp32; -1: no mirror, the two are equal); first-maximum arg-max -> coordinate as
+ * gn_nocs_head.  Target bins are VirtualGrid.get_points_grid_idxs' exactly: fp32 p * (bins - 1), truncation, clamp to [0, bins - 1].
+ * out [nsets][4] fp64 = {sum CE, sum CE mirrored, sum |pred - gt|, sum |pred - gt mirrored|} (the norms fp32 per row).  bins >= 1. */
+size_t gn_nocs_bin_metrics_workspace_bytes(const GnNocsBinSet *sets_host, int nsets);
+int gn_nocs_bin_metrics(const GnNocsBinSet *sets_host, int nsets, int bins, int mirror_axis, void *ws, size_t ws_bytes, double *out, void *stream);
+
+/* Element-wise loss sums for 1..GN_LOSS_MAX_SETS segments in one launch (volume / surface / mc-surface decoders, the regression head).
+ * out [nsegs][2] fp64 = {sum of the terms, sum against the x-mirrored target (0 unless the segment's mirror is set)}. */
+size_t gn_value_losses_workspace_bytes(const GnLossSegment *segs_host, int nsegs);
+int gn_value_losses(const GnLossSegment *segs_host, int nsegs, void *ws, size_t ws_bytes, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
