@@ -1195,3 +1195,153 @@ def value_losses(segments):
     out = torch.empty((len(rows), 2), dtype=torch.float64, device=dev)
     _lib.call("gn_value_losses", tab, len(rows), _p(ws), nws, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ operator gradients (csrc/grad.hip)
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _grad_rows(t, name, cols=None):
+    """an incoming gradient as fp32 rows (autograd may hand over an expanded or otherwise strided tensor)"""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name}: expected rows of {cols} channels, got shape {tuple(t.shape)}")
+    return t if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def grid_scatter_bwd(grad_vol, flat_idx, N, reduce, vol=None, src=None, c_real=None):
+    """grad_vol: channel-last [B][G0][G1][G2][C] -> grad_src [N][C].  max / min need the forward's output `vol` and input `src` (the winner of a
+    cell is the lowest point index whose value is bit-equal to the stored one).  'mul' is refused by name."""
+    if reduce not in REDUCE_CODES:
+        raise ValueError(f"grid_scatter_bwd: reduce={reduce!r} is not one of {sorted(REDUCE_CODES)}")
+    if reduce == "mul":
+        raise ValueError("grid_scatter_bwd: reduce='mul' has no gradient here (nobody trains with it; it divides by zero at a zero factor)")
+    _chk(grad_vol, torch.float32, "grad_vol")
+    _chk(flat_idx, _i32, "flat_idx")
+    C = grad_vol.shape[-1]
+    cells = grad_vol.numel() // C
+    N = int(N)
+    if flat_idx.numel() != N:
+        raise ValueError(f"grid_scatter_bwd: flat_idx has {flat_idx.numel()} entries for {N} points")
+    sel = reduce in ("max", "min")
+    if sel:
+        if vol is None or src is None:
+            raise ValueError(f"grid_scatter_bwd: reduce={reduce!r} needs the forward's output and input")
+        _chk(vol, torch.float32, "vol")
+        if vol.shape != grad_vol.shape or src.dtype != torch.float32 or tuple(src.shape) != (N, C):
+            raise ValueError("grid_scatter_bwd: vol / src do not match grad_vol")
+    code = REDUCE_CODES[reduce]
+    out = new_rows(N, C, grad_vol.device)
+    if N == 0:
+        return out
+    nbytes = _lib.load().gn_grid_scatter_bwd_workspace_bytes(N, C, cells, code)
+    ws = _ws(nbytes, grad_vol.device) if nbytes else None
+    _lib.call("gn_grid_scatter_bwd", _p(grad_vol), _p(vol if sel else None), _p(src if sel else None), rows_view(src)[1] if sel else 0, _p(flat_idx), N, C,
+              C if c_real is None else int(c_real), cells, code, _p(ws), nbytes, _p(out), out.stride(0), _stream())
+    return out
+
+
+def segment_max_bwd(grad_out, out, h, slot_src, M, S):
+    """gradient of segment_max with respect to h [M * S][C]"""
+    C = h.shape[1]
+    grad_out = _grad_rows(grad_out, "grad_out", C)
+    if tuple(out.shape) != (M, C) or h.shape[0] != M * S or grad_out.shape[0] != M or slot_src.numel() != M * S:
+        raise ValueError("segment_max_bwd: shapes do not match (M, S, C)")
+    _chk(slot_src, _i32, "slot_src")
+    g = new_rows(M * S, C, h.device)
+    _lib.call("gn_segment_max_bwd", _p(grad_out), rows_view(grad_out)[1], _p(out), rows_view(out)[1], _p(h), rows_view(h)[1], _p(slot_src), M, S, C,
+              _p(g), g.stride(0), _stream())
+    return g
+
+
+def global_max_pool_bwd(grad_out, out, h, ptr, B):
+    C = h.shape[1]
+    grad_out = _grad_rows(grad_out, "grad_out", C)
+    if tuple(out.shape) != (B, C) or grad_out.shape[0] != B or ptr.numel() != B + 1:
+        raise ValueError("global_max_pool_bwd: shapes do not match (B, C)")
+    _chk(ptr, _i32, "ptr")
+    g = new_rows(h.shape[0], C, h.device)
+    _lib.call("gn_global_max_pool_bwd", _p(grad_out), rows_view(grad_out)[1], _p(out), rows_view(out)[1], _p(h), rows_view(h)[1], _p(ptr), B, C,
+              _p(g), g.stride(0), _stream())
+    return g
+
+
+def sa_gather_bwd(grad_edge, slot_src, C, n_points):
+    """gradient of sa_gather with respect to x [n_points][C]: the feature part (columns :C) of the edge rows, summed per source in ascending row"""
+    grad_edge = _grad_rows(grad_edge, "grad_edge")
+    _chk(slot_src, _i32, "slot_src")
+    rows = slot_src.numel()
+    if grad_edge.shape[0] != rows or grad_edge.shape[1] < C or C < 1:
+        raise ValueError("sa_gather_bwd: grad_edge does not match slot_src / C")
+    g = new_rows(n_points, C, grad_edge.device)
+    if n_points == 0:
+        return g
+    nbytes = _lib.load().gn_sa_gather_bwd_workspace_bytes(rows, n_points)
+    ws = _ws(nbytes, grad_edge.device)
+    _lib.call("gn_sa_gather_bwd", _p(grad_edge), rows_view(grad_edge)[1], _p(slot_src), rows, C, n_points, _p(ws), nbytes, _p(g), g.stride(0), _stream())
+    return g
+
+
+def knn_neighbours(ps, ptr_s, pq, ptr_q, k):
+    """-> (nbr int32 [Nq][k], d2 fp32 [Nq][k]): the neighbours knn_interpolate uses, ascending (d2, index); -1 / 0 past an example's sources"""
+    _chk(ps, torch.float32, "ps")
+    _chk(pq, torch.float32, "pq")
+    Nq, k = pq.shape[0], int(k)
+    if k < 1:
+        raise ValueError("knn_neighbours: k must be >= 1")
+    nbr = torch.empty((Nq, k), dtype=_i32, device=pq.device)
+    d2 = torch.empty((Nq, k), dtype=torch.float32, device=pq.device)
+    if Nq:
+        _lib.call("gn_knn_neighbours", _p(ps), _p(ptr_s), _p(pq), _p(ptr_q), ptr_s.numel() - 1, Nq, k, _p(nbr), _p(d2), _stream())
+    return nbr, d2
+
+
+def knn_interpolate_bwd(grad_y, nbr, d2, n_sources):
+    """gradient of knn_interpolate with respect to the source features [n_sources][C] (nbr, d2: knn_neighbours)"""
+    grad_y = _grad_rows(grad_y, "grad_y")
+    _chk(nbr, _i32, "nbr")
+    _chk(d2, torch.float32, "d2")
+    Nq, k = nbr.shape
+    C = grad_y.shape[1]
+    if grad_y.shape[0] != Nq or d2.shape != nbr.shape:
+        raise ValueError("knn_interpolate_bwd: grad_y / d2 do not match nbr")
+    if Nq == 0 or n_sources == 0:
+        return torch.zeros((n_sources, pad4(C)), dtype=torch.float32, device=grad_y.device)[:, :C]
+    g = new_rows(n_sources, C, grad_y.device)
+    nbytes = _lib.load().gn_knn_interpolate_bwd_workspace_bytes(Nq, k, n_sources)
+    ws = _ws(nbytes, grad_y.device)
+    _lib.call("gn_knn_interpolate_bwd", _p(nbr), _p(d2), Nq, k, _p(grad_y), rows_view(grad_y)[1], n_sources, C, _p(ws), nbytes, _p(g), g.stride(0), _stream())
+    return g
+
+
+def trilinear_sample_bwd(grad_rows, vol, query, want_vol=True, want_query=False):
+    """gradient of trilinear_sample_batch: grad_rows (B, M, C), vol (B, D, H, W, C) channel-last, query (B, M, 3)
+    -> (grad_vol like vol or None, grad_query (B, M, 3) or None).  grad_vol is an ordered sum per voxel (no float atomics): bit-identical repeats."""
+    _chk(vol, torch.float32, "vol")
+    _chk(query, torch.float32, "query")
+    if vol.dim() != 5 or query.dim() != 3 or query.shape[0] != vol.shape[0] or query.shape[2] != 3:
+        raise ValueError("trilinear_sample_bwd: vol must be (B, D, H, W, C) and query (B, M, 3)")
+    B, D, H, W, C = vol.shape
+    M = query.shape[1]
+    if grad_rows.dtype != torch.float32:
+        raise TypeError(f"grad_rows: expected torch.float32, got {grad_rows.dtype}")
+    if tuple(grad_rows.shape) != (B, M, C):
+        raise ValueError(f"trilinear_sample_bwd: grad_rows must be {(B, M, C)}, got {tuple(grad_rows.shape)}")
+    if M and B and not (grad_rows.stride(2) == 1 and grad_rows.stride(1) >= C and grad_rows.stride(0) == M * grad_rows.stride(1)):
+        grad_rows = grad_rows.contiguous()
+    gv = gq = None
+    if B == 0 or M == 0:           # nothing was sampled: empty / zero gradients without a launch
+        return (torch.zeros_like(vol) if want_vol else None), (torch.zeros_like(query) if want_query else None)
+    nbytes = 0
+    ws = None
+    if want_vol:
+        gv = torch.empty_like(vol)
+        nbytes = _lib.load().gn_trilinear_sample_bwd_workspace_bytes(B, M, D, H, W)
+        ws = _ws(nbytes, vol.device)
+    if want_query:
+        gq = torch.empty_like(query)
+    if want_vol or want_query:
+        _lib.call("gn_trilinear_sample_bwd", _p(grad_rows), grad_rows.stride(1), _p(vol), B, D, H, W, C, _p(query), M, _p(ws), nbytes, _p(gv), _p(gq), _stream())
+    return gv, gq

@@ -542,6 +542,48 @@ int gn_nocs_bin_metrics(const GnNocsBinSet *sets_host, int nsets, int bins, int 
 size_t gn_value_losses_workspace_bytes(const GnLossSegment *segs_host, int nsegs);
 int gn_value_losses(const GnLossSegment *segs_host, int nsegs, void *ws, size_t ws_bytes, double *out, void *stream);
 
+/* ---- Operator gradients (csrc/grad.hip): fp32 in / fp32 out.  The selections (grid scatter max / min, segment max, global max pool) hand an output
+ * element's gradient to ONE input element: the one whose value is bit-equal to the forward's stored output, the lowest point / edge index among equal
+ * values; a NaN never wins.  The sums (sa_gather, knn_interpolate, the sampler's volume gradient) are ordered: one owner per destination adds its
+ * terms in ascending element index, so identical calls give identical bits; no float atomics anywhere. */
+
+/* Gradient of gn_grid_scatter / _ex: grad_src[p][c] = grad_vol[cell(p)][c] * k, k = 1 (sum), 1 / count(cell) (mean), and for max / min 1 for the
+ * winning point of (cell, c), else 0.  vol (the forward's output), src / lds: read for max and min only (NULL otherwise).  Channels [c_real, C) are
+ * pads: gradient 0.  reduce 4 (mul) is refused.  A point whose cell is outside [0, cells) gets 0.  ws: gn_grid_scatter_bwd_workspace_bytes. */
+size_t gn_grid_scatter_bwd_workspace_bytes(int64_t N, int C, int64_t cells, int reduce);
+int gn_grid_scatter_bwd(const float *grad_vol, const float *vol, const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int c_real,
+                        int64_t cells, int reduce, void *ws, size_t ws_bytes, float *grad_src, int ldg, void *stream);
+
+/* Gradient of gn_segment_max: grad_in[c*S+s][ch] = grad_out[c][ch] for the first valid slot s that holds out[c][ch], else 0 (every row is written). */
+int gn_segment_max_bwd(const float *grad_out, int ldg, const float *out, int ldo, const float *in, int ldi, const int32_t *slot_src, int M, int S,
+                       int C, float *grad_in, int ldgi, void *stream);
+
+/* Gradient of gn_global_max_pool: the same per example (rows ptr[b]..ptr[b+1], the lowest row among equal values). */
+int gn_global_max_pool_bwd(const float *grad_out, int ldg, const float *out, int ldo, const float *in, int ldi, const int32_t *ptr, int B, int C,
+                           float *grad_in, int ldgi, void *stream);
+
+/* Gradient of gn_sa_gather with respect to x: grad_x[j][:C] = sum of grad_edge[e][:C] over the edge rows e whose source is j, in ascending e.
+ * slot_src [rows]: gn_sa_gather's record of every row's source (after the self-loop rule; -1 = empty slot).  Every row of grad_x is written. */
+size_t gn_sa_gather_bwd_workspace_bytes(int64_t rows, int64_t n_points);
+int gn_sa_gather_bwd(const float *grad_edge, int lde, const int32_t *slot_src, int64_t rows, int C, int64_t n_points, void *ws, size_t ws_bytes,
+                     float *grad_x, int ldgx, void *stream);
+
+/* The neighbours gn_knn_interpolate / _any use (ascending (d2, index), any k >= 1): nbr [Nq][k] int32 (-1 past an example's sources), d2 [Nq][k]. */
+int gn_knn_neighbours(const float *ps, const int32_t *ptr_s, const float *pq, const int32_t *ptr_q, int B, int Nq, int k, int32_t *nbr, float *d2,
+                      void *stream);
+/* Gradient of gn_knn_interpolate / _any with respect to the source features: grad_xs[j] = sum over the (query i, rank r) pairs with nbr[i][r] == j,
+ * in ascending (i, r), of (w_ir / sum_r' w_ir') grad_y[i], w = 1 / max(d2, 1e-16).  The search and the weights are data (no gradient to positions). */
+size_t gn_knn_interpolate_bwd_workspace_bytes(int64_t Nq, int k, int64_t Ns);
+int gn_knn_interpolate_bwd(const int32_t *nbr, const float *d2, int Nq, int k, const float *grad_y, int ldg, int Ns, int C, void *ws, size_t ws_bytes,
+                           float *grad_xs, int ldgx, void *stream);
+
+/* Gradient of gn_trilinear_sample / _batch (border padding, align_corners=True).  grad_rows: (B M) rows of ldg floats; vol: B dense channel-last
+ * volumes; query (B, M, 3).  grad_vol (B, D, H, W, C) dense, every voxel written: the corner weights times grad_rows, summed per voxel in ascending
+ * (query, corner).  grad_query (B, M, 3): F.grid_sample's rule -- a coordinate clamped at the border gets 0.  Either may be NULL (not computed). */
+size_t gn_trilinear_sample_bwd_workspace_bytes(int B, int64_t M, int D, int H, int W);
+int gn_trilinear_sample_bwd(const float *grad_rows, int ldg, const float *vol, int B, int D, int H, int W, int C, const float *query, int64_t M,
+                            void *ws, size_t ws_bytes, float *grad_vol, float *grad_query, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
