@@ -1,22 +1,32 @@
-"""Differentiable bindings of the point and grid operators, under the third-party call shapes INTEGRATION.md section B documents.
+"""Differentiable bindings of the point and grid operators, under the third-party call shapes INTEGRATION.md section B documents, and of the 3-D UNet.
 
 The reference's dense layers (nn.Linear, BatchNorm1d, Conv3d, GroupNorm, ...) have torch's own backward on ROCm.  The third-party operators
 between them (torch_cluster.fps / radius, PointConv's gather + max, global_max_pool, knn_interpolate, torch_scatter.scatter, F.grid_sample) are
 the ones this package restates in HIP; here each gets a ``torch.autograd.Function`` whose forward is the existing op, unchanged, and whose backward
 is a kernel of csrc/grad.hip.  A reference-side module that binds these functions can take gradients on an MI355X.
 
-What this is NOT: a training loop, an optimiser, train-mode BatchNorm, or a backward for the conv / MLP kernels of the inference path (DESIGN.md
-section 9).  The inference modules do not import this file; ``gn_sa_fused`` stays inference-only (``point_conv_max`` is the unfused chain).
+The UNet is not a torch graph (channel-last, channel-padded volumes, GroupNorm folded into the conv's operand load, concat and upsampling never
+materialised), so it gets its own backward: ``conv3d_gcr`` / ``max_pool3d_2`` / ``unet3d`` run the existing forward kernels and differentiate them with
+csrc/unet_grad.hip (DESIGN.md "UNet gradients").
+
+What this is NOT: a training loop, an optimiser, train-mode BatchNorm, or a backward for the decoder MLPs / ``gn_linear`` layers / ``gn_sa_fused`` of
+the inference path.  The inference modules do not import this file; ``gn_sa_fused`` stays inference-only (``point_conv_max`` is
+the unfused chain).
 
 Selections (max / min) hand the gradient to ONE element per (slot, channel): among equal values the lowest point / edge index (torch_scatter's CUDA
 choice is whichever thread wins an atomic: parity unpinned).  Every sum is ordered: identical calls give identical bits.
 """
 import torch
 
+import torch.nn.functional as F
+
 from . import ops
+from .components import unet3d as U
+from .components.mlp import param_cache
 from .components.pointnet2 import Segments, _example_self_src
 
-__all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points"]
+__all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
+           "conv3d_gcr", "max_pool3d_2", "unet3d"]
 
 
 def _rows(t):
@@ -213,3 +223,204 @@ def grid_sample_points(volume, query):
     if volume.dtype != torch.float32 or query.dtype != torch.float32:
         raise TypeError("grid_sample_points: volume and query must be torch.float32")
     return _TrilinearSample.apply(volume.permute(0, 2, 3, 4, 1).contiguous(), query.contiguous())
+
+
+# ------------------------------------------------------------------------------------------------ the 3-D UNet
+def _tensor_stats(st):
+    """(sum, sumsq, V) -> the two tensors an autograd.Function can take / return, and V"""
+    return (None, None, 0) if st is None else (st[0], st[1], int(st[2]))
+
+
+class _ConvGcr(torch.autograd.Function):
+    """one 'gcr' SingleConv on stored volumes.  weight / gamma / beta are the module's own parameters (the forward is SingleConv.run on the module's
+    packs of them); they are saved, so the backward differentiates the parameters the forward used and an in-place update in between is an autograd
+    version error, not a silent gradient of the new values.  Returns (y, sum, sumsq): the output and its statistics (the next layer's GroupNorm)."""
+
+    @staticmethod
+    def forward(ctx, src0, src1, weight, gamma, beta, s0, q0, s1, q1, conv, arith):
+        st0 = (s0, q0, src0[0].numel() // src0.shape[-1])
+        st1 = None if src1 is None else (s1, q1, src1[0].numel() // src1.shape[-1])
+        y, st = conv.run(src0, src1, st0, st1, arith=arith)
+        ctx.save_for_backward(src0, src1, y, s0, q0, s1, q1, weight, gamma, beta)
+        ctx.conv = conv
+        ctx.mark_non_differentiable(st[0], st[1])
+        return y, st[0], st[1]
+
+    @staticmethod
+    def backward(ctx, grad_y, _gs, _gq):
+        src0, src1, y, s0, q0, s1, q1, weight, gamma, beta = ctx.saved_tensors
+        conv, gn = ctx.conv, ctx.conv.groupnorm
+        need = ctx.needs_input_grad
+        lay = conv._layout(src0, src1)
+        S0, S1 = src0.shape[-1], 0 if src1 is None else src1.shape[-1]
+        real = None if lay is None else lay.real
+        st0 = (s0, q0, src0[0].numel() // S0)
+        st1 = None if src1 is None else (s1, q1, src1[0].numel() // S1)
+        gamma = gamma.detach().float().contiguous()
+        dy = grad_y.contiguous()
+        dw = None
+        if need[2]:
+            a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta.detach().float().contiguous(), real=real)
+            dw = ops.conv3d_bwd_weight(src0, src1, a, d, y, dy)
+            if lay is not None:                   # stored -> real channels (the pad rows / columns are exact zeros)
+                cols = torch.cat([torch.arange(r, device=dw.device) + o for r, o in zip(lay.real, (0, S0))])
+                dw = dw[:conv.conv.out_channels].index_select(1, cols)
+        if not any(need[i] for i in (0, 1, 3, 4)):
+            return None, None, dw, None, None, None, None, None, None, None, None
+        # d operand = conv_transpose(g, W): the forward fp32 kernel on the flipped / transposed pack
+        cin_p = -(-(S0 + S1) // 32) * 32
+        # (the saved weight IS conv.conv.weight at the forward's version -- unpacking it has checked that -- so the module's version-keyed caches hold its packs)
+        wsrc = weight if lay is None else conv._padded_weight(lay)
+        wpt = param_cache(conv, "_split_packs").get(conv._gen(lay), "bwd_data", lambda: ops.pack_conv_weight_bwd_data(wsrc))
+        dxn = ops.conv3d_bwd_data(ops.relu_mask(y, dy), wpt, cin_p)
+        t0 = ops.groupnorm_bwd_stats(dxn, 0, src0)
+        t1 = None if src1 is None else ops.groupnorm_bwd_stats(dxn, S0, src1, half=True)
+        p, q, r, dgamma, dbeta = ops.groupnorm_bwd_coef(t0, t1, st0, st1, gn.num_groups, gn.eps, gamma, real=real)
+        d0 = ops.groupnorm_bwd_apply(dxn, 0, src0, p, q, r, 0) if need[0] else None
+        d1 = ops.groupnorm_bwd_apply(dxn, S0, src1, p, q, r, S0, half=True) if src1 is not None and need[1] else None
+        return d0, d1, dw, dgamma if need[3] else None, dbeta if need[4] else None, None, None, None, None, None, None
+
+
+def _check_gcr(conv):
+    if not isinstance(conv, U.SingleConv):
+        raise TypeError(f"expected a components.unet3d.SingleConv, got {type(conv).__name__}")
+    if conv.order != "gcr":
+        raise NotImplementedError(f"layer order {conv.order!r} has no gradient here: only 'gcr' (GroupNorm -> Conv3d -> ReLU) is differentiable")
+
+
+def _conv(conv, src0, src1, st0, st1, arith):
+    """-> (y, (sum, sumsq, V) of y).  st0 / st1: the inputs' statistics when their producer emitted them (else one gn_channel_stats pass)"""
+    if st0 is None:
+        st0 = ops.channel_stats(src0.detach())
+    if src1 is not None and st1 is None:
+        st1 = ops.channel_stats(src1.detach())
+    s1, q1, _ = _tensor_stats(st1)
+    gn = conv.groupnorm
+    y, s, q = _ConvGcr.apply(src0, src1, conv.conv.weight, gn.weight, gn.bias, st0[0], st0[1], s1, q1, conv, arith)
+    return y, (s, q, y[0].numel() // y.shape[-1])
+
+
+def _stored(t, name):
+    if t.dim() != 5 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected a float32 channel-last stored volume [B][D][H][W][C], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def conv3d_gcr(single_conv, src0, src1=None, arith=None):
+    """One 'gcr' ``SingleConv`` (GroupNorm -> Conv3d 3x3x3 -> ReLU) as a differentiable function of src0, src1 and the module's conv.weight,
+    groupnorm.weight, groupnorm.bias.  src0 [B][D][H][W][C0] and the optional half-resolution src1 [B][D/2][H/2][W/2][C1] are channel-last STORED
+    volumes (channel-padded when the module's in_real says so); the result is the stored output [B][D][H][W][stored Cout].  Forward: SingleConv.run
+    (the kernels ``arith`` selects, dense launch).  Backward: csrc/unet_grad.hip -- an fp32 backward whatever the forward arithmetic."""
+    _check_gcr(single_conv)
+    return _conv(single_conv, _stored(src0, "src0"), None if src1 is None else _stored(src1, "src1"), None, None, arith)[0]
+
+
+class _MaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, with_stats):
+        ctx.save_for_backward(x)
+        if with_stats:
+            out, (s, q, _) = ops.maxpool3d_2(x, with_stats=True)
+        else:
+            out = ops.maxpool3d_2(x)
+            s = q = x.new_empty(0, dtype=torch.float64)
+        ctx.mark_non_differentiable(s, q)
+        return out, s, q
+
+    @staticmethod
+    def backward(ctx, grad_out, _gs, _gq):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool3d_2_bwd(grad_out.contiguous(), x), None
+
+
+def _pool(x):
+    """-> (pooled, its statistics or None): Encoder.run's call of gn_maxpool3d_2 (its epilogue condition, restated: the no-grad test of the GPU suite
+    holds the two to the same bits on a width of either kind)"""
+    c = x.shape[-1]
+    with_stats = c <= 256 and 256 % (c // 4) == 0
+    out, s, q = _MaxPool.apply(x, with_stats)
+    return out, ((s, q, out[0].numel() // c) if with_stats else None)
+
+
+def max_pool3d_2(x):
+    """nn.MaxPool3d(2) on a channel-last stored volume [B][D][H][W][C] (even D, H, W; C % 4 == 0).  The gradient goes to the first maximum of each
+    window in (z, y, x) order, a NaN winning (ATen's CPU scan); the winner is found again from the stored input, no index tensor is kept."""
+    x = _stored(x, "x")
+    if any(n % 2 for n in x.shape[1:4]):
+        raise ValueError(f"max_pool3d_2: the volume {tuple(x.shape[1:4])} must have even dimensions")
+    return _MaxPool.apply(x, False)[0]
+
+
+class _FinalConv(torch.autograd.Function):
+    """the final 1x1x1 convolution: a row GEMM over the stored channels"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod):
+        ctx.save_for_backward(x, weight)
+        ctx.mod = mod
+        return mod.run(x)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors       # (weight: mod.weight at the forward's version, checked on unpacking)
+        mod, need = ctx.mod, ctx.needs_input_grad
+        n, ks = mod.out_channels, x.shape[-1]
+        dy = grad_y.reshape(-1, n).contiguous()
+        dx = dw = db = None
+        if need[0]:
+            wt = param_cache(mod, "_grad_packs").get((weight.device, weight._version, ks), "wt",
+                                                     lambda: U.pack_wb(mod.stored_weight().t().contiguous(), None)[0])
+            dx = ops.linear(dy, wt, K=n).reshape(x.shape)
+            if not dx.is_contiguous():
+                dx = dx.contiguous()
+        if need[1] or need[2]:
+            dws, db = ops.linear_bwd_params(dy, x.reshape(-1, ks), with_bias=mod.bias is not None)
+            dw = dws[:, :mod.in_channels].reshape(weight.shape)
+        return dx, dw if need[1] else None, db if need[2] else None, None
+
+
+def _unet_layers(model):
+    return [sc for blk in list(model.encoders) + list(model.decoders) for sc in (blk.basic_module.SingleConv1, blk.basic_module.SingleConv2)]
+
+
+def unet3d(model, x, arith=None):
+    """``Abstract3DUNet.forward``'s contract -- x (B, C, D, H, W) -> (B, C', D, H, W), a view over channel-last storage -- differentiable in x and in
+    every parameter of the model: ``conv3d_gcr`` per layer, ``max_pool3d_2`` between the encoder levels, the final 1x1x1 convolution as a row GEMM.
+    Any f_maps / num_levels the forward runs; on channel-padded widths the pad gradients are exact zeros and reach no parameter.  arith: the
+    arithmetic of the FORWARD kernels (None: model.arith, else arith.DEFAULT); the backward is fp32 throughout.  Layer orders other than 'gcr' raise
+    NotImplementedError.  Under torch.no_grad(), or when nothing requires a gradient, this is model.forward's launches and nothing is saved."""
+    if not isinstance(model, U.Abstract3DUNet):
+        raise TypeError(f"unet3d: expected a components.unet3d.Abstract3DUNet, got {type(model).__name__}")
+    for sc in _unet_layers(model):
+        _check_gcr(sc)
+    arith = arith if arith is not None else model.arith
+    if not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in model.parameters()))):
+        stats = getattr(x, "_gn_stats", None)
+        v = U.stored_volume(x)
+        if v.shape[-1] % 16 != 0:
+            v, stats = U.to_stored(v, (v.shape[-1],), (U.stored_channels(v.shape[-1]),)), None
+        with torch.no_grad():
+            return model.run(v, stats, arith=arith).permute(0, 4, 1, 2, 3)
+    if x.dim() != 5 or x.dtype != torch.float32:
+        raise ValueError(f"unet3d: expected a float32 (B, C, D, H, W) volume, got {x.dtype} {tuple(x.shape)}")
+    # model.forward's reading of its input: an x that needs no gradient may carry its channel-padded storage and the producer's statistics
+    # (VolumeFeatureAggregator); they are honoured, so the forward bits are model.forward's for such an input too
+    stats = None if x.requires_grad else getattr(x, "_gn_stats", None)
+    v = U.to_channel_last(x) if x.requires_grad else U.stored_volume(x)
+    if v.shape[-1] % 16 != 0:                     # (the gradient of the zero pads is dropped here: F.pad's backward is a slice)
+        v, stats = F.pad(v, (0, U.stored_channels(v.shape[-1]) - v.shape[-1])), None
+    model.check_input(v)
+    feats = []
+    for enc in model.encoders:
+        if enc.pooling is not None:
+            v, stats = _pool(v)
+        dc = enc.basic_module
+        v, stats = _conv(dc.SingleConv1, v, None, stats, None, arith)
+        v, stats = _conv(dc.SingleConv2, v, None, stats, None, arith)
+        feats.insert(0, (v, stats))
+    for dec, (skip, skip_stats) in zip(model.decoders, feats[1:]):
+        dc = dec.basic_module
+        v, stats = _conv(dc.SingleConv1, skip, v, skip_stats, stats, arith)
+        v, stats = _conv(dc.SingleConv2, v, None, stats, None, arith)
+    fc = model.final_conv
+    return _FinalConv.apply(v, fc.weight, fc.bias, fc).permute(0, 4, 1, 2, 3)

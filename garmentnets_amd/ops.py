@@ -1345,3 +1345,166 @@ def trilinear_sample_bwd(grad_rows, vol, query, want_vol=True, want_query=False)
     if want_vol or want_query:
         _lib.call("gn_trilinear_sample_bwd", _p(grad_rows), grad_rows.stride(1), _p(vol), B, D, H, W, C, _p(query), M, _p(ws), nbytes, _p(gv), _p(gq), _stream())
     return gv, gq
+
+
+# ------------------------------------------------------------------------------------------------ UNet gradients (csrc/unet_grad.hip)
+def _vol5(t, name, like=None):
+    _chk(t, torch.float32, name)
+    if t.dim() != 5 or (like is not None and tuple(t.shape) != tuple(like.shape)):
+        raise ValueError(f"{name}: expected a channel-last volume [B][D][H][W][C]" + (f" of shape {tuple(like.shape)}" if like is not None else "")
+                         + f", got {tuple(t.shape)}")
+    return t
+
+
+def pack_conv_weight_bwd_data(w):
+    """nn.Conv3d weight (Cout, Cin, 3, 3, 3) -> the gn_conv3d_gcr pack of the layer's DATA gradient: the transposed convolution as a forward one, the
+    weight flipped over the taps and transposed over (ci, co), wt[ci][co][kd][kh][kw] = w[co][ci][2-kd][2-kh][2-kw], its output width Cin padded with
+    zero rows to a multiple of 32 (the forward kernel's rule, roles swapped): [27][Cout/16][round_up(Cin, 32)][16].  Cout % 16 == 0.  Runs on any device."""
+    cout, cin = w.shape[:2]
+    if cout % 16 != 0:
+        raise ValueError(f"pack_conv_weight_bwd_data: Cout={cout} must be a multiple of 16 (it is the input width of the transposed convolution)")
+    cin_p = -(-cin // 32) * 32
+    wt = w.detach().float().flip(2, 3, 4).transpose(0, 1)
+    if cin_p != cin:
+        wt = torch.cat((wt, wt.new_zeros((cin_p - cin,) + tuple(wt.shape[1:]))), 0)
+    return pack_conv_weight(wt.contiguous())
+
+
+def conv3d_bwd_weight(src0, src1, a, d, y, dy):
+    """-> dw (Cout, C0 + C1, 3, 3, 3) over the stored widths: the weight gradient of one 'gcr' layer (gn_conv3d_bwd_weight).  a, d: the forward's
+    GroupNorm affine [B][C0 + C1]; y: the layer's stored output (ReLU mask), None for a layer without ReLU; dy: the gradient at that output."""
+    _vol5(src0, "src0")
+    B, D, H, W, C0 = src0.shape
+    C1 = 0
+    if src1 is not None:
+        _vol5(src1, "src1")
+        C1 = src1.shape[-1]
+        if tuple(src1.shape[:4]) != (B, D // 2, H // 2, W // 2) or D % 2 or H % 2 or W % 2:
+            raise ValueError(f"conv3d_bwd_weight: src1 {tuple(src1.shape)} is not the half-resolution companion of src0 {tuple(src0.shape)}")
+    _vol5(dy, "dy")
+    cout = dy.shape[-1]
+    if tuple(dy.shape[:4]) != (B, D, H, W):
+        raise ValueError(f"conv3d_bwd_weight: dy {tuple(dy.shape)} does not match src0 {tuple(src0.shape)}")
+    if y is not None:
+        _vol5(y, "y", dy)
+    for t, name in ((a, "a"), (d, "d")):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != (B, C0 + C1):
+            raise ValueError(f"conv3d_bwd_weight: {name} must be [B][C0 + C1] = {(B, C0 + C1)}, got {tuple(t.shape)}")
+    dw = torch.empty((cout, C0 + C1, 3, 3, 3), dtype=torch.float32, device=src0.device)
+    nbytes = _lib.load().gn_conv3d_bwd_weight_workspace_bytes(B, D, H, W, C0 + C1, cout)
+    ws = _ws(nbytes, src0.device)
+    _lib.call("gn_conv3d_bwd_weight", _p(src0), C0, _p(src1), C1, _p(a), _p(d), _p(y), _p(dy), B, D, H, W, cout, _p(ws), nbytes, _p(dw), _stream())
+    return dw
+
+
+def relu_mask(y, dy, out=None):
+    """g = y > 0 ? dy : 0 (gn_relu_mask); in place when out is dy"""
+    _chk(y, torch.float32, "y")
+    _chk(dy, torch.float32, "dy")
+    if y.shape != dy.shape or y.numel() % 4 != 0:
+        raise ValueError(f"relu_mask: y {tuple(y.shape)} and dy {tuple(dy.shape)} must match, a multiple of 4 values")
+    if out is None:
+        out = torch.empty_like(dy)
+    _lib.call("gn_relu_mask", _p(y), _p(dy), y.numel(), _p(out), _stream())
+    return out
+
+
+def conv3d_bwd_data(g, wp_t, cin_p):
+    """the data gradient at a 'gcr' layer's conv operand: gn_conv3d_gcr over the (ReLU-masked) output gradient g with the pack of
+    pack_conv_weight_bwd_data, identity affine, no ReLU -> [B][D][H][W][cin_p]"""
+    _vol5(g, "g")
+    B, cout = g.shape[0], g.shape[-1]
+    one = torch.ones((B, cout), dtype=torch.float32, device=g.device)
+    return conv3d_gcr(g, None, one, torch.zeros_like(one), wp_t, cin_p, relu=False)
+
+
+def _gn_bwd_dims(dxn, goff, x, half, who):
+    _vol5(dxn, "dxn")
+    _vol5(x, "x")
+    B, D, H, W, C = x.shape
+    k = 2 if half else 1
+    if tuple(dxn.shape[:4]) != (B, k * D, k * H, k * W) or goff < 0 or goff + C > dxn.shape[-1]:
+        raise ValueError(f"{who}: dxn {tuple(dxn.shape)} (columns {goff}..{goff + C}) does not cover x {tuple(x.shape)}" + (" at twice its resolution" if half else ""))
+    return B, D, H, W, C
+
+
+def groupnorm_bwd_stats(dxn, goff, x, half=False):
+    """-> (sum dxn, sum dxn * x) fp64 [B][C] of one source of a 'gcr' layer (gn_groupnorm_bwd_stats)"""
+    B, D, H, W, C = _gn_bwd_dims(dxn, goff, x, half, "groupnorm_bwd_stats")
+    s = torch.empty((2, B, C), dtype=torch.float64, device=x.device)
+    nbytes = _lib.load().gn_groupnorm_bwd_stats_workspace_bytes(B, D * H * W, C)
+    ws = _ws(nbytes, x.device)
+    _lib.call("gn_groupnorm_bwd_stats", _p(dxn), dxn.shape[-1], int(goff), _p(x), B, D, H, W, C, 1 if half else 0, _p(ws), nbytes, _p(s[0]), _p(s[1]), _stream())
+    return s[0], s[1]
+
+
+def groupnorm_bwd_coef(t0, t1, st0, st1, groups, eps, gamma, real=None):
+    """t0 / t1: groupnorm_bwd_stats of source 0 / 1 (t1, st1 None: one source); st0 / st1: the forward's (sum, sumsq, V); real: as groupnorm_affine.
+    -> (p, q, r [B][C0 + C1 stored], dgamma, dbeta [real channels])  (gn_groupnorm_bwd_coef)"""
+    s0, q0, V0 = st0
+    B, C0 = s0.shape
+    if st1 is not None:
+        s1, q1, V1 = st1
+        C1, rep = s1.shape[1], V0 // V1
+        a1, b1 = t1
+    else:
+        s1 = q1 = a1 = b1 = None
+        C1, V1, rep = 0, 0, 1
+    r0, r1 = (C0, C1) if real is None else (int(real[0]), int(real[1]) if len(real) > 1 else 0)
+    _chk(gamma, torch.float32, "gamma")
+    if gamma.numel() != r0 + r1:
+        raise ValueError(f"groupnorm_bwd_coef: gamma has {gamma.numel()} entries for {r0 + r1} real channels")
+    for t in (t0[0], t0[1]) + ((a1, b1) if st1 is not None else ()):
+        _chk(t, torch.float64, "groupnorm_bwd_coef: sums")
+    dev = s0.device
+    pqr = torch.empty((3, B, C0 + C1), dtype=torch.float32, device=dev)
+    dgb = torch.empty((2, r0 + r1), dtype=torch.float32, device=dev)
+    _lib.call("gn_groupnorm_bwd_coef", _p(t0[0]), _p(t0[1]), _p(s0), _p(q0), r0, C0, V0, _p(a1), _p(b1), _p(s1), _p(q1), r1, C1, V1, rep, B, int(groups),
+              float(eps), _p(gamma), _p(pqr[0]), _p(pqr[1]), _p(pqr[2]), _p(dgb[0]), _p(dgb[1]), _stream())
+    return pqr[0], pqr[1], pqr[2], dgb[0], dgb[1]
+
+
+def groupnorm_bwd_apply(dxn, goff, x, p, q, r, coff, half=False, out=None):
+    """dx = dxn * p + x * q + r for one source (half: the x2 nearest upsampling's backward folded in); out given: the result is ADDED to it
+    (gn_groupnorm_bwd_apply)"""
+    B, D, H, W, C = _gn_bwd_dims(dxn, goff, x, half, "groupnorm_bwd_apply")
+    cs = p.shape[-1]
+    for t in (p, q, r):
+        _chk(t, torch.float32, "groupnorm_bwd_apply: coefficients")
+        if tuple(t.shape) != (B, cs) or coff < 0 or coff + C > cs:
+            raise ValueError(f"groupnorm_bwd_apply: coefficients must be [B][>= {coff + C}], got {tuple(t.shape)}")
+    acc = out is not None
+    if acc:
+        _vol5(out, "out", x)
+    else:
+        out = torch.empty_like(x)
+    _lib.call("gn_groupnorm_bwd_apply", _p(dxn), dxn.shape[-1], int(goff), _p(x), B, D, H, W, C, 1 if half else 0, _p(p), _p(q), _p(r), cs, int(coff),
+              1 if acc else 0, _p(out), _stream())
+    return out
+
+
+def maxpool3d_2_bwd(grad_out, x):
+    """gradient of maxpool3d_2 with respect to its stored input x [B][D][H][W][C] (even D, H, W): gn_maxpool3d_2_bwd"""
+    _vol5(x, "x")
+    _vol5(grad_out, "grad_out")
+    B, D, H, W, C = x.shape
+    if tuple(grad_out.shape) != (B, D // 2, H // 2, W // 2, C):
+        raise ValueError(f"maxpool3d_2_bwd: grad_out {tuple(grad_out.shape)} does not match the pooled shape of x {tuple(x.shape)}")
+    g = torch.empty_like(x)
+    _lib.call("gn_maxpool3d_2_bwd", _p(grad_out), _p(x), B, D, H, W, C, _p(g), _stream())
+    return g
+
+
+def linear_bwd_params(dy, x, K=None, with_bias=True):
+    """rows dy [M][N], x [M][>= K] -> (dW [N][K], db [N] or None) of y = x W^T + b (gn_linear_bwd_params)"""
+    M, N = dy.shape
+    K = x.shape[1] if K is None else int(K)
+    if x.shape[0] != M or x.shape[1] < K or dy.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError(f"linear_bwd_params: dy {tuple(dy.shape)} and x {tuple(x.shape)} are not fp32 rows of one GEMM with K={K}")
+    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    db = torch.empty(N, dtype=torch.float32, device=x.device) if with_bias else None
+    nbytes = _lib.load().gn_linear_bwd_params_workspace_bytes(M, N, K)
+    ws = _ws(nbytes, x.device)
+    _lib.call("gn_linear_bwd_params", _p(dy), rows_view(dy)[1], _p(x), rows_view(x)[1], M, N, K, _p(ws), nbytes, _p(dw), K, _p(db), _stream())
+    return dw, db

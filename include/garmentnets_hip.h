@@ -584,6 +584,49 @@ size_t gn_trilinear_sample_bwd_workspace_bytes(int B, int64_t M, int D, int H, i
 int gn_trilinear_sample_bwd(const float *grad_rows, int ldg, const float *vol, int B, int D, int H, int W, int C, const float *query, int64_t M,
                             void *ws, size_t ws_bytes, float *grad_vol, float *grad_query, void *stream);
 
+/* ---- UNet gradients (csrc/unet_grad.hip; DESIGN.md "UNet gradients").  Channel-last [B][D][H][W][C] fp32, the stored (channel-padded) layout of the
+ * forward.  No float atomics: every sum has a fixed order, identical calls give identical bits. ---- */
+
+/* Weight gradient of one GroupNorm -> Conv3d(3x3x3, pad 1) -> ReLU layer: dw[co][ci][kd][kh][kw] (nn.Conv3d's layout over the STORED widths,
+ * Cin = C0 + C1) = sum over (b, voxel) of xn[b][voxel + tap][ci] * g[b][voxel][co], xn = x*a + d inside the volume and 0 in the padding over the virtual
+ * concat [src0 (C0, full res), src1 (C1, half res, nearest-upsampled)] -- gn_conv3d_gcr's operand -- and g = dy where y > 0, else 0 (y NULL: g = dy).
+ * a, d: [B][Cin].  C0, C1 multiples of 4, Cout of 32.  Workspace: chains x 27 x round_up(Cin, 32) x Cout floats, where the B * ceil(D/4) * ceil(H/8) *
+ * ceil(W/8) tiles are cut into chains = ceil(tiles / ceil(tiles / min(tiles, ceil(512 / blocks)))) runs, blocks = ceil(Cin/32) * Cout / (Cout % 64 ? 32 : 64). */
+size_t gn_conv3d_bwd_weight_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout);
+int gn_conv3d_bwd_weight(const float *src0, int C0, const float *src1, int C1, const float *a, const float *d, const float *y, const float *dy,
+                         int B, int D, int H, int W, int Cout, void *ws, size_t ws_bytes, float *dw, void *stream);
+
+/* g = y > 0 ? dy : 0 over n floats (n % 4 == 0); g may be dy.  The data gradient of the layer is gn_conv3d_gcr(g) with the flipped / transposed pack. */
+int gn_relu_mask(const float *y, const float *dy, int64_t n, float *g, void *stream);
+
+/* nn.GroupNorm's backward over the virtual concat, per source.  dxn: the gradient at the conv's operand, [B][fine voxels][ldg], this source's channels at
+ * column goff.  x: the source as stored, [B][D][H][W][C] at its own resolution; half != 0: x is the half-resolution source (fine = 2D x 2H x 2W) and the 8
+ * fine gradients of a coarse voxel are added first in ascending (dz, dy, dx) order.
+ * _stats: s1[b][c] = sum dxn, s2[b][c] = sum dxn * x, fp64.  Workspace: B * ceil(D*H*W / 512) * 2 * C doubles.
+ * _coef:  from those sums (t1_k, t2_k: [B][Sk]), the forward's statistics (sumk, sqk: [B][Sk], Vk voxels) and gamma [C0 + C1] (Ck real channels in rows of
+ *         Sk stored ones, groups over the real channels, as gn_groupnorm_affine_map): p, q, r [B][S0 + S1] with dx = dxn*p + x*q + r (0 on the pads),
+ *         dgamma, dbeta [C0 + C1] summed over the samples in ascending order.
+ * _apply: dx = dxn*p + x*q + r; half: dx[coarse] = sum8(dxn)*p + 8*x*q + 8*r.  p / q / r rows of cs floats, this source at column coff.  accumulate != 0:
+ *         added to what dx holds. */
+size_t gn_groupnorm_bwd_stats_workspace_bytes(int B, int64_t V, int C);
+int gn_groupnorm_bwd_stats(const float *dxn, int ldg, int goff, const float *x, int B, int D, int H, int W, int C, int half, void *ws, size_t ws_bytes,
+                           double *s1, double *s2, void *stream);
+int gn_groupnorm_bwd_coef(const double *t1_0, const double *t2_0, const double *sum0, const double *sq0, int C0, int S0, int64_t V0, const double *t1_1,
+                          const double *t2_1, const double *sum1, const double *sq1, int C1, int S1, int64_t V1, int rep1, int B, int groups, float eps,
+                          const float *gamma, float *p, float *q, float *r, float *dgamma, float *dbeta, void *stream);
+int gn_groupnorm_bwd_apply(const float *dxn, int ldg, int goff, const float *x, int B, int D, int H, int W, int C, int half, const float *p, const float *q,
+                           const float *r, int cs, int coff, int accumulate, float *dx, void *stream);
+
+/* Gradient of gn_maxpool3d_2 (even D, H, W).  The winner of each 2x2x2 window is found again from the stored input by ATen's scan: (z, y, x) order, the
+ * first of equal maxima, a NaN beats every number (and a later NaN an earlier one).  grad_in: every voxel written, the losers 0. */
+int gn_maxpool3d_2_bwd(const float *grad_out, const float *in, int B, int D, int H, int W, int C, float *grad_in, void *stream);
+
+/* Parameter gradients of a row GEMM Y = X W^T + b (the final 1x1x1 convolution): dW[n][k] = sum_rows dY[row][n] * X[row][k], db[n] = sum_rows dY[row][n]
+ * (db may be NULL).  N <= 512, K <= 1023 (LDS row tiles; any N * (K + 1): blocks of 4096 outputs).  Workspace: ceil(M / 1024) * N * (K + 1) floats. */
+size_t gn_linear_bwd_params_workspace_bytes(int64_t M, int N, int K);
+int gn_linear_bwd_params(const float *dY, int ldy, const float *X, int ldx, int64_t M, int N, int K, void *ws, size_t ws_bytes, float *dW, int ldw, float *db,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
