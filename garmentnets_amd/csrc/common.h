@@ -71,18 +71,6 @@ __device__ __forceinline__ float gn_sqdist3(float ax, float ay, float az, float 
     return s;
 }
 
-// 16 bytes per lane global -> LDS DMA (wave-uniform LDS destination `lds_addr` + 16 * lane), issued from inline asm ON PURPOSE:
-// hipcc (ROCm 7.2) guards every ds_read that follows a __builtin_amdgcn_global_load_lds with s_waitcnt vmcnt(0) (it cannot prove
-// the read does not alias the DMA's destination), which drains a multi-stage ring at every step.  Users make slot reuse safe by
-// hand (counted s_waitcnt vmcnt(N) + s_barrier) and must not use m0 otherwise.
-__device__ __forceinline__ void gn_glds16(const void *g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
-}
-// s_waitcnt vmcnt(N) lgkmcnt(0)   (gfx9 immediate: vmcnt[3:0] | expcnt[6:4] = 7 (no wait) | lgkmcnt[11:8] | vmcnt_hi[15:14])
-// s_waitcnt vmcnt(N) alone (lgkmcnt field = 15: no wait)
-#define GN_WAIT_VM_ONLY(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | 0xF00 | (((N) >> 4) << 14))
-#define GN_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | (((N) >> 4) << 14))
-
 // ReLU with torch's NaN behaviour (relu(NaN) = NaN).  fmaxf(v, 0) would return 0 for a NaN and turn an upstream overflow
 // (e.g. an activation beyond the fp16 range in the split-operand kernels) into a silently wrong finite result.
 // IEEE 754-2019 maximum(v, 0) -- NaN-propagating -- is ONE gfx950 instruction (v_maximum3_f32 v, v, 0, 0); the C form `v < 0 ? 0 : v`
@@ -90,19 +78,5 @@ __device__ __forceinline__ void gn_glds16(const void *g, unsigned lds_addr) {
 // layer hand-over).  Same values; the only bit that can differ is the sign of a zero (maximum(-0, +0) = +0, the C form kept -0).
 __device__ __forceinline__ float gn_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
 
-// Exact residual of an fp32 value r against one half of a packed fp16 pair h2 in ONE instruction: v_fma_mix_f32 reads the fp16 half in place,
-// fma(f32(h), -1, r) = r - f32(h) with one rounding -- of a value that IS representable when h = fp16_rn(r) or any fp16 within the split's range (the
-// difference has at most 13 significant bits), so the result is bit-identical to v_cvt_f32_f16 + v_sub_f32 (hipcc's selection for the C
-// expression: two instructions per value; the plane split is the largest VALU item of every f16x2 kernel).  Not volatile: schedulable, removable.
-__device__ __forceinline__ float gn_resid_lo(unsigned h2, float r) {
-    float o;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(o) : "v"(h2), "v"(r));
-    return o;
-}
-__device__ __forceinline__ float gn_resid_hi(unsigned h2, float r) {
-    float o;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(h2), "v"(r));
-    return o;
-}
-
-__device__ __forceinline__ int gn_lane() { return threadIdx.x & 63; }
+// vector types, reductions, float orders, MFMA / plane split, LDS DMA, sampler arithmetic, tile geometry
+#include "device_prims.h"

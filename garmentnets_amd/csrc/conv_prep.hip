@@ -129,8 +129,7 @@ __global__ __launch_bounds__(256) void cprep_pack_kernel(const float *__restrict
     const int S = (int)(q / 27);
     const int h = lane >> 5, r = lane & 31, n = blk * 32 + r;
     const float rs = rowscale[(int64_t)b * Cout + n];
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    h8 p1, p2;
+    f16x8 p1, p2;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = S * 16 + 8 * h + i;
@@ -161,8 +160,7 @@ __global__ __launch_bounds__(256) void cprep_pack_wino_kernel(const float *__res
     const int j = step / 9, kdh = step % 9;
     const int h = lane >> 5, r = lane & 31, n = blk * 32 + r;
     const double rs = (double)rowscale[(int64_t)b * Cout + n];
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    h8 p1, p2;
+    f16x8 p1, p2;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = S * 16 + 8 * h + i;

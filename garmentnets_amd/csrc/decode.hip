@@ -6,13 +6,6 @@
 // differences, accumulation order tnw,tne,tsw,tse,bnw,bne,bsw,bse).
 #include "common.h"
 
-__device__ __forceinline__ float src_index(float q, int size) {
-    // qn = 2q-1 ; ((qn+1)/2)*(size-1) ; clip to [0,size-1]
-    float qn = __fsub_rn(__fmul_rn(2.0f, q), 1.0f);
-    float x = __fmul_rn(__fdiv_rn(__fadd_rn(qn, 1.0f), 2.0f), (float)(size - 1));
-    return fminf((float)(size - 1), fmaxf(x, 0.0f));
-}
-
 // one query, channels over the lanes of one wavefront
 __device__ __forceinline__ void tri_query(const float *__restrict__ vol, int D, int H, int W, int C, const float *__restrict__ query,
                                           int Q, int64_t m0, int64_t m, float *__restrict__ out, int ldo, int lane) {
@@ -29,20 +22,16 @@ __device__ __forceinline__ void tri_query(const float *__restrict__ vol, int D, 
         qy = __fadd_rn(__fmul_rn((float)j, sc), -0.0f);
         qz = __fadd_rn(__fmul_rn((float)k, sc), -0.0f);
     }
-    const float ix = src_index(qx, W), iy = src_index(qy, H), iz = src_index(qz, D);
-    const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-    const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
-    const float wx1 = __fsub_rn(ix, fx0), wx0 = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-    const float wy1 = __fsub_rn(iy, fy0), wy0 = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-    const float wz1 = __fsub_rn(iz, fz0), wz0 = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
+    const float ix = gn_tri_src_index(qx, W), iy = gn_tri_src_index(qy, H), iz = gn_tri_src_index(qz, D);
+    const GnTriCell t = gn_tri_cell(ix, iy, iz);
     float wgt[8];
     int64_t off[8];
     bool ok[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;  // order tnw,tne,tsw,tse,bnw,bne,bsw,bse
-        wgt[c] = __fmul_rn(__fmul_rn(dx ? wx1 : wx0, dy ? wy1 : wy0), dz ? wz1 : wz0);
-        const int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
+        wgt[c] = gn_tri_weight(t, c);
+        const int xx = t.x0 + dx, yy = t.y0 + dy, zz = t.z0 + dz;
         ok[c] = xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < D;
         off[c] = (((int64_t)zz * H + yy) * W + xx) * C;
     }
@@ -138,9 +127,9 @@ __global__ __launch_bounds__(256) void trilinear_brick_kernel(const float *__res
     const int i0 = i_begin + bi * TB_I, j0 = bj * TB_J, k0 = bk * TB_K;
     const int i1 = min(i0 + TB_I, i_end) - 1, j1 = min(j0 + TB_J, Q) - 1, k1 = min(k0 + TB_K, Q) - 1;   // last lattice point per axis
     // voxel bounding box of the brick (src_index is monotonic): query component 0 (i) indexes the LAST volume axis
-    const int lx = (int)floorf(src_index(tb_coord(i0, Q), W)), hx = min((int)floorf(src_index(tb_coord(i1, Q), W)) + 1, W - 1);
-    const int ly = (int)floorf(src_index(tb_coord(j0, Q), H)), hy = min((int)floorf(src_index(tb_coord(j1, Q), H)) + 1, H - 1);
-    const int lz = (int)floorf(src_index(tb_coord(k0, Q), D)), hz = min((int)floorf(src_index(tb_coord(k1, Q), D)) + 1, D - 1);
+    const int lx = (int)floorf(gn_tri_src_index(tb_coord(i0, Q), W)), hx = min((int)floorf(gn_tri_src_index(tb_coord(i1, Q), W)) + 1, W - 1);
+    const int ly = (int)floorf(gn_tri_src_index(tb_coord(j0, Q), H)), hy = min((int)floorf(gn_tri_src_index(tb_coord(j1, Q), H)) + 1, H - 1);
+    const int lz = (int)floorf(gn_tri_src_index(tb_coord(k0, Q), D)), hz = min((int)floorf(gn_tri_src_index(tb_coord(k1, Q), D)) + 1, D - 1);
     const int ex = hx - lx + 1, ey = hy - ly + 1, ez = hz - lz + 1, nvox = ex * ey * ez;
     const bool in_lds = nvox <= cap_vox;            // always true for Q >= size (host-side bound); otherwise read the corners from L2
 
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(256) void trilinear_brick_kernel(const float *__res
         const int kk = ql % TB_K, jj = (ql / TB_K) % TB_J, ii = ql / (TB_K * TB_J);
         const int i = i0 + ii, j = j0 + jj, k = k0 + kk;
         const bool live = i <= i1 && j <= j1 && k <= k1;
-        const float ix = src_index(tb_coord(live ? i : i0, Q), W), iy = src_index(tb_coord(live ? j : j0, Q), H), iz = src_index(tb_coord(live ? k : k0, Q), D);
+        const float ix = gn_tri_src_index(tb_coord(live ? i : i0, Q), W), iy = gn_tri_src_index(tb_coord(live ? j : j0, Q), H), iz = gn_tri_src_index(tb_coord(live ? k : k0, Q), D);
         const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
         const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
         const float wx1 = __fsub_rn(ix, fx0), wx0 = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
@@ -280,8 +269,6 @@ extern "C" int gn_trilinear_sample_batch(const float *vol, int B, int64_t vol_bs
 // Wp[k/16][n][2][8] (see dec_layer), so the B operands of 8 consecutive MFMAs are two coalesced 16-byte loads per lane,
 // register double-buffered one 16-deep k-group ahead.  Each wave owns 64 output columns of a
 // 256-column block (2 column fragments x 1 row fragment = 32 accumulator registers).
-typedef float f32x16d __attribute__((ext_vector_type(16)));
-
 struct DecodeArgs {
     const float *vol; int D, H, W, C0;
     const float *xin; int ldxin;          // optional pre-sampled features [M][C0] (then vol/query are unused)
@@ -306,24 +293,13 @@ struct DecodeArgs {
 // in flight while the 16 MFMAs of group g issue.
 struct BFrag { float4 lo, hi; };
 
-__device__ __forceinline__ void dec_mfma8(const float4 &a0, const float4 &a1, const BFrag &b0, const BFrag &b1, f32x16d &acc0, f32x16d &acc1) {
+__device__ __forceinline__ void dec_mfma8(const float4 &a0, const float4 &a1, const BFrag &b0, const BFrag &b1, f32x16 &acc0, f32x16 &acc1) {
 #define DEC_STEP(A, B0, B1)                                                   \
     acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B0, acc0, 0, 0, 0);        \
     acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B1, acc1, 0, 0, 0);
     DEC_STEP(a0.x, b0.lo.x, b1.lo.x) DEC_STEP(a0.y, b0.lo.y, b1.lo.y) DEC_STEP(a0.z, b0.lo.z, b1.lo.z) DEC_STEP(a0.w, b0.lo.w, b1.lo.w)
     DEC_STEP(a1.x, b0.hi.x, b1.hi.x) DEC_STEP(a1.y, b0.hi.y, b1.hi.y) DEC_STEP(a1.z, b0.hi.z, b1.hi.z) DEC_STEP(a1.w, b0.hi.w, b1.hi.w)
 #undef DEC_STEP
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dec_dpp(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-// sum over the 16 lanes of a DPP row (quad xor 1, quad xor 2, row_half_mirror, row_mirror); every lane gets the sum
-__device__ __forceinline__ float dec_row_sum(float v) {
-    v += dec_dpp<0xB1>(v);
-    v += dec_dpp<0x4E>(v);
-    v += dec_dpp<0x141>(v);
-    v += dec_dpp<0x140>(v);
-    return v;
 }
 
 // OUTC == 0: write Y = bn(relu(X W^T + b)) to LDS.  OUTC > 0: this is the last hidden layer -- its activations never
@@ -346,7 +322,7 @@ __device__ __forceinline__ void dec_layer(const float *__restrict__ X, int ldx, 
     const size_t gstride = (size_t)N * 4;                                           // float4 per k-group of the pack
     for (int nb = 0; nb < N; nb += 256) {
         const int n0 = nb + wave * 64;
-        f32x16d acc0, acc1;
+        f32x16 acc0, acc1;
 #pragma unroll
         for (int q = 0; q < 16; ++q) { acc0[q] = 0.f; acc1[q] = 0.f; }
         const float4 *w0 = reinterpret_cast<const float4 *>(Wp) + ((size_t)(n0 + r) * 2 + h) * 2;   // column fragment 0
@@ -403,7 +379,7 @@ __device__ __forceinline__ void dec_layer(const float *__restrict__ X, int ldx, 
             const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
 #pragma unroll
             for (int o = 0; o < (OUTC > 0 ? OUTC : 1); ++o) {
-                const float sum = dec_row_sum(psum[q][o]);
+                const float sum = gn_row_sum(psum[q][o]);
                 if ((lane & 15) == 0) red[(part * DEC_TM + row) * OUTC + o] = sum;
             }
         }
@@ -448,7 +424,7 @@ __global__ __launch_bounds__(256, 3) void implicit_decode_kernel(DecodeArgs p) {
             qy = __fadd_rn(__fmul_rn((float)j, sc), -0.0f);
             qz = __fadd_rn(__fmul_rn((float)k, sc), -0.0f);
         }
-        const float ix = src_index(qx, p.W), iy = src_index(qy, p.H), iz = src_index(qz, p.D);
+        const float ix = gn_tri_src_index(qx, p.W), iy = gn_tri_src_index(qy, p.H), iz = gn_tri_src_index(qz, p.D);
         const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
         const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
         const float wx1 = __fsub_rn(ix, fx0), wx0 = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);

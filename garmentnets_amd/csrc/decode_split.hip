@@ -31,10 +31,6 @@
 //    tile's rows 64 VGPRs.
 #include "common.h"
 
-typedef float f32x16q __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2q __attribute__((ext_vector_type(2)));
 
 #define DS_K0 128
 #define DS_N 256
@@ -64,30 +60,23 @@ struct LatQuery {
     unsigned ok1;                    // bit 0 / 1 / 2: x0+1 / y0+1 / z0+1 inside the volume (the lower corners always are, after the border clamp)
 };
 
-__device__ __forceinline__ float lat_src_index(float q, int size) {        // = src_index of decode.hip
-    const float qn = __fsub_rn(__fmul_rn(2.0f, q), 1.0f);
-    const float x = __fmul_rn(__fdiv_rn(__fadd_rn(qn, 1.0f), 2.0f), (float)(size - 1));
-    return fminf((float)(size - 1), fmaxf(x, 0.0f));
-}
-
 __device__ __forceinline__ LatQuery lat_setup(const DecSplitArgs &p, long long m, int h) {
     const unsigned g = (unsigned)(p.m0 + m), uq = (unsigned)p.Q;          // Q^3 < 2^32 (checked on the host): 32-bit divides
     const unsigned gq = g / uq;
     const int k = (int)(g - gq * uq), i = (int)(gq / uq), j = (int)(gq - (unsigned)i * uq);
     const float sc = __fdiv_rn(1.0f, __fsub_rn((float)p.Q, 1.0f));
     const float qx = __fadd_rn(__fmul_rn((float)i, sc), -0.0f), qy = __fadd_rn(__fmul_rn((float)j, sc), -0.0f), qz = __fadd_rn(__fmul_rn((float)k, sc), -0.0f);
-    const float ix = lat_src_index(qx, p.W), iy = lat_src_index(qy, p.H), iz = lat_src_index(qz, p.D);     // component 0 indexes the LAST volume axis
-    const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-    const int x0 = (int)fx0, y0 = (int)fy0, z0 = (int)fz0;
+    const float ix = gn_tri_src_index(qx, p.W), iy = gn_tri_src_index(qy, p.H), iz = gn_tri_src_index(qz, p.D);     // component 0 indexes the LAST volume axis
+    const GnTriCell t = gn_tri_cell(ix, iy, iz);
+    const int x0 = t.x0, y0 = t.y0, z0 = t.z0;
     LatQuery q;
-    q.wx1 = __fsub_rn(ix, fx0); q.wx0 = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-    q.wy1 = __fsub_rn(iy, fy0); q.wy0 = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-    q.wz1 = __fsub_rn(iz, fz0); q.wz0 = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
+    q.wx0 = t.wx[0]; q.wx1 = t.wx[1]; q.wy0 = t.wy[0]; q.wy1 = t.wy[1]; q.wz0 = t.wz[0]; q.wz1 = t.wz[1];
     q.ok1 = (x0 + 1 < p.W ? 1u : 0u) | (y0 + 1 < p.H ? 2u : 0u) | (z0 + 1 < p.D ? 4u : 0u);
     q.goff = ((unsigned)((z0 * p.H + y0) * p.W + x0) * 32u + 8u * (unsigned)h) * 4u;
     return q;
 }
 __device__ __forceinline__ bool lat_ok(const LatQuery &q, int c) { return ((c & 1) == 0 || (q.ok1 & 1u)) && ((c & 2) == 0 || (q.ok1 & 2u)) && ((c & 4) == 0 || (q.ok1 & 4u)); }
+// gn_tri_weight on the record's scalar copies (they are what travels through LDS; a GnTriCell inside the record changed the lattice kernel's code)
 __device__ __forceinline__ float lat_weight(const LatQuery &q, int c) {
     return __fmul_rn(__fmul_rn((c & 1) ? q.wx1 : q.wx0, (c & 2) ? q.wy1 : q.wy0), (c & 4) ? q.wz1 : q.wz0);
 }
@@ -95,11 +84,10 @@ __device__ __forceinline__ float lat_weight(const LatQuery &q, int c) {
 __device__ __forceinline__ unsigned lat_corner(const DecSplitArgs &p, const LatQuery &q, int c) {
     return lat_ok(q, c) ? q.goff + (unsigned)((((c >> 2) * p.H + ((c >> 1) & 1)) * p.W + (c & 1)) * 128) : q.goff;
 }
-typedef float lat_f4 __attribute__((ext_vector_type(4)));
 // the four float4 of one corner, issued from inline asm (scalar base + 32-bit offset): invisible to hipcc's vmcnt bookkeeping, which would
 // otherwise drain the weight-DMA ring at every use; the caller waits by hand (counted s_waitcnt) and pins the first use behind that wait
 // half a corner (2 float4 = 8 of the lane's 16 channels; half 0: channels 8h.., half 1: 16 + 8h..)
-__device__ __forceinline__ void lat_issue(const float *vol, unsigned off, int half, lat_f4 (&t)[2]) {
+__device__ __forceinline__ void lat_issue(const float *vol, unsigned off, int half, f32x4 (&t)[2]) {
     if (half == 0) {
         asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(t[0]) : "v"(off), "s"(vol) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(t[1]) : "v"(off), "s"(vol) : "memory");
@@ -109,54 +97,12 @@ __device__ __forceinline__ void lat_issue(const float *vol, unsigned off, int ha
     }
 }
 
-__device__ __forceinline__ void ds_split2(float a, float b, unsigned &p1, unsigned &p2) {
-    const f32x2q v = {a, b};
-    const h16x2 x1 = __builtin_convertvector(v, h16x2);
-    p1 = __builtin_bit_cast(unsigned, x1);
-    const f32x2q res = {gn_resid_lo(p1, a), gn_resid_hi(p1, b)};      // (exact residuals, one v_fma_mix_f32 each: common.h)
-    const h16x2 x2 = __builtin_convertvector(res, h16x2);
-    p2 = __builtin_bit_cast(unsigned, x2);
-}
-
 // bias + ReLU of an accumulator register quad: the adds as two v_pk_add_f32 (the same IEEE additions, half the issue slots), the ReLU as one v_maximum3_f32 each (gn_relu)
 __device__ __forceinline__ void ds_bias_relu4(float a0, float a1, float a2, float a3, const float4 &bv, float &v0, float &v1, float &v2, float &v3) {
-    const f32x2q s01 = (f32x2q){a0, a1} + (f32x2q){bv.x, bv.y};
-    const f32x2q s23 = (f32x2q){a2, a3} + (f32x2q){bv.z, bv.w};
+    const f32x2 s01 = (f32x2){a0, a1} + (f32x2){bv.x, bv.y};
+    const f32x2 s23 = (f32x2){a2, a3} + (f32x2){bv.z, bv.w};
     v0 = gn_relu(s01.x); v1 = gn_relu(s01.y); v2 = gn_relu(s23.x); v3 = gn_relu(s23.y);
 }
-
-__device__ __forceinline__ f32x16q ds_mfma(const uint4 &a, const uint4 &b, const f32x16q &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-}
-
-// The weight DMA is issued from inline asm ON PURPOSE: hipcc (ROCm 7.2) guards every ds_read that follows a
-// __builtin_amdgcn_global_load_lds with s_waitcnt vmcnt(0) (it cannot prove the read does not alias the DMA's LDS
-// destination), which would drain the three-stage-deep ring at every k-group.  Slot reuse is made safe by hand instead: the
-// counted s_waitcnt + s_barrier of the stage hand-over.  Measured (262144 rows): 0.165 ms with the asm DMA, 0.201 ms with the
-// builtin, 0.545 ms for the fp32-MFMA kernel.  (m0 = LDS byte address of the wave's 1-KB destination; lane i lands at
-// +16 i.  Nothing else in this kernel uses m0.)
-__device__ __forceinline__ void ds_glds16(const void *g, unsigned lds_addr) {  // = gn_glds16 (common.h)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
-}
-// the same with a wave-uniform base in SGPRs and a 32-bit per-lane byte offset: no 64-bit VALU address arithmetic per piece
-__device__ __forceinline__ void ds_glds16_s(const void *sbase, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-}
-
-// a wave's four 1-KB pieces of one stage in one statement: ONE scalar base and ONE m0 value, the pieces told apart by the instruction's immediate
-// offset -- which the hardware adds to the global AND to the LDS address (LLVM's llvm.amdgcn.global.load.lds: "imm offset (applied to both global
-// and LDS address)"), and both step by 1024 from piece to piece.  Four statements with four bases made hipcc keep 72 address pairs in SGPRs across
-// the tile loop and spill them into VGPR lanes: 79 - 130 v_readlane_b32 per tile in the VALU stream of a VALU-issue-bound kernel.
-__device__ __forceinline__ void ds_glds16x4_s(const void *sbase, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %0, %1\n\t"
-                 "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
-                 "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %0, %1 offset:3072" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-}
-
-// s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14]); expcnt left at 7 (no wait)
-#define DS_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | (((N) >> 4) << 14))
 
 // K0G = 16-deep k-groups of the first layer: 8 for the plain [128, 256, 256, OUT] decoder (the non-default path: its 448 live
 // registers no longer fit without ~40 spilled values since the NaN-propagating ReLU, 0.34 ms per 262144 rows), 2 when the UNet's final 1x1x1
@@ -206,7 +152,7 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
     static_assert(!LAT || SB_ZERO, "the 3-stage ring is indexed with compile-time slots");
 #define DS_SB (SB_ZERO ? 0 : sb)
 #define DS_ISSUE(STAGE, SLOT)                                                                                                  \
-    ds_glds16x4_s(wsrc + (size_t)(STAGE) * DS_STAGE_BYTES, lane16, lds_base + (SLOT) * DS_STAGE_BYTES + (wave * 4) * 1024);
+    gn_glds16x4_s(wsrc + (size_t)(STAGE) * DS_STAGE_BYTES, lane16, lds_base + (SLOT) * DS_STAGE_BYTES + (wave * 4) * 1024);
     DS_ISSUE(0, 0) DS_ISSUE(1, 1) DS_ISSUE(2, 2)
     if (!LAT) { DS_ISSUE(3, 3) }
 
@@ -239,7 +185,7 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
             for (int g = 0; g < K0G; ++g) { raw[2 * g] = row[4 * g]; raw[2 * g + 1] = row[4 * g + 1]; }
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0): prologue DMAs + table stores
+    GN_WAIT_ALL();                                   // vmcnt(0) lgkmcnt(0): prologue DMAs + table stores
     __syncthreads();
 
     const unsigned char *const ring_rd = smem + lane * 16;
@@ -252,21 +198,21 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
         uint4 x0[2][K0G], h1[2][16];
 #pragma unroll
         for (int g = 0; g < K0G; ++g) {
-            ds_split2(__fmul_rn(raw[2 * g].x, sx), __fmul_rn(raw[2 * g].y, sx), x0[0][g].x, x0[1][g].x);
-            ds_split2(__fmul_rn(raw[2 * g].z, sx), __fmul_rn(raw[2 * g].w, sx), x0[0][g].y, x0[1][g].y);
-            ds_split2(__fmul_rn(raw[2 * g + 1].x, sx), __fmul_rn(raw[2 * g + 1].y, sx), x0[0][g].z, x0[1][g].z);
-            ds_split2(__fmul_rn(raw[2 * g + 1].z, sx), __fmul_rn(raw[2 * g + 1].w, sx), x0[0][g].w, x0[1][g].w);
+            split2(__fmul_rn(raw[2 * g].x, sx), __fmul_rn(raw[2 * g].y, sx), x0[0][g].x, x0[1][g].x);
+            split2(__fmul_rn(raw[2 * g].z, sx), __fmul_rn(raw[2 * g].w, sx), x0[0][g].y, x0[1][g].y);
+            split2(__fmul_rn(raw[2 * g + 1].x, sx), __fmul_rn(raw[2 * g + 1].y, sx), x0[0][g].z, x0[1][g].z);
+            split2(__fmul_rn(raw[2 * g + 1].z, sx), __fmul_rn(raw[2 * g + 1].w, sx), x0[0][g].w, x0[1][g].w);
         }
         float psum[OUTC];
 #pragma unroll
         for (int o = 0; o < OUTC; ++o) psum[o] = 0.f;
         // LAT: the NEXT tile's rows are gathered under this tile's MFMAs -- batch b = (corner b >> 1, channel half b & 1) is issued at the hand-over
         // of stage LAT_T0 + b and consumed at the next hand-over: 8 registers in flight; accumulators and query record live in LDS
-        lat_f4 lt[2];
+        f32x4 lt[2];
         constexpr int LAT_T0 = 1, LAT_NB = 16;
         static_assert(!LAT || LAT_T0 + LAT_NB == NSTAGE - 1, "the last batch is consumed at the tile's last hand-over");
         // two accumulator sets: the epilogue of block pair P-1 (VALU) is spread over the MFMAs of the steps that follow it
-        f32x16q acc[NSETS][2];
+        f32x16 acc[NSETS][2];
 
         // epilogue of registers [4 qd, 4 qd + 4) of both blocks of block pair P (0-3: layer 1, 4-7: layer 2)
         auto epilogue = [&](int P, int qd) {
@@ -281,11 +227,11 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
                     // registers 0-7 -> k-group 2nb, 8-15 -> k-group 2nb+1 of layer 2; a register quad fills half a fragment
                     const int g2 = 2 * nb + (qd >> 1);
                     if (qd & 1) {
-                        ds_split2(v0, v1, h1[0][g2].z, h1[1][g2].z);
-                        ds_split2(v2, v3, h1[0][g2].w, h1[1][g2].w);
+                        split2(v0, v1, h1[0][g2].z, h1[1][g2].z);
+                        split2(v2, v3, h1[0][g2].w, h1[1][g2].w);
                     } else {
-                        ds_split2(v0, v1, h1[0][g2].x, h1[1][g2].x);
-                        ds_split2(v2, v3, h1[0][g2].y, h1[1][g2].y);
+                        split2(v0, v1, h1[0][g2].x, h1[1][g2].x);
+                        split2(v2, v3, h1[0][g2].y, h1[1][g2].y);
                     }
                 } else {
                     const int nb = 2 * (P - 4) + blk;
@@ -327,9 +273,9 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
                 // LAT: VM queue, oldest first, with the corner loads issued BEFORE the stage's DMAs: G(t-3) DMA(t+1) G(t-2) DMA(t+2) G(t-1) DMA(t+3);
                 // the corner issued one hand-over ago must have landed: everything but DMA(t+3)
                 // LAT (3-stage ring, the batch's two loads issued BEFORE the stage's DMAs): G(t-2) DMA(t+1) G(t-1) DMA(t+2) -> everything but DMA(t+2)
-                if (LAT) DS_WAIT_VM_LGKM0(4);
-                else if (t > RAW_STAGE && t <= RAW_STAGE + 3) DS_WAIT_VM_LGKM0(8 + NRAW);
-                else DS_WAIT_VM_LGKM0(8);
+                if (LAT) GN_WAIT_VM_LGKM0(4);
+                else if (t > RAW_STAGE && t <= RAW_STAGE + 3) GN_WAIT_VM_LGKM0(8 + NRAW);
+                else GN_WAIT_VM_LGKM0(8);
                 __builtin_amdgcn_s_barrier();
                 if constexpr (LAT) {
                     if (t == LAT_T0) {                                    // next tile's query (clamped: the last tile re-samples its own)
@@ -393,12 +339,12 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
             }
             const uint4 b1 = l1 ? x0[0][g % K0G] : h1[0][g], b2 = l1 ? x0[1][g % K0G] : h1[1][g];
             // A: [blk0 w1, blk0 w2, blk1 w1, blk1 w2]; smallest terms first
-            acc[set][0] = ds_mfma(A[1], b1, acc[set][0]);
-            acc[set][1] = ds_mfma(A[3], b1, acc[set][1]);
-            acc[set][0] = ds_mfma(A[0], b2, acc[set][0]);
-            acc[set][1] = ds_mfma(A[2], b2, acc[set][1]);
-            acc[set][0] = ds_mfma(A[0], b1, acc[set][0]);
-            acc[set][1] = ds_mfma(A[2], b1, acc[set][1]);
+            acc[set][0] = mfma16<true>(A[1], b1, acc[set][0]);
+            acc[set][1] = mfma16<true>(A[3], b1, acc[set][1]);
+            acc[set][0] = mfma16<true>(A[0], b2, acc[set][0]);
+            acc[set][1] = mfma16<true>(A[2], b2, acc[set][1]);
+            acc[set][0] = mfma16<true>(A[0], b1, acc[set][0]);
+            acc[set][1] = mfma16<true>(A[2], b1, acc[set][1]);
             // the epilogue of an earlier pair rides along: pair Pp finished at step Lp; its 4 register quads are handled during the
             // NCH steps that follow (NCH <= K0G for layer 1, so that they are done before pair Pp + 2 reuses the accumulator set).
             // With a single accumulator set the pair's epilogue runs right after its last step instead.
@@ -443,7 +389,7 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
     }
 #undef DS_ISSUE
 #undef DS_SB
-    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0): the wrapped-around DMAs must land before the LDS goes away
+    GN_WAIT_ALL();                                   // vmcnt(0) lgkmcnt(0): the wrapped-around DMAs must land before the LDS goes away
     __syncthreads();
 }
 // Note on the counted waits.  VM operations retire in issue order.  At the hand-over of stage t the queue holds the DMAs of
@@ -492,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
     const unsigned lane16 = lane * 16;
     // stage `st` (0 .. NSTAGE-1, wrapping into the next tile) -> ring slot `slot`
     auto issue = [&](int st, int slot) {
-        ds_glds16x4_s(wsrc + (size_t)st * DS_STAGE_BYTES, lane16, lds_base + slot * DS_STAGE_BYTES + (wave * 4) * 1024);
+        gn_glds16x4_s(wsrc + (size_t)st * DS_STAGE_BYTES, lane16, lds_base + slot * DS_STAGE_BYTES + (wave * 4) * 1024);
     };
     issue(0, 0); issue(1, 1); issue(2, 2); issue(3, 3);
 
@@ -503,7 +449,7 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
         const float4 *row = reinterpret_cast<const float4 *>(p.xin + m * p.ldxin + 8 * h);
         raw[0] = row[0]; raw[1] = row[1]; raw[2] = row[4]; raw[3] = row[5];
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0): prologue DMAs + table stores
+    GN_WAIT_ALL();                                   // vmcnt(0) lgkmcnt(0): prologue DMAs + table stores
     __syncthreads();
 
     const unsigned char *const ring_rd = smem + lane * 16;
@@ -515,18 +461,18 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
         uint4 x0[2][K0G], h1[2][KG2];
 #pragma unroll
         for (int g = 0; g < K0G; ++g) {
-            ds_split2(__fmul_rn(raw[2 * g].x, sx), __fmul_rn(raw[2 * g].y, sx), x0[0][g].x, x0[1][g].x);
-            ds_split2(__fmul_rn(raw[2 * g].z, sx), __fmul_rn(raw[2 * g].w, sx), x0[0][g].y, x0[1][g].y);
-            ds_split2(__fmul_rn(raw[2 * g + 1].x, sx), __fmul_rn(raw[2 * g + 1].y, sx), x0[0][g].z, x0[1][g].z);
-            ds_split2(__fmul_rn(raw[2 * g + 1].z, sx), __fmul_rn(raw[2 * g + 1].w, sx), x0[0][g].w, x0[1][g].w);
+            split2(__fmul_rn(raw[2 * g].x, sx), __fmul_rn(raw[2 * g].y, sx), x0[0][g].x, x0[1][g].x);
+            split2(__fmul_rn(raw[2 * g].z, sx), __fmul_rn(raw[2 * g].w, sx), x0[0][g].y, x0[1][g].y);
+            split2(__fmul_rn(raw[2 * g + 1].x, sx), __fmul_rn(raw[2 * g + 1].y, sx), x0[0][g].z, x0[1][g].z);
+            split2(__fmul_rn(raw[2 * g + 1].z, sx), __fmul_rn(raw[2 * g + 1].w, sx), x0[0][g].w, x0[1][g].w);
         }
         float psum[OUTC];
 #pragma unroll
         for (int o = 0; o < OUTC; ++o) psum[o] = 0.f;
-        f32x16q acc[2][2];
+        f32x16 acc[2][2];
 
         // one k-group step: stage slot `slot` (compile-time), k-group slot kg inside it; `next_stage` = the stage to request at a hand-over (kg == 3)
-        auto step = [&](int kg, int slot, int next_stage, const uint4 &b1, const uint4 &b2, f32x16q (&ac)[2]) {
+        auto step = [&](int kg, int slot, int next_stage, const uint4 &b1, const uint4 &b2, f32x16 (&ac)[2]) {
 #pragma unroll
             for (int f = 0; f < 4; ++f) A[f] = nA[f];
             if (kg < 3) {
@@ -535,21 +481,21 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
             } else {
                 // hand-over: the next stage has landed for everybody (VM queue: three stages of four pieces; at most 8 may remain), this stage has
                 // been read by everybody -> its slot takes the stage three ahead
-                DS_WAIT_VM_LGKM0(8);
+                GN_WAIT_VM_LGKM0(8);
                 __builtin_amdgcn_s_barrier();
                 issue(next_stage, slot);
 #pragma unroll
                 for (int f = 0; f < 4; ++f) nA[f] = *reinterpret_cast<const uint4 *>(ring_rd + ((slot + 1) % DS_RING) * DS_STAGE_BYTES + f * 1024);
             }
-            ac[0] = ds_mfma(A[1], b1, ac[0]);
-            ac[1] = ds_mfma(A[3], b1, ac[1]);
-            ac[0] = ds_mfma(A[0], b2, ac[0]);
-            ac[1] = ds_mfma(A[2], b2, ac[1]);
-            ac[0] = ds_mfma(A[0], b1, ac[0]);
-            ac[1] = ds_mfma(A[2], b1, ac[1]);
+            ac[0] = mfma16<true>(A[1], b1, ac[0]);
+            ac[1] = mfma16<true>(A[3], b1, ac[1]);
+            ac[0] = mfma16<true>(A[0], b2, ac[0]);
+            ac[1] = mfma16<true>(A[2], b2, ac[1]);
+            ac[0] = mfma16<true>(A[0], b1, ac[0]);
+            ac[1] = mfma16<true>(A[2], b1, ac[1]);
         };
         // layer-1 epilogue of registers [4 qd, 4 qd + 4) of both blocks of pair P -> the layer-2 operand planes (k-groups 2 nb, 2 nb + 1)
-        auto epi1 = [&](int P, int qd, f32x16q (&ac)[2]) {
+        auto epi1 = [&](int P, int qd, f32x16 (&ac)[2]) {
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
                 const int nb = 2 * P + blk;
@@ -558,20 +504,20 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
                 ds_bias_relu4(ac[blk][4 * qd + 0], ac[blk][4 * qd + 1], ac[blk][4 * qd + 2], ac[blk][4 * qd + 3], bv, v0, v1, v2, v3);
                 const int g2 = 2 * nb + (qd >> 1);
                 if (qd & 1) {
-                    ds_split2(v0, v1, h1[0][g2].z, h1[1][g2].z);
-                    ds_split2(v2, v3, h1[0][g2].w, h1[1][g2].w);
+                    split2(v0, v1, h1[0][g2].z, h1[1][g2].z);
+                    split2(v2, v3, h1[0][g2].w, h1[1][g2].w);
                     // (the layer-2 operand planes are pinned into AGPRs where they are produced: MFMA B operands may be AGPRs, and without the pin hipcc
                     //  spills 34 values around the MFMA stream; with it: no scratch, 402 -> 432 TF-eq, same digests)
                     asm volatile("" : "+a"(h1[0][g2].z), "+a"(h1[1][g2].z), "+a"(h1[0][g2].w), "+a"(h1[1][g2].w));
                 } else {
-                    ds_split2(v0, v1, h1[0][g2].x, h1[1][g2].x);
-                    ds_split2(v2, v3, h1[0][g2].y, h1[1][g2].y);
+                    split2(v0, v1, h1[0][g2].x, h1[1][g2].x);
+                    split2(v2, v3, h1[0][g2].y, h1[1][g2].y);
                     asm volatile("" : "+a"(h1[0][g2].x), "+a"(h1[1][g2].x), "+a"(h1[0][g2].y), "+a"(h1[1][g2].y));
                 }
             }
         };
         // layer-2 epilogue of pair P2 (runtime): bias, ReLU, output-layer partial sums
-        auto epi2 = [&](int P2, int qd, f32x16q (&ac)[2]) {
+        auto epi2 = [&](int P2, int qd, f32x16 (&ac)[2]) {
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
                 const int nb = 2 * P2 + blk;
@@ -589,7 +535,7 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
                 }
             }
         };
-        auto zero = [&](f32x16q (&ac)[2]) {
+        auto zero = [&](f32x16 (&ac)[2]) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) { ac[0][q] = 0.f; ac[1][q] = 0.f; }
         };
@@ -647,7 +593,7 @@ __global__ __launch_bounds__(256, 1) void implicit_decode_split512_kernel(DecSpl
             }
         }
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);              // the wrapped-around DMAs must land before the LDS goes away
+    GN_WAIT_ALL();                                   // the wrapped-around DMAs must land before the LDS goes away
     __syncthreads();
 }
 

@@ -302,12 +302,7 @@ __global__ __launch_bounds__(256) void knn_neighbours_kernel(const float *__rest
             const float d = gn_sqdist3(ps[3 * (size_t)j], ps[3 * (size_t)j + 1], ps[3 * (size_t)j + 2], qx, qy, qz);
             if ((d > pd || (d == pd && j > pj)) && d < v) { v = d; i = j; }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float ov = __shfl_xor(v, off);
-            const int oi = __shfl_xor(i, off);
-            if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-        }
+        GN_WAVE_ARGMIN(v, i)
         if (i == INT_MAX) break;
         pd = v;
         pj = i;
@@ -360,27 +355,14 @@ extern "C" int gn_knn_interpolate_bwd(const int32_t *nbr, const float *d2, int N
 }
 
 // ------------------------------------------------------------------------------------------------ trilinear sampler
-// The forward's arithmetic (csrc/decode.hip: ATen's grid_sampler_3d, border padding, align_corners=True; query component 0 indexes the LAST volume
-// axis).  `moving`: 0 where the coordinate was clamped at the border (ATen's clip_coordinates_set_grad: x <= 0 or x >= size - 1), else 1.
-__device__ __forceinline__ float src_index_grad(float q, int size, float *moving) {
-    const float qn = __fsub_rn(__fmul_rn(2.0f, q), 1.0f);
-    const float x = __fmul_rn(__fdiv_rn(__fadd_rn(qn, 1.0f), 2.0f), (float)(size - 1));
-    *moving = (x > 0.0f && x < (float)(size - 1)) ? 1.f : 0.f;
-    return fminf((float)(size - 1), fmaxf(x, 0.0f));
-}
-
-struct TriCorners {
-    float wx[2], wy[2], wz[2], mx, my, mz;
-    int x0, y0, z0;
+// The forward's arithmetic (gn_tri_src_index / gn_tri_cell, device_prims.h; query component 0 indexes the LAST volume axis); mx, my, mz: the `moving` flags.
+struct TriCorners : GnTriCell {
+    float mx, my, mz;
 };
 __device__ __forceinline__ TriCorners tri_corners(const float *__restrict__ q, int D, int H, int W) {
     TriCorners t;
-    const float ix = src_index_grad(q[0], W, &t.mx), iy = src_index_grad(q[1], H, &t.my), iz = src_index_grad(q[2], D, &t.mz);
-    const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-    t.x0 = (int)fx0; t.y0 = (int)fy0; t.z0 = (int)fz0;
-    t.wx[1] = __fsub_rn(ix, fx0); t.wx[0] = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-    t.wy[1] = __fsub_rn(iy, fy0); t.wy[0] = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-    t.wz[1] = __fsub_rn(iz, fz0); t.wz[0] = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
+    const float ix = gn_tri_src_index(q[0], W, &t.mx), iy = gn_tri_src_index(q[1], H, &t.my), iz = gn_tri_src_index(q[2], D, &t.mz);
+    static_cast<GnTriCell &>(t) = gn_tri_cell(ix, iy, iz);
     return t;
 }
 
@@ -397,7 +379,7 @@ __global__ __launch_bounds__(256) void tri_elements_kernel(const float *__restri
         const int xx = t.x0 + dx, yy = t.y0 + dy, zz = t.z0 + dz;
         const bool ok = xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < D;
         keys[r * 8 + c] = ok ? (int32_t)(((b * D + zz) * H + yy) * (int64_t)W + xx) : -1;
-        wgt[r * 8 + c] = __fmul_rn(__fmul_rn(t.wx[dx], t.wy[dy]), t.wz[dz]);
+        wgt[r * 8 + c] = gn_tri_weight(t, c);
     }
 }
 

@@ -67,23 +67,7 @@ extern "C" int gn_grid_features(const float *feat, int ldf, int Cf, const float 
 }
 
 // ------------------------------------------------------------------------------------------------ scatter
-// order-preserving float <-> uint encoding: enc(x) is monotone in x and > 0 for every non-NaN float, so a
-// zero-filled volume reads as "empty" and atomicMax on the encoding is an order-independent float max.
-__device__ __forceinline__ unsigned enc_f32(float f) {
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(unsigned e) {
-    unsigned u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
-    return __uint_as_float(u);
-}
-
-// dec_f32(~e), written out: (e's top bit clear: ~e has it set)
-__device__ __forceinline__ float dec_inv_f32(unsigned e) {
-    return __uint_as_float((e & 0x80000000u) ? e : (~e & 0x7fffffffu));
-}
-
-// max: order-independent by construction (atomicMax on the encoding).  INV (min): atomicMax on ~enc(x), also > 0 for every non-NaN float, so a
+// max: order-independent by construction (atomicMax on the gn_ord_enc code: > 0 for every non-NaN float, so a zero-filled cell reads as empty).  INV (min): atomicMax on ~enc(x), also > 0 for every non-NaN float, so a
 // zero-filled cell still reads as empty and the finalize pass still leaves untouched cells at 0.
 template <bool INV>
 __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__restrict__ src, int lds, const int32_t *__restrict__ flat_idx,
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__r
     if (lane == 0) atomicAdd(&count[cell], 1);
     float *v = vol + cell * C;
     for (int ch = lane; ch < C; ch += 64) {
-        const unsigned e = enc_f32(src[p * lds + ch]);
+        const unsigned e = gn_ord_enc(src[p * lds + ch]);
         atomicMax(reinterpret_cast<unsigned *>(v) + ch, INV ? ~e : e);
     }
 }
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(256) void scatter_max_finalize_kernel(const int32_t
     float *v = vol + cell * C;
     for (int ch = lane; ch < C; ch += 64) {
         const unsigned e = __float_as_uint(v[ch]);
-        v[ch] = INV ? dec_inv_f32(e) : dec_f32(e);
+        v[ch] = INV ? gn_ord_dec_inv(e) : gn_ord_dec(e);
     }
 }
 
@@ -357,7 +341,7 @@ __global__ __launch_bounds__(256) void tile_flags_kernel(const int32_t *__restri
 
 extern "C" int gn_grid_tile_flags(const int32_t *flat_idx, int64_t N, int B, int G0, int G1, int G2, int reach, unsigned char *flags, void *stream) {
     GN_REQUIRE(N >= 0 && B >= 0 && G0 > 0 && G1 > 0 && G2 > 0 && reach >= 1 && reach <= 4, "gn_grid_tile_flags: bad sizes");
-    const int TD = 4, TH = 8, TW = 8;               // the output tile of csrc/unet_split.hip (SP_TZ, SP_TY, SP_TX)
+    const int TD = 4, TH = 8, TW = 8;               // the output tile of csrc/unet_split.hip (GN_CONV_TZ, GN_CONV_TY, GN_CONV_TX)
     const int tz = (int)gn_cdiv(G0, TD), ty = (int)gn_cdiv(G1, TH), tx = (int)gn_cdiv(G2, TW);
     hipStream_t st = gn_stream(stream);
     GN_HIP(hipMemsetAsync(flags, 0, (size_t)B * tz * ty * tx, st), "gn_grid_tile_flags");

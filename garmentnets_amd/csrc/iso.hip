@@ -38,9 +38,6 @@ __device__ __forceinline__ float gg_sub(float a, float b) { return __fsub_rn(a, 
 // NaN-propagating min / max (IEEE 754-2019 minimum / maximum = numpy.min / numpy.max; one v_minimum3_f32 / v_maximum3_f32 each)
 __device__ __forceinline__ float gn_min_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
 __device__ __forceinline__ float gn_max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-// order-preserving encodings so that integer atomics implement float min / max; a NaN takes the extreme code of its side and decodes to a NaN
-__device__ __forceinline__ unsigned gn_enc_min(float v) { const unsigned e = __float_as_uint(v); return v != v ? 0u : ((e & 0x80000000u) ? ~e : (e | 0x80000000u)); }
-__device__ __forceinline__ unsigned gn_enc_max(float v) { const unsigned e = __float_as_uint(v); return v != v ? 0xffffffffu : ((e & 0x80000000u) ? ~e : (e | 0x80000000u)); }
 
 // correlate1d along `axis`, edge-replicate, fp64 accumulation in scipy's operation order, fp32 store
 __global__ __launch_bounds__(256) void ggm_correlate_kernel(const float *__restrict__ in, float *__restrict__ out, int n0, int n1,
@@ -308,17 +305,15 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float *__restrict__ x
     if (threadIdx.x == 0) {
         mn = gn_min_nan(gn_min_nan(smn[0], smn[1]), gn_min_nan(smn[2], smn[3]));
         mx = gn_max_nan(gn_max_nan(smx[0], smx[1]), gn_max_nan(smx[2], smx[3]));
-        atomicMin(&out_enc[0], gn_enc_min(mn));     // (one pair per workgroup)
-        atomicMax(&out_enc[1], gn_enc_max(mx));
+        atomicMin(&out_enc[0], gn_ord_enc_min(mn));     // (one pair per workgroup)
+        atomicMax(&out_enc[1], gn_ord_enc_max(mx));
     }
 }
 __global__ void minmax_init_kernel(unsigned *o) { o += 2 * blockIdx.x; o[0] = 0xffffffffu; o[1] = 0u; }
 __global__ void minmax_decode_kernel(unsigned *o) {
     o += 2 * blockIdx.x;
     for (int k = 0; k < 2; ++k) {
-        unsigned e = o[k];
-        unsigned u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
-        o[k] = u;
+        o[k] = __float_as_uint(gn_ord_dec(o[k]));
     }
 }
 

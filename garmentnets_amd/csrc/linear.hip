@@ -15,8 +15,6 @@
 // workgroup per CU, 20 % slower).
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 #define LIN_BK 16
 #ifndef LIN_NBUF
 #define LIN_NBUF 1

@@ -68,61 +68,9 @@ extern "C" int gn_segment_ptr(const int64_t *batch, int64_t n, int B, int32_t *p
 #define FPS_THREADS 1024
 #define FPS_WAVES (FPS_THREADS / 64)
 
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-#define DPP_QUAD_XOR1 0xB1        // quad_perm [1,0,3,2]
-#define DPP_QUAD_XOR2 0x4E        // quad_perm [2,3,0,1]
-#define DPP_ROW_HALF_MIRROR 0x141
-#define DPP_ROW_MIRROR 0x140
-
-// after these four steps every 16-lane row holds its own reduction in all of its lanes
-__device__ __forceinline__ float row_max_f(float v) {
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_QUAD_XOR1>(__float_as_int(v))));
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_QUAD_XOR2>(__float_as_int(v))));
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_ROW_HALF_MIRROR>(__float_as_int(v))));
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_ROW_MIRROR>(__float_as_int(v))));
-    return v;
-}
-__device__ __forceinline__ int row_min_i(int v) {
-    v = min(v, dpp_i<DPP_QUAD_XOR1>(v));
-    v = min(v, dpp_i<DPP_QUAD_XOR2>(v));
-    v = min(v, dpp_i<DPP_ROW_HALF_MIRROR>(v));
-    v = min(v, dpp_i<DPP_ROW_MIRROR>(v));
-    return v;
-}
-// the same over N <= 16 values replicated with period N along the row: log2(N) steps
-template <int N>
-__device__ __forceinline__ float part_max_f(float v) {
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_QUAD_XOR1>(__float_as_int(v))));
-    v = fmaxf(v, __int_as_float(dpp_i<DPP_QUAD_XOR2>(__float_as_int(v))));
-    if (N > 4) v = fmaxf(v, __int_as_float(dpp_i<DPP_ROW_HALF_MIRROR>(__float_as_int(v))));
-    if (N > 8) v = fmaxf(v, __int_as_float(dpp_i<DPP_ROW_MIRROR>(__float_as_int(v))));
-    return v;
-}
-template <int N>
-__device__ __forceinline__ int part_min_i(int v) {
-    v = min(v, dpp_i<DPP_QUAD_XOR1>(v));
-    v = min(v, dpp_i<DPP_QUAD_XOR2>(v));
-    if (N > 4) v = min(v, dpp_i<DPP_ROW_HALF_MIRROR>(v));
-    if (N > 8) v = min(v, dpp_i<DPP_ROW_MIRROR>(v));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-    v = row_max_f(v);
-    const int iv = __float_as_int(v);
-    return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(iv, 0)), __int_as_float(__builtin_amdgcn_readlane(iv, 16))),
-                 fmaxf(__int_as_float(__builtin_amdgcn_readlane(iv, 32)), __int_as_float(__builtin_amdgcn_readlane(iv, 48))));
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-    v = row_min_i(v);
-    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
 // One wave per SIMD for as long as the points fit the registers (24 per lane): a step costs what its instructions cost in issue slots -- the
 // min-update is the same work however it is spread, but the arg-max reduction and the cross-wave exchange are paid once per wave.
 // The update itself runs on point PAIRS in packed fp32 (v_pk_add_f32 / v_pk_mul_f32: the same IEEE operations, half the issue slots).
-typedef float fps_f2 __attribute__((ext_vector_type(2)));
 // running minimum in ONE instruction: fminf() compiles to two canonicalising v_max_f32 + v_min_f32 under the IEEE mode bit (3 instructions per point in a
 // loop of ~8); v_min_f32 itself returns the non-NaN operand, i.e. what `if (d < dist) dist = d` leaves (oracle/gn_oracle.c gno_fps)
 __device__ __forceinline__ float fps_min(float a, float b) {
@@ -188,12 +136,12 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(const float *__restrict__ 
             dd[0] = d;
             bv = d > bv ? d : bv;
         } else {
-            const fps_f2 q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
+            const f32x2 q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
 #pragma unroll
             for (int j = 0; j < PPT; j += 2) {
                 // d = (dx*dx + dy*dy) + dz*dz, fp32, no contraction: gn_sqdist3's operations on two points at a time
-                const fps_f2 dx = (fps_f2){px[j], px[j + 1]} - q2x, dy = (fps_f2){py[j], py[j + 1]} - q2y, dz = (fps_f2){pz[j], pz[j + 1]} - q2z;
-                const fps_f2 d2 = (dx * dx + dy * dy) + dz * dz;
+                const f32x2 dx = (f32x2){px[j], px[j + 1]} - q2x, dy = (f32x2){py[j], py[j + 1]} - q2y, dz = (f32x2){pz[j], pz[j + 1]} - q2z;
+                const f32x2 d2 = (dx * dx + dy * dy) + dz * dz;
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const float d = fps_min(dd[j + u], u ? d2.y : d2.x);
@@ -203,20 +151,20 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(const float *__restrict__ 
             }
         }
         const int bi = bv >= 0.f ? tid + bj * THREADS : INT_MAX;   // (a lane whose slots are all past the end holds -1)
-        const float wv = wave_max_f(bv);
+        const float wv = gn_wave_max(bv);
         // the lanes that hold the wave's maximum: one lane in all but exact ties -> its index is read directly; ties take the DPP min
         const unsigned long long hit = __ballot(bv == wv);
         int wi;
         if (__builtin_popcountll(hit) == 1) wi = __builtin_amdgcn_readlane(bi, __builtin_ctzll(hit));
-        else wi = wave_min_i(bv == wv ? bi : INT_MAX);
+        else wi = gn_wave_min(bv == wv ? bi : INT_MAX);
         const int par = (k & 1) * WAVES;
         if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
         __syncthreads();
         // lanes 0..WAVES-1 (replicated over the 16-lane DPP row) of every wave reduce the partials
         float fv = pv[par + (lane & (WAVES - 1))];
         int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = part_max_f<WAVES>(fv);
-        fi = part_min_i<WAVES>(fv == gv ? fi : INT_MAX);
+        const float gv = gn_row_max<WAVES>(fv);
+        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
         last = __builtin_amdgcn_readfirstlane(fi);
         gmin = fps_min(gmin, gv);
         if (tid == 0) out_idx[o0 + k] = s + last;
@@ -264,15 +212,15 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_lds_kernel(const float *__res
             dd[i] = d;
             if (d > bv) { bv = d; bi = i; }          // ascending index: ties keep the lowest
         }
-        const float wv = wave_max_f(bv);
-        const int wi = wave_min_i(bv == wv ? bi : INT_MAX);
+        const float wv = gn_wave_max(bv);
+        const int wi = gn_wave_min(bv == wv ? bi : INT_MAX);
         const int par = (k & 1) * WAVES;
         if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
         __syncthreads();
         float fv = pv[par + (lane & (WAVES - 1))];
         int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = part_max_f<WAVES>(fv);
-        fi = part_min_i<WAVES>(fv == gv ? fi : INT_MAX);
+        const float gv = gn_row_max<WAVES>(fv);
+        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
         last = __builtin_amdgcn_readfirstlane(fi);
         gmin = fps_min(gmin, gv);
         if (tid == 0) out_idx[o0 + k] = s + last;
@@ -366,15 +314,15 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_ws_kernel(const float *__rest
             reinterpret_cast<float *>(rec + i)[3] = d;
             if (d > bv) { bv = d; bi = i; }          // ascending index: ties keep the lowest
         }
-        const float wv = wave_max_f(bv);
-        const int wi = wave_min_i(bv == wv ? bi : INT_MAX);
+        const float wv = gn_wave_max(bv);
+        const int wi = gn_wave_min(bv == wv ? bi : INT_MAX);
         const int par = (k & 1) * WAVES;
         if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
         __syncthreads();
         float fv = pv[par + (lane & (WAVES - 1))];
         int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = part_max_f<WAVES>(fv);
-        fi = part_min_i<WAVES>(fv == gv ? fi : INT_MAX);
+        const float gv = gn_row_max<WAVES>(fv);
+        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
         last = __builtin_amdgcn_readfirstlane(fi);
         gmin = fps_min(gmin, gv);
         if (tid == 0) out_idx[o0 + k] = s + last;
@@ -612,12 +560,7 @@ __global__ __launch_bounds__(256) void knn_interp_kernel(const float *__restrict
     for (int r = 0; r < KK; ++r) {
         float v = bd[0];
         int i = bi[0];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            float ov = __shfl_xor(v, off);
-            int oi = __shfl_xor(i, off);
-            if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-        }
+        GN_WAVE_ARGMIN(v, i)
         wd[r] = v; wi[r] = i;
         if (i != INT_MAX) nsel = r + 1;
         if (bi[0] == i && i != INT_MAX) {  // the owner pops its head
@@ -698,12 +641,7 @@ __global__ __launch_bounds__(256) void knn_interp_any_kernel(const float *__rest
             // j ascends within a lane: strict '<' keeps the lower index among equal distances
             if ((d > pd || (d == pd && j > pj)) && d < v) { v = d; i = j; }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float ov = __shfl_xor(v, off);
-            const int oi = __shfl_xor(i, off);
-            if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-        }
+        GN_WAVE_ARGMIN(v, i)
         if (i == INT_MAX) break;                   // fewer than k sources
         pd = v;
         pj = i;

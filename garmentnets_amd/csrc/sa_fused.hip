@@ -22,8 +22,6 @@
 // (centre, unit) (ordered-int encoding); the G x N3 tile of results is written once, coalesced, rows without any edge -> 0 (PyG).
 #include "common.h"
 
-typedef float f32x16a __attribute__((ext_vector_type(16)));
-
 struct SaArgs {
     const float *x; int ldx;              // [N][ldx] point features (CIN channels) or NULL when CIN == 0
     const float *pos;                     // [N][3]
@@ -37,26 +35,10 @@ struct SaArgs {
     float *out; int ldo;                  // [M][ldo]
 };
 
-__device__ __forceinline__ f32x16a sa_mfma(float a, float b, const f32x16a &c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-template <int CTRL>
-__device__ __forceinline__ float sa_dpp(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-
-// max over the 32 lanes of each lane half (every lane of the half ends up with it)
-__device__ __forceinline__ float sa_half_max(float v) {
-    v = fmaxf(v, sa_dpp<0xB1>(v));        // quad_perm [1,0,3,2]
-    v = fmaxf(v, sa_dpp<0x4E>(v));        // quad_perm [2,3,0,1]
-    v = fmaxf(v, sa_dpp<0x141>(v));       // row_half_mirror
-    v = fmaxf(v, sa_dpp<0x140>(v));       // row_mirror: every 16-lane row holds its max
-    return fmaxf(v, __shfl_xor(v, 16));   // rows 0|1 and 2|3
-}
-
-// order-preserving float -> int (signed compare): LDS atomic max on floats of either sign
-__device__ __forceinline__ int sa_enc(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float sa_dec(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+__device__ __forceinline__ f32x16 sa_mfma(float a, float b, const f32x16 &c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // bias -> ReLU -> BatchNorm affine on one 32-unit block, in place (the op order of gn_linear's epilogue)
-__device__ __forceinline__ void sa_epilogue(f32x16a &a, const float *tb) {
+__device__ __forceinline__ void sa_epilogue(f32x16 &a, const float *tb) {
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
         const float4 b = *reinterpret_cast<const float4 *>(tb + 4 * q4);
@@ -76,7 +58,7 @@ __device__ __forceinline__ void sa_epilogue(f32x16a &a, const float *tb) {
 // immediate offsets) that the caller launders once per tile -- otherwise hipcc precomputes one 64-bit address per load as a
 // loop-invariant of the tile loop (hundreds of registers, spilled).
 template <int NKB, int LASTQ, typename BF>
-__device__ __forceinline__ void sa_block(f32x16a &acc, const float4 *&w, BF bsrc) {
+__device__ __forceinline__ void sa_block(f32x16 &acc, const float4 *&w, BF bsrc) {
     float4 wc[4], wn[4];
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) wc[qq] = w[qq * 64];
@@ -113,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
     __shared__ int tile_ctr;
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
     const int c0 = blockIdx.x * G;
-    for (int i = tid; i < G * N3; i += 256) out_lds[i] = sa_enc(-INFINITY);
+    for (int i = tid; i < G * N3; i += 256) out_lds[i] = gn_sord_enc(-INFINITY);
     for (int i = tid; i < TABN; i += 256) tab[i] = p.tab[i];
     if (tid == 0) tile_ctr = 0;
     __syncthreads();
@@ -178,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
         const float4 *w1 = p.w1 + lane, *w2 = p.w2 + lane, *w3 = p.w3 + lane;
         asm volatile("" : "+v"(w1), "+v"(w2), "+v"(w3));           // see sa_block
         // ---- layer 1: K1P inputs -> N1 units
-        f32x16a a1[NB1];
+        f32x16 a1[NB1];
 #pragma unroll
         for (int nb = 0; nb < NB1; ++nb) {
 #pragma unroll
@@ -187,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
             sa_epilogue(a1[nb], tab + (nb * 2 + h) * 48);
         }
         // ---- layer 2: N1 -> N2, the operand is the accumulator file of layer 1
-        f32x16a a2[NB2];
+        f32x16 a2[NB2];
 #pragma unroll
         for (int nb = 0; nb < NB2; ++nb) {
 #pragma unroll
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
         const bool self_tile = t >= 2 * G;
 #pragma unroll 1
         for (int nb = 0; nb < NB3; ++nb) {
-            f32x16a a3;
+            f32x16 a3;
 #pragma unroll
             for (int q = 0; q < 16; ++q) a3[q] = 0.f;
             sa_block<NB2, 4>(a3, w3, [&](int kb, int q) { return a2[kb][q]; });
@@ -208,13 +190,13 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
             if (self_tile) {                               // every lane is its own centre
                 if (valid) {
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) atomicMax(o + 8 * (q >> 2) + (q & 3), sa_enc(a3[q]));
+                    for (int q = 0; q < 16; ++q) atomicMax(o + 8 * (q >> 2) + (q & 3), gn_sord_enc(a3[q]));
                 }
             } else {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const float m = sa_half_max(valid ? a3[q] : -INFINITY);
-                    if (r == 0) atomicMax(o + 8 * (q >> 2) + (q & 3), sa_enc(m));
+                    const float m = gn_half_max(valid ? a3[q] : -INFINITY);
+                    if (r == 0) atomicMax(o + 8 * (q >> 2) + (q & 3), gn_sord_enc(m));
                 }
             }
         }
@@ -223,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
     for (int i = tid; i < G * N3; i += 256) {
         const int cl = i / N3, u = i % N3, c = c0 + cl;
         if (c < p.M) {
-            const float v = sa_dec(out_lds[i]);
+            const float v = gn_sord_dec(out_lds[i]);
             p.out[(size_t)c * p.ldo + u] = v == -INFINITY ? 0.f : v;          // a centre without any edge: scatter-max leaves 0
         }
     }

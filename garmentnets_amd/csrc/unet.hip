@@ -7,8 +7,6 @@
 // :195-330 (Encoder / Decoder / Upsampling), :449-474 (forward).
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ------------------------------------------------------------------------------------------------ channel stats
 // grid (chunks, B).  Thread t owns channel t % C (C | 256) or channels t, t+256, ... (256 | C) and walks the
 // chunk's voxels; per-thread fp32 partials over <= 64 voxels, then fp64 atomics into [B][C].
@@ -289,13 +287,6 @@ extern "C" int gn_groupnorm_affine_map(const double *sum0, const double *sq0, in
 // LDS: halo 600 voxels x 20 words = 48 KB, weights 2 x NT*32 x 20 words <= 10 KB  -> 2 workgroups per CU.
 // Optional epilogue: per-(sample, channel) sum / sum-of-squares of the (post-ReLU) output, i.e. the GroupNorm statistics
 // of the NEXT layer, reduced in-wave, across waves through LDS, then one fp64 atomic per channel per workgroup.
-#define CV_TZ 4
-#define CV_TY 8
-#define CV_TX 8
-#define CV_HZ (CV_TZ + 2)
-#define CV_HY (CV_TY + 2)
-#define CV_HX (CV_TX + 2)
-#define CV_HVOX (CV_HZ * CV_HY * CV_HX)
 #define CV_KS 16
 #define CV_VSTRIDE (CV_KS + 4)
 
@@ -317,7 +308,7 @@ struct AFrag { float4 lo, hi; };
 template <int NT>
 __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
     constexpr int CT = NT * 32;
-    __shared__ __attribute__((aligned(16))) float halo[CV_HVOX * CV_VSTRIDE];
+    __shared__ __attribute__((aligned(16))) float halo[GN_CONV_HVOX * CV_VSTRIDE];
     __shared__ __attribute__((aligned(16))) float wsm[2][CT * CV_VSTRIDE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r = lane & 31;
     const int Cin = p.C0 + p.C1;
@@ -334,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
     const int tz = tile % tiles_z; tile /= tiles_z;
     const int tx = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty = tile;
-    const int z0 = tz * CV_TZ, y0 = ty * CV_TY, x0 = tx * CV_TX;
+    const int z0 = tz * GN_CONV_TZ, y0 = ty * GN_CONV_TY, x0 = tx * GN_CONV_TX;
     const int n0 = cb * CT;
     const int b = blockIdx.y;
     const int D1 = p.D >> 1, H1 = p.H >> 1, W1 = p.W >> 1;
@@ -350,8 +341,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
             for (int q = 0; q < 16; ++q) { acc[t][u][q] = 0.f; tot[t][u][q] = 0.f; }
 
     // A-operand base (float4 units) of fragment 0 at tap (0,0,0); fragment 1 is 4 halo rows further
-    const int abase = (((wave * CV_HY + (r >> 3)) * CV_HX + (r & 7)) * CV_VSTRIDE + 8 * h) >> 2;
-    constexpr int AF1 = (4 * CV_HX * CV_VSTRIDE) >> 2;
+    const int abase = (((wave * GN_CONV_HY + (r >> 3)) * GN_CONV_HX + (r & 7)) * CV_VSTRIDE + 8 * h) >> 2;
+    constexpr int AF1 = (4 * GN_CONV_HX * CV_VSTRIDE) >> 2;
     const int bbase = (r * CV_VSTRIDE + 8 * h) >> 2;
     const float4 *halo4 = reinterpret_cast<const float4 *>(halo);
 
@@ -372,9 +363,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
             const int cs = from1 ? c0 - p.C0 : c0;
             const float *ab = p.a + (int64_t)b * Cin + c0;
             const float *db = p.d + (int64_t)b * Cin + c0;
-            for (int idx = tid; idx < CV_HVOX * 4; idx += 256) {
+            for (int idx = tid; idx < GN_CONV_HVOX * 4; idx += 256) {
                 const int hv = idx >> 2, c4 = (idx & 3) * 4;
-                const int hx = hv % CV_HX, hy = (hv / CV_HX) % CV_HY, hz = hv / (CV_HX * CV_HY);
+                const int hx = hv % GN_CONV_HX, hy = (hv / GN_CONV_HX) % GN_CONV_HY, hz = hv / (GN_CONV_HX * GN_CONV_HY);
                 const int gz = z0 + hz - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (gz >= 0 && gz < p.D && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
@@ -413,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
             for (int u = 0; u < NT; ++u) { bf[u].lo = w4[bbase + u * 32 * (CV_VSTRIDE >> 2)]; bf[u].hi = w4[bbase + u * 32 * (CV_VSTRIDE >> 2) + 1]; }
             if (more) {
                 const int t1 = tap + 1;
-                const int toff = ((((t1 / 9) * CV_HY + (t1 / 3) % 3) * CV_HX + t1 % 3) * CV_VSTRIDE) >> 2;
+                const int toff = ((((t1 / 9) * GN_CONV_HY + (t1 / 3) % 3) * GN_CONV_HX + t1 % 3) * CV_VSTRIDE) >> 2;
                 na0.lo = halo4[abase + toff]; na0.hi = halo4[abase + toff + 1];
                 na1.lo = halo4[abase + AF1 + toff]; na1.hi = halo4[abase + AF1 + toff + 1];
             }
@@ -439,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
     }
     // ---- epilogue: ReLU, coalesced stores, optional statistics of the output
     const int gz = z0 + wave;
-    const bool full = z0 + CV_TZ <= p.D && y0 + CV_TY <= p.H && x0 + CV_TX <= p.W;    // tile inside the volume (workgroup-uniform)
+    const bool full = z0 + GN_CONV_TZ <= p.D && y0 + GN_CONV_TY <= p.H && x0 + GN_CONV_TX <= p.W;    // tile inside the volume (workgroup-uniform)
     double ssum[NT], ssq[NT];                       // fp64 per lane: the statistics do not depend on the kernel variant (see unet_split.hip)
 #pragma unroll
     for (int u = 0; u < NT; ++u) { ssum[u] = 0.0; ssq[u] = 0.0; }
@@ -508,9 +499,9 @@ extern "C" int gn_conv3d_gcr(const float *src0, int C0, const float *src1, int C
     ConvArgs p;
     p.src0 = src0; p.src1 = src1; p.a = a; p.d = d; p.wp = wp; p.out = out; p.osum = out_sum; p.osq = out_sumsq;
     p.C0 = C0; p.C1 = C1; p.B = B; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.relu = relu;
-    const int tz = (int)gn_cdiv(D, CV_TZ);
-    p.tiles_y = (int)gn_cdiv(H, CV_TY);
-    p.tiles_x = (int)gn_cdiv(W, CV_TX);
+    const int tz = (int)gn_cdiv(D, GN_CONV_TZ);
+    p.tiles_y = (int)gn_cdiv(H, GN_CONV_TY);
+    p.tiles_x = (int)gn_cdiv(W, GN_CONV_TX);
     const int tiles = tz * p.tiles_y * p.tiles_x;
     // small volumes / small batches: the 32-wide column tile doubles the number of workgroups (same per-CU throughput)
     const bool wide = (Cout % 64 == 0) && ((int64_t)tiles * (Cout / 64) * B >= 1024);

@@ -9,8 +9,6 @@
 // Rule of the file (as grad.hip, losses.hip): NO float atomics; every sum has a fixed order, so identical calls give identical bits.
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ------------------------------------------------------------------------------------------------ conv weight gradient
 // A workgroup owns a (32 input channels) x (NCO * 32 output channels) block of dW for ALL 27 taps and walks a chain of 4 x 8 x 8 spatial tiles.
 // Per tile it stages once: the 6 x 10 x 10 halo of its 32 input channels with the GroupNorm affine applied on the way (x*a + d inside the volume, 0 in
@@ -19,14 +17,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // 32x32x2 per tap and voxel pair -- lanes 0-31 feed voxel (z, y, x), lanes 32-63 voxel (z, y, x + 1), lane r channel r: both operands are one
 // conflict-free 64-float LDS row read.  Each tap's sum runs over the voxels of the chain in tile order, voxel order inside a tile; the chain writes one
 // partial [27][32][NCO*32]; conv3d_bwd_weight_fold_kernel adds the chains in ascending order (fp64) into the nn.Conv3d layout.
-#define BW_TZ 4
-#define BW_TY 8
-#define BW_TX 8
-#define BW_HZ 6
-#define BW_HY 10
-#define BW_HX 10
-#define BW_HVOX (BW_HZ * BW_HY * BW_HX)
-#define BW_TVOX (BW_TZ * BW_TY * BW_TX)
 #define BW_CI 32
 #define BW_TARGET_WORKGROUPS 512       /* chains x blocks: two rounds of the 256 CUs (a constant: the summation order must not depend on the device) */
 
@@ -38,7 +28,7 @@ struct BwArgs {
 };
 
 static int bw_chains(int B, int D, int H, int W, int Cin, int Cout, int *per_chain) {
-    const int64_t ntiles = (int64_t)B * gn_cdiv(D, BW_TZ) * gn_cdiv(H, BW_TY) * gn_cdiv(W, BW_TX);
+    const int64_t ntiles = (int64_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX);
     const int nco = Cout % 64 == 0 ? 2 : 1;
     const int64_t blocks = gn_cdiv(Cin, BW_CI) * (Cout / (32 * nco));
     int64_t chains = gn_cdiv(BW_TARGET_WORKGROUPS, blocks);
@@ -53,7 +43,7 @@ template <int NCO>
 __global__ __launch_bounds__(192 * NCO) void conv3d_bwd_weight_kernel(BwArgs p) {
     extern __shared__ __attribute__((aligned(16))) float bw_smem[];
     float *halo = bw_smem;                          // [600 halo voxels][32 ci]
-    float *gt = bw_smem + BW_HVOX * BW_CI;          // [NCO][256 voxels][32 co]
+    float *gt = bw_smem + GN_CONV_HVOX * BW_CI;          // [NCO][256 voxels][32 co]
     constexpr int NT = 192 * NCO;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r = lane & 31;
     const int kd = wave % 3, cu = wave / 3;
@@ -79,12 +69,12 @@ __global__ __launch_bounds__(192 * NCO) void conv3d_bwd_weight_kernel(BwArgs p) 
         const int tz = rem % p.tiles_z; rem /= p.tiles_z;
         const int tx = rem % p.tiles_x;
         const int ty = rem / p.tiles_x;
-        const int z0 = tz * BW_TZ, y0 = ty * BW_TY, x0 = tx * BW_TX;
+        const int z0 = tz * GN_CONV_TZ, y0 = ty * GN_CONV_TY, x0 = tx * GN_CONV_TX;
         // ---- halo of 32 input channels, the forward's operand: fmul then fadd, zeros outside the volume and beyond the last channel
-        for (int idx = tid; idx < BW_HVOX * (BW_CI / 4); idx += NT) {
+        for (int idx = tid; idx < GN_CONV_HVOX * (BW_CI / 4); idx += NT) {
             const int hv = idx >> 3, c4 = (idx & 7) * 4;
             const int c = ci0 + c4;
-            const int hx = hv % BW_HX, hy = (hv / BW_HX) % BW_HY, hz = hv / (BW_HX * BW_HY);
+            const int hx = hv % GN_CONV_HX, hy = (hv / GN_CONV_HX) % GN_CONV_HY, hz = hv / (GN_CONV_HX * GN_CONV_HY);
             const int gz = z0 + hz - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (c < Cin && gz >= 0 && gz < p.D && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
@@ -102,8 +92,8 @@ __global__ __launch_bounds__(192 * NCO) void conv3d_bwd_weight_kernel(BwArgs p) 
             *reinterpret_cast<float4 *>(halo + hv * BW_CI + c4) = v;
         }
         // ---- g = dy masked by y > 0 (ReLU backward), zeros outside the volume
-        for (int idx = tid; idx < NCO * BW_TVOX * 8; idx += NT) {
-            const int cb = idx / (BW_TVOX * 8), rm = idx % (BW_TVOX * 8);
+        for (int idx = tid; idx < NCO * GN_CONV_TVOX * 8; idx += NT) {
+            const int cb = idx / (GN_CONV_TVOX * 8), rm = idx % (GN_CONV_TVOX * 8);
             const int vv = rm >> 3, c4 = (rm & 7) * 4;
             const int gz = z0 + (vv >> 6), gy = y0 + ((vv >> 3) & 7), gx = x0 + (vv & 7);
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -115,19 +105,19 @@ __global__ __launch_bounds__(192 * NCO) void conv3d_bwd_weight_kernel(BwArgs p) 
                     g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f; g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
                 }
             }
-            *reinterpret_cast<float4 *>(gt + (cb * BW_TVOX + vv) * 32 + c4) = g;
+            *reinterpret_cast<float4 *>(gt + (cb * GN_CONV_TVOX + vv) * 32 + c4) = g;
         }
         __syncthreads();
-        const float *gw = gt + cu * BW_TVOX * 32 + r;
+        const float *gw = gt + cu * GN_CONV_TVOX * 32 + r;
 #pragma unroll 2
-        for (int pair = 0; pair < BW_TVOX / 2; ++pair) {
+        for (int pair = 0; pair < GN_CONV_TVOX / 2; ++pair) {
             const int vv = pair * 2 + h;
             const int z = vv >> 6, yy = (vv >> 3) & 7, x = vv & 7;
             const float gv = gw[vv * 32];
-            const float *hb = halo + (((z + kd) * BW_HY + yy) * BW_HX + x) * BW_CI + r;
+            const float *hb = halo + (((z + kd) * GN_CONV_HY + yy) * GN_CONV_HX + x) * BW_CI + r;
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
-                const float av = hb[((k / 3) * BW_HX + (k % 3)) * BW_CI];
+                const float av = hb[((k / 3) * GN_CONV_HX + (k % 3)) * BW_CI];
                 acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, gv, acc[k], 0, 0, 0);
             }
         }
@@ -167,7 +157,7 @@ extern "C" int gn_conv3d_bwd_weight(const float *src0, int C0, const float *src1
     GN_REQUIRE(C0 % 4 == 0 && C1 % 4 == 0, "gn_conv3d_bwd_weight: channel counts must be multiples of 4 (C0=%d C1=%d)", C0, C1);
     GN_REQUIRE(Cout % 32 == 0, "gn_conv3d_bwd_weight: Cout=%d must be a multiple of 32", Cout);
     GN_REQUIRE(C1 == 0 || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0), "gn_conv3d_bwd_weight: upsampled source needs even dims");
-    GN_REQUIRE((int64_t)B * gn_cdiv(D, BW_TZ) * gn_cdiv(H, BW_TY) * gn_cdiv(W, BW_TX) < ((int64_t)1 << 30), "gn_conv3d_bwd_weight: volume too large");
+    GN_REQUIRE((int64_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX) < ((int64_t)1 << 30), "gn_conv3d_bwd_weight: volume too large");
     const int Cin = C0 + C1;
     const size_t need = gn_conv3d_bwd_weight_workspace_bytes(B, D, H, W, Cin, Cout);
     GN_REQUIRE(ws_bytes >= need, "gn_conv3d_bwd_weight: workspace too small (%zu < %zu bytes)", ws_bytes, need);
@@ -181,11 +171,11 @@ extern "C" int gn_conv3d_bwd_weight(const float *src0, int C0, const float *src1
     BwArgs p;
     p.src0 = src0; p.src1 = src1; p.a = a; p.d = d; p.y = y; p.dy = dy; p.part = (float *)ws;
     p.C0 = C0; p.C1 = C1; p.B = B; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.Cin32 = (int)gn_cdiv(Cin, BW_CI) * BW_CI;
-    p.tiles_z = (int)gn_cdiv(D, BW_TZ); p.tiles_y = (int)gn_cdiv(H, BW_TY); p.tiles_x = (int)gn_cdiv(W, BW_TX);
+    p.tiles_z = (int)gn_cdiv(D, GN_CONV_TZ); p.tiles_y = (int)gn_cdiv(H, GN_CONV_TY); p.tiles_x = (int)gn_cdiv(W, GN_CONV_TX);
     p.ntiles = B * p.tiles_z * p.tiles_y * p.tiles_x;
     const int chains = bw_chains(B, D, H, W, Cin, Cout, &p.per_chain);
     const int nco = Cout % 64 == 0 ? 2 : 1;
-    const size_t lds = (size_t)(BW_HVOX * BW_CI + nco * BW_TVOX * 32) * sizeof(float);
+    const size_t lds = (size_t)(GN_CONV_HVOX * BW_CI + nco * GN_CONV_TVOX * 32) * sizeof(float);
     const dim3 grid((unsigned)((p.Cin32 / BW_CI) * (Cout / (32 * nco))), (unsigned)chains);
     if (nco == 2) {
         GN_HIP(hipFuncSetAttribute((const void *)conv3d_bwd_weight_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "gn_conv3d_bwd_weight");

@@ -39,12 +39,10 @@
 struct WinoLayout {
     static constexpr int VB = 64;                      // bytes per transformed voxel: 2 planes x 16 halfs
     static constexpr int ROWP = 4 * VB + 16;           // 4 pairs per halo row + one 16-byte pad
-    static constexpr int HZ = SP_TZ + 2, HY = SP_TY + 2;
+    static constexpr int HZ = GN_CONV_TZ + 2, HY = GN_CONV_TY + 2;
     static constexpr int SLOT = HZ * HY * ROWP;        // one transform position of one slice: 16320 B
     static constexpr int NSLOT = 5;
 };
-
-typedef float f32x4n __attribute__((ext_vector_type(4)));
 
 template <bool F16>
 __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) {
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), zs = wave & 3, cg = wave >> 2;
     const int Cin = p.C0;
     const int ncb = p.Cout / 128;
-    const int tiles_z = p.D / SP_TZ;
+    const int tiles_z = p.D / GN_CONV_TZ;
     const int tps = tiles_z * p.tiles_x * p.tiles_y;
     const int nslices = Cin / SP_KS;
     double *const stl = reinterpret_cast<double *>(smem + ST_OFF);         // [sum | sumsq][128] of this run's tiles
@@ -91,14 +89,14 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
         int tile = e - b_ * tps;
         const int tz = tile % tiles_z; tile /= tiles_z;
         const int tx = tile % p.tiles_x;
-        z0_ = tz * SP_TZ; y0_ = (tile / p.tiles_x) * SP_TY; x0_ = tx * SP_TX;
+        z0_ = tz * GN_CONV_TZ; y0_ = (tile / p.tiles_x) * GN_CONV_TY; x0_ = tx * GN_CONV_TX;
     };
     int b, cb, z0, y0, x0;
     decode(item, b, cb, z0, y0, x0);
 
     // acc: the running transform position's accumulators; tot[e]: outputs at even (e = 0) / odd x of the pairs.  (A second accumulator set -- the
     // output transform of position j folded in under position j+1's MFMAs -- needs 261 registers: 46 spilled values inside the MFMA stream.)
-    f32x16s acc[NT], tot[2][NT];
+    f32x16 acc[NT], tot[2][NT];
 
     // B fragments: pack order [slice][step = (j * 3 + dz) * 3 + dy][Cout/32][plane][lane]; wave w fetches piece w of every step (wave-uniform
     // base in SGPRs + one constant per-lane offset register: no 64-bit VALU arithmetic per piece).  Step (G + 2, st) is issued during step
@@ -109,8 +107,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
     const unsigned bvoff = (unsigned)(wave * 1024 + lane * 16);
 #define WN_ISSUE_PIECE(SLOTI, ST)                                                                                              \
     do {                                                                                                                       \
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(bvoff), "s"(bgs),                    \
-                     "s"(lds_ring + (SLOTI) * GB + (ST) * STEPB + wave * 1024) : "memory");                                    \
+        gn_glds16_s(bgs, bvoff, lds_ring + (SLOTI) * GB + (ST) * STEPB + wave * 1024);                                         \
         bgs += bstep;                                                                                                          \
     } while (0)
 
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
         inb = rowin ? (0x1eu | (in0 ? 1u : 0u) | (in5 ? 0x20u : 0u)) : 0u;
     };
     const float *base0 = p.src0;
-    f32x4n raw[NIT];
+    f32x4 raw[NIT];
     auto issue_rows = [&](int sl) {
         const unsigned cb4 = (unsigned)sl * (SP_KS * 4u), vs = (unsigned)p.C0 * 4u;
 #pragma unroll
@@ -172,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
     auto affine_rows = [&](int sl) { affine_load(sl); affine_math(0, NIT); };
     // transform position jp of both pairs -> slot `slot` (fp32 differences / sums, then the exact two-plane split), in four stages the group
     // loop threads between its MFMAs: conv_a the sums, conv_b / conv_c the splits, conv_d the stores
-    f32x4n cva, cvb;
+    f32x4 cva, cvb;
     uint2 cpa[P], cpb[P];
     auto conv_a = [&](int jp) {
         if (jp == 0) { cva = raw[0] - raw[2]; cvb = raw[2] - raw[4]; }
@@ -391,7 +388,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino_kernel(SplitArgs p) 
             float osc[NT], k63[NT];
 #pragma unroll
             for (int u = 0; u < NT; ++u) { ssum[u] = 0.0; ssq[u] = 0.0; osc[u] = ecl[cg * 64 + u * 32 + re]; k63[u] = ecl[128 + cg * 64 + u * 32 + re]; }
-            const bool interior = z0e > 0 && z0e + SP_TZ < p.D && y0e > 0 && y0e + SP_TY < p.H && x0e > 0 && x0e + SP_TX < p.W;   // no voxel of the tile on a face
+            const bool interior = z0e > 0 && z0e + GN_CONV_TZ < p.D && y0e > 0 && y0e + GN_CONV_TY < p.H && x0e > 0 && x0e + GN_CONV_TX < p.W;   // no voxel of the tile on a face
             const bool classes = p.kbias && !interior;
             const int mz = sp_axis_mask(gz, p.D);
             // stores: wave-uniform 64-bit base of output row pair (q >> 2) in SGPRs + a 32-bit lane offset per (e, u, q & 3): no 64-bit VALU

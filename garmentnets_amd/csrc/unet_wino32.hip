@@ -30,12 +30,10 @@
 struct Wino32Layout {
     static constexpr int VB = 64;                      // bytes per transformed voxel: 2 planes x 16 halfs
     static constexpr int ROWP = 4 * VB + 16;           // 4 pairs per halo row + one 16-byte pad
-    static constexpr int TZ = 8, HZ = TZ + 2, HY = SP_TY + 2, ROWS = HZ * HY;
+    static constexpr int TZ = 8, HZ = TZ + 2, HY = GN_CONV_TY + 2, ROWS = HZ * HY;
     static constexpr int SLOT = ROWS * ROWP;           // one transform position of one slice: 27 200 B
     static constexpr int NSLOT = 5;
 };
-
-typedef float f32x4m __attribute__((ext_vector_type(4)));
 
 template <bool F16>
 __global__ __launch_bounds__(512, 1) void conv3d_split_wino32pc_kernel(SplitArgs p) {
@@ -82,21 +80,20 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino32pc_kernel(SplitArgs
         int tile = e - b_ * tps;
         const int tz = tile % tiles_z; tile /= tiles_z;
         const int tx = tile % p.tiles_x;
-        z0_ = tz * WL::TZ; y0_ = (tile / p.tiles_x) * SP_TY; x0_ = tx * SP_TX;
+        z0_ = tz * WL::TZ; y0_ = (tile / p.tiles_x) * GN_CONV_TY; x0_ = tx * GN_CONV_TX;
     };
     int b, cb, z0, y0, x0;
     decode(item, b, cb, z0, y0, x0);
 
-    f32x16s acc[2], tot[2][2];                      // [fragment], [fragment][even / odd x]
+    f32x16 acc[2], tot[2][2];                      // [fragment], [fragment][even / odd x]
 
     // ---- weights: producer cw fetches piece cw of every group (step cw >> 1, plane cw & 1), producers 0 and 1 also piece cw + 4
     const int64_t bstep = (int64_t)ncb * STEPB;
     const unsigned char *bgs = nullptr;
     const unsigned bvoff = (unsigned)(lane * 16);
 #define W32_PIECE(SLOTI, PI)                                                                                                   \
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(bvoff),                                   \
-                 "s"(bgs + (int64_t)((PI) >> 1) * bstep + ((PI) & 1) * 1024),                                                  \
-                 "s"(lds_ring + (SLOTI) * GB + (unsigned)(((PI) >> 1) * STEPB + ((PI) & 1) * 1024)) : "memory")
+    gn_glds16_s(bgs + (int64_t)((PI) >> 1) * bstep + ((PI) & 1) * 1024, bvoff,                                                 \
+                lds_ring + (SLOTI) * GB + (unsigned)(((PI) >> 1) * STEPB + ((PI) & 1) * 1024))
 #define W32_ISSUE_GROUP(SLOTI)                                                                                                 \
     do {                                                                                                                       \
         W32_PIECE(SLOTI, cw);                                                                                                  \
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino32pc_kernel(SplitArgs
         }
     };
     const float *base0 = p.src0;
-    f32x4m raw[2][NIT];
+    f32x4 raw[2][NIT];
     auto issue_rows = [&](int sl) {
         const unsigned cb4 = (unsigned)sl * (SP_KS * 4u), vs = (unsigned)p.C0 * 4u;
 #pragma unroll
@@ -190,7 +187,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino32pc_kernel(SplitArgs
             unsigned char *dst = smem + slot * WL::SLOT + wrow[k];
 #pragma unroll
             for (int q = k0; q < k1; ++q) {
-                f32x4m cv;
+                f32x4 cv;
                 if (jp == 0) cv = raw[k][2 * q] - raw[k][2 * q + 2];
                 else if (jp == 1) cv = raw[k][2 * q + 1] + raw[k][2 * q + 2];
                 else if (jp == 2) cv = raw[k][2 * q + 2] - raw[k][2 * q + 1];
@@ -311,7 +308,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wino32pc_kernel(SplitArgs
                 const int n0 = cbe * 32;
                 double ssum = 0.0, ssq = 0.0;
                 const float osc = ecl[re], k63 = ecl[32 + re];
-                const bool interior = z0e > 0 && z0e + WL::TZ < p.D && y0e > 0 && y0e + SP_TY < p.H && x0e > 0 && x0e + SP_TX < p.W;
+                const bool interior = z0e > 0 && z0e + WL::TZ < p.D && y0e > 0 && y0e + GN_CONV_TY < p.H && x0e > 0 && x0e + GN_CONV_TX < p.W;
                 const bool classes = p.kbias && !interior;
                 const int64_t rs2 = 2 * (int64_t)p.W * p.Cout;
 #pragma unroll

@@ -15,14 +15,7 @@
 // (iz, iy, ix) in {0,1}^3 reads the halo at offset (pz + iz, py + iy, px + ix).  Each wave multiplies its own class's merged weights:
 // B fragments go global -> registers (1 KB per wave per fragment, coalesced, L2-resident), one step ahead; nothing is shared between
 // waves but the halo, so the only workgroup barrier is one per slice.
-#include "common.h"
-
-typedef float f32x16u __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8u __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8u __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2u __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2u __attribute__((ext_vector_type(2)));
-typedef float f32x2u __attribute__((ext_vector_type(2)));
+#include "split_conv.h"
 
 struct UpArgs {
     const float *src;             // coarse source [B][Dc][Hc][Wc][C1]
@@ -35,44 +28,10 @@ struct UpArgs {
     int tiles_y, tiles_x;
 };
 
-template <bool F16>
-__device__ __forceinline__ void up_split4(float r0, float r1, float r2, float r3, uint2 (&out)[2]) {
-    const f32x2u lo = {r0, r1}, hi = {r2, r3};
-    if (F16) {
-        const f16x2u blo = __builtin_convertvector(lo, f16x2u), bhi = __builtin_convertvector(hi, f16x2u);
-        out[0].x = __builtin_bit_cast(unsigned, blo);
-        out[0].y = __builtin_bit_cast(unsigned, bhi);
-        const f32x2u rlo = {gn_resid_lo(out[0].x, r0), gn_resid_hi(out[0].x, r1)}, rhi = {gn_resid_lo(out[0].y, r2), gn_resid_hi(out[0].y, r3)};   // (common.h)
-        out[1].x = __builtin_bit_cast(unsigned, __builtin_convertvector(rlo, f16x2u));
-        out[1].y = __builtin_bit_cast(unsigned, __builtin_convertvector(rhi, f16x2u));
-    } else {
-        const bf16x2u blo = __builtin_convertvector(lo, bf16x2u), bhi = __builtin_convertvector(hi, bf16x2u);
-        out[0].x = __builtin_bit_cast(unsigned, blo);
-        out[0].y = __builtin_bit_cast(unsigned, bhi);
-        const f32x2u rlo = {__fsub_rn(r0, __uint_as_float(out[0].x << 16)), __fsub_rn(r1, __uint_as_float(out[0].x & 0xffff0000u))};
-        const f32x2u rhi = {__fsub_rn(r2, __uint_as_float(out[0].y << 16)), __fsub_rn(r3, __uint_as_float(out[0].y & 0xffff0000u))};
-        out[1].x = __builtin_bit_cast(unsigned, __builtin_convertvector(rlo, bf16x2u));
-        out[1].y = __builtin_bit_cast(unsigned, __builtin_convertvector(rhi, bf16x2u));
-    }
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x16u up_mfma(const uint4 &a, const uint4 &b, const f32x16u &c) {
-    if (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8u, a), __builtin_bit_cast(f16x8u, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8u, a), __builtin_bit_cast(bf16x8u, b), c, 0, 0, 0);
-}
-
-// halo layout of unet_split.hip (two planes: 64 B per voxel, one 16-byte pad per row of 10 voxels: conflict-free ds_read_b128)
-template <int HZ> struct UpHalo {
-    static constexpr int ROWP = 10 * 64 + 16;
-    static constexpr int BYTES = HZ * 10 * ROWP;
-    __device__ static constexpr __forceinline__ int at(int hz, int hy, int hx) { return (hz * 10 + hy) * ROWP + hx * 64; }
-};
-
 template <int NT, bool F16>
 __global__ __launch_bounds__(512, 1) void upconv_partial_kernel(UpArgs p) {
     constexpr int TZC = NT == 1 ? 2 : 1, NF = 2 * TZC, HZ = TZC + 2, HVOX = HZ * 100;
-    using HL = UpHalo<HZ>;
+    using HL = HaloLayout<2, HZ>;               // two planes, the row pad of unet_split.hip's halo
     constexpr int NIT = (HVOX * 4 + 511) / 512;     // float4 row loads per thread per slice (4 / 3)
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * HL::BYTES + 2 * 384 * 4];
     float *const adl = reinterpret_cast<float *>(smem + 2 * HL::BYTES);     // a[C1] | d[C1] of this sample
@@ -93,7 +52,7 @@ __global__ __launch_bounds__(512, 1) void upconv_partial_kernel(UpArgs p) {
     const int nslices = p.C1 / 16;
     const int nblocks = p.Cout / 32;                // 32-wide column blocks per class
 
-    f32x16u acc[NF][NT], tot[NF][NT];               // fragment f = 2 zc + t: coarse z-slice zc, y half t
+    f32x16 acc[NF][NT], tot[NF][NT];               // fragment f = 2 zc + t: coarse z-slice zc, y half t
 #pragma unroll
     for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -136,7 +95,7 @@ __global__ __launch_bounds__(512, 1) void upconv_partial_kernel(UpArgs p) {
                 v3 = __fmaf_rn(raw[it].w, av.w, dv.w);
             }
             uint2 pl[2];
-            up_split4<F16>(v0, v1, v2, v3, pl);
+            split4<2, F16>(v0, v1, v2, v3, pl);
             unsigned char *dst = smem + buf * HL::BYTES + HL::at(hv / 100, (hv / 10) % 10, hv % 10) + c4 * 2;
             *reinterpret_cast<uint2 *>(dst) = pl[0];
             *reinterpret_cast<uint2 *>(dst + 32) = pl[1];
@@ -194,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void upconv_partial_kernel(UpArgs p) {
             }
 #define UP_PROD(IA, IB)                                                                                                        \
             _Pragma("unroll") for (int u = 0; u < NT; ++u)                                                                     \
-                _Pragma("unroll") for (int f = 0; f < NF; ++f) acc[f][u] = up_mfma<F16>(af[f][IA], bf[u][IB], acc[f][u]);
+                _Pragma("unroll") for (int f = 0; f < NF; ++f) acc[f][u] = mfma16<F16>(af[f][IA], bf[u][IB], acc[f][u]);
             UP_PROD(1, 0)
             if (more && tap >= 2 && tap < 2 + NIT) convert_row(tap - 2, s + 1, (s + 1) & 1);
             UP_PROD(0, 1) UP_PROD(0, 0)
