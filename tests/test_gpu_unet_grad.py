@@ -16,6 +16,47 @@ largest e32 / max |g| over all tensors), per seed of _composition_inputs:
         (relative 1.0e-02 / 1.3e-02 / 9.1e-03).  The test runs seed 0.  The sharp check of the arithmetic is the layer level above, where no flip exists.
 Default arithmetic (f16x2 forward, fp32 backward), measured on an MI355X: largest (ours - fp64) / e32 over all tensors 1.15 (main) and 1.60 (padded);
 asserted with k = 2, the measured ratio rounded up to the next power of two (strict-fp32 forward: 1.15 and 1.88 under the rule's 4).
+Shared selections on the non-cubic grids, the same CPU measure with the fp64 restatement's own masks and winners handed to both precisions
+(print_cpu_e32), largest e32 / max |g| over the tensors, seeds 0 / 1 / 2:
+    padded_4x12x10 (f_maps (16, 48), (4, 12, 10), B = 3):   1.358e-06 / 1.575e-06 / 1.522e-06 (e32(d x) 1.921e-06 / 2.110e-06 / 1.745e-06)
+    main_4x8x12 (f_maps (32, 64, 128), (4, 8, 12), B = 2):  4.589e-06 / 6.514e-06 / 3.616e-06 (e32(d x) 4.629e-06 / 4.829e-06 / 4.426e-06)
+plain rounding error, of the order of the cubes' (1.8e-06, 3.0e-06 where no winner flips); the GPU run of seed 0 prints the same 1.358e-06 / 4.589e-06.
+
+Geometry: which test reaches which index arithmetic of csrc/unet_grad.hip (whole tiles are 4 x 8 x 8 voxels)
+    H != W (a y / x transposition):  test_layer_gradients[32to32-6x10x12-B1, 32+64to64-4x12x20-B3, 16+32to32-6x4x10-B2, 320+192to32-2x4x6-B3,
+        48+16to48-2x6x4-B1] (the two-source ones: gn_sum8's fine offsets, the v -> (z, y, x) split of the half-resolution statistics),
+        test_groupnorm_bwd_apply_accumulates[*-2x6x4], test_groupnorm_bwd_stats_direct, test_maxpool3d_2_bwd_direct_non_cubic,
+        test_composition_shared_selections[padded_4x12x10-0, main_4x8x12-0], test_conv3d_bwd_weight_direct
+    ragged tiles (the gz / gy / gx guards and zero fills of the weight-gradient staging, the data gradient at a partial tile): z, y and x in
+        [32to32-6x10x12-B1]; y and x in [32+64to64-4x12x20-B3]; z, y, x at once below one tile in [48+16to48-2x6x4-B1]
+    B = 1: [32to32-6x10x12-B1], [48+16to48-2x6x4-B1];  odd B: the B3 layer cases, [padded_4x12x10-0], every directly called kernel (B = 3)
+    a 32-block of input channels holding both sources and one half beyond Cin: [16+32to32-6x4x10-B2]; source 1 from channel 20: [c20+12-True]
+    more than 256 channels in groupnorm_bwd_coef (the c += 256 loops), 64 channels per group: [320+192to32-2x4x6-B3]
+    a chain of two tiles spanning samples 0 / 1 and a short last chain: test_conv3d_bwd_weight_direct[chains-*] (8 chains of 2 over 15 tiles: held
+        by tests/test_unet_grad_host.py::test_workspace_sizes);  y == nullptr: [chains-False]
+    groupnorm_bwd_stats: the 208-voxel chunk tail, C / 4 = 3, 12, 24 not dividing 256 (idle threads), C = 1536 (> 1024: the multi-trip branch),
+        goff = 8 with ldg > goff + C, both resolutions: test_groupnorm_bwd_stats_direct
+    linear_bwd_params: the row tail (rows < 8), the 1024-row chunk tail, the second output block, ldx > K, db == nullptr, the N and K limits:
+        test_linear_bwd_params_direct;  M == 0: test_linear_bwd_params_of_no_rows_is_exact_zeros
+    relu_mask (-0.0, a denormal, NaN, +-inf, in place, a length that is no multiple of 1024): test_relu_mask_direct
+
+Mutation record (MI355X; mutants of csrc/unet_grad.hip that stay inside every buffer, built apart from the tree, each run once over this whole file;
+"old" = the 20 tests the file had before the geometry cases, "new" = the 30 added).  Under every mutant all 20 old tests passed.
+    1. gn_sum8 with the y and x fine offsets swapped ((k >> 1) & 1 <-> k & 1): new failures test_groupnorm_bwd_stats_direct[12-True, 48-True,
+       96-True, 1536-True], nothing else.  The swap still adds the same eight voxels -- it only changes the fp32 order to g000 + g010 + g001 + ... --
+       so no test with a rounding-error bound can see it, at any shape; the statistics test can because it restates the documented order in fp32
+       and leaves only fp64 summation to the bound.
+    2. conv3d_bwd_weight_kernel decoding ty = rem % tiles_y, tx = rem / tiles_y: no failure, old or new, and none is possible: the decode is still a
+       bijection of the sample's tiles, every tile is visited once, only the order inside the fp32 chains moves (an equivalent mutant).
+    3. linear_bwd_params_kernel staging xs[rr][kk] from row rb + min(rr, rows - 1) instead of 0 for rr >= rows: no failure, old or new, and none is
+       possible on finite x: ys[rr][.] is still 0 for those rows, so each stray term is 0 * x (an equivalent mutant; the guard is redundant).
+   Because 2 and 3 cannot bite, two neighbours of them that can were run as a fourth build, again in bounds:
+    2b. the sample of a whole chain taken from its first tile (b = t_begin / tiles_per_sample): new failures test_conv3d_bwd_weight_direct[chains-True,
+        chains-False] (the chain that spans samples 0 / 1), nothing else -- every other case has one tile per chain or chains inside one sample.
+    3b. both row tiles of the tail re-read from the last row (xs and ys at rb + min(rr, rows - 1)): new failures test_linear_bwd_params_direct
+        [1-1-1, 7-3-5, 1031-8-32, 2061-128-32, 300-512-7]; [520-5-1023] passes as it must (520 rows are whole sub-tiles).
+   The new tests that no mutant fails (the ragged / non-cubic layer, composition, max-pool, apply and relu_mask cases) duplicate no old test: each
+   runs index arithmetic (guards, zero fills, decodes with unequal extents) that the cubes never reach, so they stay.
 """
 import copy
 
@@ -58,9 +99,10 @@ def r_layer(x0, x1, w, gamma, beta, groups, eps, mask=None):
     return F.relu(h) if mask is None else h * mask
 
 
-def r_unet(model, P, x, selections=None):
+def r_unet(model, P, x, selections=None, record=None):
     """selections: (ReLU masks per layer in execution order, pool winner indices per level) taken from the HIP forward (hip_selections): the restatement
-    then differentiates the same piecewise-linear map as the HIP run, whatever the dtype; None: it forms its own"""
+    then differentiates the same piecewise-linear map as the HIP run, whatever the dtype; None: it forms its own, and appends them to the two lists
+    of record when that is given (print_cpu_e32: shared selections without a GPU)"""
     masks, winners = (None, None) if selections is None else (iter(selections[0]), iter(selections[1]))
 
     def double_conv(prefix, dc, x0, x1=None):
@@ -69,12 +111,17 @@ def r_unet(model, P, x, selections=None):
             x0 = r_layer(x0, x1, P[n + ".conv.weight"], P[n + ".groupnorm.weight"], P[n + ".groupnorm.bias"], sc.groupnorm.num_groups, sc.groupnorm.eps,
                          mask=None if masks is None else next(masks).to(x0.dtype))
             x1 = None
+            if record is not None:
+                record[0].append(x0.detach() > 0)
         return x0
     feats = []
     for i, enc in enumerate(model.encoders):
         if i > 0 and winners is not None:
             idx = next(winners)
             x = x.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
+        elif i > 0 and record is not None:
+            x, idx = F.max_pool3d(x, 2, return_indices=True)
+            record[1].append(idx)
         elif i > 0:
             x = F.max_pool3d(x, 2)
         x = double_conv(f"encoders.{i}", enc.basic_module, x)
@@ -150,28 +197,49 @@ def hip_unet_grads(model_gpu, x, R, arith, fn=None):
 
 COMPOSITIONS = {"main": dict(in_ch=32, out_ch=8, f_maps=(32, 64, 128), n=16), "padded": dict(in_ch=8, out_ch=5, f_maps=(16, 48), n=8),
                 # stored widths 64 / 96 / 160 / 256: the max-pool without a statistics epilogue (96), gn_channel_stats_any, a 256-channel virtual concat
-                "wide": dict(in_ch=16, out_ch=4, f_maps=(96, 160), n=8)}
+                "wide": dict(in_ch=16, out_ch=4, f_maps=(96, 160), n=8),
+                # n: an int (a cube) or (D, H, W).  Non-cubic grids, H != W at every level: (4, 12, 10) -> (2, 6, 5), ragged 4 x 8 x 8 tiles in y and x,
+                # B = 3; three levels (4, 8, 12) -> (2, 4, 6) -> (1, 2, 3), ragged in x
+                "padded_4x12x10": dict(in_ch=8, out_ch=5, f_maps=(16, 48), n=(4, 12, 10), B=3),
+                "main_4x8x12": dict(in_ch=32, out_ch=8, f_maps=(32, 64, 128), n=(4, 8, 12))}
+NON_CUBIC = ("padded_4x12x10", "main_4x8x12")
 
 
-def _composition_inputs(which, seed):
-    """the model and inputs of a composition case; B = 2.  tests/ holds no CPU-only runner: print_cpu_e32() (no GPU needed) prints the three-seed stability figures of the module docstring"""
+def _dims(n):
+    return (n, n, n) if isinstance(n, int) else tuple(n)
+
+
+def _composition_inputs(which, seed, B=2):
+    """the model and inputs of a composition case.  tests/ holds no CPU-only runner: print_cpu_e32() (no GPU needed) prints the stability figures of the module docstring"""
     c = COMPOSITIONS[which]
     model = _model(c["in_ch"], c["out_ch"], c["f_maps"], seed)
     g = _gen(seed + 7)
-    x = torch.randn(2, c["in_ch"], c["n"], c["n"], c["n"], generator=g)
-    R = torch.randn(2, c["out_ch"], c["n"], c["n"], c["n"], generator=g)
+    x = torch.randn(B, c["in_ch"], *_dims(c["n"]), generator=g)
+    R = torch.randn(B, c["out_ch"], *_dims(c["n"]), generator=g)
     return model, x, R
 
 
 def print_cpu_e32():
+    def figures(g64, g32):
+        return (max(float((g32[k].double() - g64[k]).abs().max()) / float(g64[k].abs().max()) for k in g64), float((g32["x"].double() - g64["x"]).abs().max()))
     for which in ("main", "padded"):
         for seed in (0, 1, 2):
             model, x, R = _composition_inputs(which, seed)
             g64, _ = restated_unet_grads(model, x, R, torch.float64)
             g32, _ = restated_unet_grads(model, x, R, torch.float32)
-            rel = max(float((g32[k].double() - g64[k]).abs().max()) / float(g64[k].abs().max()) for k in g64)
-            ex = float((g32["x"].double() - g64["x"]).abs().max())
+            rel, ex = figures(g64, g32)
             print(f"[cpu-e32] {which} seed {seed}: max over tensors of e32 / max|g| = {rel:.3e}   e32(d x) = {ex:.3e}")
+    # shared selections without a GPU: the fp64 restatement's own ReLU masks and pool winners, handed to both precisions
+    for which in NON_CUBIC:
+        for seed in (0, 1, 2):
+            model, x, R = _composition_inputs(which, seed, B=COMPOSITIONS[which].get("B", 2))
+            sel = ([], [])
+            with torch.no_grad():
+                r_unet(model, {n: p.detach().double() for n, p in model.named_parameters()}, x.double(), record=sel)
+            g64, _ = restated_unet_grads(model, x, R, torch.float64, selections=sel)
+            g32, _ = restated_unet_grads(model, x, R, torch.float32, selections=sel)
+            rel, ex = figures(g64, g32)
+            print(f"[cpu-e32] {which} seed {seed}, shared selections: max over tensors of e32 / max|g| = {rel:.3e}   e32(d x) = {ex:.3e}")
 
 
 # ------------------------------------------------------------------------------------------------ 1. one layer, linear parts isolated
@@ -181,16 +249,27 @@ def _to_stored_cl(x, stored):
     return F.pad(v, (0, stored - v.shape[-1])) if stored != v.shape[-1] else v
 
 
-@pytest.mark.parametrize("real,stored,cout,dims", [
+LAYER_CUBIC = [                                # whole 4 x 8 x 8 tiles, H == W, B = 2 (their ids are the ones pytest gave them before B was a parameter)
     ((32,), (32,), 64, (8, 16, 16)),           # one source
     ((32, 64), (32, 64), 64, (8, 8, 8)),       # two sources, 8 groups of 12 channels: group 2 (channels 24..35) straddles src0 / src1
     ((16,), (16,), 48, (8, 8, 8)),             # padded output width (stored 64), a 16-wide input: the transposed pack padded to 32 columns
     ((48,), (64,), 32, (4, 8, 8)),             # padded input
     ((48, 16), (64, 32), 48, (8, 8, 8)),       # both sources and the output padded, the groups (8 per group) over the real channels
-])
-def test_layer_gradients(real, stored, cout, dims):
+]
+LAYER_RAGGED = [                               # H != W everywhere; partial tiles: the guards and zero fills of the weight-gradient staging, the data gradient at a partial tile
+    ((32,), (32,), 32, (6, 10, 12), 1),        # ragged in z, y and x, B = 1, the NCO = 1 weight-gradient kernel
+    ((32, 64), (32, 64), 64, (4, 12, 20), 3),  # two sources, the coarse one (2, 6, 10): gn_sum8 with H != W; ragged y and x; odd B
+    ((16, 32), (16, 32), 32, (6, 4, 10), 2),   # Cin = 48: one 32-block of input channels holds both sources, the next is half beyond Cin
+    ((320, 192), (320, 192), 32, (2, 4, 6), 3),  # 512 channels, 64 per group: the c += 256 loops of groupnorm_bwd_coef take two trips
+    ((48, 16), (64, 32), 48, (2, 6, 4), 1),    # every pad at once on a volume smaller than one tile in every axis
+]
+
+
+@pytest.mark.parametrize("real,stored,cout,dims,B",
+                         [pytest.param(*c, 2, id=f"real{i}-stored{i}-{c[2]}-dims{i}") for i, c in enumerate(LAYER_CUBIC)]
+                         + [pytest.param(*c, id="{}to{}-{}-B{}".format("+".join(map(str, c[0])), c[2], "x".join(map(str, c[3])), c[4])) for c in LAYER_RAGGED])
+def test_layer_gradients(real, stored, cout, dims, B):
     g = _gen(sum(real) + cout)
-    B = 2
     conv = SingleConv(sum(real), cout)
     conv.in_real = real
     _randomise_norms(conv, g)
@@ -223,7 +302,7 @@ def test_layer_gradients(real, stored, cout, dims):
             r = real[int(name[-1])]
             assert not bool(ours[..., r:].any()), f"{name}: pad gradients must be exact zeros"
             ours = ours[..., :r].permute(0, 4, 1, 2, 3)
-        _check(f"layer {real}->{cout} {name}", res[torch.float64][1][i], res[torch.float32][1][i], ours)
+        _check(f"layer {real}->{cout} {dims} B={B} {name}", res[torch.float64][1][i], res[torch.float32][1][i], ours)
 
 
 # ------------------------------------------------------------------------------------------------ 2. max-pool: exact
@@ -266,12 +345,13 @@ def test_composition_strict_fp32(which):
         assert torch.equal(gh[k], gh2[k]), k
 
 
-@pytest.mark.parametrize("which,seed", [("main", 0), ("main", 1), ("padded", 0), ("wide", 0)])
+@pytest.mark.parametrize("which,seed", [("main", 0), ("main", 1), ("padded", 0), ("wide", 0), ("padded_4x12x10", 0), ("main_4x8x12", 0)])
 def test_composition_shared_selections(which, seed):
     """The sharp check through the depth of the net: the restatement is handed the HIP forward's ReLU masks and pool winners, so both sides differentiate
     the same piecewise-linear map, no winner can flip on either side, and e32 is the plain fp32 rounding error (about 1e-06 of the largest gradient)
-    for every seed -- the rule's 4 x e32 + ulp then holds every tensor of the 3-level net to that.  Strict-fp32 forward."""
-    model, x, R = _composition_inputs(which, seed)
+    for every seed -- the rule's 4 x e32 + ulp then holds every tensor of the 3-level net to that.  Strict-fp32 forward.  The non-cubic cases
+    (COMPOSITIONS: H != W at every level, ragged tiles, one of them B = 3) carry the same rule."""
+    model, x, R = _composition_inputs(which, seed, B=COMPOSITIONS[which].get("B", 2))
     mg = copy.deepcopy(model).to(DEV)
     fp32 = AR.DEFAULT.strict_fp32()
     sel = hip_selections(mg, x, fp32)
@@ -284,24 +364,25 @@ def test_composition_shared_selections(which, seed):
     _compare_all(f"unet {which} seed {seed} shared", g64, g32, gh)
 
 
-@pytest.mark.parametrize("half", [False, True])
-def test_groupnorm_bwd_apply_accumulates(half):
-    """out= given: the result is added to what it holds, one fp32 add per element"""
+@pytest.mark.parametrize("half,dims", [pytest.param(False, (4, 4, 4), id="False"), pytest.param(True, (4, 4, 4), id="True"),
+                                       pytest.param(False, (2, 6, 4), id="False-2x6x4"), pytest.param(True, (2, 6, 4), id="True-2x6x4")])
+def test_groupnorm_bwd_apply_accumulates(half, dims):
+    """out= given: the result is added to what it holds, one fp32 add per element.  (2, 6, 4): the v -> (z, y, x) split and gn_sum8 with H != W"""
     from garmentnets_amd import ops
     g = _gen(31 + half)
-    B, D, C, ld, goff, coff = 2, 4, 32, 96, 32, 64
+    B, (D, H, W), C, ld, goff, coff = 2, dims, 32, 96, 32, 64
     k = 2 if half else 1
-    dxn = torch.randn(B, k * D, k * D, k * D, ld, generator=g).to(DEV)
-    x = torch.randn(B, D, D, D, C, generator=g).to(DEV)
+    dxn = torch.randn(B, k * D, k * H, k * W, ld, generator=g).to(DEV)
+    x = torch.randn(B, D, H, W, C, generator=g).to(DEV)
     p, q, r = (torch.randn(B, 128, generator=g).to(DEV) for _ in range(3))
-    held = torch.randn(B, D, D, D, C, generator=g).to(DEV)
+    held = torch.randn(B, D, H, W, C, generator=g).to(DEV)
     plain = ops.groupnorm_bwd_apply(dxn, goff, x, p, q, r, coff, half=half)
     out = held.clone()
     assert ops.groupnorm_bwd_apply(dxn, goff, x, p, q, r, coff, half=half, out=out) is out
     assert torch.equal(out, held + plain)
     fine = dxn[..., goff:goff + C].double()
     if half:
-        fine = fine.view(B, D, 2, D, 2, D, 2, C).sum((2, 4, 6))
+        fine = fine.view(B, D, 2, H, 2, W, 2, C).sum((2, 4, 6))
     ref = fine * p[:, None, None, None, coff:coff + C].double() + k ** 3 * (x.double() * q[:, None, None, None, coff:coff + C].double()
                                                                           + r[:, None, None, None, coff:coff + C].double())
     assert float((plain.double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
@@ -411,3 +492,159 @@ def test_reference_training_shape():
     last = f"decoders.{len(model.decoders) - 1}.basic_module.SingleConv2.conv.weight"
     for k in ("encoders.0.basic_module.SingleConv1.conv.weight", last, "final_conv.weight", "final_conv.bias"):
         _check(f"training shape {k}", g64[k], g32[k], gh[k])
+
+
+# ------------------------------------------------------------------------------------------------ 6. the kernels called directly, at the shapes the net never gives them
+def _cl(t):
+    """(B, C, D, H, W) -> channel-last contiguous"""
+    return t.permute(0, 2, 3, 4, 1).contiguous()
+
+
+BW_DIRECT = {
+    # 15 tiles, 12 x 4 = 48 blocks -> 8 chains of 2 tiles (tests/test_unet_grad_host.py::test_workspace_sizes holds the count): chain 2 = tiles 4, 5, the
+    # last tile of sample 0 and the first of sample 1 (the per-sample affine switches in mid-chain), chain 7 = tile 14 alone (a short last chain)
+    "chains": dict(B=3, dims=(4, 8, 40), C0=384, C1=0, cout=256),
+    # widths the C ABI accepts (multiples of 4) and the net never has: source 1 begins at channel 20 of the one 32-block; ragged y and x
+    "c20+12": dict(B=3, dims=(4, 6, 10), C0=20, C1=12, cout=32),
+}
+
+
+@pytest.mark.parametrize("case,masked", [("chains", True), ("chains", False), ("c20+12", True)])
+def test_conv3d_bwd_weight_direct(case, masked):
+    """ops.conv3d_bwd_weight against d/dw of conv3d(x * a + d, w, padding=1) under the gradient dy (masked by y > 0; masked False: y = None, the layer
+    without ReLU), a and d random per sample and channel"""
+    from garmentnets_amd import ops
+    c = BW_DIRECT[case]
+    B, dims, C0, C1, cout = c["B"], c["dims"], c["C0"], c["C1"], c["cout"]
+    g = _gen(C0 + C1 + cout)
+    x0 = torch.randn(B, C0, *dims, generator=g)
+    x1 = torch.randn(B, C1, *(n // 2 for n in dims), generator=g) if C1 else None
+    a = 0.5 + torch.rand(B, C0 + C1, generator=g)
+    d = 0.3 * torch.randn(B, C0 + C1, generator=g)
+    y = torch.randn(B, cout, *dims, generator=g)
+    y[:, :, 0, 0, ::2] = 0.0                        # y == 0 masks (ReLU's gradient at 0 is 0), -0.0 as well
+    y[:, :, 1, 1, ::2] = -0.0
+    dy = torch.randn(B, cout, *dims, generator=g)
+    res = {}
+    for dtype in (torch.float64, torch.float32):
+        x = x0.to(dtype) if x1 is None else torch.cat((x0.to(dtype), F.interpolate(x1.to(dtype), scale_factor=2, mode="nearest")), 1)
+        w = torch.zeros(cout, C0 + C1, 3, 3, 3, dtype=dtype, requires_grad=True)
+        out = F.conv3d(x * a.to(dtype)[:, :, None, None, None] + d.to(dtype)[:, :, None, None, None], w, padding=1)
+        (res[dtype],) = torch.autograd.grad(out, w, (dy * (y > 0) if masked else dy).to(dtype))
+    args = (_cl(x0).to(DEV), None if x1 is None else _cl(x1).to(DEV), a.to(DEV), d.to(DEV), _cl(y).to(DEV) if masked else None, _cl(dy).to(DEV))
+    ours = ops.conv3d_bwd_weight(*args)
+    _check(f"conv3d_bwd_weight {case} {'masked' if masked else 'y=None'} d weight", res[torch.float64], res[torch.float32], ours)
+    assert torch.equal(ours, ops.conv3d_bwd_weight(*args))
+
+
+@pytest.mark.parametrize("C", [20, 96])
+def test_maxpool3d_2_bwd_direct_non_cubic(C):
+    """ops.maxpool3d_2_bwd at B = 3, (4, 6, 10): the (x, y, z) decode with Do != Ho != Wo, a width (20) that is no multiple of 16; ties and NaNs as in
+    test_max_pool_gradient_is_bit_exact_with_ties_and_a_nan, cut to this shape"""
+    from garmentnets_amd import ops
+    g = _gen(50 + C)
+    x = torch.randn(3, C, 4, 6, 10, generator=g)
+    x[:, :8, 0:2, 0:2, 0:2] = 1.25                 # whole windows tied: the first voxel in (z, y, x) order wins
+    x[:, 8:16, :, :, 1::2] = x[:, 8:16, :, :, 0::2].clone()  # pairs tied along x
+    x[0, :, 2:4, 2:4, 2:4] = x[0, :, 2:3, 2:3, 2:3].clone()
+    x[1, 3, 3, 4, 6] = float("nan")                # a NaN wins its window
+    x[1, 4, 2, 4, 4] = float("nan")
+    x[1, 4, 3, 5, 5] = float("nan")                # two NaNs in one window: ATen keeps the later one
+    x[2, C - 1, 3, 5, 9] = float("nan")            # the last voxel of the last window of the last sample
+    go = torch.randn(3, C, 2, 3, 5, generator=g)
+    xr = x.clone().requires_grad_(True)
+    (ref,) = torch.autograd.grad(F.max_pool3d(xr, 2), xr, go)
+    ours = ops.maxpool3d_2_bwd(_cl(go).to(DEV), _cl(x).to(DEV))
+    assert torch.equal(ours.cpu().permute(0, 4, 1, 2, 3), ref)
+
+
+@pytest.mark.parametrize("half", [False, True])
+@pytest.mark.parametrize("C", [12, 48, 96, 1536])
+def test_groupnorm_bwd_stats_direct(C, half):
+    """ops.groupnorm_bwd_stats at 720 voxels (6, 10, 12): a 208-voxel second chunk; C / 4 = 3, 12, 24 do not divide 256 (threads idle beyond the last
+    voxel group), C = 1536 takes the multi-trip branch; goff = 8 inside rows of goff + C + 4 columns.  The reference adds the SAME fp32 terms in fp64
+    (half: after the eight-term fp32 sum in gn_sum8's documented order, done here in fp32), so only the fp64 summation order differs, and the bound is
+    the one of fp64 summation in any order, for both sides together: |ours - ref| <= V * 2^-52 * sum |term| per entry"""
+    from garmentnets_amd import ops
+    g = _gen(400 + C + half)
+    B, (D, H, W), goff = 3, (6, 10, 12), 8
+    V, ldg, k = D * H * W, goff + C + 4, 2 if half else 1
+    dxn = torch.randn(B, k * D, k * H, k * W, ldg, generator=g)
+    x = torch.randn(B, D, H, W, C, generator=g) + 0.5
+    s1, s2 = ops.groupnorm_bwd_stats(dxn.to(DEV), goff, x.to(DEV), half=half)
+    assert s1.dtype == torch.float64 and tuple(s1.shape) == (B, C) and tuple(s2.shape) == (B, C)
+    gsum = dxn[..., goff:goff + C]
+    if half:
+        fine = gsum.view(B, D, 2, H, 2, W, 2, C)
+        gsum = None
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):                   # ((((((g000 + g001) + g010) + g011) + g100) + g101) + g110) + g111, fp32
+                    t = fine[:, :, dz, :, dy, :, dx]
+                    gsum = t if gsum is None else gsum + t
+        assert gsum.dtype == torch.float32
+    g64, x64 = gsum.double().reshape(B, V, C), x.double().reshape(B, V, C)
+    for name, ours, terms in (("sum dxn", s1, g64), ("sum dxn * x", s2, g64 * x64)):
+        err = (ours.cpu() - terms.sum(1)).abs()
+        bound = V * 2.0 ** -52 * terms.abs().sum(1)
+        print(f"[grad-error] groupnorm_bwd_stats C={C} half={half} {name}: largest error {float(err.max()):.3e}, largest error / bound {float((err / bound).max()):.3e}")
+        assert bool((err <= bound).all()), (name, float((err / bound).max()))
+
+
+# (M, N, K, columns of x beyond K, with_bias)
+LINEAR_CASES = [(1, 1, 1, 0, True),             # the smallest call
+                (7, 3, 5, 0, True),             # M below one 8-row sub-tile
+                (1031, 8, 32, 8, True),         # a 7-row second chunk; x is 40 columns wide: ldx > K
+                (2061, 128, 32, 0, True),       # N * (K + 1) = 4224: two output blocks; a 13-row third chunk (one sub-tile and a 5-row tail)
+                (300, 512, 7, 0, False),        # the N = 512 limit; no bias gradient (db == nullptr)
+                (520, 5, 1023, 0, True)]        # the K = 1023 limit
+
+
+@pytest.mark.parametrize("M,N,K,xpad,with_bias", LINEAR_CASES)
+def test_linear_bwd_params_direct(M, N, K, xpad, with_bias):
+    """ops.linear_bwd_params against dY^T X and sum dY.  The file's rule, and beside it the bound derived from the kernel's own summation (at most 1024
+    sequential fp32 fmas per chunk, the chunks folded in fp64, one rounding to fp32): (1024 + 2) * 2^-24 * (|dY|^T |X|) per entry."""
+    from garmentnets_amd import ops
+    g = _gen(7 * M + 3 * N + K)
+    dy = torch.randn(M, N, generator=g)
+    xw = torch.randn(M, K + xpad, generator=g) + 0.25
+    dw, db = ops.linear_bwd_params(dy.to(DEV), xw.to(DEV), K=K, with_bias=with_bias)
+    x = xw[:, :K]
+    assert tuple(dw.shape) == (N, K)
+    checks = [("d weight", dw, dy.double().t() @ x.double(), dy.t() @ x, dy.abs().double().t() @ x.abs().double())]
+    if with_bias:
+        checks.append(("d bias", db, dy.double().sum(0), dy.sum(0), dy.abs().double().sum(0)))
+    else:
+        assert db is None
+    for name, ours, ref64, t32, mag in checks:
+        derived = (1024 + 2) * 2.0 ** -24 * mag
+        err = (ours.double().cpu() - ref64).abs()
+        print(f"[grad-error] linear_bwd_params M={M} N={N} K={K} {name}: largest error / derived bound {float((err / derived).max()):.3e}")
+        assert bool((err <= derived).all()), name
+        _check(f"linear_bwd_params M={M} N={N} K={K} {name}", ref64, t32, ours)
+
+
+def test_linear_bwd_params_of_no_rows_is_exact_zeros():
+    from garmentnets_amd import ops
+    dw, db = ops.linear_bwd_params(torch.empty(0, 6, device=DEV), torch.empty(0, 9, device=DEV))
+    assert tuple(dw.shape) == (6, 9) and tuple(db.shape) == (6,)
+    assert not bool(dw.view(torch.int32).any()) and not bool(db.view(torch.int32).any())
+
+
+def test_relu_mask_direct():
+    """ops.relu_mask over 4 * 1027 values (a 3-float4 last block), y with the values a comparison can get wrong, out of place and in place"""
+    from garmentnets_amd import ops
+    g = _gen(77)
+    n = 4 * 1027
+    y = torch.randn(n, generator=g)
+    special = torch.tensor([0.0, -0.0, 1e-42, -1e-42, float("nan"), float("inf"), float("-inf")])
+    y[:special.numel()] = special
+    y[-special.numel():] = special
+    dy = torch.randn(n, generator=g)
+    ref = torch.where(y > 0, dy, torch.zeros(()))
+    yd, dyd = y.to(DEV), dy.to(DEV)
+    out = ops.relu_mask(yd, dyd)
+    assert torch.equal(dyd.cpu(), dy), "out of place: dy is not written"
+    assert torch.equal(out.cpu(), ref) and torch.equal(out.cpu().view(torch.int32), ref.view(torch.int32))
+    assert ops.relu_mask(yd, dyd, out=dyd) is dyd
+    assert torch.equal(dyd.cpu(), ref) and torch.equal(dyd.cpu().view(torch.int32), ref.view(torch.int32))

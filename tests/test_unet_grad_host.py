@@ -37,6 +37,8 @@ def test_workspace_sizes():
     assert lib.gn_conv3d_bwd_weight_workspace_bytes(2, 128, 128, 128, 128, 128) == 64 * 27 * 128 * 128 * 4   # 16384 tiles, 8 blocks: 64 chains of 256
     assert lib.gn_conv3d_bwd_weight_workspace_bytes(1, 8, 8, 8, 16, 32) == 2 * 27 * 32 * 32 * 4              # Cin 16 rounds up to one 32-slice
     assert lib.gn_conv3d_bwd_weight_workspace_bytes(3, 12, 8, 8, 96, 96) == 9 * 27 * 96 * 96 * 4             # 9 tiles, 9 blocks (32-wide columns)
+    # 15 tiles (5 per sample), 48 blocks: 8 chains of 2 -- chain 2 spans samples 0 / 1, chain 7 holds one tile (the GPU suite's direct weight-gradient case)
+    assert lib.gn_conv3d_bwd_weight_workspace_bytes(3, 4, 8, 40, 384, 256) == 8 * 27 * 384 * 256 * 4
     assert lib.gn_conv3d_bwd_weight_workspace_bytes(1, 8, 8, 8, 16, 48) == 0                                 # refused shape
     assert lib.gn_groupnorm_bwd_stats_workspace_bytes(2, 4096, 64) == 2 * 8 * 2 * 64 * 8
     assert lib.gn_groupnorm_bwd_stats_workspace_bytes(3, 513, 32) == 3 * 2 * 2 * 32 * 8
