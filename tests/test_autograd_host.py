@@ -1,4 +1,8 @@
-"""CPU: the operator gradients' host side -- argument checks raised before any launch, header / prototypes in step, imports without a GPU."""
+"""CPU: the operator gradients' host side -- argument checks raised before any launch, header / prototypes in step, imports without a GPU -- and
+the SPARSE restatements of the six operators (s_*: index_add_ / scatter_reduce / gather, memory linear in the input) that
+tests/test_gpu_autograd_edges.py uses as its fp64 yardstick at sizes the dense restatements of tests/test_gpu_autograd.py (masks of cells x N,
+one-hot matrices of rows x n) cannot hold.  The licence for that use is at the end of this file: on inputs small enough for the dense forms, each
+sparse form gives the same forward and the same gradient in fp64, exactly, planted ties included."""
 import os
 import re
 
@@ -117,3 +121,162 @@ def test_wrappers_refuse_mul_by_name_and_bad_shapes():
 def test_cpu_tensors_are_rejected_after_the_checks():
     with pytest.raises(_lib.GarmentNetsHipError):
         ops.grid_scatter_bwd(torch.zeros(1, 8, 4), torch.zeros(5, dtype=torch.int32), 5, "sum")
+
+
+# ------------------------------------------------------------------------------------------------ sparse restatements (plain torch, any dtype, CPU)
+def s_first_max(v, key, nkeys, valid=None):
+    """v (E, C), key (E,) int64: the destination of every element -> bool (E, C), True where the element is the FIRST maximum of its destination
+    among `valid` elements.  Written out, no argmax: the maximum per (destination, channel) by scatter_reduce('amax'), then the minimum element
+    index among the elements equal to it by scatter_reduce('amin')."""
+    E, C = v.shape
+    v = v.detach()
+    if valid is not None:
+        v = torch.where(valid[:, None], v, torch.full_like(v, -float("inf")))
+    kx = key[:, None].expand(E, C)
+    top = torch.full((nkeys, C), -float("inf"), dtype=v.dtype).scatter_reduce(0, kx, v, "amax", include_self=True)
+    eq = v == top.gather(0, kx)
+    if valid is not None:
+        eq &= valid[:, None]
+    idx = torch.arange(E)[:, None].expand(E, C)
+    first = torch.full((nkeys, C), E, dtype=torch.int64).scatter_reduce(0, kx, torch.where(eq, idx, E), "amin", include_self=True)
+    return idx == first.gather(0, kx)
+
+
+def _s_select(src, sel, key, nkeys):
+    return torch.zeros((nkeys, src.shape[1]), dtype=src.dtype).index_add_(0, key, src * sel.to(src.dtype))
+
+
+def s_scatter(src, cell, cells, reduce):
+    """src (N, C), cell (N,) int64 -> (cells, C)"""
+    if reduce in ("max", "min"):
+        return _s_select(src, s_first_max(src if reduce == "max" else -src, cell, cells), cell, cells)
+    tot = torch.zeros((cells, src.shape[1]), dtype=src.dtype).index_add_(0, cell, src)
+    if reduce == "mean":
+        tot = tot / torch.bincount(cell, minlength=cells).clamp(min=1).to(src.dtype)[:, None]
+    return tot
+
+
+def s_segment_max(h, slot_src, M, S):
+    key = torch.arange(M * S) // S
+    return _s_select(h, s_first_max(h, key, M, slot_src >= 0), key, M)
+
+
+def s_global_max(h, sizes):
+    key = torch.repeat_interleave(torch.arange(len(sizes)), torch.as_tensor(sizes, dtype=torch.int64))
+    return _s_select(h, s_first_max(h, key, len(sizes)), key, len(sizes))
+
+
+def s_sa_gather(x, pos, centre_idx, slot_src, S):
+    """edge rows [x_j, pos_j - pos_i]; an empty slot is a zero row.  x by row indexing (its gradient is an index_add_), positions are data"""
+    valid = (slot_src >= 0)[:, None].to(pos.dtype)
+    j = slot_src.clamp(min=0).long()
+    ci = centre_idx.long()[torch.arange(slot_src.numel()) // S]
+    rel = (pos[j] - pos[ci]) * valid
+    return torch.cat((x[j] * valid.to(x.dtype), rel), 1) if x is not None else rel
+
+
+def s_knn(x, nbr, d2):
+    """nbr / d2 (Nq, k) shared data: the k weighted rows gathered and summed per query (no gradient through the weights)"""
+    valid = nbr >= 0
+    w = valid.to(x.dtype) / d2.to(x.dtype).clamp(min=1e-16)
+    coef = w / w.sum(1, keepdim=True)
+    return (coef[:, :, None] * x[nbr.clamp(min=0).long()]).sum(1)
+
+
+# the sampler's restatement is F.grid_sample itself, linear in its input already: tests/test_gpu_autograd.py::r_sample serves both roles.
+
+
+# ------------------------------------------------------------------------------------------------ sparse == dense, forward and gradient, in fp64
+# Inputs are multiples of 2^-6 below 2^6 in magnitude and every weight is a power of two, so each sum and product of either form is exact in
+# fp64: the equalities below cannot depend on the order in which a GEMM or an index_add_ happens to add, and "equal" means equal bits.
+def _quant(shape, seed):
+    return torch.randint(-2 ** 12, 2 ** 12, shape, generator=torch.Generator().manual_seed(seed)).double() / 64
+
+
+def _both(dense, sparse, x, gout):
+    outs = []
+    for fn in (dense, sparse):
+        leaf = x.clone().requires_grad_(True)
+        out = fn(leaf)
+        outs.append((out.detach(), torch.autograd.grad(out, [leaf], gout)[0]))
+    (fd, gd), (fs, gs) = outs
+    assert fd.dtype == torch.float64 and fd.shape == fs.shape
+    assert torch.equal(fd, fs) and torch.equal(gd, gs)
+    assert float(gd.abs().max()) > 0
+    return fd, gd
+
+
+@pytest.mark.parametrize("reduce", ["max", "min", "mean", "sum"])
+def test_sparse_scatter_equals_dense(reduce):
+    from test_gpu_autograd import r_scatter
+    n, c, cells = 500, 7, 40
+    src = _quant((n, c), 1)
+    cell = torch.randint(0, cells, (n,), generator=torch.Generator().manual_seed(2))
+    cell[cell == 5] = 6                                        # an empty cell
+    src[300:400] = src[100:200]                                # planted ties: equal rows ...
+    cell[300:400] = cell[100:200]                              # ... in equal cells
+    cell[-30:] = 9
+    src[-30:, 0], src[-30:, 1] = 64.0, -64.0                   # thirty points of one cell hold its maximum / minimum
+    gout = _quant((cells, c), 3)
+    _, g = _both(lambda s: r_scatter(s, cell, cells, reduce), lambda s: s_scatter(s, cell, cells, reduce), src, gout)
+    if reduce in ("max", "min"):
+        ch = 0 if reduce == "max" else 1
+        assert float(g[n - 30, ch]) == float(gout[9, ch]) and float(g[n - 29:, ch].abs().max()) == 0.0
+
+
+def test_sparse_segment_max_equals_dense():
+    from test_gpu_autograd import r_segment_max
+    M, S, C = 23, 7, 11
+    h = torch.relu(_quant((M * S, C), 4))
+    h[1::S] = h[0::S]                                          # slot 1 repeats slot 0
+    slot = torch.randint(-1, 30, (M * S,), generator=torch.Generator().manual_seed(5)).to(torch.int32)
+    slot[3 * S:4 * S] = -1                                     # a centre without a valid slot
+    slot[5 * S] = -1                                           # the first of two tied slots is empty: the second one wins
+    gout = _quant((M, C), 6)
+    _, g = _both(lambda t: r_segment_max(t, slot, M, S), lambda t: s_segment_max(t, slot, M, S), h, gout)
+    assert float(g[3 * S:4 * S].abs().max()) == 0.0 and float(g[5 * S].abs().max()) == 0.0
+
+
+def test_sparse_global_max_equals_dense():
+    from test_gpu_autograd import r_global_max
+    sizes, C = [40, 1, 0, 17, 16], 9
+    h = torch.relu(_quant((sum(sizes), C), 7))
+    h[0] = h[33] = h[:40].max(0).values                        # rows 0 and 33 both hold every channel's maximum
+    gout = _quant((len(sizes), C), 8)
+    _, g = _both(lambda t: r_global_max(t, sizes), lambda t: s_global_max(t, sizes), h, gout)
+    assert torch.equal(g[0], gout[0]) and float(g[33].abs().max()) == 0.0
+
+
+def test_sparse_sa_gather_equals_dense():
+    from test_gpu_autograd import r_sa_gather
+    n, Mc, S, C = 60, 25, 6, 5
+    g = torch.Generator().manual_seed(9)
+    slot = torch.randint(-1, n, (Mc * S,), generator=g).to(torch.int32)
+    slot[:S] = 7                                               # one point in every slot of a centre
+    slot[S::S] = 11                                            # ... and one point in every centre
+    centre = torch.randint(0, n, (Mc,), generator=g)
+    pos, x = _quant((n, 3), 10), _quant((n, C), 11)
+    gout = _quant((Mc * S, C + 3), 12)
+    _both(lambda t: r_sa_gather(t, pos, centre, slot, S), lambda t: s_sa_gather(t, pos, centre, slot, S), x, gout)
+    assert torch.equal(r_sa_gather(None, pos, centre, slot, S), s_sa_gather(None, pos, centre, slot, S))
+
+
+def test_sparse_knn_equals_dense():
+    from test_gpu_autograd import r_knn
+    ns, C = 30, 6
+    # weights 1 / d2 that are powers of two with a power-of-two sum: (1), (1/2, 1/2), (1/4, 1/4, 1/2), (1/4 x 4) and a row with invalid slots
+    pat = torch.tensor([[1.0, 0, 0, 0], [2.0, 2.0, 0, 0], [4.0, 4.0, 2.0, 0], [1.0, 1.0, 1.0, 1.0], [0.0, 0.0, 0, 0]], dtype=torch.float32)
+    use = torch.tensor([[1, 0, 0, 0], [1, 1, 0, 0], [1, 1, 1, 0], [1, 1, 1, 1], [1, 1, 0, 0]], dtype=torch.bool)   # the last row: d2 = 0 twice, both clamped: 1/2, 1/2
+    g = torch.Generator().manual_seed(13)
+    rows = torch.arange(100) % 5
+    d2 = pat[rows]
+    others = torch.tensor([j for j in range(ns) if j != 3])
+    nbr = torch.stack([torch.cat((torch.tensor([3]), others[torch.randperm(ns - 1, generator=g)[:3]])) for _ in range(100)]).to(torch.int32)
+    # (source 3 is every query's first neighbour: a hot destination; the other three are distinct)
+    nbr = torch.where(use[rows], nbr, torch.full_like(nbr, -1))
+    d2 = torch.where(use[rows], d2, torch.zeros_like(d2))
+    for r in range(100):
+        v = nbr[r][nbr[r] >= 0].tolist()
+        assert len(set(v)) == len(v)
+    x, gout = _quant((ns, C), 14), _quant((100, C), 15)
+    _both(lambda t: r_knn(t, nbr, d2, ns), lambda t: s_knn(t, nbr, d2), x, gout)
