@@ -9,9 +9,15 @@ The UNet is not a torch graph (channel-last, channel-padded volumes, GroupNorm f
 materialised), so it gets its own backward: ``conv3d_gcr`` / ``max_pool3d_2`` / ``unet3d`` run the existing forward kernels and differentiate them with
 csrc/unet_grad.hip (DESIGN.md "UNet gradients").
 
-What this is NOT: a training loop, an optimiser, train-mode BatchNorm, or a backward for the decoder MLPs / ``gn_linear`` layers / ``gn_sa_fused`` of
-the inference path.  The inference modules do not import this file; ``gn_sa_fused`` stays inference-only (``point_conv_max`` is
-the unfused chain).
+The dense layers of this package (components.mlp.MLPStack, HipLinear) hold torch parameters but evaluate through ``gn_linear``, which torch's autograd
+cannot see: ``mlp`` / ``linear`` run the same forward kernels block by block, keep each block's input and ReLU output, and differentiate them with
+csrc/linear_grad.hip (DESIGN.md "MLP gradients"); ``implicit_decode`` is the decoder as the chain ``grid_sample_points`` -> ``mlp``.  With these a
+gradient flows from a torch loss on the decoder's prediction to every parameter of the second stage, and into PointNet++ through
+``point_conv_max(local_nn=lambda e: mlp(stack, e))``.
+
+What this is NOT: a training loop, an optimiser, train-mode BatchNorm, gradients of the loss kernels (csrc/losses.hip: torch's own losses close the
+chain), or a backward for the fused inference kernels (the fused / split-operand decoder, ``gn_sa_fused``: ``implicit_decode`` and ``point_conv_max``
+are the unfused chains).  The inference modules do not import this file.
 
 Selections (max / min) hand the gradient to ONE element per (slot, channel): among equal values the lowest point / edge index (torch_scatter's CUDA
 choice is whichever thread wins an atomic: parity unpinned).  Every sum is ordered: identical calls give identical bits.
@@ -22,11 +28,11 @@ import torch.nn.functional as F
 
 from . import ops
 from .components import unet3d as U
-from .components.mlp import param_cache
+from .components.mlp import HipLinear, MLPStack, pack_wb, param_cache
 from .components.pointnet2 import Segments, _example_self_src
 
 __all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
-           "conv3d_gcr", "max_pool3d_2", "unet3d"]
+           "conv3d_gcr", "max_pool3d_2", "unet3d", "mlp", "linear", "implicit_decode"]
 
 
 def _rows(t):
@@ -424,3 +430,112 @@ def unet3d(model, x, arith=None):
         v, stats = _conv(dc.SingleConv2, v, None, stats, None, arith)
     fc = model.final_conv
     return _FinalConv.apply(v, fc.weight, fc.bias, fc).permute(0, 4, 1, 2, 3)
+
+
+# ------------------------------------------------------------------------------------------------ the MLP blocks
+class _LinearBlock(torch.autograd.Function):
+    """one block r = act(x W^T + b), y = r * sc + sh of an MLPStack (or a bare HipLinear).  layer = (wp, b, sc, sh, k): the forward's packs of the
+    parameters, built at their present versions.  weight / bias / gamma / beta are the module's own parameters: they are saved, so the backward
+    differentiates the parameters the forward used and an in-place update in between is an autograd version error.  bn: the BatchNorm module
+    (its running statistics are data, read at the forward) or None; owner: the module whose ParamCache keeps the transposed weight pack."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, layer, relu, bn, owner, idx):
+        wp, b, sc, sh, k = layer
+        r = ops.linear(x, wp, b, None, None, relu=relu, K=k)          # the epilogue apart: r is what the mask and the scale gradient need
+        y = r if sc is None else ops.row_affine(r, sc, sh)
+        ctx.save_for_backward(x, r if relu else None, weight, bias, gamma, beta)
+        ctx.sc, ctx.owner, ctx.idx = sc, owner, idx
+        if bn is not None:
+            ctx.mean = bn.running_mean.detach().double()
+            ctx.inv = 1.0 / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, r, weight, bias, gamma, beta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n, k = weight.shape
+        g, sums = ops.linear_act_bwd(ops._grad_rows(grad_y, "grad_y", n), r, ctx.sc)
+        dx = dw = db = dgamma = dbeta = None
+        if need[0]:
+            # (the saved weight IS the module's at the forward's version -- unpacking it has checked that -- so the version-keyed cache holds its pack)
+            gen = (weight.device,) + tuple(p._version for p in ctx.owner.parameters())
+            wt = param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(weight.t().contiguous(), None)[0])
+            dx = ops.linear(g, wt, K=n)
+        if need[1]:
+            dw = ops.linear_bwd_weight(g, x, K=k)
+        if bias is not None and need[2]:
+            db = sums[0].float()
+        if gamma is not None and need[3]:
+            dgamma = ((sums[2] - ctx.mean * sums[1]) * ctx.inv).float()
+        if beta is not None and need[4]:
+            dbeta = sums[1].float()
+        return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+
+
+def _needs_grad(module, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+def _fp32_features(x, who):
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"{who}: expected torch.float32 features (..., C), got {getattr(x, 'dtype', type(x).__name__)}")
+    return x
+
+
+def _grad_layers(module, pack):
+    """the forward's packs at the parameters' PRESENT versions (PackedModule.packed() is not keyed by them: it serves inference, where nothing updates
+    a parameter in place)"""
+    gen = (next(module.parameters()).device,) + tuple(t._version for t in list(module.parameters()) + list(module.buffers()))
+    return param_cache(module, "_grad_fwd_packs").get(gen, "layers", pack)
+
+
+def mlp(stack, x):
+    """``MLPStack.forward``'s contract -- x fp32 (..., C) -> (..., C') through [Linear, ReLU, eval-mode BatchNorm] blocks -- differentiable in x and
+    in every Linear weight / bias and BatchNorm weight / bias of the stack; the running statistics are data.  Each block runs gn_linear with the ReLU
+    and WITHOUT the BatchNorm epilogue, keeps x and r, and applies the epilogue's own fmul / fadd as gn_row_affine: the bits are ``stack(x)``'s, and
+    the mask is the forward's own r > 0 (y = r * sc + sh cannot be inverted).  Backward: csrc/linear_grad.hip, dX = gn_linear on the transposed pack.
+    Eval-mode only: a stack with a BatchNorm in training mode raises NotImplementedError (the forward folds the running statistics whatever the mode,
+    so that gradient would silently be the wrong one; a fresh module is in training mode -- call .eval()).  Under torch.no_grad(), or when nothing
+    requires a gradient, this is ``stack(x)``'s launches and nothing is saved."""
+    if not isinstance(stack, MLPStack):
+        raise TypeError(f"mlp: expected a components.mlp.MLPStack, got {type(stack).__name__}")
+    _fp32_features(x, "mlp")
+    for block in stack:
+        if len(block) > 2 and block[2].training:
+            raise NotImplementedError("mlp: train-mode BatchNorm has no gradient here (the forward folds the running statistics): call .eval() on the stack")
+    if not _needs_grad(stack, x):
+        with torch.no_grad():
+            return stack(x)
+    lead = x.shape[:-1]
+    h = _rows(x.reshape(-1, x.shape[-1]))
+    for i, (block, layer) in enumerate(zip(stack, _grad_layers(stack, stack._pack))):
+        lin, bn = block[0], block[2] if len(block) > 2 else None
+        h = _LinearBlock.apply(h, lin.weight, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias, layer, True, bn, stack, i)
+    return h.reshape(*lead, h.shape[-1])
+
+
+def linear(hip_linear, x, relu=False):
+    """``HipLinear.forward``'s contract -- x fp32 (..., K) -> (..., N), optionally with the fused ReLU -- differentiable in x, weight and bias"""
+    if not isinstance(hip_linear, HipLinear):
+        raise TypeError(f"linear: expected a components.mlp.HipLinear, got {type(hip_linear).__name__}")
+    _fp32_features(x, "linear")
+    if not _needs_grad(hip_linear, x):
+        with torch.no_grad():
+            return hip_linear(x, relu=relu)
+    lead = x.shape[:-1]
+    h = _rows(x.reshape(-1, x.shape[-1]))
+    wp, b, k = _grad_layers(hip_linear, hip_linear._pack)
+    h = _LinearBlock.apply(h, hip_linear.weight, hip_linear.bias, None, None, (wp, b, None, None, k), bool(relu), None, hip_linear, 0)
+    return h.reshape(*lead, h.shape[-1])
+
+
+def implicit_decode(decoder, features_grid, query_points):
+    """``ImplicitWNFDecoder.forward``'s contract -- features_grid (B, C, D, H, W), query_points (B, M, 3) in [0, 1] -> (B, M, out) -- as the unfused
+    chain ``grid_sample_points`` -> ``mlp(decoder.mlp, .)``, differentiable in the volume, the queries and the decoder's parameters.  The fused and
+    split-operand decoder kernels stay inference-only."""
+    from .networks.conv_implicit_wnf import ImplicitWNFDecoder
+    if not isinstance(decoder, ImplicitWNFDecoder):
+        raise TypeError(f"implicit_decode: expected a networks.conv_implicit_wnf.ImplicitWNFDecoder, got {type(decoder).__name__}")
+    return mlp(decoder.mlp, grid_sample_points(features_grid, query_points.float()))

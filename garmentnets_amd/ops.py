@@ -1508,3 +1508,68 @@ def linear_bwd_params(dy, x, K=None, with_bias=True):
     ws = _ws(nbytes, x.device)
     _lib.call("gn_linear_bwd_params", _p(dy), rows_view(dy)[1], _p(x), rows_view(x)[1], M, N, K, _p(ws), nbytes, _p(dw), K, _p(db), _stream())
     return dw, db
+
+
+# ------------------------------------------------------------------------------------------------ MLP gradients (csrc/linear_grad.hip)
+def _fp32_rows(t, name, rows=None, cols=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name}: expected fp32 rows ({'M' if rows is None else rows}, {'N' if cols is None else cols}), got {t.dtype} {tuple(t.shape)}")
+    return t if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def linear_act_bwd(dy, r=None, sc=None, out=None):
+    """the backward of a block's epilogue y = r * sc + sh, r = relu(.): rows dy [M][N], the saved r [M][N] (None: no ReLU) and the folded scale sc [N]
+    (None: 1) -> (g [M][N] = r > 0 ? dy * sc : 0, sums fp64 [3][N] = sum g, sum dy, sum dy * r)  (gn_linear_act_bwd).  With neither r nor sc, g IS dy
+    (nothing is written).  out: the buffer of g (may be dy)."""
+    dy = _fp32_rows(dy, "linear_act_bwd: dy")
+    M, N = dy.shape
+    if r is not None:
+        r = _fp32_rows(r, "linear_act_bwd: r", M, N)
+    if sc is not None:
+        _chk(sc, torch.float32, "linear_act_bwd: sc")
+        if sc.numel() != N:
+            raise ValueError(f"linear_act_bwd: sc has {sc.numel()} entries for {N} columns")
+    if r is None and sc is None:
+        g = None
+    else:
+        g = new_rows(M, N, dy.device) if out is None else _fp32_rows(out, "linear_act_bwd: out", M, N)
+        if out is not None and g is not out:
+            raise ValueError("linear_act_bwd: out must have unit column stride")
+    sums = torch.empty((3, N), dtype=torch.float64, device=dy.device)
+    nbytes = _lib.load().gn_linear_act_bwd_workspace_bytes(M, N)
+    ws = _ws(nbytes, dy.device)
+    _lib.call("gn_linear_act_bwd", _p(dy), rows_view(dy)[1], _p(r), 0 if r is None else rows_view(r)[1], _p(sc), M, N, _p(g),
+              0 if g is None else rows_view(g)[1], _p(ws), nbytes, _p(sums), _stream())
+    return (dy if g is None else g), sums
+
+
+def linear_bwd_weight(g, x, K=None, out=None):
+    """rows g [M][N], x [M][>= K] -> dW [N][K] = g^T x on the fp32 matrix cores (gn_linear_bwd_weight); out: rows [N][K] with any row stride"""
+    g = _fp32_rows(g, "linear_bwd_weight: g")
+    M, N = g.shape
+    x = _fp32_rows(x, "linear_bwd_weight: x", M)
+    K = x.shape[1] if K is None else int(K)
+    if not 1 <= K <= x.shape[1]:
+        raise ValueError(f"linear_bwd_weight: K={K} outside x {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    elif _fp32_rows(out, "linear_bwd_weight: out", N, K) is not out:
+        raise ValueError("linear_bwd_weight: out must have unit column stride")
+    nbytes = _lib.load().gn_linear_bwd_weight_workspace_bytes(M, N, K)
+    ws = _ws(nbytes, x.device)
+    _lib.call("gn_linear_bwd_weight", _p(g), rows_view(g)[1], _p(x), rows_view(x)[1], M, N, K, _p(ws), nbytes, _p(out), rows_view(out)[1], _stream())
+    return out
+
+
+def row_affine(r, sc, sh, out=None):
+    """y = fadd(fmul(r, sc[n]), sh[n]) over rows r [M][N]: gn_linear's BatchNorm epilogue as its own pass, the same bits (gn_row_affine)"""
+    r = _fp32_rows(r, "row_affine: r")
+    M, N = r.shape
+    for t in (sc, sh):
+        _chk(t, torch.float32, "row_affine: sc / sh")
+        if t.numel() != N:
+            raise ValueError(f"row_affine: sc / sh have {t.numel()} entries for {N} columns")
+    if out is None:
+        out = new_rows(M, N, r.device)
+    _lib.call("gn_row_affine", _p(r), rows_view(r)[1], _p(sc), _p(sh), M, N, _p(out), rows_view(out)[1], _stream())
+    return out

@@ -627,6 +627,34 @@ size_t gn_linear_bwd_params_workspace_bytes(int64_t M, int N, int K);
 int gn_linear_bwd_params(const float *dY, int ldy, const float *X, int ldx, int64_t M, int N, int K, void *ws, size_t ws_bytes, float *dW, int ldw, float *db,
                          void *stream);
 
+/* ---- MLP gradients (csrc/linear_grad.hip; DESIGN.md "MLP gradients").  One block of components/mlp.py is r = relu(x W^T + b), y = fadd(fmul(r, sc), sh)
+ * with (sc, sh) the folded eval-mode BatchNorm.  Row-major fp32 rows with their own strides.  No float atomics: every sum has a fixed order that depends on
+ * the shapes alone, identical calls give identical bits. ---- */
+
+#define GN_LINEAR_BWD_CHUNK_ROWS 512   /* R: gn_linear_bwd_weight's row chunk = the length of its fp32 fma chains */
+#define GN_LINEAR_ACT_CHUNK_ROWS 1024  /* gn_linear_act_bwd's row chunk */
+
+/* The epilogue's backward over dy [M][N] and the saved r [M][N]: g[m][n] = r > 0 ? fmul(dy, sc[n]) : 0 (a NaN in r takes no gradient; sc NULL: scale 1;
+ * r NULL: no mask; g may be dy, and may be NULL when r and sc both are -- g is dy then), and sums[3][N] fp64 = sum_m g (the bias gradient), sum_m dy (the
+ * shift gradient), sum_m dy * r (the scale gradient; products exact; zeros when r is NULL).  Rows in chunks of GN_LINEAR_ACT_CHUNK_ROWS: inside a chunk
+ * four interleaved row groups, each ascending, added in ascending order; the chunks in eight contiguous runs, each ascending, the run sums added in
+ * ascending order.  M == 0: zeros.  Workspace: ceil(M / GN_LINEAR_ACT_CHUNK_ROWS) * 3 * N doubles. */
+size_t gn_linear_act_bwd_workspace_bytes(int64_t M, int N);
+int gn_linear_act_bwd(const float *dy, int lddy, const float *r, int ldr, const float *sc, int64_t M, int N, float *g, int ldg, void *ws, size_t ws_bytes,
+                      double *sums, void *stream);
+
+/* dW[n][k] = sum_m g[m][n] * x[m][k] on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): per chunk of GN_LINEAR_BWD_CHUNK_ROWS rows one fp32 fma chain
+ * over the rows in ascending order, the chunk partials (ws[chunk][N][K], plain stores) added in fp64 -- eight contiguous runs of chunks, each ascending,
+ * the run sums in ascending order -- and rounded once.  Any M >= 0, N, K >= 1, ldg >= N, ldx >= K, lddw >= K; float4 loads when ldg, ldx are multiples
+ * of 4 and g, x 16-byte aligned.  Rows beyond M and columns beyond N / K are never read.  M == 0: exact zeros.
+ * Workspace: ceil(M / GN_LINEAR_BWD_CHUNK_ROWS) * N * K floats. */
+size_t gn_linear_bwd_weight_workspace_bytes(int64_t M, int N, int K);
+int gn_linear_bwd_weight(const float *g, int ldg, const float *x, int ldx, int64_t M, int N, int K, void *ws, size_t ws_bytes, float *dW, int lddw,
+                         void *stream);
+
+/* y[m][n] = fadd(fmul(r[m][n], sc[n]), sh[n]): gn_linear's BatchNorm epilogue as a pass of its own, the same two roundings (y may be r). */
+int gn_row_affine(const float *r, int ldr, const float *sc, const float *sh, int64_t M, int N, float *y, int ldy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
