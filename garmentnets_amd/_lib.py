@@ -113,8 +113,6 @@ PROTOTYPES = {
                               _vp, _vp],
     "gn_groupnorm_bwd_apply": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "gn_maxpool3d_2_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
-    "gn_linear_bwd_params_workspace_bytes": [_i64, _i32, _i32],
-    "gn_linear_bwd_params": [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _i32, _vp, _vp],
     "gn_linear_act_bwd_workspace_bytes": [_i64, _i32],
     "gn_linear_act_bwd": [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp],
     "gn_linear_bwd_weight_workspace_bytes": [_i64, _i32, _i32],
@@ -125,7 +123,7 @@ _RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes":
              "gn_nocs_bin_metrics_workspace_bytes": _sz, "gn_value_losses_workspace_bytes": _sz,
              "gn_grid_scatter_bwd_workspace_bytes": _sz, "gn_sa_gather_bwd_workspace_bytes": _sz, "gn_knn_interpolate_bwd_workspace_bytes": _sz,
              "gn_trilinear_sample_bwd_workspace_bytes": _sz, "gn_conv3d_bwd_weight_workspace_bytes": _sz, "gn_groupnorm_bwd_stats_workspace_bytes": _sz,
-             "gn_linear_bwd_params_workspace_bytes": _sz, "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz}
+             "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz}
 
 LINEAR_BWD_CHUNK_ROWS = 512                     # GN_LINEAR_BWD_CHUNK_ROWS
 LINEAR_ACT_CHUNK_ROWS = 1024                    # GN_LINEAR_ACT_CHUNK_ROWS

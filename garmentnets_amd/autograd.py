@@ -7,7 +7,7 @@ is a kernel of csrc/grad.hip.  A reference-side module that binds these function
 
 The UNet is not a torch graph (channel-last, channel-padded volumes, GroupNorm folded into the conv's operand load, concat and upsampling never
 materialised), so it gets its own backward: ``conv3d_gcr`` / ``max_pool3d_2`` / ``unet3d`` run the existing forward kernels and differentiate them with
-csrc/unet_grad.hip (DESIGN.md "UNet gradients").
+csrc/unet_grad.hip (DESIGN.md "UNet gradients"); its final 1x1x1 convolution is a linear block of the next paragraph.
 
 The dense layers of this package (components.mlp.MLPStack, HipLinear) hold torch parameters but evaluate through ``gn_linear``, which torch's autograd
 cannot see: ``mlp`` / ``linear`` run the same forward kernels block by block, keep each block's input and ReLU output, and differentiate them with
@@ -33,15 +33,6 @@ from .components.pointnet2 import Segments, _example_self_src
 
 __all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
            "conv3d_gcr", "max_pool3d_2", "unet3d", "mlp", "linear", "implicit_decode"]
-
-
-def _rows(t):
-    """fp32 rows the C ABI can read in place (unit column stride), else a contiguous copy"""
-    if t.dtype != torch.float32:
-        raise TypeError(f"expected torch.float32 features, got {t.dtype}")
-    if t.dim() != 2:
-        raise ValueError(f"expected (rows, channels), got shape {tuple(t.shape)}")
-    return t if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ index results (no gradient)
@@ -122,9 +113,9 @@ def point_conv_max(x, pos, centre_idx, nbr, local_nn, add_self_loops=True, self_
     if x is None:
         edges, slot_src, _ = ops.sa_gather(None, pos, centre_idx, nbr, self_loops=add_self_loops, self_src=self_src)
     else:
-        edges, slot_src = _SaGather.apply(_rows(x), pos, centre_idx, nbr, add_self_loops, self_src)
+        edges, slot_src = _SaGather.apply(ops.fp32_rows(x, "x"), pos, centre_idx, nbr, add_self_loops, self_src)
     h = local_nn(edges) if local_nn is not None else edges
-    return _SegmentMax.apply(_rows(h), slot_src, M, S)
+    return _SegmentMax.apply(ops.fp32_rows(h, "local_nn(edges)"), slot_src, M, S)
 
 
 # ------------------------------------------------------------------------------------------------ global_max_pool
@@ -145,7 +136,7 @@ class _GlobalMaxPool(torch.autograd.Function):
 def global_max_pool(x, batch):
     """torch_geometric.nn.global_max_pool(x, batch) -> (B, C)"""
     seg = Segments.of(batch)
-    return _GlobalMaxPool.apply(_rows(x), seg.ptr, seg.num)
+    return _GlobalMaxPool.apply(ops.fp32_rows(x, "x"), seg.ptr, seg.num)
 
 
 # ------------------------------------------------------------------------------------------------ knn_interpolate
@@ -169,7 +160,7 @@ def knn_interpolate(x, pos_x, pos_y, batch_x, batch_y, k=3):
     """torch_geometric.nn.knn_interpolate(x, pos_x, pos_y, batch_x, batch_y, k): gradient to the features x only -- the neighbour search and the
     weights sit under no_grad in torch_geometric too."""
     seg_x, seg_y = Segments.of(batch_x), Segments.of(batch_y)
-    return _KnnInterpolate.apply(_rows(x), pos_x.detach().contiguous(), seg_x.ptr, pos_y.detach().contiguous(), seg_y.ptr, int(k))
+    return _KnnInterpolate.apply(ops.fp32_rows(x, "x"), pos_x.detach().contiguous(), seg_x.ptr, pos_y.detach().contiguous(), seg_y.ptr, int(k))
 
 
 # ------------------------------------------------------------------------------------------------ torch_scatter.scatter
@@ -202,7 +193,7 @@ def scatter(src, index, dim=-1, dim_size=None, reduce="mean"):
         dim_size = int(index.max().item()) + 1 if index.numel() else 0
     if reduce == "mul" and torch.is_grad_enabled() and src.requires_grad:
         raise ValueError("scatter: reduce='mul' has no gradient here (nobody trains with it; it divides by zero at a zero factor)")
-    rows = _rows(src.t())
+    rows = ops.fp32_rows(src.t(), "src")
     return _GridScatter.apply(rows, index.to(torch.int32).contiguous(), int(dim_size), reduce).t()
 
 
@@ -357,34 +348,6 @@ def max_pool3d_2(x):
     return _MaxPool.apply(x, False)[0]
 
 
-class _FinalConv(torch.autograd.Function):
-    """the final 1x1x1 convolution: a row GEMM over the stored channels"""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, mod):
-        ctx.save_for_backward(x, weight)
-        ctx.mod = mod
-        return mod.run(x)
-
-    @staticmethod
-    def backward(ctx, grad_y):
-        x, weight = ctx.saved_tensors       # (weight: mod.weight at the forward's version, checked on unpacking)
-        mod, need = ctx.mod, ctx.needs_input_grad
-        n, ks = mod.out_channels, x.shape[-1]
-        dy = grad_y.reshape(-1, n).contiguous()
-        dx = dw = db = None
-        if need[0]:
-            wt = param_cache(mod, "_grad_packs").get((weight.device, weight._version, ks), "wt",
-                                                     lambda: U.pack_wb(mod.stored_weight().t().contiguous(), None)[0])
-            dx = ops.linear(dy, wt, K=n).reshape(x.shape)
-            if not dx.is_contiguous():
-                dx = dx.contiguous()
-        if need[1] or need[2]:
-            dws, db = ops.linear_bwd_params(dy, x.reshape(-1, ks), with_bias=mod.bias is not None)
-            dw = dws[:, :mod.in_channels].reshape(weight.shape)
-        return dx, dw if need[1] else None, db if need[2] else None, None
-
-
 def _unet_layers(model):
     return [sc for blk in list(model.encoders) + list(model.decoders) for sc in (blk.basic_module.SingleConv1, blk.basic_module.SingleConv2)]
 
@@ -400,7 +363,7 @@ def unet3d(model, x, arith=None):
     for sc in _unet_layers(model):
         _check_gcr(sc)
     arith = arith if arith is not None else model.arith
-    if not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in model.parameters()))):
+    if not _needs_grad(model, x):
         stats = getattr(x, "_gn_stats", None)
         v = U.stored_volume(x)
         if v.shape[-1] % 16 != 0:
@@ -428,24 +391,30 @@ def unet3d(model, x, arith=None):
         dc = dec.basic_module
         v, stats = _conv(dc.SingleConv1, skip, v, skip_stats, stats, arith)
         v, stats = _conv(dc.SingleConv2, v, None, stats, None, arith)
+    # the final 1x1x1 convolution: a linear block over the rows of stored channels (FinalConv1x1.run's launch on the same pack)
     fc = model.final_conv
-    return _FinalConv.apply(v, fc.weight, fc.bias, fc).permute(0, 4, 1, 2, 3)
+    wp, b, k = _grad_layers(fc, fc._pack)
+    y = _LinearBlock.apply(v.reshape(-1, v.shape[-1]), fc.weight, fc.bias, None, None, (wp, b, None, None, k), False, None, fc, 0)
+    return y.reshape(*v.shape[:-1], fc.out_channels).permute(0, 4, 1, 2, 3)
 
 
 # ------------------------------------------------------------------------------------------------ the MLP blocks
 class _LinearBlock(torch.autograd.Function):
-    """one block r = act(x W^T + b), y = r * sc + sh of an MLPStack (or a bare HipLinear).  layer = (wp, b, sc, sh, k): the forward's packs of the
-    parameters, built at their present versions.  weight / bias / gamma / beta are the module's own parameters: they are saved, so the backward
-    differentiates the parameters the forward used and an in-place update in between is an autograd version error.  bn: the BatchNorm module
+    """one block r = act(x W^T + b), y = r * sc + sh of an MLPStack, a bare HipLinear or the UNet's final 1x1x1 convolution.  layer = (wp, b, sc, sh,
+    k): the forward's packs of the parameters, built at their present versions; wp[:, :k] is the weight as the kernels read it (the final convolution's
+    over its STORED input channels, zero columns on the pads).  weight / bias / gamma / beta are the module's own parameters: they are saved, so the
+    backward differentiates the parameters the forward used and an in-place update in between is an autograd version error.  bn: the BatchNorm module
     (its running statistics are data, read at the forward) or None; owner: the module whose ParamCache keeps the transposed weight pack."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, layer, relu, bn, owner, idx):
         wp, b, sc, sh, k = layer
+        if x.shape[1] != k:
+            raise ValueError(f"{type(owner).__name__}: input of {x.shape[1]} channels, expected {k}")
         r = ops.linear(x, wp, b, None, None, relu=relu, K=k)          # the epilogue apart: r is what the mask and the scale gradient need
         y = r if sc is None else ops.row_affine(r, sc, sh)
         ctx.save_for_backward(x, r if relu else None, weight, bias, gamma, beta)
-        ctx.sc, ctx.owner, ctx.idx = sc, owner, idx
+        ctx.wp, ctx.k, ctx.sc, ctx.owner, ctx.idx = wp, k, sc, owner, idx
         if bn is not None:
             ctx.mean = bn.running_mean.detach().double()
             ctx.inv = 1.0 / torch.sqrt(bn.running_var.detach().double() + bn.eps)
@@ -455,16 +424,19 @@ class _LinearBlock(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, r, weight, bias, gamma, beta = ctx.saved_tensors
         need = ctx.needs_input_grad
-        n, k = weight.shape
-        g, sums = ops.linear_act_bwd(ops._grad_rows(grad_y, "grad_y", n), r, ctx.sc)
+        n, k = weight.shape[0], ctx.k                # k: the width the kernels read (the final convolution's stored input channels)
+        k_real = weight[0].numel()                    # the parameter's own input width: (n, k_real) or (n, k_real, 1, 1, 1)
+        g, sums = ops.linear_act_bwd(ops.fp32_rows(grad_y, "grad_y", cols=n), r, ctx.sc)
         dx = dw = db = dgamma = dbeta = None
         if need[0]:
-            # (the saved weight IS the module's at the forward's version -- unpacking it has checked that -- so the version-keyed cache holds its pack)
+            # (the saved weight IS the module's at the forward's version -- unpacking it has checked that -- so the version-keyed cache holds its pack,
+            #  and ctx.wp, the forward's pack of it, holds its values)
             gen = (weight.device,) + tuple(p._version for p in ctx.owner.parameters())
-            wt = param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(weight.t().contiguous(), None)[0])
+            wt = param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(ctx.wp[:, :k].t().contiguous(), None)[0])
             dx = ops.linear(g, wt, K=n)
         if need[1]:
-            dw = ops.linear_bwd_weight(g, x, K=k)
+            # (over the stored width; a channel-padded input's pad columns multiply exact zeros and reach no parameter)
+            dw = ops.linear_bwd_weight(g, x, K=k)[:, :k_real].reshape(weight.shape)
         if bias is not None and need[2]:
             db = sums[0].float()
         if gamma is not None and need[3]:
@@ -509,7 +481,7 @@ def mlp(stack, x):
         with torch.no_grad():
             return stack(x)
     lead = x.shape[:-1]
-    h = _rows(x.reshape(-1, x.shape[-1]))
+    h = ops.fp32_rows(x.reshape(-1, x.shape[-1]), "x")
     for i, (block, layer) in enumerate(zip(stack, _grad_layers(stack, stack._pack))):
         lin, bn = block[0], block[2] if len(block) > 2 else None
         h = _LinearBlock.apply(h, lin.weight, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias, layer, True, bn, stack, i)
@@ -525,7 +497,7 @@ def linear(hip_linear, x, relu=False):
         with torch.no_grad():
             return hip_linear(x, relu=relu)
     lead = x.shape[:-1]
-    h = _rows(x.reshape(-1, x.shape[-1]))
+    h = ops.fp32_rows(x.reshape(-1, x.shape[-1]), "x")
     wp, b, k = _grad_layers(hip_linear, hip_linear._pack)
     h = _LinearBlock.apply(h, hip_linear.weight, hip_linear.bias, None, None, (wp, b, None, None, k), bool(relu), None, hip_linear, 0)
     return h.reshape(*lead, h.shape[-1])

@@ -1,11 +1,11 @@
-// unet_grad.hip -- backward kernels of the 3-D UNet's 'gcr' layers (GroupNorm -> Conv3d 3x3x3 -> ReLU), the 2x2x2 max-pool and the final 1x1x1
-// convolution, on the stored layout of the forward: channel-last [B][D][H][W][C] fp32, channel-padded widths (DESIGN.md "UNet gradients").
+// unet_grad.hip -- backward kernels of the 3-D UNet's 'gcr' layers (GroupNorm -> Conv3d 3x3x3 -> ReLU) and the 2x2x2 max-pool, on the stored layout
+// of the forward: channel-last [B][D][H][W][C] fp32, channel-padded widths (DESIGN.md "UNet gradients").  The final 1x1x1 convolution is a row GEMM:
+// its backward is linear_grad.hip's.
 //   gn_conv3d_bwd_weight     dW = sum over voxels of (GroupNorm-applied, virtually concatenated / upsampled input) x (ReLU-masked dy): implicit GEMM with
 //                            K = B*D*H*W on v_mfma_f32_32x32x2_f32, split over K into partials, folded in a fixed order
 //   gn_relu_mask             g = y > 0 ? dy : 0   (the data gradient then runs the FORWARD conv kernel on a flipped / transposed weight pack)
 //   gn_groupnorm_bwd_stats / _coef / _apply    nn.GroupNorm's backward over the virtual concat, the x2 nearest upsampling's backward folded in
 //   gn_maxpool3d_2_bwd       gradient to the winner of each window (ATen's scan), no index tensor
-//   gn_linear_bwd_params     dW = dY^T X, db = sum dY of a row GEMM
 // Rule of the file (as grad.hip, losses.hip): NO float atomics; every sum has a fixed order, so identical calls give identical bits.
 #include "common.h"
 
@@ -486,91 +486,5 @@ extern "C" int gn_maxpool3d_2_bwd(const float *grad_out, const float *in, int B,
     const int64_t n4 = (int64_t)B * (D / 2) * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool3d_2_bwd_kernel, dim3((unsigned)gn_cdiv(n4, 256)), dim3(256), 0, gn_stream(stream), grad_out, in, D, H, W, C, n4, grad_in);
     GN_LAUNCH_CHECK("gn_maxpool3d_2_bwd");
-    return GN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ row GEMM: parameter gradients
-// Y = X W^T + b over M rows (the final 1x1x1 convolution): dW[n][k] = sum_rows dY[row][n] X[row][k], db[n] = sum_rows dY[row][n] (X's column K is a
-// virtual 1).  stage 1: grid (chunks of 1024 rows, blocks of 4096 outputs); thread t of output block j owns outputs 4096 j + t, + 256, ... (16 of
-// them), rows in ascending order, fp32 fma; stage 2 adds the chunks in ascending order in fp64.  N <= 512 and K <= 1023 (the LDS row tiles).
-#define LB_ROWS 1024
-#define LB_SUB 8
-#define LB_MAXK 1023
-#define LB_MAXN 512
-#define LB_MAXOUT 4096
-__global__ __launch_bounds__(256) void linear_bwd_params_kernel(const float *__restrict__ dY, int ldy, const float *__restrict__ X, int ldx, int64_t M, int N,
-                                                                int K, float *__restrict__ part) {
-    __shared__ float xs[LB_SUB][LB_MAXK + 1], ys[LB_SUB][LB_MAXN];
-    const int tid = threadIdx.x, K1 = K + 1, total = N * K1, ob = blockIdx.y * LB_MAXOUT;
-    const int64_t r0 = (int64_t)blockIdx.x * LB_ROWS;
-    int64_t r1 = r0 + LB_ROWS;
-    if (r1 > M) r1 = M;
-    float acc[16];
-    int on[16], ok[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int o = ob + tid + 256 * j;
-        acc[j] = 0.f;
-        on[j] = o < total ? o / K1 : 0;
-        ok[j] = o < total ? o % K1 : 0;
-    }
-    for (int64_t rb = r0; rb < r1; rb += LB_SUB) {
-        const int rows = (int)(r1 - rb < LB_SUB ? r1 - rb : LB_SUB);
-        __syncthreads();
-        for (int i = tid; i < LB_SUB * K1; i += 256) {
-            const int rr = i / K1, kk = i % K1;
-            xs[rr][kk] = rr < rows ? (kk < K ? X[(rb + rr) * ldx + kk] : 1.f) : 0.f;
-        }
-        for (int i = tid; i < LB_SUB * N; i += 256) {
-            const int rr = i / N, nn = i % N;
-            ys[rr][nn] = rr < rows ? dY[(rb + rr) * ldy + nn] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (ob + tid + 256 * j < total) {
-#pragma unroll
-                for (int rr = 0; rr < LB_SUB; ++rr) acc[j] = __fmaf_rn(ys[rr][on[j]], xs[rr][ok[j]], acc[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (ob + tid + 256 * j < total) part[(int64_t)blockIdx.x * total + ob + tid + 256 * j] = acc[j];
-}
-
-__global__ __launch_bounds__(256) void linear_bwd_params_fold_kernel(const float *__restrict__ part, int chunks, int N, int K, float *__restrict__ dW, int ldw,
-                                                                     float *__restrict__ db) {
-    const int o = blockIdx.x * 256 + threadIdx.x, K1 = K + 1, total = N * K1;
-    if (o >= total) return;
-    double s = 0.0;
-    for (int c = 0; c < chunks; ++c) s += (double)part[(int64_t)c * total + o];
-    const int n = o / K1, k = o % K1;
-    if (k < K) dW[(int64_t)n * ldw + k] = (float)s;
-    else if (db) db[n] = (float)s;
-}
-
-extern "C" size_t gn_linear_bwd_params_workspace_bytes(int64_t M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    return (size_t)gn_cdiv(M, LB_ROWS) * (size_t)N * (K + 1) * sizeof(float);
-}
-
-extern "C" int gn_linear_bwd_params(const float *dY, int ldy, const float *X, int ldx, int64_t M, int N, int K, void *ws, size_t ws_bytes, float *dW, int ldw,
-                                    float *db, void *stream) {
-    GN_REQUIRE(M >= 0 && N > 0 && K > 0 && ldy >= N && ldx >= K && ldw >= K, "gn_linear_bwd_params: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-    GN_REQUIRE(N <= LB_MAXN && K <= LB_MAXK, "gn_linear_bwd_params: at most %d outputs of at most %d inputs (N=%d K=%d)", LB_MAXN, LB_MAXK, N, K);
-    const size_t need = gn_linear_bwd_params_workspace_bytes(M, N, K);
-    GN_REQUIRE(ws_bytes >= need, "gn_linear_bwd_params: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-    GN_REQUIRE(dW != nullptr, "gn_linear_bwd_params: null pointer");
-    hipStream_t st = gn_stream(stream);
-    const int chunks = (int)gn_cdiv(M, LB_ROWS);
-    if (chunks > 0) {
-        GN_REQUIRE(dY && X && ws, "gn_linear_bwd_params: null pointer");
-        hipLaunchKernelGGL(linear_bwd_params_kernel, dim3((unsigned)chunks, (unsigned)gn_cdiv((int64_t)N * (K + 1), LB_MAXOUT)), dim3(256), 0, st, dY, ldy, X, ldx, M, N, K, (float *)ws);
-        GN_LAUNCH_CHECK("gn_linear_bwd_params");
-    }
-    hipLaunchKernelGGL(linear_bwd_params_fold_kernel, dim3((unsigned)gn_cdiv((int64_t)N * (K + 1), 256)), dim3(256), 0, st, (const float *)ws, chunks, N, K, dW,
-                       ldw, db);
-    GN_LAUNCH_CHECK("gn_linear_bwd_params");
     return GN_OK;
 }

@@ -1202,12 +1202,13 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
-def _grad_rows(t, name, cols=None):
-    """an incoming gradient as fp32 rows (autograd may hand over an expanded or otherwise strided tensor)"""
+def fp32_rows(t, name, rows=None, cols=None):
+    """t as fp32 2-D rows the C ABI reads in place (unit column stride, row stride >= columns), else a contiguous copy: autograd may hand over an
+    expanded or otherwise strided tensor.  rows / cols: the counts t is held to.  TypeError for the dtype, ValueError for the shape."""
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
-    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
-        raise ValueError(f"{name}: expected rows of {cols} channels, got shape {tuple(t.shape)}")
+    if t.dim() != 2 or (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name}: expected rows ({'M' if rows is None else rows}, {'N' if cols is None else cols}), got shape {tuple(t.shape)}")
     return t if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
 
 
@@ -1246,7 +1247,7 @@ def grid_scatter_bwd(grad_vol, flat_idx, N, reduce, vol=None, src=None, c_real=N
 def segment_max_bwd(grad_out, out, h, slot_src, M, S):
     """gradient of segment_max with respect to h [M * S][C]"""
     C = h.shape[1]
-    grad_out = _grad_rows(grad_out, "grad_out", C)
+    grad_out = fp32_rows(grad_out, "grad_out", cols=C)
     if tuple(out.shape) != (M, C) or h.shape[0] != M * S or grad_out.shape[0] != M or slot_src.numel() != M * S:
         raise ValueError("segment_max_bwd: shapes do not match (M, S, C)")
     _chk(slot_src, _i32, "slot_src")
@@ -1258,7 +1259,7 @@ def segment_max_bwd(grad_out, out, h, slot_src, M, S):
 
 def global_max_pool_bwd(grad_out, out, h, ptr, B):
     C = h.shape[1]
-    grad_out = _grad_rows(grad_out, "grad_out", C)
+    grad_out = fp32_rows(grad_out, "grad_out", cols=C)
     if tuple(out.shape) != (B, C) or grad_out.shape[0] != B or ptr.numel() != B + 1:
         raise ValueError("global_max_pool_bwd: shapes do not match (B, C)")
     _chk(ptr, _i32, "ptr")
@@ -1270,7 +1271,7 @@ def global_max_pool_bwd(grad_out, out, h, ptr, B):
 
 def sa_gather_bwd(grad_edge, slot_src, C, n_points):
     """gradient of sa_gather with respect to x [n_points][C]: the feature part (columns :C) of the edge rows, summed per source in ascending row"""
-    grad_edge = _grad_rows(grad_edge, "grad_edge")
+    grad_edge = fp32_rows(grad_edge, "grad_edge")
     _chk(slot_src, _i32, "slot_src")
     rows = slot_src.numel()
     if grad_edge.shape[0] != rows or grad_edge.shape[1] < C or C < 1:
@@ -1300,7 +1301,7 @@ def knn_neighbours(ps, ptr_s, pq, ptr_q, k):
 
 def knn_interpolate_bwd(grad_y, nbr, d2, n_sources):
     """gradient of knn_interpolate with respect to the source features [n_sources][C] (nbr, d2: knn_neighbours)"""
-    grad_y = _grad_rows(grad_y, "grad_y")
+    grad_y = fp32_rows(grad_y, "grad_y")
     _chk(nbr, _i32, "nbr")
     _chk(d2, torch.float32, "d2")
     Nq, k = nbr.shape
@@ -1496,35 +1497,15 @@ def maxpool3d_2_bwd(grad_out, x):
     return g
 
 
-def linear_bwd_params(dy, x, K=None, with_bias=True):
-    """rows dy [M][N], x [M][>= K] -> (dW [N][K], db [N] or None) of y = x W^T + b (gn_linear_bwd_params)"""
-    M, N = dy.shape
-    K = x.shape[1] if K is None else int(K)
-    if x.shape[0] != M or x.shape[1] < K or dy.dtype != torch.float32 or x.dtype != torch.float32:
-        raise ValueError(f"linear_bwd_params: dy {tuple(dy.shape)} and x {tuple(x.shape)} are not fp32 rows of one GEMM with K={K}")
-    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    db = torch.empty(N, dtype=torch.float32, device=x.device) if with_bias else None
-    nbytes = _lib.load().gn_linear_bwd_params_workspace_bytes(M, N, K)
-    ws = _ws(nbytes, x.device)
-    _lib.call("gn_linear_bwd_params", _p(dy), rows_view(dy)[1], _p(x), rows_view(x)[1], M, N, K, _p(ws), nbytes, _p(dw), K, _p(db), _stream())
-    return dw, db
-
-
 # ------------------------------------------------------------------------------------------------ MLP gradients (csrc/linear_grad.hip)
-def _fp32_rows(t, name, rows=None, cols=None):
-    if t.dtype != torch.float32 or t.dim() != 2 or (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
-        raise ValueError(f"{name}: expected fp32 rows ({'M' if rows is None else rows}, {'N' if cols is None else cols}), got {t.dtype} {tuple(t.shape)}")
-    return t if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
-
-
 def linear_act_bwd(dy, r=None, sc=None, out=None):
     """the backward of a block's epilogue y = r * sc + sh, r = relu(.): rows dy [M][N], the saved r [M][N] (None: no ReLU) and the folded scale sc [N]
     (None: 1) -> (g [M][N] = r > 0 ? dy * sc : 0, sums fp64 [3][N] = sum g, sum dy, sum dy * r)  (gn_linear_act_bwd).  With neither r nor sc, g IS dy
     (nothing is written).  out: the buffer of g (may be dy)."""
-    dy = _fp32_rows(dy, "linear_act_bwd: dy")
+    dy = fp32_rows(dy, "linear_act_bwd: dy")
     M, N = dy.shape
     if r is not None:
-        r = _fp32_rows(r, "linear_act_bwd: r", M, N)
+        r = fp32_rows(r, "linear_act_bwd: r", M, N)
     if sc is not None:
         _chk(sc, torch.float32, "linear_act_bwd: sc")
         if sc.numel() != N:
@@ -1532,7 +1513,7 @@ def linear_act_bwd(dy, r=None, sc=None, out=None):
     if r is None and sc is None:
         g = None
     else:
-        g = new_rows(M, N, dy.device) if out is None else _fp32_rows(out, "linear_act_bwd: out", M, N)
+        g = new_rows(M, N, dy.device) if out is None else fp32_rows(out, "linear_act_bwd: out", M, N)
         if out is not None and g is not out:
             raise ValueError("linear_act_bwd: out must have unit column stride")
     sums = torch.empty((3, N), dtype=torch.float64, device=dy.device)
@@ -1545,15 +1526,15 @@ def linear_act_bwd(dy, r=None, sc=None, out=None):
 
 def linear_bwd_weight(g, x, K=None, out=None):
     """rows g [M][N], x [M][>= K] -> dW [N][K] = g^T x on the fp32 matrix cores (gn_linear_bwd_weight); out: rows [N][K] with any row stride"""
-    g = _fp32_rows(g, "linear_bwd_weight: g")
+    g = fp32_rows(g, "linear_bwd_weight: g")
     M, N = g.shape
-    x = _fp32_rows(x, "linear_bwd_weight: x", M)
+    x = fp32_rows(x, "linear_bwd_weight: x", M)
     K = x.shape[1] if K is None else int(K)
     if not 1 <= K <= x.shape[1]:
         raise ValueError(f"linear_bwd_weight: K={K} outside x {tuple(x.shape)}")
     if out is None:
         out = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    elif _fp32_rows(out, "linear_bwd_weight: out", N, K) is not out:
+    elif fp32_rows(out, "linear_bwd_weight: out", N, K) is not out:
         raise ValueError("linear_bwd_weight: out must have unit column stride")
     nbytes = _lib.load().gn_linear_bwd_weight_workspace_bytes(M, N, K)
     ws = _ws(nbytes, x.device)
@@ -1563,7 +1544,7 @@ def linear_bwd_weight(g, x, K=None, out=None):
 
 def row_affine(r, sc, sh, out=None):
     """y = fadd(fmul(r, sc[n]), sh[n]) over rows r [M][N]: gn_linear's BatchNorm epilogue as its own pass, the same bits (gn_row_affine)"""
-    r = _fp32_rows(r, "row_affine: r")
+    r = fp32_rows(r, "row_affine: r")
     M, N = r.shape
     for t in (sc, sh):
         _chk(t, torch.float32, "row_affine: sc / sh")

@@ -621,15 +621,9 @@ int gn_groupnorm_bwd_apply(const float *dxn, int ldg, int goff, const float *x, 
  * first of equal maxima, a NaN beats every number (and a later NaN an earlier one).  grad_in: every voxel written, the losers 0. */
 int gn_maxpool3d_2_bwd(const float *grad_out, const float *in, int B, int D, int H, int W, int C, float *grad_in, void *stream);
 
-/* Parameter gradients of a row GEMM Y = X W^T + b (the final 1x1x1 convolution): dW[n][k] = sum_rows dY[row][n] * X[row][k], db[n] = sum_rows dY[row][n]
- * (db may be NULL).  N <= 512, K <= 1023 (LDS row tiles; any N * (K + 1): blocks of 4096 outputs).  Workspace: ceil(M / 1024) * N * (K + 1) floats. */
-size_t gn_linear_bwd_params_workspace_bytes(int64_t M, int N, int K);
-int gn_linear_bwd_params(const float *dY, int ldy, const float *X, int ldx, int64_t M, int N, int K, void *ws, size_t ws_bytes, float *dW, int ldw, float *db,
-                         void *stream);
-
 /* ---- MLP gradients (csrc/linear_grad.hip; DESIGN.md "MLP gradients").  One block of components/mlp.py is r = relu(x W^T + b), y = fadd(fmul(r, sc), sh)
- * with (sc, sh) the folded eval-mode BatchNorm.  Row-major fp32 rows with their own strides.  No float atomics: every sum has a fixed order that depends on
- * the shapes alone, identical calls give identical bits. ---- */
+ * with (sc, sh) the folded eval-mode BatchNorm; the UNet's final 1x1x1 convolution is such a block without ReLU and BatchNorm.  Row-major fp32 rows
+ * with their own strides.  No float atomics: every sum has a fixed order that depends on the shapes alone, identical calls give identical bits. ---- */
 
 #define GN_LINEAR_BWD_CHUNK_ROWS 512   /* R: gn_linear_bwd_weight's row chunk = the length of its fp32 fma chains */
 #define GN_LINEAR_ACT_CHUNK_ROWS 1024  /* gn_linear_act_bwd's row chunk */

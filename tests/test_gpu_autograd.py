@@ -5,11 +5,10 @@ one-hot matrices; F.grid_sample itself for the sampler).  Every restatement's FO
 restatement cannot pass quietly.  Index inputs (fps / ball-query / kNN results, cells) are computed once by the HIP ops and shared by both sides.
 
 Selections (max / min) must match bit for bit, the lowest index winning a tie.  Weighted gradients must stay within
-4 x (the max error of torch's own fp32 autograd of the same restatement against the fp64 one) + one fp32 ulp of the largest gradient magnitude:
-the bound is computed at test time from the fp32-torch run, not from a constant.  The fp32-torch run is on the CPU for the single operators; for the
+4 x (the max error of torch's own fp32 autograd of the same restatement against the fp64 one) + one fp32 ulp of the largest gradient magnitude
+(tests/grad_reference.py::_check): the bound is computed at test time from the fp32-torch run, not from a constant.  The fp32-torch run is on the CPU for the single operators; for the
 PointNet++ composition it is on the GPU, where that network's dense layers run (the reason and the figures are written at that test).
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -18,32 +17,9 @@ pytestmark = pytest.mark.gpu
 
 from garmentnets_amd import autograd as A, ops  # noqa: E402
 from garmentnets_amd.components.pointnet2 import Segments  # noqa: E402
+from grad_reference import _check, _first_max, _gen, r_sa_gather, r_sample, r_segment_max  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _check_weighted(name, ref64, t32, ours):
-    """the rule of the module docstring; prints the figures before it asserts"""
-    ref64, t32, ours = ref64.double().cpu(), t32.double().cpu(), ours.double().cpu()
-    assert ref64.shape == ours.shape, (name, ref64.shape, ours.shape)
-    if ref64.numel() == 0:
-        return
-    e32 = float((t32 - ref64).abs().max())
-    eo = float((ours - ref64).abs().max())
-    ulp = float(np.spacing(np.float32(ref64.abs().max())))
-    print(f"[grad-error] {name}: torch-fp32 {e32:.3e}  hip {eo:.3e}  ulp(max |g|) {ulp:.3e}  bound {4 * e32 + ulp:.3e}")
-    assert eo <= 4 * e32 + ulp, (name, eo, e32, ulp)
-
-
-def _first_max(vals, mask, dim):
-    """one-hot (same shape) of the FIRST maximum of vals along dim among mask (all False where mask is empty): written out, no reliance on argmax"""
-    neg = torch.where(mask, vals, torch.full_like(vals, -float("inf")))
-    eq = (neg == neg.max(dim=dim, keepdim=True).values) & mask
-    return eq & (eq.cumsum(dim) == 1)
 
 
 # ------------------------------------------------------------------------------------------------ restatements (plain torch, any dtype, CPU)
@@ -60,12 +36,6 @@ def r_scatter(src, cell, cells, reduce):
     return tot
 
 
-def r_segment_max(h, slot_src, M, S):
-    hv = h.reshape(M, S, -1)
-    sel = _first_max(hv, (slot_src.reshape(M, S) >= 0)[:, :, None].expand_as(hv), 1)
-    return (hv * sel.to(h.dtype)).sum(1)
-
-
 def r_global_max(h, sizes):
     out, o = [], 0
     for n in sizes:
@@ -73,17 +43,6 @@ def r_global_max(h, sizes):
         out.append((hv * _first_max(hv, torch.ones_like(hv, dtype=torch.bool), 0).to(h.dtype)).sum(0) if n else h.new_zeros(h.shape[1]))
         o += n
     return torch.stack(out)
-
-
-def r_sa_gather(x, pos, centre_idx, slot_src, S):
-    """edge rows [x_j, pos_j - pos_i]; an empty slot is a zero row.  x through a one-hot matrix (differentiable), positions are data"""
-    rows, n = slot_src.numel(), pos.shape[0]
-    valid = slot_src >= 0
-    j = slot_src.clamp(min=0).long()
-    onehot = ((j[:, None] == torch.arange(n, device=pos.device)[None, :]) & valid[:, None]).to(pos.dtype)
-    ci = centre_idx.long()[torch.arange(rows, device=pos.device) // S]
-    rel = (pos[j] - pos[ci]) * valid[:, None].to(pos.dtype)
-    return torch.cat((onehot @ x, rel), 1) if x is not None else rel
 
 
 def r_knn(x, nbr, d2, n_sources):
@@ -94,13 +53,6 @@ def r_knn(x, nbr, d2, n_sources):
     mat = torch.zeros((nbr.shape[0], n_sources), dtype=x.dtype, device=x.device)
     mat.scatter_add_(1, nbr.clamp(min=0).long(), coef)
     return mat @ x
-
-
-def r_sample(volume, query):
-    """volume (N, C, D, H, W), query (N, M, 3) in [0, 1] -> (N, M, C): the reference's call of F.grid_sample"""
-    n, m = query.shape[:2]
-    s = F.grid_sample(volume, (2.0 * query - 1.0).view(n, m, 1, 1, 3), mode="bilinear", padding_mode="border", align_corners=True)
-    return s.view(n, volume.shape[1], m).permute(0, 2, 1)
 
 
 def _grads(fn, inputs, gout, dtype):
@@ -199,7 +151,7 @@ def test_grid_scatter_weighted_gradient(reduce):
     _, (g32,) = _grads(fn, [src], gout, torch.float32)
     out, (g,) = _hip_grads(lambda s: A.scatter(s.t(), cell.to(DEV).long(), -1, cells, reduce).t(), [src], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-6)
-    _check_weighted(f"grid_scatter[{reduce}]", g64, g32, g)
+    _check(f"grid_scatter[{reduce}]", g64, g32, g)
 
 
 def _sa_case(seed, sizes=(300, 212), ratio=0.25, r=0.25, K=16):
@@ -236,7 +188,7 @@ def test_sa_gather_gradient(scope):
     _, (g32,) = _grads(fn, [x], gout, torch.float32)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=0, atol=1e-6)
     assert torch.equal(out[:, :C].cpu(), fwd64[:, :C].float())
-    _check_weighted(f"sa_gather[{scope}]", g64, g32, g)
+    _check(f"sa_gather[{scope}]", g64, g32, g)
     # the same bits again: the sum per source point is ordered
     _, (g2,) = _hip_grads(hip, [x], gout)
     assert torch.equal(g, g2)
@@ -261,7 +213,7 @@ def test_knn_interpolate_gradient(k):
     hip = lambda t: A.knn_interpolate(t, ps.to(DEV), pq.to(DEV), sseg, qseg, k)     # noqa: E731
     out, (gx,) = _hip_grads(hip, [x], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
-    _check_weighted(f"knn_interpolate[k={k}]", g64, g32, gx)
+    _check(f"knn_interpolate[k={k}]", g64, g32, gx)
     _, (gx2,) = _hip_grads(hip, [x], gout)
     assert torch.equal(gx, gx2)
 
@@ -286,8 +238,8 @@ def test_trilinear_sample_gradient_both_outputs():
     _, (gv32, gq32) = _grads(r_sample, [vol, q], gout, torch.float32)
     out, (gv, gq) = _hip_grads(A.grid_sample_points, [vol, q], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
-    _check_weighted("trilinear_sample grad_vol", gv64, gv32, gv)
-    _check_weighted("trilinear_sample grad_query", gq64, gq32, gq)
+    _check("trilinear_sample grad_vol", gv64, gv32, gv)
+    _check("trilinear_sample grad_query", gq64, gq32, gq)
     # a coordinate clamped at the border gets gradient 0 (F.grid_sample's rule), on that axis only
     outside = ((q <= 0) | (q >= 1)).to(DEV)
     assert bool(outside.any()) and float(gq[outside].abs().max()) == 0.0
@@ -304,10 +256,10 @@ def test_trilinear_sample_gradient_only_what_is_asked_for():
     _, (gv32, gq32) = _grads(r_sample, [vol, q], gout, torch.float32)
     vd, qd = vol.to(DEV).requires_grad_(True), q.to(DEV)
     (gv,) = torch.autograd.grad(A.grid_sample_points(vd, qd), [vd], gout.to(DEV))
-    _check_weighted("trilinear_sample grad_vol only (C=128)", gv64, gv32, gv)
+    _check("trilinear_sample grad_vol only (C=128)", gv64, gv32, gv)
     vd, qd = vol.to(DEV), q.to(DEV).requires_grad_(True)
     (gq,) = torch.autograd.grad(A.grid_sample_points(vd, qd), [qd], gout.to(DEV))
-    _check_weighted("trilinear_sample grad_query only (C=128)", gq64, gq32, gq)
+    _check("trilinear_sample grad_query only (C=128)", gq64, gq32, gq)
 
 
 # ------------------------------------------------------------------------------------------------ 4. edge cases
@@ -327,7 +279,7 @@ def test_grid_scatter_bwd_channel_padded_rows_and_repeats():
             assert torch.equal(a[:, :c_real].cpu(), g64[:, :c_real].float()), reduce
         else:
             _, (g32,) = _grads(lambda s: r_scatter(s, cell.long(), cells, reduce), [src], gout, torch.float32)
-            _check_weighted(f"grid_scatter padded[{reduce}]", g64[:, :c_real], g32[:, :c_real], a[:, :c_real])
+            _check(f"grid_scatter padded[{reduce}]", g64[:, :c_real], g32[:, :c_real], a[:, :c_real])
 
 
 def test_empty_inputs_give_empty_or_zero_gradients():
@@ -504,7 +456,7 @@ def test_pointnet2_composition_parameter_gradients():
     for name, a, b, d, c in zip(names, g64, g32, g32d, gh):
         print(f"[grad-error] pointnet2 {name}: torch-fp32 on the CPU (for the record) {float((b.double() - a).abs().max()):.3e}")
         try:
-            _check_weighted(f"pointnet2 {name}", a, d, c)
+            _check(f"pointnet2 {name}", a, d, c)
         except AssertionError as e:
             failed.append(str(e.args[0])[:200])
     assert not failed, failed
@@ -534,6 +486,6 @@ def test_second_stage_front_gradient():
     l32, (g32,) = _grads(restated, [feat], one, torch.float32)
     lh, (gh,) = _hip_grads(hip, [feat], one)
     assert abs(float(lh) - float(l64)) <= 1e-5 * abs(float(l64))
-    _check_weighted("second stage front", g64, g32, gh)
+    _check("second stage front", g64, g32, gh)
     _, (gh2,) = _hip_grads(hip, [feat], one)
     assert torch.equal(gh, gh2)

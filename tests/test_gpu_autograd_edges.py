@@ -1,7 +1,7 @@
 """GPU (-m gpu): the point and grid gradient kernels (csrc/grad.hip) at the tails, strides, ties, orders and geometries where they could be wrong
 while tests/test_gpu_autograd.py stays green.  Same method and same rule as that file: the yardstick is torch autograd in fp64 on the CPU over a
 plain-torch restatement (here the SPARSE ones of tests/test_autograd_host.py, proven equal to the dense ones there); selections are bit-exact;
-weighted gradients stay within 4 x (torch-fp32 against fp64, measured in the same test) + 1 fp32 ulp of the largest gradient (_check_weighted,
+weighted gradients stay within 4 x (torch-fp32 against fp64, measured in the same test) + 1 fp32 ulp of the largest gradient (tests/grad_reference.py::_check,
 which prints the `[grad-error]` line before it asserts).  No tolerance here is a constant.  The production shapes are in
 tests/test_gpu_autograd_fullsize.py.
 
@@ -57,7 +57,8 @@ pytestmark = pytest.mark.gpu
 from garmentnets_amd import autograd as A, ops  # noqa: E402
 from garmentnets_amd.components.pointnet2 import Segments  # noqa: E402
 from test_autograd_host import s_global_max, s_knn, s_sa_gather, s_scatter, s_segment_max  # noqa: E402
-from test_gpu_autograd import DEV, _check_weighted, _gen, _grads, _hip_grads, r_sample  # noqa: E402
+from grad_reference import _check, _gen, r_sample  # noqa: E402
+from test_gpu_autograd import DEV, _grads, _hip_grads  # noqa: E402
 from test_gpu_pointnet2_any_input import _sqd  # noqa: E402
 
 CHANNELS = [1, 63, 64, 65, 127, 129, 256, 257]
@@ -264,7 +265,7 @@ def test_grid_scatter_bwd_tails_and_strides(C, reduce, layout):
             assert torch.equal(g.cpu(), g64.float()), (C, N)
         else:
             _, (g32,) = _grads(fn, [src], gout, torch.float32)
-            _check_weighted(f"grid_scatter_bwd[{reduce}, C={C}, N={N}]", g64, g32, g)
+            _check(f"grid_scatter_bwd[{reduce}, C={C}, N={N}]", g64, g32, g)
         assert _no_nan(g)
         if layout != "contiguous":
             vol2, g2 = _scatter_call(src, cell, gout, cells, reduce, "contiguous")
@@ -291,7 +292,7 @@ def test_grid_scatter_bwd_padded_channels(C, c_real, reduce):
         assert torch.equal(g[:, :c_real].cpu(), g64.float())
     else:
         _, (g32,) = _grads(fn, [src[:, :c_real].clone()], gout[:, :c_real].clone(), torch.float32)
-        _check_weighted(f"grid_scatter_bwd[{reduce}, C={C}, c_real={c_real}]", g64, g32, g[:, :c_real])
+        _check(f"grid_scatter_bwd[{reduce}, C={C}, c_real={c_real}]", g64, g32, g[:, :c_real])
 
 
 def _slot_table(rows, n_points, seed):
@@ -316,7 +317,7 @@ def test_sa_gather_bwd_tails_and_strides(C):
         gout = torch.randn(rows, C + 3, generator=_gen(401 + C))
         g64, g32 = _sa_ref(slot, C, n_points, gout, torch.float64), _sa_ref(slot, C, n_points, gout, torch.float32)
         g = ops.sa_gather_bwd(_operand(gout, "contiguous", 1), slot.to(DEV), C, n_points)
-        _check_weighted(f"sa_gather_bwd[C={C}, n={n_points}]", g64, g32, g)
+        _check(f"sa_gather_bwd[C={C}, n={n_points}]", g64, g32, g)
         g2 = ops.sa_gather_bwd(_operand(gout, "wide", 1), slot.to(DEV), C, n_points)
         assert _bits(g, g2) and _no_nan(g, g2), (C, n_points)
 
@@ -345,7 +346,7 @@ def test_knn_interpolate_bwd_tails_and_strides(C):
         gout = torch.randn(Nq, C, generator=_gen(501 + C))
         g64, g32 = _knn_ref(nbr, d2, Ns, gout, torch.float64), _knn_ref(nbr, d2, Ns, gout, torch.float32)
         g = ops.knn_interpolate_bwd(_operand(gout, "contiguous", 1, tall=k), nbr.to(DEV), d2.to(DEV), Ns)
-        _check_weighted(f"knn_interpolate_bwd[C={C}, Ns={Ns}]", g64, g32, g)
+        _check(f"knn_interpolate_bwd[C={C}, Ns={Ns}]", g64, g32, g)
         g2 = ops.knn_interpolate_bwd(_operand(gout, "wide", 1, tall=k), nbr.to(DEV), d2.to(DEV), Ns)
         assert _bits(g, g2) and _no_nan(g, g2), (C, Ns)
 
@@ -374,8 +375,8 @@ def test_trilinear_sample_bwd_tails_and_strides(C):
         _, gv64, gq64 = _sampler_ref(vol, q, gout, torch.float64)
         _, gv32, gq32 = _sampler_ref(vol, q, gout, torch.float32)
         gv, gq = ops.trilinear_sample_bwd(_rows3(gout, "contiguous", 1, tall=8), vol.to(DEV), q.to(DEV), want_vol=True, want_query=True)
-        _check_weighted(f"trilinear_sample_bwd grad_vol[C={C}, M={M}]", gv64, gv32, gv)
-        _check_weighted(f"trilinear_sample_bwd grad_query[C={C}, M={M}]", gq64, gq32, gq)
+        _check(f"trilinear_sample_bwd grad_vol[C={C}, M={M}]", gv64, gv32, gv)
+        _check(f"trilinear_sample_bwd grad_query[C={C}, M={M}]", gq64, gq32, gq)
         gv2, gq2 = ops.trilinear_sample_bwd(_rows3(gout, "wide", 1, tall=8), vol.to(DEV), q.to(DEV), want_vol=True, want_query=True)
         assert _bits(gv, gv2) and _bits(gq, gq2) and _no_nan(gv, gq, gv2, gq2), (C, M)
 
@@ -444,8 +445,8 @@ def test_hot_voxels_4000_queries_in_one_cell():
     _, gv64, gq64 = _sampler_ref(vol, q, gout, torch.float64)
     _, gv32, gq32 = _sampler_ref(vol, q, gout, torch.float32)
     gv, gq = ops.trilinear_sample_bwd(gout.to(DEV), vol.to(DEV), q.to(DEV), want_vol=True, want_query=True)
-    _check_weighted("hot voxels grad_vol", gv64, gv32, gv)
-    _check_weighted("hot voxels grad_query", gq64, gq32, gq)
+    _check("hot voxels grad_vol", gv64, gv32, gv)
+    _check("hot voxels grad_query", gq64, gq32, gq)
     # and the order: the same fp32 weights (gn_tri_weight's products restated) times grad_rows, added in ascending element index
     assert _bits(gv.view(-1, C), _expected_order(keys, wgt, gout.reshape(M, C).numpy(), 8, int(np.prod(dims))))
 
@@ -462,7 +463,7 @@ def test_hot_source_one_source_and_k_3():
     _, (g32,) = _grads(lambda t: s_knn(t, nbr, d2), [x], gout, torch.float32)
     out, (gx,) = _hip_grads(lambda t: A.knn_interpolate(t, ps.to(DEV), pq.to(DEV), sseg, qseg, k), [x], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
-    _check_weighted("hot source: one source, k = 3", g64, g32, gx)
+    _check("hot source: one source, k = 3", g64, g32, gx)
     assert _bits(gx, _expected_order(nbr.numpy().reshape(-1), _knn_coef_np(nbr, d2), gout.numpy(), k, sum(src_sizes)))
 
 
@@ -479,7 +480,7 @@ def test_hot_source_within_every_querys_first_k():
     _, (g32,) = _grads(lambda t: s_knn(t, nbr, d2), [x], gout, torch.float32)
     out, (gx,) = _hip_grads(lambda t: A.knn_interpolate(t, ps.to(DEV), pq.to(DEV), sseg, qseg, k), [x], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
-    _check_weighted("hot source: in every query's first k", g64, g32, gx)
+    _check("hot source: in every query's first k", g64, g32, gx)
     assert _bits(gx, _expected_order(nbr.numpy().reshape(-1), _knn_coef_np(nbr, d2), gout.numpy(), k, Ns))
 
 
@@ -504,7 +505,7 @@ def test_hot_point_in_every_centres_ball():
     _, (g32,) = _grads(fn, [x], gout, torch.float32)
     assert torch.equal(edges[:, :C].cpu(), fwd64[:, :C].float())
     gx = ops.sa_gather_bwd(gout.to(DEV), slot.to(DEV), C, n)
-    _check_weighted("hot point: in every centre's ball", g64, g32, gx)
+    _check("hot point: in every centre's ball", g64, g32, gx)
     assert _bits(gx, _expected_order(slot.numpy(), None, gout[:, :C].numpy(), 1, n))
 
 
@@ -590,7 +591,7 @@ def test_knn_ties_forward_and_backward_choose_the_same_sources(k):
     out, (gx,) = _hip_grads(hip, [x], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
     # 3. the gradient
-    _check_weighted(f"knn ties[k={k}]", g64, g32, gx)
+    _check(f"knn ties[k={k}]", g64, g32, gx)
     assert _bits(gx, _expected_order(nbr.numpy().reshape(-1), _knn_coef_np(nbr, d2), gout.numpy(), k, len(ps)))
 
 
@@ -612,8 +613,8 @@ def test_trilinear_sample_gradient_geometry(dims):
     out, (gv, gq) = _hip_grads(A.grid_sample_points, [vol, q], gout)
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
     name = "x".join(map(str, dims))
-    _check_weighted(f"sampler geometry {name} grad_vol", gv64, gv32, gv)
-    _check_weighted(f"sampler geometry {name} grad_query", gq64, gq32, gq)
+    _check(f"sampler geometry {name} grad_vol", gv64, gv32, gv)
+    _check(f"sampler geometry {name} grad_query", gq64, gq32, gq)
     assert _no_nan(gv, gq)
     D, H, W = dims
     for comp, size in enumerate((W, H, D)):                    # query component 0 indexes the last volume axis

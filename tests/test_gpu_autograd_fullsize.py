@@ -17,7 +17,8 @@ pytestmark = pytest.mark.gpu
 from garmentnets_amd import ops  # noqa: E402
 from garmentnets_amd.components.pointnet2 import Segments  # noqa: E402
 from test_autograd_host import s_global_max, s_knn, s_sa_gather, s_scatter, s_segment_max  # noqa: E402
-from test_gpu_autograd import DEV, _check_weighted, _gen, _grads, r_sample  # noqa: E402
+from grad_reference import _check, _gen, r_sample  # noqa: E402
+from test_gpu_autograd import DEV, _grads  # noqa: E402
 
 
 class _CpuClock:
@@ -57,7 +58,7 @@ def test_grid_scatter_bwd_at_48000_points_137_channels_8x32cubed_cells(reduce):
     else:
         with clock:
             _, (g32,) = _grads(fn, [src], gout, torch.float32)
-        _check_weighted("full size grid_scatter[mean]", g64, g32, gs)
+        _check("full size grid_scatter[mean]", g64, g32, gs)
     assert torch.equal(gs, run())
 
 
@@ -113,7 +114,7 @@ def test_sa_gather_bwd_at_24000_centres_65_slots_64_channels():
         _, (g32,) = _grads(fn, [x], gout, torch.float32)
     gd, sd = gout.to(DEV), slot.to(DEV)
     gx = ops.sa_gather_bwd(gd, sd, C, n)
-    _check_weighted("full size sa_gather", g64, g32, gx)
+    _check("full size sa_gather", g64, g32, gx)
     assert torch.equal(gx, ops.sa_gather_bwd(gd, sd, C, n))
 
 
@@ -135,7 +136,7 @@ def test_knn_interpolate_bwd_at_24000_sources_48000_queries_128_channels():
     assert torch.allclose(out.cpu().double(), fwd64, rtol=1e-5, atol=1e-5)
     gd = gout.to(DEV)
     gx = ops.knn_interpolate_bwd(gd, nbr_d, d2_d, sum(src_sizes))
-    _check_weighted("full size knn_interpolate", g64, g32, gx)
+    _check("full size knn_interpolate", g64, g32, gx)
     assert torch.equal(gx, ops.knn_interpolate_bwd(gd, nbr_d, d2_d, sum(src_sizes)))
 
 
@@ -160,7 +161,7 @@ def test_trilinear_sample_bwd_at_24x6000_queries_into_32cubed_x128():
         _, (gv32, gq32) = _grads(r_sample, [volc, q], gout, torch.float32)
     vd, qd, gd = vol.to(DEV), q.to(DEV), gout.to(DEV)
     gv, gq = ops.trilinear_sample_bwd(gd, vd, qd, want_vol=True, want_query=True)
-    _check_weighted("full size trilinear_sample grad_vol", gv64.permute(0, 2, 3, 4, 1), gv32.permute(0, 2, 3, 4, 1), gv)
-    _check_weighted("full size trilinear_sample grad_query", gq64, gq32, gq)
+    _check("full size trilinear_sample grad_vol", gv64.permute(0, 2, 3, 4, 1), gv32.permute(0, 2, 3, 4, 1), gv)
+    _check("full size trilinear_sample grad_query", gq64, gq32, gq)
     gv2, gq2 = ops.trilinear_sample_bwd(gd, vd, qd, want_vol=True, want_query=True)
     assert torch.equal(gv, gv2) and torch.equal(gq, gq2)

@@ -1,7 +1,7 @@
 """GPU (-m gpu): gradients of the 3-D UNet (csrc/unet_grad.hip, autograd.conv3d_gcr / max_pool3d_2 / unet3d).
 
 Reference: a plain-torch restatement built here from nn.functional (group_norm, conv3d, relu, max_pool3d, interpolate(mode='nearest'), cat) on the
-model's own parameters, run on the CPU in fp64 and in fp32.  Error rule (tests/test_gpu_autograd.py::_check_weighted): ours against fp64 at most
+model's own parameters (tests/grad_reference.py: r_layer, r_unet), run on the CPU in fp64 and in fp32.  Error rule (its _check): ours against fp64 at most
 4 x (torch-fp32 against fp64) + 1 fp32 ulp of the largest gradient, printed as `[grad-error] ...` before it is asserted.  No element is excluded.
 
 Layer level: the restatement is handed the ReLU mask of the HIP forward (y_hip > 0), so both sides differentiate the same piecewise-linear map.
@@ -36,8 +36,8 @@ Geometry: which test reaches which index arithmetic of csrc/unet_grad.hip (whole
         by tests/test_unet_grad_host.py::test_workspace_sizes);  y == nullptr: [chains-False]
     groupnorm_bwd_stats: the 208-voxel chunk tail, C / 4 = 3, 12, 24 not dividing 256 (idle threads), C = 1536 (> 1024: the multi-trip branch),
         goff = 8 with ldg > goff + C, both resolutions: test_groupnorm_bwd_stats_direct
-    linear_bwd_params: the row tail (rows < 8), the 1024-row chunk tail, the second output block, ldx > K, db == nullptr, the N and K limits:
-        test_linear_bwd_params_direct;  M == 0: test_linear_bwd_params_of_no_rows_is_exact_zeros
+    the final 1x1x1 convolution is a linear block (csrc/linear_grad.hip): its kernels are called directly in tests/test_gpu_mlp_grad.py; here it runs
+        inside every composition, and at a width its forward runs and no other case has in test_final_conv_wider_than_512_outputs
     relu_mask (-0.0, a denormal, NaN, +-inf, in place, a length that is no multiple of 1024): test_relu_mask_direct
 
 Mutation record (MI355X; mutants of csrc/unet_grad.hip that stay inside every buffer, built apart from the tree, each run once over this whole file;
@@ -48,19 +48,14 @@ Mutation record (MI355X; mutants of csrc/unet_grad.hip that stay inside every bu
        and leaves only fp64 summation to the bound.
     2. conv3d_bwd_weight_kernel decoding ty = rem % tiles_y, tx = rem / tiles_y: no failure, old or new, and none is possible: the decode is still a
        bijection of the sample's tiles, every tile is visited once, only the order inside the fp32 chains moves (an equivalent mutant).
-    3. linear_bwd_params_kernel staging xs[rr][kk] from row rb + min(rr, rows - 1) instead of 0 for rr >= rows: no failure, old or new, and none is
-       possible on finite x: ys[rr][.] is still 0 for those rows, so each stray term is 0 * x (an equivalent mutant; the guard is redundant).
-   Because 2 and 3 cannot bite, two neighbours of them that can were run as a fourth build, again in bounds:
+   Because 2 cannot bite, a neighbour of it that can was run as a further build, again in bounds:
     2b. the sample of a whole chain taken from its first tile (b = t_begin / tiles_per_sample): new failures test_conv3d_bwd_weight_direct[chains-True,
         chains-False] (the chain that spans samples 0 / 1), nothing else -- every other case has one tile per chain or chains inside one sample.
-    3b. both row tiles of the tail re-read from the last row (xs and ys at rb + min(rr, rows - 1)): new failures test_linear_bwd_params_direct
-        [1-1-1, 7-3-5, 1031-8-32, 2061-128-32, 300-512-7]; [520-5-1023] passes as it must (520 rows are whole sub-tiles).
    The new tests that no mutant fails (the ragged / non-cubic layer, composition, max-pool, apply and relu_mask cases) duplicate no old test: each
    runs index arithmetic (guards, zero fills, decodes with unequal extents) that the cubes never reach, so they stay.
 """
 import copy
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -69,74 +64,9 @@ pytestmark = pytest.mark.gpu
 
 from garmentnets_amd import arith as AR, autograd as A  # noqa: E402
 from garmentnets_amd.components.unet3d import Abstract3DUNet, SingleConv, stored_channels  # noqa: E402
+from grad_reference import _check, _gen, _randomise_norms, r_layer, r_sample, r_unet  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _check(name, ref64, t32, ours, factor=4):
-    """ours against fp64 <= factor x (torch-fp32 against fp64) + 1 fp32 ulp of the largest gradient; prints before it asserts; returns the ratio"""
-    ref64, t32, ours = ref64.double().cpu(), t32.double().cpu(), ours.double().cpu()
-    assert ref64.shape == ours.shape, (name, ref64.shape, ours.shape)
-    assert bool(torch.isfinite(ours).all()), name
-    e32 = float((t32 - ref64).abs().max())
-    eo = float((ours - ref64).abs().max())
-    ulp = float(np.spacing(np.float32(ref64.abs().max())))
-    bound = "none (printed only)" if factor is None else f"{factor * e32 + ulp:.3e}"
-    print(f"[grad-error] {name}: torch-fp32 {e32:.3e}  hip {eo:.3e}  ulp(max |g|) {ulp:.3e}  bound {bound}  ratio {eo / max(e32, 1e-300):.2f}")
-    if factor is not None:
-        assert eo <= factor * e32 + ulp, (name, eo, e32, ulp)
-    return eo / max(e32, 1e-300)
-
-
-# ------------------------------------------------------------------------------------------------ restatement (plain torch, any dtype, CPU, NCDHW)
-def r_layer(x0, x1, w, gamma, beta, groups, eps, mask=None):
-    x = x0 if x1 is None else torch.cat((x0, F.interpolate(x1, scale_factor=2, mode="nearest")), 1)
-    h = F.conv3d(F.group_norm(x, groups, gamma, beta, eps), w, padding=1)
-    return F.relu(h) if mask is None else h * mask
-
-
-def r_unet(model, P, x, selections=None, record=None):
-    """selections: (ReLU masks per layer in execution order, pool winner indices per level) taken from the HIP forward (hip_selections): the restatement
-    then differentiates the same piecewise-linear map as the HIP run, whatever the dtype; None: it forms its own, and appends them to the two lists
-    of record when that is given (print_cpu_e32: shared selections without a GPU)"""
-    masks, winners = (None, None) if selections is None else (iter(selections[0]), iter(selections[1]))
-
-    def double_conv(prefix, dc, x0, x1=None):
-        for k, sc in (("SingleConv1", dc.SingleConv1), ("SingleConv2", dc.SingleConv2)):
-            n = f"{prefix}.basic_module.{k}"
-            x0 = r_layer(x0, x1, P[n + ".conv.weight"], P[n + ".groupnorm.weight"], P[n + ".groupnorm.bias"], sc.groupnorm.num_groups, sc.groupnorm.eps,
-                         mask=None if masks is None else next(masks).to(x0.dtype))
-            x1 = None
-            if record is not None:
-                record[0].append(x0.detach() > 0)
-        return x0
-    feats = []
-    for i, enc in enumerate(model.encoders):
-        if i > 0 and winners is not None:
-            idx = next(winners)
-            x = x.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
-        elif i > 0 and record is not None:
-            x, idx = F.max_pool3d(x, 2, return_indices=True)
-            record[1].append(idx)
-        elif i > 0:
-            x = F.max_pool3d(x, 2)
-        x = double_conv(f"encoders.{i}", enc.basic_module, x)
-        feats.insert(0, x)
-    for i, dec in enumerate(model.decoders):
-        x = double_conv(f"decoders.{i}", dec.basic_module, feats[i + 1], x)
-    return F.conv3d(x, P["final_conv.weight"], P["final_conv.bias"])
-
-
-def _randomise_norms(module, g):
-    with torch.no_grad():
-        for m in module.modules():
-            if isinstance(m, torch.nn.GroupNorm):
-                m.weight.copy_(0.5 + torch.rand(m.weight.shape, generator=g))
-                m.bias.copy_(0.3 * torch.randn(m.bias.shape, generator=g))
 
 
 def _model(in_ch, out_ch, f_maps, seed, **kw):
@@ -434,6 +364,45 @@ def test_no_grad_path_is_model_forward_and_saves_nothing(which):
     assert out.grad_fn is None and not out.requires_grad and torch.equal(out, ref)
 
 
+def test_final_conv_wider_than_512_outputs():
+    """a final convolution of 520 outputs -- any width the forward runs -- over 512 rows of 16 channels stored as 32: a gradient on every tensor under the
+    rule, shared selections (as test_composition_shared_selections), strict-fp32 forward; two runs, the same bits"""
+    model = _model(8, 520, (16, 32), 31)
+    g = _gen(32)
+    x, R = torch.randn(1, 8, 8, 8, 8, generator=g), torch.randn(1, 520, 8, 8, 8, generator=g)
+    mg = copy.deepcopy(model).to(DEV)
+    fp32 = AR.DEFAULT.strict_fp32()
+    sel = hip_selections(mg, x, fp32)
+    g64, o64 = restated_unet_grads(model, x, R, torch.float64, selections=sel)
+    g32, _ = restated_unet_grads(model, x, R, torch.float32, selections=sel)
+    gh, oh = hip_unet_grads(mg, x, R, fp32)
+    assert float((oh.double().cpu() - o64).abs().max()) <= 1e-4 * float(o64.abs().max())
+    _compare_all("unet 520 outputs", g64, g32, gh)
+    gh2, _ = hip_unet_grads(mg, x, R, fp32)
+    for k in gh:
+        assert torch.equal(gh[k], gh2[k]), k
+
+
+@pytest.mark.parametrize("which", ["weight", "bias"])
+def test_an_in_place_update_of_the_final_conv_between_forward_and_backward_raises(which):
+    """the final convolution's own parameters are what the block saves: 'padded' stores 32 input channels for in_channels = 16, so a padded copy of the
+    weight alone would carry no version to check"""
+    model, x, _ = _composition_inputs("padded", 5)
+    mg = copy.deepcopy(model).to(DEV)
+    xd = x.to(DEV)
+    y = A.unet3d(mg, xd.clone().requires_grad_(True))
+    with torch.no_grad():
+        getattr(mg.final_conv, which).add_(1.0)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        y.sum().backward()
+    # the next forward runs on the updated parameter (the pack of the grad path is keyed by the parameters' versions)
+    ref = copy.deepcopy(mg)
+    ref.final_conv._invalidate()
+    with torch.no_grad():
+        want = ref(xd)
+    assert torch.equal(A.unet3d(mg, xd.clone().requires_grad_(True)).detach(), want)
+
+
 # ------------------------------------------------------------------------------------------------ 4. the end of the chain
 def test_second_stage_chain_gradient():
     """autograd.scatter (mean) -> autograd.unet3d -> autograd.grid_sample_points -> MSE: gradient to the scattered rows"""
@@ -441,10 +410,6 @@ def test_second_stage_chain_gradient():
         mask = (cell[None, :] == torch.arange(cells)[:, None]).to(src.dtype)
         return (mask @ src) / mask.sum(1).clamp(min=1)[:, None]
 
-    def r_sample(volume, query):
-        nb, m = query.shape[:2]
-        s = F.grid_sample(volume, (2.0 * query - 1.0).view(nb, m, 1, 1, 3), mode="bilinear", padding_mode="border", align_corners=True)
-        return s.view(nb, volume.shape[1], m).permute(0, 2, 1)
     g = _gen(61)
     B, n, C, G, M, CO = 2, 600, 32, 16, 300, 8
     model = _model(C, CO, (32, 64), 11)
@@ -589,46 +554,6 @@ def test_groupnorm_bwd_stats_direct(C, half):
         bound = V * 2.0 ** -52 * terms.abs().sum(1)
         print(f"[grad-error] groupnorm_bwd_stats C={C} half={half} {name}: largest error {float(err.max()):.3e}, largest error / bound {float((err / bound).max()):.3e}")
         assert bool((err <= bound).all()), (name, float((err / bound).max()))
-
-
-# (M, N, K, columns of x beyond K, with_bias)
-LINEAR_CASES = [(1, 1, 1, 0, True),             # the smallest call
-                (7, 3, 5, 0, True),             # M below one 8-row sub-tile
-                (1031, 8, 32, 8, True),         # a 7-row second chunk; x is 40 columns wide: ldx > K
-                (2061, 128, 32, 0, True),       # N * (K + 1) = 4224: two output blocks; a 13-row third chunk (one sub-tile and a 5-row tail)
-                (300, 512, 7, 0, False),        # the N = 512 limit; no bias gradient (db == nullptr)
-                (520, 5, 1023, 0, True)]        # the K = 1023 limit
-
-
-@pytest.mark.parametrize("M,N,K,xpad,with_bias", LINEAR_CASES)
-def test_linear_bwd_params_direct(M, N, K, xpad, with_bias):
-    """ops.linear_bwd_params against dY^T X and sum dY.  The file's rule, and beside it the bound derived from the kernel's own summation (at most 1024
-    sequential fp32 fmas per chunk, the chunks folded in fp64, one rounding to fp32): (1024 + 2) * 2^-24 * (|dY|^T |X|) per entry."""
-    from garmentnets_amd import ops
-    g = _gen(7 * M + 3 * N + K)
-    dy = torch.randn(M, N, generator=g)
-    xw = torch.randn(M, K + xpad, generator=g) + 0.25
-    dw, db = ops.linear_bwd_params(dy.to(DEV), xw.to(DEV), K=K, with_bias=with_bias)
-    x = xw[:, :K]
-    assert tuple(dw.shape) == (N, K)
-    checks = [("d weight", dw, dy.double().t() @ x.double(), dy.t() @ x, dy.abs().double().t() @ x.abs().double())]
-    if with_bias:
-        checks.append(("d bias", db, dy.double().sum(0), dy.sum(0), dy.abs().double().sum(0)))
-    else:
-        assert db is None
-    for name, ours, ref64, t32, mag in checks:
-        derived = (1024 + 2) * 2.0 ** -24 * mag
-        err = (ours.double().cpu() - ref64).abs()
-        print(f"[grad-error] linear_bwd_params M={M} N={N} K={K} {name}: largest error / derived bound {float((err / derived).max()):.3e}")
-        assert bool((err <= derived).all()), name
-        _check(f"linear_bwd_params M={M} N={N} K={K} {name}", ref64, t32, ours)
-
-
-def test_linear_bwd_params_of_no_rows_is_exact_zeros():
-    from garmentnets_amd import ops
-    dw, db = ops.linear_bwd_params(torch.empty(0, 6, device=DEV), torch.empty(0, 9, device=DEV))
-    assert tuple(dw.shape) == (6, 9) and tuple(db.shape) == (6,)
-    assert not bool(dw.view(torch.int32).any()) and not bool(db.view(torch.int32).any())
 
 
 def test_relu_mask_direct():
