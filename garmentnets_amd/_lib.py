@@ -118,15 +118,22 @@ PROTOTYPES = {
     "gn_linear_bwd_weight_workspace_bytes": [_i64, _i32, _i32],
     "gn_linear_bwd_weight": [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _i32, _vp],
     "gn_row_affine": [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _vp],
+    "gn_col_moments_workspace_bytes": [_i64, _i32],
+    "gn_col_moments": [_vp, _i32, _i64, _i32, _vp, _sz, _vp, _vp],
+    "gn_col_dots_workspace_bytes": [_i64, _i32],
+    "gn_col_dots": [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _sz, _vp, _vp],
+    "gn_bn_train_bwd_workspace_bytes": [_i64, _i32],
+    "gn_bn_train_bwd": [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp],
 }
 _RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
              "gn_nocs_bin_metrics_workspace_bytes": _sz, "gn_value_losses_workspace_bytes": _sz,
              "gn_grid_scatter_bwd_workspace_bytes": _sz, "gn_sa_gather_bwd_workspace_bytes": _sz, "gn_knn_interpolate_bwd_workspace_bytes": _sz,
              "gn_trilinear_sample_bwd_workspace_bytes": _sz, "gn_conv3d_bwd_weight_workspace_bytes": _sz, "gn_groupnorm_bwd_stats_workspace_bytes": _sz,
-             "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz}
+             "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz,
+             "gn_col_moments_workspace_bytes": _sz, "gn_col_dots_workspace_bytes": _sz, "gn_bn_train_bwd_workspace_bytes": _sz}
 
 LINEAR_BWD_CHUNK_ROWS = 512                     # GN_LINEAR_BWD_CHUNK_ROWS
-LINEAR_ACT_CHUNK_ROWS = 1024                    # GN_LINEAR_ACT_CHUNK_ROWS
+LINEAR_ACT_CHUNK_ROWS = 1024                    # GN_LINEAR_ACT_CHUNK_ROWS (gn_linear_act_bwd, gn_col_moments, gn_col_dots, gn_bn_train_bwd)
 
 LOSS_MAX_SETS = 8                               # GN_LOSS_MAX_SETS
 LOSS_KINDS = {"l2": 0, "smooth_l1": 1, "bce_logits": 2, "row_norm": 3}

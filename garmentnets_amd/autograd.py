@@ -15,7 +15,10 @@ csrc/linear_grad.hip (DESIGN.md "MLP gradients"); ``implicit_decode`` is the dec
 gradient flows from a torch loss on the decoder's prediction to every parameter of the second stage, and into PointNet++ through
 ``point_conv_max(local_nn=lambda e: mlp(stack, e))``.
 
-What this is NOT: a training loop, an optimiser, train-mode BatchNorm, gradients of the loss kernels (csrc/losses.hip: torch's own losses close the
+``mlp(..., batch_stats=True)`` gives a BatchNorm in training mode torch's semantics: the batch's own mean and biased variance over all rows, the
+gradient through both, the running buffers updated in place (DESIGN.md "Train-mode BatchNorm").
+
+What this is NOT: a training loop, an optimiser, gradients of the loss kernels (csrc/losses.hip: torch's own losses close the
 chain), or a backward for the fused inference kernels (the fused / split-operand decoder, ``gn_sa_fused``: ``implicit_decode`` and ``point_conv_max``
 are the unfused chains).  The inference modules do not import this file.
 
@@ -28,7 +31,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .components import unet3d as U
-from .components.mlp import HipLinear, MLPStack, pack_wb, param_cache
+from .components.mlp import HipLinear, MLPStack, fold_batchnorm, pack_linear, pack_wb, param_cache
 from .components.pointnet2 import Segments, _example_self_src
 
 __all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
@@ -429,11 +432,7 @@ class _LinearBlock(torch.autograd.Function):
         g, sums = ops.linear_act_bwd(ops.fp32_rows(grad_y, "grad_y", cols=n), r, ctx.sc)
         dx = dw = db = dgamma = dbeta = None
         if need[0]:
-            # (the saved weight IS the module's at the forward's version -- unpacking it has checked that -- so the version-keyed cache holds its pack,
-            #  and ctx.wp, the forward's pack of it, holds its values)
-            gen = (weight.device,) + tuple(p._version for p in ctx.owner.parameters())
-            wt = param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(ctx.wp[:, :k].t().contiguous(), None)[0])
-            dx = ops.linear(g, wt, K=n)
+            dx = ops.linear(g, _wt_pack(ctx, weight), K=n)
         if need[1]:
             # (over the stored width; a channel-padded input's pad columns multiply exact zeros and reach no parameter)
             dw = ops.linear_bwd_weight(g, x, K=k)[:, :k_real].reshape(weight.shape)
@@ -444,6 +443,77 @@ class _LinearBlock(torch.autograd.Function):
         if beta is not None and need[4]:
             dbeta = sums[1].float()
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+
+
+def _wt_pack(ctx, weight):
+    """the transposed weight pack of a block's dX = g W.  (The saved weight IS the module's at the forward's version -- unpacking it has checked that -- so
+    the version-keyed cache holds its pack, and ctx.wp, the forward's pack of it, holds its values.)"""
+    gen = (weight.device,) + tuple(p._version for p in ctx.owner.parameters())
+    return param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(ctx.wp[:, :ctx.k].t().contiguous(), None)[0])
+
+
+def _bn_update_buffers(bn, mean, m2, M):
+    """nn.BatchNorm1d's in-place update of a training module's buffers from the batch's fp64 column mean and m2 = sum (r - mean)^2 over M rows: the
+    UNBIASED variance m2 / (M - 1) goes into running_var; the factor is momentum, or 1 / num_batches_tracked (after its increment) under momentum=None"""
+    with torch.no_grad():
+        bn.num_batches_tracked.add_(1)
+        f = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.double()
+        bn.running_mean.copy_((1.0 - f) * bn.running_mean.double() + f * mean)
+        bn.running_var.copy_((1.0 - f) * bn.running_var.double() + f * (m2 / (M - 1)))
+
+
+def _bn_bwd_coef(gamma, mean, inv, s_dy, s_dyr, M):
+    """fp64, per column: the batch mean and inverse standard deviation, S_dy = sum_m dy, S_dyr = sum_m dy * r -> (dgamma, coef [3][N] = (a, b, c)) with
+    the gradient at the ReLU's output a * dy + b * r + c (DESIGN.md "Train-mode BatchNorm"; dbeta is S_dy)"""
+    dgamma = (s_dyr - mean * s_dy) * inv
+    a = gamma.detach().double() * inv
+    b = -a * inv * dgamma / M
+    c = -a * s_dy / M - b * mean
+    return dgamma, torch.stack((a, b, c))
+
+
+def _batch_stats_forward(x, wp, b, k, bn):
+    """one block under batch statistics: r = relu(x W^T + b), its column moments (gn_col_moments), y = gn_row_affine(r, sc, sh) with the batch mean and
+    biased variance folded as fold_batchnorm folds the running ones (fp64, each of sc / sh rounded once), then the buffer update.  -> (r, y, mean, inv):
+    the statistics in fp64"""
+    r = ops.linear(x, wp, b, None, None, relu=True, K=k)
+    M = r.shape[0]
+    mean, m2 = ops.col_moments(r)
+    inv = 1.0 / torch.sqrt(m2 / M + bn.eps)
+    sc = bn.weight.detach().double() * inv
+    sh = bn.bias.detach().double() - mean * sc
+    y = ops.row_affine(r, sc.float().contiguous(), sh.float().contiguous())
+    _bn_update_buffers(bn, mean, m2, M)
+    return r, y, mean, inv
+
+
+class _BatchStatsBlock(torch.autograd.Function):
+    """one block r = relu(x W^T + b), y = BatchNorm(r) in training mode (DESIGN.md "Train-mode BatchNorm").  The backward reads the batch mean and inverse
+    standard deviation the forward captured (fp64, on ctx), never the running buffers: their in-place update neither raises nor changes the gradient.
+    The parameters are saved, as _LinearBlock saves them."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, wp, b, k, bn, owner, idx):
+        if x.shape[1] != k:
+            raise ValueError(f"{type(owner).__name__}: input of {x.shape[1]} channels, expected {k}")
+        r, y, ctx.mean, ctx.inv = _batch_stats_forward(x, wp, b, k, bn)
+        ctx.save_for_backward(x, r, weight, bias, gamma, beta)
+        ctx.wp, ctx.k, ctx.owner, ctx.idx = wp, k, owner, idx
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, r, weight, bias, gamma, beta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n, M = weight.shape[0], r.shape[0]
+        dy = ops.fp32_rows(grad_y, "grad_y", cols=n)
+        s_dy, s_dyr = ops.col_dots(dy, r)
+        dgamma, coef = _bn_bwd_coef(gamma, ctx.mean, ctx.inv, s_dy, s_dyr, M)
+        g, sum_g = ops.bn_train_bwd(dy, r, coef)
+        dx = ops.linear(g, _wt_pack(ctx, weight), K=n) if need[0] else None
+        dw = ops.linear_bwd_weight(g, x, K=ctx.k).reshape(weight.shape) if need[1] else None
+        db = sum_g.float() if bias is not None and need[2] else None
+        return dx, dw, db, dgamma.float() if need[3] else None, s_dy.float() if need[4] else None, None, None, None, None, None, None
 
 
 def _needs_grad(module, x):
@@ -463,28 +533,69 @@ def _grad_layers(module, pack):
     return param_cache(module, "_grad_fwd_packs").get(gen, "layers", pack)
 
 
-def mlp(stack, x):
-    """``MLPStack.forward``'s contract -- x fp32 (..., C) -> (..., C') through [Linear, ReLU, eval-mode BatchNorm] blocks -- differentiable in x and
-    in every Linear weight / bias and BatchNorm weight / bias of the stack; the running statistics are data.  Each block runs gn_linear with the ReLU
-    and WITHOUT the BatchNorm epilogue, keeps x and r, and applies the epilogue's own fmul / fadd as gn_row_affine: the bits are ``stack(x)``'s, and
-    the mask is the forward's own r > 0 (y = r * sc + sh cannot be inverted).  Backward: csrc/linear_grad.hip, dX = gn_linear on the transposed pack.
-    Eval-mode only: a stack with a BatchNorm in training mode raises NotImplementedError (the forward folds the running statistics whatever the mode,
-    so that gradient would silently be the wrong one; a fresh module is in training mode -- call .eval()).  Under torch.no_grad(), or when nothing
-    requires a gradient, this is ``stack(x)``'s launches and nothing is saved."""
+def _batch_stats_layers(stack):
+    """the packs of a stack that holds a training BatchNorm: (wp, b, sc, sh, k) per block with (sc, sh) the folded running statistics of the EVAL-mode
+    BatchNorms only (None for a training one: its buffers change at every call and are not read).  Keyed by the parameters' versions, the modes and the
+    eval-mode buffers' versions."""
+    bns = [block[2] if len(block) > 2 else None for block in stack]
+    gen = (next(stack.parameters()).device,) + tuple(p._version for p in stack.parameters()) + \
+        tuple(None if bn is None else True if bn.training else (bn.running_mean._version, bn.running_var._version) for bn in bns)
+
+    def build():
+        layers = []
+        for block, bn in zip(stack, bns):
+            sc, sh = (None, None) if bn is None or bn.training else fold_batchnorm(bn)
+            layers.append(pack_linear(block[0])[:2] + (sc, sh, block[0].in_features))
+        return layers
+    return param_cache(stack, "_grad_batch_stats_packs").get(gen, "layers", build)
+
+
+def mlp(stack, x, batch_stats=False):
+    """``MLPStack.forward``'s contract -- x fp32 (..., C) -> (..., C') through [Linear, ReLU, BatchNorm] blocks -- differentiable in x and in every Linear
+    weight / bias and BatchNorm weight / bias of the stack.
+
+    batch_stats=False: eval-mode BatchNorm, the running statistics are data.  Each block runs gn_linear with the ReLU and WITHOUT the BatchNorm epilogue,
+    keeps x and r, and applies the epilogue's own fmul / fadd as gn_row_affine: the bits are ``stack(x)``'s, and the mask is the forward's own r > 0
+    (y = r * sc + sh cannot be inverted).  Backward: csrc/linear_grad.hip, dX = gn_linear on the transposed pack.  A stack with a BatchNorm in training
+    mode raises NotImplementedError (the forward folds the running statistics whatever the mode, so that gradient would silently be the wrong one; a
+    fresh module is in training mode -- call .eval(), or pass batch_stats=True).  Under torch.no_grad(), or when nothing requires a gradient, this is
+    ``stack(x)``'s launches and nothing is saved.
+
+    batch_stats=True: torch's per-module rule.  A BatchNorm in training mode normalises with the mean and biased variance of its input over ALL rows
+    (every leading dimension flattened, as PointBatchNorm1D does), the gradient flows through both statistics, and its running_mean / running_var /
+    num_batches_tracked are updated in place as nn.BatchNorm1d updates them -- under no_grad too, where nothing is saved.  A BatchNorm in eval mode in
+    the same stack keeps the path above.  Refused before any launch: track_running_stats=False (NotImplementedError), fewer than 2 rows (ValueError)."""
     if not isinstance(stack, MLPStack):
         raise TypeError(f"mlp: expected a components.mlp.MLPStack, got {type(stack).__name__}")
     _fp32_features(x, "mlp")
-    for block in stack:
-        if len(block) > 2 and block[2].training:
-            raise NotImplementedError("mlp: train-mode BatchNorm has no gradient here (the forward folds the running statistics): call .eval() on the stack")
-    if not _needs_grad(stack, x):
+    training = [len(block) > 2 and block[2].training for block in stack]
+    if any(training) and not batch_stats:
+        raise NotImplementedError("mlp: train-mode BatchNorm has no gradient here (the forward folds the running statistics): call .eval() on the stack, "
+                                  "or pass batch_stats=True to normalise with the batch's own statistics")
+    if any(training):
+        rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        for block, t in zip(stack, training):
+            if t and (not block[2].track_running_stats or block[2].running_mean is None or block[2].running_var is None):
+                raise NotImplementedError("mlp: a training BatchNorm with track_running_stats=False (no running buffers) is not supported")
+            if t and rows < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    grad = _needs_grad(stack, x)
+    if not grad and not any(training):
         with torch.no_grad():
             return stack(x)
     lead = x.shape[:-1]
     h = ops.fp32_rows(x.reshape(-1, x.shape[-1]), "x")
-    for i, (block, layer) in enumerate(zip(stack, _grad_layers(stack, stack._pack))):
+    layers = _batch_stats_layers(stack) if any(training) else _grad_layers(stack, stack._pack)
+    for i, (block, layer, t) in enumerate(zip(stack, layers, training)):
         lin, bn = block[0], block[2] if len(block) > 2 else None
-        h = _LinearBlock.apply(h, lin.weight, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias, layer, True, bn, stack, i)
+        wp, b, sc, sh, k = layer
+        if not grad:
+            with torch.no_grad():
+                h = _batch_stats_forward(h, wp, b, k, bn)[1] if t else ops.linear(h, wp, b, sc, sh, relu=True, K=k)
+        elif t:
+            h = _BatchStatsBlock.apply(h, lin.weight, lin.bias, bn.weight, bn.bias, wp, b, k, bn, stack, i)
+        else:
+            h = _LinearBlock.apply(h, lin.weight, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias, layer, True, bn, stack, i)
     return h.reshape(*lead, h.shape[-1])
 
 
@@ -503,11 +614,11 @@ def linear(hip_linear, x, relu=False):
     return h.reshape(*lead, h.shape[-1])
 
 
-def implicit_decode(decoder, features_grid, query_points):
+def implicit_decode(decoder, features_grid, query_points, batch_stats=False):
     """``ImplicitWNFDecoder.forward``'s contract -- features_grid (B, C, D, H, W), query_points (B, M, 3) in [0, 1] -> (B, M, out) -- as the unfused
     chain ``grid_sample_points`` -> ``mlp(decoder.mlp, .)``, differentiable in the volume, the queries and the decoder's parameters.  The fused and
-    split-operand decoder kernels stay inference-only."""
+    split-operand decoder kernels stay inference-only.  batch_stats: ``mlp``'s keyword (the statistics run over all B * M query rows)."""
     from .networks.conv_implicit_wnf import ImplicitWNFDecoder
     if not isinstance(decoder, ImplicitWNFDecoder):
         raise TypeError(f"implicit_decode: expected a networks.conv_implicit_wnf.ImplicitWNFDecoder, got {type(decoder).__name__}")
-    return mlp(decoder.mlp, grid_sample_points(features_grid, query_points.float()))
+    return mlp(decoder.mlp, grid_sample_points(features_grid, query_points.float()), batch_stats=batch_stats)

@@ -5,6 +5,7 @@
 //   gn_linear_bwd_weight  dW[n][k] = sum_m g[m][n] x[m][k] on the fp32 matrix cores
 //   gn_row_affine         y = fadd(fmul(r, sc[n]), sh[n]): gn_linear's BatchNorm epilogue as a kernel of its own (the differentiable forward keeps r)
 //   (dX = g W is gn_linear on the transposed weight pack: no kernel here)
+//   gn_col_moments / gn_col_dots / gn_bn_train_bwd   train-mode BatchNorm (batch statistics): fp64 column reductions of one shared kernel, at the end
 //
 // The weight gradient.  v_mfma_f32_32x32x2_f32 (linear.hip's instruction; exact fp32, a k-ordered fma chain): D(32x32) += A(32x2) B(2x32), operand A:
 // lane l holds A[l&31][l>>5], operand B: lane l holds B[l>>5][l&31], D: lane l, reg r -> column l&31, row (r&3)+8*(r>>2)+4*(l>>5).  The reduction
@@ -293,4 +294,131 @@ extern "C" int gn_row_affine(const float *r, int ldr, const float *sc, const flo
     hipLaunchKernelGGL(row_affine_kernel, dim3((unsigned)gn_cdiv(M * N, 256)), dim3(256), 0, gn_stream(stream), r, ldr, sc, sh, M, N, y, ldy);
     GN_LAUNCH_CHECK("gn_row_affine");
     return GN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ train-mode BatchNorm: column reductions
+// y = (r - mean) * inv * gamma + beta with the batch's own mean and biased variance over the M rows (DESIGN.md "Train-mode BatchNorm").  One kernel, four
+// per-element terms: each adds J fp64 values per (row, column) and folds them like linear_act_bwd_kernel -- chunks of GN_LINEAR_ACT_CHUNK_ROWS rows, then
+// lg_fold over the chunks.  Thread map: cw = the power of two >= N, at most 64, columns per workgroup (thread = (row group tid / cw, column tid % cw)), so
+// a wave reads 64 / cw whole rows of a narrow matrix (the decoder head's N = 1: 64 consecutive rows) and 64 consecutive columns of a wide one.  A thread
+// adds its rows m0 + group, + 256 / cw, ... in ascending order; the 256 / cw groups are then added by a halving tree through LDS (group p += group p + h,
+// h = groups / 2 ... 1): an order that depends on (M, N) alone.
+enum { CS_SUM, CS_M2, CS_DOTS, CS_BN };
+//   CS_SUM   a          -> sum a                                                      (the mean's numerator; converting a float is exact)
+//   CS_M2    a, p[n]    -> sum (a - p[n])^2                                           (p: the column mean)
+//   CS_DOTS  a, b       -> sum a, sum a * b                                           (products of two 24-bit significands: exact)
+//   CS_BN    a, b, p    -> g = b > 0 ? (float)(p[0][n] a + p[1][n] b + p[2][n]) : 0, sum g   (a = dy, b = r; g may be a: each element is read, then written, by one thread)
+template <int T>
+__global__ __launch_bounds__(256) void col_sums_kernel(const float *a, int lda, const float *__restrict__ b, int ldb, const double *__restrict__ p, int64_t M,
+                                                       int N, int cw, float *g, int ldg, double *__restrict__ part) {
+    constexpr int J = T == CS_DOTS ? 2 : 1;
+    __shared__ double red[J][256];
+    const int col = threadIdx.x & (cw - 1), grp = threadIdx.x / cw, groups = 256 / cw, n = blockIdx.y * cw + col;
+    const int64_t m0 = (int64_t)blockIdx.x * LA_ROWS;
+    const int64_t m1 = m0 + LA_ROWS < M ? m0 + LA_ROWS : M;
+    double s[J] = {};
+    if (n < N) {
+        const double p0 = T == CS_M2 || T == CS_BN ? p[n] : 0.0, p1 = T == CS_BN ? p[N + n] : 0.0, p2 = T == CS_BN ? p[2 * (int64_t)N + n] : 0.0;
+#pragma unroll 4
+        for (int64_t m = m0 + grp; m < m1; m += groups) {
+            const float av = a[m * lda + n];
+            if (T == CS_SUM) {
+                s[0] += (double)av;
+            } else if (T == CS_M2) {
+                const double d = (double)av - p0;
+                s[0] += d * d;
+            } else {
+                const float bv = b[m * ldb + n];
+                if (T == CS_DOTS) {
+                    s[0] += (double)av;
+                    s[J - 1] += (double)av * (double)bv;
+                } else {
+                    const float gv = bv > 0.f ? (float)((p0 * (double)av + p1 * (double)bv) + p2) : 0.f;      // gn_relu_mask's rule: a NaN in r takes no gradient
+                    g[m * ldg + n] = gv;
+                    s[0] += (double)gv;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) red[j][threadIdx.x] = s[j];
+    __syncthreads();
+    for (int h = groups >> 1; h >= 1; h >>= 1) {
+        if (grp < h) {
+#pragma unroll
+            for (int j = 0; j < J; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + h * cw];
+        }
+        __syncthreads();
+    }
+    if (grp == 0 && n < N) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) part[((int64_t)blockIdx.x * J + j) * N + n] = red[j][col];
+    }
+}
+
+// sums[o] = (the chunks of part[chunks][total] in lg_fold's order) / div
+__global__ __launch_bounds__(256) void col_sums_fold_kernel(const double *__restrict__ part, int chunks, int64_t total, double div, double *__restrict__ sums) {
+    __shared__ double red[LG_FOLD_RUNS][LG_FOLD_OUTS];
+    const int64_t o = (int64_t)blockIdx.x * LG_FOLD_OUTS + threadIdx.x % LG_FOLD_OUTS;
+    const double t = lg_fold(part, chunks, total, o, red);
+    if (threadIdx.x < LG_FOLD_OUTS && o < total) sums[o] = t / div;
+}
+
+static size_t col_sums_bytes(int64_t M, int N, int J) { return M <= 0 || N <= 0 ? 0 : (size_t)gn_cdiv(M, LA_ROWS) * J * (size_t)N * sizeof(double); }
+
+// one reduction: the chunk launch (none when M == 0) and the fold of its J * N outputs
+template <int T>
+static int col_sums_run(const char *who, const float *a, int lda, const float *b, int ldb, const double *p, int64_t M, int N, float *g, int ldg, double *ws,
+                        double div, double *sums, hipStream_t st) {
+    constexpr int J = T == CS_DOTS ? 2 : 1;
+    const int chunks = (int)gn_cdiv(M, LA_ROWS);
+    int cw = LA_COLS;
+    while (cw / 2 >= N) cw /= 2;
+    if (chunks > 0) {
+        hipLaunchKernelGGL(col_sums_kernel<T>, dim3((unsigned)chunks, (unsigned)gn_cdiv(N, cw)), dim3(256), 0, st, a, lda, b, ldb, p, M, N, cw, g, ldg, ws);
+        GN_LAUNCH_CHECK(who);
+    }
+    hipLaunchKernelGGL(col_sums_fold_kernel, dim3((unsigned)gn_cdiv(J * (int64_t)N, LG_FOLD_OUTS)), dim3(256), 0, st, (const double *)ws, chunks, J * (int64_t)N,
+                       div, sums);
+    GN_LAUNCH_CHECK(who);
+    return GN_OK;
+}
+
+// what the three entries refuse alike: the grid is (chunks, ceil(N / 64)) at most
+#define CS_GRID_OK(M, N) (gn_cdiv(M, LA_ROWS) <= 0x7fffffff && gn_cdiv(N, LA_COLS) <= 65535)
+
+extern "C" size_t gn_col_moments_workspace_bytes(int64_t M, int N) { return col_sums_bytes(M, N, 1); }
+
+extern "C" int gn_col_moments(const float *r, int ldr, int64_t M, int N, void *ws, size_t ws_bytes, double *moments, void *stream) {
+    GN_REQUIRE(M >= 0 && N > 0 && ldr >= N && CS_GRID_OK(M, N), "gn_col_moments: bad sizes M=%lld N=%d (ldr=%d)", (long long)M, N, ldr);
+    const size_t need = gn_col_moments_workspace_bytes(M, N);
+    GN_REQUIRE(ws_bytes >= need, "gn_col_moments: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    GN_REQUIRE(moments != nullptr && (M == 0 || (r && ws)), "gn_col_moments: null pointer");
+    hipStream_t st = gn_stream(stream);
+    // two passes: the mean first, then the squares of the differences from it (the second launch reads the first fold's result: stream order)
+    const int rc = col_sums_run<CS_SUM>("gn_col_moments", r, ldr, nullptr, 0, nullptr, M, N, nullptr, 0, (double *)ws, M > 0 ? (double)M : 1.0, moments, st);
+    if (rc != GN_OK) return rc;
+    return col_sums_run<CS_M2>("gn_col_moments", r, ldr, nullptr, 0, moments, M, N, nullptr, 0, (double *)ws, 1.0, moments + N, st);
+}
+
+extern "C" size_t gn_col_dots_workspace_bytes(int64_t M, int N) { return col_sums_bytes(M, N, 2); }
+
+extern "C" int gn_col_dots(const float *dy, int lddy, const float *r, int ldr, int64_t M, int N, void *ws, size_t ws_bytes, double *dots, void *stream) {
+    GN_REQUIRE(M >= 0 && N > 0 && lddy >= N && ldr >= N && CS_GRID_OK(M, N), "gn_col_dots: bad sizes M=%lld N=%d (lddy=%d ldr=%d)", (long long)M, N, lddy, ldr);
+    const size_t need = gn_col_dots_workspace_bytes(M, N);
+    GN_REQUIRE(ws_bytes >= need, "gn_col_dots: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    GN_REQUIRE(dots != nullptr && (M == 0 || (dy && r && ws)), "gn_col_dots: null pointer");
+    return col_sums_run<CS_DOTS>("gn_col_dots", dy, lddy, r, ldr, nullptr, M, N, nullptr, 0, (double *)ws, 1.0, dots, gn_stream(stream));
+}
+
+extern "C" size_t gn_bn_train_bwd_workspace_bytes(int64_t M, int N) { return col_sums_bytes(M, N, 1); }
+
+extern "C" int gn_bn_train_bwd(const float *dy, int lddy, const float *r, int ldr, const double *coef, int64_t M, int N, float *g, int ldg, void *ws,
+                               size_t ws_bytes, double *sum_g, void *stream) {
+    GN_REQUIRE(M >= 0 && N > 0 && lddy >= N && ldr >= N && ldg >= N && CS_GRID_OK(M, N), "gn_bn_train_bwd: bad sizes M=%lld N=%d (lddy=%d ldr=%d ldg=%d)",
+               (long long)M, N, lddy, ldr, ldg);
+    const size_t need = gn_bn_train_bwd_workspace_bytes(M, N);
+    GN_REQUIRE(ws_bytes >= need, "gn_bn_train_bwd: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    GN_REQUIRE(sum_g != nullptr && (M == 0 || (dy && r && coef && g && ws)), "gn_bn_train_bwd: null pointer");
+    return col_sums_run<CS_BN>("gn_bn_train_bwd", dy, lddy, r, ldr, coef, M, N, g, ldg, (double *)ws, 1.0, sum_g, gn_stream(stream));
 }

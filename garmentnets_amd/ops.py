@@ -1554,3 +1554,47 @@ def row_affine(r, sc, sh, out=None):
         out = new_rows(M, N, r.device)
     _lib.call("gn_row_affine", _p(r), rows_view(r)[1], _p(sc), _p(sh), M, N, _p(out), rows_view(out)[1], _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ train-mode BatchNorm (csrc/linear_grad.hip)
+def col_moments(r):
+    """rows r [M][N] -> fp64 [2][N]: the column mean and m2 = sum_m (r - mean)^2, two passes (gn_col_moments); a constant column has m2 == 0.0"""
+    r = fp32_rows(r, "col_moments: r")
+    M, N = r.shape
+    out = torch.empty((2, N), dtype=torch.float64, device=r.device)
+    nbytes = _lib.load().gn_col_moments_workspace_bytes(M, N)
+    ws = _ws(nbytes, r.device)
+    _lib.call("gn_col_moments", _p(r), rows_view(r)[1], M, N, _p(ws), nbytes, _p(out), _stream())
+    return out
+
+
+def col_dots(dy, r):
+    """rows dy, r [M][N] -> fp64 [2][N] = sum_m dy, sum_m dy * r (gn_col_dots)"""
+    dy = fp32_rows(dy, "col_dots: dy")
+    M, N = dy.shape
+    r = fp32_rows(r, "col_dots: r", M, N)
+    out = torch.empty((2, N), dtype=torch.float64, device=dy.device)
+    nbytes = _lib.load().gn_col_dots_workspace_bytes(M, N)
+    ws = _ws(nbytes, dy.device)
+    _lib.call("gn_col_dots", _p(dy), rows_view(dy)[1], _p(r), rows_view(r)[1], M, N, _p(ws), nbytes, _p(out), _stream())
+    return out
+
+
+def bn_train_bwd(dy, r, coef, out=None):
+    """rows dy, r [M][N], coef fp64 [3][N] = (a, b, c) -> (g [M][N] = r > 0 ? a * dy + b * r + c : 0, evaluated in fp64 and rounded once; sum_g fp64 [N])
+    (gn_bn_train_bwd).  out: the buffer of g (may be dy)."""
+    dy = fp32_rows(dy, "bn_train_bwd: dy")
+    M, N = dy.shape
+    r = fp32_rows(r, "bn_train_bwd: r", M, N)
+    _chk(coef, torch.float64, "bn_train_bwd: coef")
+    if tuple(coef.shape) != (3, N):
+        raise ValueError(f"bn_train_bwd: coef must be (3, {N}), got {tuple(coef.shape)}")
+    g = new_rows(M, N, dy.device) if out is None else fp32_rows(out, "bn_train_bwd: out", M, N)
+    if out is not None and g is not out:
+        raise ValueError("bn_train_bwd: out must have unit column stride")
+    sum_g = torch.empty(N, dtype=torch.float64, device=dy.device)
+    nbytes = _lib.load().gn_bn_train_bwd_workspace_bytes(M, N)
+    ws = _ws(nbytes, dy.device)
+    _lib.call("gn_bn_train_bwd", _p(dy), rows_view(dy)[1], _p(r), rows_view(r)[1], _p(coef), M, N, _p(g), rows_view(g)[1], _p(ws), nbytes, _p(sum_g),
+              _stream())
+    return g, sum_g

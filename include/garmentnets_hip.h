@@ -649,6 +649,30 @@ int gn_linear_bwd_weight(const float *g, int ldg, const float *x, int ldx, int64
 /* y[m][n] = fadd(fmul(r[m][n], sc[n]), sh[n]): gn_linear's BatchNorm epilogue as a pass of its own, the same two roundings (y may be r). */
 int gn_row_affine(const float *r, int ldr, const float *sc, const float *sh, int64_t M, int N, float *y, int ldy, void *stream);
 
+/* ---- Train-mode BatchNorm of an MLP block (DESIGN.md "Train-mode BatchNorm"): y = (r - mean) * inv * gamma + beta with the batch's own statistics over
+ * the M rows of r = relu(x W^T + b).  Three fp64 column reductions of one kernel.  Rows in chunks of GN_LINEAR_ACT_CHUNK_ROWS; inside a chunk 256 / cw
+ * interleaved row groups (cw = the power of two >= N, at most 64), each ascending, added by a halving tree; the chunks in eight contiguous runs, each
+ * ascending, the run sums added in ascending order.  M == 0: zeros.  Rows beyond M and columns beyond N are never read. ---- */
+
+/* moments[2][N] fp64: the column mean and m2 = sum_m (r - mean)^2 (biased variance m2 / M, unbiased m2 / (M - 1)).  Two passes: mean = (sum_m r) / M, then
+ * the squares of the fp64 differences from that mean.  Guarantee, u = 2^-53: |mean - exact| = d <= M u mean_m |r| + u |mean|, and
+ * |m2 - exact| <= (M + 4) u m2 + M d^2 (the second term: the computed mean is not the exact one; (M u)^2 mean|r|^2 / variance relative to m2).  A column of
+ * equal entries c gives mean == c and m2 == 0.0 exactly while M < 2^29 (every partial sum k c is an fp64 number, and (M c) / M is c).
+ * Workspace: ceil(M / GN_LINEAR_ACT_CHUNK_ROWS) * N doubles. */
+size_t gn_col_moments_workspace_bytes(int64_t M, int N);
+int gn_col_moments(const float *r, int ldr, int64_t M, int N, void *ws, size_t ws_bytes, double *moments, void *stream);
+
+/* dots[2][N] fp64 = sum_m dy, sum_m dy * r (products exact).  Nothing else is written.  Workspace: ceil(M / GN_LINEAR_ACT_CHUNK_ROWS) * 2 * N doubles. */
+size_t gn_col_dots_workspace_bytes(int64_t M, int N);
+int gn_col_dots(const float *dy, int lddy, const float *r, int ldr, int64_t M, int N, void *ws, size_t ws_bytes, double *dots, void *stream);
+
+/* The backward through the batch statistics and the ReLU: g[m][n] = r > 0 ? (float)((a[n] * dy + b[n] * r) + c[n]) : 0, coef[3][N] = (a, b, c) fp64, each
+ * operation in fp64 without contraction, rounded once to fp32 (a NaN in r takes no gradient; g may be dy), and sum_g[N] fp64 = sum_m g (the bias
+ * gradient).  Workspace: ceil(M / GN_LINEAR_ACT_CHUNK_ROWS) * N doubles. */
+size_t gn_bn_train_bwd_workspace_bytes(int64_t M, int N);
+int gn_bn_train_bwd(const float *dy, int lddy, const float *r, int ldr, const double *coef, int64_t M, int N, float *g, int ldg, void *ws, size_t ws_bytes,
+                    double *sum_g, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
