@@ -211,7 +211,8 @@ __global__ __launch_bounds__(256, 2) void sa_fused_kernel(SaArgs p) {
     }
 }
 
-// centres per workgroup.  A row of the edge MLP does not depend on its tile and the maximum not on its order: every G gives the same bits, so G is free to follow
+// centres per workgroup.  A row of the edge MLP does not depend on its tile and the maximum not on its order: every G gives the same bits (asserted for every
+// instantiation and all five groups by tests/test_gpu_pointnet2_forward_edges.py through gn_sa_fused_group), so G is free to follow
 // the launch geometry (round 6): cost(G) = (2 G + 1) / (2 G)  [the self-loop tile's share]  /  fill of the last round of resident workgroups -- 12 000 second-level
 // centres of a batch of 16 in groups of 16 were 750 workgroups on 512 slots (1.46 rounds), in groups of 8 they are 2.93; 750 centres of one garment in groups of
 // 8 were 94 workgroups on 256 CUs.  Resident workgroups per CU from the runtime's occupancy query, once per instantiation.
@@ -232,17 +233,23 @@ static double sa_cost(int M) {
     const double rounds = (double)gn_cdiv((int64_t)n, (int64_t)slots);
     return (2.0 * G + 1.0) / (2.0 * G) * rounds * slots / n;
 }
+// the group the cost rule takes for M centres on the current device
 template <int CIN, int N1, int N2, int N3>
-static int sa_launch(const SaArgs &p, hipStream_t st) {
-    const double c32 = sa_cost<CIN, N1, N2, N3, 32>(p.M), c16 = sa_cost<CIN, N1, N2, N3, 16>(p.M), c8 = sa_cost<CIN, N1, N2, N3, 8>(p.M),
-                 c4 = sa_cost<CIN, N1, N2, N3, 4>(p.M), c2 = sa_cost<CIN, N1, N2, N3, 2>(p.M);
+static int sa_auto_group(int M) {
+    const double c32 = sa_cost<CIN, N1, N2, N3, 32>(M), c16 = sa_cost<CIN, N1, N2, N3, 16>(M), c8 = sa_cost<CIN, N1, N2, N3, 8>(M),
+                 c4 = sa_cost<CIN, N1, N2, N3, 4>(M), c2 = sa_cost<CIN, N1, N2, N3, 2>(M);
     double best = c32;                              // ties go to the larger group (fewer weight re-reads)
     int g = 32;
     if (c16 < best) { best = c16; g = 16; }
     if (c8 < best) { best = c8; g = 8; }
     if (c4 < best) { best = c4; g = 4; }
     if (c2 < best) { best = c2; g = 2; }
-    switch (g) {
+    return g;
+}
+// group: 2, 4, 8, 16 or 32 (the caller's choice, checked by gn_sa_fused_group) or 0 = the cost rule
+template <int CIN, int N1, int N2, int N3>
+static int sa_launch(const SaArgs &p, hipStream_t st, int group) {
+    switch (group ? group : sa_auto_group<CIN, N1, N2, N3>(p.M)) {
         case 32: hipLaunchKernelGGL((sa_fused_kernel<CIN, N1, N2, N3, 32>), dim3((unsigned)gn_cdiv(p.M, 32)), dim3(256), 0, st, p); break;
         case 16: hipLaunchKernelGGL((sa_fused_kernel<CIN, N1, N2, N3, 16>), dim3((unsigned)gn_cdiv(p.M, 16)), dim3(256), 0, st, p); break;
         case 8: hipLaunchKernelGGL((sa_fused_kernel<CIN, N1, N2, N3, 8>), dim3((unsigned)gn_cdiv(p.M, 8)), dim3(256), 0, st, p); break;
@@ -266,13 +273,23 @@ extern "C" int gn_sa_fused_supported(int C, int N1, int N2, int N3) {
     return 0;
 }
 
-extern "C" int gn_sa_fused_scoped(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr,
-                                  const int32_t *cnt, int M, int K, int self_loops, const int32_t *self_src, const float *w1p,
-                                  const float *w2p, const float *w3p, const float *tab, int N1, int N2, int N3, float *out, int ldo,
-                                  void *stream) {
+extern "C" int gn_sa_fused_auto_group(int C, int N1, int N2, int N3, int M) {
+    GN_REQUIRE(M >= 0, "gn_sa_fused_auto_group: bad sizes");
+    GN_REQUIRE(gn_sa_fused_supported(C, N1, N2, N3), "gn_sa_fused_auto_group: edge MLP [%d+3,%d,%d,%d] is not instantiated (see SA_SHAPES in csrc/sa_fused.hip)", C, N1, N2, N3);
+#define SA_AUTO(c, n1, n2, n3) if (C == c && N1 == n1 && N2 == n2 && N3 == n3) return sa_auto_group<c, n1, n2, n3>(M);
+    SA_SHAPES(SA_AUTO)
+#undef SA_AUTO
+    return GN_EINVAL;
+}
+
+extern "C" int gn_sa_fused_group(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr,
+                                 const int32_t *cnt, int M, int K, int self_loops, const int32_t *self_src, const float *w1p,
+                                 const float *w2p, const float *w3p, const float *tab, int N1, int N2, int N3, float *out, int ldo,
+                                 void *stream, int group) {
     GN_REQUIRE(M >= 0 && K > 0 && K <= 64 && ldo >= N3, "gn_sa_fused: bad sizes (the ball-query table holds at most 64 neighbours)");
+    GN_REQUIRE(group == 0 || group == 2 || group == 4 || group == 8 || group == 16 || group == 32, "gn_sa_fused: group %d is not one of 0 (the cost rule), 2, 4, 8, 16, 32", group);
     GN_REQUIRE(gn_sa_fused_supported(C, N1, N2, N3), "gn_sa_fused: edge MLP [%d+3,%d,%d,%d] is not instantiated (see SA_SHAPES in csrc/sa_fused.hip); use gn_sa_gather + gn_linear + gn_segment_max", C, N1, N2, N3);
-    GN_REQUIRE(C == 0 || (x && ldx >= C && (C < 8 || ldx % 4 == 0)), "gn_sa_fused: feature rows need a 16-byte aligned leading dimension");
+    GN_REQUIRE(C == 0 || (x && ldx >= C && (C < 8 || (ldx % 4 == 0 && (uintptr_t)x % 16 == 0))), "gn_sa_fused: feature rows need a 16-byte aligned base and leading dimension");
     if (M == 0) return GN_OK;
     GN_REQUIRE(pos && centre_idx && nbr && cnt && w1p && w2p && w3p && tab && out, "gn_sa_fused: null pointer");
     SaArgs p;
@@ -280,15 +297,22 @@ extern "C" int gn_sa_fused_scoped(const float *x, int ldx, int C, const float *p
     p.self_src = self_src;
     p.w1 = (const float4 *)w1p; p.w2 = (const float4 *)w2p; p.w3 = (const float4 *)w3p; p.tab = tab; p.out = out; p.ldo = ldo;
     hipStream_t st = gn_stream(stream);
-#define SA_DISPATCH(c, n1, n2, n3) if (C == c && N1 == n1 && N2 == n2 && N3 == n3) sa_launch<c, n1, n2, n3>(p, st);
+#define SA_DISPATCH(c, n1, n2, n3) if (C == c && N1 == n1 && N2 == n2 && N3 == n3) sa_launch<c, n1, n2, n3>(p, st, group);
     SA_SHAPES(SA_DISPATCH)
 #undef SA_DISPATCH
     GN_LAUNCH_CHECK("gn_sa_fused");
     return GN_OK;
 }
 
+extern "C" int gn_sa_fused_scoped(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr,
+                                  const int32_t *cnt, int M, int K, int self_loops, const int32_t *self_src, const float *w1p,
+                                  const float *w2p, const float *w3p, const float *tab, int N1, int N2, int N3, float *out, int ldo,
+                                  void *stream) {
+    return gn_sa_fused_group(x, ldx, C, pos, centre_idx, nbr, cnt, M, K, self_loops, self_src, w1p, w2p, w3p, tab, N1, N2, N3, out, ldo, stream, 0);
+}
+
 extern "C" int gn_sa_fused(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr, const int32_t *cnt,
                            int M, int K, int self_loops, const float *w1p, const float *w2p, const float *w3p, const float *tab, int N1, int N2,
                            int N3, float *out, int ldo, void *stream) {
-    return gn_sa_fused_scoped(x, ldx, C, pos, centre_idx, nbr, cnt, M, K, self_loops, nullptr, w1p, w2p, w3p, tab, N1, N2, N3, out, ldo, stream);
+    return gn_sa_fused_group(x, ldx, C, pos, centre_idx, nbr, cnt, M, K, self_loops, nullptr, w1p, w2p, w3p, tab, N1, N2, N3, out, ldo, stream, 0);
 }

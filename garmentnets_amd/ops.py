@@ -181,14 +181,27 @@ def pack_sa_fused(layers):
     return SaFusedPack(packs[0], packs[1], packs[2], torch.cat(tabs).contiguous(), cin, dims)
 
 
-def sa_fused(x, pos, centre_idx, nbr, cnt, pack, self_loops=True, self_src=None):
-    """fps centres + ball-query table -> [M][n3] set-abstraction features (PointConv(local_nn, max) in one kernel, csrc/sa_fused.hip)"""
+def sa_fused(x, pos, centre_idx, nbr, cnt, pack, self_loops=True, self_src=None, group=0, out=None):
+    """fps centres + ball-query table -> [M][n3] set-abstraction features (PointConv(local_nn, max) in one kernel, csrc/sa_fused.hip).
+    group: centres per workgroup, 2 / 4 / 8 / 16 / 32, or 0 = the library's cost rule (every group gives the same bits); out: [M][n3] rows to write"""
     M, K = nbr.shape
-    out = new_rows(M, pack.cout, pos.device)
+    if out is None:
+        out = new_rows(M, pack.cout, pos.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, pack.cout):
+        raise ValueError(f"sa_fused: out must be float32 [{M}][{pack.cout}]")
     ldx = 0 if x is None else rows_view(x)[1]
-    _lib.call("gn_sa_fused_scoped", _p(x), ldx, pack.cin, _p(_chk(pos, torch.float32, "pos")), _p(centre_idx), _p(nbr), _p(cnt), M, K, 1 if self_loops else 0,
-              _p(_chk(self_src, _i32, "self_src") if self_src is not None else None), _p(pack.w1p), _p(pack.w2p), _p(pack.w3p), _p(pack.tab), pack.dims[0], pack.dims[1], pack.dims[2], _p(out), out.stride(0), _stream())
+    _lib.call("gn_sa_fused_group", _p(x), ldx, pack.cin, _p(_chk(pos, torch.float32, "pos")), _p(centre_idx), _p(nbr), _p(cnt), M, K, 1 if self_loops else 0,
+              _p(_chk(self_src, _i32, "self_src") if self_src is not None else None), _p(pack.w1p), _p(pack.w2p), _p(pack.w3p), _p(pack.tab), pack.dims[0], pack.dims[1], pack.dims[2], _p(out), rows_view(out)[1], _stream(),
+              int(group))
     return out
+
+
+def sa_fused_auto_group(cin, dims, M):
+    """the group gn_sa_fused's cost rule takes for M centres of the edge MLP [cin + 3, *dims] on the current device"""
+    g = _lib.load().gn_sa_fused_auto_group(int(cin), int(dims[0]), int(dims[1]), int(dims[2]), int(M))
+    if g <= 0:
+        raise ValueError(f"sa_fused_auto_group: {_lib.load().gn_last_error().decode(errors='replace')}")
+    return g
 
 
 def global_max_pool(h, ptr, B):

@@ -117,6 +117,15 @@ int gn_sa_fused(const float *x, int ldx, int C, const float *pos, const int32_t 
 int gn_sa_fused_scoped(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr, const int32_t *cnt,
                        int M, int K, int self_loops, const int32_t *self_src, const float *w1p, const float *w2p, const float *w3p,
                        const float *tab, int N1, int N2, int N3, float *out, int ldo, void *stream);
+/* gn_sa_fused_scoped with the number of centres per workgroup chosen by the caller: group = 2, 4, 8, 16 or 32 forces that instantiation,
+ * 0 runs the cost rule (what gn_sa_fused and gn_sa_fused_scoped do); anything else is GN_EINVAL before any launch.  Every group gives
+ * the same bits (tests/test_gpu_pointnet2_forward_edges.py); the choice is a matter of speed alone.  x must be 16-byte aligned and ldx a
+ * multiple of 4 when C >= 8 (the rows are read in 16-byte words). */
+int gn_sa_fused_group(const float *x, int ldx, int C, const float *pos, const int32_t *centre_idx, const int32_t *nbr, const int32_t *cnt,
+                      int M, int K, int self_loops, const int32_t *self_src, const float *w1p, const float *w2p, const float *w3p,
+                      const float *tab, int N1, int N2, int N3, float *out, int ldo, void *stream, int group);
+/* the group the cost rule takes for M centres of this edge MLP on the current device (GN_EINVAL: the MLP is not instantiated) */
+int gn_sa_fused_auto_group(int C, int N1, int N2, int N3, int M);
 
 /* out[b][ch] = max over rows ptr[b]..ptr[b+1].  replaces PyG global_max_pool -- components/pointnet2.py:49. */
 int gn_global_max_pool(const float *in, int ldi, const int32_t *ptr, int B, int C, float *out, int ldo, void *stream);

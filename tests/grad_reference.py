@@ -1,5 +1,5 @@
-"""What the gradient GPU suites share (test_gpu_autograd*.py, test_gpu_unet_grad.py, test_gpu_mlp_grad.py): the error rule and the plain-torch
-restatements that more than one of them differentiates.  A plain module, imported by its siblings; it holds no test."""
+"""What the GPU suites share (test_gpu_autograd*.py, test_gpu_unet_grad.py, test_gpu_mlp_grad.py, test_*pointnet2_forward*.py): the error rule and the
+plain restatements that more than one of them uses.  A plain module, imported by its siblings; it holds no test."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -115,3 +115,56 @@ def _randomise_norms(module, g):
                     if m.weight.numel() > 1:
                         m.weight[1] = 0.0
                     first = False
+
+
+# ------------------------------------------------------------------------------------------------ PointNet++ forward (tests/test_*pointnet2_forward*.py)
+def point_conv_slots(nbr, cnt, self_loops, self_src=None):
+    """(M, S) int64 source point of every edge of every centre, -1 = no edge, formed here in numpy from the ball-query table alone: the first cnt[c]
+    entries of row c; with self_loops the entries equal to "node c" (self_src[c], or the centre's own number c) are dropped and node c is appended
+    (PyG: remove_self_loops, then add_self_loops over the M targets).  S = K, + 1 with self_loops."""
+    nbr, cnt = np.asarray(nbr, np.int64), np.asarray(cnt, np.int64)
+    M, K = nbr.shape
+    node = np.arange(M, dtype=np.int64) if self_src is None else np.asarray(self_src, np.int64)
+    slots = np.where(np.arange(K)[None, :] < cnt[:, None], nbr, -1)
+    if self_loops:
+        slots = np.concatenate((np.where(slots == node[:, None], -1, slots), node[:, None]), 1)
+    return slots
+
+
+def r_point_conv(x, pos, centre_idx, nbr, cnt, self_loops, self_src, blocks, dtype):
+    """PointConv(local_nn, aggr = max) restated in plain torch at `dtype`: rows [x_j, pos_j - pos_i] of every edge (x None: the positions alone)
+    through the three blocks (w, b, sc, sh) = Linear -> ReLU -> folded eval-BatchNorm affine (sc None: no BatchNorm), the maximum over a centre's
+    edges, 0 for a centre without any.  Inputs are fp32 data (CPU); the relative position is formed at `dtype`."""
+    slots = torch.from_numpy(point_conv_slots(nbr, cnt, self_loops, self_src))
+    M, S = slots.shape
+    valid = slots >= 0
+    j = slots.clamp(min=0).reshape(-1)
+    ci = centre_idx.long().repeat_interleave(S)
+    p = pos.to(dtype)
+    h = p[j] - p[ci]
+    if x is not None:
+        h = torch.cat((x.to(dtype)[j], h), 1)
+    for w, b, sc, sh in blocks:
+        h = torch.relu(h @ w.to(dtype).t() + b.to(dtype))
+        if sc is not None:
+            h = h * sc.to(dtype) + sh.to(dtype)
+    h = torch.where(valid.reshape(-1, 1), h, torch.full_like(h, -float("inf"))).reshape(M, S, -1).max(1).values
+    return torch.where(torch.isinf(h) & (h < 0), torch.zeros_like(h), h)
+
+
+def ball_query_loop(pos, ptr, centre_idx, centre_ptr, r, K):
+    """the radius query as a numpy loop: per centre the first K points of its own example, in ascending index, whose squared distance -- float32,
+    ((dx dx + dy dy) + dz dz), every operation rounded -- is strictly below float32(r r); -> (nbr (M, K) int32, -1 from cnt on; cnt (M) int32)"""
+    pos = np.ascontiguousarray(pos, np.float32)
+    r2 = np.float32(float(r) * float(r))
+    M = len(centre_idx)
+    nbr, cnt = np.full((M, K), -1, np.int32), np.zeros(M, np.int32)
+    for b in range(len(ptr) - 1):
+        s, e = int(ptr[b]), int(ptr[b + 1])
+        for c in range(int(centre_ptr[b]), int(centre_ptr[b + 1])):
+            d = pos[s:e] - pos[int(centre_idx[c])][None, :]
+            d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            assert d2.dtype == np.float32
+            hit = s + np.nonzero(d2 < r2)[0][:K]
+            nbr[c, :len(hit)], cnt[c] = hit, len(hit)
+    return nbr, cnt
