@@ -334,12 +334,9 @@ class _MaxPool(torch.autograd.Function):
 
 
 def _pool(x):
-    """-> (pooled, its statistics or None): Encoder.run's call of gn_maxpool3d_2 (its epilogue condition, restated: the no-grad test of the GPU suite
-    holds the two to the same bits on a width of either kind)"""
-    c = x.shape[-1]
-    with_stats = c <= 256 and 256 % (c // 4) == 0
-    out, s, q = _MaxPool.apply(x, with_stats)
-    return out, ((s, q, out[0].numel() // c) if with_stats else None)
+    """-> (pooled, its statistics): Encoder.run's call of ops.maxpool3d_2"""
+    out, s, q = _MaxPool.apply(x, True)
+    return out, (s, q, out[0].numel() // x.shape[-1])
 
 
 def max_pool3d_2(x):
@@ -367,12 +364,8 @@ def unet3d(model, x, arith=None):
         _check_gcr(sc)
     arith = arith if arith is not None else model.arith
     if not _needs_grad(model, x):
-        stats = getattr(x, "_gn_stats", None)
-        v = U.stored_volume(x)
-        if v.shape[-1] % 16 != 0:
-            v, stats = U.to_stored(v, (v.shape[-1],), (U.stored_channels(v.shape[-1]),)), None
         with torch.no_grad():
-            return model.run(v, stats, arith=arith).permute(0, 4, 1, 2, 3)
+            return model.run(*U.stored_input(x), arith=arith).permute(0, 4, 1, 2, 3)
     if x.dim() != 5 or x.dtype != torch.float32:
         raise ValueError(f"unet3d: expected a float32 (B, C, D, H, W) volume, got {x.dtype} {tuple(x.shape)}")
     # model.forward's reading of its input: an x that needs no gradient may carry its channel-padded storage and the producer's statistics

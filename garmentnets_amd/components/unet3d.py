@@ -10,6 +10,9 @@ The torch layers only hold parameters.  Execution is channel-last ([B][D][H][W][
                  (components/unet3d.py:291,330) are folded into the loader (second source read at half resolution)
     MaxPool3d  = gn_maxpool3d_2,   final 1x1x1 conv = gn_linear.
 """
+import functools
+from typing import NamedTuple, Optional
+
 import torch
 from torch import nn
 
@@ -53,19 +56,57 @@ def to_stored(v, real, stored):
     return out
 
 
-def _wino_ok(arith, src0, cout):
-    """the layer fits a Winograd F(2,3)-along-x kernel (arith.winograd: csrc/unet_wino.hip for Cout % 128 == 0; arith.winograd32: csrc/unet_wino32.hip for the
-    32- / 64-wide layers).  Decided from the SAMPLE's shape alone, never
-    from the batch size: the Winograd and the direct form round differently, and a garment's result must not depend on how many garments share its
-    batch (the direct kernels may switch variant with the batch size because they are bit-identical to each other)"""
-    _, D, H, W, cin = src0.shape
-    if not (arith.winograd and arith.conv_mode == ops.SPLIT_F16X2 and ops.wino_supported(cin, cout, (D, H, W))):
-        return False
-    if cout % 128 == 0:
-        return (D // 4) * (H // 8) * (W // 8) * (cout // 128) >= 32
-    # the 32-wide column-block kernel (csrc/unet_wino32.hip, round 6): 8 x 8 x 8 tiles; one workgroup per CU walks chains of tiles -- worth it from a
-    # few tiles per CU and sample on (the 64^3 and 128^3 levels of the UNet)
-    return arith.winograd32 and (D // 8) * (H // 8) * (W // 8) * (cout // 32) >= 512
+class AtRest(NamedTuple):
+    """what is known about a layer's src0 behind gn_grid_scatter's volume: away from the scattered cells it holds one value per (sample, channel)"""
+    flat: Optional[torch.Tensor]         # flat cell index of every scattered point; None: the cells are not known (no occupancy-aware launch)
+    reach: int                           # 1: src0 IS the scattered volume; 2: the output of the reach-1 layer (non-constant within one voxel of the cells)
+    value: Optional[torch.Tensor] = None  # [B][C0] the value at rest; None: zero at reach 1 (the scattered volume itself), not known behind it
+    small: Optional[torch.Tensor] = None  # (reach 2) the reach-1 layer's output over its small all-at-rest volume
+
+
+class ConvPlan(NamedTuple):
+    """which launch one 3x3x3 'gcr' convolution takes (conv_plan)"""
+    mode: int        # arith.conv_mode: CONV_FP32 (csrc/unet.hip) or the split-operand mode (csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip)
+    aiw: bool        # operand form: affine-in-weights (ops.conv_affine_pack: exact zeros where the source is at rest) instead of the literal one
+    wino: bool       # kernel family: Winograd F(2,3) along x instead of direct
+    poly: bool       # the upsampled source arrives as a polyphase partial (csrc/upconv.hip); the launch reads the full-resolution source alone
+    small: int       # occupancy-aware launch: the edge of the small all-at-rest volume its border-class constants come from (5 or 8); 0: dense
+
+
+@functools.lru_cache(maxsize=None)      # (pure, of hashable arguments: a layer's plan is decided once per shape and arithmetic, then looked up)
+def conv_plan(arith, dims, c0, c1, cout, reach=0, rest_known=False, small=None, cells=False, rest0=False):
+    """The launch of one 'gcr' layer as a pure function of the arithmetic, the SAMPLE's (D, H, W), the stored widths (c1 = 0: one source) and what is
+    known of src0 at rest -- reach (0: nothing), rest_known (its value there), small (the dims of the previous layer's small output or None), cells
+    (the scattered cells are known); rest0: a decoder's skip connection is at rest.  No tensor, no library entry, never the batch size.
+    Winograd (arith.winograd: csrc/unet_wino.hip for Cout % 128 == 0; arith.winograd32: csrc/unet_wino32.hip for the 32- / 64-wide layers) is decided
+    from the SAMPLE's shape alone, never from the batch size: the Winograd and the direct form round differently, and a garment's result must not
+    depend on how many garments share its batch (the direct kernels may switch variant with the batch size because they are bit-identical to each other)"""
+    mode, (D, H, W) = arith.conv_mode, dims
+    if mode == ops.CONV_FP32:
+        return ConvPlan(mode, False, False, False, 0)
+    # polyphase form of a decoder's first convolution: the nearest-upsampled channels as a 2x2x2-tap convolution per output parity class on the
+    # COARSE volume (8/27 of their MACs, the coarse halo staged once for all classes: csrc/upconv.hip), added in the fine launch's epilogue
+    poly = c1 > 0 and arith.polyphase_upconv and mode != ops.SPLIT_BF16X3 and c1 <= 384
+    # (of a polyphase layer the full-resolution part may run in Winograd form on the 32- / 64-wide layers: csrc/unet_wino32.hip takes the partial
+    #  in its epilogue)
+    wino = (c1 == 0 or (poly and cout % 128 != 0)) and arith.winograd and mode == ops.SPLIT_F16X2 and ops.wino_supported(c0, cout, dims)
+    if wino and cout % 128 == 0:
+        wino = (D // 4) * (H // 8) * (W // 8) * (cout // 128) >= 32
+    elif wino:
+        # the 32-wide column-block kernel (csrc/unet_wino32.hip, round 6): 8 x 8 x 8 tiles; one workgroup per CU walks chains of tiles -- worth it from a
+        # few tiles per CU and sample on (the 64^3 and 128^3 levels of the UNet)
+        wino = arith.winograd32 and (D // 8) * (H // 8) * (W // 8) * (cout // 32) >= 512
+    # affine-in-weights: a single source at rest (0 for the scattered volume, a known value behind it), or a polyphase layer's skip connection
+    aiw = arith.affine_in_weights and mode == ops.SPLIT_F16X2 and c0 % 16 == 0 and cout % 32 == 0
+    aiw = aiw and ((c1 == 0 and (reach == 1 or (reach > 1 and rest_known))) or (poly and rest0))
+    occ = (cells and reach > 0 and arith.sparse_first_conv and c1 == 0 and mode != ops.SPLIT_BF16X3 and c0 <= 384 and (cout % 128 == 0 or cout % 64 != 0)
+           and min(dims) > 2 * reach and (reach == 1 or small is not None)
+           # (a Winograd layer handed a small volume it cannot take -- 5^3, from a layer that ran in the direct form -- simply runs dense.  At reach 2
+           #  the small volume holds the previous layer's face values, the operand is NOT zero there and the two forms round differently: constants
+           #  from the direct pack would break "occupancy-aware == dense, bit for bit" for such mixed configurations)
+           and (not wino or small is None or ops.wino_supported(c0, cout, small)))
+    # (the Winograd kernels take whole tiles, 4 x 8 x 8 / 8 x 8 x 8: 8^3 is their smallest volume, 5^3 the direct kernels')
+    return ConvPlan(mode, bool(aiw), bool(wino), bool(poly), (int(small[0]) if small is not None else 8 if wino else 5) if occ else 0)
 
 
 _ACT = {"r": ("ReLU", lambda: nn.ReLU(inplace=True), ops.ACT_RELU), "l": ("LeakyReLU", lambda: nn.LeakyReLU(negative_slope=0.1, inplace=True), ops.ACT_LEAKY),
@@ -204,120 +245,108 @@ class SingleConv(PackedModule, nn.Sequential):
                 ops.affine_act(y, a=na, d=nd, out=y)
         return y, (ops.channel_stats(y) if with_stats else None)
 
-    def run(self, src0, src1=None, stats0=None, stats1=None, with_stats=True, sparse=None, arith=None, rest0=None):
+    def run(self, src0, src1=None, stats0=None, stats1=None, with_stats=True, arith=None, rest0=None):
         """arith: the arith.Arith of this call (None: arith.DEFAULT).  src0 [B][D][H][W][C0] (full res), src1 [B][D/2][H/2][W/2][C1] or None -> ([B][D][H][W][Cout], output stats).
         stats0/stats1: (sum, sumsq, V) of the inputs when the producing kernel already emitted them.
-        sparse: occupancy-aware launch (split-operand modes), a dict
-            flat      flat cell index of every point gn_grid_scatter scattered into the volume this layer descends from
-            reach     1: src0 IS that volume; 2: src0 is the output of the reach-1 layer (non-constant within one voxel of the cells)
-            small_in  (reach 2) the reach-1 layer's output over the 5 x 5 x 5 all-zero volume; this call adds 'small_out', its own
-            rest_in   (reach 2) [B][C0]: the value src0 holds away from the cells; this call adds 'rest_out', its own output's
-        arith.sparse_first_conv: only the output tiles that can see an occupied cell (within `reach`) go through the matrix cores; the rest
-        are border-class constants taken from a dense launch of this layer over the 5^3 zero volume with the same affine: bit-identical output.
-        arith.affine_in_weights (f16x2): the GroupNorm affine moves into per-sample weights and a bias table (ops.conv_affine_pack), so that
-        the matrix cores multiply exact zeros wherever src0 is at rest -- same MACs, less power, more clock (csrc/conv_prep.hip).
         rest0 [B][C0]: (polyphase form of a decoder layer) the value the skip connection src0 holds away from the cells: its full-resolution
         launch takes the affine-in-weights form as well."""
+        return self._run(src0, src1, stats0, stats1, with_stats, arith, None, rest0)[:2]
+
+    def run_at_rest(self, src0, at_rest, stats0=None, with_stats=True, arith=None):
+        """run() of a single-source layer behind gn_grid_scatter's volume -> (y, output stats, the AtRest of y or None).  at_rest: AtRest (None: run()).
+        arith.sparse_first_conv: only the output tiles that can see an occupied cell (within at_rest.reach) go through the matrix cores; the rest
+        are border-class constants taken from a dense launch of this layer over a small all-at-rest volume with the same affine: bit-identical output.
+        arith.affine_in_weights (f16x2): the GroupNorm affine moves into per-sample weights and a bias table (ops.conv_affine_pack), so that
+        the matrix cores multiply exact zeros wherever src0 is at rest -- same MACs, less power, more clock (csrc/conv_prep.hip).
+        The AtRest handed back carries what this launch learned: its own output's rest value (affine-in-weights form) and its output over the small
+        volume (occupancy-aware launch); None when it learned neither."""
+        return self._run(src0, None, stats0, None, with_stats, arith, at_rest, None)
+
+    def _run(self, src0, src1, stats0, stats1, with_stats, arith, at_rest, rest0):
         arith = arith or AR.DEFAULT
         lay = self._layout(src0, src1)
         if self.order != "gcr":
-            return self._run_generic(src0, src1, stats0, stats1, with_stats, lay)
+            return self._run_generic(src0, src1, stats0, stats1, with_stats, lay) + (None,)
         wp, gamma, beta = self.packed()
         st0 = stats0 if stats0 is not None else ops.channel_stats(src0)
         st1 = None
         if src1 is not None:
             st1 = stats1 if stats1 is not None else ops.channel_stats(src1)
-        if arith.conv_mode == ops.CONV_FP32:
+        cout = self.conv.out_channels if lay is None else lay.cout
+        reach, value, small, flat = (0, None, None, None) if at_rest is None else (at_rest.reach, at_rest.value, at_rest.small, at_rest.flat)
+        plan = conv_plan(arith, tuple(src0.shape[1:4]), src0.shape[-1], 0 if src1 is None else src1.shape[-1], cout, reach, value is not None,
+                         None if small is None else tuple(small.shape[1:4]), flat is not None, rest0 is not None)
+        if plan.mode == ops.CONV_FP32:
             a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta, real=None if lay is None else lay.real)
             if lay is not None:
                 wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
-            r = ops.conv3d_gcr(src0, src1, a, d, wp, self.conv.out_channels if lay is None else lay.cout, relu=True, with_stats=with_stats)
+            r, nxt = ops.conv3d_gcr(src0, src1, a, d, wp, cout, relu=True, with_stats=with_stats), None
         else:
-            r = self._run_split(src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0, lay)
-        return r if with_stats else (r, None)
+            r, nxt = self._run_split(plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay)
+        return (r + (nxt,)) if with_stats else (r, None, nxt)
 
-    def _run_split(self, src0, src1, st0, st1, with_stats, sparse, arith, gamma, beta, rest0, lay=None):
-        """run() on the split-operand kernels (16-bit matrix cores: csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip) in one of two operand forms:
-        literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack).
+    def _run_split(self, plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay=None):
+        """execute a conv_plan on the split-operand kernels (16-bit matrix cores: csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip) in one of two
+        operand forms: literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack) -> (the launch's
+        result, the output's AtRest or None).
         lay: channel-padded storage (_Layout) -- the padded weight and stored widths in every pack, the GroupNorm over the real channels"""
-        gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, arith.conv_mode, src0.shape[-1]
+        gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, plan.mode, src0.shape[-1]
         real = None
         if lay is not None:
             weight, cout, real = self._padded_weight(lay), lay.cout, lay.real
-        aiw = arith.affine_in_weights and mode == ops.SPLIT_F16X2 and c0 % 16 == 0 and cout % 32 == 0
-        # polyphase form of a decoder's first convolution: the nearest-upsampled channels as a 2x2x2-tap convolution per output parity class on the
-        # COARSE volume (8/27 of their MACs, the coarse halo staged once for all classes: csrc/upconv.hip), added in the fine launch's epilogue
-        poly = src1 is not None and arith.polyphase_upconv and mode != ops.SPLIT_BF16X3 and src1.shape[-1] <= 384
-        # (of a polyphase layer the full-resolution part may run in Winograd form on the 32- / 64-wide layers: csrc/unet_wino32.hip takes the partial
-        #  in its epilogue)
-        wino = (src1 is None or (poly and cout % 128 != 0)) and _wino_ok(arith, src0, cout)
         cache, gen = param_cache(self, "_split_packs"), self._gen(lay)
-        part = prep = None
-        if src1 is None and aiw and sparse is not None and (sparse["reach"] == 1 or sparse.get("rest_in") is not None):
-            # affine-in-weights form of a layer whose input is at rest (0 for the scattered volume, sparse['rest_in'] behind it) almost everywhere
+        part = prep = act_inv = rest_out = None
+        if plan.aiw and not plan.poly:
+            # a layer whose input is at rest (0 for the scattered volume, at_rest.value behind it) almost everywhere
             a, d = ops.groupnorm_affine(st0, None, gn.num_groups, gn.eps, gamma, beta, real=real)
-            rest = sparse.get("rest_in") if sparse["reach"] > 1 else None
-            prep = ops.conv_affine_pack(weight if weight.is_contiguous() else weight.contiguous(), a, d, st0, rest, wino=wino)
+            prep = ops.conv_affine_pack(weight if weight.is_contiguous() else weight.contiguous(), a, d, st0, at_rest.value if at_rest.reach > 1 else None,
+                                        wino=plan.wino)
             # away from the cells the operand is zero: the output is ReLU(0 * scale + K[interior]) = ReLU(K[63]) -- the next layer's rest value
-            sparse["rest_out"] = torch.relu(prep.kbias[:, 63]).contiguous()
+            rest_out = torch.relu(prep.kbias[:, 63]).contiguous()
         else:
             # literal form.  fp16 planes: the sample's activations are range-normalised by a power of two (exact, undone in the epilogue)
             if mode == ops.SPLIT_F16X2:
                 a, d, act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True, real=real)
             else:
-                (a, d), act_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real), None
-            if poly:
+                a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real)
+            if plan.poly:
                 def build_poly():
                     w0, wm, _ = ops.polyphase_weights(weight, c0)
                     return (ops.pack_conv_weight_split(w0, mode).to(weight.device), ops.pack_upconv_weight(wm, cout, mode).to(weight.device))
                 pk0, pkm = cache.get(gen, ("poly", mode, c0), build_poly)
                 part = ops.upconv_partial(src1, a[:, c0:].contiguous(), d[:, c0:].contiguous(), pkm, cout, act_inv=act_inv)
-                if rest0 is not None and aiw:
+                if plan.aiw:
                     # the full-resolution part in the affine-in-weights form: the skip connection src0 is at rest away from the cells
                     # (a, d carry the sample's power-of-two activation scale: exact to undo)
                     a0 = (a[:, :c0] * act_inv[:, None]).contiguous()
                     d0 = (d[:, :c0] * act_inv[:, None]).contiguous()
                     w0c = cache.get(gen, ("w0", c0), lambda: weight.detach()[:, :c0].contiguous())
-                    prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=wino)
+                    prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=plan.wino)
                 else:
                     a, d = a[:, :c0].contiguous(), d[:, :c0].contiguous()
                     pack = (cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(weight, c0)[0]).to(weight.device))
-                            if wino else pk0)
-            elif wino:
+                            if plan.wino else pk0)
+            elif plan.wino:
                 pack = cache.get(gen, "wino", lambda: ops.pack_conv_weight_split_wino(weight).to(weight.device))
             else:
                 pack = cache.get(gen, mode, lambda: ops.pack_conv_weight_split(weight, mode).to(weight.device))
         # the one launch tail of each form (a polyphase launch reads the full-resolution source alone: the upsampled channels arrive as the partial)
         if prep is not None:
             launch = lambda x, **kw: ops.conv3d_gcr_split_persample(x, prep, relu=True, **kw)
-        elif wino:
+        elif plan.wino:
             launch = lambda x, **kw: ops.conv3d_gcr_split_wino(x, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
         else:
-            launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if poly else src1, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
-        sp = self._occupancy_aware(src0, src1, sparse, arith, wino, launch, cout)
-        return launch(src0, with_stats=with_stats, partial=part, **sp)
-
-    def _occupancy_aware(self, src0, src1, sparse, arith, wino, launch, cout):
-        """arith.sparse_first_conv: {} (a dense launch), or the keyword arguments of the occupancy-aware launch of a layer behind the scattered
-        volume (tile_active, kconst, kreach).  Its border-class constants come from `launch` -- the kernel AND the pack the real launch takes --
-        over a small all-at-rest volume; this layer's output there goes to sparse['small_out'] for the next layer."""
-        cin = src0.shape[-1]
-        if sparse is None or not arith.sparse_first_conv or src1 is not None or arith.conv_mode == ops.SPLIT_BF16X3:
-            return {}
-        B, reach, small_in = src0.shape[0], int(sparse["reach"]), sparse.get("small_in")
-        if not (cin <= 384 and (cout % 128 == 0 or cout % 64 != 0) and min(src0.shape[1:4]) > 2 * reach and (reach == 1 or small_in is not None)
-                # (a Winograd layer handed a small volume it cannot take -- 5^3, from a layer that ran in the direct form -- simply runs dense.  At reach 2
-                #  the small volume holds the previous layer's face values, the operand is NOT zero there and the two forms round differently: constants
-                #  from the direct pack would break "occupancy-aware == dense, bit for bit" for such mixed configurations)
-                and (not wino or small_in is None or ops.wino_supported(cin, cout, small_in.shape[1:4]))):
-            return {}
-        if small_in is None:
-            n = 8 if wino else 5                  # the Winograd kernels take whole tiles (4 x 8 x 8 / 8 x 8 x 8)
-            small_in = torch.zeros((B, n, n, n, cin), dtype=torch.float32, device=src0.device)
-        small_out = launch(small_in)              # (a plain dense launch)
-        sp = dict(tile_active=ops.grid_tile_flags(sparse["flat"], B, src0.shape[1:4], reach), kconst=_class_constants(small_out, reach, cout), kreach=reach)
-        sparse["small_out"] = small_out
-        return sp
+            launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if plan.poly else src1, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
+        occ, small_out = {}, None
+        if plan.small:
+            # occupancy-aware: the border-class constants come from `launch` -- the kernel AND the pack the real launch takes -- over a small all-at-rest
+            # volume (a plain dense launch); this layer's output there is the next layer's small volume
+            B, n, reach = src0.shape[0], plan.small, at_rest.reach
+            small_out = launch(at_rest.small if at_rest.small is not None else torch.zeros((B, n, n, n, c0), dtype=torch.float32, device=src0.device))
+            occ = dict(tile_active=ops.grid_tile_flags(at_rest.flat, B, src0.shape[1:4], reach), kconst=_class_constants(small_out, reach, cout), kreach=reach)
+        r = launch(src0, with_stats=with_stats, partial=part, **occ)
+        learned = rest_out is not None or small_out is not None
+        return r, (AtRest(at_rest.flat, at_rest.reach + 1, rest_out, small_out) if learned else None)
 
 
 class DoubleConv(nn.Sequential):
@@ -335,19 +364,16 @@ class DoubleConv(nn.Sequential):
             self.SingleConv1.in_real = (c1_in,)
         self.SingleConv2.in_real = (c2_in,)
 
-    def run(self, src0, src1=None, stats0=None, stats1=None, sparse_flat=None, arith=None, info=None, rest0=None):
-        """sparse_flat: src0 is gn_grid_scatter's volume (flat cell index of every scattered point): both convolutions run occupancy-aware /
-        in the affine-in-weights form; info: a dict that receives 'rest_out' [B][Cout], the value the block's output holds away from the
-        cells (when that form ran); rest0: that value for src0 of a decoder block (its skip connection)"""
-        sp1 = dict(flat=sparse_flat, reach=1) if sparse_flat is not None else None
-        y, st = self.SingleConv1.run(src0, src1, stats0, stats1, sparse=sp1, arith=arith, rest0=rest0)
-        sp2 = None
-        if sp1 is not None and ("small_out" in sp1 or "rest_out" in sp1):
-            sp2 = dict(flat=sparse_flat, reach=2, small_in=sp1.get("small_out"), rest_in=sp1.get("rest_out"))
-        r = self.SingleConv2.run(y, None, st, sparse=sp2, arith=arith)
-        if info is not None and sp2 is not None and "rest_out" in sp2:
-            info["rest_out"] = sp2["rest_out"]
-        return r
+    def run(self, src0, src1=None, stats0=None, stats1=None, sparse_flat=None, arith=None, rest0=None):
+        """-> (y, stats, rest_out).  sparse_flat: src0 is gn_grid_scatter's volume (flat cell index of every scattered point): both convolutions run
+        occupancy-aware / in the affine-in-weights form, and rest_out [B][Cout] is the value the block's output holds away from the cells (None when
+        that form did not run); rest0: that value for src0 of a decoder block (its skip connection)"""
+        if sparse_flat is None or src1 is not None:
+            y, st = self.SingleConv1.run(src0, src1, stats0, stats1, arith=arith, rest0=rest0)
+            return self.SingleConv2.run(y, None, st, arith=arith) + (None,)
+        y, st, at_rest = self.SingleConv1.run_at_rest(src0, AtRest(sparse_flat, 1), stats0, arith=arith)
+        y, st, at_rest = self.SingleConv2.run_at_rest(y, at_rest, st, arith=arith)
+        return y, st, (None if at_rest is None else at_rest.value)
 
 
 class Encoder(nn.Module):
@@ -356,15 +382,12 @@ class Encoder(nn.Module):
         self.pooling = nn.MaxPool3d(kernel_size=2) if apply_pooling else None
         self.basic_module = DoubleConv(in_channels, out_channels, encoder=True, order=conv_layer_order, num_groups=num_groups)
 
-    def run(self, x, stats=None, sparse_flat=None, arith=None, info=None):
+    def run(self, x, stats=None, sparse_flat=None, arith=None):
+        """-> (y, stats, rest_out): DoubleConv.run's"""
         if self.pooling is not None:
             sparse_flat = None
-            c = x.shape[-1]
-            if c <= 256 and 256 % (c // 4) == 0:
-                x, stats = ops.maxpool3d_2(x, with_stats=True)
-            else:
-                x, stats = ops.maxpool3d_2(x), None
-        return self.basic_module.run(x, None, stats, sparse_flat=sparse_flat, arith=arith, info=info)
+            x, stats = ops.maxpool3d_2(x, with_stats=True)
+        return self.basic_module.run(x, None, stats, sparse_flat=sparse_flat, arith=arith)
 
 
 class Decoder(nn.Module):
@@ -376,7 +399,7 @@ class Decoder(nn.Module):
 
     def run(self, encoder_features, x, stats_skip=None, stats_x=None, arith=None, skip_rest=None):
         # cat((encoder_features, upsample_nearest(x)), dim=channel) is never materialised
-        return self.basic_module.run(encoder_features, x, stats_skip, stats_x, arith=arith, rest0=skip_rest)
+        return self.basic_module.run(encoder_features, x, stats_skip, stats_x, arith=arith, rest0=skip_rest)[:2]
 
 
 class FinalConv1x1(PackedModule, nn.Conv3d):
@@ -439,9 +462,8 @@ class Abstract3DUNet(nn.Module):
         self.check_input(x)
         feats = []
         for i, enc in enumerate(self.encoders):
-            info = {}
-            x, stats = enc.run(x, stats, sparse_flat=sparse_flat if i == 0 else None, arith=arith, info=info)
-            feats.insert(0, (x, stats, info.get("rest_out")))      # rest_out: encoder 0 behind a scattered volume (affine-in-weights form)
+            x, stats, rest_out = enc.run(x, stats, sparse_flat=sparse_flat if i == 0 else None, arith=arith)
+            feats.insert(0, (x, stats, rest_out))      # rest_out: encoder 0 behind a scattered volume (affine-in-weights form)
         for dec, (skip, skip_stats, skip_rest) in zip(self.decoders, feats[1:]):
             x, stats = dec.run(skip, x, skip_stats, stats, arith=arith, skip_rest=skip_rest)
         if pre_final:       # return_stats: + (sum, sumsq, V) of the pre-final volume (the decoders derive their input scale from it)
@@ -450,11 +472,17 @@ class Abstract3DUNet(nn.Module):
 
     def forward(self, x):
         """x: (B, C, D, H, W) as in the reference; returns (B, C', D, H, W) (a view over channel-last storage)."""
-        stats = getattr(x, "_gn_stats", None)
-        v = stored_volume(x)
-        if v.shape[-1] % 16 != 0:                 # an input width the first convolution does not read as it is: channel-padded, pads 0
-            v, stats = to_stored(v, (v.shape[-1],), (stored_channels(v.shape[-1]),)), None
-        return self.run(v, stats, arith=self.arith).permute(0, 4, 1, 2, 3)
+        return self.run(*stored_input(x), arith=self.arith).permute(0, 4, 1, 2, 3)
+
+
+def stored_input(x):
+    """(B,C,D,H,W) -> (the stored volume run() reads, its statistics or None): stored_volume(x) with the producer's statistics (_gn_stats); an input
+    width the first convolution does not read as it is goes channel-padded, pads 0, and without them"""
+    stats = getattr(x, "_gn_stats", None)
+    v = stored_volume(x)
+    if v.shape[-1] % 16 != 0:
+        v, stats = to_stored(v, (v.shape[-1],), (stored_channels(v.shape[-1]),)), None
+    return v, stats
 
 
 def stored_volume(x):

@@ -875,7 +875,7 @@ def test_conv3d_winograd32_shape_contract_and_occupancy_aware_launch():
     """(1) shapes outside the 32-wide Winograd kernel's contract are refused with GN_EINVAL (ValueError), never run; (2) its occupancy-aware launch (active
     list at the kernel's 8 x 8 x 8 granularity + border-class constants from its own dense launch over the 8^3 at-rest volume) is bit-identical to its
     dense launch, through SingleConv.run behind a scattered volume (reach 1)"""
-    from garmentnets_amd.components.unet3d import SingleConv
+    from garmentnets_amd.components.unet3d import AtRest, SingleConv
     w = torch.randn(32, 32, 3, 3, 3)
     pk = ops.pack_conv_weight_split_wino(w).to(DEV)
     ones = lambda B, C: (torch.ones(B, C, device=DEV), torch.zeros(B, C, device=DEV))
@@ -897,12 +897,12 @@ def test_conv3d_winograd32_shape_contract_and_occupancy_aware_launch():
     flat = torch.cat([((b * G + idx[b, :, 0]) * G + idx[b, :, 1]) * G + idx[b, :, 2] for b in range(B - 1)]).to(torch.int32).to(DEV)
     xg = x.to(DEV)
     ar = AR.DEFAULT.replace(conv_mode=AR.SPLIT_F16X2, affine_in_weights=True, winograd=True, winograd32=True)
-    y_d, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=False))
+    y_d, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=False))
     assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_wino32pc_kernel<true>"
-    y_s, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=True))
+    y_s, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=True))
     assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_wino32pc_kernel<true>"
     assert torch.equal(y_s, y_d) and bool(torch.isfinite(y_d).all()) and float(y_d.abs().max()) > 0
-    y_strip, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=False, winograd32=False))
+    y_strip, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=False, winograd32=False))
     assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_strip_kernel<true>"
     assert float((y_strip - y_d).abs().max()) <= 2e-5 * max(1.0, float(y_d.abs().max()))       # two fp32-class roundings of the same layer
 
@@ -911,7 +911,7 @@ def test_conv3d_winograd_occupancy_aware_launch_and_shape_contract():
     """(1) the occupancy-aware launch of the Winograd kernel (active-tile list + border-class constants from the DIRECT form's 5^3 launch: away from
     the cells the operand is exactly zero in either form) is bit-identical to its dense launch; (2) shapes outside the kernel's contract are
     refused with GN_EINVAL (ValueError), never run"""
-    from garmentnets_amd.components.unet3d import SingleConv
+    from garmentnets_amd.components.unet3d import AtRest, SingleConv
     g = torch.Generator().manual_seed(21)
     B, G, C = 4, 32, 32
     conv = SingleConv(C, 128).to(DEV)
@@ -924,12 +924,12 @@ def test_conv3d_winograd_occupancy_aware_launch_and_shape_contract():
     flat = torch.cat([((b * G + idx[b, :, 0]) * G + idx[b, :, 1]) * G + idx[b, :, 2] for b in range(B - 1)]).to(torch.int32).to(DEV)
     xg = x.to(DEV)
     ar = AR.DEFAULT.replace(conv_mode=AR.SPLIT_F16X2, affine_in_weights=True, winograd=True)
-    y_d, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=False))
+    y_d, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=False))
     assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_wino_kernel<true>"
-    y_s, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=True))
+    y_s, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=True))
     assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_wino_kernel<true>"
     assert torch.equal(y_s, y_d) and bool(torch.isfinite(y_d).all()) and float(y_d.abs().max()) > 0
-    y_direct, _ = conv.run(xg, None, sparse=dict(flat=flat, reach=1), arith=ar.replace(sparse_first_conv=False, winograd=False))
+    y_direct, _, _ = conv.run_at_rest(xg, AtRest(flat, 1), arith=ar.replace(sparse_first_conv=False, winograd=False))
     assert float((y_direct - y_d).abs().max()) <= 2e-5 * max(1.0, float(y_d.abs().max()))
     # shape contract
     w = torch.randn(128, 32, 3, 3, 3, generator=g) * 0.05
@@ -949,7 +949,7 @@ def test_conv3d_winograd_chain_length_does_not_change_a_bit(monkeypatch):
     that cross from one sample into the next: the drain-and-restart path; Cout = 256: two column blocks interleaved in the item order), 16 --
     for the literal form, the per-sample packs and the occupancy-aware (active-list) launch; the statistics agree to fp64 rounding (they are
     merged by fp64 atomics in whatever order the hardware schedules them, as in every launch of these kernels)."""
-    from garmentnets_amd.components.unet3d import SingleConv
+    from garmentnets_amd.components.unet3d import AtRest, SingleConv
     g = torch.Generator().manual_seed(77)
     cases = []
     # (Cout = 32 / 64: the 32-wide column-block kernel of round 6, csrc/unet_wino32.hip -- the same chain machinery at its 8 x 8 x 8 tile granularity)
@@ -978,7 +978,7 @@ def test_conv3d_winograd_chain_length_does_not_change_a_bit(monkeypatch):
         for x, a, d, inv, pk, prep, Cout in cases:
             out.append(ops.conv3d_gcr_split_wino(x, a, d, pk, Cout, act_inv=inv, with_stats=True))
             out.append(ops.conv3d_gcr_split_persample(x, prep, with_stats=True))
-        out.append(conv.run(xs, None, sparse=dict(flat=flat, reach=1), arith=ar, with_stats=True))
+        out.append(conv.run_at_rest(xs, AtRest(flat, 1), arith=ar, with_stats=True)[:2])
         assert ops._lib.load().gn_last_kernel().decode() == "conv3d_split_wino_kernel<true>"
         return out
 
@@ -1539,7 +1539,7 @@ def test_sparse_first_conv_is_bit_identical_to_dense(G, mode, aiw):
     border-class constants (csrc/unet_split.hip tile_active / kconst / kreach).  Both outputs must equal the dense launches bit for
     bit (the epilogue statistics up to the order of their fp64 atomics): occupied cells in corners / on faces / in the interior, a
     garment without any point, a grid that is not a multiple of the tile."""
-    from garmentnets_amd.components.unet3d import DoubleConv
+    from garmentnets_amd.components.unet3d import AtRest, DoubleConv
     g = torch.Generator().manual_seed(G)
     B, C = 3, 128
     cells = [torch.tensor([[0, 0, 0], [G - 1, G - 1, G - 1], [0, G - 1, 5], [G // 2, G // 2, G // 2], [G // 2, G // 2, G // 2 + 1], [3, 8, 9], [4, 7, 8]]),
@@ -1555,20 +1555,18 @@ def test_sparse_first_conv_is_bit_identical_to_dense(G, mode, aiw):
     # the occupancy-aware launch must equal ITS dense launch bit for bit just the same
     a_sp = AR.DEFAULT.replace(conv_mode=mode, sparse_first_conv=True, affine_in_weights=aiw)
     a_dn = a_sp.replace(sparse_first_conv=False)
-    sp1 = dict(flat=flat.to(DEV), reach=1)
-    y1_s, st1_s = dc.SingleConv1.run(vol, None, stats, None, sparse=sp1, arith=a_sp)
-    assert ("rest_out" in sp1) == aiw
-    y2_s, st2_s = dc.SingleConv2.run(y1_s, None, st1_s, sparse=dict(flat=flat.to(DEV), reach=2, small_in=sp1["small_out"], rest_in=sp1.get("rest_out")),
-                                     arith=a_sp)
-    both_s, _ = dc.run(vol, None, stats, None, sparse_flat=flat.to(DEV), arith=a_sp)
-    d1 = dict(flat=flat.to(DEV), reach=1)
-    y1_d, st1_d = dc.SingleConv1.run(vol, None, stats, None, sparse=d1, arith=a_dn)
-    assert "small_out" not in d1
+    y1_s, st1_s, sp2 = dc.SingleConv1.run_at_rest(vol, AtRest(flat.to(DEV), 1), stats, arith=a_sp)
+    assert sp2.reach == 2 and sp2.small is not None and (sp2.value is not None) == aiw       # rest value reported <=> affine-in-weights ran
+    y2_s, st2_s, _ = dc.SingleConv2.run_at_rest(y1_s, sp2, st1_s, arith=a_sp)
+    both_s, _, both_rest = dc.run(vol, None, stats, None, sparse_flat=flat.to(DEV), arith=a_sp)
+    assert (both_rest is not None) == aiw
+    y1_d, st1_d, d2 = dc.SingleConv1.run_at_rest(vol, AtRest(flat.to(DEV), 1), stats, arith=a_dn)
+    assert (d2 is not None) == aiw and (d2 is None or (d2.small is None and d2.value is not None))          # no small volume when dense
     # (layer 2's GroupNorm affine from the SAME statistics in both forms: the two launches' fp64 atomic sums agree to 1 ulp only, which
     #  once in a while lands on the other side of an fp32 rounding boundary of the affine -- that is the atomics' order, not the kernels)
-    y2_d, st2_d = dc.SingleConv2.run(y1_d, None, st1_s, sparse=dict(flat=flat.to(DEV), reach=2, rest_in=d1.get("rest_out")), arith=a_dn)
+    y2_d, st2_d, _ = dc.SingleConv2.run_at_rest(y1_d, d2, st1_s, arith=a_dn)
     if aiw:            # the garment without a point is at rest everywhere: every interior voxel of layer 1's output IS the rest value
-        assert torch.equal(y1_d[1, 3, 4, 5], d1["rest_out"][1]) and torch.equal(y1_d[1, G // 2, G // 2, G // 2], d1["rest_out"][1])
+        assert torch.equal(y1_d[1, 3, 4, 5], d2.value[1]) and torch.equal(y1_d[1, G // 2, G // 2, G // 2], d2.value[1])
     f1, f2 = ops.grid_tile_flags(flat.to(DEV), B, (G, G, G), 1), ops.grid_tile_flags(flat.to(DEV), B, (G, G, G), 2)
     a1, a2 = f1.sum(dim=1).tolist(), f2.sum(dim=1).tolist()
     print(f"G={G} mode={mode}: active tiles per garment, layer 1 {a1} / layer 2 {a2} of {f1.shape[1]}")
@@ -1591,7 +1589,7 @@ def test_affine_in_weights_conv_against_fp64(Cin, Cout, dims, B, kind):
     (c = 0), on a volume at a per-channel offset with a few cells disturbed (c = that offset) and on dense noise (c = 0, nothing at
     rest), against torch in fp64 and against the standard f16x2 form.  Shapes chosen to reach every kernel variant (128-wide, 64-wide,
     x-strip, 32-wide with ragged tiles)."""
-    from garmentnets_amd.components.unet3d import SingleConv
+    from garmentnets_amd.components.unet3d import AtRest, SingleConv
     g = torch.Generator().manual_seed(Cin * 7 + Cout + dims[0])
     D, H, W = dims
     rest = None
@@ -1615,12 +1613,11 @@ def test_affine_in_weights_conv_against_fp64(Cin, Cout, dims, B, kind):
                           conv.conv.weight.double(), None, padding=1)).permute(0, 2, 3, 4, 1)
     conv = conv.to(DEV)
     xg = x.to(DEV)
-    fake_flat = torch.zeros((1,), dtype=torch.int32, device=DEV)
     a_new = AR.DEFAULT.replace(conv_mode=4, sparse_first_conv=False, affine_in_weights=True)
-    sp = dict(flat=fake_flat, reach=1) if rest is None else dict(flat=fake_flat, reach=2, rest_in=rest.to(DEV))
-    y_new, (s_new, q_new, V) = conv.run(xg, None, sparse=sp, arith=a_new)
+    sp = AtRest(None, 1) if rest is None else AtRest(None, 2, rest.to(DEV))          # (the cells are not known: the rest value alone)
+    y_new, (s_new, q_new, V), nxt = conv.run_at_rest(xg, sp, arith=a_new)
     kern = ops._lib.load().gn_last_kernel().decode()
-    assert "rest_out" in sp
+    assert nxt is not None and nxt.value is not None and nxt.small is None
     y_old, (s_old, q_old, _) = conv.run(xg, None, arith=a_new.replace(affine_in_weights=False))
     scale = float(ref.abs().max())
     e_new, e_old = float((y_new.cpu().double() - ref).abs().max()), float((y_old.cpu().double() - ref).abs().max())
@@ -1631,7 +1628,7 @@ def test_affine_in_weights_conv_against_fp64(Cin, Cout, dims, B, kind):
     assert float((q_new.cpu() - (y_new.double() ** 2).sum(dim=(1, 2, 3)).cpu()).abs().max()) <= 1e-9 * max(1.0, float(q_new.abs().max()))
     if kind != "dense" and min(dims) >= 12:
         # a garment at rest: interior voxels hold exactly the rest value this layer reports for the next one
-        assert torch.equal(y_new[B - 1, D // 2, H // 2, W // 2], sp["rest_out"][B - 1])
+        assert torch.equal(y_new[B - 1, D // 2, H // 2, W // 2], nxt.value[B - 1])
     assert bool(torch.isfinite(y_new).all())
 
 
