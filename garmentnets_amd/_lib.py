@@ -95,6 +95,9 @@ PROTOTYPES = {
     "gn_nocs_bin_metrics": [_vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
     "gn_value_losses_workspace_bytes": [_vp, _i32],
     "gn_value_losses": [_vp, _i32, _vp, _sz, _vp, _vp],
+    "gn_nocs_bin_loss_bwd": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "gn_value_losses_bwd": [_vp, _i32, _vp, _vp, _vp],
+    "gn_adam_step": [_vp, _i32, _i64, _vp, _i32, _vp],
     "gn_grid_scatter_bwd_workspace_bytes": [_i64, _i32, _i64, _i32],
     "gn_grid_scatter_bwd": [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _i32, _vp],
     "gn_segment_max_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
@@ -149,6 +152,31 @@ class NocsBinSet(ctypes.Structure):
 class LossSegment(ctypes.Structure):
     """GnLossSegment (host table entry of gn_value_losses)"""
     _fields_ = [("pred", _vp), ("target", _vp), ("count", _i64), ("kind", _i32), ("mirror", _i32)]
+
+
+class NocsBinGradSet(ctypes.Structure):
+    """GnNocsBinGradSet (host table entry of gn_nocs_bin_loss_bwd)"""
+    _fields_ = [("logits", _vp), ("gt", _vp), ("grad", _vp), ("n", _i64), ("ldl", _i32), ("ldg", _i32), ("ncols", _i32), ("pad", _i32)]
+
+
+class LossGradSegment(ctypes.Structure):
+    """GnLossGradSegment (host table entry of gn_value_losses_bwd)"""
+    _fields_ = [("pred", _vp), ("target", _vp), ("grad", _vp), ("count", _i64), ("coef", _f64), ("kind", _i32), ("mirror", _i32)]
+
+
+ADAM_CHUNK = 4096                               # GN_ADAM_CHUNK
+ADAM_MAX_HYPER = 16                             # GN_ADAM_MAX_HYPER
+
+
+class AdamEntry(ctypes.Structure):
+    """GnAdamEntry (DEVICE table entry of gn_adam_step)"""
+    _fields_ = [("p", _vp), ("g", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("numel", _i64), ("blk0", _i64), ("hyper", _i32), ("pad", _i32)]
+
+
+class AdamHyper(ctypes.Structure):
+    """GnAdamHyper (host scalars of gn_adam_step)"""
+    _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64), ("bias_correction1", _f64),
+                ("bias_correction2_sqrt", _f64)]
 
 
 _lib = None

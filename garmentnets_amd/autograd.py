@@ -18,9 +18,12 @@ gradient flows from a torch loss on the decoder's prediction to every parameter 
 ``mlp(..., batch_stats=True)`` gives a BatchNorm in training mode torch's semantics: the batch's own mean and biased variance over all rows, the
 gradient through both, the running buffers updated in place (DESIGN.md "Train-mode BatchNorm").
 
-What this is NOT: a training loop, an optimiser, gradients of the loss kernels (csrc/losses.hip: torch's own losses close the
-chain), or a backward for the fused inference kernels (the fused / split-operand decoder, ``gn_sa_fused``: ``implicit_decode`` and ``point_conv_max``
-are the unfused chains).  The inference modules do not import this file.
+``nocs_bin_loss`` / ``value_loss`` close the chain: the forward is the validation kernels of csrc/losses.hip, unchanged (the loss value is
+``validation_metrics``' to the last bit), the backward their gradient kernels, which take the mirror decision on the device from the forward's own
+sums.  The optimiser is optim.FusedAdam, the first stage's training step train.py (DESIGN.md "Training step, first stage").
+
+What this is NOT: the second stage's training step, or a backward for the fused inference kernels (the fused / split-operand decoder,
+``gn_sa_fused``: ``implicit_decode`` and ``point_conv_max`` are the unfused chains).  The inference modules do not import this file.
 
 Selections (max / min) hand the gradient to ONE element per (slot, channel): among equal values the lowest point / edge index (torch_scatter's CUDA
 choice is whichever thread wins an atomic: parity unpinned).  Every sum is ordered: identical calls give identical bits.
@@ -35,7 +38,7 @@ from .components.mlp import HipLinear, MLPStack, fold_batchnorm, pack_linear, pa
 from .components.pointnet2 import Segments, _example_self_src
 
 __all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
-           "conv3d_gcr", "max_pool3d_2", "unet3d", "mlp", "linear", "implicit_decode"]
+           "conv3d_gcr", "max_pool3d_2", "unet3d", "mlp", "linear", "implicit_decode", "nocs_bin_loss", "value_loss"]
 
 
 # ------------------------------------------------------------------------------------------------ index results (no gradient)
@@ -99,11 +102,13 @@ class _SegmentMax(torch.autograd.Function):
         return ops.segment_max_bwd(grad_out, out, h, slot_src, *ctx.ms), None, None, None
 
 
-def point_conv_max(x, pos, centre_idx, nbr, local_nn, add_self_loops=True, self_loop_scope="batch", batch=None, batch_centre=None):
+def point_conv_max(x, pos, centre_idx, nbr, local_nn, add_self_loops=True, self_loop_scope="batch", batch=None, batch_centre=None, real_edges=False):
     """PointConv(local_nn, aggr='max') over the radius graph ``nbr`` (``ball_table``): edge rows [x_j, pos_j - pos_i] -> ``local_nn`` (any
     nn.Module, torch's own backward) -> max per centre.  Differentiable in x and in local_nn's parameters; positions are data.  The unfused chain
     gn_sa_gather + local_nn + gn_segment_max.  self_loop_scope="example" (needs batch / batch_centre): the self-loop rule per example, as
-    components.pointnet2.SAModule applies it."""
+    components.pointnet2.SAModule applies it.  real_edges=True: ``local_nn`` sees the rows of real edges only (PyG's edge set: the empty slots of the
+    table are indexed out with torch and the result copied back into a zero buffer, whose empty rows gn_segment_max never reads), so a training
+    BatchNorm inside it takes its statistics over exactly PyG's rows."""
     centre_idx = centre_idx.to(torch.int32)
     M, K = nbr.shape
     S = K + (1 if add_self_loops else 0)
@@ -117,7 +122,12 @@ def point_conv_max(x, pos, centre_idx, nbr, local_nn, add_self_loops=True, self_
         edges, slot_src, _ = ops.sa_gather(None, pos, centre_idx, nbr, self_loops=add_self_loops, self_src=self_src)
     else:
         edges, slot_src = _SaGather.apply(ops.fp32_rows(x, "x"), pos, centre_idx, nbr, add_self_loops, self_src)
-    h = local_nn(edges) if local_nn is not None else edges
+    if real_edges and local_nn is not None:
+        rows = (slot_src >= 0).nonzero().squeeze(1)
+        hc = local_nn(edges.index_select(0, rows))
+        h = hc.new_zeros((M * S, hc.shape[1])).index_copy(0, rows, hc)
+    else:
+        h = local_nn(edges) if local_nn is not None else edges
     return _SegmentMax.apply(ops.fp32_rows(h, "local_nn(edges)"), slot_src, M, S)
 
 
@@ -615,3 +625,92 @@ def implicit_decode(decoder, features_grid, query_points, batch_stats=False):
     if not isinstance(decoder, ImplicitWNFDecoder):
         raise TypeError(f"implicit_decode: expected a networks.conv_implicit_wnf.ImplicitWNFDecoder, got {type(decoder).__name__}")
     return mlp(decoder.mlp, grid_sample_points(features_grid, query_points.float()), batch_stats=batch_stats)
+
+
+# ------------------------------------------------------------------------------------------------ the losses
+def _weighted_mean_loss(sums, col, weights, counts):
+    """sum_s weights[s] * (sums[s][col] / counts[s]) in fp64 on the device, left to right: validation_metrics' own expression"""
+    dev = sums.device
+    terms = torch.tensor([float(w) for w in weights], dtype=torch.float64, device=dev) * \
+        (sums[:, col] / torch.tensor([float(c) for c in counts], dtype=torch.float64, device=dev))
+    total = terms[0]
+    for s in range(1, terms.shape[0]):
+        total = total + terms[s]
+    return total
+
+
+class _NocsBinLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bins, mirror_axis, weights, gts, *logits):
+        sets = list(zip(logits, gts))
+        sums = ops.nocs_bin_metrics(sets, bins, mirror_axis)
+        counts = [lg.shape[0] * 3 for lg in logits]
+        loss = _weighted_mean_loss(sums, 0, weights, counts)
+        if mirror_axis is not None:                # the whole batch takes the smaller weighted loss (plain when equal)
+            loss = torch.minimum(loss, _weighted_mean_loss(sums, 1, weights, counts))
+        ctx.save_for_backward(sums, *logits)
+        ctx.gts, ctx.cfg = gts, (bins, mirror_axis, weights)
+        ctx.mark_non_differentiable(sums)
+        return loss.float(), sums
+
+    @staticmethod
+    def backward(ctx, grad_loss, _):
+        sums, *logits = ctx.saved_tensors
+        bins, mirror_axis, weights = ctx.cfg
+        grads = ops.nocs_bin_loss_bwd(list(zip(logits, ctx.gts)), bins, mirror_axis, sums, weights, grad_loss.float())
+        return (None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+
+
+def nocs_bin_loss(sets, bins, mirror_axis=None, weights=None):
+    """The binned NOCS loss of PointNet2NOCS (cross entropy at VirtualGrid's target bins) over 1..8 row sets sets = [(logits (N, >= bins*3) fp32, gt
+    (N, 3))]: loss = sum_s weights[s] * CE_s / (3 n_s); with a mirror_axis the whole batch takes the mirrored targets iff that weighted loss is strictly
+    smaller (``validation_metrics``' rule).  -> (loss, sums): loss a device fp32 scalar that autograd tracks, built from the fp64 sums as
+    ``validation_metrics`` builds its "loss" and cast once; sums the detached (nsets, 4) fp64 result of gn_nocs_bin_metrics.  Forward: that kernel,
+    unchanged.  Backward: gn_nocs_bin_loss_bwd -- the branch is decided on the device from the sums, nothing is read back."""
+    weights = [1.0] * len(sets) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(sets):
+        raise ValueError(f"nocs_bin_loss: {len(sets)} sets but {len(weights)} weights")
+    for logits, _ in sets:
+        _fp32_features(logits, "nocs_bin_loss")
+    gts = tuple(gt.detach() for _, gt in sets)
+    return _NocsBinLoss.apply(int(bins), mirror_axis, tuple(weights), gts, *[lg for lg, _ in sets])
+
+
+class _ValueLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kinds, weights, targets, *preds):
+        segs = [(p, t) + k for p, t, k in zip(preds, targets, kinds)]
+        sums = ops.value_losses(segs)
+        best = torch.where(torch.tensor([k[1] for k in kinds], device=sums.device), torch.minimum(sums[:, 0], sums[:, 1]), sums[:, 0])
+        loss = _weighted_mean_loss(best[:, None], 0, weights, [p.numel() for p in preds])
+        ctx.save_for_backward(sums, *preds)
+        ctx.targets, ctx.cfg = targets, (kinds, weights)
+        ctx.mark_non_differentiable(sums)
+        return loss.float(), sums
+
+    @staticmethod
+    def backward(ctx, grad_loss, _):
+        sums, *preds = ctx.saved_tensors
+        kinds, weights = ctx.cfg
+        grads = ops.value_losses_bwd([(p, t) + k for p, t, k in zip(preds, ctx.targets, kinds)], sums, weights, grad_loss.float())
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+def value_loss(segments, weights=None):
+    """Mean-reduced element-wise losses over 1..8 segments = [(pred, target, kind[, mirror])], kind "l2" | "smooth_l1" | "bce_logits" (torch's
+    F.mse_loss / smooth_l1_loss / binary_cross_entropy_with_logits): loss = sum_s weights[s] * sum_s / count_s, where a mirrored segment of (M, 3)
+    rows takes the sum against its x-mirrored target when that is strictly smaller (MirrorMSELoss, decided per segment).  "row_norm" is a metric, not
+    a loss: ValueError.  -> (loss, sums) as ``nocs_bin_loss``: forward gn_value_losses, unchanged; backward gn_value_losses_bwd, the mirror choice
+    taken on the device."""
+    weights = [1.0] * len(segments) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(segments):
+        raise ValueError(f"value_loss: {len(segments)} segments but {len(weights)} weights")
+    kinds = []
+    for seg in segments:
+        if seg[2] == "row_norm":
+            raise ValueError("value_loss: row_norm is a metric, not a loss: it has no gradient")
+        if seg[2] not in ("l2", "smooth_l1", "bce_logits"):
+            raise ValueError(f"value_loss: loss kind {seg[2]!r}: expected one of 'l2', 'smooth_l1', 'bce_logits'")
+        _fp32_features(seg[0], "value_loss")
+        kinds.append((seg[2], bool(seg[3]) if len(seg) > 3 else False))
+    return _ValueLoss.apply(tuple(kinds), tuple(weights), tuple(seg[1].detach() for seg in segments), *[seg[0] for seg in segments])

@@ -106,10 +106,11 @@ class PointConv(torch.nn.Module):
 class SAModule(torch.nn.Module):
     """fps -> ball query (<=64, first in index order) -> PointConv(local_nn, max) -- components/pointnet2.py:22-33."""
 
-    def __init__(self, ratio, r, nn, random_start=False):
+    def __init__(self, ratio, r, nn, random_start=False, max_num_neighbors=64):
         super().__init__()
         self.ratio = ratio
         self.r = r
+        self.max_num_neighbors = max_num_neighbors     # the reference's radius(..., max_num_neighbors=64); 1..64
         self.conv = PointConv(nn)
         # torch_cluster.fps defaults to random_start=True (the reference is therefore non-deterministic); the build pins
         # False (first point of each example) and exposes the upstream behaviour as a flag.
@@ -131,7 +132,7 @@ class SAModule(torch.nn.Module):
             if src is not None and src[1] == seg.sizes and src[2] == pos._version and src[0].device == pos.device:
                 nested = src[0]
         idx = ops.fps(pos, seg.ptr, cseg.ptr, max(seg.sizes) if seg.sizes else 0, cseg.total, start, gap_out=gap, nested_gap=nested)
-        nbr, cnt = ops.ball_query(pos, seg.ptr, idx, cseg.ptr, self.r, 64)
+        nbr, cnt = ops.ball_query(pos, seg.ptr, idx, cseg.ptr, self.r, self.max_num_neighbors)
         pack = self._fused_pack() if FUSED_SA else None
         self_src = None
         if self.conv.add_self_loops and self.conv.self_loop_scope == "example" and seg.num > 1:

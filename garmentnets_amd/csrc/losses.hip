@@ -295,3 +295,175 @@ extern "C" int gn_value_losses(const GnLossSegment *segs_host, int nsegs, void *
     GN_LAUNCH_CHECK("gn_value_losses");
     return GN_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ loss gradients
+// The backward of the two launches above, for a training step (garmentnets_amd/autograd.py nocs_bin_loss / value_loss).  Each reads the fp64 sums the
+// forward left on the device and takes the mirror decision there: every thread evaluates the same fp64 comparison, so no host branch sits between the
+// forward and the backward.  Every output element is written exactly once with a plain store: identical calls give identical bits.
+struct NocsGradArg {
+    const float *logits[GN_LOSS_MAX_SETS];
+    const float *gt[GN_LOSS_MAX_SETS];
+    float *grad[GN_LOSS_MAX_SETS];
+    int64_t n[GN_LOSS_MAX_SETS];
+    double coef[GN_LOSS_MAX_SETS];     // weight_s / (3 n_s)
+    double weight[GN_LOSS_MAX_SETS];
+    int ldl[GN_LOSS_MAX_SETS];
+    int ldg[GN_LOSS_MAX_SETS];
+    int ncols[GN_LOSS_MAX_SETS];
+    int blk0[GN_LOSS_MAX_SETS + 1];
+    int nsets;
+};
+
+// validation_metrics' rule: loss_c = w_0 * (sum_0c / (3 n_0)) + w_1 * (sum_1c / (3 n_1)) + ... in fp64, left to right; the WHOLE batch takes the mirrored
+// targets iff the mirrored loss is strictly smaller (plain when equal)
+__device__ __forceinline__ bool nocs_take_mirror(const NocsGradArg &a, const double *__restrict__ sums) {
+    double plain = 0.0, mirrored = 0.0;
+    for (int s = 0; s < a.nsets; ++s) {
+        const double d = (double)(a.n[s] * 3);
+        const double tp = a.weight[s] * (sums[s * 4] / d), tm = a.weight[s] * (sums[s * 4 + 1] / d);
+        plain = s == 0 ? tp : plain + tp;
+        mirrored = s == 0 ? tm : mirrored + tm;
+    }
+    return mirrored < plain;
+}
+
+// one thread per (row, axis): the forward's max-subtracted softmax (the sum of the fp32 exponentials kept in fp64), minus the one-hot of the target bin
+__global__ __launch_bounds__(LOSS_WG) void nocs_bin_loss_bwd_kernel(NocsGradArg a, int bins, int mirror_axis, const double *__restrict__ sums,
+                                                                    const float *__restrict__ upstream) {
+    const int s = loss_set_of(a.blk0, a.nsets, blockIdx.x);
+    const int64_t i = (int64_t)(blockIdx.x - a.blk0[s]) * LOSS_WG + threadIdx.x;
+    if (i >= a.n[s] * 3) return;
+    const int64_t r = i / 3;
+    const int ax = (int)(i - r * 3);
+    const float *row = a.logits[s] + r * a.ldl[s];
+    float *g = a.grad[s] + r * a.ldg[s];
+    const bool mir = mirror_axis >= 0 && nocs_take_mirror(a, sums);
+    float gt = a.gt[s][r * 3 + ax];
+    if (mir && ax == mirror_axis) gt = nocs_mirror(gt);
+    const int t = nocs_bin_of(gt, bins);
+    float mx = row[ax];
+    for (int k = 1; k < bins; ++k) {
+        const float x = row[k * 3 + ax];
+        if (x > mx) mx = x;
+    }
+    double sum = 0.0;
+    for (int k = 0; k < bins; ++k) sum += (double)expf(__fsub_rn(row[k * 3 + ax], mx));
+    const double scale = a.coef[s] * (double)upstream[0];
+    for (int k = 0; k < bins; ++k) {
+        const double p = (double)expf(__fsub_rn(row[k * 3 + ax], mx)) / sum;
+        g[k * 3 + ax] = (float)((p - (k == t ? 1.0 : 0.0)) * scale);
+    }
+    if (ax == 0)
+        for (int c = bins * 3; c < a.ncols[s]; ++c) g[c] = 0.0f;      // the pad columns of a padded row
+}
+
+struct SegsGradArg {
+    const float *pred[GN_LOSS_MAX_SETS];
+    const float *target[GN_LOSS_MAX_SETS];
+    float *grad[GN_LOSS_MAX_SETS];
+    int64_t count[GN_LOSS_MAX_SETS];
+    double coef[GN_LOSS_MAX_SETS];
+    int kind[GN_LOSS_MAX_SETS];
+    int mirror[GN_LOSS_MAX_SETS];
+    int blk0[GN_LOSS_MAX_SETS + 1];
+    int nsets;
+};
+
+// d value_loss_term / d p in fp64 of the fp32 operands.  smooth_l1 (beta 1) takes torch's choice: the quadratic branch's d for -1 <= d <= 1 -- so
+// exactly -1 / +1 at |d| == 1, where the two branches agree, and 0 at d == 0 -- and the sign beyond.  bce_logits: sigmoid(p) - t.
+__device__ __forceinline__ double value_loss_dterm(float p, float t, int kind) {
+    if (kind == GN_LOSS_BCE_LOGITS) {
+        const double x = (double)p;
+        const double sg = x >= 0.0 ? 1.0 / (1.0 + exp(-x)) : exp(x) / (1.0 + exp(x));
+        return sg - (double)t;
+    }
+    const double d = (double)p - (double)t;
+    if (kind == GN_LOSS_SMOOTH_L1) return d < -1.0 ? -1.0 : d > 1.0 ? 1.0 : d;
+    return 2.0 * d;
+}
+
+__global__ __launch_bounds__(LOSS_WG) void value_losses_bwd_kernel(SegsGradArg a, const double *__restrict__ sums, const float *__restrict__ upstream) {
+    const int s = loss_set_of(a.blk0, a.nsets, blockIdx.x);
+    const int64_t e0 = (int64_t)(blockIdx.x - a.blk0[s]) * (LOSS_WG * VL_ITEMS) + threadIdx.x;
+    const int64_t n = a.count[s];
+    const float *pred = a.pred[s], *tgt = a.target[s];
+    float *g = a.grad[s];
+    const int kind = a.kind[s];
+    // MirrorMSELoss, per segment: the mirrored target iff its sum is strictly smaller
+    const bool mir = a.mirror[s] && sums[s * 2 + 1] < sums[s * 2];
+    const double scale = a.coef[s] * (double)upstream[0];
+#pragma unroll
+    for (int i = 0; i < VL_ITEMS; ++i) {
+        const int64_t e = e0 + (int64_t)i * LOSS_WG;
+        if (e < n) {
+            float t = tgt[e];
+            if (mir && (e % 3) == 0) t = nocs_mirror(t);
+            g[e] = (float)(value_loss_dterm(pred[e], t, kind) * scale);
+        }
+    }
+}
+
+extern "C" int gn_nocs_bin_loss_bwd(const GnNocsBinGradSet *sets_host, int nsets, int bins, int mirror_axis, const double *sums,
+                                    const double *weights_host, const float *upstream, void *stream) {
+    GN_REQUIRE(sets_host != nullptr && nsets >= 1 && nsets <= GN_LOSS_MAX_SETS, "gn_nocs_bin_loss_bwd: 1..%d row sets", GN_LOSS_MAX_SETS);
+    GN_REQUIRE(bins >= 1, "gn_nocs_bin_loss_bwd: bins must be >= 1");
+    GN_REQUIRE(mirror_axis >= -1 && mirror_axis <= 2, "gn_nocs_bin_loss_bwd: mirror_axis must be -1 (none), 0, 1 or 2");
+    GN_REQUIRE(sums != nullptr && weights_host != nullptr && upstream != nullptr, "gn_nocs_bin_loss_bwd: sums, weights and upstream are required");
+    NocsGradArg a = {};
+    a.nsets = nsets;
+    int64_t tot = 0;
+    for (int s = 0; s < nsets; ++s) {
+        const GnNocsBinGradSet &t = sets_host[s];
+        GN_REQUIRE(t.n >= 1 && t.logits != nullptr && t.gt != nullptr && t.grad != nullptr, "gn_nocs_bin_loss_bwd: set %d: N >= 1 rows and three pointers", s);
+        GN_REQUIRE(t.ncols >= bins * 3 && t.ldl >= t.ncols && t.ldg >= t.ncols,
+                   "gn_nocs_bin_loss_bwd: set %d: need bins * 3 (%d) <= ncols (%d) <= ldl (%d), ldg (%d)", s, bins * 3, t.ncols, t.ldl, t.ldg);
+        GN_REQUIRE(t.n <= ((int64_t)1 << 40) / t.ldl && t.n <= ((int64_t)1 << 40) / t.ldg, "gn_nocs_bin_loss_bwd: set %d: too many rows", s);
+        a.logits[s] = t.logits;
+        a.gt[s] = t.gt;
+        a.grad[s] = t.grad;
+        a.n[s] = t.n;
+        a.ldl[s] = t.ldl;
+        a.ldg[s] = t.ldg;
+        a.ncols[s] = t.ncols;
+        a.weight[s] = weights_host[s];
+        a.coef[s] = weights_host[s] / (double)(t.n * 3);
+        a.blk0[s] = (int)tot;
+        tot += gn_cdiv(t.n * 3, LOSS_WG);
+        GN_REQUIRE(tot <= 0x7fffffff, "gn_nocs_bin_loss_bwd: too many rows");
+    }
+    a.blk0[nsets] = (int)tot;
+    hipLaunchKernelGGL(nocs_bin_loss_bwd_kernel, dim3((unsigned)tot), dim3(LOSS_WG), 0, gn_stream(stream), a, bins, mirror_axis, sums, upstream);
+    GN_LAUNCH_CHECK("gn_nocs_bin_loss_bwd");
+    return GN_OK;
+}
+
+extern "C" int gn_value_losses_bwd(const GnLossGradSegment *segs_host, int nsegs, const double *sums, const float *upstream, void *stream) {
+    GN_REQUIRE(segs_host != nullptr && nsegs >= 1 && nsegs <= GN_LOSS_MAX_SETS, "gn_value_losses_bwd: 1..%d segments", GN_LOSS_MAX_SETS);
+    GN_REQUIRE(sums != nullptr && upstream != nullptr, "gn_value_losses_bwd: sums and upstream are required");
+    SegsGradArg a = {};
+    a.nsets = nsegs;
+    int64_t tot = 0;
+    for (int s = 0; s < nsegs; ++s) {
+        const GnLossGradSegment &g = segs_host[s];
+        GN_REQUIRE(g.count >= 0 && (g.count == 0 || (g.pred != nullptr && g.target != nullptr && g.grad != nullptr)),
+                   "gn_value_losses_bwd: segment %d: bad count / pointers", s);
+        GN_REQUIRE(g.kind != GN_LOSS_ROW_NORM, "gn_value_losses_bwd: segment %d: row_norm is a metric, not a loss: it has no gradient", s);
+        GN_REQUIRE(g.kind == GN_LOSS_L2 || g.kind == GN_LOSS_SMOOTH_L1 || g.kind == GN_LOSS_BCE_LOGITS, "gn_value_losses_bwd: segment %d: unknown kind %d", s,
+                   g.kind);
+        GN_REQUIRE(!g.mirror || g.count % 3 == 0, "gn_value_losses_bwd: segment %d: a mirrored segment holds (M, 3) rows", s);
+        a.pred[s] = g.pred;
+        a.target[s] = g.target;
+        a.grad[s] = g.grad;
+        a.count[s] = g.count;
+        a.coef[s] = g.coef;
+        a.kind[s] = g.kind;
+        a.mirror[s] = g.mirror;
+        a.blk0[s] = (int)tot;
+        tot += gn_cdiv(g.count, LOSS_WG * VL_ITEMS);
+        GN_REQUIRE(tot <= 0x7fffffff, "gn_value_losses_bwd: too many elements");
+    }
+    a.blk0[nsegs] = (int)tot;
+    if (tot > 0) hipLaunchKernelGGL(value_losses_bwd_kernel, dim3((unsigned)tot), dim3(LOSS_WG), 0, gn_stream(stream), a, sums, upstream);
+    GN_LAUNCH_CHECK("gn_value_losses_bwd");
+    return GN_OK;
+}

@@ -4,7 +4,7 @@ Keeps the reference's class names, constructor kwargs, sub-module names (= check
 ``volume_agg.local_nn``, ``unet_3d.abstract_3d_unet``, ``volume_decoder.mlp`` ...), stage methods
 (``pointnet2_forward``, ``unet3d_forward``, ``volume_decoder_forward``, ``surface_decoder_forward``,
 ``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  ``validation_metrics`` gives the
-losses of the reference's infer (:405-452); optimisers, training steps and visualisation are out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
+losses of the reference's infer (:405-452); its training step (the second stage) and visualisation are out of scope -- the first stage's is garmentnets_amd/train.py, whose loss-gradient ABI (gn_value_losses_bwd: l2 / smooth_l1 / bce_logits) and optimiser (optim.FusedAdam) this model's step will reuse.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
 """
 import os
 import threading

@@ -1,9 +1,12 @@
-"""PointNet2NOCS (inference) -- API twin of /root/reference/networks/pointnet2_nocs.py:58-195.
+"""PointNet2NOCS -- API twin of the reference's networks/pointnet2_nocs.py:58-195.
 
 Same constructor kwargs, sub-module names (``sa1_module`` ... ``global_lin2``: the checkpoint schema), ``forward(data)``
 result keys and ``logits_to_nocs`` / ``get_virtual_grid`` helpers, and ``validation_metrics`` (the metric dict of the
-reference's ``infer``, :257-440, without its logging).  Optimisers, training steps and visualisation are out of scope.  All
-arithmetic runs in HIP kernels (garmentnets_amd.ops).
+reference's ``infer``, :257-440, without its logging).  ``forward`` is the fused inference path.  ``training_step`` /
+``training_metrics`` / ``configure_optimizers`` are thin methods over garmentnets_amd.train (the differentiable forward, the HIP
+loss gradients, optim.FusedAdam), imported lazily: the inference path imports none of the differentiable bindings.  Visualisation is out of
+scope.  All arithmetic runs in HIP kernels (garmentnets_amd.ops), with one exception in training mode: the reference's four
+dropouts (present iff ``dropout=True``) are torch.nn.functional.dropout (train.py's docstring).
 """
 import torch
 from torch import nn
@@ -97,6 +100,22 @@ class PointNet2NOCS(nn.Module):
             "global_feature": global_feature,
         }
 
+    # -- training (garmentnets_amd/train.py, imported on first use) --------------------------------------------
+    def training_step(self, batch, batch_idx=None):
+        """the reference's metrics['loss'] of one batch: a device scalar with a graph through every parameter"""
+        from .. import train
+        return train.training_step(self, batch, batch_idx)
+
+    def training_metrics(self, batch):
+        """validation_metrics' five keys for the model AS IT STANDS (training-mode BatchNorm and dropout included), detached python floats,
+        from the sums of the loss kernel: one forward"""
+        from .. import train
+        return train.training_metrics(self, batch)
+
+    def configure_optimizers(self):
+        from ..optim import FusedAdam
+        return FusedAdam(self.parameters(), lr=self.learning_rate, modules=self)
+
     def logits_to_nocs(self, logits):
         if self.nocs_bins is None:
             return logits
@@ -122,22 +141,29 @@ class PointNet2NOCS(nn.Module):
         logits, glogits = result["per_point_logits"], result["global_logits"]
         gt, ggt = batch.y, batch.nocs_grip_point
         n, b = gt.shape[0], ggt.shape[0]
-        wn, wg = self.nocs_loss_weight, self.grip_point_loss_weight
         if self.nocs_bins is None:
             mirror = self.symmetry_axis is not None
             s = ops.value_losses([(logits, gt, "l2", mirror), (glogits, ggt, "l2", mirror), (logits, gt, "row_norm"), (glogits, ggt, "row_norm")])
             s = s.cpu().tolist()
+            return self.metrics_from_sums(s[:2], n, b, dist=(s[2][0], s[3][0]))
+        return self.metrics_from_sums(ops.nocs_bin_metrics([(logits, gt), (glogits, ggt)], self.nocs_bins, self.symmetry_axis).cpu().tolist(), n, b)
+
+    def metrics_from_sums(self, s, n, b, dist=None):
+        """the metric dict from the loss kernels' sums as python floats, for n points and b garments.  bins: s = gn_nocs_bin_metrics' (2, 4);
+        regression: s = gn_value_losses' (2, 2) of the two l2 segments and dist = the two row-norm sums"""
+        wn, wg = self.nocs_loss_weight, self.grip_point_loss_weight
+        if self.nocs_bins is None:
+            mirror = self.symmetry_axis is not None
             nocs = min(s[0][0], s[0][1]) if mirror else s[0][0]
             grip = min(s[1][0], s[1][1]) if mirror else s[1][0]
             nocs_loss, grip_loss = nocs / (n * 3), grip / (b * 3)
             return {"loss": wn * nocs_loss + wg * grip_loss, "nocs_loss": nocs_loss, "grip_point_loss": grip_loss,
-                    "nocs_err_dist": s[2][0] / n, "grip_point_err_dist": s[3][0] / b}
-        sums = ops.nocs_bin_metrics([(logits, gt), (glogits, ggt)], self.nocs_bins, self.symmetry_axis).cpu().tolist()
+                    "nocs_err_dist": dist[0] / n, "grip_point_err_dist": dist[1] / b}
 
-        def branch(ce, dist):
-            nocs_loss, grip_loss = sums[0][ce] / (n * 3), sums[1][ce] / (b * 3)
+        def branch(ce, err):
+            nocs_loss, grip_loss = s[0][ce] / (n * 3), s[1][ce] / (b * 3)
             return {"loss": wn * nocs_loss + wg * grip_loss, "nocs_loss": nocs_loss, "grip_point_loss": grip_loss,
-                    "nocs_err_dist": sums[0][dist] / n, "grip_point_err_dist": sums[1][dist] / b}
+                    "nocs_err_dist": s[0][err] / n, "grip_point_err_dist": s[1][err] / b}
 
         plain = branch(0, 2)
         if self.symmetry_axis is None:

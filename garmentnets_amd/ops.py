@@ -1210,6 +1210,71 @@ def value_losses(segments):
     return out
 
 
+def nocs_bin_loss_bwd(sets, bins, mirror_axis, sums, weights, upstream):
+    """gradient of the weighted binned NOCS loss sum_s weights[s] * CE_s / (3 n_s) to the logits of 1..8 row sets in ONE launch
+    (gn_nocs_bin_loss_bwd).  sets: [(logits (N, >= bins*3) fp32, gt (N, 3))] as nocs_bin_metrics takes them; sums: ITS (nsets, 4) fp64 result, on
+    the device -- with a mirror_axis the kernel decides from them whether the whole batch takes the mirrored targets; upstream: fp32 device
+    scalar, the gradient of the loss.  -> one contiguous fp32 gradient per set, shaped like its logits (pad columns exactly 0)."""
+    _check_sets(len(sets))
+    if len(weights) != len(sets):
+        raise ValueError(f"{len(sets)} sets but {len(weights)} weights")
+    keep = []
+    for logits, gt in sets:
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] < bins * 3:
+            raise ValueError(f"logits: expected (N, >= {bins * 3}) float32 rows, got {tuple(logits.shape)} {logits.dtype}")
+        if logits.shape[1] > 1 and logits.stride(1) != 1:
+            logits = logits.contiguous()
+        n, ldl = rows_view(logits)
+        gt = gt.float().contiguous()
+        if n < 1 or gt.shape != (n, 3):
+            raise ValueError(f"gt: expected ({n}, 3) with at least one row, got {tuple(gt.shape)}")
+        keep.append((logits, gt, torch.empty(tuple(logits.shape), dtype=torch.float32, device=logits.device), n, ldl))
+    sums = _chk(sums, torch.float64, "sums")
+    if tuple(sums.shape) != (len(sets), 4):
+        raise ValueError(f"sums: expected ({len(sets)}, 4), got {tuple(sums.shape)}")
+    upstream = _chk(upstream.reshape(1), torch.float32, "upstream")
+    rows = [(_p(lg).value, _p(gt).value, _p(g).value, n, ldl, g.shape[1], g.shape[1], 0) for lg, gt, g, n, ldl in keep]
+    tab = _table(_lib.NocsBinGradSet, rows)
+    w = (ctypes.c_double * len(rows))(*[float(x) for x in weights])
+    _lib.call("gn_nocs_bin_loss_bwd", tab, len(rows), int(bins), -1 if mirror_axis is None else int(mirror_axis), _p(sums), w, _p(upstream), _stream())
+    return [k[2] for k in keep]
+
+
+def value_losses_bwd(segments, sums, weights, upstream):
+    """gradient of sum_s weights[s] * (segment s's sum, the mirrored one where that is strictly smaller) / count_s to pred, for 1..8 segments in ONE
+    launch (gn_value_losses_bwd).  segments: [(pred, target, kind[, mirror])] as value_losses takes them, kind "l2" | "smooth_l1" | "bce_logits"
+    ("row_norm" is a metric: ValueError); sums: value_losses' (nsegs, 2) fp64 result, on the device; upstream: fp32 device scalar.
+    -> one contiguous fp32 gradient per segment, shaped like its pred"""
+    _check_sets(len(segments))
+    if len(weights) != len(segments):
+        raise ValueError(f"{len(segments)} segments but {len(weights)} weights")
+    keep = []
+    for seg, wt in zip(segments, weights):
+        pred, target, kind = seg[:3]
+        mirror = bool(seg[3]) if len(seg) > 3 else False
+        if kind == "row_norm":
+            raise ValueError("row_norm is a metric, not a loss: it has no gradient")
+        if kind not in _lib.LOSS_KINDS:
+            raise ValueError(f"loss kind {kind!r}: expected one of {sorted(_lib.LOSS_KINDS)}")
+        shape = tuple(pred.shape)
+        pred, target = pred.float().contiguous(), target.float().contiguous()
+        if pred.numel() != target.numel():
+            raise ValueError(f"pred ({pred.numel()} elements) and target ({target.numel()}) differ in size")
+        count = pred.numel()
+        if mirror and count % 3:
+            raise ValueError(f"{kind} (mirrored) needs (M, 3) rows, got {count} elements")
+        keep.append((pred, target, torch.empty(shape, dtype=torch.float32, device=pred.device), count, float(wt) / max(count, 1), _lib.LOSS_KINDS[kind],
+                     int(mirror)))
+    sums = _chk(sums, torch.float64, "sums")
+    if tuple(sums.shape) != (len(segments), 2):
+        raise ValueError(f"sums: expected ({len(segments)}, 2), got {tuple(sums.shape)}")
+    upstream = _chk(upstream.reshape(1), torch.float32, "upstream")
+    rows = [(_p(pr).value, _p(tg).value, _p(g).value, n, c, k, m) for pr, tg, g, n, c, k, m in keep]
+    tab = _table(_lib.LossGradSegment, rows)
+    _lib.call("gn_value_losses_bwd", tab, len(rows), _p(sums), _p(upstream), _stream())
+    return [k[2] for k in keep]
+
+
 # ------------------------------------------------------------------------------------------------ operator gradients (csrc/grad.hip)
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)

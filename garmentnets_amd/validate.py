@@ -132,17 +132,11 @@ def write_outputs(output_dir, rows, summary):
         json.dump(summary, f, indent=2)
 
 
-def main(argv=None):
-    a = build_parser().parse_args(argv)
-    device = torch.device("cuda:{}".format(a.gpu_id))
-    torch.cuda.set_device(device)
-    model = load_model(a, device)
-    dataset = make_dataset(a, volume_task_space=getattr(model, "volume_task_space", False))
-    indices = dataset.subset_indices(a.subset)
+def validation_rows(model, dataset, indices, batch_size, num_batches, device, log=None):
+    """the validation loop: one row (batch_idx, garments, seconds, every val_* metric) per batch of `indices`, at most num_batches of them"""
     rows = []
-    t_start = time.time()
-    for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, a.batch_size)):
-        if a.num_batches is not None and batch_idx >= a.num_batches:
+    for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, batch_size)):
+        if num_batches is not None and batch_idx >= num_batches:
             break
         t0 = time.time()
         with torch.no_grad():
@@ -150,7 +144,20 @@ def main(argv=None):
         row = {"batch_idx": batch_idx, "garments": len(chunk), "seconds": time.time() - t0}
         row.update({"val_" + k: float(v) for k, v in metrics.items()})
         rows.append(row)
-        print(json.dumps(row))
+        if log is not None:
+            log(row)
+    return rows
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    device = torch.device("cuda:{}".format(a.gpu_id))
+    torch.cuda.set_device(device)
+    model = load_model(a, device)
+    dataset = make_dataset(a, volume_task_space=getattr(model, "volume_task_space", False))
+    indices = dataset.subset_indices(a.subset)
+    t_start = time.time()
+    rows = validation_rows(model, dataset, indices, a.batch_size, a.num_batches, device, log=lambda row: print(json.dumps(row)))
     wall = time.time() - t_start
     summary = {"model": a.model, "subset": a.subset, "batches": len(rows), "garments": int(sum(r["garments"] for r in rows)),
                "epoch": epoch_values(rows), "epoch_definition": EPOCH_DEFINITION, "wall_seconds": wall,

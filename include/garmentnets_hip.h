@@ -551,6 +551,68 @@ int gn_nocs_bin_metrics(const GnNocsBinSet *sets_host, int nsets, int bins, int 
 size_t gn_value_losses_workspace_bytes(const GnLossSegment *segs_host, int nsegs);
 int gn_value_losses(const GnLossSegment *segs_host, int nsegs, void *ws, size_t ws_bytes, double *out, void *stream);
 
+/* ---- Loss gradients (csrc/losses.hip): the backward of the two launches above, for a training step.  Both read the forward's fp64 sums FROM THE
+ * DEVICE and take the mirror decision there (every thread the same fp64 comparison; no host branch between forward and backward).  `upstream` is a
+ * device pointer to the fp32 gradient of the scalar loss.  Every output element is written exactly once with a plain store (no atomics). */
+typedef struct {
+    const float *logits;   /* [n][ldl] rows, the first bins * 3 laid out (bins, 3) */
+    const float *gt;       /* [n][3] */
+    float *grad;           /* [n][ldg] out: columns [0, bins * 3) the gradient, [bins * 3, ncols) zero */
+    int64_t n;             /* rows, >= 1 */
+    int ldl;               /* >= ncols */
+    int ldg;               /* >= ncols */
+    int ncols;             /* >= bins * 3: the columns of a (padded) logits row */
+    int pad;
+} GnNocsBinGradSet;
+
+typedef struct {
+    const float *pred;     /* [count] */
+    const float *target;   /* [count] */
+    float *grad;           /* [count] out */
+    int64_t count;         /* >= 0; a multiple of 3 when mirror is set */
+    double coef;           /* weight_s / count_s of a mean-reduced loss */
+    int kind;              /* GN_LOSS_L2 | GN_LOSS_SMOOTH_L1 | GN_LOSS_BCE_LOGITS; GN_LOSS_ROW_NORM is a metric and is refused */
+    int mirror;
+} GnLossGradSegment;
+
+/* grad[r][k * 3 + ax] = (softmax_k(logits[r][. * 3 + ax]) - [k == target bin]) * weights_host[s] / (3 n_s) * upstream, fp32.  The softmax is the
+ * forward's max-subtracted one; the target bin is the forward's (mirrored on mirror_axis for the WHOLE batch iff the mirrored weighted loss
+ * sum_s w_s * sums[s][1] / (3 n_s) is strictly smaller than the plain one over sums[s][0]).  sums: gn_nocs_bin_metrics' out, on the device. */
+int gn_nocs_bin_loss_bwd(const GnNocsBinGradSet *sets_host, int nsets, int bins, int mirror_axis, const double *sums, const double *weights_host,
+                         const float *upstream, void *stream);
+
+/* grad[e] = d term(pred[e], target[e]) / d pred[e] * coef_s * upstream, fp32: 2 d (l2); d clamped to [-1, 1] (smooth_l1: torch's choice, the quadratic
+ * branch at |d| == 1, 0 at d == 0); sigmoid(p) - t (bce_logits).  A mirrored segment differentiates against the x-mirrored target iff ITS mirrored sum
+ * sums[s][1] is strictly smaller than sums[s][0] (MirrorMSELoss, per segment).  sums: gn_value_losses' out, on the device. */
+int gn_value_losses_bwd(const GnLossGradSegment *segs_host, int nsegs, const double *sums, const float *upstream, void *stream);
+
+/* ---- Fused Adam (csrc/optim.hip): torch.optim.Adam's update (L2 weight decay g + wd * p) of every tensor of a device table in ONE launch.
+ * table: DEVICE array of n entries sorted by blk0; entry e owns the workgroups [blk0_e, blk0_e + ceil(numel_e / GN_ADAM_CHUNK)) and workgroup
+ * j of them the elements [j * GN_ADAM_CHUNK, min((j + 1) * GN_ADAM_CHUNK, numel_e)).  hyper_host: 1..GN_ADAM_MAX_HYPER sets of scalars, the bias
+ * corrections computed by the caller in fp64 from the step count.  Each element is read and written once, 16 bytes at a time where all four pointers
+ * of the tensor are 16-byte aligned; the per-element arithmetic (fp64 of the fp32 operands, each result rounded once) is one function whatever the
+ * path.  No atomics.  More workgroups than one grid holds are split over launches. */
+#define GN_ADAM_CHUNK 4096
+#define GN_ADAM_MAX_HYPER 16
+typedef struct {
+    float *p;              /* [numel] parameter, updated in place */
+    const float *g;        /* [numel] gradient */
+    float *exp_avg;        /* [numel] updated in place */
+    float *exp_avg_sq;     /* [numel] updated in place */
+    int64_t numel;         /* >= 1 */
+    int64_t blk0;          /* first workgroup of this entry */
+    int hyper;             /* index into hyper_host */
+    int pad;
+} GnAdamEntry;
+
+typedef struct {
+    double lr, beta1, beta2, eps, weight_decay;
+    double bias_correction1;        /* 1 - beta1 ^ step */
+    double bias_correction2_sqrt;   /* sqrt(1 - beta2 ^ step) */
+} GnAdamHyper;
+
+int gn_adam_step(const GnAdamEntry *table, int n, int64_t nblocks, const GnAdamHyper *hyper_host, int nhyper, void *stream);
+
 /* ---- Operator gradients (csrc/grad.hip): fp32 in / fp32 out.  The selections (grid scatter max / min, segment max, global max pool) hand an output
  * element's gradient to ONE input element: the one whose value is bit-equal to the forward's stored output, the lowest point / edge index among equal
  * values; a NaN never wins.  The sums (sa_gather, knn_interpolate, the sampler's volume gradient) are ordered: one owner per destination adds its
