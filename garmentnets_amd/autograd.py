@@ -20,9 +20,10 @@ gradient through both, the running buffers updated in place (DESIGN.md "Train-mo
 
 ``nocs_bin_loss`` / ``value_loss`` close the chain: the forward is the validation kernels of csrc/losses.hip, unchanged (the loss value is
 ``validation_metrics``' to the last bit), the backward their gradient kernels, which take the mirror decision on the device from the forward's own
-sums.  The optimiser is optim.FusedAdam, the first stage's training step train.py (DESIGN.md "Training step, first stage").
+sums.  The optimiser is optim.FusedAdam, the first stage's training step train.py (DESIGN.md "Training step, first stage"), the second stage's
+train_pipeline.py (DESIGN.md "Training step, second stage": ``mlp`` -> ``scatter`` -> ``unet3d`` -> ``implicit_decode`` per head -> ``value_loss``).
 
-What this is NOT: the second stage's training step, or a backward for the fused inference kernels (the fused / split-operand decoder,
+What this is NOT: a backward for the fused inference kernels (the fused / split-operand decoder,
 ``gn_sa_fused``: ``implicit_decode`` and ``point_conv_max`` are the unfused chains).  The inference modules do not import this file.
 
 Selections (max / min) hand the gradient to ONE element per (slot, channel): among equal values the lowest point / edge index (torch_scatter's CUDA

@@ -4,7 +4,7 @@ Keeps the reference's class names, constructor kwargs, sub-module names (= check
 ``volume_agg.local_nn``, ``unet_3d.abstract_3d_unet``, ``volume_decoder.mlp`` ...), stage methods
 (``pointnet2_forward``, ``unet3d_forward``, ``volume_decoder_forward``, ``surface_decoder_forward``,
 ``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  ``validation_metrics`` gives the
-losses of the reference's infer (:405-452); its training step (the second stage) and visualisation are out of scope -- the first stage's is garmentnets_amd/train.py, whose loss-gradient ABI (gn_value_losses_bwd: l2 / smooth_l1 / bce_logits) and optimiser (optim.FusedAdam) this model's step will reuse.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
+losses of the reference's infer (:405-452); ``training_step`` / ``training_metrics`` / ``configure_optimizers`` are the second stage's training step (garmentnets_amd/train_pipeline.py, imported on use: the loss gradients of gn_value_losses_bwd and optim.FusedAdam, as the first stage's train.py); visualisation is out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
 """
 import os
 import threading
@@ -573,8 +573,11 @@ class ConvImplicitWNFPipeline(nn.Module):
         if self.loss_type not in self.LOSS_TYPES:
             raise ValueError(f"Invalid loss_type: {self.loss_type!r} (expected one of {self.LOSS_TYPES})")
 
-    def losses_from(self, result, data):
-        """validation_metrics' loss dict from a forward() result dict and the batch's targets"""
+    def loss_segments(self, result, data):
+        """-> (segments, names, weights) of the weighted loss of infer, in its order: the volume (BCE-with-logits when volume_classification, else
+        loss_type), the surface (loss_type) and, when mc_surface_loss_weight > 0, the mc surface (BCE-with-logits).  segments are (pred, target, kind)
+        as ops.value_losses and the differentiable value_loss take them: validation (losses_from) and the training step (train_pipeline.loss_and_sums) read
+        this one list"""
         self._check_loss_type()
         segs = [(result["volume_decoder_result"]["pred_volume_value"], data.gt_volume_value, "bce_logits" if self.volume_classification else self.loss_type),
                 (result["surface_decoder_result"]["out_features"], data.gt_sim_points, self.loss_type)]
@@ -583,7 +586,35 @@ class ConvImplicitWNFPipeline(nn.Module):
             segs.append((result["mc_surface_decoder_result"]["out_features"], data.is_query_point_on_surf, "bce_logits"))
             names.append("mc_surface_loss")
             weights.append(self.mc_surface_loss_weight)
-        sums = ops.value_losses(segs)[:, 0].cpu().tolist()
-        metrics = {k: w * (s / seg[1].numel()) for k, w, s, seg in zip(names, weights, sums, segs)}
+        return segs, names, weights
+
+    @staticmethod
+    def metrics_from_sums(sums, names, weights, counts):
+        """the loss dict from the per-segment sums (python floats) of the loss kernel: each weight times the mean criterion, and loss, their sum"""
+        metrics = {k: w * (s / n) for k, w, s, n in zip(names, weights, sums, counts)}
         metrics["loss"] = sum(metrics.values())
         return metrics
+
+    def losses_from(self, result, data):
+        """validation_metrics' loss dict from a forward() result dict and the batch's targets"""
+        segs, names, weights = self.loss_segments(result, data)
+        sums = ops.value_losses(segs)[:, 0].cpu().tolist()
+        return self.metrics_from_sums(sums, names, weights, [seg[1].numel() for seg in segs])
+
+    # -- training (garmentnets_amd/train_pipeline.py; imported on use: the inference modules do not depend on the training code) ----------------------
+    def training_step(self, batch, batch_idx=None):
+        """the reference's loss of one batch: a device scalar with a graph through every parameter of the second stage (the first stage is frozen)"""
+        from .. import train_pipeline
+        return train_pipeline.training_step(self, batch, batch_idx)
+
+    def training_metrics(self, batch):
+        """validation_metrics' keys for the model AS IT STANDS (training-mode BatchNorm included), detached python floats, from the sums of the
+        loss kernel: one forward"""
+        from .. import train_pipeline
+        return train_pipeline.training_metrics(self, batch)
+
+    def configure_optimizers(self):
+        """the reference's optim.Adam(self.parameters(), lr=self.learning_rate): the frozen first stage's parameters are in the group, never get
+        a gradient, and FusedAdam skips them"""
+        from ..optim import FusedAdam
+        return FusedAdam(self.parameters(), lr=self.learning_rate, modules=self)

@@ -18,7 +18,11 @@ Dropout is the one deliberate exception to "all arithmetic in HIP": the referenc
 iff dropout=True) are torch.nn.functional.dropout on four small tensors, at the reference's positions, when the model is in training mode -- torch's
 generator stream could not be matched by a kernel of ours anyway.
 
-What stays out: the second stage's step (ConvImplicitWNFPipeline), a HIP dropout, a compacting gather kernel in place of the index_select / index_copy
+The second stage's step (ConvImplicitWNFPipeline behind this model, frozen) is a module of its own, garmentnets_amd/train_pipeline.py, named after the
+reference's script: `python -m garmentnets_amd.train_pipeline`.  It shares _bn_training / _plain / _mlp and _validate with this file; `--model pipeline`
+here keeps its refusal.
+
+What stays out: a HIP dropout, a compacting gather kernel in place of the index_select / index_copy
 around local_nn.
 """
 import argparse
@@ -185,12 +189,12 @@ def parse_args(argv=None):
     return a
 
 
-def _validate(model, a, device):
+def _validate(model, a, device, volume_task_space=False):
     """validate.py's loop over the val subset (read with static_epoch_seed=True, as the reference's val_dataset), the model in eval mode for it"""
     from . import validate
     va = argparse.Namespace(**vars(a))
     va.subset, va.static_epoch_seed = "val", True
-    dataset = validate.make_dataset(va)
+    dataset = validate.make_dataset(va, volume_task_space=volume_task_space)
     was_training = model.training
     model.eval()
     try:

@@ -25,22 +25,47 @@ from garmentnets_amd.networks.pointnet2_nocs import PointNet2NOCS  # noqa: E402
 from garmentnets_amd.optim import FusedAdam  # noqa: E402
 
 
-def timed_step(model, optimizer, batch, invalidate):
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    optimizer.zero_grad(set_to_none=True)
+def bracketed(parts, host=None):
+    """run the callables `parts` in order, each between two events on the stream; one synchronisation at the end -> their milliseconds (stream time: it
+    holds the host's time wherever the stream waits for the host).  host: a list that receives the host's own milliseconds inside each part (the time
+    to issue it, nothing waited for).  tools/pipeline_step_time.py brackets its parts with this too"""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(parts) + 1)]
     ev[0].record()
-    loss, _ = train.loss_and_sums(model, batch)
-    ev[1].record()
-    loss.backward()
-    ev[2].record()
-    optimizer.step()
-    if invalidate:
-        for m in model.modules():
-            if isinstance(m, PackedModule):
-                m._invalidate()
-    ev[3].record()
+    for i, part in enumerate(parts):
+        t0 = time.perf_counter()
+        part()
+        if host is not None:
+            host.append((time.perf_counter() - t0) * 1e3)
+        ev[i + 1].record()
     torch.cuda.synchronize()
-    return [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
+    return [ev[i].elapsed_time(ev[i + 1]) for i in range(len(parts))]
+
+
+def summarise(rows, names):
+    """rows: one list of milliseconds per step, a column per name -> the medians, the step's median / min / max and each part's share of it"""
+    cols = [[r[i] for r in rows] for i in range(len(names))]
+    total = [sum(r) for r in rows]
+    med = statistics.median(total)
+    out = {"step_ms_median": med, "step_ms_min": min(total), "step_ms_max": max(total)}
+    out.update({f"{n}_ms_median": statistics.median(c) for n, c in zip(names, cols)})
+    out["share"] = {n: statistics.median(c) / med for n, c in zip(names, cols)}
+    return out
+
+
+def timed_step(model, optimizer, batch, invalidate):
+    optimizer.zero_grad(set_to_none=True)
+    state = {}
+
+    def forward():
+        state["loss"] = train.loss_and_sums(model, batch)[0]
+
+    def step():
+        optimizer.step()
+        if invalidate:
+            for m in model.modules():
+                if isinstance(m, PackedModule):
+                    m._invalidate()
+    return bracketed([forward, lambda: state["loss"].backward(), step])
 
 
 def main():
@@ -76,12 +101,7 @@ def main():
            "nocs_bins": hp["pointnet2_params"]["nocs_bins"], "steps": a.steps, "warmup": a.warmup,
            "parameters": sum(p.numel() for p in base.parameters()), "tensors": len(list(base.parameters()))}
     for name, (_, _, rows) in runs.items():
-        fwd, bwd, opt_ms = ([r[i] for r in rows] for i in range(3))
-        total = [sum(r) for r in rows]
-        med = statistics.median(total)
-        out[name] = {"step_ms_median": med, "step_ms_min": min(total), "step_ms_max": max(total), "forward_ms_median": statistics.median(fwd),
-                     "backward_ms_median": statistics.median(bwd), "optimizer_ms_median": statistics.median(opt_ms),
-                     "share": {"forward": statistics.median(fwd) / med, "backward": statistics.median(bwd) / med, "optimizer": statistics.median(opt_ms) / med}}
+        out[name] = summarise(rows, ("forward", "backward", "optimizer"))
     line = json.dumps(out)
     print(line)
     if a.out:
