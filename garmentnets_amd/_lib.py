@@ -56,6 +56,12 @@ PROTOTYPES = {
     "gn_conv_affine_pack_wino": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "gn_conv3d_gcr_split_wino": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp],
     "gn_conv3d_gcr_split_wino_partial": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "gn_weight_pack_split_bytes": [_i32, _i32, _i32],
+    "gn_weight_pack_split_wino_bytes": [_i32, _i32],
+    "gn_weight_pack_upconv_bytes": [_i32, _i32],
+    "gn_weight_pack_split": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
+    "gn_weight_pack_split_wino": [_vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
+    "gn_weight_pack_upconv": [_vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
     "gn_affine_act": [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
     "gn_upconv_partial": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "gn_grid_tile_flags": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
@@ -130,7 +136,8 @@ PROTOTYPES = {
     "gn_bn_train_bwd_workspace_bytes": [_i64, _i32],
     "gn_bn_train_bwd": [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp],
 }
-_RESTYPES = {"gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
+_RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
+             "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
              "gn_nocs_bin_metrics_workspace_bytes": _sz, "gn_value_losses_workspace_bytes": _sz,
              "gn_grid_scatter_bwd_workspace_bytes": _sz, "gn_sa_gather_bwd_workspace_bytes": _sz, "gn_knn_interpolate_bwd_workspace_bytes": _sz,
              "gn_trilinear_sample_bwd_workspace_bytes": _sz, "gn_conv3d_bwd_weight_workspace_bytes": _sz, "gn_groupnorm_bwd_stats_workspace_bytes": _sz,

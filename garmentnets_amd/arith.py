@@ -31,6 +31,11 @@ global mutable state except immutable LUTs).  ``DEFAULT`` is read from the envir
                        3-stage weight ring cost the decoder kernel what the separate sampler launch costs
     ggm_fp32           the batched Gaussian gradient magnitude accumulates its taps in fp32 instead of scipy's fp64 (gn_ggm3d_batch_ex, round 6).  OFF by
                        default: the default is scipy's arithmetic bit for bit; on, `volume_gradient_magnitude` is 1e-6-class against it (meshes unchanged)
+    device_packs       the static split-operand weight packs of the UNet's convolutions (direct, Winograd, polyphase) are built by HIP kernels from the
+                       raw weight on the device (csrc/weight_pack.hip) instead of on the host: no weight copy to the CPU, no stream synchronisation.  Same
+                       bits (one documented exception: the scale of a row whose maximum lies a few ulps below a power of two, DESIGN.md "Device-side weight packs"); which
+                       launch a layer takes (unet3d.conv_plan) does not depend on it.  OFF by default: inference builds its packs once, so only training
+                       -- which rebuilds them after every optimiser step -- gains; `python -m garmentnets_amd.train_pipeline` turns it on
 """
 import dataclasses
 import os
@@ -63,6 +68,7 @@ class Arith:
     fold_final_conv: bool = True
     fused_lattice: bool = False
     ggm_fp32: bool = False
+    device_packs: bool = False
 
     def __post_init__(self):
         if self.conv_mode not in CONV_MODE_NAMES.values():
@@ -86,7 +92,7 @@ class Arith:
                    sparse_first_conv=_env_flag("GARMENTNETS_SPARSE_CONV"), affine_in_weights=_env_flag("GARMENTNETS_AFFINE_IN_WEIGHTS"),
                    winograd=_env_flag("GARMENTNETS_WINOGRAD"), winograd32=_env_flag("GARMENTNETS_WINOGRAD32"), polyphase_upconv=_env_flag("GARMENTNETS_POLYPHASE"),
                    fold_final_conv=_env_flag("GARMENTNETS_FOLD_FINAL_CONV"), fused_lattice=_env_flag("GARMENTNETS_FUSED_LATTICE", False),
-                   ggm_fp32=_env_flag("GARMENTNETS_GGM_FP32", False))
+                   ggm_fp32=_env_flag("GARMENTNETS_GGM_FP32", False), device_packs=_env_flag("GARMENTNETS_DEVICE_PACKS", False))
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)

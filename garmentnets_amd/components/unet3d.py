@@ -282,19 +282,27 @@ class SingleConv(PackedModule, nn.Sequential):
                 wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
             r, nxt = ops.conv3d_gcr(src0, src1, a, d, wp, cout, relu=True, with_stats=with_stats), None
         else:
-            r, nxt = self._run_split(plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay)
+            r, nxt = self._run_split(plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay, device_packs=arith.device_packs)
         return (r + (nxt,)) if with_stats else (r, None, nxt)
 
-    def _run_split(self, plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay=None):
+    def _run_split(self, plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay=None, device_packs=False):
         """execute a conv_plan on the split-operand kernels (16-bit matrix cores: csrc/unet_split.hip, unet_wino.hip, unet_wino32.hip) in one of two
         operand forms: literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack) -> (the launch's
         result, the output's AtRest or None).
-        lay: channel-padded storage (_Layout) -- the padded weight and stored widths in every pack, the GroupNorm over the real channels"""
+        lay: channel-padded storage (_Layout) -- the padded weight and stored widths in every pack, the GroupNorm over the real channels
+        device_packs (arith.device_packs, a weight on the GPU): the static packs come from the device builders (csrc/weight_pack.hip: no host round
+        trip), under keys of their own in the same ParamCache generation; the launches are the same"""
         gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, plan.mode, src0.shape[-1]
         real = None
         if lay is not None:
             weight, cout, real = self._padded_weight(lay), lay.cout, lay.real
         cache, gen = param_cache(self, "_split_packs"), self._gen(lay)
+        device_packs = bool(device_packs) and weight.is_cuda
+
+        def raw():
+            """the weight as the device builders read it (fp32, contiguous: device-side copies when it is not)"""
+            w = weight.detach()
+            return w if w.dtype == torch.float32 and w.is_contiguous() else w.float().contiguous()
         part = prep = act_inv = rest_out = None
         if plan.aiw and not plan.poly:
             # a layer whose input is at rest (0 for the scattered volume, at_rest.value behind it) almost everywhere
@@ -313,7 +321,11 @@ class SingleConv(PackedModule, nn.Sequential):
                 def build_poly():
                     w0, wm, _ = ops.polyphase_weights(weight, c0)
                     return (ops.pack_conv_weight_split(w0, mode).to(weight.device), ops.pack_upconv_weight(wm, cout, mode).to(weight.device))
-                pk0, pkm = cache.get(gen, ("poly", mode, c0), build_poly)
+                if device_packs:
+                    pk0, pkm = cache.get(gen, ("device", "poly", mode, c0), lambda: (ops.pack_conv_weight_split_device(raw(), mode, 0, c0),
+                                                                                     ops.pack_upconv_weight_device(raw(), c0, mode)))
+                else:
+                    pk0, pkm = cache.get(gen, ("poly", mode, c0), build_poly)
                 part = ops.upconv_partial(src1, a[:, c0:].contiguous(), d[:, c0:].contiguous(), pkm, cout, act_inv=act_inv)
                 if plan.aiw:
                     # the full-resolution part in the affine-in-weights form: the skip connection src0 is at rest away from the cells
@@ -324,10 +336,18 @@ class SingleConv(PackedModule, nn.Sequential):
                     prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=plan.wino)
                 else:
                     a, d = a[:, :c0].contiguous(), d[:, :c0].contiguous()
-                    pack = (cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(weight, c0)[0]).to(weight.device))
-                            if plan.wino else pk0)
+                    if not plan.wino:
+                        pack = pk0
+                    elif device_packs:
+                        pack = cache.get(gen, ("device", "poly_wino", c0), lambda: ops.pack_conv_weight_split_wino_device(raw(), 0, c0))
+                    else:
+                        pack = cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(weight, c0)[0]).to(weight.device))
+            elif plan.wino and device_packs:
+                pack = cache.get(gen, ("device", "wino"), lambda: ops.pack_conv_weight_split_wino_device(raw()))
             elif plan.wino:
                 pack = cache.get(gen, "wino", lambda: ops.pack_conv_weight_split_wino(weight).to(weight.device))
+            elif device_packs:
+                pack = cache.get(gen, ("device", mode), lambda: ops.pack_conv_weight_split_device(raw(), mode))
             else:
                 pack = cache.get(gen, mode, lambda: ops.pack_conv_weight_split(weight, mode).to(weight.device))
         # the one launch tail of each form (a polyphase launch reads the full-resolution source alone: the upsampled channels arrive as the partial)

@@ -517,6 +517,63 @@ def pack_upconv_weight(wm, cout, mode):
     return SplitPack(pk.view(torch.int16).reshape(-1), mode, (1.0 / scale).reshape(-1).contiguous())
 
 
+def _device_pack_args(who, w, c_lo, c_n):
+    """the checks the device builders share, before any launch: a raw fp32 contiguous Conv3d weight on the GPU and widths the kernels take
+    -> (w detached, cout, cin, c_lo, c_n)"""
+    if not isinstance(w, torch.Tensor) or w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"{who}: expected a Conv3d weight (Cout, Cin, 3, 3, 3)")
+    if w.dtype != torch.float32:
+        raise ValueError(f"{who}: expected torch.float32, got {w.dtype}")
+    if not w.is_contiguous():
+        raise ValueError(f"{who}: the weight must be contiguous")
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    c_lo = int(c_lo)
+    c_n = cin - c_lo if c_n is None else int(c_n)
+    if c_lo < 0 or c_n <= 0 or c_lo + c_n > cin:
+        raise ValueError(f"{who}: input channels [{c_lo}, {c_lo + c_n}) outside the weight's {cin}")
+    if c_n % 16 != 0 or cout % 32 != 0:
+        raise ValueError(f"{who}: channels must be multiples of 16 (in) / 32 (out), got {c_n} / {cout}")
+    if not w.is_cuda:
+        raise ValueError(f"{who}: the weight must be on the GPU (the host builder takes a CPU tensor)")
+    return w.detach(), cout, cin, c_lo, c_n
+
+
+def pack_conv_weight_split_device(w, mode, c_lo=0, c_n=None):
+    """pack_conv_weight_split(w[:, c_lo:c_lo + c_n], mode) built on the device (csrc/weight_pack.hip): same layout, same bits, no host round trip and
+    no synchronising call.  w: the raw fp32 contiguous weight on the GPU; the channel range packs a polyphase layer's full-resolution part without a copy.
+    Row scale from the exponent field of the row maximum: the rule pack_conv_weight_split documents (the host's log2 leaves a maximum a few ulps below
+    a power of two in [0.5, 1); include/garmentnets_hip.h).  ValueError, before any launch: a CPU / non-contiguous / non-fp32 weight, refused widths"""
+    if mode not in (SPLIT_BF16X2, SPLIT_BF16X3, SPLIT_F16X2):
+        raise ValueError(f"unknown split mode {mode}")
+    w, cout, cin, c_lo, c_n = _device_pack_args("pack_conv_weight_split_device", w, c_lo, c_n)
+    planes = 2 if mode == SPLIT_F16X2 else int(mode)
+    pk = torch.empty((c_n // 16 * 27 + 8, cout // 32 * planes * 512), dtype=torch.int16, device=w.device)
+    scale = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    _lib.call("gn_weight_pack_split", _p(w), cout, cin, c_lo, c_n, int(mode), _p(pk), pk.numel() * 2, _p(scale), _stream())
+    return SplitPack(pk, mode, scale)
+
+
+def pack_conv_weight_split_wino_device(w, c_lo=0, c_n=None):
+    """pack_conv_weight_split_wino(w[:, c_lo:c_lo + c_n]) built on the device (csrc/weight_pack.hip); as pack_conv_weight_split_device"""
+    w, cout, cin, c_lo, c_n = _device_pack_args("pack_conv_weight_split_wino_device", w, c_lo, c_n)
+    pk = torch.empty((c_n // 16 * 36 + 6, cout // 32 * 2 * 512), dtype=torch.int16, device=w.device)
+    scale = torch.empty((cout,), dtype=torch.float32, device=w.device)
+    _lib.call("gn_weight_pack_split_wino", _p(w), cout, cin, c_lo, c_n, _p(pk), pk.numel() * 2, _p(scale), _stream())
+    return SplitPack(pk, SPLIT_F16X2, scale)
+
+
+def pack_upconv_weight_device(w, c0, mode):
+    """pack_upconv_weight(polyphase_weights(w, c0)[1], Cout, mode) built on the device from the RAW weight (Cout, C0 + C1, 3,3,3): the merged weights are
+    never materialised (csrc/weight_pack.hip); as pack_conv_weight_split_device"""
+    if mode not in (SPLIT_BF16X2, SPLIT_F16X2):
+        raise ValueError("gn_upconv_partial runs the two-plane modes only")
+    w, cout, cin, c0, c1 = _device_pack_args("pack_upconv_weight_device", w, c0, None)
+    pk = torch.empty((c1 // 16 * 64 * (cout // 32) * 2 * 512,), dtype=torch.int16, device=w.device)
+    scale = torch.empty((8 * cout,), dtype=torch.float32, device=w.device)
+    _lib.call("gn_weight_pack_upconv", _p(w), cout, cin, c0, int(mode), _p(pk), pk.numel() * 2, _p(scale), _stream())
+    return SplitPack(pk, mode, scale)
+
+
 def upconv_partial(src1, a1, d1, pack, cout, act_inv=None):
     """coarse source [B][Dc][Hc][Wc][C1] -> polyphase partial sums [B][Dc][Hc][Wc][8 * cout] (csrc/upconv.hip)"""
     B, Dc, Hc, Wc, C1 = src1.shape

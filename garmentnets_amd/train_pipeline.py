@@ -10,7 +10,9 @@
                                         ConvImplicitWNFPipeline.loss_segments forms, which validation reads too), and the logged values from the same sums.
   train_step(model, optimizer, batch)   zero_grad -> forward -> backward -> optimizer.step(); nothing is read back between forward and backward
   python -m garmentnets_amd.train_pipeline
-                                        epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint
+                                        epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint.
+                                        It trains with arith.device_packs: the UNet's static weight packs, stale after every optimiser step, are rebuilt
+                                        on the device (csrc/weight_pack.hip; same bits) instead of through the host; --host_packs keeps the host builders
 
 The first stage is frozen, as the reference's pointnet2_forward freezes it on every call: pointnet2_nocs is put in eval mode (and left there, whatever
 model.train() said before) and runs its inference forward under no_grad.  None of its parameters or buffers changes and none gets a .grad; they stay in
@@ -162,6 +164,9 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--pointnet2_checkpoint", default=None,
                     help="Lightning-style .ckpt of a PointNet2NOCS: it becomes the model's first stage (and its pointnet2_params)")
+    ap.add_argument("--host_packs", action="store_true",
+                    help="build the UNet's static weight packs on the host after every step (the inference path's builders) instead of on the device "
+                         "(arith.device_packs: same bits, no stream synchronisation)")
     return ap
 
 
@@ -199,6 +204,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     torch.manual_seed(a.seed)
     model = load_model(a, device).requires_grad_(True).train()
+    model.arith = model.arith.replace(device_packs=not a.host_packs)        # (train_step reads the model's arithmetic)
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
     optimizer = model.configure_optimizers()
@@ -218,13 +224,14 @@ def main(argv=None):
             chunk, batch = item
             t1 = time.time()
             metrics = train_step(model, optimizer, batch.to(device))
-            row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1}
+            row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1,
+                   "device_packs": model.arith.device_packs}
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
             print(json.dumps(row))
             batch_idx += 1
         val = _validate(model, a, device, volume_task_space=model.volume_task_space)
-        epochs.append(dict(epoch=epoch, **val))
+        epochs.append(dict(epoch=epoch, device_packs=model.arith.device_packs, **val))
         print(json.dumps(epochs[-1]))
         torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},
                    os.path.join(a.output_dir, "checkpoints", "last.ckpt"))

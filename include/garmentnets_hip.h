@@ -331,7 +331,38 @@ int gn_conv3d_gcr_split_wino_partial(const float *src, int Cin, const float *a, 
 int gn_upconv_partial(const float *src1, int C1, const float *a, const float *d, const void *wp, int mode, const float *out_scale,
                       const float *act_inv_scale, int B, int Dc, int Hc, int Wc, int Cout, float *partial, void *stream);
 
-/* The pieces of create_conv's layer orders other than 'gcr' (components/unet3d.py:19-73: 'cr', 'crg', 'cl', 'ce', 'bcr', ...) that the fused conv
+/* The STATIC split-operand weight packs built on the device (csrc/weight_pack.hip) from the raw contiguous Conv3d weight w [Cout][Cin][3][3][3]
+ * (components/unet3d.py:53-56): what garmentnets_amd.ops.pack_conv_weight_split / pack_conv_weight_split_wino / polyphase_weights +
+ * pack_upconv_weight build on the host, without a host round trip -- a training step rebuilds every pack after each optimiser step.  No
+ * intermediate tensor in device memory, nothing read back; each entry writes the whole pack (zero steps included) and out_scale.
+ *   gn_weight_pack_split       input channels [c_lo, c_lo + c_n) (c_lo = 0, c_n = Cin: the plain layer; [0, C0): the full-resolution part of a
+ *                              polyphase layer) -> [c_n/16][27 taps][Cout/32][planes][h 2][r 32][8] x 16 bit + eight zero steps (lane 32 h + r
+ *                              holds channels 8h..8h+7 of output 32 blk + r), the pack of gn_conv3d_gcr_split; planes by the residual chain
+ *                              p = rn(r), r -= float(p), round to nearest even; mode GN_SPLIT_F16X2 / GN_SPLIT_BF16X2 / GN_SPLIT_BF16X3;
+ *                              out_scale [Cout] (all 1 for the bf16 modes)
+ *   gn_weight_pack_split_wino  the same range -> [c_n/16][36 steps = (j * 3 + kd) * 3 + kh][Cout/32][2 planes][h][r][8] + six zero steps, the
+ *                              literal-form pack of gn_conv3d_gcr_split_wino: the F(2,3) positions (g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2)
+ *                              in fp64, row scale over the TRANSFORMED row, one rounding to fp32 after scaling, two fp16 planes; out_scale [Cout]
+ *   gn_weight_pack_upconv      input channels [c0, Cin) = C1 -> [C1/16][tap 4 iz + 2 iy + ix][class 4 pz + 2 py + px][Cout/32][2 planes][h][r][8],
+ *                              the pack of gn_upconv_partial: the 27 fine taps merged in fp64 into the 2 x 2 x 2 coarse taps of each parity
+ *                              class, each merged tap rounded to fp32 once; one scale per (class, output): out_scale [8 * Cout];
+ *                              mode GN_SPLIT_F16X2 / GN_SPLIT_BF16X2
+ * Row scale (fp16 planes): 2^k with k from the exponent field of the row maximum m, so that m 2^k lies in [1, 2); 1 for a zero or
+ * non-finite maximum; k clamped to +-100.  The host builders document the same rule but compute exp2(-floor(log2(m))), which rounds up for
+ * m a few ulps below a power of two (fp32: two ulps below 2^-4, four below 2^-10): there the host leaves the maximum in [0.5, 1) and its
+ * out_scale is twice this one.  Both decompositions are exact; away from those rows the packs agree bit for bit.
+ * pack: 16-byte aligned, at least gn_weight_pack_*_bytes (0: widths the entries refuse).  GN_EINVAL: c_n % 16 != 0, Cout % 32 != 0, a
+ * channel range outside the weight, an unknown mode. */
+size_t gn_weight_pack_split_bytes(int c_n, int Cout, int mode);
+size_t gn_weight_pack_split_wino_bytes(int c_n, int Cout);
+size_t gn_weight_pack_upconv_bytes(int C1, int Cout);
+int gn_weight_pack_split(const float *w, int Cout, int Cin, int c_lo, int c_n, int mode, void *pack, size_t pack_bytes, float *out_scale,
+                         void *stream);
+int gn_weight_pack_split_wino(const float *w, int Cout, int Cin, int c_lo, int c_n, void *pack, size_t pack_bytes, float *out_scale,
+                              void *stream);
+int gn_weight_pack_upconv(const float *w, int Cout, int Cin, int c0, int mode, void *pack, size_t pack_bytes, float *out_scale, void *stream);
+
+/* The pieces of create_conv's layer orders other than 'gcr'(components/unet3d.py:19-73: 'cr', 'crg', 'cl', 'ce', 'bcr', ...) that the fused conv
  * kernels do not cover -- a learnable conv bias, LeakyReLU(0.1) / ELU, a normalisation BEHIND the non-linearity:
  * y = act(x * a[b][c] + d[b][c] + bias[c]) over channel-last [B][V][C] (C % 4 == 0); a / d ([B][C], together) and bias ([C]) may be NULL;
  * act: 0 none, 1 ReLU, 2 LeakyReLU(0.1), 3 ELU(alpha 1).  In place when out == x. */

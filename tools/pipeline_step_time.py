@@ -85,6 +85,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--strict-fp32-forward", action="store_true", help="the UNet's forward in arith.strict_fp32() instead of the model's arithmetic")
+    ap.add_argument("--device-packs", action="store_true", help="the UNet's static weight packs built on the device (arith.device_packs) instead of on the host")
     ap.add_argument("--commit", default=None, help="recorded as it is (default: git rev-parse of the tree, when there is one)")
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--merge", action="store_true", help="with --kernel-stats and --out: add the share to the existing file, time nothing")
@@ -111,6 +112,8 @@ def main():
                   gt_volume_value=torch.rand(a.batch, a.queries, generator=g), surf_query_points=torch.rand(a.batch, a.queries, 3, generator=g),
                   gt_sim_points=0.3 * torch.randn(a.batch, a.queries, 3, generator=g)).to(dev)
     opt = model.configure_optimizers()
+    if a.device_packs:
+        model.arith = model.arith.replace(device_packs=True)
     arith = model.arith.strict_fp32() if a.strict_fp32_forward else None
     rows, host_rows = [], []
     for i in range(a.warmup + a.steps):
@@ -121,7 +124,7 @@ def main():
             host_rows.append(host)
     second = [p for n, p in model.named_parameters() if not n.startswith("pointnet2_nocs.")]
     out = {"clock": time.strftime("%Y-%m-%d %H:%M:%S %Z"), "commit": a.commit or commit(), "device": torch.cuda.get_device_name(0), "batch": a.batch,
-           "points": a.points, "queries": a.queries, "grid": a.grid, "reduce_method": "max", "unet_forward": "fp32" if a.strict_fp32_forward else model.arith.conv_name, "steps": a.steps, "warmup": a.warmup,
+           "points": a.points, "queries": a.queries, "grid": a.grid, "reduce_method": "max", "unet_forward": "fp32" if a.strict_fp32_forward else model.arith.conv_name, "device_packs": model.arith.device_packs, "steps": a.steps, "warmup": a.warmup,
            "trained_parameters": sum(p.numel() for p in second), "trained_tensors": len(second), "parts": list(PARTS)}
     out.update(summarise(rows, PARTS))
     # the host's own time to issue each part: where it is close to the part's stream time, the part is bound by the host, not by its kernels
