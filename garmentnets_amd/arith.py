@@ -26,9 +26,12 @@ global mutable state except immutable LUTs).  ``DEFAULT`` is read from the envir
                        epilogue).  Off: those layers take the direct x-strip kernel (csrc/unet_split.hip)
     polyphase_upconv   polyphase form of the decoders' first convolutions (csrc/upconv.hip)
     fold_final_conv    the decoders absorb the UNet's final 1x1x1 convolution into their first layer (conv_implicit_wnf.UNetResult)
-    fused_lattice      lattice queries sampled INSIDE the decoder-MLP kernel (gn_implicit_decode_lattice_split, no sampled-row buffer in
-                       HBM; bit-identical).  OFF by default: measured 16.57 vs 16.48 ms per 16 x 128^3 lattices -- the gather's LDS traffic and the
-                       3-stage weight ring cost the decoder kernel what the separate sampler launch costs
+    fused_lattice      (f16x2 decoder) lattice queries sampled INSIDE the decoder-MLP kernel (gn_implicit_decode_lattice_split): the kernel walks bricks of
+                       4 x 8 x 8 lattice points, a brick's voxel box is DMA'd into LDS while the previous brick is multiplied and the rows are interpolated
+                       out of LDS -- one launch per garment, no sampled-row buffer in HBM; bit-identical to the sampler + decoder pair
+                       (tests/test_lattice_brick.py).  ON by default (measured 12.68 vs 13.72 ms per 16 x 128^3 lattices, 1.5 ms per step end to end: profiles/lattice_brick_ab.txt; DESIGN.md "Lattice brick inside the decoder
+                       kernel").  It applies when the lattice is at least as fine as the volume (ops.lattice_split_supported); off, GARMENTNETS_FUSED_LATTICE=0
+                       or a coarser lattice: the brick sampler feeds the decoder through a row buffer
     ggm_fp32           the batched Gaussian gradient magnitude accumulates its taps in fp32 instead of scipy's fp64 (gn_ggm3d_batch_ex, round 6).  OFF by
                        default: the default is scipy's arithmetic bit for bit; on, `volume_gradient_magnitude` is 1e-6-class against it (meshes unchanged)
     device_packs       the static split-operand weight packs of the UNet's convolutions (direct, Winograd, polyphase) are built by HIP kernels from the
@@ -66,7 +69,7 @@ class Arith:
     winograd32: bool = True
     polyphase_upconv: bool = True
     fold_final_conv: bool = True
-    fused_lattice: bool = False
+    fused_lattice: bool = True
     ggm_fp32: bool = False
     device_packs: bool = False
 
@@ -91,7 +94,7 @@ class Arith:
                    decode_mode=_env_choice("GARMENTNETS_DECODE_MODE", "f16x2", DECODE_MODES),
                    sparse_first_conv=_env_flag("GARMENTNETS_SPARSE_CONV"), affine_in_weights=_env_flag("GARMENTNETS_AFFINE_IN_WEIGHTS"),
                    winograd=_env_flag("GARMENTNETS_WINOGRAD"), winograd32=_env_flag("GARMENTNETS_WINOGRAD32"), polyphase_upconv=_env_flag("GARMENTNETS_POLYPHASE"),
-                   fold_final_conv=_env_flag("GARMENTNETS_FOLD_FINAL_CONV"), fused_lattice=_env_flag("GARMENTNETS_FUSED_LATTICE", False),
+                   fold_final_conv=_env_flag("GARMENTNETS_FOLD_FINAL_CONV"), fused_lattice=_env_flag("GARMENTNETS_FUSED_LATTICE"),
                    ggm_fp32=_env_flag("GARMENTNETS_GGM_FP32", False), device_packs=_env_flag("GARMENTNETS_DEVICE_PACKS", False))
 
     def replace(self, **kw):

@@ -45,55 +45,59 @@ struct DecSplitArgs {
     const float *xscale;             // NULL or device {s_x, 1 / s_x, unsafe, 0}: the garment's input scale (exact power of two); unsafe != 0:
                                      // this kernel does nothing (the caller's gated fp32 kernel computes the rows instead)
     float *out; int ldo;
-    // lattice form (LAT): the rows are not read from xin but sampled here -- lattice point m0 + m of the (Q,Q,Q) grid of predict.py:145-147 from
-    // the channel-last volume vol [D][H][W][32] (trilinear, border, align_corners: the arithmetic of decode.hip, bit for bit)
+    // lattice form (LAT): the rows are not read from xin but sampled here -- the lattice points of the (Q,Q,Q) grid of predict.py:145-147 from the
+    // channel-last volume vol [D][H][W][32] (trilinear, border, align_corners: the arithmetic of decode.hip, bit for bit).  A tile is a BRICK of
+    // DS_BX x DS_BY x DS_BZ lattice points (i, j, k); row ((i Q + j) Q + k) - m0 of `out` is stored when it lies in [0, M)
     const float *vol; int D, H, W, Q; long long m0;
+    int i_lo, nbj, nbk; long long lat_tiles;     // first lattice slab i of the row range; bricks along j and k; bricks in all
     // blockIdx.y: one row set of a batch (gn_implicit_decode_split_batch: the surface queries of every garment of a batch in ONE launch) with its own rows,
     // outputs and input scale; strides 0 / grid.y 1 for the single call
     long long xin_bs, out_bs; int xscale_bs;
 };
 
-// ---- lattice sampling (LAT).  A lane owns 16 channels of its query: 8h..8h+7 and 16+8h..16+8h+7 = four float4 per corner.
-struct LatQuery {
-    unsigned goff;                   // byte offset of corner (x0, y0, z0), channel 8h, inside the volume (< 2^32: checked on the host)
-    float wx0, wx1, wy0, wy1, wz0, wz1;
-    unsigned ok1;                    // bit 0 / 1 / 2: x0+1 / y0+1 / z0+1 inside the volume (the lower corners always are, after the border clamp)
-};
+// ---- lattice sampling (LAT): the brick sampler of decode.hip (trilinear_brick_kernel) inside the decoder.  Neighbouring lattice points share almost
+// all of their corners when the lattice is at least as fine as the volume (Q >= D, H, W: spacing <= 1 voxel), so the brick's voxel box -- at most
+// points + 2 per axis -- is DMA'd into LDS once per tile and every corner is a ds_read_b128.  Lattice axis i indexes the volume's LAST axis (x).
+#define DS_BX 4
+#define DS_BY 8
+#define DS_BZ 8
+#define DS_LAT_TILE (DS_BX * DS_BY * DS_BZ)          // 256 queries = 8 waves
+#define DS_EX (DS_BX + 2)                            // the box in LDS: [DS_EZ][DS_EY][DS_EX] voxels of 128 B, fixed strides
+#define DS_EY (DS_BY + 2)
+#define DS_EZ (DS_BZ + 2)
+#define DS_BRICK_PIECES 10                           // DMA instructions (1 KB = 8 voxels) per wave per brick: 8 waves x 10 x 8 = 640 >= 600 voxels
+#define DS_BRICK_BYTES (8 * DS_BRICK_PIECES * 1024)
+static_assert(DS_EX * DS_EY * DS_EZ * 128 <= DS_BRICK_BYTES, "the padded box must hold the whole brick");
 
-__device__ __forceinline__ LatQuery lat_setup(const DecSplitArgs &p, long long m, int h) {
-    const unsigned g = (unsigned)(p.m0 + m), uq = (unsigned)p.Q;          // Q^3 < 2^32 (checked on the host): 32-bit divides
-    const unsigned gq = g / uq;
-    const int k = (int)(g - gq * uq), i = (int)(gq / uq), j = (int)(gq - (unsigned)i * uq);
-    const float sc = __fdiv_rn(1.0f, __fsub_rn((float)p.Q, 1.0f));
-    const float qx = __fadd_rn(__fmul_rn((float)i, sc), -0.0f), qy = __fadd_rn(__fmul_rn((float)j, sc), -0.0f), qz = __fadd_rn(__fmul_rn((float)k, sc), -0.0f);
-    const float ix = gn_tri_src_index(qx, p.W), iy = gn_tri_src_index(qy, p.H), iz = gn_tri_src_index(qz, p.D);     // component 0 indexes the LAST volume axis
-    const GnTriCell t = gn_tri_cell(ix, iy, iz);
-    const int x0 = t.x0, y0 = t.y0, z0 = t.z0;
-    LatQuery q;
-    q.wx0 = t.wx[0]; q.wx1 = t.wx[1]; q.wy0 = t.wy[0]; q.wy1 = t.wy[1]; q.wz0 = t.wz[0]; q.wz1 = t.wz[1];
-    q.ok1 = (x0 + 1 < p.W ? 1u : 0u) | (y0 + 1 < p.H ? 2u : 0u) | (z0 + 1 < p.D ? 4u : 0u);
-    q.goff = ((unsigned)((z0 * p.H + y0) * p.W + x0) * 32u + 8u * (unsigned)h) * 4u;
-    return q;
+__device__ __forceinline__ float lat_coord(int i, int Q) {                // decode.hip's tb_coord / tri_query
+    const float sc = __fdiv_rn(1.0f, __fsub_rn((float)Q, 1.0f));
+    return __fadd_rn(__fmul_rn((float)i, sc), -0.0f);
 }
-__device__ __forceinline__ bool lat_ok(const LatQuery &q, int c) { return ((c & 1) == 0 || (q.ok1 & 1u)) && ((c & 2) == 0 || (q.ok1 & 2u)) && ((c & 4) == 0 || (q.ok1 & 4u)); }
-// gn_tri_weight on the record's scalar copies (they are what travels through LDS; a GnTriCell inside the record changed the lattice kernel's code)
-__device__ __forceinline__ float lat_weight(const LatQuery &q, int c) {
-    return __fmul_rn(__fmul_rn((c & 1) ? q.wx1 : q.wx0, (c & 2) ? q.wy1 : q.wy0), (c & 4) ? q.wz1 : q.wz0);
+struct LatBox { int i0, j0, k0, lx, ly, lz; };       // first lattice point and lowest voxel of brick `tile`
+__device__ __forceinline__ LatBox lat_box(const DecSplitArgs &p, unsigned tile) {
+    const unsigned bk = tile % (unsigned)p.nbk, t2 = tile / (unsigned)p.nbk, bj = t2 % (unsigned)p.nbj, bi = t2 / (unsigned)p.nbj;
+    LatBox b;
+    b.i0 = p.i_lo + (int)bi * DS_BX; b.j0 = (int)bj * DS_BY; b.k0 = (int)bk * DS_BZ;
+    b.lx = (int)floorf(gn_tri_src_index(lat_coord(b.i0, p.Q), p.W));
+    b.ly = (int)floorf(gn_tri_src_index(lat_coord(b.j0, p.Q), p.H));
+    b.lz = (int)floorf(gn_tri_src_index(lat_coord(b.k0, p.Q), p.D));
+    return b;
 }
-// byte offset of corner c (a corner outside the volume reads corner 0: its value is never used)
-__device__ __forceinline__ unsigned lat_corner(const DecSplitArgs &p, const LatQuery &q, int c) {
-    return lat_ok(q, c) ? q.goff + (unsigned)((((c >> 2) * p.H + ((c >> 1) & 1)) * p.W + (c & 1)) * 128) : q.goff;
-}
-// the four float4 of one corner, issued from inline asm (scalar base + 32-bit offset): invisible to hipcc's vmcnt bookkeeping, which would
-// otherwise drain the weight-DMA ring at every use; the caller waits by hand (counted s_waitcnt) and pins the first use behind that wait
-// half a corner (2 float4 = 8 of the lane's 16 channels; half 0: channels 8h.., half 1: 16 + 8h..)
-__device__ __forceinline__ void lat_issue(const float *vol, unsigned off, int half, f32x4 (&t)[2]) {
-    if (half == 0) {
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(t[0]) : "v"(off), "s"(vol) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(t[1]) : "v"(off), "s"(vol) : "memory");
-    } else {
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:64" : "=v"(t[0]) : "v"(off), "s"(vol) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:80" : "=v"(t[1]) : "v"(off), "s"(vol) : "memory");
+// the brick's box -> LDS: instruction n of wave w fills voxels [(8 n + w) 8, + 8) of the box in linear order, lane = voxel * 8 + 16-byte slot.  Voxels
+// past the volume's upper faces (and the 40 pad voxels past the box) re-read the clamped voxel: every address stays inside the volume.  Slot s of box
+// voxel (vx, vy, vz) holds piece s ^ (vz & 7): lanes of a wave differ in z first, so their reads of one piece spread over the banks.
+__device__ __forceinline__ void lat_issue_brick(const DecSplitArgs &p, const LatBox &b, int wave, int lane, unsigned lds_brick) {
+    // (opaque per call: hipcc otherwise hoists the 10 voxel coordinates of a lane out of the tile loop and keeps 30 registers alive across the MFMA stream)
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int n = 0; n < DS_BRICK_PIECES; ++n) {
+        const unsigned inst = (unsigned)(n * 8 + wave);
+        const unsigned v = inst * 8 + ((unsigned)lane >> 3);
+        const unsigned vx = v % DS_EX, vr = v / DS_EX, vy = vr % DS_EY, vz = vr / DS_EY;
+        const int x = min(b.lx + (int)vx, p.W - 1), y = min(b.ly + (int)vy, p.H - 1), z = min(b.lz + (int)vz, p.D - 1);
+        const unsigned pc = ((unsigned)lane & 7u) ^ (vz & 7u);
+        const unsigned off = ((unsigned)((z * p.H + y) * p.W + x) * 32u + pc * 4u) * 4u;      // < 2^32: checked on the host
+        gn_glds16_s(p.vol, off, lds_brick + inst * 1024);
     }
 }
 
@@ -109,7 +113,7 @@ __device__ __forceinline__ void ds_bias_relu4(float a0, float a1, float a2, floa
 // convolution (32 -> 128, linear) has been folded into the first layer on the host (pack_decode_split(..., final_conv)): the
 // decoder then reads 32-channel rows sampled from the PRE-final feature volume.
 template <int OUTC, int K0G, bool LAT = false>
-__global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit_decode_split_kernel(DecSplitArgs p) {
+__global__ __launch_bounds__(LAT ? 512 : 256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit_decode_split_kernel(DecSplitArgs p) {
     static_assert(!LAT || (K0G == 2 && OUTC == 1), "the lattice form exists for the folded scalar decoder");
     // K0G = 2: the first-layer planes are 16 registers instead of 64, which leaves room for TWO workgroups per CU (2 waves per SIMD:
     // one wave's epilogue / load work overlaps the other's MFMAs by itself) with a single accumulator set and an immediate epilogue
@@ -120,18 +124,20 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
     constexpr int NRAW = 2 * K0G;                                          // float4 row loads per lane per tile
     constexpr int RAW_STAGE = NSTAGE - 8;                                  // where the next tile's rows are requested
     static_assert(NSTEPS % 4 == 0 && (K0G == 2 || K0G == 8), "stage = 4 k-group steps");
-    // LAT: a 3-stage ring (two stages ahead) makes room in LDS for the gather's accumulators [4][256] float4 and its per-lane query record
-    // [8][256] dwords: the kernel has no REGISTERS to spare for them (239 of 256 without the gather)
-    constexpr int RING = LAT ? 3 : DS_RING;
-    constexpr int TAB_BYTES = ((TABN * 4 + 15) / 16) * 16, LATB = LAT ? (16 + 8) * 1024 : 0;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[RING * DS_STAGE_BYTES + TAB_BYTES + LATB];
-    float *const tab = reinterpret_cast<float *>(smem + RING * DS_STAGE_BYTES);
-    float4 *const lacc = reinterpret_cast<float4 *>(smem + RING * DS_STAGE_BYTES + TAB_BYTES);           // [4][256]: conflict-free b128
-    unsigned *const lrec = reinterpret_cast<unsigned *>(smem + RING * DS_STAGE_BYTES + TAB_BYTES + 16 * 1024);   // [8][256]
+    // LAT: EIGHT waves (one workgroup per CU, still two waves per SIMD) share one weight ring -- a wave DMAs 2 of a stage's 16 fragments -- and one
+    // brick box; a tile is a brick of 256 lattice points.  LDS: ring 65536 + box 81920 + table 3088 = 150544 of 163840 bytes
+    constexpr int NW = LAT ? 8 : 4, NT = 64 * NW, PW = 16 / NW, TILE = 32 * NW;
+    static_assert(!LAT || TILE == DS_LAT_TILE, "one query per lane pair");
+    constexpr int RING = DS_RING;
+    constexpr int TAB_BYTES = ((TABN * 4 + 15) / 16) * 16, LATB = LAT ? DS_BRICK_BYTES : 0;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[RING * DS_STAGE_BYTES + LATB + TAB_BYTES];
+    const unsigned char *const brick = smem + RING * DS_STAGE_BYTES;
+    float *const tab = reinterpret_cast<float *>(smem + RING * DS_STAGE_BYTES + LATB);
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long long ntiles = (p.M + DS_TILE - 1) / DS_TILE;
+    const long long ntiles = LAT ? p.lat_tiles : (p.M + TILE - 1) / TILE;
+    const unsigned lds_brick = lds_base + RING * DS_STAGE_BYTES;
 
     if (p.xin) p.xin += (long long)blockIdx.y * p.xin_bs;
     p.out += (long long)blockIdx.y * p.out_bs;
@@ -139,51 +145,32 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
     if (p.xscale && p.xscale[2] != 0.f) return;     // wave-uniform: the whole grid leaves (gn_decoder_input_scale's verdict)
     const float sx = p.xscale ? p.xscale[0] : 1.f, inv_sx = p.xscale ? p.xscale[1] : 1.f;
     // the bias entries (all of tab1, row 0 of every tab2 block) enter in the scaled units of the chain
-    for (int i = tid; i < TABN; i += 256) {
+    for (int i = tid; i < TABN; i += NT) {
         const bool bias = i < TAB1 || (i < TAB1 + TAB2 && ((i - TAB1) / 16) % (1 + OUTC) == 0);
         tab[i] = bias ? __fmul_rn(p.tab[i], sx) : p.tab[i];
     }
 
-    // each wave DMAs 4 of a stage's 16 fragments.  Stage s of tile n sits in ring slot (n * NSTAGE + s) % 4: `sb` carries n * NSTAGE
-    const unsigned char *wsrc = p.wp + (wave * 4) * 1024;   // wave-uniform (SGPRs); the lane adds 16 * lane
+    // each wave DMAs PW of a stage's 16 fragments.  Stage s of tile n sits in ring slot (n * NSTAGE + s) % 4: `sb` carries n * NSTAGE
+    const unsigned char *wsrc = p.wp + (wave * PW) * 1024;  // wave-uniform (SGPRs); the lane adds 16 * lane
     const unsigned lane16 = lane * 16;
     int sb = 0;                                     // stays 0 (and folds away) when NSTAGE % 4 == 0
     constexpr bool SB_ZERO = (NSTAGE % RING == 0);
-    static_assert(!LAT || SB_ZERO, "the 3-stage ring is indexed with compile-time slots");
 #define DS_SB (SB_ZERO ? 0 : sb)
 #define DS_ISSUE(STAGE, SLOT)                                                                                                  \
-    gn_glds16x4_s(wsrc + (size_t)(STAGE) * DS_STAGE_BYTES, lane16, lds_base + (SLOT) * DS_STAGE_BYTES + (wave * 4) * 1024);
-    DS_ISSUE(0, 0) DS_ISSUE(1, 1) DS_ISSUE(2, 2)
-    if (!LAT) { DS_ISSUE(3, 3) }
+    if constexpr (LAT) gn_glds16x2_s(wsrc + (size_t)(STAGE) * DS_STAGE_BYTES, lane16, lds_base + (SLOT) * DS_STAGE_BYTES + (wave * PW) * 1024); \
+    else gn_glds16x4_s(wsrc + (size_t)(STAGE) * DS_STAGE_BYTES, lane16, lds_base + (SLOT) * DS_STAGE_BYTES + (wave * PW) * 1024);
+    DS_ISSUE(0, 0) DS_ISSUE(1, 1) DS_ISSUE(2, 2) DS_ISSUE(3, 3)
 
-    // first tile's rows: lane (h, r) holds the 8 channels 16g + 8h .. + 7 of query r for g = 0..K0G-1
+    // first tile's rows: lane (h, r) holds the 8 channels 16g + 8h .. + 7 of query r for g = 0..K0G-1.  LAT: the first tile's box instead
     float4 raw[NRAW];
-    {
-        long long m = (long long)blockIdx.x * DS_TILE + wave * 32 + r;
+    if constexpr (LAT) {
+        lat_issue_brick(p, lat_box(p, blockIdx.x), wave, lane, lds_brick);
+    } else {
+        long long m = (long long)blockIdx.x * TILE + wave * 32 + r;
         if (m >= p.M) m = p.M - 1;
-        if constexpr (LAT) {                        // first tile: sampled synchronously (plain loads; the prologue is drained below anyway)
-            const LatQuery lq = lat_setup(p, m, h);
+        const float4 *row = reinterpret_cast<const float4 *>(p.xin + m * p.ldxin + 8 * h);
 #pragma unroll
-            for (int g = 0; g < NRAW; ++g) raw[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (lat_ok(lq, c)) {
-                    const float4 *cp = reinterpret_cast<const float4 *>(reinterpret_cast<const unsigned char *>(p.vol) + lat_corner(p, lq, c));
-                    const float w = lat_weight(lq, c);
-                    const float4 v[4] = {cp[0], cp[1], cp[4], cp[5]};
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        raw[g].x = __fadd_rn(raw[g].x, __fmul_rn(v[g].x, w));
-                        raw[g].y = __fadd_rn(raw[g].y, __fmul_rn(v[g].y, w));
-                        raw[g].z = __fadd_rn(raw[g].z, __fmul_rn(v[g].z, w));
-                        raw[g].w = __fadd_rn(raw[g].w, __fmul_rn(v[g].w, w));
-                    }
-                }
-        } else {
-            const float4 *row = reinterpret_cast<const float4 *>(p.xin + m * p.ldxin + 8 * h);
-#pragma unroll
-            for (int g = 0; g < K0G; ++g) { raw[2 * g] = row[4 * g]; raw[2 * g + 1] = row[4 * g + 1]; }
-        }
+        for (int g = 0; g < K0G; ++g) { raw[2 * g] = row[4 * g]; raw[2 * g + 1] = row[4 * g + 1]; }
     }
     GN_WAIT_ALL();                                   // vmcnt(0) lgkmcnt(0): prologue DMAs + table stores
     __syncthreads();
@@ -194,6 +181,65 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
     for (int f = 0; f < 4; ++f) nA[f] = *reinterpret_cast<const uint4 *>(ring_rd + f * 1024);
 
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        unsigned orow = 0xffffffffu;                // LAT: this lane's row of `out` (none: a clamped duplicate or outside the row range)
+        if constexpr (LAT) {
+            // ---- this tile's rows out of the box: the layer-1 / layer-2 planes are dead here, so the 8 corners accumulate in registers.  tri_query's
+            // arithmetic: corners 0..7 in order, __fmul_rn / __fadd_rn; a corner past an upper face reads corner 0 (always inside, finite whenever
+            // the query's result is) with weight 0 -- acc + (+-0) == acc exactly and acc is never -0
+            const LatBox b = lat_box(p, (unsigned)tile);
+            int ql = wave * 32 + r;
+            asm volatile("" : "+v"(ql));                  // (opaque per tile: nothing of the query's setup may stay in registers across the MFMA stream)
+            const int i = b.i0 + (ql >> 6), j = b.j0 + ((ql >> 3) & 7), k = b.k0 + (ql & 7);
+            const bool live = i < p.Q && j < p.Q && k < p.Q;               // edge bricks: clamped duplicates are computed and not stored
+            const int ic = min(i, p.Q - 1), jc = min(j, p.Q - 1), kc = min(k, p.Q - 1);
+            const long long rel = (long long)(((unsigned)ic * (unsigned)p.Q + (unsigned)jc) * (unsigned)p.Q + (unsigned)kc) - p.m0;
+            if (live && rel >= 0 && rel < p.M) orow = (unsigned)rel;
+            const float ix = gn_tri_src_index(lat_coord(ic, p.Q), p.W), iy = gn_tri_src_index(lat_coord(jc, p.Q), p.H), iz = gn_tri_src_index(lat_coord(kc, p.Q), p.D);
+            const GnTriCell t = gn_tri_cell(ix, iy, iz);
+            const int vx0 = t.x0 - b.lx, vy0 = t.y0 - b.ly, vz0 = t.z0 - b.lz;
+            const bool okx = t.x0 + 1 < p.W, oky = t.y0 + 1 < p.H, okz = t.z0 + 1 < p.D;   // the lower corners always are inside, after the border clamp
+#pragma unroll
+            for (int g = 0; g < 4; ++g) raw[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            int co[8], ckey[8];
+            float cw[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
+                const bool okc = (!dx || okx) && (!dy || oky) && (!dz || okz);
+                cw[c] = okc ? gn_tri_weight(t, c) : 0.f;
+                const int m = -(int)okc;
+                const int cz = vz0 + (dz & m);
+                co[c] = ((cz * DS_EY + vy0 + (dy & m)) * DS_EX + vx0 + (dx & m)) * 128;
+                ckey[c] = (cz & 7) << 4;
+                asm volatile("" : "+v"(co[c]), "+v"(ckey[c]));     // (opaque: hipcc otherwise turns the selects into exec-masked loads)
+            }
+            // all 32 ds_read_b128 in flight at once (128 registers: the planes' own), then the sums
+            float4 cv[8][4];
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {             // the lane's pieces 2h, 2h + 1, 4 + 2h, 5 + 2h (channels 8h.. and 16 + 8h..)
+                    const int piece = 2 * h + (g & 1) + 4 * (g >> 1);
+                    cv[c][g] = *reinterpret_cast<const float4 *>(brick + co[c] + ((piece << 4) ^ ckey[c]));
+                }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    // (two v_pk_mul_f32 + two v_pk_add_f32: the same IEEE products and sums as __fmul_rn / __fadd_rn -- the build does not contract -- in half the issue slots)
+                    const f32x2 w2 = (f32x2){cw[c], cw[c]};
+                    const f32x2 lo = (f32x2){raw[g].x, raw[g].y} + (f32x2){cv[c][g].x, cv[c][g].y} * w2;
+                    const f32x2 hi = (f32x2){raw[g].z, raw[g].w} + (f32x2){cv[c][g].z, cv[c][g].w} * w2;
+                    raw[g] = make_float4(lo.x, lo.y, hi.x, hi.y);
+                }
+            // everybody has read the box: the NEXT tile's box (the last tile re-reads its own) goes out at once and lands under this tile's MFMAs
+            GN_WAIT_VM_LGKM0(63);                   // lgkmcnt(0); the VM queue (weight stages in flight) is left alone
+            __builtin_amdgcn_s_barrier();
+            long long tn = tile + gridDim.x;
+            if (tn >= ntiles) tn = tile;
+            lat_issue_brick(p, lat_box(p, (unsigned)tn), wave, lane, lds_brick);
+        }
         // ---- X0 planes from the prefetched rows
         uint4 x0[2][K0G], h1[2][16];
 #pragma unroll
@@ -206,11 +252,6 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
         float psum[OUTC];
 #pragma unroll
         for (int o = 0; o < OUTC; ++o) psum[o] = 0.f;
-        // LAT: the NEXT tile's rows are gathered under this tile's MFMAs -- batch b = (corner b >> 1, channel half b & 1) is issued at the hand-over
-        // of stage LAT_T0 + b and consumed at the next hand-over: 8 registers in flight; accumulators and query record live in LDS
-        f32x4 lt[2];
-        constexpr int LAT_T0 = 1, LAT_NB = 16;
-        static_assert(!LAT || LAT_T0 + LAT_NB == NSTAGE - 1, "the last batch is consumed at the tile's last hand-over");
         // two accumulator sets: the epilogue of block pair P-1 (VALU) is spread over the MFMAs of the steps that follow it
         f32x16 acc[NSETS][2];
 
@@ -270,65 +311,16 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
             } else {
                 // ---- stage hand-over: stage t+1 has landed for everybody, stage t has been read by everybody
                 // VM queue (oldest first): stage t+1, t+2, t+3 [+ the NRAW row loads issued in stage RAW_STAGE]; see the note below
-                // LAT: VM queue, oldest first, with the corner loads issued BEFORE the stage's DMAs: G(t-3) DMA(t+1) G(t-2) DMA(t+2) G(t-1) DMA(t+3);
-                // the corner issued one hand-over ago must have landed: everything but DMA(t+3)
-                // LAT (3-stage ring, the batch's two loads issued BEFORE the stage's DMAs): G(t-2) DMA(t+1) G(t-1) DMA(t+2) -> everything but DMA(t+2)
-                if (LAT) GN_WAIT_VM_LGKM0(4);
+                // LAT: 2 pieces per stage and wave, and the DS_BRICK_PIECES of the next box issued at the tile's top: see the note below
+                if (LAT) { if (t < 3) GN_WAIT_VM_LGKM0(2 * PW + DS_BRICK_PIECES); else GN_WAIT_VM_LGKM0(2 * PW); }
                 else if (t > RAW_STAGE && t <= RAW_STAGE + 3) GN_WAIT_VM_LGKM0(8 + NRAW);
                 else GN_WAIT_VM_LGKM0(8);
                 __builtin_amdgcn_s_barrier();
-                if constexpr (LAT) {
-                    if (t == LAT_T0) {                                    // next tile's query (clamped: the last tile re-samples its own)
-                        long long tn = tile + gridDim.x;
-                        if (tn >= ntiles) tn = tile;
-                        long long m = tn * DS_TILE + wave * 32 + r;
-                        if (m >= p.M) m = p.M - 1;
-                        const LatQuery lq = lat_setup(p, m, h);
-                        lrec[0 * 256 + tid] = lq.goff; lrec[1 * 256 + tid] = lq.ok1;
-                        lrec[2 * 256 + tid] = __float_as_uint(lq.wx0); lrec[3 * 256 + tid] = __float_as_uint(lq.wx1);
-                        lrec[4 * 256 + tid] = __float_as_uint(lq.wy0); lrec[5 * 256 + tid] = __float_as_uint(lq.wy1);
-                        lrec[6 * 256 + tid] = __float_as_uint(lq.wz0); lrec[7 * 256 + tid] = __float_as_uint(lq.wz1);
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg) lacc[gg * 256 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                    if (t >= LAT_T0 && t <= LAT_T0 + LAT_NB) {
-                        __builtin_amdgcn_sched_barrier(0);               // the gather's temporaries live between these two fences only
-                        const unsigned goff = lrec[tid], ok1 = lrec[256 + tid];
-                        if (t > LAT_T0) {                                 // consume batch t - LAT_T0 - 1: accumulators read-modify-written in LDS
-                            const int bb = t - LAT_T0 - 1, c = bb >> 1, half = bb & 1;
-                            asm volatile("" : "+v"(lt[0]));               // first use of the asm loads: behind the hand-over's wait
-                            asm volatile("" : "+v"(lt[1]));
-                            const bool okc = ((c & 1) == 0 || (ok1 & 1u)) && ((c & 2) == 0 || (ok1 & 2u)) && ((c & 4) == 0 || (ok1 & 4u));
-                            // branch-free (a divergent branch here would cut the unrolled MFMA stream into basic blocks): a corner outside the
-                            // volume gets weight 0 on corner 0's (finite) data -- acc + (+-0) == acc exactly, acc is never -0
-                            const float wx = __uint_as_float(lrec[(2 + (c & 1)) * 256 + tid]);
-                            const float wy = __uint_as_float(lrec[(4 + ((c >> 1) & 1)) * 256 + tid]);
-                            const float wz = __uint_as_float(lrec[(6 + (c >> 2)) * 256 + tid]);
-                            const float w = okc ? __fmul_rn(__fmul_rn(wx, wy), wz) : 0.f;
-#pragma unroll
-                            for (int i2 = 0; i2 < 2; ++i2) {
-                                float4 a4 = lacc[(2 * half + i2) * 256 + tid];
-                                a4.x = __fadd_rn(a4.x, __fmul_rn(lt[i2].x, w));
-                                a4.y = __fadd_rn(a4.y, __fmul_rn(lt[i2].y, w));
-                                a4.z = __fadd_rn(a4.z, __fmul_rn(lt[i2].z, w));
-                                a4.w = __fadd_rn(a4.w, __fmul_rn(lt[i2].w, w));
-                                lacc[(2 * half + i2) * 256 + tid] = a4;
-                            }
-                        }
-                        if (t < LAT_T0 + LAT_NB) {                        // issue batch t - LAT_T0 (a corner outside the volume reads corner 0: never used)
-                            const int bb = t - LAT_T0, c = bb >> 1, half = bb & 1;
-                            const bool okc = ((c & 1) == 0 || (ok1 & 1u)) && ((c & 2) == 0 || (ok1 & 2u)) && ((c & 4) == 0 || (ok1 & 4u));
-                            const unsigned off = okc ? goff + (unsigned)((((c >> 2) * p.H + ((c >> 1) & 1)) * p.W + (c & 1)) * 128) : goff;
-                            lat_issue(p.vol, off, half, lt);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
                 DS_ISSUE((t + RING) % NSTAGE, (t + DS_SB) % RING)
                 if (!LAT && t == RAW_STAGE) {                             // next tile's rows (clamped: the last tile re-reads its own)
                     long long tn = tile + gridDim.x;
                     if (tn >= ntiles) tn = tile;
-                    long long m = tn * DS_TILE + wave * 32 + r;
+                    long long m = tn * TILE + wave * 32 + r;
                     if (m >= p.M) m = p.M - 1;
                     const float4 *row = reinterpret_cast<const float4 *>(p.xin + m * p.ldxin + 8 * h);
 #pragma unroll
@@ -369,17 +361,13 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
         }
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) epilogue(7, qd);
-        if constexpr (LAT) {
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) raw[gg] = lacc[gg * 256 + tid];      // the next tile's sampled rows
-        }
         if (!SB_ZERO) sb = (sb + NSTAGE) % RING;
         // ---- output layer: the two lane halves hold disjoint unit sets of the same query
-        const long long m = tile * DS_TILE + wave * 32 + r;
+        const long long m = LAT ? (long long)orow : tile * TILE + wave * 32 + r;
 #pragma unroll
         for (int o = 0; o < OUTC; ++o) {
             const float s = psum[o] + __shfl_xor(psum[o], 32);
-            if (h == 0 && m < p.M) {
+            if (h == 0 && (LAT ? orow != 0xffffffffu : m < p.M)) {
                 const float *t3 = tab + TAB1 + TAB2;
                 float y = gn_relu(__fadd_rn(__fmul_rn(s, inv_sx), t3[o]));
                 y = __fadd_rn(__fmul_rn(y, t3[OUTC + o]), t3[2 * OUTC + o]);
@@ -398,6 +386,11 @@ __global__ __launch_bounds__(256, (K0G <= 2 && OUTC == 1) ? 2 : 1) void implicit
 // younger than the stage being waited for, so 8 + NRAW may remain; after that they are older and the plain count applies again
 // (they had four stages = 24 x 4 MFMAs to arrive).  The wrap-around (stage (t+4) % NSTAGE belongs to the NEXT tile; the last tile
 // fetches four stages it never uses) keeps every count independent of the tile.
+// LAT: a wave issues PW = 2 pieces per stage, and the 10 pieces of the next tile's box at the top of the tile, i.e. right after the stages 1, 2, 3
+// requested at the previous tile's last three hand-overs.  Queue at hand-over 0: S1 S2 S3 B; 1: S2 S3 B S4; 2: S3 B S4 S5 -- the awaited stage is older
+// than the box, 2 PW + 10 may remain; from hand-over 3 on (B S4 S5 S6, S4 awaited) the box is older: 2 PW, which also lands the box, for everybody after
+// that hand-over's barrier, long before the next tile reads it.  The first tile's queue lacks S1..S3 (the prologue drained them): every count is then
+// merely stricter than needed.
 
 // ------------------------------------------------------------------------------------------------ [32, 512, 512, OUT]: the class-default hidden width
 // ImplicitWNFDecoder's constructor default is nn_channels = (128, 512, 512, 1) (networks/conv_implicit_wnf.py:122); with the UNet's final 1x1x1
@@ -634,22 +627,28 @@ extern "C" int gn_decoder_input_scale(const double *sumsq, int64_t V, int B, int
 }
 
 // The lattice form (the sampler inside the decoder MLP): rows m0 .. m0+M-1 of the (Q,Q,Q) lattice of predict.py:145-147, sampled from the
-// 32-channel channel-last volume by the decoder kernel itself while it multiplies the previous tile -- no sampled-row buffer in HBM.  Folded scalar
-// decoder only ([32, 256, 256, 1]: the volume decoder on the UNet's pre-final volume); bit-identical to gn_trilinear_sample + gn_implicit_decode_split.
+// 32-channel channel-last volume by the decoder kernel itself -- brick by brick out of LDS, the next brick's voxel box arriving by DMA while the current
+// one is multiplied -- no sampled-row buffer in HBM.  Folded scalar decoder only ([32, 256, 256, 1]: the volume decoder on the UNet's pre-final volume),
+// lattice at least as fine as the volume (Q >= D, H, W: what bounds a brick's box); bit-identical to gn_trilinear_sample + gn_implicit_decode_split.
+// The bricks cover the whole lattice slabs the row range touches; rows outside the range are computed and not stored.
 extern "C" int gn_implicit_decode_lattice_split(const float *vol, int D, int H, int W, int C0, int Q, int64_t m0, int64_t M, const void *wpack,
                                                 const float *tab, const float *xscale, int N1, int N2, int OUT, float *out, int ldo, void *stream) {
     GN_REQUIRE(M >= 0 && ldo >= 1 && OUT == 1 && C0 == 32 && N1 == DS_N && N2 == DS_N, "gn_implicit_decode_lattice_split: the lattice form is packed for the [32, 256, 256, 1] decoder");
     GN_REQUIRE(D > 0 && H > 0 && W > 0 && (int64_t)D * H * W * 128 < ((int64_t)1 << 32), "gn_implicit_decode_lattice_split: the volume must be addressable with 32-bit byte offsets");
     GN_REQUIRE(Q > 1 && Q <= 1024 && m0 >= 0 && m0 + M <= (int64_t)Q * Q * Q, "gn_implicit_decode_lattice_split: bad lattice range");
+    GN_REQUIRE(Q >= D && Q >= H && Q >= W, "gn_implicit_decode_lattice_split: the lattice must be at least as fine as the volume (Q >= D, H, W), got Q = %d for %d x %d x %d", Q, D, H, W);
     if (M == 0) return GN_OK;
     GN_REQUIRE(vol && wpack && tab && out, "gn_implicit_decode_lattice_split: null pointer");
     GN_REQUIRE(((uintptr_t)vol & 15) == 0, "gn_implicit_decode_lattice_split: the volume must be 16-byte aligned");
     DecSplitArgs p;
     p.xin = nullptr; p.ldxin = 0; p.M = M; p.wp = (const unsigned char *)wpack; p.tab = tab; p.xscale = xscale; p.out = out; p.ldo = ldo;
     p.vol = vol; p.D = D; p.H = H; p.W = W; p.Q = Q; p.m0 = m0; p.xin_bs = p.out_bs = 0; p.xscale_bs = 0;
-    const int64_t ntiles = gn_cdiv(M, DS_TILE);
-    const unsigned grid = (unsigned)(ntiles < 512 ? ntiles : 512);
-    hipLaunchKernelGGL((implicit_decode_split_kernel<1, 2, true>), dim3(grid), dim3(256), 0, gn_stream(stream), p);
+    const int64_t slab = (int64_t)Q * Q, i_lo = m0 / slab, i_hi = (m0 + M - 1) / slab;
+    p.i_lo = (int)i_lo; p.nbj = (int)gn_cdiv(Q, DS_BY); p.nbk = (int)gn_cdiv(Q, DS_BZ);
+    p.lat_tiles = gn_cdiv(i_hi - i_lo + 1, DS_BX) * p.nbj * p.nbk;
+    // persistent workgroups of 8 waves, one per CU
+    const unsigned grid = (unsigned)(p.lat_tiles < 256 ? p.lat_tiles : 256);
+    hipLaunchKernelGGL((implicit_decode_split_kernel<1, 2, true>), dim3(grid), dim3(512), 0, gn_stream(stream), p);
     GN_LAUNCH_CHECK("gn_implicit_decode_lattice_split");
     return GN_OK;
 }
@@ -665,7 +664,7 @@ static int implicit_decode_split_impl(const float *xin, int ldxin, int64_t M, in
     GN_REQUIRE(xin && wpack && tab && out, "gn_implicit_decode_split: null pointer");
     DecSplitArgs p;
     p.xin = xin; p.ldxin = ldxin; p.M = M; p.wp = (const unsigned char *)wpack; p.tab = tab; p.xscale = xscale; p.out = out; p.ldo = ldo;
-    p.vol = nullptr; p.D = p.H = p.W = p.Q = 0; p.m0 = 0;
+    p.vol = nullptr; p.D = p.H = p.W = p.Q = 0; p.m0 = 0; p.i_lo = p.nbj = p.nbk = 0; p.lat_tiles = 0;
     p.xin_bs = B > 1 ? M * (long long)ldxin : 0; p.out_bs = B > 1 ? M * (long long)ldo : 0; p.xscale_bs = B > 1 ? 4 : 0;
     const int64_t ntiles = gn_cdiv(M, DS_TILE);
     // persistent workgroups: two per CU when they fit (K0G = 2), else one; a batch shares the slots between its row sets (grid.y)

@@ -160,6 +160,12 @@ __device__ __forceinline__ void gn_glds16x4_s(const void *sbase, unsigned voff, 
                  "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
                  "global_load_lds_dwordx4 %0, %1 offset:3072" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
 }
+// (two pieces: the share of one of EIGHT waves in a 16-KB stage)
+__device__ __forceinline__ void gn_glds16x2_s(const void *sbase, unsigned voff, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:1024" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
+}
 // s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] = 7 (no wait) | lgkmcnt[11:8] | vmcnt_hi[15:14])
 #define GN_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | (((N) >> 4) << 14))           // vmcnt(N) lgkmcnt(0)
 #define GN_WAIT_VM_ONLY(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | 0xF00 | (((N) >> 4) << 14))    // vmcnt(N) alone (lgkmcnt field = 15: no wait)

@@ -161,11 +161,15 @@ class ImplicitWNFDecoder(PackedModule):
     """trilinear feature sampling (border, align_corners) -> MLP -- conv_implicit_wnf.py:120-149.
 
     The MLP runs as ONE kernel (gn_implicit_decode: hidden activations stay in LDS) when it has the shipped shape
-    [C0, N1, N2, out<=4] with N1, N2 multiples of 256; otherwise gn_linear per layer.  Sampling is a separate
-    high-occupancy kernel feeding it through a chunk buffer (2^20 rows x 32 channels = 134 MB: half a 128^3 lattice per launch pair; 2^18
-    rows measured 1 ms slower per 16-garment step, the whole lattice no faster) small enough to stay in the 256 MB Infinity Cache
-    (measured on MI355X, 128^3 lattice: sample 1.96 ms + MLP 4.47 ms vs 9.55 ms for sampling inside the MLP kernel,
-    where the latency-bound gathers cannot overlap the matrix-core phases of the only two resident workgroups)."""
+    [C0, N1, N2, out<=4] with N1, N2 multiples of 256; otherwise gn_linear per layer.
+
+    Lattice queries of the folded scalar decoder on the 16-bit matrix cores take ONE launch per garment (Arith.fused_lattice, the default:
+    gn_implicit_decode_lattice_split): the kernel walks bricks of 4 x 8 x 8 lattice points, a brick's voxel box arrives in LDS by DMA while the
+    previous brick is multiplied, and the rows are interpolated out of LDS -- no sampled-row buffer.  It needs a lattice at least as fine as the
+    volume (ops.lattice_split_supported(vol, pack, Q)).  Everything else -- surface queries, a coarser lattice, the fp32 decoder, fused_lattice
+    off -- samples in a separate high-occupancy kernel that feeds the MLP through a chunk buffer (2^20 rows x 32 channels = 134 MB: half a
+    128^3 lattice per launch pair; 2^18 rows measured 1 ms slower per 16-garment step, the whole lattice no faster) small enough to stay in
+    the 256 MB Infinity Cache."""
 
     ROWS_PER_CHUNK = int(os.environ.get("GARMENTNETS_DECODE_CHUNK", 1 << 20))
     fused = True
@@ -234,7 +238,7 @@ class ImplicitWNFDecoder(PackedModule):
         if layers is None:
             layers = self.packed() if self.fused else None
         split = layers is not None and layers[3] is not None and arith.decode_mode == "f16x2"
-        if query is None and split and arith.fused_lattice and ops.lattice_split_supported(vol_b, layers[3]):
+        if query is None and split and arith.fused_lattice and ops.lattice_split_supported(vol_b, layers[3], Q):
             # the lattice sampler inside the decoder kernel -- one launch per garment, no sampled-row buffer
             ops.implicit_decode_lattice_split(vol_b, Q, layers[3], out, xscale=xscale)
             if xscale is not None:          # garments the device marked unsafe for fp16 planes: the gated fp32 twin samples for itself

@@ -873,7 +873,8 @@ def implicit_decode_split(xin, pack, out=None, xscale=None):
 
 def implicit_decode_lattice_split(vol_b, Q, pack, out, xscale=None, m0=0, M=None):
     """rows m0 .. m0+M-1 of the (Q,Q,Q) lattice through the folded scalar decoder, sampled INSIDE the decoder kernel from the channel-last
-    volume vol_b [D][H][W][32] (no sampled-row buffer); bit-identical to trilinear_sample + implicit_decode_split"""
+    volume vol_b [D][H][W][32] (bricks of 4 x 8 x 8 lattice points out of LDS, no sampled-row buffer); bit-identical to trilinear_sample +
+    implicit_decode_split.  Needs Q >= D, H, W (lattice_split_supported(vol_b, pack, Q))"""
     D, H, W, C0 = vol_b.shape
     M = Q * Q * Q - m0 if M is None else M
     _lib.call("gn_implicit_decode_lattice_split", _p(_chk(vol_b, torch.float32, "vol")), D, H, W, C0, int(Q), int(m0), int(M), _p(pack.wpack), _p(pack.tab),
@@ -881,8 +882,12 @@ def implicit_decode_lattice_split(vol_b, Q, pack, out, xscale=None, m0=0, M=None
     return out
 
 
-def lattice_split_supported(vol_b, pack):
+def lattice_split_supported(vol_b, pack, Q=None):
+    """whether implicit_decode_lattice_split takes this volume and decoder pack -- and, with Q, this lattice: a brick's voxel box is bounded only when
+    the lattice is at least as fine as the volume (Q >= D, H, W), a coarser lattice keeps the sampler + decoder pair"""
     D, H, W, C0 = vol_b.shape
+    if Q is not None and not max(2, D, H, W) <= Q <= 1024:
+        return False
     return C0 == 32 and pack.out_channels == 1 and pack.hidden == 256 and D * H * W * 128 < 2 ** 32 and vol_b.is_contiguous()
 
 

@@ -503,8 +503,9 @@ int gn_implicit_decode_batch(const float *xin, int ldxin, int64_t M, int B, int 
 /* gn_implicit_decode_split with the lattice sampler INSIDE the decoder kernel (reference call site
  * networks/conv_implicit_wnf.py:137-149 under the lattice loop of predict.py:145-157): rows m0 .. m0+M-1 of the (Q,Q,Q) lattice are sampled
  * (trilinear, border, align_corners: gn_trilinear_sample's arithmetic) from the channel-last volume vol [D][H][W][32] by the kernel that
- * multiplies them -- the next tile's corner gathers ride under the current tile's MFMAs; no sampled-row buffer exists.  Folded scalar decoder
- * only ([32, 256, 256, 1]); D*H*W*128 < 2^32.  Bit-identical to gn_trilinear_sample + gn_implicit_decode_split. */
+ * multiplies them -- a tile is a brick of 4 x 8 x 8 lattice points whose voxel box is DMA'd into LDS while the previous brick is multiplied; no
+ * sampled-row buffer exists.  Folded scalar decoder only ([32, 256, 256, 1]); D*H*W*128 < 2^32; Q >= D, H, W (the lattice at least as fine as the
+ * volume: what bounds a brick's box -- an error otherwise).  Bit-identical to gn_trilinear_sample + gn_implicit_decode_split. */
 int gn_implicit_decode_lattice_split(const float *vol, int D, int H, int W, int C0, int Q, int64_t m0, int64_t M, const void *wpack,
                                      const float *tab, const float *xscale, int N1, int N2, int OUT, float *out, int ldo, void *stream);
 
