@@ -6,9 +6,11 @@ Keeps the reference's class names, constructor kwargs, sub-module names (= check
 ``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  ``validation_metrics`` gives the
 losses of the reference's infer (:405-452); ``training_step`` / ``training_metrics`` / ``configure_optimizers`` are the second stage's training step (garmentnets_amd/train_pipeline.py, imported on use: the loss gradients of gn_value_losses_bwd and optim.FusedAdam, as the first stage's train.py); visualisation is out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
 """
+import functools
 import os
 import threading
 import weakref
+from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -157,21 +159,72 @@ class UNet3D(nn.Module):
         return self.abstract_3d_unet(data)
 
 
+class DecoderPack(NamedTuple):
+    """the kernel-side parameters of one ImplicitWNFDecoder on rows of c0 channels"""
+    fp32: tuple                                  # three (w, b, sc, sh, n) layers as ops.implicit_decode takes them (csrc/decode.hip)
+    split: Optional[ops.DecodeSplitPack]         # the same layers for the 16-bit matrix cores (csrc/decode_split.hip), or None
+    c0: int
+
+    def facts(self):
+        """what decode_plan reads of it: (has a split-operand pack, c0, hidden width, out_channels)"""
+        return self.split is not None, self.c0, self.fp32[0][4], self.fp32[2][4]
+
+
+class DecodeSource(NamedTuple):
+    """what a decoder samples from: the UNet's pre-final volume with the folded pack (ImplicitWNFDecoder.run_on) or the decoder's own input volume"""
+    vol: torch.Tensor                            # (B, D, H, W, C) channel-last
+    pack: Optional[DecoderPack]
+    scales: Callable                             # smax -> (B, 4) per-garment input scales of the split-operand kernels (ops.decoder_input_scale)
+
+
+LATTICE, BATCHED, SPLIT, FUSED, MLP_LAYERS = "lattice", "batched", "split", "fused", "mlp"
+
+
+class DecodePlan(NamedTuple):
+    """which launches one decoder call takes (decode_plan)"""
+    path: str        # LATTICE | BATCHED | SPLIT | FUSED | MLP_LAYERS
+    chunk: int       # rows per sampler launch of the chunked paths (SPLIT, FUSED, MLP_LAYERS)
+    scales: bool     # a split-operand kernel runs: it takes the garment's input scale, and the gated fp32 twin follows it when there is one
+
+
+@functools.lru_cache(maxsize=1024)      # (pure, of hashable arguments; bounded: M is whatever a caller queries)
+def decode_plan(arith, fused, pack, dims, contiguous, Q, B, M, chunk_rows, batch_bytes, out_packed):
+    """The launches of one decoder call from the arithmetic, the module's `fused` switch, DecoderPack.facts() (None: no fused kernel takes the decoder),
+    the volume's (D, H, W) and contiguity, the lattice edge Q (None: B x M query points), the row budget of a chunk, the byte budget of the batched
+    launches, and whether the output's row sets lie back to back.  No tensor, no library entry.
+      MLP_LAYERS  no fused kernel (only [C0, N1, N2, out <= 4] with N1, N2 multiples of 256 has one), or `fused` off: sampler, gn_linear per layer
+      FUSED       sampler, gn_implicit_decode: the three layers in one fp32 kernel, hidden activations stay in LDS
+      SPLIT       (the shipped widths under Arith.decode_mode "f16x2") sampler, split-operand decoder on the 16-bit matrix cores
+      BATCHED     SPLIT for the queries of a whole batch in one set of launches, while the sampled rows fit the cache they are handed over in
+      LATTICE     lattice queries of the folded scalar decoder (Arith.fused_lattice) in ONE launch per garment: the kernel walks bricks of 4 x 8 x 8
+                  lattice points out of LDS, no sampled-row buffer; the lattice must be at least as fine as the volume (ops.lattice_split_shapes)
+    The first three go garment by garment, a separate high-occupancy sampler feeding the MLP through a buffer of `chunk` rows.  Behind every
+    split-operand launch its fp32 twin follows, gated on the device by the garment's `unsafe` flag."""
+    if Q is not None:                               # lattice: whole i-slabs per chunk (the brick sampler's unit)
+        chunk_rows = max(1, chunk_rows // (Q * Q)) * Q * Q
+    if not fused or pack is None:
+        return DecodePlan(MLP_LAYERS, chunk_rows, False)
+    split, c0, hidden, out_channels = pack
+    if not (split and arith.decode_mode == "f16x2"):
+        return DecodePlan(FUSED, chunk_rows, False)
+    if Q is not None:
+        brick = arith.fused_lattice and contiguous and ops.lattice_split_shapes(dims, c0, hidden, out_channels, Q)
+        return DecodePlan(LATTICE if brick else SPLIT, chunk_rows, True)
+    batched = B >= 2 and M > 0 and contiguous and out_packed and B * M * ops.pad4(c0) * 4 <= batch_bytes
+    return DecodePlan(BATCHED if batched else SPLIT, chunk_rows, True)
+
+
 class ImplicitWNFDecoder(PackedModule):
     """trilinear feature sampling (border, align_corners) -> MLP -- conv_implicit_wnf.py:120-149.
 
-    The MLP runs as ONE kernel (gn_implicit_decode: hidden activations stay in LDS) when it has the shipped shape
-    [C0, N1, N2, out<=4] with N1, N2 multiples of 256; otherwise gn_linear per layer.
+    forward, decode_lattice and run_on each name a DecodeSource and _run executes the DecodePlan that decode_plan (which describes the paths) gives
+    for it.  run_on folds the UNet's final 1x1x1 convolution into the first layer (folded_pack) and samples the pre-final volume; when it cannot
+    (Arith.fold_final_conv off, a decoder no fused kernel takes) it decodes the materialised volume like forward."""
 
-    Lattice queries of the folded scalar decoder on the 16-bit matrix cores take ONE launch per garment (Arith.fused_lattice, the default:
-    gn_implicit_decode_lattice_split): the kernel walks bricks of 4 x 8 x 8 lattice points, a brick's voxel box arrives in LDS by DMA while the
-    previous brick is multiplied, and the rows are interpolated out of LDS -- no sampled-row buffer.  It needs a lattice at least as fine as the
-    volume (ops.lattice_split_supported(vol, pack, Q)).  Everything else -- surface queries, a coarser lattice, the fp32 decoder, fused_lattice
-    off -- samples in a separate high-occupancy kernel that feeds the MLP through a chunk buffer (2^20 rows x 32 channels = 134 MB: half a
-    128^3 lattice per launch pair; 2^18 rows measured 1 ms slower per 16-garment step, the whole lattice no faster) small enough to stay in
-    the 256 MB Infinity Cache."""
-
+    # 2^20 rows x 32 channels = 134 MB: half a 128^3 lattice, stays in the 256 MB Infinity Cache (2^18 rows: 1 ms slower per step; the whole lattice: no faster)
     ROWS_PER_CHUNK = int(os.environ.get("GARMENTNETS_DECODE_CHUNK", 1 << 20))
+    # the surface decoders of predict.py:184-187 fit (16 x ~49 000 vertices x 32 channels = 100 MB); larger query sets go garment by garment
+    BATCH_ROWS_BYTES = int(os.environ.get("GARMENTNETS_DECODE_BATCH_BYTES", 192 << 20))
     fused = True
 
     def __init__(self, nn_channels=(128, 512, 512, 1), batch_norm=True):
@@ -181,177 +234,123 @@ class ImplicitWNFDecoder(PackedModule):
         self.out_channels = nn_channels[-1]
         self.arith = None          # arithmetic of a direct call (None: arith.DEFAULT); the pipeline passes its own per call
 
-    def _pack(self):
+    def _fusable(self, c0):
         ch = self.nn_channels
-        if not (len(ch) == 4 and ch[0] % 32 == 0 and ch[1] % 256 == 0 and ch[2] % 256 == 0 and ch[3] <= 4):
-            return None
+        return len(ch) == 4 and c0 % 32 == 0 and ch[1] % 256 == 0 and ch[2] % 256 == 0 and ch[3] <= 4
+
+    def _build_pack(self, c0, split_shapes, fold=None):
+        """-> DecoderPack on rows of c0 channels; fold: (Wf, bf) in fp64, a linear map in front of the first layer (W1' = W1 Wf, b1' = b1 + W1 bf); split_shapes:
+        the (c0, hidden) that also get the split-operand pack (csrc/decode_split.hip): the shipped 256 on either input, the class default 512 folded"""
+        ch = self.nn_channels
         layers, raw = [], []
         for i, block in enumerate(self.mlp):
-            w = block[0].weight.detach().float()
-            b = block[0].bias.detach().float().contiguous()
+            w, b = block[0].weight.detach(), block[0].bias.detach()
+            if i == 0 and fold is not None:
+                b = b.double() + w.double() @ fold[1]
+                w = w.double() @ fold[0]
+            w, b = w.float(), b.float().contiguous()
             sc, sh = fold_batchnorm(block[2]) if len(block) > 2 else (None, None)
             layers.append((ops.pack_kpair(w) if i < 2 else w.contiguous(), b, sc, sh, ch[i + 1]))
             raw.append((w, b, sc, sh))
-        # the shipped [128,256,256,out] decoder also gets the split-operand pack (csrc/decode_split.hip, Arith.decode_mode)
-        split = ops.pack_decode_split(raw).to(w.device) if tuple(ch[:3]) == (128, 256, 256) else None
-        return tuple(layers) + (split,)
+        split = ops.pack_decode_split(raw).to(w.device) if ch[1] == ch[2] and (c0, ch[1]) in split_shapes else None
+        return DecoderPack(tuple(layers), split, c0)
+
+    def _pack(self):
+        return self._build_pack(self.nn_channels[0], ((128, 256),)) if self._fusable(self.nn_channels[0]) else None
 
     def folded_pack(self, final_conv):
-        """The same decoder with the UNet's final 1x1x1 convolution (linear, no activation) folded into its first layer:
-        W1' = W1 Wf, b1' = b1 + W1 bf (fp64 on the host).  It runs on rows sampled from the PRE-final feature volume (f_maps[0] = 32
-        channels instead of 128): trilinear interpolation is linear and its weights sum to one, so sample(Wf x + bf) = Wf sample(x) +
-        bf up to rounding.  The 128-channel volume is then never written or read (17 GB per 16-garment batch at 128^3), the
-        sampler moves a quarter of the bytes and layer 1 does a quarter of the FLOPs.  -> packed() layout, or None when not foldable.
-        A channel-padded pre-final volume (f_maps[0] not a multiple of 32: components/unet3d.py stored_channels) gets zero weight columns
-        for its pad channels."""
-        ch = self.nn_channels
+        """The same decoder with the UNet's final 1x1x1 convolution (linear, no activation) folded into its first layer (fp64 on the host).  It runs on rows
+        sampled from the PRE-final feature volume (f_maps[0] = 32 channels instead of 128): trilinear interpolation is linear and its weights sum to one, so
+        sample(Wf x + bf) = Wf sample(x) + bf up to rounding.  The 128-channel volume is then never written or read (17 GB per 16-garment batch at 128^3), the
+        sampler moves a quarter of the bytes and layer 1 does a quarter of the FLOPs.  -> DecoderPack, or None when not foldable.  A channel-padded pre-final
+        volume (f_maps[0] not a multiple of 32: components/unet3d.py stored_channels) gets zero weight columns for its pad channels."""
         cin = final_conv.in_stored or final_conv.in_channels
-        if not (self.fused and len(ch) == 4 and ch[0] == final_conv.out_channels and cin % 32 == 0 and ch[1] % 256 == 0
-                and ch[2] % 256 == 0 and ch[3] <= 4 and final_conv.kernel_size == (1, 1, 1)):
+        if not (self.fused and self._fusable(cin) and self.nn_channels[0] == final_conv.out_channels and final_conv.kernel_size == (1, 1, 1)):
             return None
         key = (id(final_conv), cin, final_conv.weight._version, final_conv.bias._version, final_conv.weight.device) + tuple(p._version for p in self.parameters())
+        return param_cache(self, "_folded").get(key, "folded", lambda: self._build_pack(
+            cin, ((32, 256), (32, 512)), (final_conv.stored_weight().double(), final_conv.bias.detach().double())))
 
-        def build():
-            wf = final_conv.stored_weight().double()
-            bf = final_conv.bias.detach().double()
-            layers, raw = [], []
-            for i, block in enumerate(self.mlp):
-                w = block[0].weight.detach().double()
-                b = block[0].bias.detach().double()
-                if i == 0:
-                    b = b + w @ bf
-                    w = w @ wf
-                w, b = w.float(), b.float().contiguous()
-                sc, sh = fold_batchnorm(block[2]) if len(block) > 2 else (None, None)
-                layers.append((ops.pack_kpair(w) if i < 2 else w.contiguous(), b, sc, sh, ch[i + 1]))
-                raw.append((w, b, sc, sh))
-            # the split-operand pack: the shipped hidden width 256 and the class default 512 (conv_implicit_wnf.py:122), csrc/decode_split.hip
-            split = ops.pack_decode_split(raw).to(w.device) if (cin, ch[1], ch[2]) in ((32, 256, 256), (32, 512, 512)) else None
-            return tuple(layers) + (split,)
-        return param_cache(self, "_folded").get(key, "folded", build)
+    def _plan(self, arith, vol, pack, Q, M, out_packed=True):
+        """decode_plan for a (B, D, H, W, C) channel-last volume: Q rows per lattice edge, or (Q None) M query points per garment"""
+        contiguous = (vol if Q is None else vol[:1]).is_contiguous()       # the batched launches read the batch, the lattice kernel one garment
+        return decode_plan(arith, self.fused, None if pack is None else pack.facts(), tuple(vol.shape[1:4]), contiguous, Q, vol.shape[0], M,
+                           self.ROWS_PER_CHUNK, self.BATCH_ROWS_BYTES, out_packed)
 
-    def _decode_rows(self, vol_b, out, query=None, Q=0, layers=None, xscale=None, arith=None):
-        """vol_b [D][H][W][C]: the decoder's own input volume, or (with the folded `layers`) the UNet's pre-final volume;
-        xscale: this garment's (s, 1/s) input scale for the split-operand kernel (ops.decoder_input_scale)"""
-        arith = arith or AR.DEFAULT
+    def _decode_rows(self, plan, vol_b, out, pack, query=None, Q=0, xscale=None):
+        """one garment of a LATTICE, SPLIT, FUSED or MLP_LAYERS plan.  vol_b [D][H][W][C]; out [M][OUT]; query [M][3], or None: the (Q,Q,Q) lattice;
+        xscale: the garment's (s, 1/s, unsafe, 0) row of ops.decoder_input_scale"""
         M = out.shape[0]
-        if layers is None:
-            layers = self.packed() if self.fused else None
-        split = layers is not None and layers[3] is not None and arith.decode_mode == "f16x2"
-        if query is None and split and arith.fused_lattice and ops.lattice_split_supported(vol_b, layers[3], Q):
-            # SURVEY K14: the lattice sampler inside the decoder kernel -- one launch per garment, no sampled-row buffer
-            ops.implicit_decode_lattice_split(vol_b, Q, layers[3], out, xscale=xscale)
+        if plan.path == LATTICE:
+            ops.implicit_decode_lattice_split(vol_b, Q, pack.split, out, xscale=xscale)
             if xscale is not None:          # garments the device marked unsafe for fp16 planes: the gated fp32 twin samples for itself
-                ops.implicit_decode(vol_b, layers[:3], Q=Q, m0=0, M=M, out=out, run_if=xscale[2:3])
+                ops.implicit_decode(vol_b, pack.fp32, Q=Q, m0=0, M=M, out=out, run_if=xscale[2:3])
             return
-        chunk = self.ROWS_PER_CHUNK
-        if query is None:                           # lattice: whole i-slabs per chunk (the brick sampler's unit)
-            chunk = max(1, chunk // (Q * Q)) * Q * Q
-        buf = ops.new_rows(min(M, chunk), vol_b.shape[-1], vol_b.device)
-        for m0 in range(0, M, chunk):
-            m = min(chunk, M - m0)
+        buf = ops.new_rows(min(M, plan.chunk), vol_b.shape[-1], vol_b.device)
+        for m0 in range(0, M, plan.chunk):
+            m = min(plan.chunk, M - m0)
             if query is not None:
                 s = ops.trilinear_sample(vol_b, query=query[m0:m0 + m], out=buf[:m])
             else:
                 s = ops.trilinear_sample(vol_b, Q=Q, m0=m0, M=m, out=buf[:m])
-            if split:
-                ops.implicit_decode_split(s, layers[3], out=out[m0:m0 + m], xscale=xscale)
+            if plan.path == SPLIT:
+                ops.implicit_decode_split(s, pack.split, out=out[m0:m0 + m], xscale=xscale)
                 if xscale is not None:      # the garments the device marked unsafe for fp16 planes: gated fp32 twin (a no-op otherwise)
-                    ops.implicit_decode(None, layers[:3], M=m, out=out[m0:m0 + m], xin=s, run_if=xscale[2:3])
-            elif layers is not None:
-                ops.implicit_decode(None, layers[:3], M=m, out=out[m0:m0 + m], xin=s)
+                    ops.implicit_decode(None, pack.fp32, M=m, out=out[m0:m0 + m], xin=s, run_if=xscale[2:3])
+            elif plan.path == FUSED:
+                ops.implicit_decode(None, pack.fp32, M=m, out=out[m0:m0 + m], xin=s)
             else:
                 out[m0:m0 + m] = self.mlp(s)
 
-    # queries of a whole batch in one set of launches when their sampled rows fit the cache they are handed over in (the surface decoders of
-    # predict.py:184-187: 16 x ~49 000 vertices x 32 channels = 100 MB); larger query sets (and the lattice) go garment by garment in 1 M-row chunks
-    BATCH_ROWS_BYTES = int(os.environ.get("GARMENTNETS_DECODE_BATCH_BYTES", 192 << 20))
+    def _run(self, src, query_points, Q, arith):
+        """query_points (B,M,3) -> (B,M,out); query_points None -> the (Q,Q,Q) lattice -> (B,Q,Q,Q[,out])"""
+        vol, pack, scales = src
+        q = None if query_points is None else query_points.float().contiguous()
+        B, Q, M = (vol.shape[0], Q, Q * Q * Q) if q is None else (vol.shape[0], None, q.shape[1])
+        out = torch.empty((B, M, self.out_channels), dtype=torch.float32, device=vol.device)
+        plan = self._plan(arith, vol, pack, Q, M, out.stride(0) == M * out.stride(1))
+        xs = scales(pack.split.smax) if plan.scales else None
+        if plan.path == BATCHED:            # three launches for the whole batch: sampler, decoder, gated fp32 twin -- row for row what the garment loop gives
+            rows = ops.trilinear_sample_batch(vol, q)
+            ops.implicit_decode_split_batch(rows, pack.split, out, xscale=xs)
+            ops.implicit_decode_batch(rows, pack.fp32, out, run_if=xs[:, 2:], run_if_stride=xs.stride(0))
+        else:
+            for b in range(B):
+                self._decode_rows(plan, vol[b], out[b], pack, None if q is None else q[b], Q, None if xs is None else xs[b])
+        return out if q is not None else out.reshape(B, Q, Q, Q, self.out_channels).squeeze(-1)
 
-    def _decode_queries_batched(self, vol, q, out, layers, xs, arith):
-        """vol (B,D,H,W,C) channel-last, q (B,M,3), out (B,M,OUT) through the split-operand decoder in three launches for the whole batch (sampler, decoder,
-        gated fp32 twin); -> False when this path does not apply (the caller loops over the garments: same results row for row)"""
-        B, M = q.shape[:2]
-        C = vol.shape[-1]
-        if (B < 2 or M == 0 or layers is None or layers[3] is None or arith.decode_mode != "f16x2" or not vol.is_contiguous()
-                or B * M * ops.pad4(C) * 4 > self.BATCH_ROWS_BYTES or out.stride(0) != M * out.stride(1)):
-            return False
-        rows = ops.trilinear_sample_batch(vol, q)
-        ops.implicit_decode_split_batch(rows, layers[3], out, xscale=xs)
-        if xs is not None:                  # the garments the device marked unsafe for fp16 planes: gated fp32 twin (a no-op otherwise)
-            ops.implicit_decode_batch(rows, layers[:3], out, run_if=xs[:, 2:], run_if_stride=xs.stride(0))
-        return True
+    def _tensor_source(self, features_grid):
+        """the decoder's own (B,C,D,H,W) input.  Its scales take one gn_channel_stats pass, remembered ON the caller's tensor object with its version counter
+        (the reference's chunk loop calls the decoder 8 times per garment on one volume): the entry dies with the tensor, never mistaken for a recycled one"""
+        vol = to_channel_last(features_grid)
+
+        def scales(smax):
+            cached = getattr(features_grid, "_gn_chan_stats", None)
+            if cached is None or cached[0] != features_grid._version:
+                cached = (features_grid._version, ops.channel_stats(vol))
+                try:
+                    features_grid._gn_chan_stats = cached
+                except AttributeError:
+                    pass
+            return ops.decoder_input_scale(cached[1][1], cached[1][2], smax)
+        return DecodeSource(vol, self.packed(), scales)
 
     def forward(self, features_grid, query_points, arith=None):
         """features_grid (B,C,D,H,W), query_points (B,M,3) in [0,1] -> (B,M,out)"""
-        arith = arith or self.arith or AR.DEFAULT
-        vol = to_channel_last(features_grid)
-        B, M = query_points.shape[:2]
-        q = query_points.float().contiguous()
-        out = torch.empty((B, M, self.out_channels), dtype=torch.float32, device=vol.device)
-        xs = self._volume_scales(features_grid, vol, arith)
-        if self._decode_queries_batched(vol, q, out, self.packed() if self.fused else None, xs, arith):
-            return out
-        for b in range(B):
-            self._decode_rows(vol[b], out[b], query=q[b], xscale=None if xs is None else xs[b], arith=arith)
-        return out
-
-    def _volume_scales(self, owner, vol, arith):
-        """(B, 4) input scales of the split-operand decoder kernel for the channel-last volume the rows are sampled from, or None when
-        that kernel is not the one that runs.  One gn_channel_stats pass over the volume, remembered ON the caller's tensor object
-        `owner` together with its version counter (the reference's chunk loop calls the decoder 8 times per garment on one volume): the
-        entry dies with the tensor, so a recycled allocation can never be mistaken for it."""
-        layers = self.packed() if self.fused else None
-        if layers is None or layers[3] is None or arith.decode_mode != "f16x2":
-            return None
-        cached = getattr(owner, "_gn_chan_stats", None)
-        if cached is None or cached[0] != owner._version:
-            cached = (owner._version, ops.channel_stats(vol))
-            try:
-                owner._gn_chan_stats = cached
-            except AttributeError:
-                pass
-        stats = cached[1]
-        return ops.decoder_input_scale(stats[1], stats[2], layers[3].smax)
+        return self._run(self._tensor_source(features_grid), query_points, None, arith or self.arith or AR.DEFAULT)
 
     def decode_lattice(self, features_grid, Q, arith=None):
         """All (Q,Q,Q) lattice queries of predict.py:145-157 without materialising them -> (B,Q,Q,Q[,out])"""
-        arith = arith or self.arith or AR.DEFAULT
-        vol = to_channel_last(features_grid)
-        B = vol.shape[0]
-        out = torch.empty((B, Q * Q * Q, self.out_channels), dtype=torch.float32, device=vol.device)
-        xs = self._volume_scales(features_grid, vol, arith)
-        for b in range(B):
-            self._decode_rows(vol[b], out[b], Q=Q, xscale=None if xs is None else xs[b], arith=arith)
-        return out.reshape(B, Q, Q, Q, self.out_channels).squeeze(-1)
+        return self._run(self._tensor_source(features_grid), None, Q, arith or self.arith or AR.DEFAULT)
 
     def run_on(self, unet3d_result, query_points=None, Q=0, arith=None):
-        """decode against a unet3d_forward result: through the folded first layer when the result still carries the pre-final
-        volume (UNetResult) and this decoder can absorb the final convolution, else on the materialised 128-channel volume.
-        query_points (B,M,3) -> (B,M,out); query_points None -> the (Q,Q,Q) lattice -> (B,Q,Q,Q[,out])"""
+        """decode against a unet3d_forward result: on its pre-final volume (UNetResult) when this decoder can absorb the final convolution, else on the
+        materialised 128-channel volume.  query_points (B,M,3) -> (B,M,out); query_points None -> the (Q,Q,Q) lattice -> (B,Q,Q,Q[,out])"""
         arith = arith or self.arith or AR.DEFAULT
-        layers = None
-        if isinstance(unet3d_result, UNetResult) and arith.fold_final_conv:
-            layers = self.folded_pack(unet3d_result.final_conv)
-        if layers is None:
-            vol = unet3d_result["out_feature_volume"]
-            return self.decode_lattice(vol, Q, arith) if query_points is None else self(vol, query_points, arith)
-        vol = unet3d_result.pre_final
-        B = vol.shape[0]
-        xs = None
-        if layers[3] is not None and arith.decode_mode == "f16x2":
-            xs = unet3d_result.input_scales(layers[3].smax)
-        if query_points is None:
-            out = torch.empty((B, Q * Q * Q, self.out_channels), dtype=torch.float32, device=vol.device)
-            for b in range(B):
-                self._decode_rows(vol[b], out[b], Q=Q, layers=layers, xscale=None if xs is None else xs[b], arith=arith)
-            return out.reshape(B, Q, Q, Q, self.out_channels).squeeze(-1)
-        q = query_points.float().contiguous()
-        out = torch.empty((B, q.shape[1], self.out_channels), dtype=torch.float32, device=vol.device)
-        if self._decode_queries_batched(vol, q, out, layers, xs, arith):
-            return out
-        for b in range(B):
-            self._decode_rows(vol[b], out[b], query=q[b], layers=layers, xscale=None if xs is None else xs[b], arith=arith)
-        return out
+        pack = self.folded_pack(unet3d_result.final_conv) if isinstance(unet3d_result, UNetResult) and arith.fold_final_conv else None
+        if pack is None:
+            return self._run(self._tensor_source(unet3d_result["out_feature_volume"]), query_points, Q, arith)
+        return self._run(DecodeSource(unet3d_result.pre_final, pack, unet3d_result.input_scales), query_points, Q, arith)
 
 
 # zero-fill of the scattered volume overlapped with PointNet++ (VolumeFeatureAggregator.prefetch_zero)

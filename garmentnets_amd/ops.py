@@ -878,17 +878,22 @@ def implicit_decode_lattice_split(vol_b, Q, pack, out, xscale=None, m0=0, M=None
     D, H, W, C0 = vol_b.shape
     M = Q * Q * Q - m0 if M is None else M
     _lib.call("gn_implicit_decode_lattice_split", _p(_chk(vol_b, torch.float32, "vol")), D, H, W, C0, int(Q), int(m0), int(M), _p(pack.wpack), _p(pack.tab),
-              _p(xscale), 256, 256, pack.out_channels, _p(out), rows_view(out)[1], _stream())
+              _p(xscale), pack.hidden, pack.hidden, pack.out_channels, _p(out), rows_view(out)[1], _stream())
     return out
 
 
-def lattice_split_supported(vol_b, pack, Q=None):
-    """whether implicit_decode_lattice_split takes this volume and decoder pack -- and, with Q, this lattice: a brick's voxel box is bounded only when
-    the lattice is at least as fine as the volume (Q >= D, H, W), a coarser lattice keeps the sampler + decoder pair"""
-    D, H, W, C0 = vol_b.shape
+def lattice_split_shapes(dims, c0, hidden, out_channels, Q=None):
+    """the shapes implicit_decode_lattice_split takes: a (D, H, W) volume of c0 channels, the decoder's widths -- and, with Q, the lattice: a brick's
+    voxel box is bounded only when the lattice is at least as fine as the volume (Q >= D, H, W), a coarser lattice keeps the sampler + decoder pair"""
+    D, H, W = dims
     if Q is not None and not max(2, D, H, W) <= Q <= 1024:
         return False
-    return C0 == 32 and pack.out_channels == 1 and pack.hidden == 256 and D * H * W * 128 < 2 ** 32 and vol_b.is_contiguous()
+    return c0 == 32 and out_channels == 1 and hidden == 256 and D * H * W * 128 < 2 ** 32
+
+
+def lattice_split_supported(vol_b, pack, Q=None):
+    """whether implicit_decode_lattice_split takes this (contiguous) volume and decoder pack -- and, with Q, this lattice (lattice_split_shapes)"""
+    return lattice_split_shapes(tuple(vol_b.shape[:3]), vol_b.shape[3], pack.hidden, pack.out_channels, Q) and vol_b.is_contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ isosurface

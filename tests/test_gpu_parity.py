@@ -1244,7 +1244,7 @@ def test_decoder_batch_entries_are_the_single_calls_row_for_row(k0, out_ch, M):
     rows = ops.trilinear_sample_batch(vol, q)
     out = torch.full((B, M, out_ch), 7.0, dtype=torch.float32, device=DEV)
     ops.implicit_decode_split_batch(rows, pack, out, xscale=xs)
-    ops.implicit_decode_batch(rows, layers[:3], out, run_if=xs[:, 2:], run_if_stride=xs.stride(0))
+    ops.implicit_decode_batch(rows, layers, out, run_if=xs[:, 2:], run_if_stride=xs.stride(0))
     for b in range(B):
         r1 = ops.trilinear_sample(vol[b], query=q[b])
         assert torch.equal(rows[b], r1), b

@@ -259,7 +259,7 @@ def test_padded_unet_pre_final_and_folded_decoder(f_maps):
     assert pre.shape[-1] == 32 and int(torch.count_nonzero(pre[..., f_maps:])) == 0
     dec = ImplicitWNFDecoder((16, 256, 256, 1)).to(DEV).eval()
     layers = dec.folded_pack(net.final_conv)
-    assert layers is not None and layers[3] is not None                       # the fused split-operand decoder on 32 stored channels
+    assert layers is not None and layers.split is not None                    # the fused split-operand decoder on 32 stored channels
     res = UNetResult(pre, net.final_conv, st)
     out = res["out_feature_volume"]
     assert out.shape == (2, 16, 16, 16, 16)

@@ -7,7 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from garmentnets_amd import arith as AR, ops  # noqa: E402
-from garmentnets_amd.networks.conv_implicit_wnf import ImplicitWNFDecoder  # noqa: E402
+from garmentnets_amd.networks.conv_implicit_wnf import DecoderPack, ImplicitWNFDecoder  # noqa: E402
 
 DEV = "cuda:0"
 FUSED, PAIR = AR.DEFAULT.replace(decode_mode="f16x2", fused_lattice=True), AR.DEFAULT.replace(decode_mode="f16x2", fused_lattice=False)
@@ -23,7 +23,7 @@ def decoder():
                     (torch.rand(n, generator=g) + 0.5) if i < 2 else None, torch.randn(n, generator=g) * 0.1 if i < 2 else None))
     dev = lambda v: None if v is None else v.contiguous().to(DEV)
     layers = tuple((dev(ops.pack_kpair(w) if i < 2 else w), dev(b), dev(sc), dev(sh), w.shape[0]) for i, (w, b, sc, sh) in enumerate(raw))
-    return ImplicitWNFDecoder((32, 256, 256, 1)), layers + (ops.pack_decode_split(raw).to(DEV),)
+    return ImplicitWNFDecoder((32, 256, 256, 1)), DecoderPack(layers, ops.pack_decode_split(raw).to(DEV), 32)
 
 
 def _volume(dims, seed):
@@ -38,7 +38,7 @@ def _scale(vol, pack):
 def _decode(decoder, vol, Q, arith, xscale):
     dec, layers = decoder
     out = torch.full((Q * Q * Q, 1), float("nan"), device=DEV)
-    dec._decode_rows(vol, out, Q=Q, layers=layers, xscale=xscale, arith=arith)
+    dec._decode_rows(dec._plan(arith, vol[None], layers, Q, Q * Q * Q), vol, out, layers, Q=Q, xscale=xscale)
     return out
 
 
@@ -47,8 +47,8 @@ def _decode(decoder, vol, Q, arith, xscale):
 @pytest.mark.parametrize("dims,Q", [((8, 8, 8), 8), ((8, 8, 8), 16), ((12, 12, 12), 18), ((8, 12, 16), 16), ((16, 16, 16), 12)])
 def test_fused_lattice_equals_sampler_plus_decoder(decoder, dims, Q):
     vol = _volume(dims, Q + dims[2])
-    assert ops.lattice_split_supported(vol, decoder[1][3], Q) == (Q >= max(dims))
-    for xs in (None, _scale(vol, decoder[1][3])):
+    assert ops.lattice_split_supported(vol, decoder[1].split, Q) == (Q >= max(dims))
+    for xs in (None, _scale(vol, decoder[1].split)):
         want = _decode(decoder, vol, Q, PAIR, xs)
         got = _decode(decoder, vol, Q, FUSED, xs)
         assert torch.isfinite(want).all()
@@ -57,7 +57,7 @@ def test_fused_lattice_equals_sampler_plus_decoder(decoder, dims, Q):
 
 def test_fused_lattice_propagates_nan_and_inf_voxels_like_the_pair(decoder):
     vol = _volume((8, 8, 8), 3)
-    xs = _scale(vol, decoder[1][3])
+    xs = _scale(vol, decoder[1].split)
     vol[2, 3, 4, 5] = float("nan")
     vol[5, 1, 6, 0] = float("inf")
     want = _decode(decoder, vol, 16, PAIR, xs)
@@ -73,7 +73,7 @@ def test_fused_lattice_per_garment_scale_and_unsafe_garment(decoder):
     dec, layers = decoder
     Q = 16
     vols = [_volume((8, 8, 8), 11), _volume((8, 8, 8), 12) * 0.01]
-    xs = [_scale(v, layers[3]) for v in vols]
+    xs = [_scale(v, layers.split) for v in vols]
     assert float(xs[0][0]) != float(xs[1][0]) and float(xs[0][2]) == 0.0
     xs[1] = xs[1].clone()
     xs[1][2] = 1.0
@@ -81,12 +81,12 @@ def test_fused_lattice_per_garment_scale_and_unsafe_garment(decoder):
         want = _decode(decoder, vols[b], Q, PAIR, xs[b])
         got = _decode(decoder, vols[b], Q, FUSED, xs[b])
         assert torch.equal(got, want), b
-    fp32 = ops.implicit_decode(vols[1], layers[:3], Q=Q, m0=0, M=Q * Q * Q)
+    fp32 = ops.implicit_decode(vols[1], layers.fp32, Q=Q, m0=0, M=Q * Q * Q)
     assert torch.equal(got, fp32)
 
 
 def test_fused_lattice_repeats_bit_for_bit(decoder):
     vol = _volume((12, 12, 12), 5)
-    xs = _scale(vol, decoder[1][3])
+    xs = _scale(vol, decoder[1].split)
     first = _decode(decoder, vol, 18, FUSED, xs)
     assert torch.equal(_decode(decoder, vol, 18, FUSED, xs), first)

@@ -81,8 +81,13 @@ def _scalar(v):
 
 class Recorder:
     """for the duration of the `with` block: every garmentnets_amd._lib.call noted as (entry, gn_last_kernel() after it, scalar arguments), grouped per
-    SingleConv invocation; the weight-pack builders counted.  A statistics pass at the head of a layer (gn_channel_stats[_any] over its input, before
-    anything else of the layer) is noted in FRONT of the layer: it belongs to whoever produced that input, not to the layer's dispatch."""
+    invocation of one of `groups` -- (class, method names) pairs, by default SingleConv's run entries; the `packers` of ops counted.  A statistics pass
+    at the head of a group (gn_channel_stats[_any] over its input, before anything else of the group) is noted in FRONT of the group: it belongs to
+    whoever produced that input, not to the group's dispatch."""
+
+    def __init__(self, groups=None, packers=PACKERS):
+        self.groups = ((U.SingleConv, LAYER_ENTRIES),) if groups is None else groups
+        self.packers = packers
 
     def __enter__(self):
         self.trace, self.scalars, self.pack_builds, self._group, self._saved = [], [], 0, None, []
@@ -112,16 +117,17 @@ class Recorder:
                     self.trace.append(self._group)
                     self._group = None
             return run
-        for name in LAYER_ENTRIES:
-            if hasattr(U.SingleConv, name):
-                self._patch(U.SingleConv, name, layer(getattr(U.SingleConv, name)))
+        for cls, names in self.groups:
+            for name in names:
+                if hasattr(cls, name):
+                    self._patch(cls, name, layer(getattr(cls, name)))
 
         def counted(orig):
             def build(*args, **kwargs):
                 self.pack_builds += 1
                 return orig(*args, **kwargs)
             return build
-        for name in PACKERS:
+        for name in self.packers:
             self._patch(ops, name, counted(getattr(ops, name)))
         return self
 

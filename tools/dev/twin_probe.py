@@ -27,7 +27,7 @@ for name in ("volume_decoder", "surface_decoder"):
     layers = dec.folded_pack(u3.final_conv)
     if layers is None:
         print(name, "not foldable"); continue
-    pk = layers[3]
+    pk = layers.split
     tab = pk.tab.cpu()
     t1 = tab[:256]
     print(f"{name}: out={pk.out_channels} smax=2^{math.log2(pk.smax):.0f} max|b1 scaled|={float(t1.abs().max()):.3e}")
