@@ -135,6 +135,11 @@ PROTOTYPES = {
     "gn_col_dots": [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _sz, _vp, _vp],
     "gn_bn_train_bwd_workspace_bytes": [_i64, _i32],
     "gn_bn_train_bwd": [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp, _vp],
+    "gn_resident_points": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_resident_garment": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_resident_volume": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "gn_resident_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "gn_resident_mc_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -184,6 +189,17 @@ class AdamHyper(ctypes.Structure):
     """GnAdamHyper (host scalars of gn_adam_step)"""
     _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64), ("bias_correction1", _f64),
                 ("bias_correction2_sqrt", _f64)]
+
+
+RESIDENT_META = ("pc_off", "pc_len", "vert_off", "face_off", "num_faces", "mc_vert_off", "mc_face_off", "num_mc_faces", "dataset_idx",
+                 "scale_bits")                  # GN_RESIDENT_* : the int64 columns of GnResidentStore.meta
+RESIDENT_ARRAYS = ("pc_sim", "pc_nocs", "pc_rgb", "sim_verts", "nocs_verts", "task_verts", "faces", "cdf_nocs", "cdf_task", "mc_verts", "mc_flags",
+                   "mc_faces", "cdf_mc", "volume", "meta", "grip", "aabb")
+
+
+class ResidentStore(ctypes.Structure):
+    """GnResidentStore (host struct of the gn_resident_* calls: device pointers of the resident arrays, NULL for the ones a store does not hold)"""
+    _fields_ = [(k, _vp) for k in RESIDENT_ARRAYS] + [("n", _i32), ("D", _i32), ("H", _i32), ("W", _i32)]
 
 
 _lib = None

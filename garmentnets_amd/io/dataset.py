@@ -8,6 +8,8 @@ data module does to pick the samples of a subset (prepare_data 478-529), re-buil
                      numpy RandomState seeded with the sample's dataset index when ``static_epoch_seed`` (None = OS entropy
                      otherwise), in a fixed order: [views kept] -> [points kept]; [noise]; [angle].  Bit-identical samples
                      for a given (idx, static_epoch_seed=True) are pinned by tests/golden/ref_dataset.npz.
+                     Its methods return the DRAWS of each sampler without the arithmetic (point_selection, volume_draws, mesh_draws, noise,
+                     z_rotation); the samplers below are expressed through them, and io/resident.py uploads them to assemble batches on the device.
   visible_points     view sub-sampling as index arithmetic (np.repeat owner table + np.isin), no per-view loop.
   FIELD tables       which stored arrays feed which output fields, and which fields a rotation touches, as data.
 
@@ -23,7 +25,7 @@ import torch
 from scipy.spatial.transform import Rotation
 
 from ..batch import Batch
-from ..common.metrics import barycentric_interpolation, mesh_sample_barycentric
+from ..common.metrics import barycentric_interpolation, doublearea
 from . import zarr_store
 
 # stored array (group, name) -> key of the raw sample dict
@@ -76,8 +78,31 @@ class SeededDraws:
     def noise(self, std, shape):
         return self.fresh().normal(loc=np.zeros(3), scale=np.full(3, std), size=shape)
 
+    def mesh_draws(self, num_samples):
+        """-> (face uniforms (n,), uv (n, 2)), float64: what mesh_sample_barycentric draws from its fresh RandomState.  RandomState.choice(F, n,
+        replace=True, p=w) IS searchsorted(face_cdf, random_sample(n), side="right"), which is how the faces are found here (sample_faces)."""
+        rs = self.fresh()
+        return rs.random_sample(num_samples), rs.uniform(0, 1, size=(num_samples, 2))
+
+    def volume_draws(self, num_volume_sample, surface_sample_ratio=0, surface_sample_std=0.05):
+        """the draws of get_volume_sample -> {"uniform": (n_uniform, 3) float32 query points} and, when surface_sample_ratio != 0, "face_u" / "uv"
+        (mesh_draws of the n_surface near-surface points, a RandomState of their own) and "noise" (n_surface, 3) float64, drawn after the uniform
+        points from their stream"""
+        rs = self.fresh()
+        if surface_sample_ratio == 0:
+            return {"uniform": rs.uniform(low=0, high=1, size=(num_volume_sample, 3)).astype(np.float32)}
+        n_uniform = int(num_volume_sample * surface_sample_ratio)
+        n_surface = num_volume_sample - n_uniform
+        uniform = rs.uniform(low=0, high=1, size=(n_uniform, 3)).astype(np.float32)
+        face_u, uv = self.mesh_draws(n_surface)
+        noise = rs.normal(loc=(0,) * 3, scale=(surface_sample_std,) * 3, size=(n_surface, 3))
+        return {"uniform": uniform, "face_u": face_u, "uv": uv, "noise": noise}
+
+    def z_angle(self, lo, hi):
+        return self.fresh().uniform(lo, hi)
+
     def z_rotation(self, lo, hi):
-        angle = self.fresh().uniform(lo, hi)
+        angle = self.z_angle(lo, hi)
         return Rotation.from_euler("z", angle, degrees=True).as_matrix().astype(np.float32)
 
 
@@ -85,6 +110,33 @@ def visible_points(view_sizes, kept_views):
     """ascending indices of the stored points that belong to one of `kept_views` (views are stored back to back, view_sizes[v] points each)"""
     owner = np.repeat(np.arange(len(view_sizes)), np.asarray(view_sizes, dtype=np.int64))
     return np.flatnonzero(np.isin(owner, kept_views))
+
+
+def face_cdf(verts, faces):
+    """the float64 table RandomState.choice(len(faces), p=area share) searches: cumsum of the normalised doubled areas, divided by its last entry"""
+    w = doublearea(verts, faces)
+    cdf = np.cumsum(w / np.sum(w))
+    cdf /= cdf[-1]
+    if np.isnan(cdf[-1]):
+        raise ValueError("probabilities contain NaN")                       # (RandomState.choice's refusal of a mesh without area)
+    return cdf
+
+
+def sample_faces(cdf, face_u, uv, index_dtype=np.int64):
+    """mesh_sample_barycentric's arithmetic on given draws -> (barycentric float64 (n, 3), face index (n,)): the face is the upper bound of its
+    uniform in the CDF; u, v reflected when u + v >= 1; w = 1 - (u + v)"""
+    face_idx = np.searchsorted(cdf, face_u, side="right").astype(index_dtype)
+    uv = np.array(uv, dtype=np.float64)
+    flip = np.sum(uv, axis=1) >= 1
+    uv[flip] = 1 - uv[flip]
+    bc = np.empty((len(uv), 3), dtype=uv.dtype)
+    bc[:, :2] = uv
+    bc[:, 2] = 1 - np.sum(uv, axis=1)
+    return bc, face_idx
+
+
+def _mesh_sample(draws, verts, faces, num_samples):
+    return sample_faces(face_cdf(verts, faces), *draws.mesh_draws(num_samples), index_dtype=np.asarray(faces).dtype)
 
 
 def data_io(sample_group):
@@ -167,19 +219,14 @@ def get_volume_sample(idx, data_in, volume, num_volume_sample, surface_sample_ra
     """volume query points and the volume's values there (get_volume_sample: 231-281).  surface_sample_ratio == 0: uniform points of the unit
     cube; otherwise int(num_volume_sample * surface_sample_ratio) UNIFORM points (the reference sizes the uniform part by the ratio) followed
     by points of the NOCS mesh plus N(0, surface_sample_std) noise, all clipped to [0, 1].  Occupancy grids threshold the value at > 0.1."""
-    draws = SeededDraws(idx, static_epoch_seed)
-    rs = draws.fresh()
+    d = SeededDraws(idx, static_epoch_seed).volume_draws(num_volume_sample, surface_sample_ratio, surface_sample_std)
     if surface_sample_ratio == 0:
-        query = rs.uniform(low=0, high=1, size=(num_volume_sample, 3)).astype(np.float32)
+        query = d["uniform"]
     else:
-        n_uniform = int(num_volume_sample * surface_sample_ratio)
-        n_surface = num_volume_sample - n_uniform
-        uniform = rs.uniform(low=0, high=1, size=(n_uniform, 3)).astype(np.float32)
         verts, faces = data_in["cloth_nocs_verts"], data_in["cloth_faces_tri"]
-        bc, face_idx = mesh_sample_barycentric(verts, faces, n_surface, seed=draws.seed)
+        bc, face_idx = sample_faces(face_cdf(verts, faces), d["face_u"], d["uv"], index_dtype=np.asarray(faces).dtype)
         on_mesh = barycentric_interpolation(bc, verts, faces[face_idx])
-        noise = rs.normal(loc=(0,) * 3, scale=(surface_sample_std,) * 3, size=(n_surface, 3))
-        query = np.clip(np.concatenate([uniform, on_mesh + noise], axis=0).astype(np.float32), 0, 1)
+        query = np.clip(np.concatenate([d["uniform"], on_mesh + d["noise"]], axis=0).astype(np.float32), 0, 1)
     values = nocs_grid_sample(volume, query)
     if volume_group == "nocs_occupancy_grid":
         values = (values > 0.1).astype(np.float32)
@@ -200,7 +247,7 @@ def get_surface_sample(idx, data_in, num_surface_sample, static_epoch_seed=False
     nocs_verts, sim_verts, faces = data_in["cloth_nocs_verts"], data_in["cloth_sim_verts"], data_in["cloth_faces_tri"]
     if volume_task_space:
         nocs_verts, sim_verts = AABBGripNormalizer(cloth_sim_aabb)(sim_verts), nocs_verts
-    bc, face_idx = mesh_sample_barycentric(nocs_verts, faces, num_surface_sample, seed=SeededDraws(idx, static_epoch_seed).seed)
+    bc, face_idx = _mesh_sample(SeededDraws(idx, static_epoch_seed), nocs_verts, faces, num_surface_sample)
     sampled_faces = faces[face_idx]
     return _for_batching({"surf_query_points": barycentric_interpolation(bc, nocs_verts, sampled_faces),
                           "gt_sim_points": barycentric_interpolation(bc, sim_verts, sampled_faces)})
@@ -211,7 +258,7 @@ def get_mc_surface_sample(idx, data_in, num_surface_sample, static_epoch_seed=Fa
     per-vertex flag > 0.5.  The reference draws num_surface_sample points here, not num_mc_surface_sample; so does this."""
     verts, faces = data_in["marching_cube_verts"], data_in["marching_cube_faces"]
     flags = np.expand_dims(data_in["is_vertex_on_surface"].astype(np.float32), axis=-1)
-    bc, face_idx = mesh_sample_barycentric(verts, faces, num_surface_sample, seed=SeededDraws(idx, static_epoch_seed).seed)
+    bc, face_idx = _mesh_sample(SeededDraws(idx, static_epoch_seed), verts, faces, num_surface_sample)
     sampled_faces = faces[face_idx]
     on_surface = barycentric_interpolation(bc, flags, sampled_faces)
     return _for_batching({"mc_surf_query_points": barycentric_interpolation(bc, verts, sampled_faces),

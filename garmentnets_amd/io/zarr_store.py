@@ -149,6 +149,12 @@ class Group:
             return Group(path, create=False)
         raise KeyError(name)
 
+    def array_meta(self, name):
+        """(shape, dtype) of an array from its .zarray alone: no chunk is read"""
+        path = os.path.join(self.path, *name.strip("/").split("/"))
+        meta = json.load(open(os.path.join(path, ".zarray")))
+        return tuple(meta["shape"]), np.dtype(meta["dtype"])
+
     def keys(self):
         return sorted(d for d in os.listdir(self.path) if not d.startswith("."))
 

@@ -1743,3 +1743,61 @@ def bn_train_bwd(dy, r, coef, out=None):
     _lib.call("gn_bn_train_bwd", _p(dy), rows_view(dy)[1], _p(r), rows_view(r)[1], _p(coef), M, N, _p(g), rows_view(g)[1], _p(ws), nbytes, _p(sum_g),
               _stream())
     return g, sum_g
+
+
+# ------------------------------------------------------------------------------------------------ resident dataset (csrc/resident.hip)
+def resident_store(arrays, volume_shape=(0, 0, 0)):
+    """the GnResidentStore of a dict of device tensors keyed by _lib.RESIDENT_ARRAYS (a missing / None entry: NULL); the caller keeps the tensors alive"""
+    n = arrays["meta"].shape[0]
+    if tuple(arrays["meta"].shape) != (n, len(_lib.RESIDENT_META)) or arrays["meta"].dtype != torch.int64:
+        raise ValueError(f"resident_store: meta must be int64 (n, {len(_lib.RESIDENT_META)})")
+    dtypes = {"pc_rgb": torch.uint8, "faces": torch.int32, "mc_faces": torch.int32, "cdf_nocs": torch.float64, "cdf_task": torch.float64,
+              "cdf_mc": torch.float64, "meta": torch.int64}
+    ptrs = []
+    for k in _lib.RESIDENT_ARRAYS:
+        t = arrays.get(k)
+        ptrs.append(None if t is None else _p(_chk(t, dtypes.get(k, torch.float32), "resident_store: " + k)).value)
+    _CALL.dev = None
+    return _lib.ResidentStore(*ptrs, n, *[int(v) for v in volume_shape])
+
+
+def _res(store):
+    return ctypes.byref(store)
+
+
+def resident_points(store, slots, sel, noise, rot, x, y, pos, batch):
+    """gn_resident_points: sel int32 (B, P) -> x, y, pos (B*P, 3) fp32 and batch (B*P,) int64, written in place"""
+    B, P = sel.shape
+    _lib.call("gn_resident_points", _res(store), _p(_chk(slots, torch.int32, "slots")), B, P, _p(_chk(sel, torch.int32, "sel")),
+              _p(None if noise is None else _chk(noise, torch.float64, "noise")), _p(None if rot is None else _chk(rot, torch.float32, "rot")),
+              _p(x), _p(y), _p(pos), _p(_chk(batch, torch.int64, "batch")), _stream())
+
+
+def resident_garment(store, slots, sel, rot, grip_pc_idx, sim_grip, nocs_grip, scale_bits, dataset_idx, aabb, rot_out):
+    """gn_resident_garment: the per-garment fields of a batch, written in place"""
+    B, P = sel.shape
+    _lib.call("gn_resident_garment", _res(store), _p(slots), B, P, _p(sel), _p(rot), _p(_chk(grip_pc_idx, torch.int64, "grip_pc_idx")), _p(sim_grip),
+              _p(nocs_grip), _p(_chk(scale_bits, torch.int64, "scale_bits")), _p(_chk(dataset_idx, torch.int64, "dataset_idx")), _p(aabb), _p(rot_out),
+              _stream())
+
+
+def resident_volume(store, slots, uniform, face_u, uv, noise, rot, occupancy, query, value):
+    """gn_resident_volume: query (B, M, 3), value (B, M) fp32 written in place; uniform (B, n_uniform, 3) fp32; face_u / uv / noise fp64 or None"""
+    B, M = value.shape
+    _lib.call("gn_resident_volume", _res(store), _p(slots), B, M, uniform.shape[1], _p(_chk(uniform, torch.float32, "uniform")),
+              _p(None if face_u is None else _chk(face_u, torch.float64, "face_u")), _p(None if uv is None else _chk(uv, torch.float64, "uv")),
+              _p(None if noise is None else _chk(noise, torch.float64, "noise")), _p(rot), int(bool(occupancy)), _p(query), _p(value), _stream())
+
+
+def resident_surface(store, slots, face_u, uv, task_space, rot, query, target):
+    """gn_resident_surface: query, target (B, M, 3) fp32 written in place; face_u (B, M), uv (B, M, 2) fp64"""
+    B, M = face_u.shape
+    _lib.call("gn_resident_surface", _res(store), _p(slots), B, M, _p(_chk(face_u, torch.float64, "face_u")), _p(_chk(uv, torch.float64, "uv")),
+              int(bool(task_space)), _p(rot), _p(query), _p(target), _stream())
+
+
+def resident_mc_surface(store, slots, face_u, uv, query, on_surf):
+    """gn_resident_mc_surface: query (B, M, 3), on_surf (B, M, 1) fp32 written in place"""
+    B, M = face_u.shape
+    _lib.call("gn_resident_mc_surface", _res(store), _p(slots), B, M, _p(_chk(face_u, torch.float64, "face_u")), _p(_chk(uv, torch.float64, "uv")),
+              _p(query), _p(on_surf), _stream())

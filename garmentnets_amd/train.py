@@ -179,6 +179,7 @@ def build_parser():
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--learning_rate", type=float, default=None, help="default: the model's hyper-parameter")
     ap.add_argument("--seed", type=int, default=0)
+    validate.add_resident_arguments(ap)
     return ap
 
 
@@ -189,16 +190,25 @@ def parse_args(argv=None):
     return a
 
 
-def _validate(model, a, device, volume_task_space=False):
-    """validate.py's loop over the val subset (read with static_epoch_seed=True, as the reference's val_dataset), the model in eval mode for it"""
+def _val_dataset(a, volume_task_space=False):
+    """the val subset's host dataset: read with static_epoch_seed=True, as the reference's val_dataset"""
     from . import validate
     va = argparse.Namespace(**vars(a))
     va.subset, va.static_epoch_seed = "val", True
-    dataset = validate.make_dataset(va, volume_task_space=volume_task_space)
+    return validate.make_dataset(va, volume_task_space=volume_task_space)
+
+
+def _validate(model, a, device, volume_task_space=False, resident=None):
+    """validate.py's loop over the val subset, the model in eval mode for it.  resident: the val subset as a ResidentDataset (built once by the caller);
+    None: a host dataset made here"""
+    from . import validate
+    dataset = _val_dataset(a, volume_task_space) if resident is None else resident.dataset
+    indices = dataset.subset_indices("val")
     was_training = model.training
     model.eval()
     try:
-        rows = validate.validation_rows(model, dataset, dataset.subset_indices("val"), a.batch_size, a.num_batches, device)
+        rows = validate.validation_rows(model, dataset, indices, a.batch_size, a.num_batches, device,
+                                        batches=None if resident is None else resident.batches(indices, a.batch_size))
     finally:
         model.train(was_training)
     return validate.epoch_values(rows)
@@ -214,27 +224,33 @@ def main(argv=None):
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
     optimizer = model.configure_optimizers()
-    a.subset, a.static_epoch_seed = "train", False
+    a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a)
     indices = dataset.subset_indices("train")
+    resident = validate.make_resident(a, dataset, "train", device) if a.resident else None
+    val_resident = validate.make_resident(a, _val_dataset(a), "val", device) if a.resident else None
     os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
     rows, epochs = [], []
     for epoch in range(a.epochs):
-        for batch_idx, (chunk, batch) in enumerate(validate.host_batches(dataset, indices, a.batch_size)):
+        order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
+        source = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
+        for batch_idx, (chunk, batch) in enumerate(source):
             if a.num_batches is not None and batch_idx >= a.num_batches:
                 break
             t0 = time.time()
             metrics = train_step(model, optimizer, batch.to(device))
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "seconds": time.time() - t0}
+            if a.resident:
+                row["resident"] = True
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
             print(json.dumps(row))
-        val = _validate(model, a, device)
+        val = _validate(model, a, device, resident=val_resident)
         epochs.append(dict(epoch=epoch, **val))
         print(json.dumps(epochs[-1]))
         torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},
                    os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
-    cols = ["epoch", "batch_idx", "garments", "seconds"] + ["train_" + k for k in METRIC_KEYS]
+    cols = ["epoch", "batch_idx", "garments", "seconds"] + (["resident"] if a.resident else []) + ["train_" + k for k in METRIC_KEYS]
     with open(os.path.join(a.output_dir, "train_metrics.csv"), "w", newline="") as f:
         w = csv.DictWriter(f, fieldnames=cols)
         w.writeheader()
@@ -242,7 +258,7 @@ def main(argv=None):
             w.writerow({k: r.get(k, "") for k in cols})
     with open(os.path.join(a.output_dir, "val_epochs.json"), "w") as f:
         json.dump(epochs, f, indent=2)
-    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs}
+    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
 
 
 if __name__ == "__main__":

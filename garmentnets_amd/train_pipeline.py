@@ -22,8 +22,10 @@ every point) is data: no gradient reaches the predicted NOCS coordinates or the 
 The stages are functions of their own (first_stage / aggregate / unet / heads) so that tools/pipeline_step_time.py can bracket them and the tests can
 record the second stage alone.
 
-What stays out: a worker pool for the host dataset (each csv row records data_seconds, the host time to read and collate the batch, for the change that
-builds one), a backward for the fused inference kernels.
+--resident holds the train and the val subset in device memory and assembles every batch there (io/resident.py); each csv row records data_seconds, the
+host time until the batch is handed to the step, either way.
+
+What stays out: a worker pool for the host dataset, a backward for the fused inference kernels.
 """
 import csv
 import json
@@ -34,7 +36,7 @@ import torch
 
 from . import autograd as A
 from . import ops
-from .train import _bn_training, _mlp, _plain, _validate
+from .train import _bn_training, _mlp, _plain, _val_dataset, _validate
 
 HEADS = (("volume_decoder", "volume_decoder_result", "volume_query_points"), ("surface_decoder", "surface_decoder_result", "surf_query_points"),
          ("mc_surface_decoder", "mc_surface_decoder_result", "mc_surf_query_points"))
@@ -167,6 +169,7 @@ def build_parser():
     ap.add_argument("--host_packs", action="store_true",
                     help="build the UNet's static weight packs on the host after every step (the inference path's builders) instead of on the device "
                          "(arith.device_packs: same bits, no stream synchronisation)")
+    validate.add_resident_arguments(ap)
     return ap
 
 
@@ -208,17 +211,22 @@ def main(argv=None):
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
     optimizer = model.configure_optimizers()
-    a.subset, a.static_epoch_seed = "train", False
+    a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a, volume_task_space=model.volume_task_space)
     indices = dataset.subset_indices("train")
+    task = model.volume_task_space
+    resident = validate.make_resident(a, dataset, "train", device) if a.resident else None
+    val_resident = validate.make_resident(a, _val_dataset(a, task), "val", device) if a.resident else None
     os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
     keys = metric_keys(model)
     rows, epochs = [], []
     for epoch in range(a.epochs):
-        batches, batch_idx = validate.host_batches(dataset, indices, a.batch_size), 0
+        order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
+        batches = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
+        batch_idx = 0
         while a.num_batches is None or batch_idx < a.num_batches:
             t0 = time.time()
-            item = next(batches, None)                      # the host dataset: read, sample and collate one batch
+            item = next(batches, None)                      # host: read, sample and collate one batch; resident: draw, upload, launch
             if item is None:
                 break
             chunk, batch = item
@@ -226,16 +234,18 @@ def main(argv=None):
             metrics = train_step(model, optimizer, batch.to(device))
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1,
                    "device_packs": model.arith.device_packs}
+            if a.resident:
+                row["resident"] = True
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
             print(json.dumps(row))
             batch_idx += 1
-        val = _validate(model, a, device, volume_task_space=model.volume_task_space)
+        val = _validate(model, a, device, volume_task_space=task, resident=val_resident)
         epochs.append(dict(epoch=epoch, device_packs=model.arith.device_packs, **val))
         print(json.dumps(epochs[-1]))
         torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},
                    os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
-    cols = ["epoch", "batch_idx", "garments", "data_seconds", "seconds"] + ["train_" + k for k in keys]
+    cols = ["epoch", "batch_idx", "garments", "data_seconds", "seconds"] + (["resident"] if a.resident else []) + ["train_" + k for k in keys]
     with open(os.path.join(a.output_dir, "train_metrics.csv"), "w", newline="") as f:
         w = csv.DictWriter(f, fieldnames=cols)
         w.writeheader()
@@ -243,7 +253,7 @@ def main(argv=None):
             w.writerow({k: r.get(k, "") for k in cols})
     with open(os.path.join(a.output_dir, "val_epochs.json"), "w") as f:
         json.dump(epochs, f, indent=2)
-    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs}
+    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
 
 
 if __name__ == "__main__":

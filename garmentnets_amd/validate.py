@@ -90,6 +90,30 @@ def host_batches(dataset, indices, batch_size):
         yield chunk, GarmentInputDataset.collate([dataset[k] for k in chunk])
 
 
+def add_resident_arguments(ap):
+    """the training loops' data-source flags (train.py, train_pipeline.py)"""
+    ap.add_argument("--resident", action="store_true",
+                    help="read the train and the val subset once into device memory (io/resident.py) and assemble every batch there")
+    ap.add_argument("--resident_gib", type=float, default=None, help="device-memory budget of EACH resident subset; default: half of what is free")
+    ap.add_argument("--shuffle", action="store_true",
+                    help="visit the train subset in a RandomState(seed + epoch) permutation (the reference's train_dataloader: shuffle=True)")
+
+
+def epoch_order(indices, shuffle, seed, epoch):
+    """the order of the train subset in `epoch`"""
+    indices = np.asarray(indices)
+    return indices[np.random.RandomState(seed + epoch).permutation(len(indices))] if shuffle else indices
+
+
+def make_resident(a, dataset, subset, device):
+    """the subset of `dataset` as a ResidentDataset under --resident_gib; prints its one-off load time and footprint"""
+    from .io.resident import ResidentDataset
+    budget = None if a.resident_gib is None else int(a.resident_gib * 2 ** 30)
+    res = ResidentDataset(dataset, dataset.subset_indices(subset), device, max_bytes=budget)
+    print(json.dumps({"resident_subset": subset, "samples": len(res), "nbytes": res.nbytes, "load_seconds": res.load_seconds}))
+    return res
+
+
 def epoch_values(rows):
     """{key: garment-weighted mean} over the per-batch rows (dicts with "garments" and the val_* keys)"""
     w = np.array([r["garments"] for r in rows], dtype=np.float64)
@@ -132,10 +156,11 @@ def write_outputs(output_dir, rows, summary):
         json.dump(summary, f, indent=2)
 
 
-def validation_rows(model, dataset, indices, batch_size, num_batches, device, log=None):
-    """the validation loop: one row (batch_idx, garments, seconds, every val_* metric) per batch of `indices`, at most num_batches of them"""
+def validation_rows(model, dataset, indices, batch_size, num_batches, device, log=None, batches=None):
+    """the validation loop: one row (batch_idx, garments, seconds, every val_* metric) per batch of `indices`, at most num_batches of them.
+    batches: another source of (dataset indices, Batch) pairs than host_batches(dataset, indices, batch_size), e.g. ResidentDataset.batches(...)"""
     rows = []
-    for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, batch_size)):
+    for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, batch_size) if batches is None else batches):
         if num_batches is not None and batch_idx >= num_batches:
             break
         t0 = time.time()

@@ -776,6 +776,62 @@ size_t gn_bn_train_bwd_workspace_bytes(int64_t M, int N);
 int gn_bn_train_bwd(const float *dy, int lddy, const float *r, int ldr, const double *coef, int64_t M, int N, float *g, int ldg, void *ws, size_t ws_bytes,
                     double *sum_g, void *stream);
 
+/* ---- Resident dataset (csrc/resident.hip; DESIGN.md "Resident dataset"): a training batch assembled on the device.  The samples of a subset are packed
+ * into the arrays of a GnResidentStore (ragged parts back to back, their starts in `meta`); the host draws every random number and uploads them; one garment
+ * per blockIdx.y reads its sample through the DEVICE index table slots[B] (a slot outside [0, n) writes nothing).  A fixed number of launches per batch, no
+ * atomics, explicit _rn arithmetic in numpy's order: identical calls give identical bits.  rot: [B][3][3] fp32 rotation matrices, NULL = none. ---- */
+
+#define GN_RESIDENT_META 10          /* int64 columns of GnResidentStore.meta */
+#define GN_RESIDENT_PC_OFF 0         /* first row of the sample in pc_* */
+#define GN_RESIDENT_PC_LEN 1         /* its stored cloud length */
+#define GN_RESIDENT_VERT_OFF 2       /* first row in sim_verts / nocs_verts / task_verts */
+#define GN_RESIDENT_FACE_OFF 3       /* first row in faces, first entry in cdf_nocs / cdf_task */
+#define GN_RESIDENT_NUM_FACES 4
+#define GN_RESIDENT_MC_VERT_OFF 5    /* first row in mc_verts / mc_flags */
+#define GN_RESIDENT_MC_FACE_OFF 6    /* first row in mc_faces, first entry in cdf_mc */
+#define GN_RESIDENT_NUM_MC_FACES 7
+#define GN_RESIDENT_DATASET_IDX 8
+#define GN_RESIDENT_SCALE_BITS 9     /* the 8 bytes of the sample's `scale` */
+
+typedef struct {
+    const float *pc_sim, *pc_nocs;   /* [sum N][3] */
+    const uint8_t *pc_rgb;           /* [sum N][3] */
+    const float *sim_verts, *nocs_verts, *task_verts; /* [sum V][3]; task_verts: the AABBGripNormalizer'd simulation vertices (task space), else NULL */
+    const int32_t *faces;            /* [sum F][3], vertex numbers within the sample */
+    const double *cdf_nocs, *cdf_task; /* [sum F]: the face-area CDF RandomState.choice searches, of the NOCS / the task-space mesh */
+    const float *mc_verts, *mc_flags; /* [sum MV][3], [sum MV]: the marching-cubes mesh and is_vertex_on_surface as 0 / 1 */
+    const int32_t *mc_faces;         /* [sum MF][3] */
+    const double *cdf_mc;            /* [sum MF] */
+    const float *volume;             /* [n][D][H][W] */
+    const int64_t *meta;             /* [n][GN_RESIDENT_META] */
+    const float *grip;               /* [n][6]: the grip vertex in simulation space, in NOCS space */
+    const float *aabb;               /* [2][3]: the store's cloth_aabb_union */
+    int32_t n, D, H, W;
+} GnResidentStore;
+
+/* the selected rows sel[B][P] (indices into the sample's stored cloud) -> x = rgb / 255, y, pos [B*P][3] fp32 and batch[B*P] = garment.  noise [B][P][3]
+ * fp64 or NULL: pos = double(pos) + noise, and the rotation (p.x*R[j][0] + p.y*R[j][1]) + p.z*R[j][2] then runs in fp64, rounded once; without noise in fp32. */
+int gn_resident_points(const GnResidentStore *store, const int32_t *slots, int B, int P, const int32_t *sel, const double *noise, const float *rot, float *x,
+                       float *y, float *pos, int64_t *batch, void *stream);
+/* per garment: grip_pc_idx = the first selected row minimising fp32 sqrt((dx*dx + dy*dy) + dz*dz) to the simulation grip point (stored positions: no noise,
+ * no rotation), sim_grip [B][3] (rotated), nocs_grip [B][3], scale_bits, dataset_idx [B], aabb [B][2][3], rot_out [B][3][3] (identity when rot is NULL) */
+int gn_resident_garment(const GnResidentStore *store, const int32_t *slots, int B, int P, const int32_t *sel, const float *rot, int64_t *grip_pc_idx,
+                        float *sim_grip, float *nocs_grip, int64_t *scale_bits, int64_t *dataset_idx, float *aabb, float *rot_out, void *stream);
+/* M volume queries per garment: the first n_uniform are uniform[B][n_uniform][3]; the others a point of the NOCS mesh (face = upper bound of face_u in
+ * cdf_nocs; uv [..][2] flipped when u + v >= 1; barycentric_interpolation's fp64 -> fp32 accumulation) plus noise [..][3] in fp64, rounded to fp32 and clipped
+ * to [0, 1] (face_u, uv, noise: [B][M - n_uniform] rows).  value [B][M] = the garment's volume there, trilinear in fp32 in ATen's CPU order (corner weight
+ * (w_W*w_H)*w_D, corners added in (D, H, W) bit order, those past the far face skipped); occupancy != 0: value > 0.1 as 0 / 1.  rot: the queries turn about
+ * (0.5, 0.5, 0) AFTER the values are taken (task space). */
+int gn_resident_volume(const GnResidentStore *store, const int32_t *slots, int B, int M, int n_uniform, const float *uniform, const double *face_u,
+                       const double *uv, const double *noise, const float *rot, int occupancy, float *query, float *value, void *stream);
+/* M points of the garment mesh per garment: query [B][M][3] from the NOCS vertices and target from the simulation vertices (rot turns the target); task_space
+ * != 0: faces by cdf_task, query from task_verts (rot turns it about (0.5, 0.5, 0)), target from the NOCS vertices */
+int gn_resident_surface(const GnResidentStore *store, const int32_t *slots, int B, int M, const double *face_u, const double *uv, int task_space,
+                        const float *rot, float *query, float *target, void *stream);
+/* M points of the marching-cubes mesh per garment: query [B][M][3], on_surf [B][M] = interpolated is_vertex_on_surface > 0.5 as 0 / 1 */
+int gn_resident_mc_surface(const GnResidentStore *store, const int32_t *slots, int B, int M, const double *face_u, const double *uv, float *query,
+                           float *on_surf, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
