@@ -1166,6 +1166,16 @@ def nearest_neighbor_f64(query, ref):
     return nearest_neighbor_f64_batch([query], [ref])[0]
 
 
+def _faces_i32(f):
+    if f.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"faces: expected an integer tensor, got {f.dtype}")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces: expected an (F, 3) tensor, got {tuple(f.shape)}")
+    if f.dtype == torch.int64:              # int32 on the device; an index that does not fit is out of range: keep it so
+        f = f.clamp(min=-1, max=2 ** 31 - 1)
+    return f
+
+
 def point_mesh_sqdist_batch(queries, meshes):
     """fp64 unsigned squared distance of every query to the nearest triangle of its mesh, every (queries[k], meshes[k] = (verts, faces))
     pair in ONE launch (gn_point_mesh_sqdist_batch) -> list of (face_idx int32 [nq_k], d2 float64 [nq_k]).  libigl's
@@ -1177,15 +1187,7 @@ def point_mesh_sqdist_batch(queries, meshes):
         return []
     queries = [_rows3_f64(q, "query") for q in queries]
     verts = [_rows3_f64(v, "verts") for v, _ in meshes]
-    faces = []
-    for _, f in meshes:
-        if f.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"faces: expected an integer tensor, got {f.dtype}")
-        if f.dim() != 2 or f.shape[1] != 3:
-            raise ValueError(f"faces: expected an (F, 3) tensor, got {tuple(f.shape)}")
-        if f.dtype == torch.int64:          # int32 on the device; an index that does not fit is out of range: keep it so
-            f = f.clamp(min=-1, max=2 ** 31 - 1)
-        faces.append(f)
+    faces = [_faces_i32(f) for _, f in meshes]
     dev = queries[0].device
     q, qo = _cat_sets(queries, "query", dedup=False)
     v, vo = _cat_sets(verts, "verts")
@@ -1208,6 +1210,64 @@ def point_mesh_sqdist_batch(queries, meshes):
 def point_mesh_sqdist(query, verts, faces):
     """-> (face_idx int32 [Nq], d2 float64 [Nq]): squared distance of every query to the nearest triangle of (verts, faces)"""
     return point_mesh_sqdist_batch([query], [(verts, faces)])[0]
+
+
+def winding_number_batch(queries, meshes):
+    """fp64 generalised winding number of every query about its mesh, every (queries[k], meshes[k] = (verts, faces)) pair in ONE launch
+    (gn_winding_number_batch) -> list of float64 [nq_k].  The exact all-pairs sum of Van Oosterom-Strackee solid angles in face-index order,
+    divided by 4 pi (garmentnets_amd/winding.py has the definition): a pure function of (query, mesh), whatever else the launch carries.
+    An empty mesh gives 0.  A face index outside [0, V) raises IndexError (after the launch: one host synchronisation)."""
+    if len(queries) != len(meshes):
+        raise ValueError("winding_number_batch: one mesh per query set")
+    if not queries:
+        return []
+    queries = [_rows3_f64(q, "query") for q in queries]
+    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
+    faces = [_faces_i32(f) for _, f in meshes]
+    dev = queries[0].device
+    q, qo = _cat_sets(queries, "query", dedup=False)
+    v, vo = _cat_sets(verts, "verts")
+    f, fo = _cat_sets(faces, "faces", dtype=_i32)
+    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+        raise ValueError("winding_number_batch: more than 2^31 vertices or faces")
+    rows = [(qo[k], queries[k].shape[0], vo[k], verts[k].shape[0], fo[k], faces[k].shape[0]) for k in range(len(queries))]
+    pairs = _pairs_table(rows, dev)
+    max_nq = max(r[1] for r in rows)
+    out = torch.empty(q.shape[0], dtype=torch.float64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.call("gn_winding_number_batch", _p(q), _p(v), _p(f), _p(pairs), len(rows), max_nq, _p(out), _p(bad), _stream())
+    if int(bad.item()):
+        raise IndexError("winding_number: a face index is out of bounds for its mesh's vertices")
+    return [out[r[0]:r[0] + r[1]] for r in rows]
+
+
+def winding_number(query, verts, faces):
+    """-> float64 [Nq]: the generalised winding number of every query about the mesh (verts, faces)"""
+    return winding_number_batch([query], [(verts, faces)])[0]
+
+
+def winding_field_batch(meshes, shape):
+    """the winding number of every mesh of `meshes` = [(verts, faces)] at every node of a `shape` = (D, H, W) lattice over the unit cube, all
+    meshes in ONE launch (gn_winding_field_batch) -> (B, D, H, W) float32.  Node (i, j, k) is the point (i/(D-1), j/(H-1), k/(W-1)) (what
+    io.dataset.nocs_grid_sample reads); the kernel forms the points itself and writes float(w), rounded once: bit for bit
+    winding_number_batch at the lattice points, .float().  A face index outside [0, V) raises IndexError (after the launch)."""
+    D, H, W = (int(n) for n in shape)
+    if not meshes:
+        raise ValueError("winding_field_batch: no meshes")
+    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
+    faces = [_faces_i32(f) for _, f in meshes]
+    dev = verts[0].device
+    v, vo = _cat_sets(verts, "verts", dedup=False)
+    f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
+    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+        raise ValueError("winding_field_batch: more than 2^31 vertices or faces")
+    csr = _pairs_table([(vo[k], fo[k]) for k in range(len(meshes))] + [(v.shape[0], f.shape[0])], dev)
+    out = torch.empty((len(meshes), D, H, W), dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.call("gn_winding_field_batch", _p(v), _p(f), _p(csr), len(meshes), D, H, W, _p(out), _p(bad), _stream())
+    if int(bad.item()):
+        raise IndexError("winding_field: a face index is out of bounds for its mesh's vertices")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ validation losses

@@ -1,0 +1,161 @@
+"""python -m garmentnets_amd.prepare: complete a dataset store with the training targets that are computed from its garment meshes.
+
+Reads, per sample, mesh/{cloth_verts, cloth_nocs_verts, cloth_faces_tri} (and summary/cloth_aabb_union for the task-space group) and writes
+through io.zarr_store, with default_compressor():
+
+  volume/nocs_winding_number_field/<size>       the generalised winding number (winding.py) of the NOCS mesh at every node of the
+                                                size^3 lattice over the unit cube, float32
+  volume/sim_nocs_winding_number_field/<size>   the same of AABBGripNormalizer(cloth_aabb_union)(cloth_verts): the task-space vertices
+                                                io.dataset.get_surface_sample queries
+  marching_cube_mesh/ (--marching_cubes)        marching_cube_verts float32 (V, 3), marching_cube_faces int32 (F, 3): common.marching_cubes_util.
+                                                marching_cubes(NOCS field, 0.5, spacing 1/(size-1)); is_vertex_on_surface bool (V,)
+
+The on-surface rule is THIS PACKAGE'S OWN (the reference ships the flag, not how it was made): a marching-cubes vertex is on the surface
+when its distance to the NOCS mesh, sqrt(ops.point_mesh_sqdist), is <= tau.  The default tau = 1/(size-1) is derived, not tuned: a
+marching-cubes vertex lies on a lattice edge that the 0.5 level crosses, and where the garment's surface makes that crossing the surface
+passes through the same edge, within one edge length of the vertex; a vertex farther away than that closes the field over an opening.
+
+A field whose range does not contain 0.5 has no isosurface: its marching_cube_mesh arrays are written empty and the group's attributes
+say why ("empty": the reason).  Existing arrays are kept unless --overwrite is given.  Marching cubes and the distances run on the device
+whatever --backend says (the package has no host marching cubes); --backend picks who computes the winding numbers.
+"""
+import argparse
+import json
+import time
+
+import numpy as np
+
+from . import winding
+from .io import zarr_store
+from .io.dataset import TASK_SPACE_VOLUME_GROUP, AABBGripNormalizer
+
+NOCS_GROUP = "nocs_winding_number_field"
+GROUPS = (NOCS_GROUP, TASK_SPACE_VOLUME_GROUP)
+MESH_ARRAYS = ("cloth_verts", "cloth_nocs_verts", "cloth_faces_tri")
+MC_ARRAYS = ("marching_cube_verts", "marching_cube_faces", "is_vertex_on_surface")
+ISO_LEVEL = 0.5
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="complete a garmentnets dataset store: winding-number volumes and the marching-cubes mesh of "
+                                             "every sample, computed from its garment mesh")
+    ap.add_argument("--zarr_in", required=True, help="garmentnets dataset store (Zarr v2); completed in place")
+    ap.add_argument("--volume_size", type=int, default=128)
+    ap.add_argument("--groups", nargs="*", default=list(GROUPS), help=f"volume groups to build, of {GROUPS}")
+    ap.add_argument("--marching_cubes", action="store_true", help="build the marching_cube_mesh group from the NOCS field (on the device)")
+    ap.add_argument("--on_surface_distance", type=float, default=None, help="tau of the on-surface rule; default 1/(volume_size-1)")
+    ap.add_argument("--batch_size", type=int, default=4, help="garments per launch")
+    ap.add_argument("--overwrite", action="store_true", help="rebuild arrays that the store already holds")
+    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"), help="who computes the winding numbers")
+    return ap
+
+
+def sample_mesh(sample_group, group, aabb):
+    """(verts float64, faces) of the mesh whose field `group` holds"""
+    mesh = sample_group["mesh"]
+    faces = mesh["cloth_faces_tri"][:]
+    if group == NOCS_GROUP:
+        return mesh["cloth_nocs_verts"][:].astype(np.float64), faces
+    return np.asarray(AABBGripNormalizer(aabb)(mesh["cloth_verts"][:]), dtype=np.float64), faces
+
+
+def marching_cube_group(volume, nocs_verts, faces, tau):
+    """the three arrays of marching_cube_mesh for one NOCS field (device work) -> (dict of numpy arrays, None or why they are empty)"""
+    import torch
+
+    from . import ops
+    from .common import marching_cubes_util
+    dev = torch.device("cuda", torch.cuda.current_device())
+    size = volume.shape[-1]
+    try:
+        verts64, mc_faces, _, _, _ = marching_cubes_util.marching_cubes(torch.from_numpy(volume).to(dev), ISO_LEVEL, (1.0 / (size - 1),) * 3)
+    except (ValueError, RuntimeError) as e:
+        return {"marching_cube_verts": np.zeros((0, 3), np.float32), "marching_cube_faces": np.zeros((0, 3), np.int32),
+                "is_vertex_on_surface": np.zeros((0,), bool)}, str(e)
+    verts = verts64.float()                                  # what the store holds; the flag is measured from these
+    _, d2 = ops.point_mesh_sqdist(verts.double(), torch.from_numpy(np.ascontiguousarray(nocs_verts, dtype=np.float64)).to(dev),
+                                  torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int64)).to(dev))
+    return {"marching_cube_verts": verts.cpu().numpy(), "marching_cube_faces": mc_faces.to(torch.int32).cpu().numpy(),
+            "is_vertex_on_surface": (torch.sqrt(d2) <= tau).cpu().numpy()}, None
+
+
+def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False, on_surface_distance=None, batch_size=4, overwrite=False,
+                  backend="hip", log=print):
+    """-> summary dict {"samples", "written": {what: count}, "seconds"}; log gets one dict per sample"""
+    groups = list(groups)
+    unknown = [g for g in groups if g not in GROUPS]
+    if unknown:
+        raise ValueError(f"unknown volume group(s) {unknown}: this command builds {list(GROUPS)}")
+    size = int(volume_size)
+    if size < 2:
+        raise ValueError(f"volume_size {size}: a lattice needs at least 2 nodes per axis")
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size} < 1")
+    tau = 1.0 / (size - 1) if on_surface_distance is None else float(on_surface_distance)
+    root = zarr_store.open_group(zarr_in, create=False)
+    if "samples" not in root:
+        raise ValueError(f"{zarr_in}: no samples group")
+    samples = root["samples"]
+    keys = sorted(samples.keys())
+    for k in keys:
+        missing = [a for a in MESH_ARRAYS if f"mesh/{a}" not in samples[k]]
+        if missing:
+            raise ValueError(f"{zarr_in}: sample {k} has no mesh/{missing[0]}: the targets are computed from the garment meshes")
+    aabb = None
+    if TASK_SPACE_VOLUME_GROUP in groups:
+        if "summary/cloth_aabb_union" not in root:
+            raise ValueError(f"{zarr_in}: no summary/cloth_aabb_union, which {TASK_SPACE_VOLUME_GROUP} is normalised with")
+        aabb = root["summary"]["cloth_aabb_union"][:].astype(np.float32)          # the dtype GarmentInputDataset normalises with
+    comp = zarr_store.default_compressor()
+    written = {g: 0 for g in groups}
+    if marching_cubes:
+        written["marching_cube_mesh"] = 0
+    t_all = time.perf_counter()
+    for s in range(0, len(keys), batch_size):
+        chunk = keys[s:s + batch_size]
+        t0 = time.perf_counter()
+        did = {k: [] for k in chunk}
+        for g in groups:
+            todo = [k for k in chunk if overwrite or f"volume/{g}/{size}" not in samples[k]]
+            if not todo:
+                continue
+            fields = winding.winding_field([sample_mesh(samples[k], g, aabb) for k in todo], (size,) * 3, backend=backend)
+            for k, field in zip(todo, fields):
+                samples[k].require_group("volume").require_group(g).array(str(size), field, compressor=comp)
+                did[k].append(g)
+                written[g] += 1
+        if marching_cubes:
+            for k in chunk:
+                sg = samples[k]
+                if not overwrite and all(f"marching_cube_mesh/{a}" in sg for a in MC_ARRAYS):
+                    continue
+                if f"volume/{NOCS_GROUP}/{size}" not in sg:
+                    raise ValueError(f"sample {k}: --marching_cubes reads volume/{NOCS_GROUP}/{size}; build it in the same run (--groups)")
+                nocs_verts, faces = sample_mesh(sg, NOCS_GROUP, None)
+                arrays, empty = marching_cube_group(sg["volume"][NOCS_GROUP][str(size)][:], nocs_verts, faces, tau)
+                mc = sg.require_group("marching_cube_mesh")
+                for name in MC_ARRAYS:
+                    mc.array(name, arrays[name], compressor=comp)
+                mc.put_attrs({"empty": empty or False, "on_surface_distance": tau, "volume_size": size})
+                did[k].append("marching_cube_mesh")
+                written["marching_cube_mesh"] += 1
+        dt = time.perf_counter() - t0
+        for k in chunk:
+            log({"sample": k, "written": did[k], "seconds": dt / len(chunk)})
+    summary = {"samples": len(keys), "written": written, "seconds": time.perf_counter() - t_all}
+    log(summary)
+    return summary
+
+
+def main(argv=None):
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    try:
+        return prepare_store(a.zarr_in, a.volume_size, a.groups, a.marching_cubes, a.on_surface_distance, a.batch_size, a.overwrite, a.backend,
+                             log=lambda row: print(json.dumps(row)))
+    except ValueError as e:
+        ap.error(str(e))
+
+
+if __name__ == "__main__":
+    main()

@@ -13,7 +13,8 @@
  *   - stream is a hipStream_t passed as void* (NULL = default stream); all work is stream-ordered, no
  *     allocation, no host synchronisation, no global mutable state (LUTs are immutable).
  *   - dense float tensors are fp32, row-major with an explicit leading dimension (ld*) in elements.  Exception: the two
- *     evaluation distances (gn_nearest_neighbor_f64_batch, gn_point_mesh_sqdist_batch) take and return fp64 tensors.
+ *     evaluation distances (gn_nearest_neighbor_f64_batch, gn_point_mesh_sqdist_batch) take and return fp64 tensors, and the two
+ *     winding-number calls (gn_winding_number_batch, gn_winding_field_batch) take fp64 vertices.
  *   - volumes are CHANNEL-LAST: [B][D][H][W][C]  (the reference's NCDHW is a host-side view of this).
  *   - indices: point / vertex indices int32 on device (int64 only where the reference API exposes them).
  */
@@ -540,6 +541,30 @@ int gn_nearest_neighbor_f64_batch(const double *query, const double *ref, const 
  * meaningless).  P <= 65535. */
 int gn_point_mesh_sqdist_batch(const double *query, const double *verts, const int32_t *faces, const int64_t *pairs, int P, int64_t max_nq,
                                int32_t *face_idx, double *d2, int64_t *bad, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Dataset preparation: the generalised winding number of a triangle mesh (the WNF training target), fp64, all pairs, exact (no hierarchy).
+ * Per (query q, face (v0, v1, v2)): a = v0 - q, b = v1 - q, c = v2 - q (one subtraction per component),
+ *     la = sqrt((a.x*a.x + a.y*a.y) + a.z*a.z)  (lb, lc alike),  cr = b x c,  num = (a.x*cr.x + a.y*cr.y) + a.z*cr.z,
+ *     dab = (a.x*b.x + a.y*b.y) + a.z*b.z  (dbc, dca alike),  den = (((la*lb)*lc + dab*lc) + dbc*la) + dca*lb,
+ *     omega = 2 * atan2(num, den)   (Van Oosterom-Strackee),   w(q) = (0 + omega_0 + omega_1 + ...) / (4 pi) in face-index order,
+ * every operation rounded on its own (no fma).  A query on a vertex gets atan2(+-0, +0) = +-0 from the incident faces; an empty mesh gives 0.
+ * Each value is accumulated by one thread in face order: a pure function of (q, mesh), independent of the launch.
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* P (query set, mesh) pairs in one launch, the pairs table of gn_point_mesh_sqdist_batch: query / verts [*][3] fp64, faces [*][3] int32
+ * RELATIVE to the pair's v_off, pairs [P][6] int64 on the device = {q_off, nq, v_off, nv, f_off, nf}; max_nq = the largest nq.  out [*] fp64
+ * at the query rows.  A face with an index outside [0, nv) sets *bad = 1 (caller zeroes it) and contributes nothing.  P <= 65535. */
+int gn_winding_number_batch(const double *query, const double *verts, const int32_t *faces, const int64_t *pairs, int P, int64_t max_nq,
+                            double *out, int64_t *bad, void *stream);
+
+/* The winding number of B meshes at every node of a (D, H, W) lattice over the unit cube: node (i, j, k) is the point
+ * (i / (D-1), j / (H-1), k / (W-1)), divided in fp64 inside the kernel.  mesh_csr [B + 1][2] int64 on the device = {v_off, f_off}: mesh b
+ * owns the vertex rows v_off[b] .. v_off[b+1] - 1 and the face rows f_off[b] .. f_off[b+1] - 1, its face indices relative to v_off[b].
+ * out [B][D][H][W] float32 = float(w), rounded once: the bits of float(gn_winding_number_batch at the lattice points).  *bad as above.
+ * B <= 65535; D, H, W >= 2; D*H*W < 2^31. */
+int gn_winding_field_batch(const double *verts, const int32_t *faces, const int64_t *mesh_csr, int B, int D, int H, int W, float *out,
+                           int64_t *bad, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Validation losses (networks/pointnet2_nocs.py:257-440, networks/conv_implicit_wnf.py:405-452).
