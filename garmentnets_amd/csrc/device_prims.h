@@ -63,14 +63,13 @@ __device__ __forceinline__ int gn_wave_min(int v) {
     }
 
 // ------------------------------------------------------------------------------------------------ float orders for integer atomics
-// Three conventions, NOT interchangeable -- each site's memset / empty test / NaN rule depends on its own:
-//  * gn_ord_*  (grid scatter, unsigned compare): enc(x) is monotone in x and > 0 for every non-NaN float, so a zero-filled volume reads as
-//    "empty" and atomicMax on the encoding is an order-independent float max; ~enc(x) is > 0 too (atomicMax on it = float min) and
-//    gn_ord_dec_inv undoes it.  NaNs are not ordered.
-//  * gn_ord_enc_min / _max (isosurface value range, unsigned compare): the same code for numbers, but a NaN takes the extreme code of its side
-//    (0 for the atomicMin, ~0 for the atomicMax), wins, and gn_ord_dec turns it back into a NaN: numpy.min / numpy.max.
+// Two conventions, NOT interchangeable -- each site's memset / empty test depends on its own:
+//  * gn_ord_* (unsigned compare): the code is monotone in x and lies strictly between 0 and ~0 for every non-NaN float.  A NaN of EITHER sign
+//    takes the extreme code of its side (gn_ord_enc_min: 0 for an atomicMin, gn_ord_enc_max: ~0 for an atomicMax), wins, and gn_ord_dec turns it
+//    back into a NaN: numpy.min / numpy.max, torch's amin / amax.  The isosurface value range uses them as they are.  The grid scatter runs
+//    atomicMax on gn_ord_enc_max(x) for 'max' and on ~gn_ord_enc_min(x) for 'min' (gn_ord_dec_inv undoes the complement): both are > 0 for
+//    every float, a NaN included (~0 either way), so a zero-filled volume still reads as "empty".
 //  * gn_sord_* (sa_fused's LDS max, SIGNED compare): an involution on the bit pattern, enc(-inf) is the smallest code; nothing means "empty".
-__device__ __forceinline__ unsigned gn_ord_enc(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float gn_ord_dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
 // gn_ord_dec(~e), written out: (e's top bit clear: ~e has it set)
 __device__ __forceinline__ float gn_ord_dec_inv(unsigned e) { return __uint_as_float((e & 0x80000000u) ? e : (~e & 0x7fffffffu)); }

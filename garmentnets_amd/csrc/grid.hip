@@ -1,5 +1,5 @@
 // grid.hip -- VolumeFeatureAggregator: per-point cell index + aggregation features, scatter (max | mean | sum | min | mul) into a
-// channel-last feature volume.  Reference: /root/reference/networks/conv_implicit_wnf.py:43-100,
+// channel-last feature volume.  Reference: networks/conv_implicit_wnf.py:43-100,
 // components/gridding.py:161-256 (VirtualGrid index maths, fp32, truncation toward zero).
 #include "common.h"
 
@@ -67,8 +67,9 @@ extern "C" int gn_grid_features(const float *feat, int ldf, int Cf, const float 
 }
 
 // ------------------------------------------------------------------------------------------------ scatter
-// max: order-independent by construction (atomicMax on the gn_ord_enc code: > 0 for every non-NaN float, so a zero-filled cell reads as empty).  INV (min): atomicMax on ~enc(x), also > 0 for every non-NaN float, so a
-// zero-filled cell still reads as empty and the finalize pass still leaves untouched cells at 0.
+// max: order-independent by construction (atomicMax on the gn_ord_enc_max code: > 0 for every float, so a zero-filled cell reads as empty).  INV (min): atomicMax on ~gn_ord_enc_min(x), also > 0 for every float, so a
+// zero-filled cell still reads as empty and the finalize pass still leaves untouched cells at 0.  A NaN of either sign takes the code ~0 in both, wins, and decodes to a NaN: one NaN among a
+// cell's points makes that channel NaN, as under mean / sum / mul and as torch.scatter_reduce's amax / amin do (DESIGN.md "Gridding").
 template <bool INV>
 __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__restrict__ src, int lds, const int32_t *__restrict__ flat_idx,
                                                                 int64_t N, int C, float *__restrict__ vol, int32_t *__restrict__ count) {
@@ -79,8 +80,8 @@ __global__ __launch_bounds__(256) void scatter_max_accum_kernel(const float *__r
     if (lane == 0) atomicAdd(&count[cell], 1);
     float *v = vol + cell * C;
     for (int ch = lane; ch < C; ch += 64) {
-        const unsigned e = gn_ord_enc(src[p * lds + ch]);
-        atomicMax(reinterpret_cast<unsigned *>(v) + ch, INV ? ~e : e);
+        const float x = src[p * lds + ch];
+        atomicMax(reinterpret_cast<unsigned *>(v) + ch, INV ? ~gn_ord_enc_min(x) : gn_ord_enc_max(x));
     }
 }
 

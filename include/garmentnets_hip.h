@@ -172,7 +172,8 @@ int gn_grid_features(const float *feat, int ldf, int Cf, const float *nocs, cons
  * through order-independent fp64 partial sums, mul as a sequential fp32 product in ascending point index; the workspace `ws`
  * holds gn_grid_scatter_workspace_bytes(N, C, reduce) bytes (0 / NULL for max and min).  vol_is_zeroed != 0: the caller has already
  * zero-filled vol and count_ws (e.g. on a side stream, overlapped with the serial FPS kernels) and the memsets are skipped (mul
- * still writes its identity into every cell). */
+ * still writes its identity into every cell).  A NaN of either sign in any point of a cell makes that cell's channel NaN under every
+ * reduction (torch.scatter_reduce's rule); the other cells are not affected. */
 size_t gn_grid_scatter_workspace_bytes(int64_t N, int C, int reduce);
 int gn_grid_scatter(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int64_t cells, int reduce,
                     float *vol, int32_t *count_ws, void *ws, size_t ws_bytes, int vol_is_zeroed, void *stream);

@@ -21,6 +21,7 @@ from garmentnets_amd.batch import Batch  # noqa: E402
 from garmentnets_amd.common import marching_cubes_util as MCU  # noqa: E402
 from garmentnets_amd.components.pointnet2 import Segments  # noqa: E402
 from garmentnets_amd.networks.conv_implicit_wnf import ConvImplicitWNFPipeline  # noqa: E402
+from gridding_reference import sparse_first_conv_case  # noqa: E402
 
 DEV = "cuda:0"
 TOL = 1e-4   # north_star tolerance for fp32 WNF / NOCS / features
@@ -1539,43 +1540,7 @@ def test_sparse_first_conv_is_bit_identical_to_dense(G, mode, aiw):
     border-class constants (csrc/unet_split.hip tile_active / kconst / kreach).  Both outputs must equal the dense launches bit for
     bit (the epilogue statistics up to the order of their fp64 atomics): occupied cells in corners / on faces / in the interior, a
     garment without any point, a grid that is not a multiple of the tile."""
-    from garmentnets_amd.components.unet3d import AtRest, DoubleConv
-    g = torch.Generator().manual_seed(G)
-    B, C = 3, 128
-    cells = [torch.tensor([[0, 0, 0], [G - 1, G - 1, G - 1], [0, G - 1, 5], [G // 2, G // 2, G // 2], [G // 2, G // 2, G // 2 + 1], [3, 8, 9], [4, 7, 8]]),
-             torch.zeros((0, 3), dtype=torch.int64),
-             torch.randint(0, G, (200, 3), generator=g)]
-    flat = torch.cat([(((b * G + c[:, 0]) * G + c[:, 1]) * G + c[:, 2]) for b, c in enumerate(cells)]).to(torch.int32)
-    feats = torch.randn(flat.numel(), C, generator=g)
-    vol, stats = ops.grid_scatter(feats.to(DEV), flat.to(DEV), B, (G, G, G), "max", with_stats=True)
-    dc = DoubleConv(C, 32, encoder=True)                                   # 128 -> 128 -> 32, the shipped encoders.0
-    dc.load_state_dict({k: S.synthetic_tensor("c." + k, tuple(v.shape), 1) for k, v in dc.state_dict().items()})
-    dc = dc.to(DEV)
-    # aiw: both layers in the affine-in-weights form (arith.affine_in_weights: per-sample weight packs + bias table, csrc/conv_prep.hip) --
-    # the occupancy-aware launch must equal ITS dense launch bit for bit just the same
-    a_sp = AR.DEFAULT.replace(conv_mode=mode, sparse_first_conv=True, affine_in_weights=aiw)
-    a_dn = a_sp.replace(sparse_first_conv=False)
-    y1_s, st1_s, sp2 = dc.SingleConv1.run_at_rest(vol, AtRest(flat.to(DEV), 1), stats, arith=a_sp)
-    assert sp2.reach == 2 and sp2.small is not None and (sp2.value is not None) == aiw       # rest value reported <=> affine-in-weights ran
-    y2_s, st2_s, _ = dc.SingleConv2.run_at_rest(y1_s, sp2, st1_s, arith=a_sp)
-    both_s, _, both_rest = dc.run(vol, None, stats, None, sparse_flat=flat.to(DEV), arith=a_sp)
-    assert (both_rest is not None) == aiw
-    y1_d, st1_d, d2 = dc.SingleConv1.run_at_rest(vol, AtRest(flat.to(DEV), 1), stats, arith=a_dn)
-    assert (d2 is not None) == aiw and (d2 is None or (d2.small is None and d2.value is not None))          # no small volume when dense
-    # (layer 2's GroupNorm affine from the SAME statistics in both forms: the two launches' fp64 atomic sums agree to 1 ulp only, which
-    #  once in a while lands on the other side of an fp32 rounding boundary of the affine -- that is the atomics' order, not the kernels)
-    y2_d, st2_d, _ = dc.SingleConv2.run_at_rest(y1_d, d2, st1_s, arith=a_dn)
-    if aiw:            # the garment without a point is at rest everywhere: every interior voxel of layer 1's output IS the rest value
-        assert torch.equal(y1_d[1, 3, 4, 5], d2.value[1]) and torch.equal(y1_d[1, G // 2, G // 2, G // 2], d2.value[1])
-    f1, f2 = ops.grid_tile_flags(flat.to(DEV), B, (G, G, G), 1), ops.grid_tile_flags(flat.to(DEV), B, (G, G, G), 2)
-    a1, a2 = f1.sum(dim=1).tolist(), f2.sum(dim=1).tolist()
-    print(f"G={G} mode={mode}: active tiles per garment, layer 1 {a1} / layer 2 {a2} of {f1.shape[1]}")
-    assert a1[1] == 0 and a2[1] == 0 and 0 < a1[0] <= a2[0] < f1.shape[1] and bool((f2 >= f1).all())
-    assert torch.equal(y1_s, y1_d) and torch.equal(y2_s, y2_d) and torch.equal(both_s, y2_d)
-    # the statistics are fp64 atomic sums of identical per-tile fp32 partials: equal up to the order of the fp64 additions (1 ulp)
-    for (s_s, q_s, _), (s_d, q_d, _) in ((st1_s, st1_d), (st2_s, st2_d)):
-        assert float(((s_s - s_d).abs() / s_d.abs().clamp_min(1e-30)).max()) <= 1e-13 and float(((q_s - q_d).abs() / q_d.abs().clamp_min(1e-30)).max()) <= 1e-13
-    assert bool(torch.isfinite(y2_s).all()) and float(y2_s.abs().max()) > 0
+    sparse_first_conv_case((G, G, G), mode, aiw, DEV)          # the body, shared with the non-cubic grids of test_gpu_gridding_edges.py
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm affine in per-sample weights
