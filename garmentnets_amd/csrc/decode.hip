@@ -76,6 +76,15 @@ __device__ __forceinline__ void tri_query(const float *__restrict__ vol, int D, 
     }
 }
 
+// bytes per access of trilinear_kernel on volumes of C channels written with leading dimension ldo: the kernel's choice of mode AND the alignment the host
+// demands of the vol and out base pointers (with C % 4 == 0 / C even every voxel and, with ldo % 4 == 0 / ldo even, every row then is aligned as well)
+__host__ __device__ __forceinline__ int tri_access_bytes(int C, int ldo) {
+    const int lpq = C >> 2;   // lanes per query in 16-byte mode
+    if ((C & 3) == 0 && lpq <= 32 && (64 % lpq) == 0 && (ldo & 3) == 0) return 16;
+    return (C & 1) == 0 ? 8 : 4;
+}
+static inline bool gn_aligned(const void *p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+
 // each wavefront walks TRI_QPW consecutive queries (amortises wave launch, keeps several queries' gathers in flight)
 #define TRI_QPW 8
 __global__ __launch_bounds__(256) void trilinear_kernel(const float *__restrict__ vol, int D, int H, int W, int C,
@@ -88,7 +97,7 @@ __global__ __launch_bounds__(256) void trilinear_kernel(const float *__restrict_
     const int lane = threadIdx.x & 63;
     const int64_t mb = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * TRI_QPW;
     const int lpq = C >> 2;   // lanes per query in 16-byte mode
-    if ((C & 3) == 0 && lpq <= 32 && (64 % lpq) == 0 && (ldo & 3) == 0) {
+    if (tri_access_bytes(C, ldo) == 16) {
         const int qpw = 64 / lpq, sub = lane / lpq, c4 = lane % lpq;
         for (int q = sub; q < TRI_QPW; q += qpw)
             if (mb + q < M) tri_query(vol, D, H, W, C, query, Q, m0, mb + q, out, ldo, -(1 + c4));
@@ -104,7 +113,11 @@ __global__ __launch_bounds__(256) void trilinear_kernel(const float *__restrict_
 // least as fine as the volume (Q >= size: the north-star's 128^3 / 128^3, the shipped 128^3 / 32^3) neighbouring queries share
 // almost all of their 8 corners, so the brick's voxel bounding box (<= 6 x 6 x 6 voxels) of one 32-channel group is DMA'd into
 // LDS (global_load_lds, 128-byte pieces) and every corner is an LDS read: L2 traffic falls from 8 x 512 B per query to
-// ~1.8 x 512 B.  Same arithmetic and accumulation order as tri_query (bit-identical output, checked in the tests).
+// ~1.8 x 512 B.  Same arithmetic and accumulation order as tri_query: bit-identical output wherever that is finite (checked in the tests).  NON-FINITE
+// VOXELS: a corner past the volume's upper face is not skipped here but read as corner 0 with weight 0 (below), so a query whose cell corner (x0, y0, z0)
+// holds +-inf and which lies on an upper face (x0 = W - 1, y0 = H - 1 or z0 = D - 1: the last lattice plane of an axis, and every query on an axis of one
+// voxel) adds inf x 0 and gives NaN where tri_query and ATen give +-inf.  Corner 0 always carries a weight > 0, so the result is non-finite on either path;
+// no finite result differs, and a NaN voxel gives NaN on both (DESIGN.md "Decoder forward kernels at their edges").
 #define TB_I 4
 #define TB_J 4
 #define TB_K 4
@@ -131,7 +144,10 @@ __global__ __launch_bounds__(256) void trilinear_brick_kernel(const float *__res
     const int ly = (int)floorf(gn_tri_src_index(tb_coord(j0, Q), H)), hy = min((int)floorf(gn_tri_src_index(tb_coord(j1, Q), H)) + 1, H - 1);
     const int lz = (int)floorf(gn_tri_src_index(tb_coord(k0, Q), D)), hz = min((int)floorf(gn_tri_src_index(tb_coord(k1, Q), D)) + 1, D - 1);
     const int ex = hx - lx + 1, ey = hy - ly + 1, ez = hz - lz + 1, nvox = ex * ey * ez;
-    const bool in_lds = nvox <= cap_vox;            // always true for Q >= size (host-side bound); otherwise read the corners from L2
+    // always true under gn_trilinear_sample's dispatch (Q >= size, Q <= 1024): a brick of 4 lattice points per axis, started on any slab, spans at most 6 voxels
+    // per axis in this fp32 arithmetic (enumerated in tests/test_decoder_reference_host.py), so NO LAUNCH REACHES the !in_lds branch below; it is kept as the
+    // guard that keeps a box larger than the LDS allotment from ever being staged
+    const bool in_lds = nvox <= cap_vox;
 
     // ---- this thread's TB_Q/32 queries: 8 lanes per query (4 channels each within a 32-channel group)
     constexpr int NQ = TB_Q / 32;
@@ -202,7 +218,7 @@ __global__ __launch_bounds__(256) void trilinear_brick_kernel(const float *__res
             }
             return;
         }
-        // (a lattice coarser than the volume: the corners come from L2)
+        // (a box beyond the LDS allotment: the corners come from L2.  Dead under the host's dispatch, see in_lds above)
 #pragma unroll
         for (int qn = 0; qn < NQ; ++qn) {
             if (!(okm[qn] & 256u)) continue;
@@ -228,10 +244,11 @@ extern "C" int gn_trilinear_sample(const float *vol, int D, int H, int W, int C,
     if (M == 0) return GN_OK;   // (an empty query tensor has a NULL data pointer: not a lattice request)
     GN_REQUIRE(query != nullptr || (Q > 1 && Q <= 1024 && m0 >= 0 && m0 + M <= (int64_t)Q * Q * Q), "gn_trilinear_sample: bad lattice range");
     GN_REQUIRE((C & 1) || (ldo % 2 == 0), "gn_trilinear_sample: even channel counts need an even output leading dimension");
-    if (M == 0) return GN_OK;
+    GN_REQUIRE(vol != nullptr && out != nullptr, "gn_trilinear_sample: null pointer");
     // lattice chunks made of whole i-slabs, lattice at least as fine as the volume, 32-channel groups: the brick kernel
     const int64_t slab = (int64_t)Q * Q;
     if (query == nullptr && C % 32 == 0 && ldo % 4 == 0 && m0 % slab == 0 && M % slab == 0 && Q >= D && Q >= H && Q >= W) {
+        GN_REQUIRE(gn_aligned(vol, 16) && gn_aligned(out, 16), "gn_trilinear_sample: the lattice brick kernel needs 16-byte aligned vol and out");
         const int cap_vox = (TB_I + 2) * (TB_J + 2) * (TB_K + 2);           // extent <= points + 2 per axis when the spacing is <= 1 voxel
         const size_t lds = (((size_t)cap_vox * 128 + 4095) / 4096) * 4096;
         const int i_begin = (int)(m0 / slab), i_end = (int)((m0 + M) / slab);
@@ -240,6 +257,9 @@ extern "C" int gn_trilinear_sample(const float *vol, int D, int H, int W, int C,
         GN_LAUNCH_CHECK("gn_trilinear_sample");
         return GN_OK;
     }
+    const int ab = tri_access_bytes(C, ldo);
+    GN_REQUIRE(gn_aligned(vol, ab) && gn_aligned(out, ab), "gn_trilinear_sample: C = %d with ldo = %d is sampled in %d-byte accesses: vol and out must be aligned to them", C,
+               ldo, ab);
     hipLaunchKernelGGL(trilinear_kernel, dim3((unsigned)gn_cdiv(M, 4 * TRI_QPW)), dim3(256), 0, gn_stream(stream), vol, D, H, W, C, query, Q, m0, M,
                        out, ldo, (int64_t)0, (int64_t)0);
     GN_LAUNCH_CHECK("gn_trilinear_sample");
@@ -252,6 +272,9 @@ extern "C" int gn_trilinear_sample_batch(const float *vol, int B, int64_t vol_bs
     GN_REQUIRE((C & 1) || (ldo % 2 == 0), "gn_trilinear_sample_batch: even channel counts need an even output leading dimension");
     if (M == 0 || B == 0) return GN_OK;
     GN_REQUIRE(query != nullptr && vol != nullptr && out != nullptr, "gn_trilinear_sample_batch: null pointer");
+    const int ab = tri_access_bytes(C, ldo);
+    GN_REQUIRE(gn_aligned(vol, ab) && gn_aligned(out, ab) && (vol_bstride * 4) % ab == 0,
+               "gn_trilinear_sample_batch: C = %d with ldo = %d is sampled in %d-byte accesses: vol, its batch stride and out must be aligned to them", C, ldo, ab);
     hipLaunchKernelGGL(trilinear_kernel, dim3((unsigned)gn_cdiv(M, 4 * TRI_QPW), (unsigned)B), dim3(256), 0, gn_stream(stream), vol, D, H, W, C, query, 0,
                        (int64_t)0, M, out, ldo, vol_bstride, M * (int64_t)ldo);
     GN_LAUNCH_CHECK("gn_trilinear_sample_batch");
@@ -472,9 +495,13 @@ static int implicit_decode_impl(const float *vol, int D, int H, int W, int C0, c
                                 const float *s3, const float *t3, int OUT, float *out, int ldo, const float *run_if, int B, int run_if_bs, void *stream) {
     GN_REQUIRE((xin != nullptr || (vol != nullptr && D > 0 && H > 0 && W > 0)) && M >= 0 && ldo >= OUT, "gn_implicit_decode: bad sizes");
     if (M == 0) return GN_OK;
-    GN_REQUIRE(xin == nullptr || (ldxin >= C0 && ldxin % 4 == 0), "gn_implicit_decode: pre-sampled rows need a 16-byte aligned leading dimension");
+    GN_REQUIRE(xin == nullptr || (ldxin >= C0 && ldxin % 4 == 0 && gn_aligned(xin, 16)),
+               "gn_implicit_decode: pre-sampled rows need a 16-byte aligned base pointer and leading dimension");
+    GN_REQUIRE(out != nullptr && w1p != nullptr && w2p != nullptr && b1 != nullptr && b2 != nullptr, "gn_implicit_decode: null pointer");
+    GN_REQUIRE(gn_aligned(w1p, 16) && gn_aligned(w2p, 16), "gn_implicit_decode: the weight packs w1p and w2p must be 16-byte aligned");
     GN_REQUIRE(C0 % 32 == 0 && N1 % 256 == 0 && N2 % 256 == 0 && OUT >= 1 && OUT <= 4,
                "gn_implicit_decode: unsupported layer widths [%d,%d,%d,%d] (need C0 %% 32 == 0, N1 and N2 multiples of 256, out <= 4)", C0, N1, N2, OUT);
+    GN_REQUIRE(w3 != nullptr && b3 != nullptr, "gn_implicit_decode: null pointer");
     GN_REQUIRE(xin != nullptr || query != nullptr || (Q > 1 && Q <= 1024 && m0 >= 0 && m0 + M <= (int64_t)Q * Q * Q), "gn_implicit_decode: bad lattice range");
     GN_REQUIRE((s1 == nullptr) == (t1 == nullptr) && (s2 == nullptr) == (t2 == nullptr) && (s3 == nullptr) == (t3 == nullptr),
                "gn_implicit_decode: BN scale and shift must come together");

@@ -700,13 +700,15 @@ def maxpool3d_2(x, with_stats=False):
 
 # ------------------------------------------------------------------------------------------------ decoder
 def trilinear_sample(vol_b, query=None, Q=0, m0=0, M=None, out=None):
-    """vol_b: one sample, channel-last [D][H][W][C].  query [M][3] or lattice rows m0..m0+M of (Q,Q,Q)."""
-    D, H, W, C = vol_b.shape
+    """vol_b: one sample, channel-last [D][H][W][C], packed fp32.  query [M][3] or lattice rows m0..m0+M of (Q,Q,Q)."""
+    D, H, W, C = _chk(vol_b, torch.float32, "vol_b").shape
     if query is not None:
         M = query.shape[0]
         _chk(query, torch.float32, "query")
     if out is None:
         out = new_rows(M, C, vol_b.device)
+    elif out.dtype != torch.float32:
+        raise TypeError(f"out: expected {torch.float32}, got {out.dtype}")
     _lib.call("gn_trilinear_sample", _p(vol_b), D, H, W, C, _p(query), int(Q), int(m0), int(M), _p(out), rows_view(out)[1], _stream())
     return out
 
@@ -725,20 +727,36 @@ def implicit_decode(vol_b, layers, query=None, Q=0, m0=0, M=None, out=None, xin=
     is non-zero (the fp32 twin of a gated implicit_decode_split call)."""
     (w1p, b1, s1, t1, N1), (w2p, b2, s2, t2, N2), (w3, b3, s3, t3, OUT) = layers
     if xin is not None:
+        if xin.dtype != torch.float32:
+            raise TypeError(f"xin: expected {torch.float32}, got {xin.dtype}")
         D = H = W = 0
         M, C0 = xin.shape
         ldxin = rows_view(xin)[1]
+        vol_b = None                                    # (unused by the kernel)
     else:
-        D, H, W, C0 = vol_b.shape
+        D, H, W, C0 = _chk(vol_b, torch.float32, "vol_b").shape
         ldxin = 0
     if query is not None:
         M = query.shape[0]
         _chk(query, torch.float32, "query")
     if out is None:
         out = torch.empty((M, OUT), dtype=torch.float32, device=(xin if xin is not None else vol_b).device)
+    elif out.dtype != torch.float32:
+        raise TypeError(f"out: expected {torch.float32}, got {out.dtype}")
     _lib.call("gn_implicit_decode", _p(vol_b), D, H, W, C0, _p(xin), ldxin, _p(query), int(Q), int(m0), int(M), _p(w1p), _p(b1), _p(s1), _p(t1), N1,
               _p(w2p), _p(b2), _p(s2), _p(t2), N2, _p(w3), _p(b3), _p(s3), _p(t3), OUT, _p(out), rows_view(out)[1], _p(run_if), _stream())
     return out
+
+
+def _chk_row_sets(t, name):
+    """t (B, M, C) fp32 as the batch kernels address it: rows of unit stride, leading dimension stride(1), row sets packed back to back"""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected {torch.float32}, got {t.dtype}")
+    if t.dim() == 3 and t.numel() == 0:              # (nothing is addressed: the kernels return before any launch)
+        return t
+    if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1) or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+        raise ValueError(f"{name}: need (B, M, C) rows of unit stride, the row sets packed back to back")
+    return t
 
 
 def trilinear_sample_batch(vol, query, out=None):
@@ -749,6 +767,7 @@ def trilinear_sample_batch(vol, query, out=None):
     _chk(query, torch.float32, "query")
     if out is None:
         out = torch.empty((B, M, pad4(C)), dtype=torch.float32, device=vol.device)[:, :, :C]
+    _chk_row_sets(out, "out")
     _lib.call("gn_trilinear_sample_batch", _p(vol), B, vol.stride(0), D, H, W, C, _p(query), int(M), _p(out), out.stride(1), _stream())
     return out
 
@@ -757,7 +776,8 @@ def implicit_decode_batch(xin, layers, out, run_if=None, run_if_stride=0):
     """implicit_decode(xin=...) for B row sets in one launch: xin (B, M, C0) [row stride = leading dimension], out (B, M, OUT); run_if: one device flag per
     row set at run_if[b * run_if_stride] (the gated fp32 twin of implicit_decode_split_batch)"""
     (w1p, b1, s1, t1, N1), (w2p, b2, s2, t2, N2), (w3, b3, s3, t3, OUT) = layers
-    B, M, C0 = xin.shape
+    B, M, C0 = _chk_row_sets(xin, "xin").shape
+    _chk_row_sets(out, "out")
     _lib.call("gn_implicit_decode_batch", _p(xin), xin.stride(1), int(M), B, C0, _p(w1p), _p(b1), _p(s1), _p(t1), N1, _p(w2p), _p(b2), _p(s2), _p(t2), N2,
               _p(w3), _p(b3), _p(s3), _p(t3), OUT, _p(out), out.stride(1), _p(run_if), int(run_if_stride), _stream())
     return out

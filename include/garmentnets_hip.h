@@ -381,11 +381,16 @@ int gn_maxpool3d_2(const float *in, int B, int D, int H, int W, int C, float *ou
 /* Trilinear feature sampling.  replaces F.grid_sample(bilinear, border, align_corners=True) on a 5-D input --
  * networks/conv_implicit_wnf.py:135-145 (including its axis convention: query x -> LAST volume axis).
  * vol: one sample [D][H][W][C].  If query == NULL the queries are the lattice of predict.py:145-147:
- * q[i][j][k] = (i,j,k) * (1/(Q-1)), rows m0..m0+M of the flattened (Q,Q,Q) lattice. */
+ * q[i][j][k] = (i,j,k) * (1/(Q-1)), rows m0..m0+M of the flattened (Q,Q,Q) lattice.
+ * vol is PACKED fp32 (no strides).  Alignment: channels are moved in 16-byte accesses when C is 4, 8, 16, 32, 64 or 128 and ldo % 4 == 0, and whenever the lattice
+ * brick kernel serves the call (query == NULL, C % 32 == 0, ldo % 4 == 0, whole i-slabs, Q >= D, H, W); in 8-byte accesses for every other even C (ldo must be even);
+ * one float at a time for odd C.  vol and out must be aligned to the access size: GN_EINVAL otherwise, before any launch.
+ * A NaN query component samples source index 0 (fmax's rule; ATen's std::max chain gives size - 1).  Results are ATen's grid_sampler_3d bits, with one exception in
+ * the brick kernel: where the lower cell corner (x0, y0, z0) holds +-inf and the query lies on an upper face of the volume it returns NaN, not +-inf. */
 int gn_trilinear_sample(const float *vol, int D, int H, int W, int C, const float *query, int Q, int64_t m0, int64_t M,
                         float *out, int ldo, void *stream);
 /* the query form for B volumes in one launch (round 6; the surface decoders of predict.py:184-187 for a whole batch): volume b = vol + b * vol_bstride
- * floats, its M queries query [b][M][3], its rows out [b][M][ldo]. */
+ * floats, its M queries query [b][M][3], its rows out [b][M][ldo].  Alignment as gn_trilinear_sample's per-query form; vol_bstride must keep it for every volume. */
 int gn_trilinear_sample_batch(const float *vol, int B, int64_t vol_bstride, int D, int H, int W, int C, const float *query, int64_t M, float *out, int ldo,
                               void *stream);
 
@@ -394,7 +399,8 @@ int gn_trilinear_sample_batch(const float *vol, int B, int64_t vol_bstride, int 
  * predict.py:145-157,184-187.  Activations stay in LDS; w1p / w2p are k-pair-major packs Wp[k/2][n][2] of the Linear
  * weights W[n][k]; w3 is [OUT][N2] row-major; (s*, t*) are the folded eval-BatchNorm scale/shift (NULL = no BN).
  * If xin != NULL the rows xin[M][C0] (ld ldxin) are used instead of sampling (two-kernel form: gn_trilinear_sample first).
- * Constraints: C0 % 32 == 0, N1 and N2 multiples of 256, OUT <= 4 (otherwise use gn_trilinear_sample + gn_linear).
+ * Constraints: C0 % 32 == 0, N1 and N2 multiples of 256, OUT <= 4 (otherwise use gn_trilinear_sample + gn_linear); xin, w1p and w2p 16-byte aligned and
+ * ldxin % 4 == 0 (16-byte loads; GN_EINVAL otherwise, before any launch); vol packed fp32, read one float at a time (no alignment beyond a float's).
  * run_if: NULL, or a device float: the launch does nothing unless *run_if != 0 (pairs with gn_implicit_decode_split, which skips
  * the garments gn_decoder_input_scale marks unsafe for the fp16 planes: the choice is made on the device, without a host sync). */
 int gn_implicit_decode(const float *vol, int D, int H, int W, int C0, const float *xin, int ldxin, const float *query, int Q, int64_t m0, int64_t M,
