@@ -99,6 +99,7 @@ PROTOTYPES = {
     "gn_point_mesh_sqdist_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
     "gn_winding_number_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "gn_winding_field_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "gn_distance_field_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "gn_nocs_bin_metrics_workspace_bytes": [_vp, _i32],
     "gn_nocs_bin_metrics": [_vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
     "gn_value_losses_workspace_bytes": [_vp, _i32],

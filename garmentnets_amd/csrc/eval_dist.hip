@@ -3,8 +3,10 @@
 //   gn_nearest_neighbor_f64_batch  exact 1-NN (scipy cKDTree.query(k=1)) -- chamfer, hybrid chamfer, gradient threshold
 //   gn_point_mesh_sqdist_batch     unsigned squared point-to-triangle-mesh distance (libigl point_mesh_squared_distance,
 //                                  what igl.hausdorff calls in both directions)
+//   gn_distance_field_batch        the same distance at every node of a (D, H, W) lattice over the unit cube, B meshes in one launch: the
+//                                  distance, signed-distance and occupancy training targets (garmentnets_amd/distance.py)
 //
-// Both take a pairs table so that one launch serves every (query set, reference set) pair of a sample: blockIdx.y = pair,
+// The first two take a pairs table so that one launch serves every (query set, reference set) pair of a sample: blockIdx.y = pair,
 // blockIdx.x = a block of 256 queries (one per thread), blocks past the pair's query count leave at once.  The reference set
 // streams through LDS in SoA tiles; every lane reads the same LDS element at a time (a broadcast).  The library is built with
 // -ffp-contract=off and the per-pair arithmetic below has no fma: every distance is the plain-rounded expression written here.
@@ -87,6 +89,75 @@ __device__ __forceinline__ double pm_seg(double wx, double wy, double wz, double
     return ed_dot3(rx, ry, rz, rx, ry, rz);
 }
 
+// Stage the faces t0 .. t0 + n - 1 of the mesh (V, nv, F) into `tri`: the PM_NCONST constants of each.  Called by the whole workgroup of ED_BLOCK
+// threads between two barriers.  A face index outside [0, nv) sets *bad and is never dereferenced (a zero vertex stands in).
+__device__ __forceinline__ void pm_stage_tile(double (*tri)[PM_TILE], const double *__restrict__ V, int64_t nv, const int32_t *__restrict__ F, int64_t t0,
+                                              int n, int64_t *__restrict__ bad) {
+    for (int j = threadIdx.x; j < n; j += ED_BLOCK) {
+        double p[3][3];
+        for (int k = 0; k < 3; ++k) {
+            const int32_t vi = F[3 * (t0 + j) + k];
+            p[k][0] = p[k][1] = p[k][2] = 0.0;
+            if (vi >= 0 && vi < nv) {
+                p[k][0] = V[3 * (int64_t)vi]; p[k][1] = V[3 * (int64_t)vi + 1]; p[k][2] = V[3 * (int64_t)vi + 2];
+            } else {
+                *bad = 1;                                   // out of range: flagged, never read
+            }
+        }
+        const double e0x = __dsub_rn(p[1][0], p[0][0]), e0y = __dsub_rn(p[1][1], p[0][1]), e0z = __dsub_rn(p[1][2], p[0][2]);
+        const double e1x = __dsub_rn(p[2][0], p[0][0]), e1y = __dsub_rn(p[2][1], p[0][1]), e1z = __dsub_rn(p[2][2], p[0][2]);
+        const double e2x = __dsub_rn(p[2][0], p[1][0]), e2y = __dsub_rn(p[2][1], p[1][1]), e2z = __dsub_rn(p[2][2], p[1][2]);
+        const double a = ed_dot3(e0x, e0y, e0z, e0x, e0y, e0z), b = ed_dot3(e0x, e0y, e0z, e1x, e1y, e1z);
+        const double c = ed_dot3(e1x, e1y, e1z, e1x, e1y, e1z), l2 = ed_dot3(e2x, e2y, e2z, e2x, e2y, e2z);
+        const double det = __dsub_rn(__dmul_rn(a, c), __dmul_rn(b, b));
+        tri[PM_V0X][j] = p[0][0]; tri[PM_V0Y][j] = p[0][1]; tri[PM_V0Z][j] = p[0][2];
+        tri[PM_E0X][j] = e0x; tri[PM_E0Y][j] = e0y; tri[PM_E0Z][j] = e0z;
+        tri[PM_E1X][j] = e1x; tri[PM_E1Y][j] = e1y; tri[PM_E1Z][j] = e1z;
+        tri[PM_V1X][j] = p[1][0]; tri[PM_V1Y][j] = p[1][1]; tri[PM_V1Z][j] = p[1][2];
+        tri[PM_E2X][j] = e2x; tri[PM_E2Y][j] = e2y; tri[PM_E2Z][j] = e2z;
+        tri[PM_A][j] = a; tri[PM_B][j] = b; tri[PM_C][j] = c;
+        tri[PM_IDET][j] = pm_rcp_or_zero(det);
+        tri[PM_IA][j] = pm_rcp_or_zero(a); tri[PM_IC][j] = pm_rcp_or_zero(c); tri[PM_IE2][j] = pm_rcp_or_zero(l2);
+    }
+}
+
+// one staged triangle in registers: every lane reads the same LDS elements (a broadcast); a thread that owns several queries reads it once for all
+struct PmTri { double k[PM_NCONST]; };
+
+__device__ __forceinline__ PmTri pm_load(const double (*tri)[PM_TILE], int j) {
+    PmTri t;
+#pragma unroll
+    for (int c = 0; c < PM_NCONST; ++c) t.k[c] = tri[c][j];
+    return t;
+}
+
+// the squared distance from q to the staged triangle T: the per-pair arithmetic of both kernels below (no fma, the operation order written here)
+__device__ __forceinline__ double pm_sqdist(const PmTri &T, double qx, double qy, double qz) {
+    const double wx = __dsub_rn(qx, T.k[PM_V0X]), wy = __dsub_rn(qy, T.k[PM_V0Y]), wz = __dsub_rn(qz, T.k[PM_V0Z]);
+    const double e0x = T.k[PM_E0X], e0y = T.k[PM_E0Y], e0z = T.k[PM_E0Z];
+    const double e1x = T.k[PM_E1X], e1y = T.k[PM_E1Y], e1z = T.k[PM_E1Z];
+    const double d0 = ed_dot3(wx, wy, wz, e0x, e0y, e0z), d1 = ed_dot3(wx, wy, wz, e1x, e1y, e1z);
+    // the three clamped segment distances (a zero-length edge clamps to its start point: degenerate triangles land here)
+    const double s0 = pm_seg(wx, wy, wz, e0x, e0y, e0z, d0, T.k[PM_IA]);
+    const double s1 = pm_seg(wx, wy, wz, e1x, e1y, e1z, d1, T.k[PM_IC]);
+    const double ux = __dsub_rn(qx, T.k[PM_V1X]), uy = __dsub_rn(qy, T.k[PM_V1Y]), uz = __dsub_rn(qz, T.k[PM_V1Z]);
+    const double e2x = T.k[PM_E2X], e2y = T.k[PM_E2Y], e2z = T.k[PM_E2Z];
+    const double s2 = pm_seg(ux, uy, uz, e2x, e2y, e2z, ed_dot3(ux, uy, uz, e2x, e2y, e2z), T.k[PM_IE2]);
+    // the projection onto the plane in barycentric form: w = s e0 + t e1 + (normal part)
+    const double a = T.k[PM_A], b = T.k[PM_B], c = T.k[PM_C], idet = T.k[PM_IDET];
+    const double s = __dmul_rn(__dsub_rn(__dmul_rn(c, d0), __dmul_rn(b, d1)), idet);
+    const double t = __dmul_rn(__dsub_rn(__dmul_rn(a, d1), __dmul_rn(b, d0)), idet);
+    const double rx = __dsub_rn(__dsub_rn(wx, __dmul_rn(s, e0x)), __dmul_rn(t, e1x));
+    const double ry = __dsub_rn(__dsub_rn(wy, __dmul_rn(s, e0y)), __dmul_rn(t, e1y));
+    const double rz = __dsub_rn(__dsub_rn(wz, __dmul_rn(s, e0z)), __dmul_rn(t, e1z));
+    const double plane = ed_dot3(rx, ry, rz, rx, ry, rz);
+    const bool inside = idet > 0.0 && s >= 0.0 && t >= 0.0 && __dadd_rn(s, t) <= 1.0;
+    // the segment distances stay in the minimum when the projection is inside: on a sliver (det nearly cancelled) s and t are
+    // noise, `plane` is then only an upper bound and an edge can be closer
+    const double seg = fmin(fmin(s0, s1), s2);
+    return inside ? fmin(plane, seg) : seg;
+}
+
 __global__ __launch_bounds__(ED_BLOCK) void point_mesh_sqdist_batch_kernel(const double *__restrict__ q, const double *__restrict__ verts,
                                                                            const int32_t *__restrict__ faces, const int64_t *__restrict__ pairs,
                                                                            int32_t *__restrict__ face_idx, double *__restrict__ d2,
@@ -114,57 +185,10 @@ __global__ __launch_bounds__(ED_BLOCK) void point_mesh_sqdist_batch_kernel(const
     for (int64_t t0 = 0; t0 < nf; t0 += PM_TILE) {
         const int n = (int)((nf - t0) < PM_TILE ? (nf - t0) : PM_TILE);
         __syncthreads();
-        for (int j = threadIdx.x; j < n; j += ED_BLOCK) {
-            double p[3][3];
-            for (int k = 0; k < 3; ++k) {
-                const int32_t vi = F[3 * (t0 + j) + k];
-                p[k][0] = p[k][1] = p[k][2] = 0.0;
-                if (vi >= 0 && vi < nv) {
-                    p[k][0] = V[3 * (int64_t)vi]; p[k][1] = V[3 * (int64_t)vi + 1]; p[k][2] = V[3 * (int64_t)vi + 2];
-                } else {
-                    *bad = 1;                               // out of range: flagged, never read (a zero vertex stands in)
-                }
-            }
-            const double e0x = __dsub_rn(p[1][0], p[0][0]), e0y = __dsub_rn(p[1][1], p[0][1]), e0z = __dsub_rn(p[1][2], p[0][2]);
-            const double e1x = __dsub_rn(p[2][0], p[0][0]), e1y = __dsub_rn(p[2][1], p[0][1]), e1z = __dsub_rn(p[2][2], p[0][2]);
-            const double e2x = __dsub_rn(p[2][0], p[1][0]), e2y = __dsub_rn(p[2][1], p[1][1]), e2z = __dsub_rn(p[2][2], p[1][2]);
-            const double a = ed_dot3(e0x, e0y, e0z, e0x, e0y, e0z), b = ed_dot3(e0x, e0y, e0z, e1x, e1y, e1z);
-            const double c = ed_dot3(e1x, e1y, e1z, e1x, e1y, e1z), l2 = ed_dot3(e2x, e2y, e2z, e2x, e2y, e2z);
-            const double det = __dsub_rn(__dmul_rn(a, c), __dmul_rn(b, b));
-            tri[PM_V0X][j] = p[0][0]; tri[PM_V0Y][j] = p[0][1]; tri[PM_V0Z][j] = p[0][2];
-            tri[PM_E0X][j] = e0x; tri[PM_E0Y][j] = e0y; tri[PM_E0Z][j] = e0z;
-            tri[PM_E1X][j] = e1x; tri[PM_E1Y][j] = e1y; tri[PM_E1Z][j] = e1z;
-            tri[PM_V1X][j] = p[1][0]; tri[PM_V1Y][j] = p[1][1]; tri[PM_V1Z][j] = p[1][2];
-            tri[PM_E2X][j] = e2x; tri[PM_E2Y][j] = e2y; tri[PM_E2Z][j] = e2z;
-            tri[PM_A][j] = a; tri[PM_B][j] = b; tri[PM_C][j] = c;
-            tri[PM_IDET][j] = pm_rcp_or_zero(det);
-            tri[PM_IA][j] = pm_rcp_or_zero(a); tri[PM_IC][j] = pm_rcp_or_zero(c); tri[PM_IE2][j] = pm_rcp_or_zero(l2);
-        }
+        pm_stage_tile(tri, V, nv, F, t0, n, bad);
         __syncthreads();
         for (int j = 0; j < n; ++j) {
-            const double wx = __dsub_rn(qx, tri[PM_V0X][j]), wy = __dsub_rn(qy, tri[PM_V0Y][j]), wz = __dsub_rn(qz, tri[PM_V0Z][j]);
-            const double e0x = tri[PM_E0X][j], e0y = tri[PM_E0Y][j], e0z = tri[PM_E0Z][j];
-            const double e1x = tri[PM_E1X][j], e1y = tri[PM_E1Y][j], e1z = tri[PM_E1Z][j];
-            const double d0 = ed_dot3(wx, wy, wz, e0x, e0y, e0z), d1 = ed_dot3(wx, wy, wz, e1x, e1y, e1z);
-            // the three clamped segment distances (a zero-length edge clamps to its start point: degenerate triangles land here)
-            const double s0 = pm_seg(wx, wy, wz, e0x, e0y, e0z, d0, tri[PM_IA][j]);
-            const double s1 = pm_seg(wx, wy, wz, e1x, e1y, e1z, d1, tri[PM_IC][j]);
-            const double ux = __dsub_rn(qx, tri[PM_V1X][j]), uy = __dsub_rn(qy, tri[PM_V1Y][j]), uz = __dsub_rn(qz, tri[PM_V1Z][j]);
-            const double e2x = tri[PM_E2X][j], e2y = tri[PM_E2Y][j], e2z = tri[PM_E2Z][j];
-            const double s2 = pm_seg(ux, uy, uz, e2x, e2y, e2z, ed_dot3(ux, uy, uz, e2x, e2y, e2z), tri[PM_IE2][j]);
-            // the projection onto the plane in barycentric form: w = s e0 + t e1 + (normal part)
-            const double a = tri[PM_A][j], b = tri[PM_B][j], c = tri[PM_C][j], idet = tri[PM_IDET][j];
-            const double s = __dmul_rn(__dsub_rn(__dmul_rn(c, d0), __dmul_rn(b, d1)), idet);
-            const double t = __dmul_rn(__dsub_rn(__dmul_rn(a, d1), __dmul_rn(b, d0)), idet);
-            const double rx = __dsub_rn(__dsub_rn(wx, __dmul_rn(s, e0x)), __dmul_rn(t, e1x));
-            const double ry = __dsub_rn(__dsub_rn(wy, __dmul_rn(s, e0y)), __dmul_rn(t, e1y));
-            const double rz = __dsub_rn(__dsub_rn(wz, __dmul_rn(s, e0z)), __dmul_rn(t, e1z));
-            const double plane = ed_dot3(rx, ry, rz, rx, ry, rz);
-            const bool inside = idet > 0.0 && s >= 0.0 && t >= 0.0 && __dadd_rn(s, t) <= 1.0;
-            // the segment distances stay in the minimum when the projection is inside: on a sliver (det nearly cancelled) s and t are
-            // noise, `plane` is then only an upper bound and an edge can be closer
-            const double seg = fmin(fmin(s0, s1), s2);
-            const double d = inside ? fmin(plane, seg) : seg;
+            const double d = pm_sqdist(pm_load(tri, j), qx, qy, qz);
             if (d < best) { best = d; bi = (int)(t0 + j); }          // strict: ties keep the lowest face index
         }
     }
@@ -172,6 +196,60 @@ __global__ __launch_bounds__(ED_BLOCK) void point_mesh_sqdist_batch_kernel(const
         if (isnan(qx) || isnan(qy) || isnan(qz)) best = __longlong_as_double(0x7ff8000000000000LL);   // a NaN query has no distance
         face_idx[q_off + i] = bi;
         d2[q_off + i] = best;
+    }
+}
+
+// The lattice form: every node of a (D, H, W) lattice over the unit cube against each of B meshes (blockIdx.y), the nodes formed here as
+// winding_field_batch_kernel forms them.  A thread owns DF_QPT nodes in registers, a workgroup DF_SPAN consecutive ones; each broadcast read of
+// a staged triangle serves all DF_QPT.  Every node scans the faces in index order with the strict `<` of the kernel above and is written by its
+// one owner: no atomics, no cross-thread reduction, and (face_idx, d2) are the bits gn_point_mesh_sqdist_batch gives at the lattice points.
+#define DF_QPT 4
+#define DF_SPAN (ED_BLOCK * DF_QPT)
+
+__global__ __launch_bounds__(ED_BLOCK) void distance_field_batch_kernel(const double *__restrict__ verts, const int32_t *__restrict__ faces,
+                                                                        const int64_t *__restrict__ mesh_csr, int D, int H, int W,
+                                                                        int32_t *__restrict__ face_idx, double *__restrict__ d2,
+                                                                        int64_t *__restrict__ bad) {
+    __shared__ double tri[PM_NCONST][PM_TILE];
+    const int64_t *m = mesh_csr + 2 * (int64_t)blockIdx.y;
+    const int64_t v_off = m[0], nv = m[2] - m[0], f_off = m[1], nf = m[3] - m[1];
+    const int32_t *F = faces + 3 * f_off;
+    const double *V = verts + 3 * v_off;
+    const int64_t nq = (int64_t)D * H * W;
+    const int64_t i0 = (int64_t)blockIdx.x * DF_SPAN;        // < nq: the grid has cdiv(nq, DF_SPAN) blocks along x
+    const double sd = (double)(D - 1), sh = (double)(H - 1), sw = (double)(W - 1);
+    double qx[DF_QPT], qy[DF_QPT], qz[DF_QPT], best[DF_QPT];
+    int bi[DF_QPT];
+#pragma unroll
+    for (int k = 0; k < DF_QPT; ++k) {
+        const int64_t i = i0 + k * ED_BLOCK + threadIdx.x;
+        qx[k] = qy[k] = qz[k] = 0.0;
+        best[k] = __longlong_as_double(0x7ff0000000000000LL);    // +inf
+        bi[k] = -1;
+        if (i < nq) {                                        // node (id, ih, iw) is the point (id / (D-1), ih / (H-1), iw / (W-1))
+            const int iw = (int)(i % W), ih = (int)((i / W) % H), id = (int)(i / ((int64_t)W * H));
+            qx[k] = __ddiv_rn((double)id, sd); qy[k] = __ddiv_rn((double)ih, sh); qz[k] = __ddiv_rn((double)iw, sw);
+        }
+    }
+    for (int64_t t0 = 0; t0 < nf; t0 += PM_TILE) {
+        const int n = (int)((nf - t0) < PM_TILE ? (nf - t0) : PM_TILE);
+        __syncthreads();
+        pm_stage_tile(tri, V, nv, F, t0, n, bad);
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const PmTri T = pm_load(tri, j);
+#pragma unroll
+            for (int k = 0; k < DF_QPT; ++k) {
+                const double d = pm_sqdist(T, qx[k], qy[k], qz[k]);
+                if (d < best[k]) { best[k] = d; bi[k] = (int)(t0 + j); }      // strict: ties keep the lowest face index
+            }
+        }
+    }
+    const int64_t o = (int64_t)blockIdx.y * nq;
+#pragma unroll
+    for (int k = 0; k < DF_QPT; ++k) {
+        const int64_t i = i0 + k * ED_BLOCK + threadIdx.x;
+        if (i < nq) { face_idx[o + i] = bi[k]; d2[o + i] = best[k]; }
     }
 }
 
@@ -184,5 +262,18 @@ extern "C" int gn_point_mesh_sqdist_batch(const double *query, const double *ver
     hipLaunchKernelGGL(point_mesh_sqdist_batch_kernel, dim3((unsigned)(max_nq > 0 ? gn_cdiv(max_nq, ED_BLOCK) : 1), (unsigned)P), dim3(ED_BLOCK), 0,
                        gn_stream(stream), query, verts, faces, pairs, face_idx, d2, bad);
     GN_LAUNCH_CHECK("gn_point_mesh_sqdist_batch");
+    return GN_OK;
+}
+
+extern "C" int gn_distance_field_batch(const double *verts, const int32_t *faces, const int64_t *mesh_csr, int B, int D, int H, int W,
+                                       int32_t *face_idx, double *d2, int64_t *bad, void *stream) {
+    GN_REQUIRE(B >= 0 && B <= 65535, "gn_distance_field_batch: B=%d outside [0, 65535]", B);
+    GN_REQUIRE(D >= 2 && H >= 2 && W >= 2 && (int64_t)D * H * W < INT32_MAX,
+               "gn_distance_field_batch: lattice (%d, %d, %d): every axis needs >= 2 nodes and D*H*W < 2^31", D, H, W);
+    if (B == 0) return GN_OK;
+    GN_REQUIRE(mesh_csr && face_idx && d2 && bad, "gn_distance_field_batch: null pointer");
+    hipLaunchKernelGGL(distance_field_batch_kernel, dim3((unsigned)gn_cdiv((int64_t)D * H * W, DF_SPAN), (unsigned)B), dim3(ED_BLOCK), 0,
+                       gn_stream(stream), verts, faces, mesh_csr, D, H, W, face_idx, d2, bad);
+    GN_LAUNCH_CHECK("gn_distance_field_batch");
     return GN_OK;
 }

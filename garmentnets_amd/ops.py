@@ -1290,6 +1290,33 @@ def winding_field_batch(meshes, shape):
     return out
 
 
+def distance_field_batch(meshes, shape):
+    """the squared distance from every node of a `shape` = (D, H, W) lattice over the unit cube (the lattice of winding_field_batch) to every mesh
+    of `meshes` = [(verts, faces)], all meshes in ONE launch (gn_distance_field_batch) -> (d2 float64 (B, D, H, W), face_idx int32 (B, D, H, W)).
+    Bit for bit point_mesh_sqdist_batch at the lattice points: ties -> lowest face index, an empty mesh gives (+inf, -1).  A face index outside
+    [0, V) raises IndexError (after the launch: one host synchronisation)."""
+    D, H, W = (int(n) for n in shape)
+    if not meshes:
+        raise ValueError("distance_field_batch: no meshes")
+    if min(D, H, W) < 2 or D * H * W >= 2 ** 31 - 1:        # the limits of the entry, refused here before the outputs are allocated
+        raise ValueError(f"gn_distance_field_batch: lattice {(D, H, W)}: every axis needs >= 2 nodes and D*H*W < 2^31")
+    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
+    faces = [_faces_i32(f) for _, f in meshes]
+    dev = verts[0].device
+    v, vo = _cat_sets(verts, "verts", dedup=False)
+    f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
+    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+        raise ValueError("distance_field_batch: more than 2^31 vertices or faces")
+    csr = _pairs_table([(vo[k], fo[k]) for k in range(len(meshes))] + [(v.shape[0], f.shape[0])], dev)
+    face_idx = torch.empty((len(meshes), D, H, W), dtype=_i32, device=dev)
+    d2 = torch.empty((len(meshes), D, H, W), dtype=torch.float64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.call("gn_distance_field_batch", _p(v), _p(f), _p(csr), len(meshes), D, H, W, _p(face_idx), _p(d2), _p(bad), _stream())
+    if int(bad.item()):
+        raise IndexError("distance_field: a face index is out of bounds for its mesh's vertices")
+    return d2, face_idx
+
+
 # ------------------------------------------------------------------------------------------------ validation losses
 def _check_sets(n):
     if not 1 <= n <= _lib.LOSS_MAX_SETS:

@@ -7,6 +7,10 @@ through io.zarr_store, with default_compressor():
                                                 size^3 lattice over the unit cube, float32
   volume/sim_nocs_winding_number_field/<size>   the same of AABBGripNormalizer(cloth_aabb_union)(cloth_verts): the task-space vertices
                                                 io.dataset.get_surface_sample queries
+  volume/nocs_distance_field/<size>             (--derived_groups) the distance from every node of that lattice to the NOCS mesh, float32
+  volume/nocs_signed_distance_field/<size>      (--derived_groups) clip(1 - 2 w, -1, 1) times that distance, w the stored nocs_winding_number_field of the
+                                                same size: minus the distance inside, plus outside, zero on the garment and where w crosses 0.5
+  volume/nocs_occupancy_grid/<size>             (--derived_groups) float32(w > 0.5)
   marching_cube_mesh/ (--marching_cubes)        marching_cube_verts float32 (V, 3), marching_cube_faces int32 (F, 3): common.marching_cubes_util.
                                                 marching_cubes(NOCS field, 0.5, spacing 1/(size-1)); is_vertex_on_surface bool (V,)
 
@@ -15,9 +19,12 @@ when its distance to the NOCS mesh, sqrt(ops.point_mesh_sqdist), is <= tau.  The
 marching-cubes vertex lies on a lattice edge that the 0.5 level crosses, and where the garment's surface makes that crossing the surface
 passes through the same edge, within one edge length of the vertex; a vertex farther away than that closes the field over an opening.
 
+The derived groups (distance.py has their definitions, this package's own as well) are built after --groups, a chunk of --batch_size garments
+per launch; the signed field and the occupancy grid read the stored winding field, so it has to be there or be built in the same run.
+
 A field whose range does not contain 0.5 has no isosurface: its marching_cube_mesh arrays are written empty and the group's attributes
-say why ("empty": the reason).  Existing arrays are kept unless --overwrite is given.  Marching cubes and the distances run on the device
-whatever --backend says (the package has no host marching cubes); --backend picks who computes the winding numbers.
+say why ("empty": the reason).  Existing arrays are kept unless --overwrite is given.  Marching cubes and the on-surface distances run on the device
+whatever --backend says (the package has no host marching cubes); --backend picks who computes the winding numbers and the lattice distances.
 """
 import argparse
 import json
@@ -25,12 +32,13 @@ import time
 
 import numpy as np
 
-from . import winding
+from . import distance, winding
 from .io import zarr_store
 from .io.dataset import TASK_SPACE_VOLUME_GROUP, AABBGripNormalizer
 
 NOCS_GROUP = "nocs_winding_number_field"
 GROUPS = (NOCS_GROUP, TASK_SPACE_VOLUME_GROUP)
+DERIVED_GROUPS = (distance.DISTANCE_GROUP, distance.SIGNED_DISTANCE_GROUP, distance.OCCUPANCY_GROUP)
 MESH_ARRAYS = ("cloth_verts", "cloth_nocs_verts", "cloth_faces_tri")
 MC_ARRAYS = ("marching_cube_verts", "marching_cube_faces", "is_vertex_on_surface")
 ISO_LEVEL = 0.5
@@ -42,11 +50,13 @@ def build_parser():
     ap.add_argument("--zarr_in", required=True, help="garmentnets dataset store (Zarr v2); completed in place")
     ap.add_argument("--volume_size", type=int, default=128)
     ap.add_argument("--groups", nargs="*", default=list(GROUPS), help=f"volume groups to build, of {GROUPS}")
+    ap.add_argument("--derived_groups", nargs="*", default=[], choices=DERIVED_GROUPS,
+                    help="volume groups to derive from the NOCS mesh's distance field and the stored NOCS winding field; default none")
     ap.add_argument("--marching_cubes", action="store_true", help="build the marching_cube_mesh group from the NOCS field (on the device)")
     ap.add_argument("--on_surface_distance", type=float, default=None, help="tau of the on-surface rule; default 1/(volume_size-1)")
     ap.add_argument("--batch_size", type=int, default=4, help="garments per launch")
     ap.add_argument("--overwrite", action="store_true", help="rebuild arrays that the store already holds")
-    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"), help="who computes the winding numbers")
+    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"), help="who computes the winding numbers and the lattice distances")
     return ap
 
 
@@ -79,13 +89,42 @@ def marching_cube_group(volume, nocs_verts, faces, tau):
             "is_vertex_on_surface": (torch.sqrt(d2) <= tau).cpu().numpy()}, None
 
 
+def build_derived_groups(samples, chunk, derived, size, overwrite, backend, comp):
+    """write the missing (or, with overwrite, all) `derived` volumes of the samples `chunk`; the distances of the whole chunk come from one
+    launch -> [(sample, group)] written"""
+    todo = {k: [g for g in derived if overwrite or f"volume/{g}/{size}" not in samples[k]] for k in chunk}
+    todo = {k: gs for k, gs in todo.items() if gs}
+    meshes, wnf = {}, {}
+    for k, gs in todo.items():
+        if any(g != distance.DISTANCE_GROUP for g in gs):
+            if f"volume/{NOCS_GROUP}/{size}" not in samples[k]:
+                raise ValueError(f"sample {k}: --derived_groups {' '.join(g for g in gs if g != distance.DISTANCE_GROUP)} reads "
+                                 f"volume/{NOCS_GROUP}/{size}; build it in the same run (--groups)")
+            wnf[k] = samples[k]["volume"][NOCS_GROUP][str(size)][:]
+        if any(g != distance.OCCUPANCY_GROUP for g in gs):
+            meshes[k] = sample_mesh(samples[k], NOCS_GROUP, None)
+            if len(meshes[k][1]) == 0:
+                raise ValueError(f"sample {k}: its mesh has no faces, so its distance to every lattice node is infinite: no target volume")
+    d2 = dict(zip(meshes, distance.distance_field(list(meshes.values()), (size,) * 3, backend=backend)[0])) if meshes else {}
+    done = []
+    for k, gs in todo.items():
+        for g in gs:
+            samples[k].require_group("volume").require_group(g).array(str(size), distance.derived_volume(g, d2.get(k), wnf.get(k)), compressor=comp)
+            done.append((k, g))
+    return done
+
+
 def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False, on_surface_distance=None, batch_size=4, overwrite=False,
-                  backend="hip", log=print):
+                  backend="hip", log=print, derived_groups=()):
     """-> summary dict {"samples", "written": {what: count}, "seconds"}; log gets one dict per sample"""
     groups = list(groups)
     unknown = [g for g in groups if g not in GROUPS]
     if unknown:
         raise ValueError(f"unknown volume group(s) {unknown}: this command builds {list(GROUPS)}")
+    derived = list(derived_groups)
+    unknown = [g for g in derived if g not in DERIVED_GROUPS]
+    if unknown:
+        raise ValueError(f"unknown derived group(s) {unknown}: this command derives {list(DERIVED_GROUPS)}")
     size = int(volume_size)
     if size < 2:
         raise ValueError(f"volume_size {size}: a lattice needs at least 2 nodes per axis")
@@ -107,7 +146,7 @@ def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False,
             raise ValueError(f"{zarr_in}: no summary/cloth_aabb_union, which {TASK_SPACE_VOLUME_GROUP} is normalised with")
         aabb = root["summary"]["cloth_aabb_union"][:].astype(np.float32)          # the dtype GarmentInputDataset normalises with
     comp = zarr_store.default_compressor()
-    written = {g: 0 for g in groups}
+    written = {g: 0 for g in groups + derived}
     if marching_cubes:
         written["marching_cube_mesh"] = 0
     t_all = time.perf_counter()
@@ -122,6 +161,10 @@ def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False,
             fields = winding.winding_field([sample_mesh(samples[k], g, aabb) for k in todo], (size,) * 3, backend=backend)
             for k, field in zip(todo, fields):
                 samples[k].require_group("volume").require_group(g).array(str(size), field, compressor=comp)
+                did[k].append(g)
+                written[g] += 1
+        if derived:
+            for k, g in build_derived_groups(samples, chunk, derived, size, overwrite, backend, comp):
                 did[k].append(g)
                 written[g] += 1
         if marching_cubes:
@@ -152,7 +195,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         return prepare_store(a.zarr_in, a.volume_size, a.groups, a.marching_cubes, a.on_surface_distance, a.batch_size, a.overwrite, a.backend,
-                             log=lambda row: print(json.dumps(row)))
+                             log=lambda row: print(json.dumps(row)), derived_groups=a.derived_groups)
     except ValueError as e:
         ap.error(str(e))
 
