@@ -39,6 +39,15 @@ global mutable state except immutable LUTs).  ``DEFAULT`` is read from the envir
                        bits (one documented exception: the scale of a row whose maximum lies a few ulps below a power of two, DESIGN.md "Device-side weight packs"); which
                        launch a layer takes (unet3d.conv_plan) does not depend on it.  OFF by default: inference builds its packs once, so only training
                        -- which rebuilds them after every optimiser step -- gains; `python -m garmentnets_amd.train_pipeline` turns it on
+    conv_grad_mode     arithmetic of the BACKWARD of the 3x3x3 'gcr' convolutions (autograd.conv3d_gcr / unet3d; which kernel a layer's two gradients take:
+                       unet3d.conv_grad_plan):
+                         fp32   (default) v_mfma_f32_32x32x2_f32 throughout (csrc/unet_grad.hip, the data gradient on csrc/unet.hip): today's launches
+                         f16x2  both operands of the weight gradient and the masked output gradient of the data gradient split into two fp16 planes
+                                after a power-of-two range scale found on the device, 3 products on the 16-bit matrix cores, fp32 accumulation
+                                (csrc/unet_grad_split.hip; the data gradient on csrc/unet_split.hip's direct kernels with the pack of the flipped /
+                                transposed weight).  The GroupNorm backward, the max-pool and the final 1x1x1 convolution stay fp32.  Measured error
+                                against fp64 within K_F16X2_BWD x the torch-fp32 error (tests/test_gpu_unet_grad_split.py).  The forward is untouched.
+                                `python -m garmentnets_amd.train_pipeline --split_backward` turns it on
 """
 import dataclasses
 import os
@@ -46,6 +55,7 @@ import os
 CONV_FP32, SPLIT_BF16X2, SPLIT_BF16X3, SPLIT_F16X2 = 0, 2, 3, 4          # 2..4 = GN_SPLIT_* of include/garmentnets_hip.h
 CONV_MODE_NAMES = {"fp32": CONV_FP32, "f16x2": SPLIT_F16X2, "bf16x3": SPLIT_BF16X3, "bf16x2": SPLIT_BF16X2}
 DECODE_MODES = ("f16x2", "fp32")
+CONV_GRAD_MODES = ("fp32", "f16x2")
 
 
 def _env_choice(name, default, choices):
@@ -72,12 +82,15 @@ class Arith:
     fused_lattice: bool = True
     ggm_fp32: bool = False
     device_packs: bool = False
+    conv_grad_mode: str = "fp32"
 
     def __post_init__(self):
         if self.conv_mode not in CONV_MODE_NAMES.values():
             raise ValueError(f"conv_mode={self.conv_mode!r}")
         if self.decode_mode not in DECODE_MODES:
             raise ValueError(f"decode_mode={self.decode_mode!r}")
+        if self.conv_grad_mode not in CONV_GRAD_MODES:
+            raise ValueError(f"conv_grad_mode={self.conv_grad_mode!r}: expected one of {list(CONV_GRAD_MODES)}")
         if self.conv_mode == SPLIT_BF16X2:
             import warnings
             warnings.warn("garmentnets_amd: conv_mode bf16x2 is a PREVIEW arithmetic -- it does not guarantee the 1e-4 WNF tolerance (0.9-1.2e-4 "
@@ -95,7 +108,8 @@ class Arith:
                    sparse_first_conv=_env_flag("GARMENTNETS_SPARSE_CONV"), affine_in_weights=_env_flag("GARMENTNETS_AFFINE_IN_WEIGHTS"),
                    winograd=_env_flag("GARMENTNETS_WINOGRAD"), winograd32=_env_flag("GARMENTNETS_WINOGRAD32"), polyphase_upconv=_env_flag("GARMENTNETS_POLYPHASE"),
                    fold_final_conv=_env_flag("GARMENTNETS_FOLD_FINAL_CONV"), fused_lattice=_env_flag("GARMENTNETS_FUSED_LATTICE"),
-                   ggm_fp32=_env_flag("GARMENTNETS_GGM_FP32", False), device_packs=_env_flag("GARMENTNETS_DEVICE_PACKS", False))
+                   ggm_fp32=_env_flag("GARMENTNETS_GGM_FP32", False), device_packs=_env_flag("GARMENTNETS_DEVICE_PACKS", False),
+                   conv_grad_mode=_env_choice("GARMENTNETS_CONV_GRAD_MODE", "fp32", CONV_GRAD_MODES))
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -106,7 +120,7 @@ class Arith:
         return self.conv_mode != CONV_FP32 or self.decode_mode != "fp32"
 
     def strict_fp32(self):
-        return self.replace(conv_mode=CONV_FP32, decode_mode="fp32")
+        return self.replace(conv_mode=CONV_FP32, decode_mode="fp32", conv_grad_mode="fp32")
 
     @property
     def conv_name(self):

@@ -7,7 +7,9 @@ is a kernel of csrc/grad.hip.  A reference-side module that binds these function
 
 The UNet is not a torch graph (channel-last, channel-padded volumes, GroupNorm folded into the conv's operand load, concat and upsampling never
 materialised), so it gets its own backward: ``conv3d_gcr`` / ``max_pool3d_2`` / ``unet3d`` run the existing forward kernels and differentiate them with
-csrc/unet_grad.hip (DESIGN.md "UNet gradients"); its final 1x1x1 convolution is a linear block of the next paragraph.
+csrc/unet_grad.hip (DESIGN.md "UNet gradients"); its final 1x1x1 convolution is a linear block of the next paragraph.  With
+``arith.Arith.conv_grad_mode = "f16x2"`` the two gradients of every 3x3x3 convolution run on the 16-bit matrix cores instead (csrc/unet_grad_split.hip,
+``unet3d.conv_grad_plan``; DESIGN.md "f16x2 backward of the UNet convolutions"); the default is the fp32 backward, launch for launch.
 
 The dense layers of this package (components.mlp.MLPStack, HipLinear) hold torch parameters but evaluate through ``gn_linear``, which torch's autograd
 cannot see: ``mlp`` / ``linear`` run the same forward kernels block by block, keep each block's input and ReLU output, and differentiate them with
@@ -33,6 +35,7 @@ import torch
 
 import torch.nn.functional as F
 
+from . import arith as AR
 from . import ops
 from .components import unet3d as U
 from .components.mlp import HipLinear, MLPStack, fold_batchnorm, pack_linear, pack_wb, param_cache
@@ -254,12 +257,16 @@ class _ConvGcr(torch.autograd.Function):
         y, st = conv.run(src0, src1, st0, st1, arith=arith)
         ctx.save_for_backward(src0, src1, y, s0, q0, s1, q1, weight, gamma, beta)
         ctx.conv = conv
+        ctx.arith = arith
         ctx.mark_non_differentiable(st[0], st[1])
         return y, st[0], st[1]
 
     @staticmethod
     def backward(ctx, grad_y, _gs, _gq):
         src0, src1, y, s0, q0, s1, q1, weight, gamma, beta = ctx.saved_tensors
+        plan = U.conv_grad_plan(ctx.arith or AR.DEFAULT, tuple(src0.shape[1:4]), src0.shape[-1], 0 if src1 is None else src1.shape[-1], y.shape[-1])
+        if plan.data != "fp32" or plan.weight != "fp32":
+            return _conv_gcr_backward_split(ctx, grad_y, plan)
         conv, gn = ctx.conv, ctx.conv.groupnorm
         need = ctx.needs_input_grad
         lay = conv._layout(src0, src1)
@@ -292,6 +299,57 @@ class _ConvGcr(torch.autograd.Function):
         return d0, d1, dw, dgamma if need[3] else None, dbeta if need[4] else None, None, None, None, None, None, None
 
 
+def _conv_gcr_backward_split(ctx, grad_y, plan):
+    """_ConvGcr.backward under arith.conv_grad_mode = "f16x2" (plan: unet3d.conv_grad_plan, at least one gradient on the split-operand kernels).  One
+    masking pass (gn_relu_mask_max) serves both gradients: the masked gradient g, its per-sample maximum and the power-of-two scales from it, found on
+    the device.  The weight gradient reads the forward's operand with the sample's activation scale (the affine of the f16x2 forward); the data gradient
+    is the forward's direct split kernel on the pack of the flipped / transposed weight.  The GroupNorm backward stays fp32."""
+    src0, src1, y, s0, q0, s1, q1, weight, gamma, beta = ctx.saved_tensors
+    conv, gn, arith = ctx.conv, ctx.conv.groupnorm, ctx.arith or AR.DEFAULT
+    need = ctx.needs_input_grad
+    lay = conv._layout(src0, src1)
+    S0, S1 = src0.shape[-1], 0 if src1 is None else src1.shape[-1]
+    real = None if lay is None else lay.real
+    st0 = (s0, q0, src0[0].numel() // S0)
+    st1 = None if src1 is None else (s1, q1, src1[0].numel() // S1)
+    gamma = gamma.detach().float().contiguous()
+    beta = beta.detach().float().contiguous()
+    dy = grad_y.contiguous()
+    need_data = any(need[i] for i in (0, 1, 3, 4))
+    g = gmax = scale = inv = None
+    if (need[2] and plan.weight == "f16x2") or (need_data and plan.data == "f16x2"):
+        g, gmax, scale, inv = ops.relu_mask_max(y, dy)
+    dw = None
+    if need[2]:
+        if plan.weight == "f16x2":
+            a, d, x_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True, real=real)
+            dw = ops.conv3d_bwd_weight_split(src0, src1, a, d, None, g, x_inv=x_inv, gmax=gmax)      # (g is masked already: no second read of y)
+        else:
+            a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real)
+            dw = ops.conv3d_bwd_weight(src0, src1, a, d, y, dy)
+        if lay is not None:                   # stored -> real channels (the pad rows / columns are exact zeros)
+            cols = torch.cat([torch.arange(r, device=dw.device) + o for r, o in zip(lay.real, (0, S0))])
+            dw = dw[:conv.conv.out_channels].index_select(1, cols)
+    if not need_data:
+        return None, None, dw, None, None, None, None, None, None, None, None
+    cin_p = -(-(S0 + S1) // 32) * 32
+    wsrc = weight if lay is None else conv._padded_weight(lay)
+    cache, gen = param_cache(conv, "_split_packs"), conv._gen(lay)
+    if plan.data == "f16x2":
+        dev = bool(arith.device_packs) and wsrc.is_cuda
+        pack = cache.get(gen, ("device", "bwd_data_split") if dev else "bwd_data_split", lambda: ops.pack_conv_weight_bwd_data_split(wsrc, dev))
+        dxn = ops.conv3d_bwd_data_split(g, scale, inv, pack, cin_p)
+    else:
+        wpt = cache.get(gen, "bwd_data", lambda: ops.pack_conv_weight_bwd_data(wsrc))
+        dxn = ops.conv3d_bwd_data(g if g is not None else ops.relu_mask(y, dy), wpt, cin_p)
+    t0 = ops.groupnorm_bwd_stats(dxn, 0, src0)
+    t1 = None if src1 is None else ops.groupnorm_bwd_stats(dxn, S0, src1, half=True)
+    p, q, r, dgamma, dbeta = ops.groupnorm_bwd_coef(t0, t1, st0, st1, gn.num_groups, gn.eps, gamma, real=real)
+    d0 = ops.groupnorm_bwd_apply(dxn, 0, src0, p, q, r, 0) if need[0] else None
+    d1 = ops.groupnorm_bwd_apply(dxn, S0, src1, p, q, r, S0, half=True) if src1 is not None and need[1] else None
+    return d0, d1, dw, dgamma if need[3] else None, dbeta if need[4] else None, None, None, None, None, None, None
+
+
 def _check_gcr(conv):
     if not isinstance(conv, U.SingleConv):
         raise TypeError(f"expected a components.unet3d.SingleConv, got {type(conv).__name__}")
@@ -321,7 +379,8 @@ def conv3d_gcr(single_conv, src0, src1=None, arith=None):
     """One 'gcr' ``SingleConv`` (GroupNorm -> Conv3d 3x3x3 -> ReLU) as a differentiable function of src0, src1 and the module's conv.weight,
     groupnorm.weight, groupnorm.bias.  src0 [B][D][H][W][C0] and the optional half-resolution src1 [B][D/2][H/2][W/2][C1] are channel-last STORED
     volumes (channel-padded when the module's in_real says so); the result is the stored output [B][D][H][W][stored Cout].  Forward: SingleConv.run
-    (the kernels ``arith`` selects, dense launch).  Backward: csrc/unet_grad.hip -- an fp32 backward whatever the forward arithmetic."""
+    (the kernels ``arith`` selects, dense launch).  Backward: csrc/unet_grad.hip -- an fp32 backward whatever the forward arithmetic, unless
+    ``arith.conv_grad_mode`` is "f16x2": then the layer's two convolution gradients take the kernels unet3d.conv_grad_plan names (csrc/unet_grad_split.hip)."""
     _check_gcr(single_conv)
     return _conv(single_conv, _stored(src0, "src0"), None if src1 is None else _stored(src1, "src1"), None, None, arith)[0]
 
@@ -367,7 +426,8 @@ def unet3d(model, x, arith=None):
     """``Abstract3DUNet.forward``'s contract -- x (B, C, D, H, W) -> (B, C', D, H, W), a view over channel-last storage -- differentiable in x and in
     every parameter of the model: ``conv3d_gcr`` per layer, ``max_pool3d_2`` between the encoder levels, the final 1x1x1 convolution as a row GEMM.
     Any f_maps / num_levels the forward runs; on channel-padded widths the pad gradients are exact zeros and reach no parameter.  arith: the
-    arithmetic of the FORWARD kernels (None: model.arith, else arith.DEFAULT); the backward is fp32 throughout.  Layer orders other than 'gcr' raise
+    arithmetic of the FORWARD kernels (None: model.arith, else arith.DEFAULT); the backward is fp32 throughout unless arith.conv_grad_mode is "f16x2"
+    (the 3x3x3 convolutions' gradients on the 16-bit matrix cores, unet3d.conv_grad_plan; GroupNorm, max-pool and the final convolution stay fp32).  Layer orders other than 'gcr' raise
     NotImplementedError.  Under torch.no_grad(), or when nothing requires a gradient, this is model.forward's launches and nothing is saved."""
     if not isinstance(model, U.Abstract3DUNet):
         raise TypeError(f"unet3d: expected a components.unet3d.Abstract3DUNet, got {type(model).__name__}")

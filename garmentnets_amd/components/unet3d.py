@@ -109,6 +109,38 @@ def conv_plan(arith, dims, c0, c1, cout, reach=0, rest_known=False, small=None, 
     return ConvPlan(mode, bool(aiw), bool(wino), bool(poly), (int(small[0]) if small is not None else 8 if wino else 5) if occ else 0)
 
 
+class ConvGradPlan(NamedTuple):
+    """which kernel each gradient of one 3x3x3 'gcr' convolution takes (conv_grad_plan): "fp32" or "f16x2" """
+    data: str        # the data gradient: "fp32" gn_conv3d_gcr (csrc/unet.hip) / "f16x2" gn_conv3d_gcr_split, direct form, both on the flipped / transposed pack
+    weight: str      # the weight gradient: "fp32" gn_conv3d_bwd_weight (csrc/unet_grad.hip) / "f16x2" gn_conv3d_bwd_weight_split (csrc/unet_grad_split.hip)
+
+
+# The rules under which a layer's gradient stays on the fp32 kernel although arith.conv_grad_mode asks for "f16x2" -- each written here, once, by name.
+def grad_data_pack_unsupported(cout_stored):
+    """the data gradient reads the layer's OUTPUT width as its input, 16 channels at a time (the split pack's K slices): a stored width that is no
+    multiple of 16 has no f16x2 pack (no stored activation has one -- stored_channels rounds to 32 -- but a direct caller's may)"""
+    return cout_stored % 16 != 0
+
+
+def grad_weight_partial_quad(c0, c1):
+    """the weight gradient stages its operand four channels at a time and a quad must not straddle the two sources: both widths multiples of 4 (the
+    fp32 kernel's own rule; such a layer has no weight gradient at all and the fp32 entry refuses it by name)"""
+    return c0 % 4 != 0 or c1 % 4 != 0
+
+
+@functools.lru_cache(maxsize=None)
+def conv_grad_plan(arith, dims, c0, c1, cout_stored):
+    """The backward of one 'gcr' layer as a pure function of the arithmetic, the SAMPLE's (D, H, W) and the stored widths (c1 = 0: one source): which
+    kernel the data gradient and which the weight gradient takes.  No tensor, no library entry, never the batch size.  arith.conv_grad_mode "fp32":
+    always the fp32 kernels.  "f16x2": the split-operand kernels unless one of the named rules above holds.  No shape rule: at both measured shapes --
+    every layer of the reference's training UNet (f_maps 32, 4 levels, 32^3, down to 4^3 volumes of one tile) and 128 -> 128 at 128^3 -- the f16x2
+    kernels are the faster ones (profiles/unet_grad_split_time.json, DESIGN.md "f16x2 backward of the UNet convolutions"), so dims decides nothing yet;
+    it is an argument so that a measured shape rule has its place."""
+    if arith.conv_grad_mode != "f16x2":
+        return ConvGradPlan("fp32", "fp32")
+    return ConvGradPlan("fp32" if grad_data_pack_unsupported(cout_stored) else "f16x2", "fp32" if grad_weight_partial_quad(c0, c1) else "f16x2")
+
+
 _ACT = {"r": ("ReLU", lambda: nn.ReLU(inplace=True), ops.ACT_RELU), "l": ("LeakyReLU", lambda: nn.LeakyReLU(negative_slope=0.1, inplace=True), ops.ACT_LEAKY),
         "e": ("ELU", lambda: nn.ELU(inplace=True), ops.ACT_ELU)}
 

@@ -1616,11 +1616,7 @@ def pack_conv_weight_bwd_data(w):
     cout, cin = w.shape[:2]
     if cout % 16 != 0:
         raise ValueError(f"pack_conv_weight_bwd_data: Cout={cout} must be a multiple of 16 (it is the input width of the transposed convolution)")
-    cin_p = -(-cin // 32) * 32
-    wt = w.detach().float().flip(2, 3, 4).transpose(0, 1)
-    if cin_p != cin:
-        wt = torch.cat((wt, wt.new_zeros((cin_p - cin,) + tuple(wt.shape[1:]))), 0)
-    return pack_conv_weight(wt.contiguous())
+    return pack_conv_weight(bwd_data_weight(w))
 
 
 def conv3d_bwd_weight(src0, src1, a, d, y, dy):
@@ -1670,6 +1666,98 @@ def conv3d_bwd_data(g, wp_t, cin_p):
     B, cout = g.shape[0], g.shape[-1]
     one = torch.ones((B, cout), dtype=torch.float32, device=g.device)
     return conv3d_gcr(g, None, one, torch.zeros_like(one), wp_t, cin_p, relu=False)
+
+
+# ---- the f16x2 form (csrc/unet_grad_split.hip; DESIGN.md "f16x2 backward of the UNet convolutions")
+def bwd_data_weight(w):
+    """nn.Conv3d weight (Cout, Cin, 3, 3, 3) -> the weight of the layer's data gradient as a forward convolution, (round_up(Cin, 32), Cout, 3, 3, 3)
+    contiguous: flipped over the taps, transposed over (ci, co), zero rows beyond Cin -- what pack_conv_weight_bwd_data packs.  Device-side copies only."""
+    cout, cin = w.shape[:2]
+    if cout % 16 != 0:
+        raise ValueError(f"bwd_data_weight: Cout={cout} must be a multiple of 16 (it is the input width of the transposed convolution)")
+    cin_p = -(-cin // 32) * 32
+    wt = w.detach().float().flip(2, 3, 4).transpose(0, 1)
+    if cin_p != cin:
+        wt = torch.cat((wt, wt.new_zeros((cin_p - cin,) + tuple(wt.shape[1:]))), 0)
+    return wt.contiguous()
+
+
+def pack_conv_weight_bwd_data_split(w, device_packs=False):
+    """the GN_SPLIT_F16X2 pack of the layer's DATA gradient: pack_conv_weight_split of bwd_data_weight(w) (on the weight's device), or, device_packs and a
+    weight on the GPU, pack_conv_weight_split_device of it (no host round trip)"""
+    wt = bwd_data_weight(w)
+    if device_packs and wt.is_cuda:
+        return pack_conv_weight_split_device(wt, SPLIT_F16X2)
+    return pack_conv_weight_split(wt, SPLIT_F16X2).to(w.device)
+
+
+def relu_mask_max(y, dy, with_scale=True):
+    """gn_relu_mask_max over a channel-last volume [B][...][C]: g = y > 0 ? dy : 0 (y None: g = dy) -> (g, gmax [B], scale [B][C], inv [B]): the largest
+    finite |g| per sample and the power-of-two range scale from it, all on the device (scale / inv None without with_scale)"""
+    _chk(dy, torch.float32, "dy")
+    if dy.dim() < 2:
+        raise ValueError(f"relu_mask_max: dy {tuple(dy.shape)} must be [B][...][C]")
+    if y is not None:
+        _chk(y, torch.float32, "y")
+        if y.shape != dy.shape:
+            raise ValueError(f"relu_mask_max: y {tuple(y.shape)} and dy {tuple(dy.shape)} must match")
+    B, C = dy.shape[0], dy.shape[-1]
+    n = dy.numel() // B if B else 0
+    if n % 4 != 0:
+        raise ValueError(f"relu_mask_max: {n} values per sample are not a multiple of 4")
+    g = torch.empty_like(dy)
+    gmax = torch.empty((B,), dtype=torch.float32, device=dy.device)
+    scale = torch.empty((B, C), dtype=torch.float32, device=dy.device) if with_scale else None
+    inv = torch.empty((B,), dtype=torch.float32, device=dy.device) if with_scale else None
+    nbytes = _lib.load().gn_relu_mask_max_workspace_bytes(B)
+    ws = _ws(nbytes, dy.device)
+    _lib.call("gn_relu_mask_max", _p(y), _p(dy), B, n, C, _p(g), _p(gmax), _p(scale), _p(inv), _p(ws), nbytes, _stream())
+    return g, gmax, scale, inv
+
+
+def conv3d_bwd_data_split(g, scale, inv, pack, cin_p):
+    """the data gradient at a 'gcr' layer's conv operand on the 16-bit matrix cores: gn_conv3d_gcr_split (direct form, no ReLU, no statistics) over the
+    masked output gradient g with the pack of pack_conv_weight_bwd_data_split; scale [B][Cout] / inv [B]: relu_mask_max's -> [B][D][H][W][cin_p]"""
+    _vol5(g, "g")
+    return conv3d_gcr_split(g, None, scale, torch.zeros_like(scale), pack, cin_p, relu=False, act_inv=inv)
+
+
+def conv3d_bwd_weight_split(src0, src1, a, d, y, dy, x_inv=None, gmax=None):
+    """-> dw (Cout, C0 + C1, 3, 3, 3) over the stored widths as conv3d_bwd_weight, on fp16 planes (gn_conv3d_bwd_weight_split).  a, d [B][C0 + C1]: the
+    forward's GroupNorm affine; with x_inv [B] they carry each sample's power-of-two activation scale and x_inv is its inverse
+    (groupnorm_affine(with_act_scale=True)), without it the operand x * a + d must lie inside fp16's range as it is.  gmax [B]: relu_mask_max's
+    per-sample maximum of the masked gradient; None: one masking pass finds it here."""
+    _vol5(src0, "src0")
+    B, D, H, W, C0 = src0.shape
+    C1 = 0
+    if src1 is not None:
+        _vol5(src1, "src1")
+        C1 = src1.shape[-1]
+        if tuple(src1.shape[:4]) != (B, D // 2, H // 2, W // 2) or D % 2 or H % 2 or W % 2:
+            raise ValueError(f"conv3d_bwd_weight_split: src1 {tuple(src1.shape)} is not the half-resolution companion of src0 {tuple(src0.shape)}")
+    _vol5(dy, "dy")
+    cout = dy.shape[-1]
+    if tuple(dy.shape[:4]) != (B, D, H, W):
+        raise ValueError(f"conv3d_bwd_weight_split: dy {tuple(dy.shape)} does not match src0 {tuple(src0.shape)}")
+    if y is not None:
+        _vol5(y, "y", dy)
+    for t, name in ((a, "a"), (d, "d")):
+        _chk(t, torch.float32, name)
+        if tuple(t.shape) != (B, C0 + C1):
+            raise ValueError(f"conv3d_bwd_weight_split: {name} must be [B][C0 + C1] = {(B, C0 + C1)}, got {tuple(t.shape)}")
+    for t, name in ((x_inv, "x_inv"), (gmax, "gmax")):
+        if t is not None:
+            _chk(t, torch.float32, name)
+            if tuple(t.shape) != (B,):
+                raise ValueError(f"conv3d_bwd_weight_split: {name} must be [B] = {(B,)}, got {tuple(t.shape)}")
+    if gmax is None:
+        gmax = relu_mask_max(y, dy, with_scale=False)[1]
+    dw = torch.empty((cout, C0 + C1, 3, 3, 3), dtype=torch.float32, device=src0.device)
+    nbytes = _lib.load().gn_conv3d_bwd_weight_split_workspace_bytes(B, D, H, W, C0 + C1, cout)
+    ws = _ws(nbytes, src0.device)
+    _lib.call("gn_conv3d_bwd_weight_split", _p(src0), C0, _p(src1), C1, _p(a), _p(d), _p(x_inv), _p(y), _p(dy), _p(gmax), B, D, H, W, cout, _p(ws), nbytes,
+              _p(dw), _stream())
+    return dw
 
 
 def _gn_bwd_dims(dxn, goff, x, half, who):

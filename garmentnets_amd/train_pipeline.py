@@ -12,7 +12,9 @@
   python -m garmentnets_amd.train_pipeline
                                         epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint.
                                         It trains with arith.device_packs: the UNet's static weight packs, stale after every optimiser step, are rebuilt
-                                        on the device (csrc/weight_pack.hip; same bits) instead of through the host; --host_packs keeps the host builders
+                                        on the device (csrc/weight_pack.hip; same bits) instead of through the host; --host_packs keeps the host builders.
+                                        --split_backward: the UNet convolutions' gradients on the 16-bit matrix cores (arith.conv_grad_mode = "f16x2",
+                                        csrc/unet_grad_split.hip); without it the backward is fp32, today's launches
 
 The first stage is frozen, as the reference's pointnet2_forward freezes it on every call: pointnet2_nocs is put in eval mode (and left there, whatever
 model.train() said before) and runs its inference forward under no_grad.  None of its parameters or buffers changes and none gets a .grad; they stay in
@@ -169,6 +171,9 @@ def build_parser():
     ap.add_argument("--host_packs", action="store_true",
                     help="build the UNet's static weight packs on the host after every step (the inference path's builders) instead of on the device "
                          "(arith.device_packs: same bits, no stream synchronisation)")
+    ap.add_argument("--split_backward", action="store_true",
+                    help="run the gradients of the UNet's 3x3x3 convolutions on the 16-bit matrix cores (arith.conv_grad_mode = 'f16x2': fp16 operand "
+                         "planes, fp32 accumulation); default: the fp32 backward")
     validate.add_resident_arguments(ap)
     return ap
 
@@ -208,6 +213,8 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     model = load_model(a, device).requires_grad_(True).train()
     model.arith = model.arith.replace(device_packs=not a.host_packs)        # (train_step reads the model's arithmetic)
+    if a.split_backward:
+        model.arith = model.arith.replace(conv_grad_mode="f16x2")
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
     optimizer = model.configure_optimizers()

@@ -744,6 +744,32 @@ int gn_conv3d_bwd_weight(const float *src0, int C0, const float *src1, int C1, c
 /* g = y > 0 ? dy : 0 over n floats (n % 4 == 0); g may be dy.  The data gradient of the layer is gn_conv3d_gcr(g) with the flipped / transposed pack. */
 int gn_relu_mask(const float *y, const float *dy, int64_t n, float *g, void *stream);
 
+/* ---- f16x2 backward of the UNet convolutions (csrc/unet_grad_split.hip; DESIGN.md "f16x2 backward of the UNet convolutions").  Opt-in
+ * (arith.Arith.conv_grad_mode = "f16x2"); the same mathematical objects as the fp32 entries above on the 16-bit matrix cores: operands split into two
+ * fp16 planes after a power-of-two scale, the products hi*hi, hi*lo, lo*hi on v_mfma_f32_32x32x16_f16, fp32 accumulation.  No float atomics. ---- */
+
+/* gn_relu_mask over B samples of n floats each (n % 4 == 0; y NULL: g = dy), and on the way gmax[b] = the largest FINITE |g| of sample b (0 for an
+ * all-zero sample; an Inf / NaN never decides a scale).  scale / inv (both or neither): scale[b][0..C) = 2^k[b], inv[b] = 2^-k[b] with
+ * gmax[b] * 2^k[b] in [2^14, 2^15) (k = 0 for an all-zero sample, held to [-126, 126]) -- the a (with d = 0) and act_inv_scale that gn_conv3d_gcr_split
+ * takes for the DATA gradient: the direct GN_SPLIT_F16X2 form on the pack of the flipped / transposed weight, no ReLU.  Two launches (a partial
+ * maximum per workgroup in the workspace, then one workgroup per sample), no atomics; nothing is read back. */
+size_t gn_relu_mask_max_workspace_bytes(int B);
+int gn_relu_mask_max(const float *y, const float *dy, int B, int64_t n, int C, float *g, float *gmax, float *scale, float *inv, void *ws,
+                     size_t ws_bytes, void *stream);
+
+/* gn_conv3d_bwd_weight on fp16 planes.  Same operands, layout, chains and fixed summation order (the chain count is gn_conv3d_bwd_weight's; the
+ * workspace holds a header of ceil((16 + 4 B) / 256) * 256 bytes in front of the partials and must be 16-byte aligned).  Scales, one power of two per
+ * operand per LAUNCH (a chain may span samples), found on the device and undone exactly when the chains are folded:
+ *   a, d, x_inv: the forward's operand as gn_conv3d_gcr_split takes it -- a and d multiplied by the sample's power of two, x_inv[b] its inverse
+ *                (gn_groupnorm_affine's act_inv_scale); the launch scale is 1 / max_b x_inv[b].  x_inv NULL: a, d as gn_conv3d_bwd_weight takes them, the
+ *                operand's range is the caller's (|x a + d| < 65504)
+ *   gmax [B]:    the largest finite |g| per sample (gn_relu_mask_max); g is scaled so that the batch maximum lies in [2^14, 2^15)
+ * All-zero dy: exact zeros.  An Inf / NaN in g: every dw entry of that output channel is non-finite. */
+size_t gn_conv3d_bwd_weight_split_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout);
+int gn_conv3d_bwd_weight_split(const float *src0, int C0, const float *src1, int C1, const float *a, const float *d, const float *x_inv, const float *y,
+                               const float *dy, const float *gmax, int B, int D, int H, int W, int Cout, void *ws, size_t ws_bytes, float *dw,
+                               void *stream);
+
 /* nn.GroupNorm's backward over the virtual concat, per source.  dxn: the gradient at the conv's operand, [B][fine voxels][ldg], this source's channels at
  * column goff.  x: the source as stored, [B][D][H][W][C] at its own resolution; half != 0: x is the half-resolution source (fine = 2D x 2H x 2W) and the 8
  * fine gradients of a coarse voxel are added first in ascending (dz, dy, dx) order.
