@@ -147,6 +147,8 @@ PROTOTYPES = {
     "gn_resident_volume": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "gn_resident_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "gn_resident_mc_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "gn_render_points_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gn_color_idx_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -207,6 +209,23 @@ RESIDENT_ARRAYS = ("pc_sim", "pc_nocs", "pc_rgb", "sim_verts", "nocs_verts", "ta
 class ResidentStore(ctypes.Structure):
     """GnResidentStore (host struct of the gn_resident_* calls: device pointers of the resident arrays, NULL for the ones a store does not hold)"""
     _fields_ = [(k, _vp) for k in RESIDENT_ARRAYS] + [("n", _i32), ("D", _i32), ("H", _i32), ("W", _i32)]
+
+
+RENDER_MAX_SIZE = 4096                          # GN_RENDER_MAX_SIZE
+RENDER_MAX_OVERLAYS = 3                         # GN_RENDER_MAX_OVERLAYS
+RENDER_SIDES = {"front": 0, "top": 1, "left": 2}   # GN_RENDER_*
+COLOR_TABLE, COLOR_VIRIDIS = 0, 1               # GN_COLOR_*
+
+
+class OverlayPoint(ctypes.Structure):
+    """GnOverlayPoint"""
+    _fields_ = [("xyz", _f32 * 3), ("rgba", _f32 * 4), ("kernel_size", _i32)]
+
+
+class ColorImage(ctypes.Structure):
+    """GnColorImage (table entry of gn_color_idx_batch: the same bytes on the host and on the device)"""
+    _fields_ = [("offset", _i64), ("count", _i64), ("mode", _i32), ("side", _i32), ("vmin", _f32), ("vmax", _f32), ("default_color", _f32 * 4),
+                ("num_overlays", _i32), ("pad", _i32), ("overlay", OverlayPoint * RENDER_MAX_OVERLAYS)]
 
 
 _lib = None

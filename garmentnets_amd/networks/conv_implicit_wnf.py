@@ -4,7 +4,7 @@ Keeps the reference's class names, constructor kwargs, sub-module names (= check
 ``volume_agg.local_nn``, ``unet_3d.abstract_3d_unet``, ``volume_decoder.mlp`` ...), stage methods
 (``pointnet2_forward``, ``unet3d_forward``, ``volume_decoder_forward``, ``surface_decoder_forward``,
 ``mc_surface_decoder_forward``, ``forward``) and result-dict keys, so that predict.py is a drop-in.  ``validation_metrics`` gives the
-losses of the reference's infer (:405-452); ``training_step`` / ``training_metrics`` / ``configure_optimizers`` are the second stage's training step (garmentnets_amd/train_pipeline.py, imported on use: the loss gradients of gn_value_losses_bwd and optim.FusedAdam, as the first stage's train.py); visualisation is out of scope.  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
+losses of the reference's infer (:405-452); ``training_step`` / ``training_metrics`` / ``configure_optimizers`` are the second stage's training step (garmentnets_amd/train_pipeline.py, imported on use: the loss gradients of gn_value_losses_bwd and optim.FusedAdam, as the first stage's train.py); ``vis_batch`` renders the reference's monitor images on the device (garmentnets_amd.visualize).  Feature volumes are stored channel-last; the (B,C,D,H,W) tensors handed out are views.
 """
 import functools
 import os
@@ -442,7 +442,8 @@ class ConvImplicitWNFPipeline(nn.Module):
                             mc_surface_decoder_params=None if mc_surface_decoder_params is None else dict(mc_surface_decoder_params),
                             mc_surface_loss_weight=mc_surface_loss_weight, volume_task_space=volume_task_space,
                             learning_rate=learning_rate, loss_type=loss_type, volume_loss_weight=volume_loss_weight,
-                            surface_loss_weight=surface_loss_weight, volume_classification=volume_classification)
+                            surface_loss_weight=surface_loss_weight, volume_classification=volume_classification, vis_per_items=vis_per_items,
+                            max_vis_per_epoch_train=max_vis_per_epoch_train, max_vis_per_epoch_val=max_vis_per_epoch_val)
         self.pointnet2_nocs = PointNet2NOCS(**pointnet2_params)
         self.volume_agg = VolumeFeatureAggregator(**volume_agg_params)
         self.unet_3d = UNet3D(**unet3d_params)
@@ -459,6 +460,9 @@ class ConvImplicitWNFPipeline(nn.Module):
         self.surface_loss_weight = surface_loss_weight
         self.mc_surface_loss_weight = mc_surface_loss_weight
         self.volume_classification = volume_classification
+        self.vis_per_items = vis_per_items
+        self.max_vis_per_epoch_train = max_vis_per_epoch_train
+        self.max_vis_per_epoch_val = max_vis_per_epoch_val
         self.arith = AR.DEFAULT      # this model's arithmetic (an immutable arith.Arith); every stage method also takes arith= per call
 
     # -- checkpoint ------------------------------------------------------------------------------------------
@@ -563,14 +567,15 @@ class ConvImplicitWNFPipeline(nn.Module):
     # -- validation ------------------------------------------------------------------------------------------
     LOSS_TYPES = ("l2", "smooth_l1")
 
-    def validation_metrics(self, data, arith=None):
+    def validation_metrics(self, data, arith=None, result=None):
         """the loss dict of the reference's infer (conv_implicit_wnf.py:405-452) as python floats: volume_loss, surface_loss[, mc_surface_loss
         when mc_surface_loss_weight > 0] (each its weight times the mean criterion) and loss, their sum.  data: the network input plus the
         targets io.dataset draws (volume_query_points / gt_volume_value, surf_query_points / gt_sim_points[, mc_surf_query_points /
         is_query_point_on_surf]).  Criterion: loss_type (l2 = MSE, smooth_l1 with beta 1); the volume takes BCE-with-logits when
-        volume_classification, the mc surface always.  forward() runs the decoders, ONE gn_value_losses launch the three losses."""
+        volume_classification, the mc surface always.  forward() runs the decoders, ONE gn_value_losses launch the three losses.  result: this
+        model's forward(data) when the caller already has it."""
         self._check_loss_type()
-        return self.losses_from(self.forward(data, arith), data)
+        return self.losses_from(self.forward(data, arith) if result is None else result, data)
 
     def _check_loss_type(self):
         if self.loss_type not in self.LOSS_TYPES:
@@ -603,6 +608,31 @@ class ConvImplicitWNFPipeline(nn.Module):
         segs, names, weights = self.loss_segments(result, data)
         sums = ops.value_losses(segs)[:, 0].cpu().tolist()
         return self.metrics_from_sums(sums, names, weights, [seg[1].numel() for seg in segs])
+
+    # -- monitors (garmentnets_amd/visualize.py) ---------------------------------------------------------------
+    def vis_batch(self, batch, batch_idx, result, is_train=False, img_size=256, backend="device"):
+        """the reference's vis_batch (conv_implicit_wnf.py:345-403) -> {label: (2 S, 2 S, 4) fp32 image}, labels train_<vis_idx> / val_<vis_idx>: per
+        selected garment (get_vis_idxs over vis_per_items / max_vis_per_epoch_* / batch_size) the NOCS pair of the first stage with the
+        ground-truth and the predicted grip point, above the pair of WNF slices (0.5 < y < 0.6 of the volume queries: target and prediction, the
+        sigmoid of the logits when volume_classification).  result: this model's forward of the batch; all images of the batch in one launch
+        pair.  No garment selected: nothing is launched, nothing synchronises."""
+        from .. import visualize as V
+        picked = V.monitor_selection(self, batch_idx, batch.nocs_grip_point.shape[0], is_train)
+        if not picked:
+            return {}
+        with torch.no_grad():
+            pred_nocs = result["pointnet2_result"]["nocs_data"].pos
+            pred_value = result["volume_decoder_result"]["pred_volume_value"].detach()
+            if self.volume_classification:
+                pred_value = torch.sigmoid(pred_value)
+            rows = V.garment_rows(batch)
+            specs = []
+            for i, _ in picked:
+                pred = rows(pred_nocs, i)
+                specs += V.nocs_pair_specs(rows(batch.y, i), pred, batch.nocs_grip_point[i], V.grip_row(rows(batch.pos, i), pred))
+                specs += V.wnf_pair_specs(batch.volume_query_points[i], batch.gt_volume_value[i], pred_value[i])
+            images = V.render_batch(specs, img_size, backend)
+        return dict(zip([label for _, label in picked], V.compose(images, 4)))
 
     # -- training (garmentnets_amd/train_pipeline.py; imported on use: the inference modules do not depend on the training code) ----------------------
     def training_step(self, batch, batch_idx=None):

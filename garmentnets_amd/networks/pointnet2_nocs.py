@@ -4,8 +4,8 @@ Same constructor kwargs, sub-module names (``sa1_module`` ... ``global_lin2``: t
 result keys and ``logits_to_nocs`` / ``get_virtual_grid`` helpers, and ``validation_metrics`` (the metric dict of the
 reference's ``infer``, :257-440, without its logging).  ``forward`` is the fused inference path.  ``training_step`` /
 ``training_metrics`` / ``configure_optimizers`` are thin methods over garmentnets_amd.train (the differentiable forward, the HIP
-loss gradients, optim.FusedAdam), imported lazily: the inference path imports none of the differentiable bindings.  Visualisation is out of
-scope.  All arithmetic runs in HIP kernels (garmentnets_amd.ops), with one exception in training mode: the reference's four
+loss gradients, optim.FusedAdam), imported lazily: the inference path imports none of the differentiable bindings.  ``vis_batch`` renders the
+reference's monitor images on the device (garmentnets_amd.visualize).  All arithmetic runs in HIP kernels (garmentnets_amd.ops), with one exception in training mode: the reference's four
 dropouts (present iff ``dropout=True``) are torch.nn.functional.dropout (train.py's docstring).
 """
 import torch
@@ -25,7 +25,8 @@ class PointNet2NOCS(nn.Module):
         self.hparams = dict(feature_dim=feature_dim, batch_norm=batch_norm, dropout=dropout, sa1_ratio=sa1_ratio, sa1_r=sa1_r,
                             sa2_ratio=sa2_ratio, sa2_r=sa2_r, fp3_k=fp3_k, fp2_k=fp2_k, fp1_k=fp1_k, symmetry_axis=symmetry_axis,
                             nocs_bins=nocs_bins, learning_rate=learning_rate, nocs_loss_weight=nocs_loss_weight,
-                            grip_point_loss_weight=grip_point_loss_weight)
+                            grip_point_loss_weight=grip_point_loss_weight, vis_per_items=vis_per_items,
+                            max_vis_per_epoch_train=max_vis_per_epoch_train, max_vis_per_epoch_val=max_vis_per_epoch_val)
         self.sa1_module = SAModule(sa1_ratio, sa1_r, MLP([3 + 3, 64, 64, 128], batch_norm=batch_norm))
         self.sa2_module = SAModule(sa2_ratio, sa2_r, MLP([128 + 3, 128, 128, 256], batch_norm=batch_norm))
         self.sa3_module = GlobalSAModule(nn=MLP([256 + 3, 256, 512, 1024], batch_norm=batch_norm))
@@ -44,6 +45,9 @@ class PointNet2NOCS(nn.Module):
         self.learning_rate = learning_rate
         self.nocs_loss_weight = nocs_loss_weight
         self.grip_point_loss_weight = grip_point_loss_weight
+        self.vis_per_items = vis_per_items
+        self.max_vis_per_epoch_train = max_vis_per_epoch_train
+        self.max_vis_per_epoch_val = max_vis_per_epoch_val
 
     @classmethod
     def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", **overrides):
@@ -126,6 +130,29 @@ class PointNet2NOCS(nn.Module):
     def get_virtual_grid(self):
         return VirtualGrid(lower_corner=(0, 0, 0), upper_corner=(1, 1, 1), grid_shape=(self.nocs_bins,) * 3, batch_size=1,
                            device=self.device, int_dtype=torch.int64, float_dtype=torch.float32)
+
+    # -- monitors (garmentnets_amd/visualize.py) -------------------------------------------------------------
+    def vis_batch(self, batch, batch_idx, result, is_train=False, img_size=256, backend="device"):
+        """the reference's vis_batch (pointnet2_nocs.py:203-255) -> {label: (2 S or S, 2 S, 4) fp32 image}, labels train_<vis_idx> / val_<vis_idx>: per
+        selected garment (get_vis_idxs over vis_per_items / max_vis_per_epoch_* / batch_size) the NOCS pair with the ground-truth, the predicted
+        (the prediction at the point nearest the gripper) and the global head's grip point over it, above the confidence pair of the x bins when
+        the head has bins.  result: this model's forward of the batch; all images of the batch in one launch pair.  No garment selected: nothing
+        is launched, nothing synchronises."""
+        from .. import visualize as V
+        picked = V.monitor_selection(self, batch_idx, batch.nocs_grip_point.shape[0], is_train)
+        if not picked:
+            return {}
+        with torch.no_grad():
+            logits, glogits = result["per_point_logits"].detach(), result["global_logits"].detach()
+            if self.nocs_bins is None:
+                pred, grip_nn, conf = logits, glogits, None
+            else:
+                _, conf, pred = ops.nocs_head(logits, self.nocs_bins)
+                grip_nn = self.logits_to_nocs(glogits)
+            rows = V.garment_rows(batch)
+            specs = [s for i, _ in picked for s in V.nocs_monitor_specs(rows, i, batch, pred, grip_nn, conf)]
+            images = V.render_batch(specs, img_size, backend)
+        return dict(zip([label for _, label in picked], V.compose(images, len(specs) // len(picked))))
 
     # -- validation ----------------------------------------------------------------------------------------
     def validation_metrics(self, batch, result=None):

@@ -1996,3 +1996,93 @@ def resident_mc_surface(store, slots, face_u, uv, query, on_surf):
     B, M = face_u.shape
     _lib.call("gn_resident_mc_surface", _res(store), _p(slots), B, M, _p(_chk(face_u, torch.float64, "face_u")), _p(_chk(uv, torch.float64, "uv")),
               _p(query), _p(on_surf), _stream())
+
+
+# ------------------------------------------------------------------------------------------------ training monitors
+def _render_dims(who, n_images, img_size):
+    """the limits of the two render entries that size an output: refused here, before it is allocated, in the entry's words"""
+    S = int(img_size)
+    if not 1 <= S <= _lib.RENDER_MAX_SIZE:
+        raise ValueError(f"{who}: image size S={S} outside [1, {_lib.RENDER_MAX_SIZE}]")
+    if n_images > 65535:
+        raise ValueError(f"{who}: I={n_images} images outside [0, 65535]")
+    return S
+
+
+def _side(s):
+    return _lib.RENDER_SIDES.get(s, s) if isinstance(s, str) else int(s)
+
+
+def render_points_batch(points, seg, sides, kernel_sizes, img_size):
+    """the reference's render_points_idx behind its camera, I images in ONE launch (gn_render_points_batch) -> (I, S, S) int32 holding the uint32 index
+    images (0xFFFFFFFF, i.e. -1, where no point covers the pixel).  points: (N, 3) fp32 on the device; image i draws points seg[i] .. seg[i+1] (seg: I + 1
+    host integers, non-decreasing) from sides[i] ('front' / 'top' / 'left' or 0 / 1 / 2) with a kernel_sizes[i]-wide footprint.  A pixel holds the index,
+    counted from seg[i], of the covering point nearest to the camera (fp64 depth; equal depths: the lowest index)."""
+    points = _chk(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points: expected an (N, 3) tensor, got {tuple(points.shape)}")
+    seg = np.ascontiguousarray(np.asarray(seg, dtype=np.int64).reshape(-1))
+    n = seg.shape[0] - 1
+    side = np.ascontiguousarray(np.array([_side(s) for s in sides], dtype=np.int32).reshape(-1))
+    ks = np.ascontiguousarray(np.asarray(kernel_sizes, dtype=np.int32).reshape(-1))
+    if n < 0 or side.shape[0] != n or ks.shape[0] != n:
+        raise ValueError(f"render_points_batch: seg holds I + 1 entries for I sides and kernel sizes (got {seg.shape[0]}, {side.shape[0]}, {ks.shape[0]})")
+    S = _render_dims("gn_render_points_batch", n, img_size)
+    if n and (seg[0] < 0 or np.any(np.diff(seg) < 0) or seg[-1] > points.shape[0]):
+        raise ValueError("render_points_batch: seg must be non-decreasing within [0, N]")
+    out = torch.empty((n, S, S), dtype=_i32, device=points.device)
+    if n == 0:
+        return out
+    tab = torch.from_numpy(np.stack([seg[:-1], seg[1:], side.astype(np.int64), ks.astype(np.int64)], axis=1)).to(points.device)
+    _lib.call("gn_render_points_batch", _p(points), seg.ctypes.data_as(ctypes.c_void_p), side.ctypes.data_as(ctypes.c_void_p),
+              ks.ctypes.data_as(ctypes.c_void_p), _p(tab), n, S, _p(out), _stream())
+    return out
+
+
+def color_idx_batch(idx_img, images, colors=None, values=None):
+    """the reference's color_idx_img for I index images in ONE launch (gn_color_idx_batch) -> (I, S, S, 4) fp32 RGBA.  idx_img: (I, S, S) int32 as
+    render_points_batch returns it.  images: one dict per image --
+        offset, count     the image's rows of `colors` ((M, 4) fp32) or entries of `values` ((M,) fp32); index j reads row offset + j
+        mode              "table" (colors) or "viridis" (values through matplotlib's viridis over (vmin, vmax))
+        side, default_color (4 floats; default (1, 1, 1, 0)), vmin, vmax
+        overlays          up to 3 of (xyz, rgba, kernel_size): overlay_grip's one-point images, applied in order"""
+    idx_img = _chk(idx_img, _i32, "idx_img")
+    if idx_img.dim() != 3 or idx_img.shape[1] != idx_img.shape[2]:
+        raise ValueError(f"idx_img: expected an (I, S, S) tensor, got {tuple(idx_img.shape)}")
+    n = idx_img.shape[0]
+    if len(images) != n:
+        raise ValueError(f"color_idx_batch: {len(images)} image entries for {n} index images")
+    S = _render_dims("gn_color_idx_batch", n, idx_img.shape[1])
+    dev = idx_img.device
+    for name, t, width in (("colors", colors, 4), ("values", values, None)):
+        if t is None:
+            continue
+        _chk(t, torch.float32, name)
+        if t.device != dev or (t.dim() != 2 or t.shape[1] != 4 if width else t.dim() != 1):
+            raise ValueError(f"{name}: expected {'an (M, 4)' if width else 'an (M,)'} tensor on {dev}, got {tuple(t.shape)} on {t.device}")
+    if colors is not None and colors.data_ptr() % 16:
+        colors = colors.clone()                              # (the kernel reads a row as one float4)
+    out = torch.empty((n, S, S, 4), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    tab = (_lib.ColorImage * n)()
+    for e, im in zip(tab, images):
+        mode = im.get("mode", "table")
+        if mode not in ("table", "viridis"):
+            raise ValueError(f"color_idx_batch: unknown mode {mode!r}")
+        src = colors if mode == "table" else values
+        e.offset, e.count = int(im.get("offset", 0)), int(im["count"])
+        if e.offset < 0 or e.count < 0 or e.offset + e.count > (0 if src is None else src.shape[0]):
+            raise ValueError(f"color_idx_batch: rows {e.offset} .. {e.offset + e.count} are outside the image's colour source")
+        e.mode, e.side = (_lib.COLOR_TABLE if mode == "table" else _lib.COLOR_VIRIDIS), _side(im.get("side", "front"))
+        e.vmin, e.vmax = float(im.get("vmin", 0.0)), float(im.get("vmax", 1.0))
+        e.default_color[:] = [float(v) for v in im.get("default_color", (1, 1, 1, 0))]
+        overlays = im.get("overlays", ())
+        if len(overlays) > _lib.RENDER_MAX_OVERLAYS:
+            raise ValueError(f"color_idx_batch: {len(overlays)} overlays (at most {_lib.RENDER_MAX_OVERLAYS})")
+        e.num_overlays = len(overlays)
+        for o, (xyz, rgba, k) in zip(e.overlay, overlays):
+            o.xyz[:], o.rgba[:], o.kernel_size = [float(v) for v in xyz], [float(v) for v in rgba], int(k)
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    _lib.call("gn_color_idx_batch", _p(idx_img), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), _p(colors), _p(values), n, S, _p(out), _stream())
+    return out

@@ -9,7 +9,9 @@
   training_step / training_metrics      the reference's metrics['loss'] as a device scalar with a graph (autograd.nocs_bin_loss over the per-point and the
                                         global row set; autograd.value_loss with l2 in regression mode), and the five logged values from the same sums.
   train_step(model, optimizer, batch)   zero_grad -> training_step -> backward -> optimizer.step()
-  python -m garmentnets_amd.train       epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint
+  python -m garmentnets_amd.train       epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint;
+                                        with --vis_per_items > 0 the reference's monitor images of the selected garments (visualize.py) as PNGs under
+                                        <output_dir>/vis/epoch_<NNN>/, rendered from the step's own forward
 
 Real edges only.  Inside the two SA modules local_nn runs over the rows of real edges (slot_src >= 0) and not over the empty slots of the ball table:
 BatchNorm statistics and the running buffers see exactly PyG's edge set, which is also what the fused inference kernel later applies them to.
@@ -159,13 +161,16 @@ def training_metrics(model, batch):
     return metrics_from_sums(model, loss_and_sums(model, batch, result)[1], result, batch)
 
 
-def train_step(model, optimizer, batch):
-    """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward"""
+def train_step(model, optimizer, batch, monitor=None):
+    """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward.  monitor: called with
+    that forward's result after the step (the training monitors: no second forward)"""
     optimizer.zero_grad(set_to_none=True)
     result = pointnet2_nocs_forward(model, batch)
     loss, sums = loss_and_sums(model, batch, result)
     loss.backward()
     optimizer.step()
+    if monitor is not None:
+        monitor(result)
     return metrics_from_sums(model, sums, result, batch)
 
 
@@ -180,6 +185,7 @@ def build_parser():
     ap.add_argument("--learning_rate", type=float, default=None, help="default: the model's hyper-parameter")
     ap.add_argument("--seed", type=int, default=0)
     validate.add_resident_arguments(ap)
+    validate.add_monitor_arguments(ap)
     return ap
 
 
@@ -198,9 +204,9 @@ def _val_dataset(a, volume_task_space=False):
     return validate.make_dataset(va, volume_task_space=volume_task_space)
 
 
-def _validate(model, a, device, volume_task_space=False, resident=None):
+def _validate(model, a, device, volume_task_space=False, resident=None, hook=None):
     """validate.py's loop over the val subset, the model in eval mode for it.  resident: the val subset as a ResidentDataset (built once by the caller);
-    None: a host dataset made here"""
+    None: a host dataset made here.  hook: validation_rows' (the validation monitors)"""
     from . import validate
     dataset = _val_dataset(a, volume_task_space) if resident is None else resident.dataset
     indices = dataset.subset_indices("val")
@@ -208,14 +214,19 @@ def _validate(model, a, device, volume_task_space=False, resident=None):
     model.eval()
     try:
         rows = validate.validation_rows(model, dataset, indices, a.batch_size, a.num_batches, device,
-                                        batches=None if resident is None else resident.batches(indices, a.batch_size))
+                                        batches=None if resident is None else resident.batches(indices, a.batch_size), hook=hook)
     finally:
         model.train(was_training)
     return validate.epoch_values(rows)
 
 
+def _train_monitor(writer, batch_idx, batch):
+    """train_step's monitor for one batch, from an epoch's visualize.epoch_writer (None: no monitors)"""
+    return None if writer is None else lambda result: writer(batch_idx, batch, result)
+
+
 def main(argv=None):
-    from . import validate
+    from . import validate, visualize
     a = parse_args(argv)
     device = torch.device("cuda:{}".format(a.gpu_id))
     torch.cuda.set_device(device)
@@ -223,6 +234,7 @@ def main(argv=None):
     model = validate.load_model(a, device).requires_grad_(True).train()
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
+    validate.apply_monitor_arguments(model, a)
     optimizer = model.configure_optimizers()
     a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a)
@@ -234,18 +246,20 @@ def main(argv=None):
     for epoch in range(a.epochs):
         order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
         source = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
+        writer = visualize.epoch_writer(model, a.output_dir, epoch, True)
         for batch_idx, (chunk, batch) in enumerate(source):
             if a.num_batches is not None and batch_idx >= a.num_batches:
                 break
             t0 = time.time()
-            metrics = train_step(model, optimizer, batch.to(device))
+            batch = batch.to(device)
+            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch))
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "seconds": time.time() - t0}
             if a.resident:
                 row["resident"] = True
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
             print(json.dumps(row))
-        val = _validate(model, a, device, resident=val_resident)
+        val = _validate(model, a, device, resident=val_resident, hook=visualize.epoch_writer(model, a.output_dir, epoch, False))
         epochs.append(dict(epoch=epoch, **val))
         print(json.dumps(epochs[-1]))
         torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},

@@ -14,7 +14,9 @@
                                         It trains with arith.device_packs: the UNet's static weight packs, stale after every optimiser step, are rebuilt
                                         on the device (csrc/weight_pack.hip; same bits) instead of through the host; --host_packs keeps the host builders.
                                         --split_backward: the UNet convolutions' gradients on the 16-bit matrix cores (arith.conv_grad_mode = "f16x2",
-                                        csrc/unet_grad_split.hip); without it the backward is fp32, today's launches
+                                        csrc/unet_grad_split.hip); without it the backward is fp32, today's launches.
+                                        --vis_per_items > 0: the reference's monitor images of the selected garments (visualize.py) as PNGs under
+                                        <output_dir>/vis/epoch_<NNN>/, rendered from the step's own forward
 
 The first stage is frozen, as the reference's pointnet2_forward freezes it on every call: pointnet2_nocs is put in eval mode (and left there, whatever
 model.train() said before) and runs its inference forward under no_grad.  None of its parameters or buffers changes and none gets a .grad; they stay in
@@ -38,7 +40,7 @@ import torch
 
 from . import autograd as A
 from . import ops
-from .train import _bn_training, _mlp, _plain, _val_dataset, _validate
+from .train import _bn_training, _mlp, _plain, _train_monitor, _val_dataset, _validate
 
 HEADS = (("volume_decoder", "volume_decoder_result", "volume_query_points"), ("surface_decoder", "surface_decoder_result", "surf_query_points"),
          ("mc_surface_decoder", "mc_surface_decoder_result", "mc_surf_query_points"))
@@ -145,13 +147,16 @@ def training_metrics(model, batch):
     return metrics_from_sums(model, loss_and_sums(model, batch, result)[1], result, batch)
 
 
-def train_step(model, optimizer, batch):
-    """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward"""
+def train_step(model, optimizer, batch, monitor=None):
+    """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward.  monitor: called with
+    that forward's result after the step (the training monitors: no second forward)"""
     optimizer.zero_grad(set_to_none=True)
     result = pipeline_forward(model, batch)
     loss, sums = loss_and_sums(model, batch, result)
     loss.backward()
     optimizer.step()
+    if monitor is not None:
+        monitor(result)
     return metrics_from_sums(model, sums, result, batch)
 
 
@@ -175,6 +180,7 @@ def build_parser():
                     help="run the gradients of the UNet's 3x3x3 convolutions on the 16-bit matrix cores (arith.conv_grad_mode = 'f16x2': fp16 operand "
                          "planes, fp32 accumulation); default: the fp32 backward")
     validate.add_resident_arguments(ap)
+    validate.add_monitor_arguments(ap)
     return ap
 
 
@@ -206,7 +212,7 @@ def load_model(a, device):
 
 
 def main(argv=None):
-    from . import validate
+    from . import validate, visualize
     a = parse_args(argv)
     device = torch.device("cuda:{}".format(a.gpu_id))
     torch.cuda.set_device(device)
@@ -217,6 +223,7 @@ def main(argv=None):
         model.arith = model.arith.replace(conv_grad_mode="f16x2")
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
+    validate.apply_monitor_arguments(model, a)
     optimizer = model.configure_optimizers()
     a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a, volume_task_space=model.volume_task_space)
@@ -230,6 +237,7 @@ def main(argv=None):
     for epoch in range(a.epochs):
         order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
         batches = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
+        writer = visualize.epoch_writer(model, a.output_dir, epoch, True)
         batch_idx = 0
         while a.num_batches is None or batch_idx < a.num_batches:
             t0 = time.time()
@@ -238,7 +246,8 @@ def main(argv=None):
                 break
             chunk, batch = item
             t1 = time.time()
-            metrics = train_step(model, optimizer, batch.to(device))
+            batch = batch.to(device)
+            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch))
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1,
                    "device_packs": model.arith.device_packs}
             if a.resident:
@@ -247,7 +256,8 @@ def main(argv=None):
             rows.append(row)
             print(json.dumps(row))
             batch_idx += 1
-        val = _validate(model, a, device, volume_task_space=task, resident=val_resident)
+        val = _validate(model, a, device, volume_task_space=task, resident=val_resident,
+                        hook=visualize.epoch_writer(model, a.output_dir, epoch, False))
         epochs.append(dict(epoch=epoch, device_packs=model.arith.device_packs, **val))
         print(json.dumps(epochs[-1]))
         torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},

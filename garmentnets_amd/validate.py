@@ -99,6 +99,24 @@ def add_resident_arguments(ap):
                     help="visit the train subset in a RandomState(seed + epoch) permutation (the reference's train_dataloader: shuffle=True)")
 
 
+def add_monitor_arguments(ap):
+    """the training loops' monitor flags (train.py, train_pipeline.py): the reference's three hyper-parameters of vis_batch"""
+    ap.add_argument("--vis_per_items", type=int, default=None,
+                    help="draw every this-many-th garment of an epoch into <output_dir>/vis/epoch_<NNN>/ (0: none); default: the model's hyper-parameter")
+    ap.add_argument("--max_vis_per_epoch_train", type=int, default=None, help="at most this many train images per epoch; default: the model's")
+    ap.add_argument("--max_vis_per_epoch_val", type=int, default=None, help="at most this many val images per epoch; default: the model's")
+
+
+def apply_monitor_arguments(model, a):
+    """the three flags that were given replace the model's hyper-parameters (and travel in its checkpoints); the model learns the loop's batch size,
+    which get_vis_idxs numbers the garments of an epoch with"""
+    for key in ("vis_per_items", "max_vis_per_epoch_train", "max_vis_per_epoch_val"):
+        if getattr(a, key) is not None:
+            setattr(model, key, getattr(a, key))
+            model.hparams[key] = getattr(a, key)
+    model.batch_size = a.batch_size
+
+
 def epoch_order(indices, shuffle, seed, epoch):
     """the order of the train subset in `epoch`"""
     indices = np.asarray(indices)
@@ -156,16 +174,24 @@ def write_outputs(output_dir, rows, summary):
         json.dump(summary, f, indent=2)
 
 
-def validation_rows(model, dataset, indices, batch_size, num_batches, device, log=None, batches=None):
+def validation_rows(model, dataset, indices, batch_size, num_batches, device, log=None, batches=None, hook=None):
     """the validation loop: one row (batch_idx, garments, seconds, every val_* metric) per batch of `indices`, at most num_batches of them.
-    batches: another source of (dataset indices, Batch) pairs than host_batches(dataset, indices, batch_size), e.g. ResidentDataset.batches(...)"""
+    batches: another source of (dataset indices, Batch) pairs than host_batches(dataset, indices, batch_size), e.g. ResidentDataset.batches(...).
+    hook: called as hook(batch_idx, batch on the device, the model's forward of it) after each batch's metrics, which are then formed from that one
+    forward (the training loops' validation monitors)"""
     rows = []
     for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, batch_size) if batches is None else batches):
         if num_batches is not None and batch_idx >= num_batches:
             break
         t0 = time.time()
         with torch.no_grad():
-            metrics = model.validation_metrics(batch.to(device))
+            if hook is None:
+                metrics = model.validation_metrics(batch.to(device))
+            else:
+                on_device = batch.to(device)
+                result = model(on_device)
+                metrics = model.validation_metrics(on_device, result=result)
+                hook(batch_idx, on_device, result)
         row = {"batch_idx": batch_idx, "garments": len(chunk), "seconds": time.time() - t0}
         row.update({"val_" + k: float(v) for k, v in metrics.items()})
         rows.append(row)

@@ -900,6 +900,44 @@ int gn_resident_surface(const GnResidentStore *store, const int32_t *slots, int 
 int gn_resident_mc_surface(const GnResidentStore *store, const int32_t *slots, int B, int M, const double *face_u, const double *uv, float *query,
                            float *on_surf, void *stream);
 
+/* ---- Training monitors (csrc/render.hip; DESIGN.md "Training monitors"): the reference's z-buffered point splat (common/rendering_util.py) and its
+ * colouring, every image of a batch in one launch each.  No atomics: a pixel is written once by its owner, identical calls give identical bits. ---- */
+
+#define GN_RENDER_MAX_SIZE 4096      /* 1 <= S <= this */
+#define GN_RENDER_MAX_OVERLAYS 3
+#define GN_RENDER_FRONT 0            /* camera (x, 1 - z, y) */
+#define GN_RENDER_TOP 1              /* camera (x, 1 - y, 1 - z) */
+#define GN_RENDER_LEFT 2             /* camera (1 - y, 1 - z, x) */
+#define GN_COLOR_TABLE 0             /* colour = colors[offset + idx] */
+#define GN_COLOR_VIRIDIS 1           /* colour = viridis((values[offset + idx] - vmin) / (vmax - vmin)), matplotlib's Colormap.__call__ in fp32 */
+
+typedef struct {
+    float xyz[3], rgba[4];           /* a point in the image's own space (it goes through the image's camera) and its colour; alpha <= 0: not drawn */
+    int32_t kernel_size;
+} GnOverlayPoint;
+
+typedef struct {
+    int64_t offset, count;           /* the image's rows of colors / entries of values; an index >= count keeps the default colour */
+    int32_t mode, side;              /* GN_COLOR_*, GN_RENDER_* */
+    float vmin, vmax;
+    float default_color[4];
+    int32_t num_overlays, pad;
+    GnOverlayPoint overlay[GN_RENDER_MAX_OVERLAYS];   /* applied in order, each over the ones before */
+} GnColorImage;
+
+/* points [N][3] fp32 -> out [I][S][S] uint32: image i draws the points seg[i] .. seg[i+1] from side[i] with a kernel_size[i]-wide footprint; a pixel holds
+ * the index (from the start of its image's segment) of the covering point with the smallest camera depth in fp64, the lowest index among equal depths,
+ * 0xFFFFFFFF when nobody covers it.  A point with a non-finite coordinate is not drawn.  seg_host [I+1], side_host [I], kernel_size_host [I]: HOST arrays,
+ * checked here (S in [1, GN_RENDER_MAX_SIZE], 1 <= k <= S, I <= 65535, a segment shorter than 2^32 - 1, side in {0, 1, 2}); tab [I][4] int64: the same
+ * (first point, end point, side, kernel_size) per image in DEVICE memory, what the kernel reads. */
+int gn_render_points_batch(const float *points, const int64_t *seg_host, const int32_t *side_host, const int32_t *kernel_size_host, const int64_t *tab,
+                           int I, int S, uint32_t *out, void *stream);
+/* idx_img [I][S][S] -> out [I][S][S][4] fp32 RGBA: default_color where the index is 0xFFFFFFFF, else the image's colour of that index; then the overlay
+ * points, each a one-point image of its own footprint copied where it is drawn (the reference's overlay_grip).  tab_host: the table on the HOST (checked
+ * here); tab: the same table in DEVICE memory; colors [..][4] (16-byte aligned) and values [..] fp32, NULL when no image reads them. */
+int gn_color_idx_batch(const uint32_t *idx_img, const GnColorImage *tab_host, const GnColorImage *tab, const float *colors, const float *values, int I,
+                       int S, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
