@@ -107,6 +107,7 @@ PROTOTYPES = {
     "gn_nocs_bin_loss_bwd": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "gn_value_losses_bwd": [_vp, _i32, _vp, _vp, _vp],
     "gn_adam_step": [_vp, _i32, _i64, _vp, _i32, _vp],
+    "gn_grad_pack": [_vp, _i32, _i64, _vp, _i64, _i32, _vp],
     "gn_grid_scatter_bwd_workspace_bytes": [_i64, _i32, _i64, _i32],
     "gn_grid_scatter_bwd": [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _i32, _vp],
     "gn_segment_max_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
@@ -192,6 +193,11 @@ ADAM_MAX_HYPER = 16                             # GN_ADAM_MAX_HYPER
 class AdamEntry(ctypes.Structure):
     """GnAdamEntry (DEVICE table entry of gn_adam_step)"""
     _fields_ = [("p", _vp), ("g", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("numel", _i64), ("blk0", _i64), ("hyper", _i32), ("pad", _i32)]
+
+
+class PackEntry(ctypes.Structure):
+    """GnPackEntry (DEVICE table entry of gn_grad_pack)"""
+    _fields_ = [("src", _vp), ("dst_off", _i64), ("numel", _i64), ("blk0", _i64)]
 
 
 class AdamHyper(ctypes.Structure):

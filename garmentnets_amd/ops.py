@@ -2086,3 +2086,30 @@ def color_idx_batch(idx_img, images, colors=None, values=None):
     tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
     _lib.call("gn_color_idx_batch", _p(idx_img), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), _p(colors), _p(values), n, S, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ gradient pack (data-parallel training)
+def grad_pack_table(rows, device):
+    """the device table of gn_grad_pack.  rows: [(source pointer or None, dst_off, numel)] in the order of their workgroups; dst_off a multiple of 4
+    (parallel.plan_flat).  -> (uint8 device tensor, number of workgroups)"""
+    entries, blk = [], 0
+    for ptr, off, numel in rows:
+        if off % 4 or off < 0 or numel < 0:
+            raise ValueError(f"grad_pack_table: dst_off must be a non-negative multiple of 4 and numel non-negative, got ({off}, {numel})")
+        entries.append((ptr or None, int(off), int(numel), blk))
+        blk += -(-int(numel) // _lib.ADAM_CHUNK)
+    host = _table(_lib.PackEntry, entries)
+    return torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device), blk
+
+
+def grad_pack(table, n_entries, n_blocks, flat, world=1, flat_numel=None):
+    """gn_grad_pack: every source of the device `table` (grad_pack_table) into its slice of the fp32 buffer `flat`, divided by `world` (bit copies for
+    world == 1), pads and null sources as zeros, in ONE launch.  flat_numel: the floats of flat the kernel may write (default: all of it).  -> flat"""
+    flat = _chk(flat, torch.float32, "flat")
+    if table.dtype != torch.uint8 or not table.is_contiguous() or table.numel() < int(n_entries) * ctypes.sizeof(_lib.PackEntry):
+        raise ValueError("grad_pack: table must be the contiguous uint8 tensor of grad_pack_table, n_entries entries long")
+    numel = flat.numel() if flat_numel is None else int(flat_numel)
+    if numel > flat.numel():
+        raise ValueError(f"grad_pack: flat_numel {numel} exceeds the buffer's {flat.numel()} elements")
+    _lib.call("gn_grad_pack", _p(table), int(n_entries), int(n_blocks), _p(flat), numel, int(world), _stream())
+    return flat

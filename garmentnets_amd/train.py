@@ -20,6 +20,10 @@ Dropout is the one deliberate exception to "all arithmetic in HIP": the referenc
 iff dropout=True) are torch.nn.functional.dropout on four small tensors, at the reference's positions, when the model is in training mode -- torch's
 generator stream could not be matched by a kernel of ours anyway.
 
+Several GPUs: `python -m torch.distributed.run --nproc-per-node N -m garmentnets_amd.train ...` trains data-parallel (parallel.py): every
+rank takes its fixed share of the train subset (--batch_size is per rank), train_step gets a GradientReducer, rank 0 alone prints and writes.  Without
+torchrun nothing of that runs.
+
 The second stage's step (ConvImplicitWNFPipeline behind this model, frozen) is a module of its own, garmentnets_amd/train_pipeline.py, named after the
 reference's script: `python -m garmentnets_amd.train_pipeline`.  It shares _bn_training / _plain / _mlp and _validate with this file; `--model pipeline`
 here keeps its refusal.
@@ -161,13 +165,16 @@ def training_metrics(model, batch):
     return metrics_from_sums(model, loss_and_sums(model, batch, result)[1], result, batch)
 
 
-def train_step(model, optimizer, batch, monitor=None):
+def train_step(model, optimizer, batch, monitor=None, reducer=None):
     """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward.  monitor: called with
-    that forward's result after the step (the training monitors: no second forward)"""
+    that forward's result after the step (the training monitors: no second forward).  reducer: a parallel.GradientReducer over `optimizer`
+    (data-parallel training): the gradients become their mean over the ranks before the update; None: this process's own, no launch added"""
     optimizer.zero_grad(set_to_none=True)
     result = pointnet2_nocs_forward(model, batch)
     loss, sums = loss_and_sums(model, batch, result)
     loss.backward()
+    if reducer is not None:
+        reducer.reduce()
     optimizer.step()
     if monitor is not None:
         monitor(result)
@@ -204,20 +211,51 @@ def _val_dataset(a, volume_task_space=False):
     return validate.make_dataset(va, volume_task_space=volume_task_space)
 
 
-def _validate(model, a, device, volume_task_space=False, resident=None, hook=None):
+def _validate(model, a, device, volume_task_space=False, resident=None, hook=None, ranks=None):
     """validate.py's loop over the val subset, the model in eval mode for it.  resident: the val subset as a ResidentDataset (built once by the caller);
-    None: a host dataset made here.  hook: validation_rows' (the validation monitors)"""
-    from . import validate
+    None: a host dataset made here.  hook: validation_rows' (the validation monitors).  ranks: parallel.training_ranks' namespace of a data-parallel
+    run: this rank loops over its share of the subset (no collective inside the loop) and the garment-weighted means are formed over every rank's sums"""
+    from . import parallel, validate
     dataset = _val_dataset(a, volume_task_space) if resident is None else resident.dataset
     indices = dataset.subset_indices("val")
+    if ranks is not None and ranks.world > 1:
+        indices = parallel.shard_indices(indices, ranks.rank, ranks.world, pad=False)        # (its fixed share, not padded: a partition of the subset)
     was_training = model.training
     model.eval()
+    many = ranks is not None and ranks.world > 1
+    own = parallel.borrow_buffers(model) if many else None  # (rank 0's running statistics on every rank: the ones last.ckpt holds)
     try:
         rows = validate.validation_rows(model, dataset, indices, a.batch_size, a.num_batches, device,
                                         batches=None if resident is None else resident.batches(indices, a.batch_size), hook=hook)
     finally:
+        if many:
+            parallel.restore_buffers(model, own)
         model.train(was_training)
+    if many:
+        return parallel.gather_epoch_values(rows, ranks.metrics_device)
     return validate.epoch_values(rows)
+
+
+def _data_parallel(model, optimizer, dataset, a, ranks, volume_task_space=False):
+    """the data-parallel part of a training loop's set-up -> (reducer, train indices, train resident, val resident).  One process: no reducer, the whole
+    subsets.  WORLD_SIZE > 1: rank 0's parameters and buffers everywhere, a GradientReducer, and this rank's fixed shares of the train subset (padded:
+    every rank takes the same number of steps) and of the val subset (not padded)"""
+    from . import parallel, validate
+    indices = dataset.subset_indices("train")
+    many = ranks.world > 1
+    reducer = None
+    if many:
+        parallel.broadcast_module(model)
+        reducer = parallel.GradientReducer(optimizer, ranks.backend, names=model)
+        indices = parallel.shard_indices(indices, ranks.rank, ranks.world, pad=True)
+    resident = val_resident = None
+    if a.resident:
+        tag = ranks.rank if many else None
+        resident = validate.make_resident(a, dataset, "train", ranks.device, indices=indices if many else None, rank=tag)
+        val_dataset = _val_dataset(a, volume_task_space)
+        val_indices = parallel.shard_indices(val_dataset.subset_indices("val"), ranks.rank, ranks.world, pad=False) if many else None
+        val_resident = validate.make_resident(a, val_dataset, "val", ranks.device, indices=val_indices, rank=tag)
+    return reducer, indices, resident, val_resident
 
 
 def _train_monitor(writer, batch_idx, batch):
@@ -226,11 +264,12 @@ def _train_monitor(writer, batch_idx, batch):
 
 
 def main(argv=None):
-    from . import validate, visualize
+    from . import parallel, validate, visualize
     a = parse_args(argv)
-    device = torch.device("cuda:{}".format(a.gpu_id))
+    ranks = parallel.training_ranks(a.gpu_id)               # (one process: cuda:<gpu_id>; under torch.distributed.run: LOCAL_RANK's device, data-parallel)
+    device, chief = ranks.device, ranks.rank == 0
     torch.cuda.set_device(device)
-    torch.manual_seed(a.seed)
+    torch.manual_seed(a.seed + ranks.rank)                  # (the dropout masks differ between the ranks; the data draws are seeded by dataset index)
     model = validate.load_model(a, device).requires_grad_(True).train()
     if a.learning_rate is not None:
         model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
@@ -238,33 +277,40 @@ def main(argv=None):
     optimizer = model.configure_optimizers()
     a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a)
-    indices = dataset.subset_indices("train")
-    resident = validate.make_resident(a, dataset, "train", device) if a.resident else None
-    val_resident = validate.make_resident(a, _val_dataset(a), "val", device) if a.resident else None
-    os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
+    reducer, indices, resident, val_resident = _data_parallel(model, optimizer, dataset, a, ranks)
+    if chief:
+        os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
     rows, epochs = [], []
     for epoch in range(a.epochs):
         order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
         source = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
-        writer = visualize.epoch_writer(model, a.output_dir, epoch, True)
+        writer = visualize.epoch_writer(model, a.output_dir, epoch, True) if chief else None
         for batch_idx, (chunk, batch) in enumerate(source):
             if a.num_batches is not None and batch_idx >= a.num_batches:
                 break
             t0 = time.time()
             batch = batch.to(device)
-            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch))
+            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch), reducer=reducer)
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "seconds": time.time() - t0}
+            if ranks.world > 1:
+                row["world"] = ranks.world
             if a.resident:
                 row["resident"] = True
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
-            print(json.dumps(row))
-        val = _validate(model, a, device, resident=val_resident, hook=visualize.epoch_writer(model, a.output_dir, epoch, False))
+            if chief:
+                print(json.dumps(row))
+        val = _validate(model, a, device, resident=val_resident, hook=visualize.epoch_writer(model, a.output_dir, epoch, False) if chief else None,
+                        ranks=ranks)
         epochs.append(dict(epoch=epoch, **val))
-        print(json.dumps(epochs[-1]))
-        torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},
-                   os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
-    cols = ["epoch", "batch_idx", "garments", "seconds"] + (["resident"] if a.resident else []) + ["train_" + k for k in METRIC_KEYS]
+        if chief:
+            print(json.dumps(epochs[-1]))
+            torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()],
+                        "epoch": epoch}, os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
+    result = {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
+    if not chief:                                           # (rank 0 alone writes: the csv holds its own batches' metrics, the checkpoint its buffers)
+        return result
+    cols = ["epoch", "batch_idx", "garments", "seconds"] + (["world"] if ranks.world > 1 else []) + (["resident"] if a.resident else []) + ["train_" + k for k in METRIC_KEYS]
     with open(os.path.join(a.output_dir, "train_metrics.csv"), "w", newline="") as f:
         w = csv.DictWriter(f, fieldnames=cols)
         w.writeheader()
@@ -272,8 +318,10 @@ def main(argv=None):
             w.writerow({k: r.get(k, "") for k in cols})
     with open(os.path.join(a.output_dir, "val_epochs.json"), "w") as f:
         json.dump(epochs, f, indent=2)
-    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
+    return result
 
 
 if __name__ == "__main__":
     main()
+    from . import parallel
+    parallel.finish()

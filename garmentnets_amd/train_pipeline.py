@@ -29,7 +29,10 @@ record the second stage alone.
 --resident holds the train and the val subset in device memory and assembles every batch there (io/resident.py); each csv row records data_seconds, the
 host time until the batch is handed to the step, either way.
 
-What stays out: a worker pool for the host dataset, a backward for the fused inference kernels.
+Several GPUs: `python -m torch.distributed.run --nproc-per-node N -m garmentnets_amd.train_pipeline ...` trains data-parallel, as train.py does (its
+docstring; parallel.py): the frozen first stage has no gradient and stays out of the reduced buffer; BatchNorm running buffers stay per rank.
+
+What stays out: a worker pool for the host dataset, a backward for the fused inference kernels, SyncBN, overlap of the all-reduce with the backward.
 """
 import csv
 import json
@@ -40,7 +43,7 @@ import torch
 
 from . import autograd as A
 from . import ops
-from .train import _bn_training, _mlp, _plain, _train_monitor, _val_dataset, _validate
+from .train import _bn_training, _data_parallel, _mlp, _plain, _train_monitor, _validate
 
 HEADS = (("volume_decoder", "volume_decoder_result", "volume_query_points"), ("surface_decoder", "surface_decoder_result", "surf_query_points"),
          ("mc_surface_decoder", "mc_surface_decoder_result", "mc_surf_query_points"))
@@ -147,13 +150,16 @@ def training_metrics(model, batch):
     return metrics_from_sums(model, loss_and_sums(model, batch, result)[1], result, batch)
 
 
-def train_step(model, optimizer, batch, monitor=None):
+def train_step(model, optimizer, batch, monitor=None, reducer=None):
     """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward.  monitor: called with
-    that forward's result after the step (the training monitors: no second forward)"""
+    that forward's result after the step (the training monitors: no second forward).  reducer: a parallel.GradientReducer over `optimizer`
+    (data-parallel training): the gradients become their mean over the ranks before the update; None: this process's own, no launch added"""
     optimizer.zero_grad(set_to_none=True)
     result = pipeline_forward(model, batch)
     loss, sums = loss_and_sums(model, batch, result)
     loss.backward()
+    if reducer is not None:
+        reducer.reduce()
     optimizer.step()
     if monitor is not None:
         monitor(result)
@@ -212,11 +218,12 @@ def load_model(a, device):
 
 
 def main(argv=None):
-    from . import validate, visualize
+    from . import parallel, validate, visualize
     a = parse_args(argv)
-    device = torch.device("cuda:{}".format(a.gpu_id))
+    ranks = parallel.training_ranks(a.gpu_id)               # (one process: cuda:<gpu_id>; under torch.distributed.run: LOCAL_RANK's device, data-parallel)
+    device, chief = ranks.device, ranks.rank == 0
     torch.cuda.set_device(device)
-    torch.manual_seed(a.seed)
+    torch.manual_seed(a.seed + ranks.rank)
     model = load_model(a, device).requires_grad_(True).train()
     model.arith = model.arith.replace(device_packs=not a.host_packs)        # (train_step reads the model's arithmetic)
     if a.split_backward:
@@ -227,17 +234,16 @@ def main(argv=None):
     optimizer = model.configure_optimizers()
     a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
     dataset = validate.make_dataset(a, volume_task_space=model.volume_task_space)
-    indices = dataset.subset_indices("train")
     task = model.volume_task_space
-    resident = validate.make_resident(a, dataset, "train", device) if a.resident else None
-    val_resident = validate.make_resident(a, _val_dataset(a, task), "val", device) if a.resident else None
-    os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
+    reducer, indices, resident, val_resident = _data_parallel(model, optimizer, dataset, a, ranks, volume_task_space=task)
+    if chief:
+        os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
     keys = metric_keys(model)
     rows, epochs = [], []
     for epoch in range(a.epochs):
         order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
         batches = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
-        writer = visualize.epoch_writer(model, a.output_dir, epoch, True)
+        writer = visualize.epoch_writer(model, a.output_dir, epoch, True) if chief else None
         batch_idx = 0
         while a.num_batches is None or batch_idx < a.num_batches:
             t0 = time.time()
@@ -247,22 +253,30 @@ def main(argv=None):
             chunk, batch = item
             t1 = time.time()
             batch = batch.to(device)
-            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch))
+            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch), reducer=reducer)
             row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1,
                    "device_packs": model.arith.device_packs}
+            if ranks.world > 1:
+                row["world"] = ranks.world
             if a.resident:
                 row["resident"] = True
             row.update({"train_" + k: float(v) for k, v in metrics.items()})
             rows.append(row)
-            print(json.dumps(row))
+            if chief:
+                print(json.dumps(row))
             batch_idx += 1
         val = _validate(model, a, device, volume_task_space=task, resident=val_resident,
-                        hook=visualize.epoch_writer(model, a.output_dir, epoch, False))
+                        hook=visualize.epoch_writer(model, a.output_dir, epoch, False) if chief else None, ranks=ranks)
         epochs.append(dict(epoch=epoch, device_packs=model.arith.device_packs, **val))
-        print(json.dumps(epochs[-1]))
-        torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()], "epoch": epoch},
-                   os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
-    cols = ["epoch", "batch_idx", "garments", "data_seconds", "seconds"] + (["resident"] if a.resident else []) + ["train_" + k for k in keys]
+        if chief:
+            print(json.dumps(epochs[-1]))
+            torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()],
+                        "epoch": epoch}, os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
+    result = {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
+    if not chief:                                           # (rank 0 alone writes: the csv holds its own batches' metrics, the checkpoint its buffers)
+        return result
+    cols = (["epoch", "batch_idx", "garments", "data_seconds", "seconds"] + (["world"] if ranks.world > 1 else []) + (["resident"] if a.resident else []) +
+            ["train_" + k for k in keys])
     with open(os.path.join(a.output_dir, "train_metrics.csv"), "w", newline="") as f:
         w = csv.DictWriter(f, fieldnames=cols)
         w.writeheader()
@@ -270,8 +284,10 @@ def main(argv=None):
             w.writerow({k: r.get(k, "") for k in cols})
     with open(os.path.join(a.output_dir, "val_epochs.json"), "w") as f:
         json.dump(epochs, f, indent=2)
-    return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
+    return result
 
 
 if __name__ == "__main__":
     main()
+    from . import parallel
+    parallel.finish()

@@ -123,12 +123,16 @@ def epoch_order(indices, shuffle, seed, epoch):
     return indices[np.random.RandomState(seed + epoch).permutation(len(indices))] if shuffle else indices
 
 
-def make_resident(a, dataset, subset, device):
-    """the subset of `dataset` as a ResidentDataset under --resident_gib; prints its one-off load time and footprint"""
+def make_resident(a, dataset, subset, device, indices=None, rank=None):
+    """the subset of `dataset` as a ResidentDataset under --resident_gib; prints its one-off load time and footprint.  indices: this rank's share of
+    the subset (parallel.shard_indices) in place of all of it; the report of EVERY rank then carries its rank and its index list"""
     from .io.resident import ResidentDataset
     budget = None if a.resident_gib is None else int(a.resident_gib * 2 ** 30)
-    res = ResidentDataset(dataset, dataset.subset_indices(subset), device, max_bytes=budget)
-    print(json.dumps({"resident_subset": subset, "samples": len(res), "nbytes": res.nbytes, "load_seconds": res.load_seconds}))
+    res = ResidentDataset(dataset, dataset.subset_indices(subset) if indices is None else indices, device, max_bytes=budget)
+    report = {"resident_subset": subset, "samples": len(res), "nbytes": res.nbytes, "load_seconds": res.load_seconds}
+    if rank is not None:
+        report.update(rank=rank, indices=res.indices)
+    print(json.dumps(report), flush=rank is not None)
     return res
 
 

@@ -687,6 +687,24 @@ typedef struct {
 
 int gn_adam_step(const GnAdamEntry *table, int n, int64_t nblocks, const GnAdamHyper *hyper_host, int nhyper, void *stream);
 
+/* ---- Gradient pack (csrc/optim.hip): every gradient of a device table into ONE flat fp32 buffer, divided by the world size, in ONE launch -- the
+ * buffer a data-parallel step hands to one all-reduce (sum), whose result is then the mean over the ranks (garmentnets_amd/parallel.py).
+ * table: DEVICE array of n_entries entries sorted by blk0; entry e owns the workgroups [blk0_e, blk0_e + ceil(numel_e / GN_ADAM_CHUNK)) and the floats
+ * [dst_off_e, dst_off_e + ceil4(numel_e)) of flat: dst_off_e % 4 == 0, the ranges of two entries do not overlap, and the kernel writes zeros from numel_e up
+ * to the next multiple of 4.  src == NULL writes zeros over the whole range.  Value written: src[i] for world == 1 (the bits), __fdiv_rn(src[i], world)
+ * otherwise.  src needs a float's alignment only: a slice of it that starts 16-byte aligned is read in 16-byte loads, any other element by element (no
+ * alignment beyond a float's is assumed); every store is 16 bytes wide.  No atomics, one writer per element, and no store at or beyond flat_numel whatever the table says.
+ * GN_EINVAL before any launch: a null table or flat, n_entries < 1, world < 1, n_blocks outside [1, 2^31), flat_numel not a multiple of 4, flat not
+ * 16-byte aligned. */
+typedef struct {
+    const void *src;       /* [numel] fp32 gradient, or NULL: zeros */
+    int64_t dst_off;       /* first float of this entry in flat, a multiple of 4 */
+    int64_t numel;
+    int64_t blk0;          /* first workgroup of this entry */
+} GnPackEntry;
+
+int gn_grad_pack(const GnPackEntry *table, int n_entries, int64_t n_blocks, float *flat, int64_t flat_numel, int world, void *stream);
+
 /* ---- Operator gradients (csrc/grad.hip): fp32 in / fp32 out.  The selections (grid scatter max / min, segment max, global max pool) hand an output
  * element's gradient to ONE input element: the one whose value is bit-equal to the forward's stored output, the lowest point / edge index among equal
  * values; a NaN never wins.  The sums (sa_gather, knn_interpolate, the sampler's volume gradient) are ordered: one owner per destination adds its
