@@ -38,7 +38,7 @@ def init(backend=None, device=None, timeout=INIT_TIMEOUT):
 
 
 def dist_backend():
-    """the backend the training loops ask for: GARMENTNETS_DIST_BACKEND, "nccl" (RCCL) by default; "gloo" lets ranks share a device (bench.py's rule)"""
+    """the backend the training loop asks for: GARMENTNETS_DIST_BACKEND, "nccl" (RCCL) by default; "gloo" lets ranks share a device (bench.py's rule)"""
     return os.environ.get("GARMENTNETS_DIST_BACKEND", "nccl")
 
 
@@ -183,7 +183,7 @@ def shard_indices(indices, rank, world, pad=True):
     """pure planning: this rank's FIXED share of a subset, indices[rank::world].  pad: the list is first wrapped with its own head to a multiple of
     `world`, so that every rank takes the same number of steps (a rank with fewer would leave the others waiting in the all-reduce); without it the
     shares partition the list exactly (validation: no collective inside the loop).  The share holds for the whole run and an epoch shuffles inside it
-    (validate.epoch_order over the share), so a rank's resident dataset is 1 / world of the subset -- not DistributedSampler's rule, which deals a
+    (train_loop.epoch_order over the share), so a rank's resident dataset is 1 / world of the subset -- not DistributedSampler's rule, which deals a
     global permutation out anew every epoch and so needs every rank to reach every sample."""
     if world == 1:
         return indices
@@ -348,7 +348,7 @@ class GradientReducer:
 
 
 def training_ranks(gpu_id=0):
-    """what a training loop needs to know of its place (train.py, train_pipeline.py) -> namespace(rank, local_rank, world, device, backend, metrics_device,
+    """what the training loop needs to know of its place (train_loop.py) -> namespace(rank, local_rank, world, device, backend, metrics_device,
     affinity).  One process (no torchrun): cuda:<gpu_id>, nothing initialised.  WORLD_SIZE > 1: the device is LOCAL_RANK's (rank_device), the process
     group is initialised with the timeout and the process pinned to its device's cores"""
     import types

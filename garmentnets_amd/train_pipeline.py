@@ -4,19 +4,19 @@
   pipeline_forward(model, data, arith)  ConvImplicitWNFPipeline.forward's contract and result keys, differentiable in every parameter of volume_agg, unet_3d
                                         and the two or three decoders: autograd.mlp -> autograd.scatter -> autograd.unet3d -> autograd.implicit_decode per
                                         head on the one volume (the engine's add is where the heads' volume gradients meet).  Every MLPStack honours its own
-                                        .training (train.py's rule).  When no gradient is wanted and no BatchNorm of the second stage is in training mode it
-                                        IS model.forward(data, arith): the fused decoders, the occupancy-aware first convolution, forward's bits.
-  training_step / training_metrics      the reference's metrics['loss'] as a device scalar with a graph (ONE autograd.value_loss over the segments
+                                        .training (train_loop.py's rule).  When no gradient is wanted and no BatchNorm of the second stage is in training
+                                        mode it IS model.forward(data, arith): the fused decoders, the occupancy-aware first convolution, forward's bits.
+  loss_and_sums / metrics_from_sums     the reference's metrics['loss'] as a device scalar with a graph (ONE autograd.value_loss over the segments
                                         ConvImplicitWNFPipeline.loss_segments forms, which validation reads too), and the logged values from the same sums.
-  train_step(model, optimizer, batch)   zero_grad -> forward -> backward -> optimizer.step(); nothing is read back between forward and backward
+  STAGE                                 this stage as train_loop.py's loop reads it; train_step / training_step / training_metrics are the loop's, bound to it
   python -m garmentnets_amd.train_pipeline
-                                        epochs over the train subset of a dataset store, validate.py's loop on val after each, a csv and a checkpoint.
+                                        train_loop.run over the train subset of a dataset store (train_loop.py's docstring), every row with data_seconds,
+                                        the host time until the batch is handed to the step, and with device_packs.
                                         It trains with arith.device_packs: the UNet's static weight packs, stale after every optimiser step, are rebuilt
                                         on the device (csrc/weight_pack.hip; same bits) instead of through the host; --host_packs keeps the host builders.
                                         --split_backward: the UNet convolutions' gradients on the 16-bit matrix cores (arith.conv_grad_mode = "f16x2",
-                                        csrc/unet_grad_split.hip); without it the backward is fp32, today's launches.
-                                        --vis_per_items > 0: the reference's monitor images of the selected garments (visualize.py) as PNGs under
-                                        <output_dir>/vis/epoch_<NNN>/, rendered from the step's own forward
+                                        csrc/unet_grad_split.hip); without it the backward is fp32.
+                                        --pointnet2_checkpoint: a trained first stage in place of the model's own
 
 The first stage is frozen, as the reference's pointnet2_forward freezes it on every call: pointnet2_nocs is put in eval mode (and left there, whatever
 model.train() said before) and runs its inference forward under no_grad.  None of its parameters or buffers changes and none gets a .grad; they stay in
@@ -26,24 +26,19 @@ every point) is data: no gradient reaches the predicted NOCS coordinates or the 
 The stages are functions of their own (first_stage / aggregate / unet / heads) so that tools/pipeline_step_time.py can bracket them and the tests can
 record the second stage alone.
 
---resident holds the train and the val subset in device memory and assembles every batch there (io/resident.py); each csv row records data_seconds, the
-host time until the batch is handed to the step, either way.
-
-Several GPUs: `python -m torch.distributed.run --nproc-per-node N -m garmentnets_amd.train_pipeline ...` trains data-parallel, as train.py does (its
-docstring; parallel.py): the frozen first stage has no gradient and stays out of the reduced buffer; BatchNorm running buffers stay per rank.
+Several GPUs (train_loop.py's docstring; parallel.py): the frozen first stage has no gradient and stays out of the reduced buffer; BatchNorm running
+buffers stay per rank.
 
 What stays out: a worker pool for the host dataset, a backward for the fused inference kernels, SyncBN, overlap of the all-reduce with the backward.
 """
-import csv
-import json
-import os
-import time
+import functools
 
 import torch
 
 from . import autograd as A
 from . import ops
-from .train import _bn_training, _data_parallel, _mlp, _plain, _train_monitor, _validate
+from . import train_loop as L
+from . import validate
 
 HEADS = (("volume_decoder", "volume_decoder_result", "volume_query_points"), ("surface_decoder", "surface_decoder_result", "surf_query_points"),
          ("mc_surface_decoder", "mc_surface_decoder_result", "mc_surf_query_points"))
@@ -60,7 +55,7 @@ def _inference(model):
     """True when pipeline_forward is model.forward itself: no gradient is wanted and no BatchNorm of the second stage is in training mode"""
     if torch.is_grad_enabled() and any(p.requires_grad for p in model.unet_3d.parameters()):
         return False
-    return all(_plain(stack) for stack in second_stage_stacks(model))
+    return all(L.plain(stack) for stack in second_stage_stacks(model))
 
 
 def first_stage(model, data):
@@ -83,7 +78,7 @@ def aggregate(model, nocs_data):
                                         nocs_data.pred_confidence.contiguous(), nocs_data.batch, agg.lower_corner, agg.upper_corner, agg.grid_shape,
                                         agg.include_point_feature, agg.include_confidence_feature)
     if agg.local_nn is not None:
-        feats = _mlp(agg.local_nn, feats)
+        feats = L.mlp(agg.local_nn, feats)
     B, C = nocs_data.num_graphs, feats.shape[1]
     cells = B * agg.grid_shape[0] * agg.grid_shape[1] * agg.grid_shape[2]
     vol = A.scatter(feats.t(), flat, -1, cells, agg.reduce_method)
@@ -103,7 +98,7 @@ def heads(model, unet3d_result, data):
         decoder = getattr(model, name, None)
         if decoder is None:
             continue
-        y = A.implicit_decode(decoder, vol, getattr(data, queries), batch_stats=_bn_training(decoder.mlp))
+        y = A.implicit_decode(decoder, vol, getattr(data, queries), batch_stats=L.bn_training(decoder.mlp))
         out[key] = {"out_features": y}
         if name == "volume_decoder":
             out[key]["pred_volume_value"] = y.view(*y.shape[:-1])
@@ -141,42 +136,21 @@ def metric_keys(model):
     return ("loss", "volume_loss", "surface_loss") + (("mc_surface_loss",) if model.mc_surface_loss_weight > 0 else ())
 
 
-def training_step(model, batch, batch_idx=None):
-    return loss_and_sums(model, batch)[0]
-
-
-def training_metrics(model, batch):
-    result = pipeline_forward(model, batch)
-    return metrics_from_sums(model, loss_and_sums(model, batch, result)[1], result, batch)
-
-
-def train_step(model, optimizer, batch, monitor=None, reducer=None):
-    """one optimisation step; -> the detached metrics of the batch (python floats), from the sums of the step's own forward.  monitor: called with
-    that forward's result after the step (the training monitors: no second forward).  reducer: a parallel.GradientReducer over `optimizer`
-    (data-parallel training): the gradients become their mean over the ranks before the update; None: this process's own, no launch added"""
-    optimizer.zero_grad(set_to_none=True)
-    result = pipeline_forward(model, batch)
-    loss, sums = loss_and_sums(model, batch, result)
-    loss.backward()
-    if reducer is not None:
-        reducer.reduce()
-    optimizer.step()
-    if monitor is not None:
-        monitor(result)
-    return metrics_from_sums(model, sums, result, batch)
+STAGE = L.Stage(forward=pipeline_forward, loss_and_sums=loss_and_sums, metrics_from_sums=metrics_from_sums, metric_keys=metric_keys, task_space=True,
+                timing=("data_seconds", "seconds"), extras=lambda model: {"device_packs": model.arith.device_packs})
+training_step = functools.partial(L.training_step, STAGE)       # (model, batch, batch_idx=None)
+training_metrics = functools.partial(L.training_metrics, STAGE)  # (model, batch)
+train_step = functools.partial(L.train_step, STAGE)             # (model, optimizer, batch, monitor=None, reducer=None)
 
 
 # ------------------------------------------------------------------------------------------------ command line
 def build_parser():
-    from . import validate
     ap = validate.build_parser()
     ap.description = ("GarmentNets second-stage training (MI355X-native): ConvImplicitWNFPipeline behind a frozen PointNet2NOCS, with FusedAdam over the "
                       "train subset of a dataset store")
     ap.prog = "python -m garmentnets_amd.train_pipeline"
     ap.set_defaults(model="pipeline", batch_size=24, subset="train")
-    ap.add_argument("--epochs", type=int, default=1)
-    ap.add_argument("--learning_rate", type=float, default=None, help="default: the model's hyper-parameter")
-    ap.add_argument("--seed", type=int, default=0)
+    L.add_arguments(ap)
     ap.add_argument("--pointnet2_checkpoint", default=None,
                     help="Lightning-style .ckpt of a PointNet2NOCS: it becomes the model's first stage (and its pointnet2_params)")
     ap.add_argument("--host_packs", action="store_true",
@@ -185,8 +159,6 @@ def build_parser():
     ap.add_argument("--split_backward", action="store_true",
                     help="run the gradients of the UNet's 3x3x3 convolutions on the 16-bit matrix cores (arith.conv_grad_mode = 'f16x2': fp16 operand "
                          "planes, fp32 accumulation); default: the fp32 backward")
-    validate.add_resident_arguments(ap)
-    validate.add_monitor_arguments(ap)
     return ap
 
 
@@ -201,7 +173,7 @@ def load_model(a, device):
     """the model to train.  --checkpoint_path: that pipeline checkpoint; neither checkpoint: validate.load_model's seeded synthetic weights; only
     --pointnet2_checkpoint: the second-stage modules keep their constructors' initialisation (under torch.manual_seed(--seed)).  A
     --pointnet2_checkpoint replaces the first stage, and hparams["pointnet2_params"], in every case."""
-    from . import synthetic, validate
+    from . import synthetic
     from .networks.conv_implicit_wnf import ConvImplicitWNFPipeline
     from .networks.pointnet2_nocs import PointNet2NOCS
     if a.checkpoint_path or not a.pointnet2_checkpoint:
@@ -218,76 +190,14 @@ def load_model(a, device):
 
 
 def main(argv=None):
-    from . import parallel, validate, visualize
     a = parse_args(argv)
-    ranks = parallel.training_ranks(a.gpu_id)               # (one process: cuda:<gpu_id>; under torch.distributed.run: LOCAL_RANK's device, data-parallel)
-    device, chief = ranks.device, ranks.rank == 0
-    torch.cuda.set_device(device)
-    torch.manual_seed(a.seed + ranks.rank)
-    model = load_model(a, device).requires_grad_(True).train()
-    model.arith = model.arith.replace(device_packs=not a.host_packs)        # (train_step reads the model's arithmetic)
+    ranks = L.start(a)
+    model = load_model(a, ranks.device).requires_grad_(True).train()
+    model.arith = model.arith.replace(device_packs=not a.host_packs)        # (the step reads the model's arithmetic)
     if a.split_backward:
         model.arith = model.arith.replace(conv_grad_mode="f16x2")
-    if a.learning_rate is not None:
-        model.learning_rate = model.hparams["learning_rate"] = a.learning_rate
-    validate.apply_monitor_arguments(model, a)
-    optimizer = model.configure_optimizers()
-    a.subset = "train"                                      # (--static_epoch_seed: the same draws every epoch, for a reproducible run)
-    dataset = validate.make_dataset(a, volume_task_space=model.volume_task_space)
-    task = model.volume_task_space
-    reducer, indices, resident, val_resident = _data_parallel(model, optimizer, dataset, a, ranks, volume_task_space=task)
-    if chief:
-        os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
-    keys = metric_keys(model)
-    rows, epochs = [], []
-    for epoch in range(a.epochs):
-        order = validate.epoch_order(indices, a.shuffle, a.seed, epoch)
-        batches = resident.batches(order, a.batch_size) if a.resident else validate.host_batches(dataset, order, a.batch_size)
-        writer = visualize.epoch_writer(model, a.output_dir, epoch, True) if chief else None
-        batch_idx = 0
-        while a.num_batches is None or batch_idx < a.num_batches:
-            t0 = time.time()
-            item = next(batches, None)                      # host: read, sample and collate one batch; resident: draw, upload, launch
-            if item is None:
-                break
-            chunk, batch = item
-            t1 = time.time()
-            batch = batch.to(device)
-            metrics = train_step(model, optimizer, batch, _train_monitor(writer, batch_idx, batch), reducer=reducer)
-            row = {"epoch": epoch, "batch_idx": batch_idx, "garments": len(chunk), "data_seconds": t1 - t0, "seconds": time.time() - t1,
-                   "device_packs": model.arith.device_packs}
-            if ranks.world > 1:
-                row["world"] = ranks.world
-            if a.resident:
-                row["resident"] = True
-            row.update({"train_" + k: float(v) for k, v in metrics.items()})
-            rows.append(row)
-            if chief:
-                print(json.dumps(row))
-            batch_idx += 1
-        val = _validate(model, a, device, volume_task_space=task, resident=val_resident,
-                        hook=visualize.epoch_writer(model, a.output_dir, epoch, False) if chief else None, ranks=ranks)
-        epochs.append(dict(epoch=epoch, device_packs=model.arith.device_packs, **val))
-        if chief:
-            print(json.dumps(epochs[-1]))
-            torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()],
-                        "epoch": epoch}, os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
-    result = {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
-    if not chief:                                           # (rank 0 alone writes: the csv holds its own batches' metrics, the checkpoint its buffers)
-        return result
-    cols = (["epoch", "batch_idx", "garments", "data_seconds", "seconds"] + (["world"] if ranks.world > 1 else []) + (["resident"] if a.resident else []) +
-            ["train_" + k for k in keys])
-    with open(os.path.join(a.output_dir, "train_metrics.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=cols)
-        w.writeheader()
-        for r in rows:
-            w.writerow({k: r.get(k, "") for k in cols})
-    with open(os.path.join(a.output_dir, "val_epochs.json"), "w") as f:
-        json.dump(epochs, f, indent=2)
-    return result
+    return L.run(STAGE, model, a, ranks)
 
 
 if __name__ == "__main__":
-    main()
-    from . import parallel
-    parallel.finish()
+    L.command(main)

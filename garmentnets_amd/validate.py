@@ -90,52 +90,6 @@ def host_batches(dataset, indices, batch_size):
         yield chunk, GarmentInputDataset.collate([dataset[k] for k in chunk])
 
 
-def add_resident_arguments(ap):
-    """the training loops' data-source flags (train.py, train_pipeline.py)"""
-    ap.add_argument("--resident", action="store_true",
-                    help="read the train and the val subset once into device memory (io/resident.py) and assemble every batch there")
-    ap.add_argument("--resident_gib", type=float, default=None, help="device-memory budget of EACH resident subset; default: half of what is free")
-    ap.add_argument("--shuffle", action="store_true",
-                    help="visit the train subset in a RandomState(seed + epoch) permutation (the reference's train_dataloader: shuffle=True)")
-
-
-def add_monitor_arguments(ap):
-    """the training loops' monitor flags (train.py, train_pipeline.py): the reference's three hyper-parameters of vis_batch"""
-    ap.add_argument("--vis_per_items", type=int, default=None,
-                    help="draw every this-many-th garment of an epoch into <output_dir>/vis/epoch_<NNN>/ (0: none); default: the model's hyper-parameter")
-    ap.add_argument("--max_vis_per_epoch_train", type=int, default=None, help="at most this many train images per epoch; default: the model's")
-    ap.add_argument("--max_vis_per_epoch_val", type=int, default=None, help="at most this many val images per epoch; default: the model's")
-
-
-def apply_monitor_arguments(model, a):
-    """the three flags that were given replace the model's hyper-parameters (and travel in its checkpoints); the model learns the loop's batch size,
-    which get_vis_idxs numbers the garments of an epoch with"""
-    for key in ("vis_per_items", "max_vis_per_epoch_train", "max_vis_per_epoch_val"):
-        if getattr(a, key) is not None:
-            setattr(model, key, getattr(a, key))
-            model.hparams[key] = getattr(a, key)
-    model.batch_size = a.batch_size
-
-
-def epoch_order(indices, shuffle, seed, epoch):
-    """the order of the train subset in `epoch`"""
-    indices = np.asarray(indices)
-    return indices[np.random.RandomState(seed + epoch).permutation(len(indices))] if shuffle else indices
-
-
-def make_resident(a, dataset, subset, device, indices=None, rank=None):
-    """the subset of `dataset` as a ResidentDataset under --resident_gib; prints its one-off load time and footprint.  indices: this rank's share of
-    the subset (parallel.shard_indices) in place of all of it; the report of EVERY rank then carries its rank and its index list"""
-    from .io.resident import ResidentDataset
-    budget = None if a.resident_gib is None else int(a.resident_gib * 2 ** 30)
-    res = ResidentDataset(dataset, dataset.subset_indices(subset) if indices is None else indices, device, max_bytes=budget)
-    report = {"resident_subset": subset, "samples": len(res), "nbytes": res.nbytes, "load_seconds": res.load_seconds}
-    if rank is not None:
-        report.update(rank=rank, indices=res.indices)
-    print(json.dumps(report), flush=rank is not None)
-    return res
-
-
 def epoch_values(rows):
     """{key: garment-weighted mean} over the per-batch rows (dicts with "garments" and the val_* keys)"""
     w = np.array([r["garments"] for r in rows], dtype=np.float64)
@@ -182,7 +136,7 @@ def validation_rows(model, dataset, indices, batch_size, num_batches, device, lo
     """the validation loop: one row (batch_idx, garments, seconds, every val_* metric) per batch of `indices`, at most num_batches of them.
     batches: another source of (dataset indices, Batch) pairs than host_batches(dataset, indices, batch_size), e.g. ResidentDataset.batches(...).
     hook: called as hook(batch_idx, batch on the device, the model's forward of it) after each batch's metrics, which are then formed from that one
-    forward (the training loops' validation monitors)"""
+    forward (train_loop.py's validation monitors)"""
     rows = []
     for batch_idx, (chunk, batch) in enumerate(host_batches(dataset, indices, batch_size) if batches is None else batches):
         if num_batches is not None and batch_idx >= num_batches:

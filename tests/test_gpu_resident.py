@@ -314,9 +314,9 @@ def test_shuffled_resident_epochs_visit_the_permutation(train_store, tmp_path):
         out = TP.main(common + ["--output_dir", str(tmp_path / "s")])
     finally:
         ResidentDataset.batch = real
-    from garmentnets_amd import validate as V
+    from garmentnets_amd import train_loop as L
     assert len(out["train_rows"]) == 4
     train_idx = GarmentInputDataset(train_store[1], volume_size=int(train_store[3])).subset_indices("train")
-    want = [V.epoch_order(train_idx, True, 3, e)[:4].tolist() for e in range(2)]
+    want = [L.epoch_order(train_idx, True, 3, e)[:4].tolist() for e in range(2)]
     train_chunks = [c for c in seen if set(c) <= set(train_idx.tolist())]
     assert [sum(train_chunks[2 * e:2 * e + 2], []) for e in range(2)] == want and want[0] != want[1]

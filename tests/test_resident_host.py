@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from garmentnets_amd import train as T
+from garmentnets_amd import train_loop as L
 from garmentnets_amd import train_pipeline as TP
 from garmentnets_amd import validate as V
 from garmentnets_amd._lib import RESIDENT_META
@@ -168,12 +169,12 @@ def test_new_flags_default_off(mod):
 
 def test_shuffle_order_depends_on_seed_and_epoch_only():
     idx = np.arange(100, 140)
-    assert V.epoch_order(idx, False, 0, 3) is not None and np.array_equal(V.epoch_order(idx, False, 0, 3), idx)
-    a = V.epoch_order(idx, True, 2, 1)
-    assert np.array_equal(a, V.epoch_order(idx, True, 2, 1)) and np.array_equal(np.sort(a), idx)
+    assert L.epoch_order(idx, False, 0, 3) is not None and np.array_equal(L.epoch_order(idx, False, 0, 3), idx)
+    a = L.epoch_order(idx, True, 2, 1)
+    assert np.array_equal(a, L.epoch_order(idx, True, 2, 1)) and np.array_equal(np.sort(a), idx)
     assert np.array_equal(a, idx[np.random.RandomState(3).permutation(len(idx))])
-    assert not np.array_equal(a, V.epoch_order(idx, True, 2, 2)) and not np.array_equal(a, V.epoch_order(idx, True, 5, 1))
-    assert np.array_equal(a, V.epoch_order(idx, True, 1, 2))                                # RandomState(seed + epoch), as stated
+    assert not np.array_equal(a, L.epoch_order(idx, True, 2, 2)) and not np.array_equal(a, L.epoch_order(idx, True, 5, 1))
+    assert np.array_equal(a, L.epoch_order(idx, True, 1, 2))                                # RandomState(seed + epoch), as stated
 
 
 def test_validation_rows_takes_another_batch_source():
