@@ -100,6 +100,9 @@ PROTOTYPES = {
     "gn_winding_number_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],
     "gn_winding_field_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "gn_distance_field_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "gn_query_targets_face_chunk": [],
+    "gn_query_targets_workspace_bytes": [_i32, _i64, _i64, _i32],
+    "gn_query_targets_batch": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_nocs_bin_metrics_workspace_bytes": [_vp, _i32],
     "gn_nocs_bin_metrics": [_vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp],
     "gn_value_losses_workspace_bytes": [_vp, _i32],
@@ -146,6 +149,8 @@ PROTOTYPES = {
     "gn_resident_points": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_resident_garment": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_resident_volume": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "gn_resident_volume_queries": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_resident_query_targets": [_vp, _vp, _i32, _i64, _i32, _i64, _i64, _i32, _i32, _f32, _i32, _vp, _vp, _sz, _vp, _vp, _vp],
     "gn_resident_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "gn_resident_mc_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "gn_render_points_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
@@ -157,7 +162,8 @@ _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes
              "gn_grid_scatter_bwd_workspace_bytes": _sz, "gn_sa_gather_bwd_workspace_bytes": _sz, "gn_knn_interpolate_bwd_workspace_bytes": _sz,
              "gn_trilinear_sample_bwd_workspace_bytes": _sz, "gn_conv3d_bwd_weight_workspace_bytes": _sz, "gn_conv3d_bwd_weight_split_workspace_bytes": _sz, "gn_relu_mask_max_workspace_bytes": _sz, "gn_groupnorm_bwd_stats_workspace_bytes": _sz,
              "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz,
-             "gn_col_moments_workspace_bytes": _sz, "gn_col_dots_workspace_bytes": _sz, "gn_bn_train_bwd_workspace_bytes": _sz}
+             "gn_col_moments_workspace_bytes": _sz, "gn_col_dots_workspace_bytes": _sz, "gn_bn_train_bwd_workspace_bytes": _sz,
+             "gn_query_targets_workspace_bytes": _sz}
 
 LINEAR_BWD_CHUNK_ROWS = 512                     # GN_LINEAR_BWD_CHUNK_ROWS
 LINEAR_ACT_CHUNK_ROWS = 1024                    # GN_LINEAR_ACT_CHUNK_ROWS (gn_linear_act_bwd, gn_col_moments, gn_col_dots, gn_bn_train_bwd)
@@ -185,6 +191,9 @@ class LossGradSegment(ctypes.Structure):
     """GnLossGradSegment (host table entry of gn_value_losses_bwd)"""
     _fields_ = [("pred", _vp), ("target", _vp), ("grad", _vp), ("count", _i64), ("coef", _f64), ("kind", _i32), ("mirror", _i32)]
 
+
+QT_KINDS = {"nocs_winding_number_field": 0, "sim_nocs_winding_number_field": 0, "nocs_distance_field": 1, "nocs_signed_distance_field": 2,
+            "nocs_occupancy_grid": 3}             # GN_QT_*: the dataset's volume_group -> the kind of gn_query_targets_batch
 
 ADAM_CHUNK = 4096                               # GN_ADAM_CHUNK
 ADAM_MAX_HYPER = 16                             # GN_ADAM_MAX_HYPER

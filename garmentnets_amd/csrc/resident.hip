@@ -4,6 +4,7 @@
 //   gn_resident_points      the selected rows of the cloud -> x, y, pos (noise, rotation) and the batch vector
 //   gn_resident_garment     the per-garment fields: nearest selected point to the grip vertex (segmented arg-min), grip points, bookkeeping
 //   gn_resident_volume      volume queries (uniform | near the NOCS mesh) and the garment's own volume there (trilinear, ATen's CPU order)
+//   gn_resident_volume_queries  those queries alone (exact targets: gn_resident_query_targets of query_targets.hip takes the values from the mesh)
 //   gn_resident_surface     points of the garment mesh in query space and their targets
 //   gn_resident_mc_surface  points of the marching-cubes mesh and their on-surface flag
 //
@@ -208,14 +209,10 @@ __device__ __forceinline__ float res_trilinear(const float *__restrict__ vol, in
     return out;
 }
 
-__global__ __launch_bounds__(RES_WG) void resident_volume_kernel(GnResidentStore s, const int32_t *__restrict__ slots, int M, int n_uniform,
-                                                                 const float *__restrict__ uniform, const double *__restrict__ face_u,
-                                                                 const double *__restrict__ uv, const double *__restrict__ noise, const float *__restrict__ rot,
-                                                                 int occupancy, float *__restrict__ query, float *__restrict__ value) {
-    const int b = blockIdx.y, i = blockIdx.x * RES_WG + threadIdx.x;
-    const int64_t *m = res_meta(s, slots, b);
-    if (i >= M || m == nullptr) return;
-    float q[3];
+// volume query i of garment b (its meta row m): the first n_uniform are the uploaded uniform points; the others a point of the NOCS mesh plus noise (fp64),
+// rounded to fp32, clipped to [0, 1].  Shared by resident_volume_kernel and resident_volume_queries_kernel: the two form the same bits.
+__device__ __forceinline__ void res_volume_query(const GnResidentStore &s, const int64_t *m, int b, int i, int M, int n_uniform, const float *__restrict__ uniform,
+                                                 const double *__restrict__ face_u, const double *__restrict__ uv, const double *__restrict__ noise, float q[3]) {
     if (i < n_uniform) {
         const float *u = uniform + ((int64_t)b * n_uniform + i) * 3;
         q[0] = u[0];
@@ -232,6 +229,17 @@ __global__ __launch_bounds__(RES_WG) void resident_volume_kernel(GnResidentStore
             q[c] = fminf(fmaxf(v, 0.0f), 1.0f);
         }
     }
+}
+
+__global__ __launch_bounds__(RES_WG) void resident_volume_kernel(GnResidentStore s, const int32_t *__restrict__ slots, int M, int n_uniform,
+                                                                 const float *__restrict__ uniform, const double *__restrict__ face_u,
+                                                                 const double *__restrict__ uv, const double *__restrict__ noise, const float *__restrict__ rot,
+                                                                 int occupancy, float *__restrict__ query, float *__restrict__ value) {
+    const int b = blockIdx.y, i = blockIdx.x * RES_WG + threadIdx.x;
+    const int64_t *m = res_meta(s, slots, b);
+    if (i >= M || m == nullptr) return;
+    float q[3];
+    res_volume_query(s, m, b, i, M, n_uniform, uniform, face_u, uv, noise, q);
     float v = res_trilinear(s.volume + (int64_t)slots[b] * s.D * s.H * s.W, s.D, s.H, s.W, q);
     if (occupancy) v = v > 0.1f ? 1.0f : 0.0f;
     if (rot != nullptr) res_pivot_rot(rot + (int64_t)b * 9, q);    // after the values are taken
@@ -252,6 +260,44 @@ extern "C" int gn_resident_volume(const GnResidentStore *store, const int32_t *s
     hipLaunchKernelGGL(resident_volume_kernel, dim3((unsigned)gn_cdiv(M, RES_WG), (unsigned)B), dim3(RES_WG), 0, gn_stream(stream), *store, slots, M, n_uniform,
                        uniform, face_u, uv, noise, rot, occupancy, query, value);
     GN_LAUNCH_CHECK("gn_resident_volume");
+    return GN_OK;
+}
+
+// the queries of gn_resident_volume alone: `plain` (optional) before the turn, what gn_resident_query_targets (query_targets.hip) evaluates the mesh's own
+// field at; `query` as the batch carries them (turned about the pivot when rot is given)
+__global__ __launch_bounds__(RES_WG) void resident_volume_queries_kernel(GnResidentStore s, const int32_t *__restrict__ slots, int M, int n_uniform,
+                                                                         const float *__restrict__ uniform, const double *__restrict__ face_u,
+                                                                         const double *__restrict__ uv, const double *__restrict__ noise, const float *__restrict__ rot,
+                                                                         float *__restrict__ plain, float *__restrict__ query) {
+    const int b = blockIdx.y, i = blockIdx.x * RES_WG + threadIdx.x;
+    const int64_t *m = res_meta(s, slots, b);
+    if (i >= M || m == nullptr) return;
+    float q[3];
+    res_volume_query(s, m, b, i, M, n_uniform, uniform, face_u, uv, noise, q);
+    const int64_t o = (int64_t)b * M + i;
+    if (plain != nullptr) {
+        plain[o * 3] = q[0];
+        plain[o * 3 + 1] = q[1];
+        plain[o * 3 + 2] = q[2];
+    }
+    if (rot != nullptr) res_pivot_rot(rot + (int64_t)b * 9, q);
+    query[o * 3] = q[0];
+    query[o * 3 + 1] = q[1];
+    query[o * 3 + 2] = q[2];
+}
+
+extern "C" int gn_resident_volume_queries(const GnResidentStore *store, const int32_t *slots, int B, int M, int n_uniform, const float *uniform,
+                                          const double *face_u, const double *uv, const double *noise, const float *rot, float *plain, float *query,
+                                          void *stream) {
+    GN_REQUIRE(store != nullptr && B >= 1 && B <= 65535 && M >= 1 && n_uniform >= 0 && n_uniform <= M,
+               "gn_resident_volume_queries: 1 <= B <= 65535, 0 <= n_uniform <= M");
+    GN_REQUIRE(store->meta && slots && query && plain != query, "gn_resident_volume_queries: null pointer (or plain == query)");
+    GN_REQUIRE(n_uniform == 0 || uniform != nullptr, "gn_resident_volume_queries: the uniform points are required");
+    GN_REQUIRE(n_uniform == M || (face_u && uv && noise && store->cdf_nocs && store->faces && store->nocs_verts),
+               "gn_resident_volume_queries: near-surface queries need face_u, uv, noise and the resident NOCS mesh with its CDF");
+    hipLaunchKernelGGL(resident_volume_queries_kernel, dim3((unsigned)gn_cdiv(M, RES_WG), (unsigned)B), dim3(RES_WG), 0, gn_stream(stream), *store, slots, M,
+                       n_uniform, uniform, face_u, uv, noise, rot, plain, query);
+    GN_LAUNCH_CHECK("gn_resident_volume_queries");
     return GN_OK;
 }
 

@@ -15,77 +15,8 @@
 // LDS element (a broadcast) and each read serves WN_QPT queries.  Every query adds its faces in index order into its own register and is
 // written by its one owner: no atomics, no cross-thread reduction, so w(q) is a pure function of (q, mesh) -- whatever the launch geometry,
 // the other pairs of the table, or the tile size.
-#include <math.h>
-
-#include "common.h"
-
-#define WN_BLOCK 256
-#define WN_QPT 4
-#define WN_TILE 128
-#define WN_SPAN (WN_BLOCK * WN_QPT)
-#define WN_FOUR_PI 12.566370614359172             /* 4 * M_PI (a power-of-two multiple: exact) */
-
-__device__ __forceinline__ double wn_dot3(double ax, double ay, double az, double bx, double by, double bz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)), __dmul_rn(az, bz));
-}
-
-// the solid angle of the triangle (v0, v1, v2) seen from q
-__device__ __forceinline__ double wn_omega(double qx, double qy, double qz, double v0x, double v0y, double v0z, double v1x, double v1y, double v1z,
-                                           double v2x, double v2y, double v2z) {
-    const double ax = __dsub_rn(v0x, qx), ay = __dsub_rn(v0y, qy), az = __dsub_rn(v0z, qz);
-    const double bx = __dsub_rn(v1x, qx), by = __dsub_rn(v1y, qy), bz = __dsub_rn(v1z, qz);
-    const double cx = __dsub_rn(v2x, qx), cy = __dsub_rn(v2y, qy), cz = __dsub_rn(v2z, qz);
-    const double la = __dsqrt_rn(wn_dot3(ax, ay, az, ax, ay, az));
-    const double lb = __dsqrt_rn(wn_dot3(bx, by, bz, bx, by, bz));
-    const double lc = __dsqrt_rn(wn_dot3(cx, cy, cz, cx, cy, cz));
-    const double crx = __dsub_rn(__dmul_rn(by, cz), __dmul_rn(bz, cy));
-    const double cry = __dsub_rn(__dmul_rn(bz, cx), __dmul_rn(bx, cz));
-    const double crz = __dsub_rn(__dmul_rn(bx, cy), __dmul_rn(by, cx));
-    const double num = wn_dot3(ax, ay, az, crx, cry, crz);
-    const double dab = wn_dot3(ax, ay, az, bx, by, bz), dbc = wn_dot3(bx, by, bz, cx, cy, cz), dca = wn_dot3(cx, cy, cz, ax, ay, az);
-    double den = __dadd_rn(__dmul_rn(__dmul_rn(la, lb), lc), __dmul_rn(dab, lc));
-    den = __dadd_rn(den, __dmul_rn(dbc, la));
-    den = __dadd_rn(den, __dmul_rn(dca, lb));
-    return __dmul_rn(2.0, atan2(num, den));
-}
-
-// acc[k] += omega(q[k], face) over the nf faces of one mesh, in face order.  Called by the whole workgroup (it holds barriers).  A face with an
-// index outside [0, nv) sets *bad and is staged as three coincident points: its numerator is an exact zero, so it adds +-0.
-__device__ __forceinline__ void wn_accumulate(double (*tri)[WN_TILE], const double *__restrict__ V, int64_t nv, const int32_t *__restrict__ F, int64_t nf,
-                                              const double (&qx)[WN_QPT], const double (&qy)[WN_QPT], const double (&qz)[WN_QPT],
-                                              double (&acc)[WN_QPT], int64_t *__restrict__ bad) {
-    for (int64_t t0 = 0; t0 < nf; t0 += WN_TILE) {
-        const int n = (int)((nf - t0) < WN_TILE ? (nf - t0) : WN_TILE);
-        __syncthreads();
-        for (int j = threadIdx.x; j < n; j += WN_BLOCK) {
-            double p[9];
-            bool ok = true;
-            for (int k = 0; k < 3; ++k) {
-                const int32_t vi = F[3 * (t0 + j) + k];
-                const bool in = vi >= 0 && vi < nv;
-                ok = ok && in;
-                for (int c = 0; c < 3; ++c) p[3 * k + c] = in ? V[3 * (int64_t)vi + c] : 0.0;     // out of range: flagged, never read
-            }
-            if (!ok) *bad = 1;
-            for (int c = 0; c < 9; ++c) tri[c][j] = ok ? p[c] : 0.0;
-        }
-        __syncthreads();
-        for (int j = 0; j < n; ++j) {
-            const double v0x = tri[0][j], v0y = tri[1][j], v0z = tri[2][j];
-            const double v1x = tri[3][j], v1y = tri[4][j], v1z = tri[5][j];
-            const double v2x = tri[6][j], v2y = tri[7][j], v2z = tri[8][j];
-#pragma unroll
-            for (int k = 0; k < WN_QPT; ++k)
-                acc[k] = __dadd_rn(acc[k], wn_omega(qx[k], qy[k], qz[k], v0x, v0y, v0z, v1x, v1y, v1z, v2x, v2y, v2z));
-        }
-    }
-}
-
-// a pair / mesh that no workgroup walks still has its face indices checked (by its first workgroup): the wrapper raises on any bad index
-__device__ __forceinline__ void wn_check_faces(const int32_t *__restrict__ F, int64_t nf, int64_t nv, int64_t *__restrict__ bad) {
-    for (int64_t f = threadIdx.x; f < 3 * nf; f += WN_BLOCK)
-        if (F[f] < 0 || F[f] >= nv) *bad = 1;
-}
+// wn_omega / wn_accumulate / wn_check_faces and the WN_* sizes live in mesh_pair.h (query_targets.hip runs the same core).
+#include "mesh_pair.h"
 
 __global__ __launch_bounds__(WN_BLOCK) void winding_number_batch_kernel(const double *__restrict__ q, const double *__restrict__ verts,
                                                                         const int32_t *__restrict__ faces, const int64_t *__restrict__ pairs,

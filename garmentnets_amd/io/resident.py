@@ -10,6 +10,8 @@
                                               RandomState per stage; the chunk's draws go into one pinned buffer (draw_sections()) and up in one async copy;
                                               at most five gn_resident_* launches (csrc/resident.hip) do the selection, the target sampling, the ground-truth
                                               lookup and the augmentation.  Nothing is read back and the stream is not synchronised.
+  ResidentDataset(..., exact_targets=True)    holds no volume: gt_volume_value is the field of the garment's own resident mesh at the same query points
+                                              (targets.py; gn_resident_volume_queries + gn_resident_query_targets), so a store without a `volume` group trains.
 
 Not here: a device RNG (it would break the seeded contract validation relies on), fp16 volumes, eviction.
 """
@@ -19,7 +21,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib, ops, targets
 from ..batch import Batch
 from . import dataset as D
 
@@ -40,8 +42,9 @@ Layout = namedtuple("Layout", "arrays offsets nbytes staging_bytes")
 DrawLayout = namedtuple("DrawLayout", "sections nbytes")
 
 
-def held_arrays(num_volume_sample=0, num_surface_sample=0, num_mc_surface_sample=0, surface_sample_ratio=0, volume_task_space=False):
-    """the names of ARRAY_SPECS a dataset with these sampler settings needs resident"""
+def held_arrays(num_volume_sample=0, num_surface_sample=0, num_mc_surface_sample=0, surface_sample_ratio=0, volume_task_space=False, exact_targets=False):
+    """the names of ARRAY_SPECS a dataset with these sampler settings needs resident.  exact_targets: gt_volume_value comes from the mesh
+    (targets.py), so no volume is held; in task space the field is the one of the task-space vertices, which are then held."""
     near = num_volume_sample > 0 and surface_sample_ratio != 0
     surf = num_surface_sample > 0
     names = ["pc_sim", "pc_nocs", "pc_rgb", "sim_verts", "nocs_verts", "faces"]
@@ -49,9 +52,11 @@ def held_arrays(num_volume_sample=0, num_surface_sample=0, num_mc_surface_sample
         names.append("cdf_nocs")
     if surf and volume_task_space:
         names += ["task_verts", "cdf_task"]
+    elif exact_targets and num_volume_sample > 0 and volume_task_space:
+        names.append("task_verts")
     if num_mc_surface_sample > 0:
         names += ["mc_verts", "mc_flags", "mc_faces", "cdf_mc"]
-    if num_volume_sample > 0:
+    if num_volume_sample > 0 and not exact_targets:
         names.append("volume")
     return tuple(names)
 
@@ -144,6 +149,7 @@ def host_sample(dataset, idx, names):
         out["cdf_nocs"] = D.face_cdf(nocs, raw["cloth_faces_tri"])
     if "task_verts" in names:
         out["task_verts"] = _f32_verts(D.AABBGripNormalizer(dataset.cloth_sim_aabb)(sim), "the task-space normalised cloth_verts", idx)
+    if "cdf_task" in names:
         out["cdf_task"] = D.face_cdf(out["task_verts"], raw["cloth_faces_tri"])
     if "mc_verts" in names:
         mc = D.read_mc_mesh(group)
@@ -163,7 +169,9 @@ def host_sample(dataset, idx, names):
 
 
 class ResidentDataset:
-    def __init__(self, dataset, indices, device, max_bytes=None):
+    def __init__(self, dataset, indices, device, max_bytes=None, exact_targets=False):
+        """exact_targets: gt_volume_value is the field of the garment's own mesh at the query points (targets.py, gn_resident_query_targets) instead
+        of a trilinear sample of a stored volume: the store needs no `volume` group and none is read or held"""
         t0 = time.time()
         self.dataset, self.device = dataset, torch.device(device)
         self.indices = [int(k) for k in indices]
@@ -172,7 +180,11 @@ class ResidentDataset:
             raise AssertionError("random_rot_range must be (low, high)")
         if ds.num_mc_surface_sample > 0 and ds.num_surface_sample <= 0:
             raise ValueError("ResidentDataset: the mc-surface sampler draws num_surface_sample points; it is 0")
-        self.names = held_arrays(ds.num_volume_sample, ds.num_surface_sample, ds.num_mc_surface_sample, ds.surface_sample_ratio, ds.volume_task_space)
+        self.exact_targets = bool(exact_targets) and ds.num_volume_sample > 0
+        if self.exact_targets:
+            targets.check_kind(ds.volume_group)                      # ValueError naming the group
+        self.names = held_arrays(ds.num_volume_sample, ds.num_surface_sample, ds.num_mc_surface_sample, ds.surface_sample_ratio, ds.volume_task_space,
+                                 self.exact_targets)
         self.near = ds.num_volume_sample > 0 and ds.surface_sample_ratio != 0
         self.n_uniform = int(ds.num_volume_sample * ds.surface_sample_ratio) if self.near else ds.num_volume_sample
         counts = [sample_counts(ds, k, self.names) for k in self.indices]
@@ -185,6 +197,7 @@ class ResidentDataset:
         budget = max_bytes if max_bytes is not None else torch.cuda.mem_get_info(self.device)[0] // 2
         if self.nbytes > budget:
             raise ValueError(f"ResidentDataset: {len(self.indices)} samples need {self.nbytes} bytes of device memory, the budget is {int(budget)} bytes")
+        self.max_faces = max((int(c["faces"]) for c in counts), default=0)
         self._load(counts)
         self._slot = {k: i for i, k in enumerate(self.indices)}       # (a repeated index keeps its last copy)
         self._ring = [[None, None] for _ in range(DRAW_RING)]        # [pinned buffer, the event behind its last upload]
@@ -235,6 +248,8 @@ class ResidentDataset:
         self.arrays["grip"] = torch.from_numpy(grip).to(dev)
         self.arrays["aabb"] = torch.from_numpy(np.ascontiguousarray(self.dataset.cloth_sim_aabb, dtype=np.float32).reshape(6)).to(dev)
         self.store = ops.resident_store(self.arrays, self.volume_shape)
+        # gn_resident_query_targets' flags: never read back (host_sample refuses a face index outside its mesh at load), not counted in nbytes
+        self._qt_bad = torch.zeros(2, dtype=torch.int64, device=dev) if self.exact_targets else None
 
     # ------------------------------------------------------------------------------------------------ draws
     def draw_layout(self, B):
@@ -305,8 +320,17 @@ class ResidentDataset:
             if ds.num_volume_sample > 0:
                 M = ds.num_volume_sample
                 out.update(volume_query_points=new(B, M, 3), gt_volume_value=new(B, M))
-                ops.resident_volume(self.store, d["slots"], d["vol_uniform"], d.get("vol_face_u"), d.get("vol_uv"), d.get("vol_noise"), rot if task else None,
-                                    ds.volume_group == "nocs_occupancy_grid", out["volume_query_points"], out["gt_volume_value"])
+                turn = rot if task else None
+                if self.exact_targets:                                 # the same queries; the values from the mesh, taken before the queries turn
+                    plain = new(B, M, 3) if turn is not None else None
+                    ops.resident_volume_queries(self.store, d["slots"], d["vol_uniform"], d.get("vol_face_u"), d.get("vol_uv"), d.get("vol_noise"), turn,
+                                                plain, out["volume_query_points"])
+                    ops.resident_query_targets(self.store, d["slots"], out["volume_query_points"] if plain is None else plain, task,
+                                               int(self.layout.offsets["verts"][-1]), self.max_faces, ds.volume_group, ds.tsdf_clip_value,
+                                               ds.volume_absolute_value, out["gt_volume_value"], self._qt_bad)
+                else:
+                    ops.resident_volume(self.store, d["slots"], d["vol_uniform"], d.get("vol_face_u"), d.get("vol_uv"), d.get("vol_noise"), turn,
+                                        ds.volume_group == "nocs_occupancy_grid", out["volume_query_points"], out["gt_volume_value"])
             if ds.num_surface_sample > 0:
                 M = ds.num_surface_sample
                 out.update(surf_query_points=new(B, M, 3), gt_sim_points=new(B, M, 3))

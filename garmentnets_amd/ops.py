@@ -1317,6 +1317,62 @@ def distance_field_batch(meshes, shape):
     return d2, face_idx
 
 
+def _qt_kind(kind, who):
+    if kind not in _lib.QT_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r}; expected one of {sorted(_lib.QT_KINDS)}")
+    return _lib.QT_KINDS[kind]
+
+
+def _qt_bad(bad, who):
+    index, short = (int(v) for v in bad.tolist())                    # one host synchronisation
+    if short:
+        raise _lib.GarmentNetsHipError(f"{who}: a mesh has more faces than the max_nf the workspace was sized for")
+    if index:
+        raise IndexError(f"{who}: a face index is out of bounds for its mesh's vertices")
+
+
+def query_targets_batch(queries, meshes, kind, tsdf_clip_value=None, absolute=False, return_fp64=False):
+    """the float32 training target of volume_group `kind` at queries (B, M, 3) fp32, garment b against meshes[b] = (verts fp32 (V, 3), faces (F, 3)), from
+    the meshes alone: two launches of gn_query_targets_batch -> target (B, M) float32; return_fp64: (target, w, d2, face_idx) with w, d2 float64 (B, M) and
+    face_idx int32 (B, M), None for what `kind` does not compute.  garmentnets_amd/targets.py has the definition: w is winding_number_batch's sum cut into
+    chunks of QT_FACE_CHUNK faces (its bits when F <= QT_FACE_CHUNK), (d2, face_idx) are point_mesh_sqdist_batch's bits; then tsdf_clip_value and
+    absolute as the dataset's data_io applies them.  A face index outside [0, V) raises IndexError (after the launch: one host synchronisation)."""
+    code = _qt_kind(kind, "query_targets_batch")
+    queries = _chk(queries, torch.float32, "queries")
+    if queries.dim() != 3 or queries.shape[2] != 3:
+        raise ValueError(f"queries: expected a (B, M, 3) tensor, got {tuple(queries.shape)}")
+    B, M = int(queries.shape[0]), int(queries.shape[1])
+    if len(meshes) != B:
+        raise ValueError("query_targets_batch: one mesh per query set")
+    dev = queries.device
+    need_w, need_d = kind != "nocs_distance_field", code in (1, 2)
+    target = torch.empty((B, M), dtype=torch.float32, device=dev)
+    w = torch.empty((B, M), dtype=torch.float64, device=dev) if return_fp64 and need_w else None
+    d2 = torch.empty((B, M), dtype=torch.float64, device=dev) if return_fp64 and need_d else None
+    face_idx = torch.empty((B, M), dtype=_i32, device=dev) if return_fp64 and need_d else None
+    if B:
+        verts = []
+        for v, _ in meshes:
+            if v.dim() != 2 or v.shape[1] != 3:
+                raise ValueError(f"verts: expected an (N, 3) tensor, got {tuple(v.shape)}")
+            verts.append(_chk(v.contiguous(), torch.float32, "verts"))
+        faces = [_faces_i32(f) for _, f in meshes]
+        v, vo = _cat_sets(verts, "verts", dtype=torch.float32, dedup=False)
+        f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
+        if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+            raise ValueError("query_targets_batch: more than 2^31 vertices or faces")
+        csr = _pairs_table([(vo[k], fo[k]) for k in range(B)] + [(v.shape[0], f.shape[0])], dev)
+        max_nf = max(int(x.shape[0]) for x in faces)
+        nbytes = _lib.load().gn_query_targets_workspace_bytes(B, M, max_nf, code)
+        ws = _ws(nbytes, dev)
+        bad = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.call("gn_query_targets_batch", _p(queries), _p(v), _p(f), _p(csr), B, M, max_nf, code, int(tsdf_clip_value is not None),
+                  float(tsdf_clip_value) if tsdf_clip_value is not None else 0.0, int(bool(absolute)), _p(ws), nbytes, _p(target), _p(w), _p(d2),
+                  _p(face_idx), _p(bad), _stream())
+        _qt_bad(bad, "query_targets")
+    return (target, w, d2, face_idx) if return_fp64 else target
+
+
 # ------------------------------------------------------------------------------------------------ validation losses
 def _check_sets(n):
     if not 1 <= n <= _lib.LOSS_MAX_SETS:
@@ -1982,6 +2038,27 @@ def resident_volume(store, slots, uniform, face_u, uv, noise, rot, occupancy, qu
     _lib.call("gn_resident_volume", _res(store), _p(slots), B, M, uniform.shape[1], _p(_chk(uniform, torch.float32, "uniform")),
               _p(None if face_u is None else _chk(face_u, torch.float64, "face_u")), _p(None if uv is None else _chk(uv, torch.float64, "uv")),
               _p(None if noise is None else _chk(noise, torch.float64, "noise")), _p(rot), int(bool(occupancy)), _p(query), _p(value), _stream())
+
+
+def resident_volume_queries(store, slots, uniform, face_u, uv, noise, rot, plain, query):
+    """gn_resident_volume_queries: the queries of resident_volume alone, query (B, M, 3) written in place; plain (B, M, 3) or None: the queries before `rot`"""
+    B, M = query.shape[0], query.shape[1]
+    _lib.call("gn_resident_volume_queries", _res(store), _p(slots), B, M, uniform.shape[1], _p(_chk(uniform, torch.float32, "uniform")),
+              _p(None if face_u is None else _chk(face_u, torch.float64, "face_u")), _p(None if uv is None else _chk(uv, torch.float64, "uv")),
+              _p(None if noise is None else _chk(noise, torch.float64, "noise")), _p(rot), _p(None if plain is None else _chk(plain, torch.float32, "plain")),
+              _p(_chk(query, torch.float32, "query")), _stream())
+
+
+def resident_query_targets(store, slots, query, task_space, total_verts, max_nf, kind, tsdf_clip_value, absolute, value, bad):
+    """gn_resident_query_targets: value (B, M) fp32 written in place = the target of volume_group `kind` at query (B, M, 3), garment b against the resident
+    mesh of slots[b] (task_space: its task-space vertices); bad int64 (2,), zeroed by the caller, stays on the device: nothing is read back here"""
+    B, M = value.shape
+    code = _qt_kind(kind, "resident_query_targets")
+    nbytes = _lib.load().gn_query_targets_workspace_bytes(B, M, int(max_nf), code)
+    ws = _ws(nbytes, value.device)
+    _lib.call("gn_resident_query_targets", _res(store), _p(slots), B, M, int(bool(task_space)), int(total_verts), int(max_nf), code,
+              int(tsdf_clip_value is not None), float(tsdf_clip_value) if tsdf_clip_value is not None else 0.0, int(bool(absolute)),
+              _p(_chk(query, torch.float32, "query")), _p(ws), nbytes, _p(_chk(value, torch.float32, "value")), _p(_chk(bad, torch.int64, "bad")), _stream())
 
 
 def resident_surface(store, slots, face_u, uv, task_space, rot, query, target):

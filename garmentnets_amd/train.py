@@ -146,7 +146,8 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = L.check_arguments(ap, ap.parse_args(argv))
     if a.model == "pipeline":
         raise SystemExit("not implemented yet: second-stage training step")
     return a

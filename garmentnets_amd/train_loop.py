@@ -9,7 +9,7 @@ forward, its loss, its own flags and its model's set-up.  Nothing here asks whic
                                         zero_grad -> forward -> loss -> backward -> reducer.reduce() -> optimizer.step() -> monitor(result), then the
                                         metrics from the sums of that one forward; nothing is read back between forward and backward
   training_step / training_metrics      the loss with its graph, and the logged values, of one batch
-  add_arguments(ap)                     --epochs, --learning_rate, --seed, the data-source flags (--resident, --resident_gib, --shuffle) and the monitor
+  add_arguments(ap)                     --epochs, --learning_rate, --seed, the data-source flags (--resident, --resident_gib, --exact_targets, --shuffle) and the monitor
                                         flags (--vis_per_items, --max_vis_per_epoch_train, --max_vis_per_epoch_val)
   start(a)                              parallel.training_ranks, the device, torch.manual_seed(seed + rank): what precedes the model's construction
   run(stage, model, a, ranks)           the learning-rate override, the monitor arguments, the optimizer, the train dataset, the data-parallel set-up;
@@ -105,6 +105,9 @@ def add_arguments(ap):
     ap.add_argument("--resident", action="store_true",
                     help="read the train and the val subset once into device memory (io/resident.py) and assemble every batch there")
     ap.add_argument("--resident_gib", type=float, default=None, help="device-memory budget of EACH resident subset; default: half of what is free")
+    ap.add_argument("--exact_targets", action="store_true", default=argparse.SUPPRESS,      # (absent from the namespace unless given: exact_targets(a))
+                    help="with --resident: take gt_volume_value from the garment's own mesh at the query points (targets.py) instead of a stored volume; "
+                         "the store then needs no `volume` group")
     ap.add_argument("--shuffle", action="store_true",
                     help="visit the train subset in a RandomState(seed + epoch) permutation (the reference's train_dataloader: shuffle=True)")
     # the reference's three hyper-parameters of vis_batch
@@ -112,6 +115,18 @@ def add_arguments(ap):
                     help="draw every this-many-th garment of an epoch into <output_dir>/vis/epoch_<NNN>/ (0: none); default: the model's hyper-parameter")
     ap.add_argument("--max_vis_per_epoch_train", type=int, default=None, help="at most this many train images per epoch; default: the model's")
     ap.add_argument("--max_vis_per_epoch_val", type=int, default=None, help="at most this many val images per epoch; default: the model's")
+
+
+def exact_targets(a):
+    """--exact_targets of a parsed namespace"""
+    return bool(getattr(a, "exact_targets", False))
+
+
+def check_arguments(ap, a):
+    """what the flags of add_arguments owe each other, as an argparse error of `ap`"""
+    if exact_targets(a) and not a.resident:
+        ap.error("--exact_targets requires --resident: the exact targets are built on the device from the resident meshes")
+    return a
 
 
 def apply_monitor_arguments(model, a):
@@ -135,8 +150,11 @@ def make_resident(a, dataset, subset, device, indices=None, rank=None):
     the subset (parallel.shard_indices) in place of all of it; the report of EVERY rank then carries its rank and its index list"""
     from .io.resident import ResidentDataset
     budget = None if a.resident_gib is None else int(a.resident_gib * 2 ** 30)
-    res = ResidentDataset(dataset, dataset.subset_indices(subset) if indices is None else indices, device, max_bytes=budget)
+    exact = exact_targets(a)
+    res = ResidentDataset(dataset, dataset.subset_indices(subset) if indices is None else indices, device, max_bytes=budget, exact_targets=exact)
     report = {"resident_subset": subset, "samples": len(res), "nbytes": res.nbytes, "load_seconds": res.load_seconds}
+    if exact:
+        report["exact_targets"] = res.exact_targets
     if rank is not None:
         report.update(rank=rank, indices=res.indices)
     print(json.dumps(report), flush=rank is not None)
@@ -202,20 +220,20 @@ def _train_monitor(writer, batch_idx, batch):
 
 
 # ------------------------------------------------------------------------------------------------ rows, columns, the loop
-def _flags(world, resident):
-    """a row's entries that only a data-parallel and only a --resident run have"""
-    return {**({"world": world} if world > 1 else {}), **({"resident": True} if resident else {})}
+def _flags(world, resident, exact_targets=False):
+    """a row's entries that only a data-parallel, only a --resident and only an --exact_targets run have"""
+    return {**({"world": world} if world > 1 else {}), **({"resident": True} if resident else {}), **({"exact_targets": True} if exact_targets else {})}
 
 
-def train_row(stage, model, epoch, batch_idx, garments, seconds, world, resident, metrics):
+def train_row(stage, model, epoch, batch_idx, garments, seconds, world, resident, metrics, exact_targets=False):
     """the printed row of one step, in its key order.  seconds: {"data_seconds": .., "seconds": ..}, of which the stage's timing columns are kept"""
     return {"epoch": epoch, "batch_idx": batch_idx, "garments": garments, **{k: seconds[k] for k in stage.timing}, **stage.extras(model),
-            **_flags(world, resident), **{"train_" + k: float(v) for k, v in metrics.items()}}
+            **_flags(world, resident, exact_targets), **{"train_" + k: float(v) for k, v in metrics.items()}}
 
 
-def csv_columns(stage, model, world, resident):
+def csv_columns(stage, model, world, resident, exact_targets=False):
     """train_metrics.csv's columns: a row's keys without the stage's extras"""
-    return ["epoch", "batch_idx", "garments", *stage.timing, *_flags(world, resident), *("train_" + k for k in stage.metric_keys(model))]
+    return ["epoch", "batch_idx", "garments", *stage.timing, *_flags(world, resident, exact_targets), *("train_" + k for k in stage.metric_keys(model))]
 
 
 def _write_outputs(output_dir, cols, rows, epochs):
@@ -248,6 +266,7 @@ def run(stage, model, a, ranks):
     task = model.volume_task_space if stage.task_space else False
     dataset = validate.make_dataset(a, volume_task_space=task)
     reducer, indices, resident, val_resident = _data_parallel(model, optimizer, dataset, a, ranks, volume_task_space=task)
+    exact = resident is not None and resident.exact_targets  # (--exact_targets where the stage samples volume queries at all)
     if chief:
         os.makedirs(os.path.join(a.output_dir, "checkpoints"), exist_ok=True)
     rows, epochs = [], []
@@ -266,7 +285,7 @@ def run(stage, model, a, ranks):
             batch = batch.to(device)
             metrics = train_step(stage, model, optimizer, batch, _train_monitor(writer, batch_idx, batch), reducer=reducer)
             seconds = {"data_seconds": t1 - t0, "seconds": time.time() - t1}
-            rows.append(train_row(stage, model, epoch, batch_idx, len(chunk), seconds, ranks.world, a.resident, metrics))
+            rows.append(train_row(stage, model, epoch, batch_idx, len(chunk), seconds, ranks.world, a.resident, metrics, exact))
             if chief:
                 print(json.dumps(rows[-1]))
             batch_idx += 1
@@ -278,7 +297,7 @@ def run(stage, model, a, ranks):
             torch.save({"state_dict": model.state_dict(), "hyper_parameters": model.hparams, "optimizer_states": [optimizer.state_dict()],
                         "epoch": epoch}, os.path.join(a.output_dir, "checkpoints", "last.ckpt"))
     if chief:                                               # (rank 0 alone writes: the csv holds its own batches' metrics, the checkpoint its buffers)
-        _write_outputs(a.output_dir, csv_columns(stage, model, ranks.world, a.resident), rows, epochs)
+        _write_outputs(a.output_dir, csv_columns(stage, model, ranks.world, a.resident, exact), rows, epochs)
     return {"model": model, "optimizer": optimizer, "train_rows": rows, "val_epochs": epochs, "resident": resident, "val_resident": val_resident}
 
 

@@ -163,7 +163,8 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = L.check_arguments(ap, ap.parse_args(argv))
     if a.model != "pipeline":
         raise SystemExit("garmentnets_amd.train_pipeline trains the pipeline model; the first stage's step is python -m garmentnets_amd.train")
     return a

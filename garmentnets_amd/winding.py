@@ -49,6 +49,12 @@ def _mesh_arrays(verts, faces):
 def winding_number_reference(queries, verts, faces):
     """w(q) of the definition above for every row of `queries` (M, 3) -> (M,) float64.  numpy, fp64, the faces summed sequentially in index
     order (np.cumsum adds one element after the other)."""
+    return solid_angle_sum_reference(queries, verts, faces) / FOUR_PI
+
+
+def solid_angle_sum_reference(queries, verts, faces):
+    """0 + omega_0 + omega_1 + ... in face-index order for every row of `queries` (M, 3) -> (M,) float64: winding_number_reference before its division
+    by 4 pi (targets.query_targets_reference adds these per chunk of faces)"""
     queries = np.asarray(queries, dtype=np.float64)
     if queries.ndim != 2 or queries.shape[1] != 3:
         raise ValueError(f"queries: expected an (M, 3) array, got {queries.shape}")
@@ -67,7 +73,7 @@ def winding_number_reference(queries, verts, faces):
         dab, dbc, dca = _dot(a, b), _dot(b, c), _dot(c, a)
         den = (((la * lb) * lc + dab * lc) + dbc * la) + dca * lb
         omega = 2.0 * np.arctan2(num, den)
-        out[s:s + step] = (0.0 + np.cumsum(omega, axis=1)[:, -1]) / FOUR_PI
+        out[s:s + step] = 0.0 + np.cumsum(omega, axis=1)[:, -1]
     return out
 
 

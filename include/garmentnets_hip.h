@@ -584,6 +584,45 @@ int gn_distance_field_batch(const double *verts, const int32_t *faces, const int
                             int32_t *face_idx, double *d2, int64_t *bad, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Exact volume targets at query points (csrc/query_targets.hip; DESIGN.md "Exact volume targets"; garmentnets_amd/targets.py restates it in numpy):
+ * the second stage's gt_volume_value from the garment's mesh alone, for "few queries, many faces" (a training batch: 24 x 6000 queries, ~10 000 faces).
+ * A query's fp32 coordinates and the fp32 vertices are widened exactly to fp64; the per-pair arithmetic is gn_winding_number_batch's and
+ * gn_point_mesh_sqdist_batch's.  The faces are cut into chunks of GN_QT_FACE_CHUNK consecutive faces (the second grid dimension):
+ *     w        each chunk's solid angles added in face order from 0, the chunk sums added in ascending chunk order from 0, the total divided by 4 pi:
+ *              the bits of gn_winding_number_batch when F <= GN_QT_FACE_CHUNK, within F * 2^-50 of it otherwise;
+ *     d2, face the strict `<` minimum in face order per chunk, then over ascending chunks: the bits of gn_point_mesh_sqdist_batch for every F.
+ * With w32 = float(w), the float32 target of `kind`:
+ *     GN_QT_WINDING          w32
+ *     GN_QT_DISTANCE         float(sqrt(d2)), the root in fp64
+ *     GN_QT_SIGNED_DISTANCE  float(clip(1 - 2 * double(w32), -1, 1) * sqrt(d2))
+ *     GN_QT_OCCUPANCY        w32 > 0.5f ? 1 : 0
+ * then, with use_clip != 0, clip(v / tsdf_clip, -1, 1) (one fp32 division) and, with absolute != 0, |v|: the dataset's data_io steps in their order.
+ * An empty mesh gives w = 0, d2 = +inf, face = -1; a NaN query gives NaN (occupancy: 0).  Only the kinds that read w compute solid angles, only those that
+ * read d2 compute distances.  One partial per (query, chunk) goes to the workspace and a second launch folds them in ascending chunk order: no atomics, one
+ * writer per value, identical calls give identical bits, and a query's result does not depend on B, M, the grid or what else the launch carries.
+ * ------------------------------------------------------------------------------------------------------- */
+#define GN_QT_FACE_CHUNK 512         /* faces per chunk: a compile-time constant that depends on nothing but itself */
+#define GN_QT_WINDING 0              /* volume_group nocs_winding_number_field, sim_nocs_winding_number_field */
+#define GN_QT_DISTANCE 1             /* nocs_distance_field */
+#define GN_QT_SIGNED_DISTANCE 2      /* nocs_signed_distance_field */
+#define GN_QT_OCCUPANCY 3            /* nocs_occupancy_grid */
+
+/* GN_QT_FACE_CHUNK of the built library (what garmentnets_amd/targets.py chunks its numpy sum by) */
+int gn_query_targets_face_chunk(void);
+/* bytes of workspace for B query sets of M queries against meshes of at most max_nf faces: B * max(1, cdiv(max_nf, GN_QT_FACE_CHUNK)) * M * (8 for w + 12
+ * for (d2, face), as `kind` reads them); 0 for an unknown kind or an empty launch */
+size_t gn_query_targets_workspace_bytes(int B, int64_t M, int64_t max_nf, int kind);
+/* query [B][M][3] fp32; verts [*][3] fp32, faces [*][3] int32 and mesh_csr [B + 1][2] int64 on the device as gn_winding_field_batch reads them (mesh b owns
+ * the vertex rows v_off[b] .. v_off[b+1] - 1 and the face rows f_off[b] .. f_off[b+1] - 1, its face indices relative to v_off[b]); max_nf >= the largest
+ * face count.  target [B][M] fp32; w, d2 [B][M] fp64 and face_idx [B][M] int32 (relative to the mesh's first face): optional (NULL), written when `kind`
+ * computes them.  bad [2] int64 (caller zeroes it): bad[0] = 1 when a face index lies outside [0, nv) (never dereferenced), bad[1] = 1 when a mesh has
+ * more than max_nf faces (it is then not walked).  Refused by name before any launch: null pointers, an unknown kind, a short workspace, B > 65535,
+ * M >= 2^31, max_nf > 65535 * GN_QT_FACE_CHUNK. */
+int gn_query_targets_batch(const float *query, const float *verts, const int32_t *faces, const int64_t *mesh_csr, int B, int64_t M, int64_t max_nf, int kind,
+                           int use_clip, float tsdf_clip, int absolute, void *ws, size_t ws_bytes, float *target, double *w, double *d2, int32_t *face_idx,
+                           int64_t *bad, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Validation losses (networks/pointnet2_nocs.py:257-440, networks/conv_implicit_wnf.py:405-452).
  * Per-element terms in fp32 as torch computes them; sums in fp64.  Deterministic: one plain store of a partial per workgroup into ws,
  * then a fold launch in a fixed order (no atomics: two identical calls give identical bits).  The set / segment tables are HOST arrays
@@ -910,6 +949,15 @@ int gn_resident_garment(const GnResidentStore *store, const int32_t *slots, int 
  * (0.5, 0.5, 0) AFTER the values are taken (task space). */
 int gn_resident_volume(const GnResidentStore *store, const int32_t *slots, int B, int M, int n_uniform, const float *uniform, const double *face_u,
                        const double *uv, const double *noise, const float *rot, int occupancy, float *query, float *value, void *stream);
+/* the M queries of gn_resident_volume alone, bit for bit (exact targets: the store holds no volume).  plain [B][M][3] or NULL: the queries before `rot`
+ * turns them, what gn_resident_query_targets evaluates; query [B][M][3]: turned about (0.5, 0.5, 0) when rot != NULL, else the plain ones. */
+int gn_resident_volume_queries(const GnResidentStore *store, const int32_t *slots, int B, int M, int n_uniform, const float *uniform, const double *face_u,
+                               const double *uv, const double *noise, const float *rot, float *plain, float *query, void *stream);
+/* gn_query_targets_batch on the resident meshes: garment b is sample slots[b], its faces store->faces and its vertices store->nocs_verts (task_space != 0:
+ * store->task_verts) through the store's own meta rows; total_verts: the rows of the store's vertex arrays; query [B][M][3] (un-turned), value [B][M]. */
+int gn_resident_query_targets(const GnResidentStore *store, const int32_t *slots, int B, int64_t M, int task_space, int64_t total_verts, int64_t max_nf,
+                              int kind, int use_clip, float tsdf_clip, int absolute, const float *query, void *ws, size_t ws_bytes, float *value,
+                              int64_t *bad, void *stream);
 /* M points of the garment mesh per garment: query [B][M][3] from the NOCS vertices and target from the simulation vertices (rot turns the target); task_space
  * != 0: faces by cdf_task, query from task_verts (rot turns it about (0.5, 0.5, 0)), target from the NOCS vertices */
 int gn_resident_surface(const GnResidentStore *store, const int32_t *slots, int B, int M, const double *face_u, const double *uv, int task_space,

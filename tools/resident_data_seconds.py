@@ -7,6 +7,7 @@
   --summarise_csv CSV         the medians of a train_metrics.csv of `python -m garmentnets_amd.train_pipeline` (of any commit: the parent's host run)
   --resident_run STORE        train_pipeline with --resident over STORE (two epochs, batch 24, 6000 / 6000 / 6000), its medians, the one-off load time and
                               nbytes, and the summed device time of the gn_resident_* launches of a batch, each launch between two events on the stream
+  --exact_targets             with --resident_run: the run takes gt_volume_value from the meshes (--exact_targets; the store's volumes are not read)
 Every mode prints one JSON object; --out FILE merges it into FILE under --label.  Not a test and not read by bench.py.  The runs need a GPU."""
 import argparse
 import csv
@@ -21,7 +22,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 RUN_ARGS = ["--epochs", "2", "--batch_size", "24", "--num_pc_sample", "6000", "--num_volume_sample", "6000", "--num_surface_sample", "6000"]
-LAUNCHES = ("resident_points", "resident_garment", "resident_volume", "resident_surface", "resident_mc_surface")
+LAUNCHES = ("resident_points", "resident_garment", "resident_volume", "resident_volume_queries", "resident_query_targets", "resident_surface",
+            "resident_mc_surface")
 
 
 def write_store(path, samples=48, views=(8000,) * 4, verts=5000, faces=10000, volume=128, seed=0):
@@ -59,11 +61,12 @@ def medians(rows):
             "seconds_median": statistics.median(f("seconds")), "data_seconds": f("data_seconds"), "seconds": f("seconds")}
 
 
-def resident_run(store, output_dir):
+def resident_run(store, output_dir, exact_targets=False):
     import torch
     from garmentnets_amd import ops, train_pipeline
-    res = train_pipeline.main(["--zarr_in", store, "--output_dir", output_dir, "--resident"] + RUN_ARGS)
+    res = train_pipeline.main(["--zarr_in", store, "--output_dir", output_dir, "--resident"] + (["--exact_targets"] if exact_targets else []) + RUN_ARGS)
     out = medians(res["train_rows"])
+    out["exact_targets"] = bool(exact_targets)
     resident, val = res["resident"], res["val_resident"]
     out.update({"load_seconds": resident.load_seconds, "nbytes": resident.nbytes, "val_load_seconds": val.load_seconds, "val_nbytes": val.nbytes,
                 "device": torch.cuda.get_device_name(0)})
@@ -104,6 +107,7 @@ def main():
     ap.add_argument("--write_store", default=None)
     ap.add_argument("--summarise_csv", default=None)
     ap.add_argument("--resident_run", default=None)
+    ap.add_argument("--exact_targets", action="store_true")
     ap.add_argument("--output_dir", default="resident_run_out")
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
@@ -115,7 +119,7 @@ def main():
     elif a.summarise_csv:
         result = medians(list(csv.DictReader(open(a.summarise_csv))))
     elif a.resident_run:
-        result = resident_run(a.resident_run, a.output_dir)
+        result = resident_run(a.resident_run, a.output_dir, a.exact_targets)
     else:
         raise SystemExit("one of --write_store, --summarise_csv, --resident_run")
     result["clock"] = time.strftime("%Y-%m-%d %H:%M:%S %Z")
