@@ -710,6 +710,11 @@ def test_conv3d_split_wide_variant_against_torch(C0, C1, Cout, dims, planes):
     a, d = ops.groupnorm_affine(ops.channel_stats(s0), None if s1 is None else ops.channel_stats(s1), 8, 1e-5, gamma.to(DEV), beta.to(DEV))
     out32 = ops.conv3d_gcr(s0, s1, a, d, ops.pack_conv_weight(w).to(DEV), Cout).permute(0, 4, 1, 2, 3).cpu().double()
     out, (osum, osq, V) = ops.conv3d_gcr_split(s0, s1, a, d, ops.pack_conv_weight_split(w, planes).to(DEV), Cout, with_stats=True)
+    # the variant the shape was chosen for is the one that ran (the tall-tile x-strip kernel reads one full-resolution source: the 32-wide case with an
+    # upsampled source stays on conv3d_split_kernel<1>, at a large workgroup count)
+    f16 = "true" if planes == 4 else "false"
+    want = f"conv3d_split_wide_kernel<2, {f16}>" if Cout % 128 == 0 else f"conv3d_split_strip_kernel<{f16}>" if C1 == 0 else f"conv3d_split_kernel<1, 2, {f16}>"
+    assert ops._lib.load().gn_last_kernel().decode() == want
     got = out.permute(0, 4, 1, 2, 3).cpu().double()
     e_split, e_f32 = (got - ref64).abs().max().item(), (out32 - ref64).abs().max().item()
     print(f"wide mode {planes}: err vs fp64 {e_split:.2e} (fp32-MFMA kernel {e_f32:.2e})")
