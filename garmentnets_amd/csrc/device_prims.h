@@ -96,6 +96,9 @@ __device__ __forceinline__ float gn_resid_hi(unsigned h2, float r) {
 
 // four floats -> P 16-bit planes (exact residual chain x = x1 + x2 [+ x3], xi = fp16_rn / bf16_rn of the running residual), each plane
 // packed as 4 x 16 bit = uint2.  v_cvt_pk_bf16_f32 rounds to nearest even like the host-side pack of the weights.
+// The staging step AROUND it (affine, zero padding after the affine, this split, the store of P planes) is written out at each of its four sites in
+// unet_split.hip ON PURPOSE: as one inlined function called from the three generic sites it changed 10 of 12 kernels inside their main loops
+// (conv3d_split_wide_kernel<2, true> 228 -> 232 VGPRs, conv3d_split_kernel<2, 2, *> +115 / +118 instructions, <2, 3, false> +370).
 template <int P, bool F16>
 __device__ __forceinline__ void split4(float r0, float r1, float r2, float r3, uint2 (&out)[P]) {
 #pragma unroll

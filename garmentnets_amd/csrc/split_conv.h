@@ -75,6 +75,137 @@ __device__ __forceinline__ bool sp_work_item(const SplitArgs &p, int ncb, int ti
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------ tile decode
+// Tile index inside the sample -> origin of the tile, TZ x 8 x 8 voxels.  z-fastest order: the z halo is the fattest (2 of TZ + 2 slices), so tiles
+// adjacent in z run back to back.  tiles_z: the caller's (the Winograd kernels take whole tiles only: D / TZ).
+__device__ __forceinline__ void sp_tile_origin(const SplitArgs &p, int tile, int tiles_z, int TZ, int &z0, int &y0, int &x0) {
+    const int tz = tile % tiles_z; tile /= tiles_z;
+    const int tx = tile % p.tiles_x; tile /= p.tiles_x;
+    const int ty = tile;
+    z0 = tz * TZ; y0 = ty * GN_CONV_TY; x0 = tx * GN_CONV_TX;
+}
+// the tile lies inside the volume / no voxel of it lies on a face of the volume (both workgroup-uniform)
+__device__ __forceinline__ bool sp_tile_full(const SplitArgs &p, int z0, int y0, int x0, int TZ, int TY, int TX) {
+    return z0 + TZ <= p.D && y0 + TY <= p.H && x0 + TX <= p.W;
+}
+__device__ __forceinline__ bool sp_tile_interior(const SplitArgs &p, int z0, int y0, int x0, int TZ, int TY, int TX) {
+    return z0 > 0 && z0 + TZ < p.D && y0 > 0 && y0 + TY < p.H && x0 > 0 && x0 + TX < p.W;
+}
+
+// ------------------------------------------------------------------------------------------------ the epilogue of the direct kernels
+// ONE contract for conv3d_split_kernel, conv3d_split_strip_kernel, conv3d_split_wide_kernel (unet_split.hip).  Per output value: accumulator * scale (+ border-class bias) (+ polyphase partial) (ReLU), in this order, each step
+// rounded to fp32; channel statistics of the stored values in fp64.
+// kb / pb: NULL when the layer has no bias table / no partial; kv(), pv(): the value's bias / partial, evaluated only behind that test (in the generic
+// path they are loads behind 64-bit index arithmetic).  Callables and pointers ON PURPOSE: with the two terms passed by value, or their presence as
+// bools formed at the call, every kernel's epilogue was scheduled differently and the 64-wide instances' main loops with it.
+template <class KV, class PV>
+__device__ __forceinline__ float sp_out_value(float acc, float osc, const float *kb, KV kv, const float *pb, PV pv, int relu) {
+    float v = __fmul_rn(acc, osc);
+    if (kb) v = __fadd_rn(v, kv());
+    if (pb) v = __fadd_rn(v, pv());
+    if (relu) v = gn_relu(v);
+    return v;
+}
+// output scale of channel n of sample b: the pack's weight scale times the sample's activation scale undone (exact powers of two)
+__device__ __forceinline__ float sp_out_scale(const SplitArgs &p, int b, int n) {
+    const float osn = p.out_scale[(int64_t)b * p.osc_bstride + n];
+    return p.act_inv ? __fmul_rn(osn, p.act_inv[b]) : osn;
+}
+// NULL or channel n's column of sample b's kbias table (class stride Cout)
+__device__ __forceinline__ const float *sp_kbias_col(const SplitArgs &p, int b, int n) { return p.kbias ? p.kbias + (int64_t)b * 64 * p.Cout + n : nullptr; }
+// kbias class of voxel (gz, gy, gx)
+__device__ __forceinline__ int sp_kbias_class(const SplitArgs &p, int gz, int gy, int gx) {
+    return (sp_axis_mask(gz, p.D) * 4 + sp_axis_mask(gy, p.H)) * 4 + sp_axis_mask(gx, p.W);
+}
+
+// The generic (ragged-tile) store of ONE value: bounds, a 64-bit output address, the class lookup and the five-factor partial index per value.
+__device__ __forceinline__ void sp_store_ragged(const SplitArgs &p, int b, int gz, int gy, int gx, int n, float acc, float osc, const float *kb, double &ssum,
+                                                double &ssq) {
+    if (gz < p.D && gy < p.H && gx < p.W) {
+        const float v = sp_out_value(
+            acc, osc, kb, [&] { return kb[(int64_t)sp_kbias_class(p, gz, gy, gx) * p.Cout]; }, p.partial,
+            [&] { return p.partial[((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + (((gz & 1) * 4 + (gy & 1) * 2 + (gx & 1)) * p.Cout + n)]; },
+            p.relu);
+        p.out[((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n] = v;
+        ssum += (double)v;
+        ssq += (double)v * (double)v;
+    }
+}
+
+// Epilogue of one 32 x 32 D fragment when the tile lies inside the volume and is active: lane (h, r) holds channel n and the 16 voxels
+// (y = j, x = 4 h + k), q = 4 j + k, of one y half.  `ob` / `pb` point at (j, k) = (0, 0) of this lane; every other (j, k) is a
+// workgroup-uniform element offset from there (the generic path above spends ~40 instructions per value, five of them quarter-rate
+// integer multiplies, on 64-bit addresses and bounds: 9 % of the 128 -> 128 layer, 25 % of a 32 -> 32 one).  Same arithmetic, same
+// order as the generic path, channel statistics accumulated q = 0 .. 15.  kb: sp_kbias_col; interior tiles (workgroup-uniform) add the one
+// class-63 constant, tiles on a face of the volume look the class of each voxel up (gz: the fragment's plane; gy, gx: its first row / column,
+// both even: the parity of voxel q is that of (j, k)).
+// The x-strip kernel's fragment is the TRANSPOSE of this one (q walks (z, y) at one x) and keeps its own copy of this body around
+// sp_out_value: with the two axes and their strides as compile-time traits of this function the strip kernel's main loop came out with
+// another block order and 94 more lines of device code (profiles/conv_epilogue_isa_diff.txt), and the traits then served that one caller.
+__device__ __forceinline__ void sp_store_frag_full(const SplitArgs &p, const f32x16 &val, float osc, float *ob, const float *pb, double &ssum, double &ssq,
+                                                   const float *kb, bool interior, int gz, int gy, int gx) {
+    const int64_t rs = (int64_t)p.W * p.Cout;
+    float pv[16];
+    float kv[16];
+    if (kb) {
+        if (interior) {
+            const float k63 = kb[63 * (int64_t)p.Cout];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) kv[q] = k63;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) kv[q] = kb[(int64_t)sp_kbias_class(p, gz, gy + (q >> 2), gx + (q & 3)) * p.Cout];
+        }
+    }
+    if (pb) {
+        const int64_t prs = (int64_t)(p.W >> 1) * 8 * p.Cout;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int j = q >> 2, k = q & 3;
+            pv[q] = pb[(j >> 1) * prs + (int64_t)((k >> 1) * 8 + (j & 1) * 2 + (k & 1)) * p.Cout];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int j = q >> 2, k = q & 3;
+        const float v = sp_out_value(val[q], osc, kb, [&] { return kv[q]; }, pb, [&] { return pv[q]; }, p.relu);
+        ob[j * rs + (int64_t)k * p.Cout] = v;
+        ssum += (double)v;
+        ssq += (double)v * (double)v;
+    }
+}
+// ob / pb of the call above: the output element of channel n at voxel (gz, gy, gx) of sample b / NULL or its entry of the polyphase partial
+__device__ __forceinline__ float *sp_out_at(const SplitArgs &p, int b, int gz, int gy, int gx, int n) {
+    return p.out + ((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n;
+}
+__device__ __forceinline__ const float *sp_partial_at(const SplitArgs &p, int b, int gz, int gy, int gx, int n) {
+    return p.partial ? p.partial + ((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + (((gz & 1) * 4 + (gy & 1) * 2 + (gx & 1)) * p.Cout + n) : nullptr;
+}
+
+// Channel statistics of a 4-wave workgroup over NT * 32 channels from column COL0 of sample B (wave w: one row of each channel, lane (h, r) holds channel
+// u * 32 + r in SSUM[u] / SSQ[u]): fold the lane halves, RED[sum | sq][wave][NT * 32] through LDS (8 * NT * 32 doubles), then one fp64 atomic pair per
+// channel; the four waves' rows are added in the order 0 + 1 + 2 + 3 (the per-tile partials are the same in dense and occupancy-aware launches).  Uses
+// the caller's tid, h, r.  A macro ON PURPOSE (as GN_WAVE_ARGMIN, device_prims.h): as an inlined function -- array references or pointers, the output
+// address formed inside or outside -- the same text changed the block placement and the scratch use of conv3d_split_kernel<2, 3, false>'s MAIN LOOP.
+// conv3d_split_wide_kernel keeps its own [cg][zs][64] form of this: with either form of the shared text its main loop was allocated differently
+// (226 instead of 228 VGPRs, another schedule), and that kernel is 58 % of the UNet's FLOPs (profiles/conv_epilogue_isa_diff.txt).
+#define SP_REDUCE_STATS(NT_, P, B, COL0, SSUM, SSQ, RED, WAVE)                                                                 \
+    do {                                                                                                                       \
+        constexpr int ct_ = (NT_) * 32;                                                                                        \
+        double *const red_ = (RED);                                                                                            \
+        _Pragma("unroll") for (int u = 0; u < (NT_); ++u) {                                                                    \
+            const double s2 = SSUM[u] + __shfl_xor(SSUM[u], 32), q2 = SSQ[u] + __shfl_xor(SSQ[u], 32);                         \
+            if (h == 0) { red_[(WAVE) * ct_ + u * 32 + r] = s2; red_[4 * ct_ + (WAVE) * ct_ + u * 32 + r] = q2; }              \
+        }                                                                                                                      \
+        __syncthreads();                                                                                                       \
+        if (tid < ct_) {                                                                                                       \
+            const double s4 = red_[tid] + red_[ct_ + tid] + red_[2 * ct_ + tid] + red_[3 * ct_ + tid];                         \
+            const double q4 = red_[4 * ct_ + tid] + red_[5 * ct_ + tid] + red_[6 * ct_ + tid] + red_[7 * ct_ + tid];           \
+            atomicAdd(&(P).osum[(int64_t)(B) * (P).Cout + (COL0) + tid], s4);                                                  \
+            atomicAdd(&(P).osq[(int64_t)(B) * (P).Cout + (COL0) + tid], q4);                                                   \
+        }                                                                                                                      \
+    } while (0)
+
 // LDS halo layout.  ds_read_b128 is serviced in four 16-lane groups that are NOT contiguous lane ranges ({0-3,12-15,20-27},
 // {4-11,16-19,28-31} and the same +32: MI355X_MICROARCH.md, LDS table); with the fragment's row r = (y = r>>3, x = r&7) a group is
 // four runs of 4 x-consecutive voxels in 4 different halo rows, and 16-byte bank quads repeat every 256 B.  Two planes (P = 2):

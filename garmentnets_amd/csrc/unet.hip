@@ -428,7 +428,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_gcr_kernel(ConvArgs p) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) { tot[t][u][q] = __fadd_rn(tot[t][u][q], acc[t][u][q]); acc[t][u][q] = 0.f; }
     }
-    // ---- epilogue: ReLU, coalesced stores, optional statistics of the output
+    // ---- epilogue: ReLU, coalesced stores, optional statistics of the output.  The split-operand kernels share their work-item order, tile decode and
+    // statistics reduction (split_conv.h); this kernel keeps its own copies and an epilogue without scale, bias or partial.  Tried: sp_work_item +
+    // sp_tile_origin in place of the index arithmetic above changed the main loop's schedule of both instances (<1>: 1847 -> 1833 lines of device code, 77 -> 76
+    // SGPRs); SP_REDUCE_STATS in place of the block below took <1> to 2860 lines and 106 SGPRs (profiles/conv_epilogue_isa_diff.txt)
     const int gz = z0 + wave;
     const bool full = z0 + GN_CONV_TZ <= p.D && y0 + GN_CONV_TY <= p.H && x0 + GN_CONV_TX <= p.W;    // tile inside the volume (workgroup-uniform)
     double ssum[NT], ssq[NT];                       // fp64 per lane: the statistics do not depend on the kernel variant (see unet_split.hip)
@@ -505,9 +508,11 @@ extern "C" int gn_conv3d_gcr(const float *src0, int C0, const float *src1, int C
     const int tiles = tz * p.tiles_y * p.tiles_x;
     // small volumes / small batches: the 32-wide column tile doubles the number of workgroups (same per-CU throughput)
     const bool wide = (Cout % 64 == 0) && ((int64_t)tiles * (Cout / 64) * B >= 1024);
-    if (wide) hipLaunchKernelGGL(conv3d_gcr_kernel<2>, dim3(tiles * (Cout / 64), B), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(conv3d_gcr_kernel<1>, dim3(tiles * (Cout / 32), B), dim3(256), 0, st, p);
-    gn_note_kernel(wide ? "conv3d_gcr_kernel<2>" : "conv3d_gcr_kernel<1>");
+    static const struct { void (*kernel)(ConvArgs); int cols; const char *name; } variants[2] = {
+        {conv3d_gcr_kernel<2>, 64, "conv3d_gcr_kernel<2>"}, {conv3d_gcr_kernel<1>, 32, "conv3d_gcr_kernel<1>"}};
+    const auto &v = variants[wide ? 0 : 1];
+    hipLaunchKernelGGL(v.kernel, dim3(tiles * (Cout / v.cols), B), dim3(256), 0, st, p);
+    gn_note_kernel(v.name);
     GN_LAUNCH_CHECK("gn_conv3d_gcr");
     return GN_OK;
 }

@@ -23,50 +23,6 @@
 #include "common.h"
 #include "split_conv.h"
 
-// Epilogue of one 32 x 32 D fragment when the tile lies inside the volume and is active: lane (h, r) holds channel n and the 16 voxels
-// (y = j, x = 4 h + k), q = 4 j + k, of one y half.  `ob` / `pb` point at (j, k) = (0, 0) of this lane; every other (j, k) is a
-// workgroup-uniform element offset from there (the generic path below spent ~40 instructions per value, five of them quarter-rate
-// integer multiplies, on 64-bit addresses and bounds: 9 % of the 128 -> 128 layer, 25 % of a 32 -> 32 one).  Same arithmetic, same
-// order as the generic path: value * scale (+ polyphase partial) (ReLU), channel statistics accumulated q = 0 .. 15.
-// kb: NULL or this lane's column of the sample's kbias table (class stride Cout); interior tiles (workgroup-uniform) add the one class-63
-// constant, tiles on a face of the volume look the class of each voxel up (gz: the fragment's plane; gy, gx: its first row / column).
-__device__ __forceinline__ void sp_store_frag_full(const SplitArgs &p, const f32x16 &val, float osc, float *ob, const float *pb, double &ssum, double &ssq,
-                                                   const float *kb = nullptr, bool interior = true, int gz = 0, int gy = 0, int gx = 0) {
-    const int64_t rs = (int64_t)p.W * p.Cout;
-    float pv[16];
-    float kv[16];
-    if (kb) {
-        if (interior) {
-            const float k63 = kb[63 * (int64_t)p.Cout];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) kv[q] = k63;
-        } else {
-            const int mz = sp_axis_mask(gz, p.D);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) kv[q] = kb[(int64_t)((mz * 4 + sp_axis_mask(gy + (q >> 2), p.H)) * 4 + sp_axis_mask(gx + (q & 3), p.W)) * p.Cout];
-        }
-    }
-    if (pb) {
-        const int64_t prs = (int64_t)(p.W >> 1) * 8 * p.Cout;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int j = q >> 2, k = q & 3;
-            pv[q] = pb[(j >> 1) * prs + (int64_t)((k >> 1) * 8 + (j & 1) * 2 + (k & 1)) * p.Cout];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int j = q >> 2, k = q & 3;
-        float v = __fmul_rn(val[q], osc);
-        if (kb) v = __fadd_rn(v, kv[q]);
-        if (pb) v = __fadd_rn(v, pv[q]);
-        if (p.relu) v = gn_relu(v);
-        ob[j * rs + (int64_t)k * p.Cout] = v;
-        ssum += (double)v;
-        ssq += (double)v * (double)v;
-    }
-}
-
 // tile 4 x 8 x 8: wave w takes z-slice w, as two 32-row fragments (y halves).  (A tall 8 x 8 x 8 tile, two z-slices per wave, was measured on the
 // 32-wide layers: 327-347 TFLOP/s against 340 -- its synchronous staging phase is 29 % of the kernel -- and dropped.)
 template <int NT, int P, bool F16>
@@ -91,10 +47,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     const int tiles_z = (p.D + TZ - 1) / TZ;
     int b, tile, cb;
     if (!sp_work_item(p, ncb, tiles_z * p.tiles_x * p.tiles_y, b, tile, cb)) return;      // (workgroup-uniform)
-    const int tz = tile % tiles_z; tile /= tiles_z;
-    const int tx = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty = tile;
-    const int z0 = tz * TZ, y0 = ty * GN_CONV_TY, x0 = tx * GN_CONV_TX;
+    int z0, y0, x0;
+    sp_tile_origin(p, tile, tiles_z, TZ, z0, y0, x0);
     const int n0 = cb * CT;
     const int D1 = p.D >> 1, H1 = p.H >> 1, W1 = p.W >> 1;
 
@@ -300,55 +254,27 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_kernel(SplitArgs p) {
     double ssum[NT], ssq[NT];
 #pragma unroll
     for (int u = 0; u < NT; ++u) { ssum[u] = 0.0; ssq[u] = 0.0; }
-    const bool full = z0 + TZ <= p.D && y0 + GN_CONV_TY <= p.H && x0 + GN_CONV_TX <= p.W;       // (workgroup-uniform)
-    const bool interior = z0 > 0 && z0 + TZ < p.D && y0 > 0 && y0 + GN_CONV_TY < p.H && x0 > 0 && x0 + GN_CONV_TX < p.W;   // no voxel of the tile on a face
+    const bool full = sp_tile_full(p, z0, y0, x0, TZ, GN_CONV_TY, GN_CONV_TX), interior = sp_tile_interior(p, z0, y0, x0, TZ, GN_CONV_TY, GN_CONV_TX);   // (workgroup-uniform)
 #pragma unroll
     for (int f = 0; f < NF; ++f)
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
             const int t = f, gz = z0 + wave;
             const int n = n0 + u * 32 + r;
-            const float osn = p.out_scale[(int64_t)b * p.osc_bstride + n];
-            const float osc = p.act_inv ? __fmul_rn(osn, p.act_inv[b]) : osn;
-            const float *kb = p.kbias ? p.kbias + (int64_t)b * 64 * p.Cout + n : nullptr;
+            const float osc = sp_out_scale(p, b, n);
+            const float *kb = sp_kbias_col(p, b, n);
             if (full) {
                 const int gy = y0 + t * 4, gx = x0 + 4 * h;
-                float *ob = p.out + ((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n;
-                const float *pb = p.partial ? p.partial + ((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + ((gz & 1) * 4 * p.Cout + n) : nullptr;
-                sp_store_frag_full(p, tot[f][u], osc, ob, pb, ssum[u], ssq[u], kb, interior, gz, gy, gx);
+                sp_store_frag_full(p, tot[f][u], osc, sp_out_at(p, b, gz, gy, gx, n), sp_partial_at(p, b, gz, gy, gx, n), ssum[u], ssq[u], kb, interior, gz, gy, gx);
                 continue;
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int i = (q & 3) + 8 * (q >> 2) + 4 * h;
-                const int gy = y0 + t * 4 + (i >> 3), gx = x0 + (i & 7);
-                if (gz < p.D && gy < p.H && gx < p.W) {
-                    float v;
-                    v = __fmul_rn(tot[f][u][q], osc);
-                    if (kb) v = __fadd_rn(v, kb[(int64_t)((sp_axis_mask(gz, p.D) * 4 + sp_axis_mask(gy, p.H)) * 4 + sp_axis_mask(gx, p.W)) * p.Cout]);
-                    if (p.partial) v = __fadd_rn(v, p.partial[((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + (((gz & 1) * 4 + (gy & 1) * 2 + (gx & 1)) * p.Cout + n)]);
-                    if (p.relu) v = gn_relu(v);
-                    p.out[((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n] = v;
-                    ssum[u] += (double)v;
-                    ssq[u] += (double)v * (double)v;
-                }
+                sp_store_ragged(p, b, gz, y0 + t * 4 + (i >> 3), x0 + (i & 7), n, tot[f][u][q], osc, kb, ssum[u], ssq[u]);
             }
         }
-    if (p.osum) {
-        double *red = reinterpret_cast<double *>(halo);
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            const double s2 = ssum[u] + __shfl_xor(ssum[u], 32), q2 = ssq[u] + __shfl_xor(ssq[u], 32);
-            if (h == 0) { red[wave * CT + u * 32 + r] = s2; red[4 * CT + wave * CT + u * 32 + r] = q2; }
-        }
-        __syncthreads();
-        if (tid < CT) {
-            const double s4 = red[tid] + red[CT + tid] + red[2 * CT + tid] + red[3 * CT + tid];
-            const double q4 = red[4 * CT + tid] + red[5 * CT + tid] + red[6 * CT + tid] + red[7 * CT + tid];
-            atomicAdd(&p.osum[(int64_t)b * p.Cout + n0 + tid], s4);
-            atomicAdd(&p.osq[(int64_t)b * p.Cout + n0 + tid], q4);
-        }
-    }
+    if (p.osum) SP_REDUCE_STATS(NT, p, b, n0, ssum, ssq, reinterpret_cast<double *>(halo), wave);
 }
 
 // ------------------------------------------------------------------------------------------------ 32-wide "x-strip" variant (P = 2)
@@ -388,10 +314,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_strip_kernel(SplitArgs p)
     const int tiles_z = (p.D + T - 1) / T;
     int b, tile, cb;
     if (!sp_work_item(p, ncb, tiles_z * p.tiles_x * p.tiles_y, b, tile, cb)) return;      // (workgroup-uniform)
-    const int tz = tile % tiles_z; tile /= tiles_z;
-    const int tx = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty = tile;
-    const int z0 = tz * T, y0 = ty * T, x0 = tx * T;
+    int z0, y0, x0;
+    sp_tile_origin(p, tile, tiles_z, T, z0, y0, x0);
     const int n0 = cb * 32;
 
     f32x16 acc[NX], tot[NX];
@@ -505,14 +429,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_strip_kernel(SplitArgs p)
     }
     __syncthreads();                                // the epilogue reuses the halo as scratch
     // ---- epilogue: fragment xo of this wave = rows (zr = q >> 2, yr = (q & 3) + 4 h) at x = x0 + xw + xo, lane r = channel
-    double ssum = 0.0, ssq = 0.0;                   // fp64 per lane (see conv3d_split_kernel)
+    double ssum[1] = {0.0}, ssq[1] = {0.0};         // fp64 per lane (see conv3d_split_kernel)
     const int n = n0 + r;
-    const float osn = p.out_scale[(int64_t)b * p.osc_bstride + n];
-            const float osc = p.act_inv ? __fmul_rn(osn, p.act_inv[b]) : osn;
-    const bool full = z0 + T <= p.D && y0 + T <= p.H && x0 + T <= p.W;       // (workgroup-uniform)
-    const bool interior = z0 > 0 && z0 + T < p.D && y0 > 0 && y0 + T < p.H && x0 > 0 && x0 + T < p.W;
-    const float *kb = p.kbias ? p.kbias + (int64_t)b * 64 * p.Cout + n : nullptr;
-    if (full) {
+    const float osc = sp_out_scale(p, b, n);
+    const bool full = sp_tile_full(p, z0, y0, x0, T, T, T), interior = sp_tile_interior(p, z0, y0, x0, T, T, T);   // (workgroup-uniform)
+    const float *kb = sp_kbias_col(p, b, n);
+    if (full) {                                     // sp_store_frag_full transposed: this kernel's own copy (why: at that function, split_conv.h)
         const int64_t rs = (int64_t)p.W * p.Cout, zs_ = (int64_t)p.H * rs;
         const int gz0 = z0 + zw, gy0 = y0 + 4 * h;
 #pragma unroll
@@ -536,52 +458,25 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_strip_kernel(SplitArgs p)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) kv[q] = k63;
                 } else {
-                    const int xmask = sp_axis_mask(gx, p.W);
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) kv[q] = kb[(int64_t)((sp_axis_mask(gz0 + (q >> 2), p.D) * 4 + sp_axis_mask(gy0 + (q & 3), p.H)) * 4 + xmask) * p.Cout];
+                    for (int q = 0; q < 16; ++q) kv[q] = kb[(int64_t)sp_kbias_class(p, gz0 + (q >> 2), gy0 + (q & 3), gx) * p.Cout];
                 }
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                float v = __fmul_rn(tot[xo][q], osc);
-                if (kb) v = __fadd_rn(v, kv[q]);
-                if (p.partial) v = __fadd_rn(v, pv[q]);
-                if (p.relu) v = gn_relu(v);
+                const float v = sp_out_value(tot[xo][q], osc, kb, [&] { return kv[q]; }, p.partial, [&] { return pv[q]; }, p.relu);
                 ob[(q >> 2) * zs_ + (q & 3) * rs] = v;
-                ssum += (double)v;
-                ssq += (double)v * (double)v;
+                ssum[0] += (double)v;
+                ssq[0] += (double)v * (double)v;
             }
         }
     } else {
 #pragma unroll
         for (int xo = 0; xo < NX; ++xo)
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int gz = z0 + zw + (q >> 2), gy = y0 + 4 * h + (q & 3), gx = x0 + xw + xo;
-                if (gz < p.D && gy < p.H && gx < p.W) {
-                    float v;
-                    v = __fmul_rn(tot[xo][q], osc);
-                    if (kb) v = __fadd_rn(v, kb[(int64_t)((sp_axis_mask(gz, p.D) * 4 + sp_axis_mask(gy, p.H)) * 4 + sp_axis_mask(gx, p.W)) * p.Cout]);
-                    if (p.partial) v = __fadd_rn(v, p.partial[((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + (((gz & 1) * 4 + (gy & 1) * 2 + (gx & 1)) * p.Cout + n)]);
-                    if (p.relu) v = gn_relu(v);
-                    p.out[((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n] = v;
-                    ssum += (double)v;
-                    ssq += (double)v * (double)v;
-                }
-            }
+            for (int q = 0; q < 16; ++q) sp_store_ragged(p, b, z0 + zw + (q >> 2), y0 + 4 * h + (q & 3), x0 + xw + xo, n, tot[xo][q], osc, kb, ssum[0], ssq[0]);
     }
-    if (p.osum) {
-        double *red = reinterpret_cast<double *>(halo);
-        const double s2 = ssum + __shfl_xor(ssum, 32), q2 = ssq + __shfl_xor(ssq, 32);
-        if (h == 0) { red[wave * 32 + r] = s2; red[128 + wave * 32 + r] = q2; }
-        __syncthreads();
-        if (tid < 32) {
-            const double s4 = red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid];
-            const double q4 = red[128 + tid] + red[160 + tid] + red[192 + tid] + red[224 + tid];
-            atomicAdd(&p.osum[(int64_t)b * p.Cout + n0 + tid], s4);
-            atomicAdd(&p.osq[(int64_t)b * p.Cout + n0 + tid], q4);
-        }
-    }
+    if (p.osum) SP_REDUCE_STATS(1, p, b, n0, ssum, ssq, reinterpret_cast<double *>(halo), wave);
 }
 
 // ------------------------------------------------------------------------------------------------ 128-wide variant (P = 2)
@@ -615,10 +510,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wide_kernel(SplitArgs p) 
     const int tiles_z = (p.D + TZ - 1) / TZ;
     int b, tile, cb;
     if (!sp_work_item(p, ncb, tiles_z * p.tiles_x * p.tiles_y, b, tile, cb)) return;      // (workgroup-uniform)
-    const int tz = tile % tiles_z; tile /= tiles_z;
-    const int tx = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty = tile;
-    const int z0 = tz * TZ, y0 = ty * GN_CONV_TY, x0 = tx * GN_CONV_TX;
+    int z0, y0, x0;
+    sp_tile_origin(p, tile, tiles_z, TZ, z0, y0, x0);
     const int n0 = cb * 128 + cg * 64;
     const int zl = zs;                              // this wave's z-slice inside the tile
     const int D1 = p.D >> 1, H1 = p.H >> 1, W1 = p.W >> 1;
@@ -806,41 +699,27 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_wide_kernel(SplitArgs p) 
     double ssum[NT], ssq[NT];
 #pragma unroll
     for (int u = 0; u < NT; ++u) { ssum[u] = 0.0; ssq[u] = 0.0; }
-    const bool full = z0 + TZ <= p.D && y0 + GN_CONV_TY <= p.H && x0 + GN_CONV_TX <= p.W;       // (workgroup-uniform)
-    const bool interior = z0 > 0 && z0 + TZ < p.D && y0 > 0 && y0 + GN_CONV_TY < p.H && x0 > 0 && x0 + GN_CONV_TX < p.W;
+    const bool full = sp_tile_full(p, z0, y0, x0, TZ, GN_CONV_TY, GN_CONV_TX), interior = sp_tile_interior(p, z0, y0, x0, TZ, GN_CONV_TY, GN_CONV_TX);   // (workgroup-uniform)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
             const int n = n0 + u * 32 + r;
-            const float osn = p.out_scale[(int64_t)b * p.osc_bstride + n];
-            const float osc = p.act_inv ? __fmul_rn(osn, p.act_inv[b]) : osn;
-            const float *kb = p.kbias ? p.kbias + (int64_t)b * 64 * p.Cout + n : nullptr;
+            const float osc = sp_out_scale(p, b, n);
+            const float *kb = sp_kbias_col(p, b, n);
             if (full) {
                 const int gy = y0 + t * 4, gx = x0 + 4 * h;
-                float *ob = p.out + ((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n;
-                const float *pb = p.partial ? p.partial + ((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + ((gz & 1) * 4 * p.Cout + n) : nullptr;
-                sp_store_frag_full(p, tot[t][u], osc, ob, pb, ssum[u], ssq[u], kb, interior, gz, gy, gx);
+                sp_store_frag_full(p, tot[t][u], osc, sp_out_at(p, b, gz, gy, gx, n), sp_partial_at(p, b, gz, gy, gx, n), ssum[u], ssq[u], kb, interior, gz, gy, gx);
                 continue;
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int i = (q & 3) + 8 * (q >> 2) + 4 * h;
-                const int gy = y0 + t * 4 + (i >> 3), gx = x0 + (i & 7);
-                if (gz < p.D && gy < p.H && gx < p.W) {
-                    float v;
-                    v = __fmul_rn(tot[t][u][q], osc);
-                    if (kb) v = __fadd_rn(v, kb[(int64_t)((sp_axis_mask(gz, p.D) * 4 + sp_axis_mask(gy, p.H)) * 4 + sp_axis_mask(gx, p.W)) * p.Cout]);
-                    if (p.partial) v = __fadd_rn(v, p.partial[((((int64_t)b * (p.D >> 1) + (gz >> 1)) * (p.H >> 1) + (gy >> 1)) * (p.W >> 1) + (gx >> 1)) * (8 * p.Cout) + (((gz & 1) * 4 + (gy & 1) * 2 + (gx & 1)) * p.Cout + n)]);
-                    if (p.relu) v = gn_relu(v);
-                    p.out[((((int64_t)b * p.D + gz) * p.H + gy) * p.W + gx) * p.Cout + n] = v;
-                    ssum[u] += (double)v;
-                    ssq[u] += (double)v * (double)v;
-                }
+                sp_store_ragged(p, b, gz, y0 + t * 4 + (i >> 3), x0 + (i & 7), n, tot[t][u][q], osc, kb, ssum[u], ssq[u]);
             }
         }
     if (p.osum) {
-        double *red = reinterpret_cast<double *>(smem);                         // [sum | sq][cg][zs][64]
+        double *red = reinterpret_cast<double *>(smem);                         // [sum | sq][cg][zs][64]: SP_REDUCE_STATS for 8 waves, kept local (why: there)
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
             const double s2 = ssum[u] + __shfl_xor(ssum[u], 32), q2 = ssq[u] + __shfl_xor(ssq[u], 32);
@@ -968,6 +847,27 @@ extern "C" size_t gn_conv3d_occupancy_workspace_bytes(int B, int D, int H, int W
     return ((size_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX) + 16) * sizeof(int);
 }
 
+// The direct variants: kernel, block size, tile depth (4: 4 x 8 x 8 tiles, 8: the x-strip kernel's 8 x 8 x 8), output channels per workgroup and the name
+// gn_note_kernel reports.  The grid of a variant is (tiles at its depth * (Cout / cols), B).
+struct SplitVariant {
+    void (*kernel)(SplitArgs);
+    int block, tile_z, cols;
+    const char *name;
+};
+#define SP_VARIANT(BLOCK, TZ, COLS, ...) {__VA_ARGS__, BLOCK, TZ, COLS, #__VA_ARGS__}      // the name is the kernel's own text
+static const SplitVariant &split_direct_variant(int mode, bool wide128, bool strip, bool wide) {
+    static const SplitVariant table[] = {
+        SP_VARIANT(256, 8, 32, conv3d_split_strip_kernel<true>),    SP_VARIANT(256, 8, 32, conv3d_split_strip_kernel<false>),
+        SP_VARIANT(512, 4, 128, conv3d_split_wide_kernel<2, true>), SP_VARIANT(512, 4, 128, conv3d_split_wide_kernel<2, false>),
+        SP_VARIANT(256, 4, 64, conv3d_split_kernel<2, 3, false>),   SP_VARIANT(256, 4, 32, conv3d_split_kernel<1, 3, false>),
+        SP_VARIANT(256, 4, 64, conv3d_split_kernel<2, 2, false>),   SP_VARIANT(256, 4, 32, conv3d_split_kernel<1, 2, false>),
+        SP_VARIANT(256, 4, 64, conv3d_split_kernel<2, 2, true>),    SP_VARIANT(256, 4, 32, conv3d_split_kernel<1, 2, true>)};
+    if (strip) return table[mode == GN_SPLIT_F16X2 ? 0 : 1];
+    if (wide128) return table[mode == GN_SPLIT_F16X2 ? 2 : 3];
+    return table[(mode == GN_SPLIT_BF16X3 ? 4 : (mode == GN_SPLIT_BF16X2 ? 6 : 8)) + (wide ? 0 : 1)];
+}
+#undef SP_VARIANT
+
 static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, int C1, const float *a, const float *d,
                                  const void *wp_planes, int mode, const float *out_scale, const float *act_inv_scale, int B, int D, int H,
                                  int W, int Cout, int relu, float *out, double *out_sum, double *out_sumsq, const unsigned char *tile_active,
@@ -1014,12 +914,6 @@ static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, i
     const int tiles8 = (int)gn_cdiv(D, 8) * p.tiles_y * p.tiles_x;
     const bool strip = !wino && mode != GN_SPLIT_BF16X3 && !wide128 && C1 == 0 && (int64_t)tiles8 * (Cout / 32) * B >= 512;
     const bool wide = !wino && !wide128 && !strip && (Cout % 64 == 0) && ((int64_t)tiles * (Cout / 64) * B >= 1024);
-#define SP_LAUNCH(P_, F16_)                                                                                                    \
-    do {                                                                                                                       \
-        if (wide) hipLaunchKernelGGL((conv3d_split_kernel<2, P_, F16_>), dim3(tiles * (Cout / 64), B), dim3(256), 0, st, p);    \
-        else hipLaunchKernelGGL((conv3d_split_kernel<1, P_, F16_>), dim3(tiles * (Cout / 32), B), dim3(256), 0, st, p);        \
-        gn_note_kernel(wide ? "conv3d_split_kernel<2, " #P_ ", " #F16_ ">" : "conv3d_split_kernel<1, " #P_ ", " #F16_ ">");     \
-    } while (0)
     // The variant is chosen from the SHAPE alone -- an occupancy-aware launch (tile_active) takes the kernel the dense launch of the same
     // shape takes, so the two give bit-identical outputs AND the same per-tile fp32 partials of the epilogue statistics.  (Outputs are
     // bit-identical across all variants anyway: per element the products arrive in the same order; the border-class constants of an
@@ -1047,19 +941,11 @@ static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, i
     } else if (wino) {
         gn_launch_conv3d_wino(p, tiles, st);
         gn_note_kernel("conv3d_split_wino_kernel<true>");
-    } else if (strip) {
-        if (mode == GN_SPLIT_F16X2) hipLaunchKernelGGL((conv3d_split_strip_kernel<true>), dim3(tiles8 * (Cout / 32), B), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((conv3d_split_strip_kernel<false>), dim3(tiles8 * (Cout / 32), B), dim3(256), 0, st, p);
-        gn_note_kernel(mode == GN_SPLIT_F16X2 ? "conv3d_split_strip_kernel<true>" : "conv3d_split_strip_kernel<false>");
-    } else if (wide128) {
-        if (mode == GN_SPLIT_F16X2) hipLaunchKernelGGL((conv3d_split_wide_kernel<2, true>), dim3(tiles * (Cout / 128), B), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((conv3d_split_wide_kernel<2, false>), dim3(tiles * (Cout / 128), B), dim3(512), 0, st, p);
-        gn_note_kernel(mode == GN_SPLIT_F16X2 ? "conv3d_split_wide_kernel<2, true>" : "conv3d_split_wide_kernel<2, false>");
-    } else
-    if (mode == GN_SPLIT_BF16X3) SP_LAUNCH(3, false);
-    else if (mode == GN_SPLIT_BF16X2) SP_LAUNCH(2, false);
-    else SP_LAUNCH(2, true);
-#undef SP_LAUNCH
+    } else {
+        const SplitVariant &v = split_direct_variant(mode, wide128, strip, wide);
+        hipLaunchKernelGGL(v.kernel, dim3((v.tile_z == 8 ? tiles8 : tiles) * (Cout / v.cols), B), dim3(v.block), 0, st, p);
+        gn_note_kernel(v.name);
+    }
     GN_LAUNCH_CHECK("gn_conv3d_gcr_split");
     return GN_OK;
 }

@@ -17,6 +17,8 @@ Which case launches which gn_note_kernel name of the direct family (shapes (16, 
                                                test_occupancy_constants_cross_variant (<true> and <false>: dense and occupancy-aware at B = 8)
     conv3d_split_wide_kernel<2, true / false>  test_split_variants 1src_c128 (B = 16), 2src_c128 (16: with the upsampled source); test_bwd_data_split,
                                                test_persample_variants (<2, true>)
+    with a polyphase partial, ragged tiles     test_partial_variants (14, 12, 30), 32 -> 128: <1, 2, true>, strip<true> (B = 8), wide<2, true> (16), both
+                                               entries; <1, 3, false>, <2, 3, false> (16)
 (gn_conv3d_gcr_split_persample is GN_SPLIT_F16X2 with one source: <1, 2, true>, strip<true> and wide<2, true> are all it can take -- with one source
 the strip rule always holds before the 64-wide one.)  NOT covered: the fits32 == false branch of conv3d_gcr_split_impl (a 128-wide layer kept off
 conv3d_split_wide_kernel because one sample of its source exceeds 2^32 bytes): that needs a sample above 4 GiB, which cannot be small.
@@ -446,6 +448,73 @@ def test_persample_variants(dims):
     for relu in (True, False):
         call = lambda lo, hi: ops.conv3d_gcr_split_persample(c.gx0[lo:hi].contiguous(), prep(lo, hi), relu=relu)   # noqa: E731,B023
         _slot_independent(call, "gn_conv3d_gcr_split_persample", F16X2, dims, c.C0, c.Cout, (_k(1, F16X2), _strip(F16X2), _wide(F16X2)))
+
+
+def _upsampled_partial(part, dims):
+    """partial [B][D/2][H/2][W/2][8 * Cout] -> what the epilogue adds at every voxel, [B][D][H][W][Cout]: entry ((z&1)*4 + (y&1)*2 + (x&1)) * Cout + n
+    of coarse voxel (z>>1, y>>1, x>>1)"""
+    B, (D, H, W) = part.shape[0], dims
+    return part.view(B, D // 2, H // 2, W // 2, 2, 2, 2, -1).permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, D, H, W, -1)
+
+
+@pytest.mark.parametrize("mode", [F16X2, BF16X3], ids=["f16x2", "bf16x3"])
+def test_partial_variants(mode):
+    """a polyphase partial on RAGGED tiles through every direct split variant (32 -> 128 at (14, 12, 30)): <1, 2, true>, strip, 128-wide (f16x2) and
+    <1, 3, false>, <2, 3, false> (bf16x3).  Every variant one below and at its threshold, bit for bit and against its B = 1 launch (_slot_independent);
+    each variant against fp64 (the conv reference + the partial, added before the ReLU; the bars of _variant_checks) with its epilogue statistics; the
+    f16x2 case through the affine-in-weights entry as well (kbias and partial together).  The partial enters by ONE __fadd_rn before the ReLU, so
+    the launch with it must also equal the launch without it (relu off) + partial, then ReLU, to the bit."""
+    C0, Cout, dims, Bmax = 32, 128, RAGGED, 16
+    names = (_k(1, mode), _strip(mode), _wide(mode)) if mode == F16X2 else (_k(1, mode), _k(2, mode))
+    c = _case(C0, 0, Cout, dims, Bmax)
+    D, H, W = dims
+    part = torch.randn(Bmax, D // 2, H // 2, W // 2, 8 * Cout, generator=torch.Generator().manual_seed(4242 + mode))
+    part[BIG] *= 1024.0
+    gpart = part.to(DEV)
+    up = _upsampled_partial(part, dims)                                    # host, fp32
+    pack = _pack_of(c, mode)
+    starts = variant_starts("gn_conv3d_gcr_split", mode, dims, C0, 0, Cout)
+    assert [k for k, _ in starts] == list(names) and starts[-1][1] <= Bmax, starts
+    ref_slots = (0, starts[1][1] - 2)                                      # in every launch below; never the large slot
+    assert BIG not in ref_slots
+    figs = {}
+    for relu in (True, False):
+        launch = lambda lo, hi, **kw: ops.conv3d_gcr_split(c.gx0[lo:hi].contiguous(), None, c.ga[lo:hi].contiguous(), c.gd[lo:hi].contiguous(), pack,   # noqa: E731,B023
+                                                           Cout, relu=relu, partial=gpart[lo:hi].contiguous(), **kw)                              # noqa: B023
+        _slot_independent(launch, "gn_conv3d_gcr_split", mode, dims, C0, Cout, names)
+        e32 = _e32(C0, 0, Cout, dims, Bmax, ref_slots, relu)
+        for (name, T), B in zip(starts, [starts[1][1] - 1] + [T for _, T in starts[1:]]):
+            out, (s, q, V) = launch(0, B, with_stats=True)
+            assert last_kernel() == name and V == D * H * W, (last_kernel(), name, B)
+            figs.setdefault(name, []).append(("stats", _stats_figure(out, s, q), 1.0))
+            for slot in ref_slots:
+                want = _ref_of(c, slot, False) + up[slot].double()
+                err = float((out[slot].cpu().double() - (F.relu(want) if relu else want)).abs().max())
+                figs[name].append((f"fp64 (e32 {e32:.2e})", err, 2 * max(e32, 2e-6)))
+            # the partial is one fp32 addition before the ReLU
+            bare = ops.conv3d_gcr_split(c.gx0[:B].contiguous(), None, c.ga[:B].contiguous(), c.gd[:B].contiguous(), pack, Cout, relu=False)
+            assert last_kernel() == name
+            want = bare + _upsampled_partial(gpart[:B], dims)
+            assert torch.equal(out, F.relu(want) if relu else want), (name, B, relu, "partial added before the ReLU")
+    _report_and_assert(f"partial mode {mode} {dims}", figs, set(names), names)
+    if mode != F16X2:
+        return
+    # kbias and partial together: the affine-in-weights form of the same layer
+    w = c.w.to(DEV).contiguous()
+    sm, sq = c.x0.double().sum(dim=(1, 2, 3)).to(DEV), (c.x0.double() ** 2).sum(dim=(1, 2, 3)).to(DEV)
+
+    @functools.lru_cache(maxsize=None)
+    def prep(lo, hi):
+        return ops.conv_affine_pack(w, c.ga[lo:hi].contiguous(), c.gd[lo:hi].contiguous(), (sm[lo:hi].contiguous(), sq[lo:hi].contiguous(), D * H * W))
+    for relu in (True, False):
+        call = lambda lo, hi: ops.conv3d_gcr_split_persample(c.gx0[lo:hi].contiguous(), prep(lo, hi), relu=relu, partial=gpart[lo:hi].contiguous())   # noqa: E731,B023
+        _slot_independent(call, "gn_conv3d_gcr_split_persample", F16X2, dims, C0, Cout, names)
+        for name, B in zip(names, [starts[1][1] - 1] + [T for _, T in starts[1:]]):
+            out, (s, q, _) = ops.conv3d_gcr_split_persample(c.gx0[:B].contiguous(), prep(0, B), relu=relu, with_stats=True, partial=gpart[:B].contiguous())
+            assert last_kernel() == name
+            assert _stats_figure(out, s, q) <= 1.0, (name, B, "statistics")
+            want = ops.conv3d_gcr_split_persample(c.gx0[:B].contiguous(), prep(0, B), relu=False) + _upsampled_partial(gpart[:B], dims)
+            assert torch.equal(out, F.relu(want) if relu else want), (name, B, relu, "kbias, then the partial, then the ReLU")
 
 
 @pytest.mark.parametrize("mode", [F16X2, BF16X2], ids=["f16x2", "bf16x2"])

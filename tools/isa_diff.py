@@ -6,7 +6,9 @@
 Every .hip file of both directories is compiled to device assembly with the Makefile's flags (the directories must sit two levels below
 an include/ folder, as garmentnets_amd/csrc does).  A kernel is the text between its `_Z...:` label and the next one; comment lines and
 .file/.ident/.loc lines are ignored.  Prints one line per kernel that differs (instruction counts and the five resource values of its
-metadata, old -> new) and a summary; the exit status is 1 when any kernel differs, was added or was removed.
+metadata, old -> new) and a summary; the exit status is 1 when any kernel differs, was added or was removed.  For a kernel with matrix
+instructions the line also says whether the two streams are equal up to and including the kernel's last v_mfma: "main loop equal" means that
+only the epilogue behind it was re-scheduled, "main loop DIFFERS" that the change reached the loop itself.
 """
 import argparse, concurrent.futures as cf, os, re, subprocess, sys, tempfile
 
@@ -43,6 +45,12 @@ def kernels(path):
     return {k: (v, res.get(k, {})) for k, v in body.items()}
 
 
+def through_last_mfma(code):
+    """the code lines up to and including the last matrix instruction (None: the kernel has none)"""
+    last = max((i for i, l in enumerate(code) if l.startswith("v_mfma")), default=None)
+    return None if last is None else code[:last + 1]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old"), ap.add_argument("new")
@@ -72,7 +80,9 @@ def main():
             else:
                 res = " ".join(f"{r[1:]}={o[k][1].get(r)}->{n[k][1].get(r)}" for r in RES)
                 cnt = [sum(1 for l in x[k][0] if l[0] != "." and l[-1] != ":") for x in (o, n)]
-                print(f"{f}: {k}: DIFFERS instructions {cnt[0]}->{cnt[1]} {res}")
+                head = [through_last_mfma(x[k][0]) for x in (o, n)]
+                loop = "" if head[0] is None and head[1] is None else (" main loop equal" if head[0] == head[1] else " main loop DIFFERS")
+                print(f"{f}: {k}: DIFFERS instructions {cnt[0]}->{cnt[1]} {res}{loop}")
                 bad += 1
     print(f"{same} kernels identical, {bad} differ / added / removed")
     return 1 if bad else 0
