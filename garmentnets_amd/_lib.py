@@ -155,6 +155,8 @@ PROTOTYPES = {
     "gn_resident_mc_surface": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "gn_render_points_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "gn_color_idx_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gn_render_mesh_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gn_color_mesh_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -241,6 +243,12 @@ class ColorImage(ctypes.Structure):
     """GnColorImage (table entry of gn_color_idx_batch: the same bytes on the host and on the device)"""
     _fields_ = [("offset", _i64), ("count", _i64), ("mode", _i32), ("side", _i32), ("vmin", _f32), ("vmax", _f32), ("default_color", _f32 * 4),
                 ("num_overlays", _i32), ("pad", _i32), ("overlay", OverlayPoint * RENDER_MAX_OVERLAYS)]
+
+
+class MeshImage(ctypes.Structure):
+    """GnMeshImage (table entry of gn_render_mesh_batch / gn_color_mesh_batch: the same bytes on the host and on the device)"""
+    _fields_ = [("vert_begin", _i64), ("vert_end", _i64), ("face_begin", _i64), ("face_end", _i64), ("side", _i32), ("ambient", _f32),
+                ("default_color", _f32 * 4)]
 
 
 _lib = None

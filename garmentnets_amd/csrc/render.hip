@@ -1,7 +1,7 @@
 // render.hip -- the training monitors' images: the z-buffered point splat of the reference's common/rendering_util.py and its colouring, every image of
-// a batch in one launch each.
+// a batch in one launch each; below them the evaluation's mesh images, a triangle rasteriser behind the same camera ("mesh images").
 //
-//   gn_render_points_batch   fp32 points -> uint32 index images: per pixel the index of the covering point nearest to the camera
+//   gn_render_points_batch  fp32 points -> uint32 index images: per pixel the index of the covering point nearest to the camera
 //   gn_color_idx_batch       index images -> fp32 RGBA: a colour table or a scalar through viridis, the default colour elsewhere, then the overlay points
 //
 // The definitions ("Training monitors"; garmentnets_amd/visualize.py restates them in numpy, operation for operation):
@@ -191,5 +191,219 @@ extern "C" int gn_color_idx_batch(const uint32_t *idx_img, const GnColorImage *t
     hipLaunchKernelGGL(color_idx_batch_kernel, dim3((unsigned)gn_cdiv((int64_t)S * S, 256), (unsigned)I), dim3(256), 0, gn_stream(stream), idx_img, tab,
                        colors, values, S, out);
     GN_LAUNCH_CHECK("gn_color_idx_batch");
+    return GN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mesh images
+//   gn_render_mesh_batch     fp32 vertices + int32 faces -> uint32 index images: per pixel the index of the covering face nearest to the camera
+//   gn_color_mesh_batch      index images -> fp32 RGBA: the barycentric mix of the face's vertex colours times a headlight shade, the default colour elsewhere
+//
+// The definitions ("Mesh images"; visualize.py restates them in numpy, operation for operation):
+//   screen     u = cam[0] * (S - 1), v = cam[1] * (S - 1) in fp64 (rd_camera, as the splat); fixed point fx = rint(u * 256), fy = rint(v * 256), half to
+//              even; pixel (X, Y) is sampled at (256 X + 128, 256 Y + 128)
+//   not drawn  a vertex index outside [0, V), a non-finite coordinate, |fx| or |fy| > 2^24 at a vertex, area2 == 0
+//   two-sided  area2 = (bx - ax)(cy - ay) - (by - ay)(cx - ax) in int64; area2 < 0: b and c swap, with their depths and colours
+//   coverage   w_a = E(b, c, p), w_b = E(c, a, p), w_c = E(a, b, p), E(p, q, r) = (qx - px)(ry - py) - (qy - py)(rx - px); covered iff every w is > 0,
+//              or == 0 on an edge d = q - p with dy > 0 or (dy == 0 and dx < 0): a sample on a shared edge belongs to exactly one of its two faces
+//   depth      z = ((w_a z_a + w_b z_b) + w_c z_c) / area2 in fp64, every operation rounded on its own
+//   winner     the smallest z; equal depths: the lowest face index (strict < in ascending order); nobody: 0xFFFFFFFF
+// Every product has factors below 2^26, so the int64 values stay below 2^53 and convert to fp64 exactly.
+//
+// Shape: the splat's.  A workgroup owns a 16 x 16 tile, a thread one pixel; the faces stream through LDS in tiles of 256, one face per staging thread
+// (gather, camera, fixed point, the pixels whose samples lie in its bounding box), the ones that miss the tile dropped by the same ballot compaction.
+struct MrFace {
+    int x[3], y[3], v[3];                                                 // fixed-point screen coordinates and vertex indices, a b c after the swap
+    double z[3];
+    double cam[3][3];
+};
+
+// rint(c * (S - 1) * 256) as an int; false beyond 2^24 in magnitude
+__device__ __forceinline__ bool mr_fixed(double c, int S, int &f) {
+    const double r = rint(__dmul_rn(__dmul_rn(c, (double)(S - 1)), 256.0));
+    if (!(fabs(r) <= 16777216.0)) return false;
+    f = (int)r;
+    return true;
+}
+
+// E(p, q, r): every difference fits an int, every product an int64
+__device__ __forceinline__ long long mr_edge(int px, int py, int qx, int qy, int rx, int ry) {
+    return (long long)(qx - px) * (long long)(ry - py) - (long long)(qy - py) * (long long)(rx - px);
+}
+
+// the directed edge p -> q owns the samples on it
+__device__ __forceinline__ bool mr_owns(int px, int py, int qx, int qy) {
+    const int dx = qx - px, dy = qy - py;
+    return dy > 0 || (dy == 0 && dx < 0);
+}
+
+// the face `idx` (three indices into the V vertices at `verts`) in positive orientation; false: never drawn
+__device__ __forceinline__ bool mr_face(const float *__restrict__ verts, int64_t V, const int32_t *__restrict__ idx, int side, int S, MrFace &f) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int v = idx[k];
+        if (v < 0 || (int64_t)v >= V) return false;
+        if (!rd_camera(verts + 3 * (int64_t)v, side, f.cam[k])) return false;
+        if (!mr_fixed(f.cam[k][0], S, f.x[k]) || !mr_fixed(f.cam[k][1], S, f.y[k])) return false;
+        f.z[k] = f.cam[k][2];
+        f.v[k] = v;
+    }
+    const long long area2 = mr_edge(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2]);
+    if (area2 == 0) return false;
+    if (area2 < 0) {
+        int t = f.x[1]; f.x[1] = f.x[2]; f.x[2] = t;
+        t = f.y[1]; f.y[1] = f.y[2]; f.y[2] = t;
+        t = f.v[1]; f.v[1] = f.v[2]; f.v[2] = t;
+        double d = f.z[1]; f.z[1] = f.z[2]; f.z[2] = d;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { d = f.cam[1][j]; f.cam[1][j] = f.cam[2][j]; f.cam[2][j] = d; }
+    }
+    return true;
+}
+
+// the weights of the sample (px, py) in the positively oriented face; false: not covered
+__device__ __forceinline__ bool mr_cover(int ax, int ay, int bx, int by, int cx, int cy, int px, int py, long long &wa, long long &wb, long long &wc) {
+    wa = mr_edge(bx, by, cx, cy, px, py);
+    wb = mr_edge(cx, cy, ax, ay, px, py);
+    wc = mr_edge(ax, ay, bx, by, px, py);
+    return (wa > 0 || (wa == 0 && mr_owns(bx, by, cx, cy))) && (wb > 0 || (wb == 0 && mr_owns(cx, cy, ax, ay))) &&
+           (wc > 0 || (wc == 0 && mr_owns(ax, ay, bx, by)));
+}
+
+__global__ __launch_bounds__(RD_BLOCK) void render_mesh_batch_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
+                                                                     const GnMeshImage *__restrict__ tab, int S, uint32_t *__restrict__ out) {
+    __shared__ double sz[3][RD_BLOCK];
+    __shared__ int sx[3][RD_BLOCK], sy[3][RD_BLOCK];
+    __shared__ uint32_t si[RD_BLOCK];
+    __shared__ int scnt[RD_WAVES];
+    const GnMeshImage &im = tab[blockIdx.z];
+    const int64_t begin = im.face_begin, end = im.face_end, V = im.vert_end - im.vert_begin;
+    const float *iv = verts + 3 * im.vert_begin;
+    const int side = im.side;
+    const int tid = threadIdx.x, lane = tid & (GN_WAVE - 1), wave = tid / GN_WAVE;
+    const int tx0 = blockIdx.x * RD_TILE, ty0 = blockIdx.y * RD_TILE;
+    const int X = tx0 + (tid & (RD_TILE - 1)), Y = ty0 + tid / RD_TILE;
+    const int px = 256 * X + 128, py = 256 * Y + 128;
+    double best = INFINITY;
+    uint32_t best_idx = RD_NONE;
+    for (int64_t c0 = begin; c0 < end; c0 += RD_BLOCK) {                 // block-uniform bounds: every thread reaches every barrier
+        const int64_t j = c0 + tid;
+        bool hit = false;
+        MrFace f;
+        if (j < end && mr_face(iv, V, faces + 3 * j, side, S, f)) {
+            // the pixels whose samples 256 X + 128 lie within [min, max]: X from ceil((min - 128) / 256) to floor((max - 128) / 256)
+            const int xlo = (min(f.x[0], min(f.x[1], f.x[2])) + 127) >> 8, xhi = (max(f.x[0], max(f.x[1], f.x[2])) - 128) >> 8;
+            const int ylo = (min(f.y[0], min(f.y[1], f.y[2])) + 127) >> 8, yhi = (max(f.y[0], max(f.y[1], f.y[2])) - 128) >> 8;
+            hit = xlo <= xhi && ylo <= yhi && xlo <= min(tx0 + RD_TILE, S) - 1 && xhi >= tx0 && ylo <= min(ty0 + RD_TILE, S) - 1 && yhi >= ty0;
+        }
+        const unsigned long long mask = __ballot(hit);
+        __syncthreads();                                                 // the previous tile's scan is over: the stage may be overwritten
+        if (lane == 0) scnt[wave] = __popcll(mask);
+        __syncthreads();
+        int base = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < RD_WAVES; ++w) {
+            const int n = scnt[w];
+            base += w < wave ? n : 0;
+            total += n;
+        }
+        if (hit) {
+            const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { sx[k][slot] = f.x[k]; sy[k][slot] = f.y[k]; sz[k][slot] = f.z[k]; }
+            si[slot] = (uint32_t)(j - begin);
+        }
+        __syncthreads();
+        for (int s = 0; s < total; ++s) {                                // ascending index: a strict < keeps the first of equal depths
+            long long wa, wb, wc;
+            if (!mr_cover(sx[0][s], sy[0][s], sx[1][s], sy[1][s], sx[2][s], sy[2][s], px, py, wa, wb, wc)) continue;
+            const double num = __dadd_rn(__dadd_rn(__dmul_rn((double)wa, sz[0][s]), __dmul_rn((double)wb, sz[1][s])), __dmul_rn((double)wc, sz[2][s]));
+            const double z = __ddiv_rn(num, (double)(wa + wb + wc));     // the weights sum to area2
+            if (z < best) { best = z; best_idx = si[s]; }
+        }
+    }
+    if (X < S && Y < S) out[((int64_t)blockIdx.z * S + Y) * S + X] = best_idx;
+}
+
+__global__ __launch_bounds__(256) void color_mesh_batch_kernel(const uint32_t *__restrict__ idx_img, const float *__restrict__ verts,
+                                                               const int32_t *__restrict__ faces, const float *__restrict__ colors,
+                                                               const GnMeshImage *__restrict__ tab, int S, float *__restrict__ out) {
+    const GnMeshImage &im = tab[blockIdx.y];
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= S * S) return;
+    const int X = pix % S, Y = pix / S;
+    const int64_t o = (int64_t)blockIdx.y * S * S + pix;
+    const uint32_t idx = idx_img[o];
+    float4 col = make_float4(im.default_color[0], im.default_color[1], im.default_color[2], im.default_color[3]);
+    MrFace f;
+    long long wa, wb, wc;
+    if (idx != RD_NONE && (int64_t)idx < im.face_end - im.face_begin &&
+        mr_face(verts + 3 * im.vert_begin, im.vert_end - im.vert_begin, faces + 3 * (im.face_begin + idx), im.side, S, f) &&
+        mr_cover(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2], 256 * X + 128, 256 * Y + 128, wa, wb, wc)) {
+        const double area2 = (double)(wa + wb + wc);
+        const float ba = (float)__ddiv_rn((double)wa, area2), bb = (float)__ddiv_rn((double)wb, area2), bc = (float)__ddiv_rn((double)wc, area2);
+        const float4 ca = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[0]));
+        const float4 cb = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[1]));
+        const float4 cc = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[2]));
+        // n = (B - A) x (C - A) on the camera coordinates
+        const double ux = __dsub_rn(f.cam[1][0], f.cam[0][0]), uy = __dsub_rn(f.cam[1][1], f.cam[0][1]), uz = __dsub_rn(f.cam[1][2], f.cam[0][2]);
+        const double vx = __dsub_rn(f.cam[2][0], f.cam[0][0]), vy = __dsub_rn(f.cam[2][1], f.cam[0][1]), vz = __dsub_rn(f.cam[2][2], f.cam[0][2]);
+        const double nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy)), ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
+        const double nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+        const double len = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(nx, nx), __dmul_rn(ny, ny)), __dmul_rn(nz, nz)));
+        const double amb = (double)im.ambient;
+        double shade = amb;
+        if (len > 0.0 && len < INFINITY) shade = __dadd_rn(amb, __dmul_rn(__dsub_rn(1.0, amb), __ddiv_rn(fabs(nz), len)));
+        const float sh = (float)shade;
+        col.x = __fmul_rn(sh, __fadd_rn(__fadd_rn(__fmul_rn(ba, ca.x), __fmul_rn(bb, cb.x)), __fmul_rn(bc, cc.x)));
+        col.y = __fmul_rn(sh, __fadd_rn(__fadd_rn(__fmul_rn(ba, ca.y), __fmul_rn(bb, cb.y)), __fmul_rn(bc, cc.y)));
+        col.z = __fmul_rn(sh, __fadd_rn(__fadd_rn(__fmul_rn(ba, ca.z), __fmul_rn(bb, cb.z)), __fmul_rn(bc, cc.z)));
+        col.w = 1.f;
+    }
+    *reinterpret_cast<float4 *>(out + 4 * o) = col;
+}
+
+static int mr_check(const char *who, const int64_t *vseg_host, const int64_t *fseg_host, const GnMeshImage *tab_host, int I) {
+    for (int i = 0; i < I; ++i) {
+        const GnMeshImage &g = tab_host[i];
+        GN_REQUIRE(vseg_host[i] >= 0 && vseg_host[i + 1] >= vseg_host[i], "%s: image %d: vseg is not a non-decreasing CSR", who, i);
+        GN_REQUIRE(fseg_host[i] >= 0 && fseg_host[i + 1] >= fseg_host[i], "%s: image %d: fseg is not a non-decreasing CSR", who, i);
+        GN_REQUIRE(g.vert_begin == vseg_host[i] && g.vert_end == vseg_host[i + 1] && g.face_begin == fseg_host[i] && g.face_end == fseg_host[i + 1],
+                   "%s: image %d: the table's segments differ from vseg / fseg", who, i);
+        GN_REQUIRE(g.face_end - g.face_begin < (int64_t)RD_NONE, "%s: image %d: a segment of %lld faces (needs fewer than 2^32 - 1)", who, i,
+                   (long long)(g.face_end - g.face_begin));
+        GN_REQUIRE(g.side >= 0 && g.side <= 2, "%s: image %d: side=%d outside {0 front, 1 top, 2 left}", who, i, g.side);
+        GN_REQUIRE(g.ambient >= 0.f && g.ambient <= 1.f, "%s: image %d: ambient=%g outside [0, 1]", who, i, (double)g.ambient);
+    }
+    return GN_OK;
+}
+
+extern "C" int gn_render_mesh_batch(const float *verts, const int32_t *faces, const int64_t *vseg_host, const int64_t *fseg_host,
+                                    const GnMeshImage *tab_host, const GnMeshImage *tab, int I, int S, uint32_t *out, void *stream) {
+    int rc = rd_check_size("gn_render_mesh_batch", I, S);
+    if (rc != GN_OK) return rc;
+    if (I == 0) return GN_OK;
+    GN_REQUIRE(vseg_host && fseg_host && tab_host && tab && out, "gn_render_mesh_batch: null pointer");
+    rc = mr_check("gn_render_mesh_batch", vseg_host, fseg_host, tab_host, I);
+    if (rc != GN_OK) return rc;
+    GN_REQUIRE(fseg_host[I] == 0 || (faces && (vseg_host[I] == 0 || verts)), "gn_render_mesh_batch: null verts / faces");
+    const unsigned tiles = (unsigned)gn_cdiv(S, RD_TILE);
+    hipLaunchKernelGGL(render_mesh_batch_kernel, dim3(tiles, tiles, (unsigned)I), dim3(RD_BLOCK), 0, gn_stream(stream), verts, faces, tab, S, out);
+    GN_LAUNCH_CHECK("gn_render_mesh_batch");
+    return GN_OK;
+}
+
+extern "C" int gn_color_mesh_batch(const uint32_t *idx_img, const float *verts, const int32_t *faces, const float *colors, const int64_t *vseg_host,
+                                   const int64_t *fseg_host, const GnMeshImage *tab_host, const GnMeshImage *tab, int I, int S, float *out,
+                                   void *stream) {
+    int rc = rd_check_size("gn_color_mesh_batch", I, S);
+    if (rc != GN_OK) return rc;
+    if (I == 0) return GN_OK;
+    GN_REQUIRE(idx_img && vseg_host && fseg_host && tab_host && tab && out, "gn_color_mesh_batch: null pointer");
+    rc = mr_check("gn_color_mesh_batch", vseg_host, fseg_host, tab_host, I);
+    if (rc != GN_OK) return rc;
+    GN_REQUIRE(fseg_host[I] == 0 || (faces && (vseg_host[I] == 0 || (verts && colors))), "gn_color_mesh_batch: null verts / faces / colors");
+    hipLaunchKernelGGL(color_mesh_batch_kernel, dim3((unsigned)gn_cdiv((int64_t)S * S, 256), (unsigned)I), dim3(256), 0, gn_stream(stream), idx_img, verts,
+                       faces, colors, tab, S, out);
+    GN_LAUNCH_CHECK("gn_color_mesh_batch");
     return GN_OK;
 }

@@ -2165,6 +2165,72 @@ def color_idx_batch(idx_img, images, colors=None, values=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ mesh images
+def _mesh_args(who, verts, faces, vseg, fseg, sides, ambients, default_colors):
+    """the checked tensors, the two host CSRs and the GnMeshImage table (host, device) of the mesh entries.  What only sizes an access is refused
+    here (a segment beyond its tensor); sides, ambients and the CSRs' order are the entry's to refuse, in its words"""
+    verts, faces = _chk(verts, torch.float32, "verts"), _chk(faces, _i32, "faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise ValueError(f"{who}: expected (V, 3) fp32 verts and (F, 3) int32 faces on one device, got {tuple(verts.shape)}, {tuple(faces.shape)}")
+    vseg = np.ascontiguousarray(np.asarray(vseg, dtype=np.int64).reshape(-1))
+    fseg = np.ascontiguousarray(np.asarray(fseg, dtype=np.int64).reshape(-1))
+    n = vseg.shape[0] - 1
+    side = [_side(s) for s in sides]
+    ambients = [0.35] * n if ambients is None else list(ambients)
+    default_colors = [(1.0, 1.0, 1.0, 0.0)] * n if default_colors is None else list(default_colors)
+    if n < 0 or fseg.shape[0] != n + 1 or len(side) != n or len(ambients) != n or len(default_colors) != n:
+        raise ValueError(f"{who}: vseg and fseg hold I + 1 entries for I sides, ambients and default colours")
+    if n and (vseg.max() > verts.shape[0] or fseg.max() > faces.shape[0]):
+        raise ValueError(f"{who}: a segment ends beyond its tensor ({verts.shape[0]} verts, {faces.shape[0]} faces)")
+    tab = (_lib.MeshImage * max(n, 1))()
+    for i in range(n):
+        e = tab[i]
+        e.vert_begin, e.vert_end, e.face_begin, e.face_end = int(vseg[i]), int(vseg[i + 1]), int(fseg[i]), int(fseg[i + 1])
+        e.side, e.ambient = side[i], float(ambients[i])
+        e.default_color[:] = [float(v) for v in default_colors[i]]
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(verts.device)
+    return verts, faces, vseg, fseg, tab, tab_dev, n
+
+
+def render_mesh_batch(verts, faces, vseg, fseg, sides, img_size):
+    """the triangle rasteriser, I images in ONE launch (gn_render_mesh_batch) -> (I, S, S) int32 holding the uint32 index images (0xFFFFFFFF, i.e. -1,
+    where no face covers the pixel's sample).  verts: (V, 3) fp32 and faces: (F, 3) int32 on the device; image i draws the faces fseg[i] .. fseg[i+1],
+    which index into the vertices vseg[i] .. vseg[i+1] from 0, seen from sides[i].  A pixel holds the index, counted from fseg[i], of the covering face
+    with the smallest interpolated fp64 depth (equal depths: the lowest index).  DESIGN.md "Mesh images" has the rules."""
+    verts, faces, vseg, fseg, tab, tab_dev, n = _mesh_args("render_mesh_batch", verts, faces, vseg, fseg, sides, None, None)
+    S = _render_dims("gn_render_mesh_batch", n, img_size)
+    out = torch.empty((n, S, S), dtype=_i32, device=verts.device)
+    if n == 0:
+        return out
+    _lib.call("gn_render_mesh_batch", _p(verts), _p(faces), vseg.ctypes.data_as(ctypes.c_void_p), fseg.ctypes.data_as(ctypes.c_void_p),
+              ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), n, S, _p(out), _stream())
+    return out
+
+
+def color_mesh_batch(idx_img, verts, faces, colors, vseg, fseg, sides, ambients=None, default_colors=None):
+    """render_mesh_batch's index images -> (I, S, S, 4) fp32 RGBA in ONE launch (gn_color_mesh_batch): shade * the barycentric mix of the winning
+    face's vertex colours with alpha 1, default_colors[i] where nobody covers.  colors: (V, 4) fp32, one row per row of verts; ambients[i] in [0, 1]
+    (default 0.35: a look, not a measurement): shade = ambient + (1 - ambient) * |n_z| / |n| of the face's camera-space normal."""
+    idx_img = _chk(idx_img, _i32, "idx_img")
+    if idx_img.dim() != 3 or idx_img.shape[1] != idx_img.shape[2]:
+        raise ValueError(f"idx_img: expected an (I, S, S) tensor, got {tuple(idx_img.shape)}")
+    verts, faces, vseg, fseg, tab, tab_dev, n = _mesh_args("color_mesh_batch", verts, faces, vseg, fseg, sides, ambients, default_colors)
+    colors = _chk(colors, torch.float32, "colors")
+    if colors.dim() != 2 or colors.shape[1] != 4 or colors.shape[0] != verts.shape[0] or colors.device != verts.device or idx_img.device != verts.device:
+        raise ValueError(f"color_mesh_batch: expected ({verts.shape[0]}, 4) colors on {verts.device}, got {tuple(colors.shape)} on {colors.device}")
+    if idx_img.shape[0] != n:
+        raise ValueError(f"color_mesh_batch: {n} image entries for {idx_img.shape[0]} index images")
+    S = _render_dims("gn_color_mesh_batch", n, idx_img.shape[1])
+    if colors.data_ptr() % 16:
+        colors = colors.clone()                              # (the kernel reads a row as one float4)
+    out = torch.empty((n, S, S, 4), dtype=torch.float32, device=verts.device)
+    if n == 0:
+        return out
+    _lib.call("gn_color_mesh_batch", _p(idx_img), _p(verts), _p(faces), _p(colors), vseg.ctypes.data_as(ctypes.c_void_p),
+              fseg.ctypes.data_as(ctypes.c_void_p), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), n, S, _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ gradient pack (data-parallel training)
 def grad_pack_table(rows, device):
     """the device table of gn_grad_pack.  rows: [(source pointer or None, dst_off, numel)] in the order of their workgroups; dst_off a multiple of 4

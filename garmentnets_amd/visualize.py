@@ -16,6 +16,10 @@ sides and sits INSIDE render_points_idx (the reference's takes camera coordinate
 reference's uint32 cast wraps there); a point with any non-finite coordinate is not drawn; render_confidence_pair honours its img_size / kernel_size
 (the reference ignores them and renders 256 / 4, which are the defaults here).  render_wnf / render_wnf_pair (skimage's resize; never called in
 training) are not provided.
+
+Mesh images (the evaluation's visualisation; DESIGN.md, "Mesh images") are described by `mesh_spec` (vertices, faces, a colour row per vertex, side,
+ambient) and rendered by `render_mesh_batch`, again on the device (ops.render_mesh_batch + ops.color_mesh_batch, one launch pair for all of them) or
+by the numpy restatement: a z-buffered, two-sided, shaded triangle rasteriser whose coverage is decided in integers.
 """
 import os
 import re
@@ -232,6 +236,183 @@ def render_idx_batch(points, sides, kernel_sizes, img_size=256, backend="device"
     seg = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])]).astype(np.int64)
     joint = torch.cat(pts).contiguous() if pts else torch.empty((0, 3), dtype=torch.float32, device=device or "cuda")
     return ops.render_points_batch(joint, seg, sides, kernel_sizes, S).cpu().numpy().view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ mesh images
+# DESIGN.md "Mesh images": a z-buffered, two-sided, shaded triangle rasteriser behind the same camera.  Coverage is decided in integers on 1/256-pixel
+# fixed-point coordinates, so the numpy restatement below and csrc/render.hip agree bit for bit.
+MESH_SUBPIXEL = 256
+MESH_COORD_LIMIT = 2 ** 24
+DEFAULT_AMBIENT = 0.35                          # a look, not a measurement: how dark a face seen edge-on gets
+
+
+def _edge(px, py, qx, qy, rx, ry):
+    """E(p, q, r) = (qx - px)(ry - py) - (qy - py)(rx - px) in int64"""
+    return (qx - px) * (ry - py) - (qy - py) * (rx - px)
+
+
+def _owns(px, py, qx, qy):
+    """the directed edge p -> q owns the samples on it: dy > 0 or (dy == 0 and dx < 0)"""
+    dx, dy = qx - px, qy - py
+    return (dy > 0) | ((dy == 0) & (dx < 0))
+
+
+def _mesh_faces(verts, faces, side, S):
+    """the drawn faces in positive orientation -> (index [D] int64, vertex indices [D, 3] after the swap, fx, fy [D, 3] int64, cam [D, 3, 3] fp64)"""
+    v = _host(verts).reshape(-1, 3)
+    f = _host(faces, np.int64).reshape(-1, 3)
+    ok = ((f >= 0) & (f < len(v))).all(axis=1)
+    keep = np.flatnonzero(ok)
+    f = f[keep]
+    with np.errstate(invalid="ignore", over="ignore"):
+        cam = to_camera(v, side)[f]                                                     # (D, 3 corners, 3 coordinates)
+        fin = np.isfinite(v).all(axis=1)[f].all(axis=1)
+        fx = np.rint(cam[:, :, 0] * np.float64(S - 1) * np.float64(MESH_SUBPIXEL))      # half to even
+        fy = np.rint(cam[:, :, 1] * np.float64(S - 1) * np.float64(MESH_SUBPIXEL))
+        fin &= (np.abs(fx) <= MESH_COORD_LIMIT).all(axis=1) & (np.abs(fy) <= MESH_COORD_LIMIT).all(axis=1)
+    keep, f, cam = keep[fin], f[fin], cam[fin]
+    fx, fy = fx[fin].astype(np.int64), fy[fin].astype(np.int64)
+    area2 = _edge(fx[:, 0], fy[:, 0], fx[:, 1], fy[:, 1], fx[:, 2], fy[:, 2])
+    drawn = area2 != 0
+    keep, f, cam, fx, fy, area2 = keep[drawn], f[drawn], cam[drawn], fx[drawn], fy[drawn], area2[drawn]
+    order = np.where((area2 < 0)[:, None], np.array([0, 2, 1]), np.array([0, 1, 2]))    # two-sided: b and c swap, with everything they carry
+    rows = np.arange(len(keep))[:, None]
+    return keep, f[rows, order], fx[rows, order], fy[rows, order], cam[rows, order]
+
+
+def _mesh_weights(fx, fy, px, py):
+    """-> (w_a, w_b, w_c, covered) of the samples (px, py) in the faces (fx, fy) [.., 3], all int64"""
+    ax, ay, bx, by, cx, cy = fx[..., 0], fy[..., 0], fx[..., 1], fy[..., 1], fx[..., 2], fy[..., 2]
+    wa, wb, wc = _edge(bx, by, cx, cy, px, py), _edge(cx, cy, ax, ay, px, py), _edge(ax, ay, bx, by, px, py)
+    covered = ((wa > 0) | ((wa == 0) & _owns(bx, by, cx, cy))) & ((wb > 0) | ((wb == 0) & _owns(cx, cy, ax, ay))) & \
+        ((wc > 0) | ((wc == 0) & _owns(ax, ay, bx, by)))
+    return wa, wb, wc, covered
+
+
+def _render_mesh_idx_numpy(verts, faces, side, S):
+    return _render_mesh_numpy(verts, faces, side, S)[0]
+
+
+def _render_mesh_numpy(verts, faces, side, S):
+    """-> (index image (S, S) uint32, the winners' depths (S, S) fp64, +inf where nobody covers)"""
+    img = np.full((S, S), DEFAULT_IDX, dtype=np.uint32)
+    zimg = np.full((S, S), np.inf)
+    index, _, fx, fy, cam = _mesh_faces(verts, faces, side, S)
+    # the pixels whose samples 256 X + 128 lie in the face's bounding box, within the image
+    half = MESH_SUBPIXEL // 2
+    xlo = np.maximum(-((-(fx.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
+    xhi = np.minimum((fx.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
+    ylo = np.maximum(-((-(fy.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
+    yhi = np.minimum((fy.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
+    wd, ht = np.maximum(xhi - xlo + 1, 0), np.maximum(yhi - ylo + 1, 0)
+    n = wd * ht
+    if n.sum() == 0:
+        return img, zimg
+    face = np.repeat(np.arange(len(index)), n)                                          # every (face, pixel of its box) pair
+    local = np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n)
+    X, Y = xlo[face] + local % wd[face], ylo[face] + local // wd[face]
+    wa, wb, wc, covered = _mesh_weights(fx[face], fy[face], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
+    face, X, Y, wa, wb, wc = face[covered], X[covered], Y[covered], wa[covered], wb[covered], wc[covered]
+    z = cam[face][:, :, 2]
+    depth = ((wa.astype(np.float64) * z[:, 0] + wb.astype(np.float64) * z[:, 1]) + wc.astype(np.float64) * z[:, 2]) / (wa + wb + wc).astype(np.float64)
+    pixel = Y * S + X
+    order = np.lexsort((index[face], depth, pixel))                                     # per pixel: the smallest depth, then the lowest index
+    first = np.ones(order.size, dtype=bool)
+    first[1:] = pixel[order][1:] != pixel[order][:-1]
+    img.reshape(-1)[pixel[order][first]] = index[face][order][first].astype(np.uint32)
+    zimg.reshape(-1)[pixel[order][first]] = depth[order][first]
+    return img, zimg
+
+
+def _color_mesh_numpy(idx_img, verts, faces, colors, side, ambient, default_color):
+    S = idx_img.shape[0]
+    img = np.empty((S, S, 4), dtype=np.float32)
+    img[:, :] = np.asarray(default_color, dtype=np.float32)
+    index, f, fx, fy, cam = _mesh_faces(verts, faces, side, S)
+    Y, X = np.nonzero(idx_img != DEFAULT_IDX)
+    if len(Y) == 0:
+        return img
+    row = np.searchsorted(index, idx_img[Y, X].astype(np.int64))                        # the winner is a drawn face: recompute its weights
+    half = MESH_SUBPIXEL // 2
+    wa, wb, wc, covered = _mesh_weights(fx[row], fy[row], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
+    assert covered.all() and np.array_equal(index[row], idx_img[Y, X])
+    area2 = (wa + wb + wc).astype(np.float64)
+    beta = [(w.astype(np.float64) / area2).astype(np.float32) for w in (wa, wb, wc)]
+    c = _host(colors).reshape(-1, 4)[f[row]]                                            # (P, 3 corners, 4)
+    rgb = (beta[0][:, None] * c[:, 0, :3] + beta[1][:, None] * c[:, 1, :3]) + beta[2][:, None] * c[:, 2, :3]
+    A, B, C = cam[row][:, 0], cam[row][:, 1], cam[row][:, 2]
+    u, w = B - A, C - A
+    nx, ny, nz = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+    amb = np.float64(np.float32(ambient))
+    with np.errstate(all="ignore"):
+        length = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        shade = np.where((length > 0) & np.isfinite(length), amb + (1.0 - amb) * (np.abs(nz) / length), amb)
+    img[Y, X, :3] = shade.astype(np.float32)[:, None] * rgb
+    img[Y, X, 3] = 1
+    return img
+
+
+def mesh_spec(verts, faces, colors, side="front", ambient=DEFAULT_AMBIENT, default_color=(1, 1, 1, 0)):
+    """one mesh image: (V, 3) vertices and (F, 3) faces seen from `side`, coloured per vertex by `colors` ((V, 4) RGBA; scalar colourings are built
+    with `viridis`), shaded by ambient + (1 - ambient) * |n_z| / |n|.  verts / faces / colors: numpy arrays or torch tensors"""
+    if side not in SIDES:
+        raise ValueError(f"side={side!r}: expected one of {tuple(SIDES)}")
+    if len(colors) != len(verts):
+        raise ValueError(f"mesh_spec: one colour row per vertex ({len(verts)} vertices, {len(colors)} rows)")
+    if len(default_color) != 4:
+        raise ValueError("default_color: expected 4 floats (RGBA)")
+    return {"verts": verts, "faces": faces, "colors": colors, "side": side, "ambient": float(ambient),
+            "default_color": tuple(float(v) for v in default_color)}
+
+
+def _mesh_device_args(specs, device):
+    import torch
+
+    def dev(a, dtype, width):
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(_host(a, np.int32 if dtype == torch.int32 else np.float32)).to(device or "cuda")
+        return a.detach().to(dtype).reshape(-1, width)
+
+    verts = [dev(s["verts"], torch.float32, 3) for s in specs]
+    faces = [dev(s["faces"], torch.int32, 3) for s in specs]
+    colors = [dev(s["colors"], torch.float32, 4) for s in specs]
+    vseg = np.concatenate([[0], np.cumsum([v.shape[0] for v in verts])]).astype(np.int64)
+    fseg = np.concatenate([[0], np.cumsum([f.shape[0] for f in faces])]).astype(np.int64)
+    return torch.cat(verts).contiguous(), torch.cat(faces).contiguous(), torch.cat(colors).contiguous(), vseg, fseg
+
+
+def render_mesh_idx_batch(specs, img_size=256, backend="device", device=None):
+    """the index images alone -> (I, S, S) uint32 on the host: per pixel the face (counted within its image) that covers the pixel's sample nearest
+    to the camera, 0xFFFFFFFF where there is none"""
+    specs, S = list(specs), int(img_size)
+    if backend not in ("device", "numpy"):
+        raise ValueError(f"backend={backend!r}: expected 'device' or 'numpy'")
+    if not specs:
+        return np.empty((0, S, S), np.uint32)
+    if backend == "numpy":
+        return np.stack([_render_mesh_idx_numpy(s["verts"], s["faces"], s["side"], S) for s in specs])
+    from . import ops
+    verts, faces, _, vseg, fseg = _mesh_device_args(specs, device)
+    return ops.render_mesh_batch(verts, faces, vseg, fseg, [s["side"] for s in specs], S).cpu().numpy().view(np.uint32)
+
+
+def render_mesh_batch(specs, img_size=256, backend="device", device=None):
+    """every mesh image of `specs` (mesh_spec) -> (I, S, S, 4) fp32 on the host.  backend "device": one launch pair (ops.render_mesh_batch,
+    ops.color_mesh_batch) for all of them; "numpy": the restatement"""
+    specs, S = list(specs), int(img_size)
+    if backend not in ("device", "numpy"):
+        raise ValueError(f"backend={backend!r}: expected 'device' or 'numpy'")
+    if not specs:
+        return np.empty((0, S, S, 4), dtype=np.float32)
+    if backend == "numpy":
+        return np.stack([_color_mesh_numpy(_render_mesh_idx_numpy(s["verts"], s["faces"], s["side"], S), s["verts"], s["faces"], s["colors"],
+                                           s["side"], s["ambient"], s["default_color"]) for s in specs])
+    from . import ops
+    verts, faces, colors, vseg, fseg = _mesh_device_args(specs, device)
+    sides = [s["side"] for s in specs]
+    idx = ops.render_mesh_batch(verts, faces, vseg, fseg, sides, S)
+    return ops.color_mesh_batch(idx, verts, faces, colors, vseg, fseg, sides, [s["ambient"] for s in specs],
+                                [s["default_color"] for s in specs]).cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------ the reference's API

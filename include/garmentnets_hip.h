@@ -1004,6 +1004,29 @@ int gn_render_points_batch(const float *points, const int64_t *seg_host, const i
 int gn_color_idx_batch(const uint32_t *idx_img, const GnColorImage *tab_host, const GnColorImage *tab, const float *colors, const float *values, int I,
                        int S, float *out, void *stream);
 
+/* ---- Mesh images (csrc/render.hip; DESIGN.md "Mesh images"): a z-buffered, two-sided, shaded triangle rasteriser behind the same camera, every image of
+ * a batch in one launch each.  Coverage and ownership of shared edges are decided in integers on 1/256-pixel fixed-point coordinates; no atomics. ---- */
+
+typedef struct {
+    int64_t vert_begin, vert_end;    /* the image's rows of verts and of colors; a face indexes from vert_begin */
+    int64_t face_begin, face_end;    /* the image's rows of faces; a pixel's index counts from face_begin */
+    int32_t side;                    /* GN_RENDER_* */
+    float ambient;                   /* shade = ambient + (1 - ambient) * |n_z| / |n|, in [0, 1] */
+    float default_color[4];          /* pixels nobody covers */
+} GnMeshImage;
+
+/* verts [..][3] fp32, faces [..][3] int32 -> out [I][S][S] uint32: per pixel the index (from face_begin) of the face that covers the pixel's sample with
+ * the smallest interpolated camera depth (fp64), the lowest index among equal depths, 0xFFFFFFFF when nobody covers it.  Never drawn: a face with a vertex
+ * index outside [0, vert_end - vert_begin), with a non-finite coordinate, with a fixed-point coordinate beyond 2^24 in magnitude, or of zero area.
+ * vseg_host, fseg_host [I+1] and tab_host [I]: HOST arrays, checked here (non-decreasing CSRs that the table repeats, fewer than 2^32 - 1 faces per image,
+ * side in {0, 1, 2}, ambient in [0, 1], I <= 65535, S in [1, GN_RENDER_MAX_SIZE]); tab: the same table in DEVICE memory, what the kernel reads. */
+int gn_render_mesh_batch(const float *verts, const int32_t *faces, const int64_t *vseg_host, const int64_t *fseg_host, const GnMeshImage *tab_host,
+                         const GnMeshImage *tab, int I, int S, uint32_t *out, void *stream);
+/* idx_img [I][S][S] (gn_render_mesh_batch's, same verts / faces / table) -> out [I][S][S][4] fp32 RGBA: default_color where the index is 0xFFFFFFFF,
+ * else shade * the barycentric mix of the face's three rows of colors [..][4] (one row per row of verts), alpha 1. */
+int gn_color_mesh_batch(const uint32_t *idx_img, const float *verts, const int32_t *faces, const float *colors, const int64_t *vseg_host,
+                        const int64_t *fseg_host, const GnMeshImage *tab_host, const GnMeshImage *tab, int I, int S, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
