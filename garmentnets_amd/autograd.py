@@ -38,7 +38,7 @@ import torch.nn.functional as F
 from . import arith as AR
 from . import ops
 from .components import unet3d as U
-from .components.mlp import HipLinear, MLPStack, fold_batchnorm, pack_linear, pack_wb, param_cache
+from .components.mlp import HipLinear, MLPStack, fold_batchnorm, generation, pack_linear, pack_wb, param_cache
 from .components.pointnet2 import Segments, _example_self_src
 
 __all__ = ["fps", "radius", "ball_table", "point_conv_max", "global_max_pool", "knn_interpolate", "scatter", "grid_sample_points",
@@ -263,91 +263,53 @@ class _ConvGcr(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_y, _gs, _gq):
+        """One body for every unet3d.conv_grad_plan.  Under ("fp32", "fp32") -- the default -- the launches are those of csrc/unet_grad.hip alone.  With a
+        gradient on the split-operand kernels (arith.conv_grad_mode = "f16x2") one masking pass (gn_relu_mask_max) serves both: the masked gradient g,
+        its per-sample maximum and the power-of-two scales from it, found on the device.  The weight gradient then reads the forward's operand with the
+        sample's activation scale (the affine of the f16x2 forward); the data gradient is the forward's direct split kernel on the pack of the flipped /
+        transposed weight.  The GroupNorm backward stays fp32."""
         src0, src1, y, s0, q0, s1, q1, weight, gamma, beta = ctx.saved_tensors
-        plan = U.conv_grad_plan(ctx.arith or AR.DEFAULT, tuple(src0.shape[1:4]), src0.shape[-1], 0 if src1 is None else src1.shape[-1], y.shape[-1])
-        if plan.data != "fp32" or plan.weight != "fp32":
-            return _conv_gcr_backward_split(ctx, grad_y, plan)
-        conv, gn = ctx.conv, ctx.conv.groupnorm
+        conv, gn, arith = ctx.conv, ctx.conv.groupnorm, ctx.arith or AR.DEFAULT
         need = ctx.needs_input_grad
         lay = conv._layout(src0, src1)
         S0, S1 = src0.shape[-1], 0 if src1 is None else src1.shape[-1]
+        plan = U.conv_grad_plan(arith, tuple(src0.shape[1:4]), S0, S1, y.shape[-1])
         real = None if lay is None else lay.real
         st0 = (s0, q0, src0[0].numel() // S0)
         st1 = None if src1 is None else (s1, q1, src1[0].numel() // S1)
         gamma = gamma.detach().float().contiguous()
         dy = grad_y.contiguous()
+        need_data = any(need[i] for i in (0, 1, 3, 4))
+        g = gmax = scale = inv = None
+        if (need[2] and plan.weight == "f16x2") or (need_data and plan.data == "f16x2"):
+            g, gmax, scale, inv = ops.relu_mask_max(y, dy)
         dw = None
         if need[2]:
-            a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta.detach().float().contiguous(), real=real)
-            dw = ops.conv3d_bwd_weight(src0, src1, a, d, y, dy)
+            beta = beta.detach().float().contiguous()
+            if plan.weight == "f16x2":
+                a, d, x_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True, real=real)
+                dw = ops.conv3d_bwd_weight_split(src0, src1, a, d, None, g, x_inv=x_inv, gmax=gmax)      # (g is masked already: no second read of y)
+            else:
+                a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real)
+                dw = ops.conv3d_bwd_weight(src0, src1, a, d, y, dy)
             if lay is not None:                   # stored -> real channels (the pad rows / columns are exact zeros)
                 cols = torch.cat([torch.arange(r, device=dw.device) + o for r, o in zip(lay.real, (0, S0))])
                 dw = dw[:conv.conv.out_channels].index_select(1, cols)
-        if not any(need[i] for i in (0, 1, 3, 4)):
+        if not need_data:
             return None, None, dw, None, None, None, None, None, None, None, None
-        # d operand = conv_transpose(g, W): the forward fp32 kernel on the flipped / transposed pack
+        # d operand = conv_transpose(g, W): the forward kernels on the flipped / transposed pack.  (The saved weight IS conv.conv.weight at the forward's
+        # version -- unpacking it has checked that -- so the module's generation-keyed cache holds its packs.)
         cin_p = -(-(S0 + S1) // 32) * 32
-        # (the saved weight IS conv.conv.weight at the forward's version -- unpacking it has checked that -- so the module's version-keyed caches hold its packs)
-        wsrc = weight if lay is None else conv._padded_weight(lay)
-        wpt = param_cache(conv, "_split_packs").get(conv._gen(lay), "bwd_data", lambda: ops.pack_conv_weight_bwd_data(wsrc))
-        dxn = ops.conv3d_bwd_data(ops.relu_mask(y, dy), wpt, cin_p)
+        if plan.data == "f16x2":
+            dxn = ops.conv3d_bwd_data_split(g, scale, inv, conv.weight_pack("bwd_data_split", lay, device=arith.device_packs), cin_p)
+        else:
+            dxn = ops.conv3d_bwd_data(g if g is not None else ops.relu_mask(y, dy), conv.weight_pack("bwd_data", lay), cin_p)
         t0 = ops.groupnorm_bwd_stats(dxn, 0, src0)
         t1 = None if src1 is None else ops.groupnorm_bwd_stats(dxn, S0, src1, half=True)
         p, q, r, dgamma, dbeta = ops.groupnorm_bwd_coef(t0, t1, st0, st1, gn.num_groups, gn.eps, gamma, real=real)
         d0 = ops.groupnorm_bwd_apply(dxn, 0, src0, p, q, r, 0) if need[0] else None
         d1 = ops.groupnorm_bwd_apply(dxn, S0, src1, p, q, r, S0, half=True) if src1 is not None and need[1] else None
         return d0, d1, dw, dgamma if need[3] else None, dbeta if need[4] else None, None, None, None, None, None, None
-
-
-def _conv_gcr_backward_split(ctx, grad_y, plan):
-    """_ConvGcr.backward under arith.conv_grad_mode = "f16x2" (plan: unet3d.conv_grad_plan, at least one gradient on the split-operand kernels).  One
-    masking pass (gn_relu_mask_max) serves both gradients: the masked gradient g, its per-sample maximum and the power-of-two scales from it, found on
-    the device.  The weight gradient reads the forward's operand with the sample's activation scale (the affine of the f16x2 forward); the data gradient
-    is the forward's direct split kernel on the pack of the flipped / transposed weight.  The GroupNorm backward stays fp32."""
-    src0, src1, y, s0, q0, s1, q1, weight, gamma, beta = ctx.saved_tensors
-    conv, gn, arith = ctx.conv, ctx.conv.groupnorm, ctx.arith or AR.DEFAULT
-    need = ctx.needs_input_grad
-    lay = conv._layout(src0, src1)
-    S0, S1 = src0.shape[-1], 0 if src1 is None else src1.shape[-1]
-    real = None if lay is None else lay.real
-    st0 = (s0, q0, src0[0].numel() // S0)
-    st1 = None if src1 is None else (s1, q1, src1[0].numel() // S1)
-    gamma = gamma.detach().float().contiguous()
-    beta = beta.detach().float().contiguous()
-    dy = grad_y.contiguous()
-    need_data = any(need[i] for i in (0, 1, 3, 4))
-    g = gmax = scale = inv = None
-    if (need[2] and plan.weight == "f16x2") or (need_data and plan.data == "f16x2"):
-        g, gmax, scale, inv = ops.relu_mask_max(y, dy)
-    dw = None
-    if need[2]:
-        if plan.weight == "f16x2":
-            a, d, x_inv = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, with_act_scale=True, real=real)
-            dw = ops.conv3d_bwd_weight_split(src0, src1, a, d, None, g, x_inv=x_inv, gmax=gmax)      # (g is masked already: no second read of y)
-        else:
-            a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real)
-            dw = ops.conv3d_bwd_weight(src0, src1, a, d, y, dy)
-        if lay is not None:                   # stored -> real channels (the pad rows / columns are exact zeros)
-            cols = torch.cat([torch.arange(r, device=dw.device) + o for r, o in zip(lay.real, (0, S0))])
-            dw = dw[:conv.conv.out_channels].index_select(1, cols)
-    if not need_data:
-        return None, None, dw, None, None, None, None, None, None, None, None
-    cin_p = -(-(S0 + S1) // 32) * 32
-    wsrc = weight if lay is None else conv._padded_weight(lay)
-    cache, gen = param_cache(conv, "_split_packs"), conv._gen(lay)
-    if plan.data == "f16x2":
-        dev = bool(arith.device_packs) and wsrc.is_cuda
-        pack = cache.get(gen, ("device", "bwd_data_split") if dev else "bwd_data_split", lambda: ops.pack_conv_weight_bwd_data_split(wsrc, dev))
-        dxn = ops.conv3d_bwd_data_split(g, scale, inv, pack, cin_p)
-    else:
-        wpt = cache.get(gen, "bwd_data", lambda: ops.pack_conv_weight_bwd_data(wsrc))
-        dxn = ops.conv3d_bwd_data(g if g is not None else ops.relu_mask(y, dy), wpt, cin_p)
-    t0 = ops.groupnorm_bwd_stats(dxn, 0, src0)
-    t1 = None if src1 is None else ops.groupnorm_bwd_stats(dxn, S0, src1, half=True)
-    p, q, r, dgamma, dbeta = ops.groupnorm_bwd_coef(t0, t1, st0, st1, gn.num_groups, gn.eps, gamma, real=real)
-    d0 = ops.groupnorm_bwd_apply(dxn, 0, src0, p, q, r, 0) if need[0] else None
-    d1 = ops.groupnorm_bwd_apply(dxn, S0, src1, p, q, r, S0, half=True) if src1 is not None and need[1] else None
-    return d0, d1, dw, dgamma if need[3] else None, dbeta if need[4] else None, None, None, None, None, None, None
 
 
 def _check_gcr(conv):
@@ -460,7 +422,7 @@ def unet3d(model, x, arith=None):
         v, stats = _conv(dc.SingleConv2, v, None, stats, None, arith)
     # the final 1x1x1 convolution: a linear block over the rows of stored channels (FinalConv1x1.run's launch on the same pack)
     fc = model.final_conv
-    wp, b, k = _grad_layers(fc, fc._pack)
+    wp, b, k = fc.packed()
     y = _LinearBlock.apply(v.reshape(-1, v.shape[-1]), fc.weight, fc.bias, None, None, (wp, b, None, None, k), False, None, fc, 0)
     return y.reshape(*v.shape[:-1], fc.out_channels).permute(0, 4, 1, 2, 3)
 
@@ -511,9 +473,8 @@ class _LinearBlock(torch.autograd.Function):
 
 def _wt_pack(ctx, weight):
     """the transposed weight pack of a block's dX = g W.  (The saved weight IS the module's at the forward's version -- unpacking it has checked that -- so
-    the version-keyed cache holds its pack, and ctx.wp, the forward's pack of it, holds its values.)"""
-    gen = (weight.device,) + tuple(p._version for p in ctx.owner.parameters())
-    return param_cache(ctx.owner, "_grad_packs").get(gen, ("wt", ctx.idx), lambda: pack_wb(ctx.wp[:, :ctx.k].t().contiguous(), None)[0])
+    the generation-keyed cache holds its pack, and ctx.wp, the forward's pack of it, holds its values.)"""
+    return param_cache(ctx.owner, "_grad_packs").get(generation(ctx.owner), ("wt", ctx.idx), lambda: pack_wb(ctx.wp[:, :ctx.k].t().contiguous(), None)[0])
 
 
 def _bn_update_buffers(bn, mean, m2, M):
@@ -590,20 +551,13 @@ def _fp32_features(x, who):
     return x
 
 
-def _grad_layers(module, pack):
-    """the forward's packs at the parameters' PRESENT versions (PackedModule.packed() is not keyed by them: it serves inference, where nothing updates
-    a parameter in place)"""
-    gen = (next(module.parameters()).device,) + tuple(t._version for t in list(module.parameters()) + list(module.buffers()))
-    return param_cache(module, "_grad_fwd_packs").get(gen, "layers", pack)
-
-
 def _batch_stats_layers(stack):
     """the packs of a stack that holds a training BatchNorm: (wp, b, sc, sh, k) per block with (sc, sh) the folded running statistics of the EVAL-mode
-    BatchNorms only (None for a training one: its buffers change at every call and are not read).  Keyed by the parameters' versions, the modes and the
-    eval-mode buffers' versions."""
+    BatchNorms only (None for a training one: its buffers change at every call and are not read).  Its generation follows exactly the tensors it
+    reads -- the parameters and the eval-mode buffers -- and the modes."""
     bns = [block[2] if len(block) > 2 else None for block in stack]
-    gen = (next(stack.parameters()).device,) + tuple(p._version for p in stack.parameters()) + \
-        tuple(None if bn is None else True if bn.training else (bn.running_mean._version, bn.running_var._version) for bn in bns)
+    read = list(stack.parameters()) + [t for bn in bns if bn is not None and not bn.training for t in (bn.running_mean, bn.running_var)]
+    gen = generation(stack, tuple(bn is not None and bn.training for bn in bns), tensors=read)
 
     def build():
         layers = []
@@ -649,7 +603,7 @@ def mlp(stack, x, batch_stats=False):
             return stack(x)
     lead = x.shape[:-1]
     h = ops.fp32_rows(x.reshape(-1, x.shape[-1]), "x")
-    layers = _batch_stats_layers(stack) if any(training) else _grad_layers(stack, stack._pack)
+    layers = _batch_stats_layers(stack) if any(training) else stack.packed()
     for i, (block, layer, t) in enumerate(zip(stack, layers, training)):
         lin, bn = block[0], block[2] if len(block) > 2 else None
         wp, b, sc, sh, k = layer
@@ -673,7 +627,7 @@ def linear(hip_linear, x, relu=False):
             return hip_linear(x, relu=relu)
     lead = x.shape[:-1]
     h = ops.fp32_rows(x.reshape(-1, x.shape[-1]), "x")
-    wp, b, k = _grad_layers(hip_linear, hip_linear._pack)
+    wp, b, k = hip_linear.packed()
     h = _LinearBlock.apply(h, hip_linear.weight, hip_linear.bias, None, None, (wp, b, None, None, k), bool(relu), None, hip_linear, 0)
     return h.reshape(*lead, h.shape[-1])
 

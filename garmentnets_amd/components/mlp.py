@@ -5,6 +5,7 @@ API / checkpoint-schema twin of /root/reference/components/mlp.py:3-20: ``MLP(ch
 AFTER the ReLU and also on the last layer.  The torch layers only HOLD the parameters; ``forward`` folds the eval-mode
 BatchNorm into a per-channel (scale, shift) and runs ``gn_linear`` (fp32 MFMA, fused bias+ReLU+affine epilogue).
 """
+import itertools
 import threading
 
 import torch
@@ -15,7 +16,7 @@ from .. import ops
 
 class ParamCache:
     """kernel-side packs derived from a module's parameters, shared by the host threads that run the module: `generation` names the
-    parameter state (device, tensor versions) -- a new one drops every older entry -- and `key` the variant (arithmetic, split point ...).
+    parameter state (generation() below) -- a new one drops every older entry -- and `key` the variant (arithmetic, split point ...).
     One lock per cache; entries are immutable once built; a reader that already holds an entry keeps it alive whatever happens to the table."""
 
     def __init__(self):
@@ -46,28 +47,49 @@ def param_cache(module, name):
     return c
 
 
-class PackedModule(nn.Module):
-    """Caches kernel-friendly parameter packs; dropped whenever parameters move or are reloaded."""
+_EPOCH = itertools.count()
 
-    def _invalidate(self):
-        object.__setattr__(self, "_packed", None)
+
+def generation(module, *extra, tensors=None):
+    """THE rule for when a pack of `module` is still valid, the generation every ParamCache of this package is asked with: the device and the
+    ``_version`` of every parameter and buffer of the module, recursively, plus what else the cache depends on (`extra`: a channel layout, a mode).
+    Every in-place update bumps a version -- torch's own, and FusedAdam.step's raw-pointer one through increment_version -- so no caller invalidates
+    anything by hand.  tensors: the tensors the packs read, for a cache that must NOT follow all of them (the training path's batch-statistics packs: a
+    training BatchNorm's buffers change at every forward).
+    A PackedModule holds the list of its tensor objects (walking parameters() and buffers() costs ten times the version reads) under an epoch number;
+    whatever can change the module's structure or swap a tensor's storage -- _apply, _load_from_state_dict, assigning a tensor or a submodule -- drops
+    the list, and the next call takes a new epoch: a new generation although no version moved (module.double().float()).  What the hooks do not see
+    is a tensor OBJECT swapped on a plain submodule (stack[0][0].weight = Parameter(...)): update in place or through load_state_dict."""
+    if isinstance(module, PackedModule):
+        held = module.__dict__.get("_held")
+        if held is None:                                           # (setdefault: two threads agree on one epoch)
+            held = module.__dict__.setdefault("_held", (next(_EPOCH), list(module.parameters()) + list(module.buffers())))
+    else:                                                          # any other module: walked at every call, nothing held, no epoch
+        held = (None, None if tensors is not None else list(module.parameters()) + list(module.buffers()))
+    if tensors is None:
+        tensors = held[1]
+    return (held[0], tensors[0].device if tensors else None, tuple([t._version for t in tensors])) + extra
+
+
+class PackedModule(nn.Module):
+    """Caches kernel-friendly parameter packs under `generation`.  The overrides below exist for one reason: to drop the held tensor list."""
 
     def _apply(self, fn, *args, **kwargs):
         r = super()._apply(fn, *args, **kwargs)
-        self._invalidate()
+        self.__dict__.pop("_held", None)
         return r
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
-        self._invalidate()
+        self.__dict__.pop("_held", None)
+
+    def __setattr__(self, name, value):
+        super().__setattr__(name, value)
+        if isinstance(value, (torch.Tensor, nn.Module)):
+            self.__dict__.pop("_held", None)
 
     def packed(self):
-        p = getattr(self, "_packed", None)
-        if p is None:
-            with torch.no_grad():
-                p = self._pack()
-            object.__setattr__(self, "_packed", p)
-        return p
+        return param_cache(self, "_packed").get(generation(self), "pack", self._pack)
 
 
 def pack_wb(weight, bias):

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .mlp import fold_batchnorm, generation, param_cache
 
 FUSED_SA = os.environ.get("GARMENTNETS_FUSED_SA", "1") != "0"      # False: the unfused gather -> gn_linear x3 -> segment-max chain
 
@@ -156,7 +157,7 @@ class SAModule(torch.nn.Module):
         return _DEBUG.__dict__.get("graphs", {}).get(self)
 
     def _fused_pack(self):
-        """SaFusedPack of local_nn when it is one of the edge MLPs gn_sa_fused is instantiated for, else None (cached per parameter version)"""
+        """SaFusedPack of local_nn when it is one of the edge MLPs gn_sa_fused is instantiated for, else None (cached under local_nn's generation)"""
         nn_ = self.conv.local_nn
         blocks = list(nn_) if nn_ is not None else []
         if len(blocks) != 3:
@@ -165,17 +166,13 @@ class SAModule(torch.nn.Module):
         cin = blocks[0][0].in_features - 3
         if not ops.sa_fused_supported(cin, dims):
             return None
-        key = tuple((p._version, p.device) for p in nn_.parameters()) + tuple(b._version for b in nn_.buffers())
-        cached = self.__dict__.get("_sa_pack")
-        if cached is None or cached[0] != key:
-            from .mlp import fold_batchnorm
+        def build():
             layers = []
             for b in blocks:
                 sc, sh = fold_batchnorm(b[2]) if len(b) > 2 else (None, None)
                 layers.append((b[0].weight, b[0].bias, sc, sh))
-            cached = (key, ops.pack_sa_fused(layers).to(blocks[0][0].weight.device))
-            self.__dict__["_sa_pack"] = cached
-        return cached[1]
+            return ops.pack_sa_fused(layers).to(blocks[0][0].weight.device)
+        return param_cache(self, "_sa_pack").get(generation(nn_), "pack", build)
 
 
 class GlobalSAModule(torch.nn.Module):

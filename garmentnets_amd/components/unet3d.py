@@ -18,7 +18,7 @@ from torch import nn
 
 from .. import arith as AR
 from .. import ops
-from .mlp import PackedModule, pack_wb, param_cache
+from .mlp import PackedModule, generation, pack_wb, param_cache
 
 
 def number_of_features_per_level(init_channel_number, num_levels):
@@ -159,6 +159,38 @@ def _class_constants(small_out, reach, cout):
     return k.reshape(B, len(pos) ** 3, cout).contiguous()
 
 
+def _raw(w):
+    """the weight as the device builders read it (fp32, contiguous: device-side copies when it is not)"""
+    w = w.detach()
+    return w if w.dtype == torch.float32 and w.is_contiguous() else w.float().contiguous()
+
+
+def _host_poly(w, mode, c0):
+    w0, wm, _ = ops.polyphase_weights(w, c0)
+    return (ops.pack_conv_weight_split(w0, mode).to(w.device), ops.pack_upconv_weight(wm, w.shape[0], mode).to(w.device))
+
+
+# Every pack of a SingleConv's convolution weight, named once: kind -> (cache key, host builder, device builder or None), each a function of
+# (w: the weight in the stored layout, mode, c0).  The builders reach `ops` by name at call time.  A device pack (csrc/weight_pack.hip: no host round
+# trip) sits under ("device",) + the host key, in the same ParamCache generation.
+CONV_PACKS = {
+    "fp32": ("fp32", lambda w, mode, c0: ops.pack_conv_weight(w), None),
+    "split": (lambda mode, c0: mode, lambda w, mode, c0: ops.pack_conv_weight_split(w, mode).to(w.device),
+              lambda w, mode, c0: ops.pack_conv_weight_split_device(_raw(w), mode)),
+    "wino": ("wino", lambda w, mode, c0: ops.pack_conv_weight_split_wino(w).to(w.device), lambda w, mode, c0: ops.pack_conv_weight_split_wino_device(_raw(w))),
+    # (full-resolution part, polyphase part) of a decoder's first convolution split at c0
+    "poly": (lambda mode, c0: ("poly", mode, c0), _host_poly,
+             lambda w, mode, c0: (ops.pack_conv_weight_split_device(_raw(w), mode, 0, c0), ops.pack_upconv_weight_device(_raw(w), c0, mode))),
+    "poly_wino": (lambda mode, c0: ("poly_wino", c0), lambda w, mode, c0: ops.pack_conv_weight_split_wino(ops.polyphase_weights(w, c0)[0]).to(w.device),
+                  lambda w, mode, c0: ops.pack_conv_weight_split_wino_device(_raw(w), 0, c0)),
+    "w0": (lambda mode, c0: ("w0", c0), lambda w, mode, c0: w.detach()[:, :c0].contiguous(), None),
+    # the data gradient: the forward kernels on the flipped / transposed weight
+    "bwd_data": ("bwd_data", lambda w, mode, c0: ops.pack_conv_weight_bwd_data(w), None),
+    "bwd_data_split": ("bwd_data_split", lambda w, mode, c0: ops.pack_conv_weight_bwd_data_split(w, False),
+                       lambda w, mode, c0: ops.pack_conv_weight_bwd_data_split(w, True)),
+}
+
+
 class SingleConv(PackedModule, nn.Sequential):
     """One conv block of the reference's create_conv (components/unet3d.py:19-73), same module names and parameter layout for every layer order:
     'g' GroupNorm, 'b' BatchNorm3d, 'c' Conv3d 3x3x3 pad 1 (bias only when the order has no norm layer), 'r' ReLU, 'l' LeakyReLU(0.1), 'e' ELU.
@@ -212,19 +244,32 @@ class SingleConv(PackedModule, nn.Sequential):
             return None
         return _Layout((real, stored, stored_channels(cout)))
 
-    def _padded_weight(self, lay):
-        """the Conv3d weight in the stored layout (lay.cout, sum(lay.stored), 3, 3, 3): zero rows and columns for the pad channels"""
-        def build():
-            w = self.conv.weight.detach()
-            wp = w.new_zeros((lay.cout, sum(lay.stored)) + tuple(w.shape[2:]))
-            wp[:w.shape[0]] = to_stored(w.transpose(1, -1), lay.real, lay.stored).transpose(1, -1)
-            return wp.contiguous()
-        return param_cache(self, "_split_packs").get(self._gen(lay), "padded_weight", build)
+    def weight_pack(self, kind, lay, *, mode=None, c0=None, device=False):
+        """The pack `kind` of the convolution weight under the channel layout `lay` (_layout: None when nothing is padded), built once per generation of
+        the module's tensors and layout.  kind: "padded_weight" -- the Conv3d weight in the stored layout (lay.cout, sum(lay.stored), 3, 3, 3), zero rows and
+        columns for the pad channels; the weight itself when nothing is padded -- or a key of CONV_PACKS, built from that weight.  mode: the
+        split-operand mode ("split", "poly"); c0: the stored width of the first source ("poly", "poly_wino", "w0"); device: take the device builder
+        when the kind has one and the weight is on a GPU (arith.device_packs)."""
+        if kind == "fp32" and lay is None:
+            return self.packed()[0]
+        cache, gen = param_cache(self, "_split_packs"), generation(self, lay)
+        w = self.conv.weight if lay is None else cache.get(gen, "padded_weight", lambda: self._pad_weight(lay))
+        if kind == "padded_weight":
+            return w
+        key, host, dev = CONV_PACKS[kind]
+        key = key(mode, c0) if callable(key) else key
+        if device and dev is not None and w.is_cuda:
+            return cache.get(gen, ("device",) + (key if isinstance(key, tuple) else (key,)), lambda: dev(w, mode, c0))
+        return cache.get(gen, key, lambda: host(w, mode, c0))
 
-    def _gen(self, lay):
-        """the ParamCache generation of this layer's packs: parameter state and (when padded) channel layout"""
-        w = self.conv.weight
-        return (w.device, w._version) if lay is None else (w.device, w._version, lay)
+    def _pad_weight(self, lay):
+        w = self.conv.weight.detach()
+        wp = w.new_zeros((lay.cout, sum(lay.stored)) + tuple(w.shape[2:]))
+        wp[:w.shape[0]] = to_stored(w.transpose(1, -1), lay.real, lay.stored).transpose(1, -1)
+        return wp.contiguous()
+
+    def _padded_weight(self, lay):
+        return self.weight_pack("padded_weight", lay)
 
     def _norm_affine(self, ch, B, st0, st1, real=None, stored=None):
         """per-(sample, channel) affine of one normalisation layer from the statistics of what it normalises (real / stored: the channel
@@ -244,10 +289,7 @@ class SingleConv(PackedModule, nn.Sequential):
         order, ic = self.order, self.order.index("c")
         B, cout = src0.shape[0], self.conv.out_channels if lay is None else lay.cout
         cin = src0.shape[-1] + (0 if src1 is None else src1.shape[-1])
-        if lay is None:
-            wp, _, _ = self.packed()
-        else:
-            wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
+        wp = self.weight_pack("fp32", lay)
         if ic == 0:
             a = torch.ones((B, cin), dtype=torch.float32, device=src0.device)
             d = torch.zeros_like(a)
@@ -299,7 +341,7 @@ class SingleConv(PackedModule, nn.Sequential):
         lay = self._layout(src0, src1)
         if self.order != "gcr":
             return self._run_generic(src0, src1, stats0, stats1, with_stats, lay) + (None,)
-        wp, gamma, beta = self.packed()
+        _, gamma, beta = self.packed()
         st0 = stats0 if stats0 is not None else ops.channel_stats(src0)
         st1 = None
         if src1 is not None:
@@ -310,9 +352,7 @@ class SingleConv(PackedModule, nn.Sequential):
                          None if small is None else tuple(small.shape[1:4]), flat is not None, rest0 is not None)
         if plan.mode == ops.CONV_FP32:
             a, d = ops.groupnorm_affine(st0, st1, self.groupnorm.num_groups, self.groupnorm.eps, gamma, beta, real=None if lay is None else lay.real)
-            if lay is not None:
-                wp = param_cache(self, "_split_packs").get(self._gen(lay), "fp32", lambda: ops.pack_conv_weight(self._padded_weight(lay)))
-            r, nxt = ops.conv3d_gcr(src0, src1, a, d, wp, cout, relu=True, with_stats=with_stats), None
+            r, nxt = ops.conv3d_gcr(src0, src1, a, d, self.weight_pack("fp32", lay), cout, relu=True, with_stats=with_stats), None
         else:
             r, nxt = self._run_split(plan, src0, src1, st0, st1, with_stats, at_rest, gamma, beta, rest0, lay, device_packs=arith.device_packs)
         return (r + (nxt,)) if with_stats else (r, None, nxt)
@@ -322,19 +362,14 @@ class SingleConv(PackedModule, nn.Sequential):
         operand forms: literal (the GroupNorm affine applied while the halo is staged) or affine-in-weights (ops.conv_affine_pack) -> (the launch's
         result, the output's AtRest or None).
         lay: channel-padded storage (_Layout) -- the padded weight and stored widths in every pack, the GroupNorm over the real channels
-        device_packs (arith.device_packs, a weight on the GPU): the static packs come from the device builders (csrc/weight_pack.hip: no host round
-        trip), under keys of their own in the same ParamCache generation; the launches are the same"""
-        gn, weight, cout, mode, c0 = self.groupnorm, self.conv.weight, self.conv.out_channels, plan.mode, src0.shape[-1]
+        device_packs (arith.device_packs): the static packs come from the device builders (weight_pack); the launches are the same"""
+        gn, weight, cout, mode, c0 = self.groupnorm, self.weight_pack("padded_weight", lay), self.conv.out_channels, plan.mode, src0.shape[-1]
         real = None
         if lay is not None:
-            weight, cout, real = self._padded_weight(lay), lay.cout, lay.real
-        cache, gen = param_cache(self, "_split_packs"), self._gen(lay)
-        device_packs = bool(device_packs) and weight.is_cuda
+            cout, real = lay.cout, lay.real
 
-        def raw():
-            """the weight as the device builders read it (fp32, contiguous: device-side copies when it is not)"""
-            w = weight.detach()
-            return w if w.dtype == torch.float32 and w.is_contiguous() else w.float().contiguous()
+        def pack(kind):
+            return self.weight_pack(kind, lay, mode=mode, c0=c0, device=device_packs)
         part = prep = act_inv = rest_out = None
         if plan.aiw and not plan.poly:
             # a layer whose input is at rest (0 for the scattered volume, at_rest.value behind it) almost everywhere
@@ -350,45 +385,26 @@ class SingleConv(PackedModule, nn.Sequential):
             else:
                 a, d = ops.groupnorm_affine(st0, st1, gn.num_groups, gn.eps, gamma, beta, real=real)
             if plan.poly:
-                def build_poly():
-                    w0, wm, _ = ops.polyphase_weights(weight, c0)
-                    return (ops.pack_conv_weight_split(w0, mode).to(weight.device), ops.pack_upconv_weight(wm, cout, mode).to(weight.device))
-                if device_packs:
-                    pk0, pkm = cache.get(gen, ("device", "poly", mode, c0), lambda: (ops.pack_conv_weight_split_device(raw(), mode, 0, c0),
-                                                                                     ops.pack_upconv_weight_device(raw(), c0, mode)))
-                else:
-                    pk0, pkm = cache.get(gen, ("poly", mode, c0), build_poly)
+                pk0, pkm = pack("poly")
                 part = ops.upconv_partial(src1, a[:, c0:].contiguous(), d[:, c0:].contiguous(), pkm, cout, act_inv=act_inv)
                 if plan.aiw:
                     # the full-resolution part in the affine-in-weights form: the skip connection src0 is at rest away from the cells
                     # (a, d carry the sample's power-of-two activation scale: exact to undo)
                     a0 = (a[:, :c0] * act_inv[:, None]).contiguous()
                     d0 = (d[:, :c0] * act_inv[:, None]).contiguous()
-                    w0c = cache.get(gen, ("w0", c0), lambda: weight.detach()[:, :c0].contiguous())
-                    prep = ops.conv_affine_pack(w0c, a0, d0, st0, rest0, wino=plan.wino)
+                    prep = ops.conv_affine_pack(pack("w0"), a0, d0, st0, rest0, wino=plan.wino)
                 else:
                     a, d = a[:, :c0].contiguous(), d[:, :c0].contiguous()
-                    if not plan.wino:
-                        pack = pk0
-                    elif device_packs:
-                        pack = cache.get(gen, ("device", "poly_wino", c0), lambda: ops.pack_conv_weight_split_wino_device(raw(), 0, c0))
-                    else:
-                        pack = cache.get(gen, ("poly_wino", c0), lambda: ops.pack_conv_weight_split_wino(ops.polyphase_weights(weight, c0)[0]).to(weight.device))
-            elif plan.wino and device_packs:
-                pack = cache.get(gen, ("device", "wino"), lambda: ops.pack_conv_weight_split_wino_device(raw()))
-            elif plan.wino:
-                pack = cache.get(gen, "wino", lambda: ops.pack_conv_weight_split_wino(weight).to(weight.device))
-            elif device_packs:
-                pack = cache.get(gen, ("device", mode), lambda: ops.pack_conv_weight_split_device(raw(), mode))
+                    wpack = pack("poly_wino") if plan.wino else pk0
             else:
-                pack = cache.get(gen, mode, lambda: ops.pack_conv_weight_split(weight, mode).to(weight.device))
+                wpack = pack("wino" if plan.wino else "split")
         # the one launch tail of each form (a polyphase launch reads the full-resolution source alone: the upsampled channels arrive as the partial)
         if prep is not None:
             launch = lambda x, **kw: ops.conv3d_gcr_split_persample(x, prep, relu=True, **kw)
         elif plan.wino:
-            launch = lambda x, **kw: ops.conv3d_gcr_split_wino(x, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
+            launch = lambda x, **kw: ops.conv3d_gcr_split_wino(x, a, d, wpack, cout, relu=True, act_inv=act_inv, **kw)
         else:
-            launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if plan.poly else src1, a, d, pack, cout, relu=True, act_inv=act_inv, **kw)
+            launch = lambda x, **kw: ops.conv3d_gcr_split(x, None if plan.poly else src1, a, d, wpack, cout, relu=True, act_inv=act_inv, **kw)
         occ, small_out = {}, None
         if plan.small:
             # occupancy-aware: the border-class constants come from `launch` -- the kernel AND the pack the real launch takes -- over a small all-at-rest

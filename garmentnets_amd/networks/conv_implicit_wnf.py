@@ -18,7 +18,7 @@ from torch import nn
 from .. import arith as AR
 from .. import ops
 from ..batch import Batch
-from ..components.mlp import MLP, PackedModule, fold_batchnorm, param_cache
+from ..components.mlp import MLP, PackedModule, fold_batchnorm, generation, param_cache
 from ..components.unet3d import Abstract3DUNet, DoubleConv, stored_channels, stored_volume, to_channel_last
 from ..components.pointnet2 import Segments
 from .pointnet2_nocs import PointNet2NOCS
@@ -267,8 +267,8 @@ class ImplicitWNFDecoder(PackedModule):
         cin = final_conv.in_stored or final_conv.in_channels
         if not (self.fused and self._fusable(cin) and self.nn_channels[0] == final_conv.out_channels and final_conv.kernel_size == (1, 1, 1)):
             return None
-        key = (id(final_conv), cin, final_conv.weight._version, final_conv.bias._version, final_conv.weight.device) + tuple(p._version for p in self.parameters())
-        return param_cache(self, "_folded").get(key, "folded", lambda: self._build_pack(
+        # (both modules' parameters AND buffers: _build_pack folds the BatchNorm running statistics in)
+        return param_cache(self, "_folded").get(generation(self, id(final_conv), cin, generation(final_conv)), "folded", lambda: self._build_pack(
             cin, ((32, 256), (32, 512)), (final_conv.stored_weight().double(), final_conv.bias.detach().double())))
 
     def _plan(self, arith, vol, pack, Q, M, out_packed=True):

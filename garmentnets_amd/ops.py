@@ -441,15 +441,13 @@ def _conv3d_wino(who, src, a, d, pack, out_scale, act_inv, kbias, cout, relu, wi
     """both operand forms through the Winograd kernels (kbias None: literal, else affine-in-weights): gn_conv3d_gcr_split_wino, or its _partial entry
     when a polyphase partial is added (never occupancy-aware)"""
     B, D, H, W, C0 = src.shape
-    out = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=src.device)
-    s, q = _stats_buffers(B, cout, src.device, with_stats)
+    if partial is not None and tile_active is not None:
+        raise ValueError(f"{who}: the occupancy-aware launch cannot take a polyphase partial")
+    out, s, q, ows, ows_bytes = _conv_outputs(src, cout, with_stats, tile_active)
     if partial is not None:
-        if tile_active is not None:
-            raise ValueError(f"{who}: the occupancy-aware launch cannot take a polyphase partial")
         _lib.call("gn_conv3d_gcr_split_wino_partial", _p(src), C0, _p(a), _p(d), _p(pack), _p(out_scale), _p(act_inv), _p(kbias), B, D, H, W, cout,
                   1 if relu else 0, _p(out), _p(s), _p(q), _p(_chk(partial, torch.float32, "partial")), _stream())
     else:
-        ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src.device)
         _lib.call("gn_conv3d_gcr_split_wino", _p(src), C0, _p(a), _p(d), _p(pack), _p(out_scale), _p(act_inv), _p(kbias), B, D, H, W, cout,
                   1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(ows), ows_bytes, _stream())
     return (out, (s, q, D * H * W)) if with_stats else out
@@ -587,9 +585,7 @@ def conv3d_gcr_split(src0, src1, a, d, pack, cout, relu=True, with_stats=False, 
                      partial=None):
     B, D, H, W, C0 = src0.shape
     C1 = 0 if src1 is None else src1.shape[-1]
-    out = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=src0.device)
-    s, q = _stats_buffers(B, cout, src0.device, with_stats)
-    ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src0.device)
+    out, s, q, ows, ows_bytes = _conv_outputs(src0, cout, with_stats, tile_active)
     _lib.call("gn_conv3d_gcr_split", _p(src0), C0, _p(src1), C1, _p(a), _p(d), _p(pack.tensor), pack.mode, _p(pack.out_scale), _p(act_inv), B, D, H, W, cout,
               1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(partial), _p(ows), ows_bytes, _stream())
     return (out, (s, q, D * H * W)) if with_stats else out
@@ -637,9 +633,7 @@ def conv3d_gcr_split_persample(src, prep, relu=True, with_stats=False, tile_acti
     if prep.wino:
         return _conv3d_wino("conv3d_gcr_split_persample", src, prep.stage_a, prep.stage_d, prep.pack, prep.out_scale, None, prep.kbias, prep.cout, relu,
                             with_stats, tile_active, kconst, kreach, partial)
-    out = torch.empty((B, D, H, W, prep.cout), dtype=torch.float32, device=src.device)
-    s, q = _stats_buffers(B, prep.cout, src.device, with_stats)
-    ows, ows_bytes = _occupancy_ws(tile_active, B, D, H, W, src.device)
+    out, s, q, ows, ows_bytes = _conv_outputs(src, prep.cout, with_stats, tile_active)
     _lib.call("gn_conv3d_gcr_split_persample", _p(src), C, _p(prep.stage_a), _p(prep.stage_d), _p(prep.pack), _p(prep.out_scale), _p(prep.kbias),
               B, D, H, W, prep.cout, 1 if relu else 0, _p(out), _p(s), _p(q), _p(tile_active), _p(kconst), int(kreach), _p(partial), _p(ows), ows_bytes,
               _stream())
@@ -652,6 +646,14 @@ def _occupancy_ws(tile_active, B, D, H, W, device):
         return None, 0
     n = _lib.load().gn_conv3d_occupancy_workspace_bytes(B, D, H, W)
     return torch.empty((n,), dtype=torch.uint8, device=device), n
+
+
+def _conv_outputs(src, cout, with_stats, tile_active):
+    """what a split-operand conv launch over src [B][D][H][W][C] writes: (the output [B][D][H][W][cout], the sum and sumsq buffers of its statistics
+    or None twice, the occupancy workspace or None, its bytes)"""
+    B, D, H, W = src.shape[:4]
+    out = torch.empty((B, D, H, W, cout), dtype=torch.float32, device=src.device)
+    return (out,) + _stats_buffers(B, cout, src.device, with_stats) + _occupancy_ws(tile_active, B, D, H, W, src.device)
 
 
 def _stats_buffers(B, C, device, want):
@@ -1675,9 +1677,8 @@ def pack_conv_weight_bwd_data(w):
     return pack_conv_weight(bwd_data_weight(w))
 
 
-def conv3d_bwd_weight(src0, src1, a, d, y, dy):
-    """-> dw (Cout, C0 + C1, 3, 3, 3) over the stored widths: the weight gradient of one 'gcr' layer (gn_conv3d_bwd_weight).  a, d: the forward's
-    GroupNorm affine [B][C0 + C1]; y: the layer's stored output (ReLU mask), None for a layer without ReLU; dy: the gradient at that output."""
+def _bwd_weight_args(who, src0, src1, a, d, y, dy):
+    """the checks the two weight-gradient entries share, before any launch -> (B, D, H, W, C0, C1, Cout)"""
     _vol5(src0, "src0")
     B, D, H, W, C0 = src0.shape
     C1 = 0
@@ -1685,17 +1686,24 @@ def conv3d_bwd_weight(src0, src1, a, d, y, dy):
         _vol5(src1, "src1")
         C1 = src1.shape[-1]
         if tuple(src1.shape[:4]) != (B, D // 2, H // 2, W // 2) or D % 2 or H % 2 or W % 2:
-            raise ValueError(f"conv3d_bwd_weight: src1 {tuple(src1.shape)} is not the half-resolution companion of src0 {tuple(src0.shape)}")
+            raise ValueError(f"{who}: src1 {tuple(src1.shape)} is not the half-resolution companion of src0 {tuple(src0.shape)}")
     _vol5(dy, "dy")
     cout = dy.shape[-1]
     if tuple(dy.shape[:4]) != (B, D, H, W):
-        raise ValueError(f"conv3d_bwd_weight: dy {tuple(dy.shape)} does not match src0 {tuple(src0.shape)}")
+        raise ValueError(f"{who}: dy {tuple(dy.shape)} does not match src0 {tuple(src0.shape)}")
     if y is not None:
         _vol5(y, "y", dy)
     for t, name in ((a, "a"), (d, "d")):
         _chk(t, torch.float32, name)
         if tuple(t.shape) != (B, C0 + C1):
-            raise ValueError(f"conv3d_bwd_weight: {name} must be [B][C0 + C1] = {(B, C0 + C1)}, got {tuple(t.shape)}")
+            raise ValueError(f"{who}: {name} must be [B][C0 + C1] = {(B, C0 + C1)}, got {tuple(t.shape)}")
+    return B, D, H, W, C0, C1, cout
+
+
+def conv3d_bwd_weight(src0, src1, a, d, y, dy):
+    """-> dw (Cout, C0 + C1, 3, 3, 3) over the stored widths: the weight gradient of one 'gcr' layer (gn_conv3d_bwd_weight).  a, d: the forward's
+    GroupNorm affine [B][C0 + C1]; y: the layer's stored output (ReLU mask), None for a layer without ReLU; dy: the gradient at that output."""
+    B, D, H, W, C0, C1, cout = _bwd_weight_args("conv3d_bwd_weight", src0, src1, a, d, y, dy)
     dw = torch.empty((cout, C0 + C1, 3, 3, 3), dtype=torch.float32, device=src0.device)
     nbytes = _lib.load().gn_conv3d_bwd_weight_workspace_bytes(B, D, H, W, C0 + C1, cout)
     ws = _ws(nbytes, src0.device)
@@ -1783,24 +1791,7 @@ def conv3d_bwd_weight_split(src0, src1, a, d, y, dy, x_inv=None, gmax=None):
     forward's GroupNorm affine; with x_inv [B] they carry each sample's power-of-two activation scale and x_inv is its inverse
     (groupnorm_affine(with_act_scale=True)), without it the operand x * a + d must lie inside fp16's range as it is.  gmax [B]: relu_mask_max's
     per-sample maximum of the masked gradient; None: one masking pass finds it here."""
-    _vol5(src0, "src0")
-    B, D, H, W, C0 = src0.shape
-    C1 = 0
-    if src1 is not None:
-        _vol5(src1, "src1")
-        C1 = src1.shape[-1]
-        if tuple(src1.shape[:4]) != (B, D // 2, H // 2, W // 2) or D % 2 or H % 2 or W % 2:
-            raise ValueError(f"conv3d_bwd_weight_split: src1 {tuple(src1.shape)} is not the half-resolution companion of src0 {tuple(src0.shape)}")
-    _vol5(dy, "dy")
-    cout = dy.shape[-1]
-    if tuple(dy.shape[:4]) != (B, D, H, W):
-        raise ValueError(f"conv3d_bwd_weight_split: dy {tuple(dy.shape)} does not match src0 {tuple(src0.shape)}")
-    if y is not None:
-        _vol5(y, "y", dy)
-    for t, name in ((a, "a"), (d, "d")):
-        _chk(t, torch.float32, name)
-        if tuple(t.shape) != (B, C0 + C1):
-            raise ValueError(f"conv3d_bwd_weight_split: {name} must be [B][C0 + C1] = {(B, C0 + C1)}, got {tuple(t.shape)}")
+    B, D, H, W, C0, C1, cout = _bwd_weight_args("conv3d_bwd_weight_split", src0, src1, a, d, y, dy)
     for t, name in ((x_inv, "x_inv"), (gmax, "gmax")):
         if t is not None:
             _chk(t, torch.float32, name)

@@ -1,12 +1,12 @@
-"""FusedAdam: torch.optim.Adam's update as ONE HIP launch per step (csrc/optim.hip gn_adam_step), and the bookkeeping an in-place update owes this package.
+"""FusedAdam: torch.optim.Adam's update as ONE HIP launch per step (csrc/optim.hip gn_adam_step), and the one thing an in-place update owes this package.
 
-Why the optimiser lives here.  MLPStack and HipLinear evaluate through PACKS of their parameters.  A kernel that writes through a raw pointer does not
-bump ``tensor._version``, and ``PackedModule.packed()`` (the inference forward) is not keyed by versions at all.  So after the launch ``step()``
-  * bumps the version counter of every updated parameter, exp_avg and exp_avg_sq (``torch.autograd.graph.increment_version``): the version-keyed caches
-    (autograd._grad_layers / _batch_stats_layers, SAModule._fused_pack) rebuild, and a ``backward()`` whose forward ran before the step raises autograd's
-    "modified by an inplace operation" error instead of differentiating the new values;
-  * calls ``_invalidate()`` on every PackedModule that owns an updated parameter, when it knows the modules (``modules=`` of the constructor or of
-    ``step``): the next ``model.eval()(batch)`` reads the new weights.
+Why the optimiser lives here.  MLPStack, HipLinear and the UNet's layers evaluate through PACKS of their parameters, and every pack is cached under one
+rule: the device and ``_version`` of the module's tensors (``components.mlp.generation``).  torch's own in-place updates bump those versions; a kernel
+that writes through a raw pointer does not.  So after the launch ``step()`` bumps the version counter of every updated parameter, exp_avg and
+exp_avg_sq (``torch.autograd.graph.increment_version``): every pack of an updated module is rebuilt at its next use -- the inference forward's as the
+training forward's -- and a ``backward()`` whose forward ran before the step raises autograd's "modified by an inplace operation" error instead of
+differentiating the new values.  Nothing else is kept: ``FusedAdam(model)`` means the model's parameters, and the ``modules=`` keywords of the
+constructor and of ``step`` are accepted and need no bookkeeping.
 
 Semantics: torch.optim.Adam's, per parameter group (lr, betas, eps, weight_decay as L2: g + wd * p).  State keys and types are torch's (``step`` a CPU
 fp32 scalar tensor, ``exp_avg``, ``exp_avg_sq``) and the groups carry torch's keys, so ``state_dict()`` loads into a torch.optim.Adam over the same
@@ -22,7 +22,6 @@ import math
 import torch
 
 from . import _lib, ops
-from .components.mlp import PackedModule
 
 __all__ = ["FusedAdam"]
 
@@ -36,8 +35,7 @@ def _check_param(p):
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, modules=None):
-        if isinstance(params, torch.nn.Module):                       # FusedAdam(model): its parameters, and its packs to invalidate
-            modules = params if modules is None else modules
+        if isinstance(params, torch.nn.Module):                       # FusedAdam(model): its parameters
             params = params.parameters()
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not all(0.0 <= b < 1.0 for b in betas):
             raise ValueError(f"FusedAdam: invalid lr / betas / eps / weight_decay: {lr}, {betas}, {eps}, {weight_decay}")
@@ -49,10 +47,7 @@ class FusedAdam(torch.optim.Optimizer):
         for group in self.param_groups:
             for p in group["params"]:
                 _check_param(p)
-        self._owners = {}
         self._tables = {}                                              # batch number -> (key, device table)
-        if modules is not None:
-            self.bind(modules)
 
     def _check_groups(self):
         for group in self.param_groups:
@@ -64,18 +59,6 @@ class FusedAdam(torch.optim.Optimizer):
                 raise NotImplementedError("FusedAdam: decoupled_weight_decay / capturable / differentiable are not implemented")
             if isinstance(group["lr"], torch.Tensor):
                 raise NotImplementedError("FusedAdam: a tensor lr is not implemented")
-
-    def bind(self, modules):
-        """remember which PackedModule owns which parameter: ``step`` invalidates the packs of the ones it updates.  modules: a module or several"""
-        mods = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
-        for root in mods:
-            for m in root.modules():
-                if isinstance(m, PackedModule):
-                    for p in m.parameters():
-                        owners = self._owners.setdefault(id(p), [])
-                        if all(o is not m for o in owners):
-                            owners.append(m)
-        return self
 
     def _collect(self):
         """-> [(p, grad, state, group)] of this step, everything checked: nothing has been launched or advanced when a check raises"""
@@ -111,8 +94,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if modules is not None:
-            self.bind(modules)
         work = self._collect()
         if not work:
             return loss
@@ -146,12 +127,6 @@ class FusedAdam(torch.optim.Optimizer):
         for k in [k for k in self._tables if k >= len(batches)]:
             del self._tables[k]
         torch.autograd.graph.increment_version([t for p, _, m, v, _ in rows for t in (p, m, v)])
-        seen = set()
-        for p, *_ in rows:
-            for mod in self._owners.get(id(p), ()):
-                if id(mod) not in seen:
-                    seen.add(id(mod))
-                    mod._invalidate()
         return loss
 
     def _launch(self, bi, rows, used, hypers):

@@ -228,14 +228,9 @@ def agree_layout(layout):
     return layout
 
 
-def _packed_modules(model):
-    from .components.mlp import PackedModule
-    return [m for m in model.modules() if isinstance(m, PackedModule)]
-
-
-def _broadcast_tensors(model, tensors, src):
-    """rank `src`'s values into `tensors` of `model` on every rank: one broadcast per dtype (through the host under gloo).  The in-place copies bump the
-    version counters, as FusedAdam.step does, and every PackedModule is invalidated: the next forward reads the new values"""
+def _broadcast_tensors(tensors, src):
+    """rank `src`'s values into `tensors` on every rank: one broadcast per dtype (through the host under gloo).  The in-place copies bump the
+    version counters, as FusedAdam.step does: the next forward rebuilds its packs from the new values (components.mlp.generation)"""
     gloo = dist.get_backend() != "nccl"
     by_dtype = {}
     for t in tensors:
@@ -250,15 +245,13 @@ def _broadcast_tensors(model, tensors, src):
             for t in tensors:
                 t.copy_(flat[at:at + t.numel()].view(t.shape))
                 at += t.numel()
-    for m in _packed_modules(model):
-        m._invalidate()
 
 
 @torch.no_grad()
 def broadcast_module(model, src=0):
     """every parameter and buffer of `model` becomes rank `src`'s, once, before the first step"""
     if dist.is_initialized() and dist.get_world_size() > 1:
-        _broadcast_tensors(model, list(model.parameters()) + list(model.buffers()), src)
+        _broadcast_tensors(list(model.parameters()) + list(model.buffers()), src)
     return model
 
 
@@ -268,7 +261,7 @@ def borrow_buffers(model, src=0):
     values then describe that checkpoint) -> this rank's own, for restore_buffers.  One collective per dtype, before the validation loop, none inside"""
     own = [b.detach().clone() for b in model.buffers()]
     if dist.is_initialized() and dist.get_world_size() > 1:
-        _broadcast_tensors(model, list(model.buffers()), src)
+        _broadcast_tensors(list(model.buffers()), src)
     return own
 
 
@@ -277,8 +270,6 @@ def restore_buffers(model, own):
     """the buffers borrow_buffers set aside go back: training goes on with this rank's own running statistics"""
     for b, mine in zip(model.buffers(), own):
         b.copy_(mine)
-    for m in _packed_modules(model):
-        m._invalidate()
 
 
 class GradientReducer:

@@ -318,6 +318,13 @@ def test_fused_adam_step_between_forward_and_backward_raises():
     with pytest.raises(RuntimeError, match="modified by an inplace operation"):
         y.backward()
     assert not torch.equal(lin(x), stale)                          # FusedAdam(module) invalidated the inference pack
+    # ... and so does an optimiser that was never told the module: the pack follows the tensor versions
+    opt = FusedAdam(lin.parameters())
+    for p in lin.parameters():
+        p.grad = torch.ones_like(p)
+    stale = lin(x).clone()
+    opt.step()
+    assert not torch.equal(lin(x), stale)
 
 
 # ================================================================================================ the model

@@ -3,9 +3,8 @@
 
 The reference's configuration: batch 8, 6000 points per garment, nocs_bins = 64, synthetic clouds (synthetic.synthetic_cloud), the model in
 training mode (batch-statistics BatchNorm, dropout).  Reports the median of 20 steps after 5 warm-up steps and the share of forward (with the loss),
-backward and optimizer.step(), each bracketed by events on the stream; then the same step with torch.optim.Adam(foreach=True) in FusedAdam's place,
-followed by the _invalidate() of the packs that torch's optimiser does not know about, the two alternating within one run.  Not a test and not read by
-bench.py.  Needs a GPU: there is no fallback."""
+backward and optimizer.step(), each bracketed by events on the stream; then the same step with torch.optim.Adam(foreach=True) in FusedAdam's place
+(its in-place updates bump the tensor versions the packs are keyed by), the two alternating within one run.  Not a test and not read by bench.py.  Needs a GPU: there is no fallback."""
 import argparse
 import copy
 import json
@@ -20,7 +19,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from garmentnets_amd import synthetic, train  # noqa: E402
 from garmentnets_amd.batch import Batch  # noqa: E402
-from garmentnets_amd.components.mlp import PackedModule  # noqa: E402
 from garmentnets_amd.networks.pointnet2_nocs import PointNet2NOCS  # noqa: E402
 from garmentnets_amd.optim import FusedAdam  # noqa: E402
 
@@ -52,20 +50,14 @@ def summarise(rows, names):
     return out
 
 
-def timed_step(model, optimizer, batch, invalidate):
+def timed_step(model, optimizer, batch):
     optimizer.zero_grad(set_to_none=True)
     state = {}
 
     def forward():
         state["loss"] = train.loss_and_sums(model, batch)[0]
 
-    def step():
-        optimizer.step()
-        if invalidate:
-            for m in model.modules():
-                if isinstance(m, PackedModule):
-                    m._invalidate()
-    return bracketed([forward, lambda: state["loss"].backward(), step])
+    return bracketed([forward, lambda: state["loss"].backward(), optimizer.step])
 
 
 def main():
@@ -94,7 +86,7 @@ def main():
     torch.manual_seed(0)
     for i in range(a.warmup + a.steps):                 # the two alternate, step by step: the same machine state for both
         for name, (model, opt, rows) in runs.items():
-            t = timed_step(model, opt, batch, invalidate=name == "foreach")
+            t = timed_step(model, opt, batch)
             if i >= a.warmup:
                 rows.append(t)
     out = {"clock": time.strftime("%Y-%m-%d %H:%M:%S %Z"), "device": torch.cuda.get_device_name(0), "batch": a.batch, "points": a.points,
