@@ -157,6 +157,9 @@ PROTOTYPES = {
     "gn_color_idx_batch": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "gn_render_mesh_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "gn_color_mesh_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gn_depth_render_batch": [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gn_depth_cloud_offsets": [_vp, _i32, _i32, _vp, _vp, _vp],
+    "gn_depth_cloud_write": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -249,6 +252,12 @@ class MeshImage(ctypes.Structure):
     """GnMeshImage (table entry of gn_render_mesh_batch / gn_color_mesh_batch: the same bytes on the host and on the device)"""
     _fields_ = [("vert_begin", _i64), ("vert_end", _i64), ("face_begin", _i64), ("face_end", _i64), ("side", _i32), ("ambient", _f32),
                 ("default_color", _f32 * 4)]
+
+
+class DepthImage(ctypes.Structure):
+    """GnDepthImage (table entry of gn_depth_render_batch / gn_depth_cloud_write: the same bytes on the host and on the device)"""
+    _fields_ = [("vert_begin", _i64), ("vert_end", _i64), ("face_begin", _i64), ("face_end", _i64), ("R", _f64 * 9), ("t", _f64 * 3), ("f", _f64),
+                ("c", _f64), ("znear", _f64), ("ambient", _f32), ("base_color", _f32 * 3)]
 
 
 _lib = None

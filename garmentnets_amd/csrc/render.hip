@@ -1,5 +1,6 @@
 // render.hip -- the training monitors' images: the z-buffered point splat of the reference's common/rendering_util.py and its colouring, every image of
-// a batch in one launch each; below them the evaluation's mesh images, a triangle rasteriser behind the same camera ("mesh images").
+// a batch in one launch each; below them the evaluation's mesh images, a triangle rasteriser behind the same camera ("mesh images"), and below those
+// the dataset's input clouds, the same rasteriser behind a perspective camera and a compaction of its covered pixels ("point clouds from meshes").
 //
 //   gn_render_points_batch  fp32 points -> uint32 index images: per pixel the index of the covering point nearest to the camera
 //   gn_color_idx_batch       index images -> fp32 RGBA: a colour table or a scalar through viridis, the default colour elsewhere, then the overlay points
@@ -236,17 +237,8 @@ __device__ __forceinline__ bool mr_owns(int px, int py, int qx, int qy) {
     return dy > 0 || (dy == 0 && dx < 0);
 }
 
-// the face `idx` (three indices into the V vertices at `verts`) in positive orientation; false: never drawn
-__device__ __forceinline__ bool mr_face(const float *__restrict__ verts, int64_t V, const int32_t *__restrict__ idx, int side, int S, MrFace &f) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int v = idx[k];
-        if (v < 0 || (int64_t)v >= V) return false;
-        if (!rd_camera(verts + 3 * (int64_t)v, side, f.cam[k])) return false;
-        if (!mr_fixed(f.cam[k][0], S, f.x[k]) || !mr_fixed(f.cam[k][1], S, f.y[k])) return false;
-        f.z[k] = f.cam[k][2];
-        f.v[k] = v;
-    }
+// the positive orientation of a face whose x, y, v, z and cam are filled in: area2 < 0 swaps b and c with everything they carry; false: area2 == 0
+__device__ __forceinline__ bool mr_orient(MrFace &f) {
     const long long area2 = mr_edge(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2]);
     if (area2 == 0) return false;
     if (area2 < 0) {
@@ -260,6 +252,20 @@ __device__ __forceinline__ bool mr_face(const float *__restrict__ verts, int64_t
     return true;
 }
 
+// the face `idx` (three indices into the V vertices at `verts`) in positive orientation; false: never drawn
+__device__ __forceinline__ bool mr_face(const float *__restrict__ verts, int64_t V, const int32_t *__restrict__ idx, int side, int S, MrFace &f) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int v = idx[k];
+        if (v < 0 || (int64_t)v >= V) return false;
+        if (!rd_camera(verts + 3 * (int64_t)v, side, f.cam[k])) return false;
+        if (!mr_fixed(f.cam[k][0], S, f.x[k]) || !mr_fixed(f.cam[k][1], S, f.y[k])) return false;
+        f.z[k] = f.cam[k][2];
+        f.v[k] = v;
+    }
+    return mr_orient(f);
+}
+
 // the weights of the sample (px, py) in the positively oriented face; false: not covered
 __device__ __forceinline__ bool mr_cover(int ax, int ay, int bx, int by, int cx, int cy, int px, int py, long long &wa, long long &wb, long long &wc) {
     wa = mr_edge(bx, by, cx, cy, px, py);
@@ -269,27 +275,43 @@ __device__ __forceinline__ bool mr_cover(int ax, int ay, int bx, int by, int cx,
            (wc > 0 || (wc == 0 && mr_owns(ax, ay, bx, by)));
 }
 
-__global__ __launch_bounds__(RD_BLOCK) void render_mesh_batch_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
-                                                                     const GnMeshImage *__restrict__ tab, int S, uint32_t *__restrict__ out) {
+// What a rasteriser is made of besides the loop below: its table entry, how a face gets to the screen (face(): x, y, v, cam and the three staged values z),
+// what the staged values give at a covered sample (value()) and which of two such values is nearer (nearer(); farthest() loses to every finite one).
+struct MrOrtho {                                                          // the mesh images: the axis camera of `side`, the interpolated depth, smallest wins
+    typedef GnMeshImage Image;
+    static __device__ __forceinline__ bool face(const GnMeshImage &im, const float *__restrict__ iv, int64_t V, const int32_t *__restrict__ idx, int S,
+                                                MrFace &f) {
+        return mr_face(iv, V, idx, im.side, S, f);
+    }
+    static __device__ __forceinline__ double value(long long wa, long long wb, long long wc, double za, double zb, double zc) {
+        const double num = __dadd_rn(__dadd_rn(__dmul_rn((double)wa, za), __dmul_rn((double)wb, zb)), __dmul_rn((double)wc, zc));
+        return __ddiv_rn(num, (double)(wa + wb + wc));                    // the weights sum to area2
+    }
+    static __device__ __forceinline__ double farthest() { return INFINITY; }
+    static __device__ __forceinline__ bool nearer(double z, double best) { return z < best; }
+};
+
+template <class P>
+__device__ __forceinline__ void mr_raster(const float *__restrict__ verts, const int32_t *__restrict__ faces, const typename P::Image *__restrict__ tab,
+                                          int S, uint32_t *__restrict__ out) {
     __shared__ double sz[3][RD_BLOCK];
     __shared__ int sx[3][RD_BLOCK], sy[3][RD_BLOCK];
     __shared__ uint32_t si[RD_BLOCK];
     __shared__ int scnt[RD_WAVES];
-    const GnMeshImage &im = tab[blockIdx.z];
+    const typename P::Image &im = tab[blockIdx.z];
     const int64_t begin = im.face_begin, end = im.face_end, V = im.vert_end - im.vert_begin;
     const float *iv = verts + 3 * im.vert_begin;
-    const int side = im.side;
     const int tid = threadIdx.x, lane = tid & (GN_WAVE - 1), wave = tid / GN_WAVE;
     const int tx0 = blockIdx.x * RD_TILE, ty0 = blockIdx.y * RD_TILE;
     const int X = tx0 + (tid & (RD_TILE - 1)), Y = ty0 + tid / RD_TILE;
     const int px = 256 * X + 128, py = 256 * Y + 128;
-    double best = INFINITY;
+    double best = P::farthest();
     uint32_t best_idx = RD_NONE;
     for (int64_t c0 = begin; c0 < end; c0 += RD_BLOCK) {                 // block-uniform bounds: every thread reaches every barrier
         const int64_t j = c0 + tid;
         bool hit = false;
         MrFace f;
-        if (j < end && mr_face(iv, V, faces + 3 * j, side, S, f)) {
+        if (j < end && P::face(im, iv, V, faces + 3 * j, S, f)) {
             // the pixels whose samples 256 X + 128 lie within [min, max]: X from ceil((min - 128) / 256) to floor((max - 128) / 256)
             const int xlo = (min(f.x[0], min(f.x[1], f.x[2])) + 127) >> 8, xhi = (max(f.x[0], max(f.x[1], f.x[2])) - 128) >> 8;
             const int ylo = (min(f.y[0], min(f.y[1], f.y[2])) + 127) >> 8, yhi = (max(f.y[0], max(f.y[1], f.y[2])) - 128) >> 8;
@@ -313,15 +335,19 @@ __global__ __launch_bounds__(RD_BLOCK) void render_mesh_batch_kernel(const float
             si[slot] = (uint32_t)(j - begin);
         }
         __syncthreads();
-        for (int s = 0; s < total; ++s) {                                // ascending index: a strict < keeps the first of equal depths
+        for (int s = 0; s < total; ++s) {                                // ascending index: a strict comparison keeps the first of equal depths
             long long wa, wb, wc;
             if (!mr_cover(sx[0][s], sy[0][s], sx[1][s], sy[1][s], sx[2][s], sy[2][s], px, py, wa, wb, wc)) continue;
-            const double num = __dadd_rn(__dadd_rn(__dmul_rn((double)wa, sz[0][s]), __dmul_rn((double)wb, sz[1][s])), __dmul_rn((double)wc, sz[2][s]));
-            const double z = __ddiv_rn(num, (double)(wa + wb + wc));     // the weights sum to area2
-            if (z < best) { best = z; best_idx = si[s]; }
+            const double z = P::value(wa, wb, wc, sz[0][s], sz[1][s], sz[2][s]);
+            if (P::nearer(z, best)) { best = z; best_idx = si[s]; }
         }
     }
     if (X < S && Y < S) out[((int64_t)blockIdx.z * S + Y) * S + X] = best_idx;
+}
+
+__global__ __launch_bounds__(RD_BLOCK) void render_mesh_batch_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
+                                                                     const GnMeshImage *__restrict__ tab, int S, uint32_t *__restrict__ out) {
+    mr_raster<MrOrtho>(verts, faces, tab, S, out);
 }
 
 __global__ __launch_bounds__(256) void color_mesh_batch_kernel(const uint32_t *__restrict__ idx_img, const float *__restrict__ verts,
@@ -405,5 +431,265 @@ extern "C" int gn_color_mesh_batch(const uint32_t *idx_img, const float *verts, 
     hipLaunchKernelGGL(color_mesh_batch_kernel, dim3((unsigned)gn_cdiv((int64_t)S * S, 256), (unsigned)I), dim3(256), 0, gn_stream(stream), idx_img, verts,
                        faces, colors, tab, S, out);
     GN_LAUNCH_CHECK("gn_color_mesh_batch");
+    return GN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ point clouds from meshes
+//   gn_depth_render_batch    fp32 vertices + int32 faces behind a perspective camera -> uint32 index images: per pixel the covering face nearest to it
+//   gn_depth_cloud_offsets   index images -> the exclusive prefix sum of the covered pixels per image row, and the count per image
+//   gn_depth_cloud_write     index images + those offsets -> point rows (position, NOCS label, colour) in raster order, image after image
+//
+// The definitions ("Point clouds from meshes"; garmentnets_amd/point_cloud.py restates them in numpy, operation for operation):
+//   camera     cam[j] = ((R[j][0] x + R[j][1] y) + R[j][2] z) + t[j] in fp64 on the fp32 vertex, every operation rounded on its own
+//   screen     u = (f * cam[0]) / cam[2] + c, v likewise; fx = rint(u * 256), fy = rint(v * 256), half to even; samples at (256 X + 128, 256 Y + 128)
+//   not drawn  what the mesh images never draw, and a face with a vertex at cam[2] < near (no clipping)
+//   two-sided, coverage, ownership   mr_orient, mr_cover, mr_owns: the mesh images' own
+//   winner     i_k = 1 / z_k, q_k = double(w_k) * i_k, q = (q_a + q_b) + q_c, inv = q / double(area2); the LARGEST inv, equal ones: the lowest face index
+//   point      b_k = q_k / q; ((b_a A + b_b B) + b_c C) per coordinate in fp64 on the fp32 corners, rounded once to fp32; the NOCS label likewise
+//   colour     n = (B - A) x (C - A) on the camera coordinates, p = the camera coordinates of the fp32 point; nn = (nx nx + ny ny) + nz nz, pp and np
+//              likewise, root = sqrt(nn * pp); shade = ambient + (1 - ambient) * (|np| / root), ambient where root is 0 or not finite;
+//              rgb_c = uint8(clamp(rint((255 * float(shade)) * base_c), 0, 255)) in fp32, NaN -> 0
+//   order      images back to back; within an image the covered pixels in raster order (Y, then X)
+// Shape: the rasteriser is mr_raster with the three inverse depths staged in place of the three depths.  The compaction is three small kernels and has
+// no atomics: a wave counts the covered pixels of one image row (ballot + popcount), ONE workgroup scans the I * S counts in place (a wave-shuffle scan
+// per 256 counts, a running carry), and a wave writes its row's points at its offset, a lane's slot from the popcount of the covered lanes below it.
+// The write pass recomputes the winner's weights from the face index, as color_mesh_batch_kernel does.
+#define PC_ROWS (256 / GN_WAVE)                                           // image rows per workgroup of the count and the write pass
+#define PC_SCAN_BLOCK 256
+
+__device__ __forceinline__ bool pc_camera(const GnDepthImage &im, const float *__restrict__ p, double (&c)[3]) {
+    const float x = p[0], y = p[1], z = p[2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
+    const double dx = (double)x, dy = (double)y, dz = (double)z;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        c[j] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(im.R[3 * j], dx), __dmul_rn(im.R[3 * j + 1], dy)), __dmul_rn(im.R[3 * j + 2], dz)), im.t[j]);
+    return true;
+}
+
+// rint(((f * a) / z + c) * 256) as an int; false beyond 2^24 in magnitude (or NaN)
+__device__ __forceinline__ bool pc_fixed(const GnDepthImage &im, double a, double z, int &fx) {
+    const double r = rint(__dmul_rn(__dadd_rn(__ddiv_rn(__dmul_rn(im.f, a), z), im.c), 256.0));
+    if (!(fabs(r) <= 16777216.0)) return false;
+    fx = (int)r;
+    return true;
+}
+
+struct MrPersp {                                                          // the depth images: a free-standing pinhole, the inverse depth, largest wins
+    typedef GnDepthImage Image;
+    static __device__ __forceinline__ bool face(const GnDepthImage &im, const float *__restrict__ iv, int64_t V, const int32_t *__restrict__ idx, int S,
+                                                MrFace &f) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int v = idx[k];
+            if (v < 0 || (int64_t)v >= V) return false;
+            if (!pc_camera(im, iv + 3 * (int64_t)v, f.cam[k])) return false;
+            if (!(f.cam[k][2] >= im.znear)) return false;                 // behind the near plane (or NaN): no clipping, the face is not drawn
+            if (!pc_fixed(im, f.cam[k][0], f.cam[k][2], f.x[k]) || !pc_fixed(im, f.cam[k][1], f.cam[k][2], f.y[k])) return false;
+            f.z[k] = __ddiv_rn(1.0, f.cam[k][2]);
+            f.v[k] = v;
+        }
+        return mr_orient(f);
+    }
+    static __device__ __forceinline__ double value(long long wa, long long wb, long long wc, double ia, double ib, double ic) {
+        const double q = __dadd_rn(__dadd_rn(__dmul_rn((double)wa, ia), __dmul_rn((double)wb, ib)), __dmul_rn((double)wc, ic));
+        return __ddiv_rn(q, (double)(wa + wb + wc));
+    }
+    static __device__ __forceinline__ double farthest() { return -INFINITY; }
+    static __device__ __forceinline__ bool nearer(double inv, double best) { return inv > best; }
+};
+
+__global__ __launch_bounds__(RD_BLOCK) void depth_render_batch_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
+                                                                      const GnDepthImage *__restrict__ tab, int S, uint32_t *__restrict__ out) {
+    mr_raster<MrPersp>(verts, faces, tab, S, out);
+}
+
+// row_off[row] = the covered pixels of image row `row` (rows = I * S of them), a wave per row
+__global__ __launch_bounds__(256) void depth_cloud_count_kernel(const uint32_t *__restrict__ idx_img, int64_t rows, int S, int64_t *__restrict__ row_off) {
+    const int lane = threadIdx.x & (GN_WAVE - 1);
+    const int64_t row = (int64_t)blockIdx.x * PC_ROWS + threadIdx.x / GN_WAVE;
+    if (row >= rows) return;                                              // wave-uniform
+    int n = 0;
+    for (int x0 = 0; x0 < S; x0 += GN_WAVE) {
+        const int X = x0 + lane;
+        n += __popcll(__ballot(X < S && idx_img[row * S + X] != RD_NONE));
+    }
+    if (lane == 0) row_off[row] = n;
+}
+
+// counts -> exclusive offsets in place, the total at row_off[rows]; sizes[i] = the points of image i.  ONE workgroup.
+__global__ __launch_bounds__(PC_SCAN_BLOCK) void depth_cloud_scan_kernel(int64_t *row_off, int64_t rows, int I, int S, int64_t *sizes) {
+    __shared__ long long swave[PC_SCAN_BLOCK / GN_WAVE];
+    const int tid = threadIdx.x, lane = tid & (GN_WAVE - 1), wave = tid / GN_WAVE;
+    long long carry = 0;
+    for (int64_t c0 = 0; c0 < rows; c0 += PC_SCAN_BLOCK) {                // block-uniform bounds: every thread reaches every barrier
+        const int64_t i = c0 + tid;
+        const long long v = i < rows ? (long long)row_off[i] : 0;
+        long long x = v;                                                  // the inclusive scan of the wave
+#pragma unroll
+        for (int d = 1; d < GN_WAVE; d <<= 1) {
+            const long long y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        __syncthreads();                                                  // the previous chunk's wave sums are read
+        if (lane == GN_WAVE - 1) swave[wave] = x;
+        __syncthreads();
+        long long base = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < PC_SCAN_BLOCK / GN_WAVE; ++w) {
+            const long long n = swave[w];
+            base += w < wave ? n : 0;
+            total += n;
+        }
+        if (i < rows) row_off[i] = (int64_t)(carry + base + x - v);
+        carry += total;
+    }
+    if (tid == 0) row_off[rows] = (int64_t)carry;
+    __threadfence();
+    __syncthreads();                                                      // this workgroup wrote every offset: they are visible to it
+    for (int i = tid; i < I; i += PC_SCAN_BLOCK) sizes[i] = row_off[(int64_t)(i + 1) * S] - row_off[(int64_t)i * S];
+}
+
+__global__ __launch_bounds__(256) void depth_cloud_write_kernel(const uint32_t *__restrict__ idx_img, const float *__restrict__ verts,
+                                                                const float *__restrict__ nocs, const int32_t *__restrict__ faces,
+                                                                const GnDepthImage *__restrict__ tab, const int64_t *__restrict__ row_off, int64_t rows,
+                                                                int S, int64_t N, float *__restrict__ point, float *__restrict__ nocs_out,
+                                                                uint8_t *__restrict__ rgb) {
+    const int lane = threadIdx.x & (GN_WAVE - 1);
+    const int64_t row = (int64_t)blockIdx.x * PC_ROWS + threadIdx.x / GN_WAVE;
+    if (row >= rows) return;                                              // wave-uniform
+    const int64_t first = row_off[row];
+    if (row_off[row + 1] == first) return;                                // an empty row costs two loads
+    const GnDepthImage &im = tab[row / S];
+    const int Y = (int)(row % S);
+    const int64_t V = im.vert_end - im.vert_begin;
+    const float *iv = verts + 3 * im.vert_begin, *in = nocs + 3 * im.vert_begin;
+    int64_t done = 0;
+    for (int x0 = 0; x0 < S; x0 += GN_WAVE) {
+        const int X = x0 + lane;
+        const uint32_t idx = X < S ? idx_img[row * S + X] : RD_NONE;
+        const unsigned long long mask = __ballot(idx != RD_NONE);
+        const int64_t slot = first + done + __popcll(mask & ((1ull << lane) - 1ull));
+        done += __popcll(mask);
+        if (idx == RD_NONE || slot < 0 || slot >= N) continue;
+        float P[3] = {0.f, 0.f, 0.f}, L[3] = {0.f, 0.f, 0.f};
+        uint8_t col[3] = {0, 0, 0};
+        MrFace f;
+        long long wa, wb, wc;
+        if ((int64_t)idx < im.face_end - im.face_begin && MrPersp::face(im, iv, V, faces + 3 * (im.face_begin + idx), S, f) &&
+            mr_cover(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2], 256 * X + 128, 256 * Y + 128, wa, wb, wc)) {
+            const double qa = __dmul_rn((double)wa, f.z[0]), qb = __dmul_rn((double)wb, f.z[1]), qc = __dmul_rn((double)wc, f.z[2]);
+            const double q = __dadd_rn(__dadd_rn(qa, qb), qc);
+            const double ba = __ddiv_rn(qa, q), bb = __ddiv_rn(qb, q), bc = __ddiv_rn(qc, q);
+            const float *A = iv + 3 * (int64_t)f.v[0], *B = iv + 3 * (int64_t)f.v[1], *C = iv + 3 * (int64_t)f.v[2];
+            const float *LA = in + 3 * (int64_t)f.v[0], *LB = in + 3 * (int64_t)f.v[1], *LC = in + 3 * (int64_t)f.v[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                P[c] = (float)__dadd_rn(__dadd_rn(__dmul_rn(ba, (double)A[c]), __dmul_rn(bb, (double)B[c])), __dmul_rn(bc, (double)C[c]));
+                L[c] = (float)__dadd_rn(__dadd_rn(__dmul_rn(ba, (double)LA[c]), __dmul_rn(bb, (double)LB[c])), __dmul_rn(bc, (double)LC[c]));
+            }
+            // n = (B - A) x (C - A) on the camera coordinates; p = the point seen from the camera
+            const double ux = __dsub_rn(f.cam[1][0], f.cam[0][0]), uy = __dsub_rn(f.cam[1][1], f.cam[0][1]), uz = __dsub_rn(f.cam[1][2], f.cam[0][2]);
+            const double vx = __dsub_rn(f.cam[2][0], f.cam[0][0]), vy = __dsub_rn(f.cam[2][1], f.cam[0][1]), vz = __dsub_rn(f.cam[2][2], f.cam[0][2]);
+            const double nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy)), ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
+            const double nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+            const double amb = (double)im.ambient;
+            double shade = amb, p[3];
+            if (pc_camera(im, P, p)) {
+                const double nn = __dadd_rn(__dadd_rn(__dmul_rn(nx, nx), __dmul_rn(ny, ny)), __dmul_rn(nz, nz));
+                const double pp = __dadd_rn(__dadd_rn(__dmul_rn(p[0], p[0]), __dmul_rn(p[1], p[1])), __dmul_rn(p[2], p[2]));
+                const double np = __dadd_rn(__dadd_rn(__dmul_rn(nx, p[0]), __dmul_rn(ny, p[1])), __dmul_rn(nz, p[2]));
+                const double root = __dsqrt_rn(__dmul_rn(nn, pp));
+                if (root > 0.0 && root < INFINITY) shade = __dadd_rn(amb, __dmul_rn(__dsub_rn(1.0, amb), __ddiv_rn(fabs(np), root)));
+            }
+            const float sh = __fmul_rn(255.f, (float)shade);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float r = rintf(__fmul_rn(sh, im.base_color[c]));
+                col[c] = (uint8_t)(r >= 255.f ? 255.f : (r > 0.f ? r : 0.f));      // NaN -> 0
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            point[3 * slot + c] = P[c];
+            nocs_out[3 * slot + c] = L[c];
+            rgb[3 * slot + c] = col[c];
+        }
+    }
+}
+
+static int pc_check(const char *who, const int64_t *vseg_host, const int64_t *fseg_host, int M, const int32_t *mesh_host, const GnDepthImage *tab_host,
+                    int I) {
+    GN_REQUIRE(M >= 0, "%s: M=%d meshes", who, M);
+    for (int m = 0; m < M; ++m) {
+        GN_REQUIRE(vseg_host[m] >= 0 && vseg_host[m + 1] >= vseg_host[m], "%s: mesh %d: vseg is not a non-decreasing CSR", who, m);
+        GN_REQUIRE(fseg_host[m] >= 0 && fseg_host[m + 1] >= fseg_host[m], "%s: mesh %d: fseg is not a non-decreasing CSR", who, m);
+        GN_REQUIRE(fseg_host[m + 1] - fseg_host[m] < (int64_t)RD_NONE, "%s: mesh %d: a segment of %lld faces (needs fewer than 2^32 - 1)", who, m,
+                   (long long)(fseg_host[m + 1] - fseg_host[m]));
+    }
+    for (int i = 0; i < I; ++i) {
+        const GnDepthImage &g = tab_host[i];
+        const int m = mesh_host[i];
+        GN_REQUIRE(m >= 0 && m < M, "%s: image %d: mesh=%d outside [0, M=%d)", who, i, m, M);
+        GN_REQUIRE(g.vert_begin == vseg_host[m] && g.vert_end == vseg_host[m + 1] && g.face_begin == fseg_host[m] && g.face_end == fseg_host[m + 1],
+                   "%s: image %d: the table's segments differ from vseg / fseg of mesh %d", who, i, m);
+        for (int k = 0; k < 9; ++k) GN_REQUIRE(std::isfinite(g.R[k]), "%s: image %d: camera entry R[%d]=%g is not finite", who, i, k, g.R[k]);
+        for (int k = 0; k < 3; ++k) GN_REQUIRE(std::isfinite(g.t[k]), "%s: image %d: camera entry t[%d]=%g is not finite", who, i, k, g.t[k]);
+        GN_REQUIRE(std::isfinite(g.c), "%s: image %d: camera entry c=%g is not finite", who, i, g.c);
+        GN_REQUIRE(std::isfinite(g.f) && g.f > 0.0, "%s: image %d: f=%g is not a positive finite focal length", who, i, g.f);
+        GN_REQUIRE(std::isfinite(g.znear) && g.znear > 0.0, "%s: image %d: near=%g is not positive and finite", who, i, g.znear);
+        GN_REQUIRE(g.ambient >= 0.f && g.ambient <= 1.f, "%s: image %d: ambient=%g outside [0, 1]", who, i, (double)g.ambient);
+        for (int k = 0; k < 3; ++k)
+            GN_REQUIRE(std::isfinite(g.base_color[k]), "%s: image %d: base_color[%d]=%g is not finite", who, i, k, (double)g.base_color[k]);
+    }
+    return GN_OK;
+}
+
+extern "C" int gn_depth_render_batch(const float *verts, const int32_t *faces, const int64_t *vseg_host, const int64_t *fseg_host, int M,
+                                     const int32_t *mesh_host, const GnDepthImage *tab_host, const GnDepthImage *tab, int I, int S, uint32_t *out,
+                                     void *stream) {
+    int rc = rd_check_size("gn_depth_render_batch", I, S);
+    if (rc != GN_OK) return rc;
+    if (I == 0) return GN_OK;
+    GN_REQUIRE(vseg_host && fseg_host && mesh_host && tab_host && tab && out, "gn_depth_render_batch: null pointer");
+    rc = pc_check("gn_depth_render_batch", vseg_host, fseg_host, M, mesh_host, tab_host, I);
+    if (rc != GN_OK) return rc;
+    GN_REQUIRE(fseg_host[M] == 0 || (faces && (vseg_host[M] == 0 || verts)), "gn_depth_render_batch: null verts / faces");
+    const unsigned tiles = (unsigned)gn_cdiv(S, RD_TILE);
+    hipLaunchKernelGGL(depth_render_batch_kernel, dim3(tiles, tiles, (unsigned)I), dim3(RD_BLOCK), 0, gn_stream(stream), verts, faces, tab, S, out);
+    GN_LAUNCH_CHECK("gn_depth_render_batch");
+    return GN_OK;
+}
+
+extern "C" int gn_depth_cloud_offsets(const uint32_t *idx_img, int I, int S, int64_t *row_off, int64_t *sizes, void *stream) {
+    const int rc = rd_check_size("gn_depth_cloud_offsets", I, S);
+    if (rc != GN_OK) return rc;
+    if (I == 0) return GN_OK;
+    GN_REQUIRE(idx_img && row_off && sizes, "gn_depth_cloud_offsets: null pointer");
+    const int64_t rows = (int64_t)I * S;
+    hipLaunchKernelGGL(depth_cloud_count_kernel, dim3((unsigned)gn_cdiv(rows, PC_ROWS)), dim3(256), 0, gn_stream(stream), idx_img, rows, S, row_off);
+    GN_LAUNCH_CHECK("gn_depth_cloud_offsets (count)");
+    hipLaunchKernelGGL(depth_cloud_scan_kernel, dim3(1), dim3(PC_SCAN_BLOCK), 0, gn_stream(stream), row_off, rows, I, S, sizes);
+    GN_LAUNCH_CHECK("gn_depth_cloud_offsets (scan)");
+    return GN_OK;
+}
+
+extern "C" int gn_depth_cloud_write(const uint32_t *idx_img, const float *verts, const float *nocs, const int32_t *faces, const int64_t *vseg_host,
+                                    const int64_t *fseg_host, int M, const int32_t *mesh_host, const GnDepthImage *tab_host, const GnDepthImage *tab,
+                                    const int64_t *row_off, int I, int S, int64_t N, float *point, float *nocs_out, uint8_t *rgb, void *stream) {
+    int rc = rd_check_size("gn_depth_cloud_write", I, S);
+    if (rc != GN_OK) return rc;
+    if (I == 0) return GN_OK;
+    GN_REQUIRE(idx_img && vseg_host && fseg_host && mesh_host && tab_host && tab && row_off, "gn_depth_cloud_write: null pointer");
+    rc = pc_check("gn_depth_cloud_write", vseg_host, fseg_host, M, mesh_host, tab_host, I);
+    if (rc != GN_OK) return rc;
+    GN_REQUIRE(N >= 0, "gn_depth_cloud_write: N=%lld rows", (long long)N);
+    if (N == 0) return GN_OK;
+    GN_REQUIRE(point && nocs_out && rgb, "gn_depth_cloud_write: null output");
+    GN_REQUIRE(faces && verts && nocs, "gn_depth_cloud_write: null verts / nocs / faces");
+    const int64_t rows = (int64_t)I * S;
+    hipLaunchKernelGGL(depth_cloud_write_kernel, dim3((unsigned)gn_cdiv(rows, PC_ROWS)), dim3(256), 0, gn_stream(stream), idx_img, verts, nocs, faces, tab,
+                       row_off, rows, S, N, point, nocs_out, rgb);
+    GN_LAUNCH_CHECK("gn_depth_cloud_write");
     return GN_OK;
 }

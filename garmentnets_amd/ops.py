@@ -2222,6 +2222,86 @@ def color_mesh_batch(idx_img, verts, faces, colors, vseg, fseg, sides, ambients=
     return out
 
 
+# ------------------------------------------------------------------------------------------------ point clouds from meshes
+def _depth_args(who, verts, faces, vseg, fseg, mesh_of, cameras, ambients, base_colors):
+    """the checked tensors, the meshes' host CSRs, the images' mesh numbers and the GnDepthImage table (host, device).  cameras: one record per image
+    ({"R" (3, 3), "t" (3,), "f", "c", "near"}; point_cloud.camera_ring builds them).  What only sizes an access is refused here (a segment beyond its
+    tensor, a mesh number outside the CSRs); cameras, ambients and the CSRs' order are the entry's to refuse, in its words"""
+    verts, faces = _chk(verts, torch.float32, "verts"), _chk(faces, _i32, "faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise ValueError(f"{who}: expected (V, 3) fp32 verts and (F, 3) int32 faces on one device, got {tuple(verts.shape)}, {tuple(faces.shape)}")
+    vseg = np.ascontiguousarray(np.asarray(vseg, dtype=np.int64).reshape(-1))
+    fseg = np.ascontiguousarray(np.asarray(fseg, dtype=np.int64).reshape(-1))
+    mesh_of = np.ascontiguousarray(np.asarray(mesh_of, dtype=np.int32).reshape(-1))
+    m, n = vseg.shape[0] - 1, mesh_of.shape[0]
+    cameras = list(cameras)
+    ambients = [0.35] * n if ambients is None else list(ambients)
+    base_colors = [(0.5, 0.5, 0.5)] * n if base_colors is None else list(base_colors)
+    if m < 0 or fseg.shape[0] != m + 1 or len(cameras) != n or len(ambients) != n or len(base_colors) != n:
+        raise ValueError(f"{who}: vseg and fseg hold M + 1 entries for M meshes; mesh_of, cameras, ambients and base colours one entry per image")
+    if n and (m == 0 or mesh_of.min() < 0 or mesh_of.max() >= m):
+        raise ValueError(f"{who}: an image's mesh number is outside [0, M={m})")
+    if m and (vseg.max() > verts.shape[0] or fseg.max() > faces.shape[0]):
+        raise ValueError(f"{who}: a segment ends beyond its tensor ({verts.shape[0]} verts, {faces.shape[0]} faces)")
+    tab = (_lib.DepthImage * max(n, 1))()
+    for i in range(n):
+        e, cam, g = tab[i], cameras[i], int(mesh_of[i])
+        e.vert_begin, e.vert_end, e.face_begin, e.face_end = int(vseg[g]), int(vseg[g + 1]), int(fseg[g]), int(fseg[g + 1])
+        e.R[:] = [float(v) for v in np.asarray(cam["R"], dtype=np.float64).reshape(9)]
+        e.t[:] = [float(v) for v in np.asarray(cam["t"], dtype=np.float64).reshape(3)]
+        e.f, e.c, e.znear, e.ambient = float(cam["f"]), float(cam["c"]), float(cam["near"]), float(ambients[i])
+        e.base_color[:] = [float(v) for v in base_colors[i]]
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(verts.device)
+    return verts, faces, vseg, fseg, mesh_of, tab, tab_dev, m, n
+
+
+def depth_render_batch(verts, faces, vseg, fseg, mesh_of, cameras, img_size):
+    """the triangle rasteriser behind perspective cameras, I images in ONE launch (gn_depth_render_batch) -> (I, S, S) int32 holding the uint32 index
+    images (0xFFFFFFFF, i.e. -1, where no face covers the pixel's sample).  verts: (V, 3) fp32 and faces: (F, 3) int32 on the device, M meshes behind the
+    CSRs vseg / fseg; image i draws mesh mesh_of[i] through cameras[i].  A pixel holds the index, counted from the mesh's first face, of the covering
+    face with the largest perspective-correct inverse depth (equal ones: the lowest index).  DESIGN.md "Point clouds from meshes" has the rules."""
+    verts, faces, vseg, fseg, mesh_of, tab, tab_dev, m, n = _depth_args("depth_render_batch", verts, faces, vseg, fseg, mesh_of, cameras, None, None)
+    S = _render_dims("gn_depth_render_batch", n, img_size)
+    out = torch.empty((n, S, S), dtype=_i32, device=verts.device)
+    if n == 0:
+        return out
+    _lib.call("gn_depth_render_batch", _p(verts), _p(faces), vseg.ctypes.data_as(ctypes.c_void_p), fseg.ctypes.data_as(ctypes.c_void_p), m,
+              mesh_of.ctypes.data_as(ctypes.c_void_p), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), n, S, _p(out), _stream())
+    return out
+
+
+def depth_cloud(idx_img, verts, nocs, faces, vseg, fseg, mesh_of, cameras, ambients=None, base_colors=None):
+    """depth_render_batch's index images -> (point (N, 3) fp32, nocs (N, 3) fp32, rgb (N, 3) uint8, sizes (I,) int64 on the HOST): the covered pixels as
+    point rows, image after image, within an image in raster order.  Two entries: gn_depth_cloud_offsets (a count per image row and one scan; the
+    per-image sizes come back to the host to size the outputs) and gn_depth_cloud_write.  nocs: (V, 3) fp32, one row per row of verts."""
+    idx_img = _chk(idx_img, _i32, "idx_img")
+    if idx_img.dim() != 3 or idx_img.shape[1] != idx_img.shape[2]:
+        raise ValueError(f"idx_img: expected an (I, S, S) tensor, got {tuple(idx_img.shape)}")
+    verts, faces, vseg, fseg, mesh_of, tab, tab_dev, m, n = _depth_args("depth_cloud", verts, faces, vseg, fseg, mesh_of, cameras, ambients, base_colors)
+    nocs = _chk(nocs, torch.float32, "nocs")
+    if nocs.shape != verts.shape or nocs.device != verts.device or idx_img.device != verts.device:
+        raise ValueError(f"depth_cloud: expected {tuple(verts.shape)} nocs on {verts.device}, got {tuple(nocs.shape)} on {nocs.device}")
+    if idx_img.shape[0] != n:
+        raise ValueError(f"depth_cloud: {n} image entries for {idx_img.shape[0]} index images")
+    S = _render_dims("gn_depth_cloud_offsets", n, idx_img.shape[1])
+    dev = verts.device
+    if n == 0:
+        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.float32, device=dev),
+                torch.empty((0, 3), dtype=torch.uint8, device=dev), np.zeros(0, dtype=np.int64))
+    row_off = torch.empty(n * S + 1, dtype=torch.int64, device=dev)
+    sizes = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.call("gn_depth_cloud_offsets", _p(idx_img), n, S, _p(row_off), _p(sizes), _stream())
+    sizes = sizes.cpu().numpy()
+    total = int(sizes.sum())
+    point = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    label = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    rgb = torch.empty((total, 3), dtype=torch.uint8, device=dev)
+    _lib.call("gn_depth_cloud_write", _p(idx_img), _p(verts), _p(nocs), _p(faces), vseg.ctypes.data_as(ctypes.c_void_p),
+              fseg.ctypes.data_as(ctypes.c_void_p), m, mesh_of.ctypes.data_as(ctypes.c_void_p), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev),
+              _p(row_off), n, S, total, _p(point), _p(label), _p(rgb), _stream())
+    return point, label, rgb, sizes
+
+
 # ------------------------------------------------------------------------------------------------ gradient pack (data-parallel training)
 def grad_pack_table(rows, device):
     """the device table of gn_grad_pack.  rows: [(source pointer or None, dst_off, numel)] in the order of their workgroups; dst_off a multiple of 4

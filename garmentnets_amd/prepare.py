@@ -14,6 +14,10 @@ through io.zarr_store, with default_compressor():
   marching_cube_mesh/ (--marching_cubes)        marching_cube_verts float32 (V, 3), marching_cube_faces int32 (F, 3): common.marching_cubes_util.
                                                 marching_cubes(NOCS field, 0.5, spacing 1/(size-1)); is_vertex_on_surface bool (V,)
 
+  point_cloud/ (--point_clouds)                 point float32 (N, 3), nocs float32 (N, 3), rgb uint8 (N, 3), sizes int64 (views,): the simulation mesh seen by
+                                                --pc_views pinhole cameras on a ring around cloth_aabb_union, the covered pixels of every view in raster
+                                                order (point_cloud.py; DESIGN.md "Point clouds from meshes"); the cameras go into the group's attributes
+
 The on-surface rule is THIS PACKAGE'S OWN (the reference ships the flag, not how it was made): a marching-cubes vertex is on the surface
 when its distance to the NOCS mesh, sqrt(ops.point_mesh_sqdist), is <= tau.  The default tau = 1/(size-1) is derived, not tuned: a
 marching-cubes vertex lies on a lattice edge that the 0.5 level crosses, and where the garment's surface makes that crossing the surface
@@ -32,7 +36,7 @@ import time
 
 import numpy as np
 
-from . import distance, winding
+from . import distance, point_cloud, winding
 from .io import zarr_store
 from .io.dataset import TASK_SPACE_VOLUME_GROUP, AABBGripNormalizer
 
@@ -56,7 +60,17 @@ def build_parser():
     ap.add_argument("--on_surface_distance", type=float, default=None, help="tau of the on-surface rule; default 1/(volume_size-1)")
     ap.add_argument("--batch_size", type=int, default=4, help="garments per launch")
     ap.add_argument("--overwrite", action="store_true", help="rebuild arrays that the store already holds")
-    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"), help="who computes the winding numbers and the lattice distances")
+    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"),
+                    help="who computes the winding numbers, the lattice distances and the point clouds")
+    ap.add_argument("--point_clouds", action="store_true", help="render point_cloud/{point, nocs, rgb, sizes} from the garment mesh (point_cloud.py)")
+    ap.add_argument("--pc_views", type=int, default=4, help="cameras on the ring")
+    ap.add_argument("--pc_img_size", type=int, default=256, help="pixels per image side: a view holds at most its square in points")
+    ap.add_argument("--pc_fov", type=float, default=point_cloud.DEFAULT_FOV, help="field of view, degrees (a look)")
+    ap.add_argument("--pc_elevation", type=float, default=point_cloud.DEFAULT_ELEVATION, help="degrees above the xy plane (a look)")
+    ap.add_argument("--pc_azimuth0", type=float, default=0.0, help="azimuth of the first camera, degrees about z")
+    ap.add_argument("--pc_distance", type=float, default=None, help="camera distance; default r / sin(fov / 2), r the half-diagonal of cloth_aabb_union")
+    ap.add_argument("--pc_color", type=float, nargs=3, default=list(point_cloud.DEFAULT_BASE_COLOR), metavar=("R", "G", "B"),
+                    help="the base colour the headlight shades, in [0, 1]")
     return ap
 
 
@@ -114,8 +128,29 @@ def build_derived_groups(samples, chunk, derived, size, overwrite, backend, comp
     return done
 
 
+def build_point_clouds(samples, chunk, cameras, img_size, color, overwrite, backend, comp):
+    """write point_cloud/{point, nocs, rgb, sizes} of the samples of `chunk` that lack one of them (or, with overwrite, of all): the simulation mesh
+    seen from `cameras`, every garment times every view in one launch set -> [sample] written"""
+    todo = [k for k in chunk if overwrite or not all(f"point_cloud/{a}" in samples[k] for a in point_cloud.CLOUD_ARRAYS)]
+    if not todo:
+        return []
+    meshes = [(samples[k]["mesh"]["cloth_verts"][:].astype(np.float32), samples[k]["mesh"]["cloth_nocs_verts"][:].astype(np.float32),
+               samples[k]["mesh"]["cloth_faces_tri"][:].astype(np.int32)) for k in todo]
+    clouds = point_cloud.render_point_clouds(meshes, cameras, img_size, color, backend="numpy" if backend == "numpy" else "device")
+    for k, cloud in zip(todo, clouds):
+        if cloud["sizes"].sum() == 0:
+            raise ValueError(f"sample {k}: no camera sees its mesh (no covered pixel in any of {len(cameras)} views): no point cloud")
+        pc = samples[k].require_group("point_cloud")
+        for a in point_cloud.CLOUD_ARRAYS:
+            pc.array(a, cloud[a], compressor=comp)
+        pc.put_attrs({"cameras": point_cloud.camera_attrs(cameras), "img_size": int(img_size), "base_color": [float(c) for c in color],
+                      "ambient": point_cloud.DEFAULT_AMBIENT})
+    return todo
+
+
 def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False, on_surface_distance=None, batch_size=4, overwrite=False,
-                  backend="hip", log=print, derived_groups=()):
+                  backend="hip", log=print, derived_groups=(), point_clouds=False, pc_views=4, pc_img_size=256, pc_fov=point_cloud.DEFAULT_FOV,
+                  pc_elevation=point_cloud.DEFAULT_ELEVATION, pc_azimuth0=0.0, pc_distance=None, pc_color=point_cloud.DEFAULT_BASE_COLOR):
     """-> summary dict {"samples", "written": {what: count}, "seconds"}; log gets one dict per sample"""
     groups = list(groups)
     unknown = [g for g in groups if g not in GROUPS]
@@ -145,8 +180,17 @@ def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False,
         if "summary/cloth_aabb_union" not in root:
             raise ValueError(f"{zarr_in}: no summary/cloth_aabb_union, which {TASK_SPACE_VOLUME_GROUP} is normalised with")
         aabb = root["summary"]["cloth_aabb_union"][:].astype(np.float32)          # the dtype GarmentInputDataset normalises with
+    cameras = None
+    if point_clouds:
+        if "summary/cloth_aabb_union" not in root:
+            raise ValueError(f"{zarr_in}: no summary/cloth_aabb_union, which the cameras of --point_clouds are placed around")
+        cameras = point_cloud.camera_ring(root["summary"]["cloth_aabb_union"][:], pc_views, pc_img_size, pc_fov, pc_elevation, pc_azimuth0, pc_distance)
+        if not 1 <= int(pc_img_size) <= 4096:
+            raise ValueError(f"pc_img_size {pc_img_size} outside [1, 4096]")
     comp = zarr_store.default_compressor()
     written = {g: 0 for g in groups + derived}
+    if point_clouds:
+        written["point_cloud"] = 0
     if marching_cubes:
         written["marching_cube_mesh"] = 0
     t_all = time.perf_counter()
@@ -167,6 +211,10 @@ def prepare_store(zarr_in, volume_size=128, groups=GROUPS, marching_cubes=False,
             for k, g in build_derived_groups(samples, chunk, derived, size, overwrite, backend, comp):
                 did[k].append(g)
                 written[g] += 1
+        if point_clouds:
+            for k in build_point_clouds(samples, chunk, cameras, int(pc_img_size), pc_color, overwrite, backend, comp):
+                did[k].append("point_cloud")
+                written["point_cloud"] += 1
         if marching_cubes:
             for k in chunk:
                 sg = samples[k]
@@ -195,7 +243,9 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         return prepare_store(a.zarr_in, a.volume_size, a.groups, a.marching_cubes, a.on_surface_distance, a.batch_size, a.overwrite, a.backend,
-                             log=lambda row: print(json.dumps(row)), derived_groups=a.derived_groups)
+                             log=lambda row: print(json.dumps(row)), derived_groups=a.derived_groups, point_clouds=a.point_clouds,
+                             pc_views=a.pc_views, pc_img_size=a.pc_img_size, pc_fov=a.pc_fov, pc_elevation=a.pc_elevation, pc_azimuth0=a.pc_azimuth0,
+                             pc_distance=a.pc_distance, pc_color=a.pc_color)
     except ValueError as e:
         ap.error(str(e))
 

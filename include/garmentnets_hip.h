@@ -1027,6 +1027,37 @@ int gn_render_mesh_batch(const float *verts, const int32_t *faces, const int64_t
 int gn_color_mesh_batch(const uint32_t *idx_img, const float *verts, const int32_t *faces, const float *colors, const int64_t *vseg_host,
                         const int64_t *fseg_host, const GnMeshImage *tab_host, const GnMeshImage *tab, int I, int S, float *out, void *stream);
 
+/* ---- Point clouds from meshes (csrc/render.hip; DESIGN.md "Point clouds from meshes"): the same rasteriser behind a free-standing perspective camera,
+ * perspective-correct depth and attributes, and the covered pixels compacted into point rows in raster order.  No atomics anywhere. ---- */
+
+typedef struct {
+    int64_t vert_begin, vert_end;    /* the rows of verts (and of nocs) of the image's mesh; a face indexes from vert_begin */
+    int64_t face_begin, face_end;    /* the rows of faces of the image's mesh; a pixel's index counts from face_begin */
+    double R[9], t[3];               /* world -> camera (x right, y down, z forward): cam[j] = ((R[3j] x + R[3j+1] y) + R[3j+2] z) + t[j] */
+    double f, c, znear;              /* u = (f * cam[0]) / cam[2] + c, v likewise; a face with a vertex at cam[2] < znear ("near") is never drawn */
+    float ambient;                   /* shade = ambient + (1 - ambient) * |n.p| / sqrt((n.n)(p.p)), in [0, 1] */
+    float base_color[3];             /* rgb = uint8(clamp(rint(255 * shade * base_color), 0, 255)) */
+} GnDepthImage;
+
+/* verts [..][3] fp32, faces [..][3] int32 -> out [I][S][S] uint32: per pixel the index (from face_begin) of the face that covers the pixel's sample with
+ * the LARGEST perspective-correct inverse depth (fp64), the lowest index among equal ones, 0xFFFFFFFF when nobody covers it.  Never drawn: what
+ * gn_render_mesh_batch never draws, and a face with a vertex at cam[2] < near.  Several images may share a mesh: vseg_host, fseg_host [M+1] are the CSRs of
+ * the M meshes and mesh_host [I] names each image's mesh.  HOST arrays, checked here (non-decreasing CSRs that the table repeats through mesh_host, fewer than
+ * 2^32 - 1 faces per mesh, finite R and t, f > 0 and finite, c finite, near > 0 and finite, ambient in [0, 1], I <= 65535, S in [1, GN_RENDER_MAX_SIZE]); tab:
+ * the same table in DEVICE memory, what the kernels read. */
+int gn_depth_render_batch(const float *verts, const int32_t *faces, const int64_t *vseg_host, const int64_t *fseg_host, int M, const int32_t *mesh_host,
+                          const GnDepthImage *tab_host, const GnDepthImage *tab, int I, int S, uint32_t *out, void *stream);
+/* idx_img [I][S][S] -> row_off [I*S+1] int64: the exclusive prefix sum, over image rows in (image, Y) order, of the number of covered pixels (index !=
+ * 0xFFFFFFFF) per row, the total last; sizes [I] int64: covered pixels per image.  A count per row (one wave each), then one scan. */
+int gn_depth_cloud_offsets(const uint32_t *idx_img, int I, int S, int64_t *row_off, int64_t *sizes, void *stream);
+/* the covered pixels of idx_img (gn_depth_render_batch's, same verts / faces / table) as point rows, image after image, within an image in raster order
+ * (Y, then X): the pixel of row offset r writes point [r][3] fp32 (the perspective-correct mix of the face's corners), nocs_out [r][3] fp32 (the same mix
+ * of the rows of nocs [..][3], one per row of verts) and rgb [r][3] uint8.  row_off: gn_depth_cloud_offsets' of the same idx_img; N: the rows the three
+ * outputs hold (row_off's total); a row offset outside [0, N) is not written. */
+int gn_depth_cloud_write(const uint32_t *idx_img, const float *verts, const float *nocs, const int32_t *faces, const int64_t *vseg_host,
+                         const int64_t *fseg_host, int M, const int32_t *mesh_host, const GnDepthImage *tab_host, const GnDepthImage *tab,
+                         const int64_t *row_off, int I, int S, int64_t N, float *point, float *nocs_out, uint8_t *rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
