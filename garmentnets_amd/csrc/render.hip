@@ -53,6 +53,25 @@ __device__ __forceinline__ void rd_span(int v, int k, int S, int &lo, int &hi) {
     hi = a + k - 1 > S - 1 ? S - 1 : a + k - 1;
 }
 
+// The ballot compaction of a stage: -> this thread's slot among the block's kept items (kept: hit), which stay in ascending thread order; total: how many
+// are kept.  It CONTAINS TWO __syncthreads(), so every thread of the block calls it, whatever its hit: the first ends the previous tile's scan (after it
+// the stage may be overwritten), the second publishes the wave counts.  The caller writes its slot and places the third barrier before it scans.
+__device__ __forceinline__ int rd_compact(bool hit, int lane, int wave, int (&scnt)[RD_WAVES], int &total) {
+    const unsigned long long mask = __ballot(hit);
+    __syncthreads();
+    if (lane == 0) scnt[wave] = __popcll(mask);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < RD_WAVES; ++w) {
+        const int n = scnt[w];
+        base += w < wave ? n : 0;
+        total += n;
+    }
+    return base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
 // tab: per image (first point, end point, side, k) as int64
 __global__ __launch_bounds__(RD_BLOCK) void render_points_batch_kernel(const float *__restrict__ points, const int64_t *__restrict__ tab, int S,
                                                                        uint32_t *__restrict__ out) {
@@ -77,19 +96,9 @@ __global__ __launch_bounds__(RD_BLOCK) void render_points_batch_kernel(const flo
             rd_span(rd_pixel(c[1], S), k, S, ylo, yhi);
             hit = xlo <= tx0 + RD_TILE - 1 && xhi >= tx0 && ylo <= ty0 + RD_TILE - 1 && yhi >= ty0;
         }
-        const unsigned long long mask = __ballot(hit);
-        __syncthreads();                                                 // the previous tile's scan is over: the stage may be overwritten
-        if (lane == 0) scnt[wave] = __popcll(mask);
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RD_WAVES; ++w) {
-            const int n = scnt[w];
-            base += w < wave ? n : 0;
-            total += n;
-        }
+        int total;
+        const int slot = rd_compact(hit, lane, wave, scnt, total);       // (two barriers inside)
         if (hit) {
-            const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
             sz[slot] = c[2];
             sx[slot] = (uint32_t)xlo | ((uint32_t)xhi << 16);
             sy[slot] = (uint32_t)ylo | ((uint32_t)yhi << 16);
@@ -275,6 +284,15 @@ __device__ __forceinline__ bool mr_cover(int ax, int ay, int bx, int by, int cx,
            (wc > 0 || (wc == 0 && mr_owns(ax, ay, bx, by)));
 }
 
+// n = (B - A) x (C - A) on the camera coordinates of the (oriented) face
+__device__ __forceinline__ void mr_normal(const MrFace &f, double &nx, double &ny, double &nz) {
+    const double ux = __dsub_rn(f.cam[1][0], f.cam[0][0]), uy = __dsub_rn(f.cam[1][1], f.cam[0][1]), uz = __dsub_rn(f.cam[1][2], f.cam[0][2]);
+    const double vx = __dsub_rn(f.cam[2][0], f.cam[0][0]), vy = __dsub_rn(f.cam[2][1], f.cam[0][1]), vz = __dsub_rn(f.cam[2][2], f.cam[0][2]);
+    nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy));
+    ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
+    nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+}
+
 // What a rasteriser is made of besides the loop below: its table entry, how a face gets to the screen (face(): x, y, v, cam and the three staged values z),
 // what the staged values give at a covered sample (value()) and which of two such values is nearer (nearer(); farthest() loses to every finite one).
 struct MrOrtho {                                                          // the mesh images: the axis camera of `side`, the interpolated depth, smallest wins
@@ -317,19 +335,9 @@ __device__ __forceinline__ void mr_raster(const float *__restrict__ verts, const
             const int ylo = (min(f.y[0], min(f.y[1], f.y[2])) + 127) >> 8, yhi = (max(f.y[0], max(f.y[1], f.y[2])) - 128) >> 8;
             hit = xlo <= xhi && ylo <= yhi && xlo <= min(tx0 + RD_TILE, S) - 1 && xhi >= tx0 && ylo <= min(ty0 + RD_TILE, S) - 1 && yhi >= ty0;
         }
-        const unsigned long long mask = __ballot(hit);
-        __syncthreads();                                                 // the previous tile's scan is over: the stage may be overwritten
-        if (lane == 0) scnt[wave] = __popcll(mask);
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RD_WAVES; ++w) {
-            const int n = scnt[w];
-            base += w < wave ? n : 0;
-            total += n;
-        }
+        int total;
+        const int slot = rd_compact(hit, lane, wave, scnt, total);       // (two barriers inside)
         if (hit) {
-            const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
 #pragma unroll
             for (int k = 0; k < 3; ++k) { sx[k][slot] = f.x[k]; sy[k][slot] = f.y[k]; sz[k][slot] = f.z[k]; }
             si[slot] = (uint32_t)(j - begin);
@@ -344,6 +352,14 @@ __device__ __forceinline__ void mr_raster(const float *__restrict__ verts, const
     }
     if (X < S && Y < S) out[((int64_t)blockIdx.z * S + Y) * S + X] = best_idx;
 }
+
+// The winner's weights from its index: the colour / write passes store no weights, they rebuild face `idx` of the image (counted from its first face; iv, V:
+// the image's vertices) under the policy P and cover the sample of pixel (X, Y) again.  false: not a face of the image, never drawn, or not covering --
+// none of which an index image of mr_raster<P> holds.  A macro ON PURPOSE: as an inlined function template (references or the sample point passed, with
+// or without __restrict__, one return or three) the same text took depth_cloud_write_kernel from 76 to 86 SGPRs.
+#define MR_WINNER(P, im, iv, V, faces, idx, X, Y, S, f, wa, wb, wc)                                                              \
+    ((int64_t)(idx) < (im).face_end - (im).face_begin && P::face(im, iv, V, (faces) + 3 * ((im).face_begin + (idx)), S, f) && \
+     mr_cover((f).x[0], (f).y[0], (f).x[1], (f).y[1], (f).x[2], (f).y[2], 256 * (X) + 128, 256 * (Y) + 128, wa, wb, wc))
 
 __global__ __launch_bounds__(RD_BLOCK) void render_mesh_batch_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
                                                                      const GnMeshImage *__restrict__ tab, int S, uint32_t *__restrict__ out) {
@@ -362,19 +378,14 @@ __global__ __launch_bounds__(256) void color_mesh_batch_kernel(const uint32_t *_
     float4 col = make_float4(im.default_color[0], im.default_color[1], im.default_color[2], im.default_color[3]);
     MrFace f;
     long long wa, wb, wc;
-    if (idx != RD_NONE && (int64_t)idx < im.face_end - im.face_begin &&
-        mr_face(verts + 3 * im.vert_begin, im.vert_end - im.vert_begin, faces + 3 * (im.face_begin + idx), im.side, S, f) &&
-        mr_cover(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2], 256 * X + 128, 256 * Y + 128, wa, wb, wc)) {
+    if (idx != RD_NONE && MR_WINNER(MrOrtho, im, verts + 3 * im.vert_begin, im.vert_end - im.vert_begin, faces, idx, X, Y, S, f, wa, wb, wc)) {
         const double area2 = (double)(wa + wb + wc);
         const float ba = (float)__ddiv_rn((double)wa, area2), bb = (float)__ddiv_rn((double)wb, area2), bc = (float)__ddiv_rn((double)wc, area2);
         const float4 ca = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[0]));
         const float4 cb = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[1]));
         const float4 cc = *reinterpret_cast<const float4 *>(colors + 4 * (im.vert_begin + f.v[2]));
-        // n = (B - A) x (C - A) on the camera coordinates
-        const double ux = __dsub_rn(f.cam[1][0], f.cam[0][0]), uy = __dsub_rn(f.cam[1][1], f.cam[0][1]), uz = __dsub_rn(f.cam[1][2], f.cam[0][2]);
-        const double vx = __dsub_rn(f.cam[2][0], f.cam[0][0]), vy = __dsub_rn(f.cam[2][1], f.cam[0][1]), vz = __dsub_rn(f.cam[2][2], f.cam[0][2]);
-        const double nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy)), ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
-        const double nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+        double nx, ny, nz;
+        mr_normal(f, nx, ny, nz);
         const double len = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(nx, nx), __dmul_rn(ny, ny)), __dmul_rn(nz, nz)));
         const double amb = (double)im.ambient;
         double shade = amb;
@@ -388,11 +399,18 @@ __global__ __launch_bounds__(256) void color_mesh_batch_kernel(const uint32_t *_
     *reinterpret_cast<float4 *>(out + 4 * o) = col;
 }
 
+// entry i of the two host CSRs; what: "image" or "mesh", whichever the CSRs count
+static int mr_check_csr(const char *who, const char *what, const int64_t *vseg_host, const int64_t *fseg_host, int i) {
+    GN_REQUIRE(vseg_host[i] >= 0 && vseg_host[i + 1] >= vseg_host[i], "%s: %s %d: vseg is not a non-decreasing CSR", who, what, i);
+    GN_REQUIRE(fseg_host[i] >= 0 && fseg_host[i + 1] >= fseg_host[i], "%s: %s %d: fseg is not a non-decreasing CSR", who, what, i);
+    return GN_OK;
+}
+
 static int mr_check(const char *who, const int64_t *vseg_host, const int64_t *fseg_host, const GnMeshImage *tab_host, int I) {
     for (int i = 0; i < I; ++i) {
         const GnMeshImage &g = tab_host[i];
-        GN_REQUIRE(vseg_host[i] >= 0 && vseg_host[i + 1] >= vseg_host[i], "%s: image %d: vseg is not a non-decreasing CSR", who, i);
-        GN_REQUIRE(fseg_host[i] >= 0 && fseg_host[i + 1] >= fseg_host[i], "%s: image %d: fseg is not a non-decreasing CSR", who, i);
+        const int rc = mr_check_csr(who, "image", vseg_host, fseg_host, i);
+        if (rc != GN_OK) return rc;
         GN_REQUIRE(g.vert_begin == vseg_host[i] && g.vert_end == vseg_host[i + 1] && g.face_begin == fseg_host[i] && g.face_end == fseg_host[i + 1],
                    "%s: image %d: the table's segments differ from vseg / fseg", who, i);
         GN_REQUIRE(g.face_end - g.face_begin < (int64_t)RD_NONE, "%s: image %d: a segment of %lld faces (needs fewer than 2^32 - 1)", who, i,
@@ -576,8 +594,7 @@ __global__ __launch_bounds__(256) void depth_cloud_write_kernel(const uint32_t *
         uint8_t col[3] = {0, 0, 0};
         MrFace f;
         long long wa, wb, wc;
-        if ((int64_t)idx < im.face_end - im.face_begin && MrPersp::face(im, iv, V, faces + 3 * (im.face_begin + idx), S, f) &&
-            mr_cover(f.x[0], f.y[0], f.x[1], f.y[1], f.x[2], f.y[2], 256 * X + 128, 256 * Y + 128, wa, wb, wc)) {
+        if (MR_WINNER(MrPersp, im, iv, V, faces, idx, X, Y, S, f, wa, wb, wc)) {
             const double qa = __dmul_rn((double)wa, f.z[0]), qb = __dmul_rn((double)wb, f.z[1]), qc = __dmul_rn((double)wc, f.z[2]);
             const double q = __dadd_rn(__dadd_rn(qa, qb), qc);
             const double ba = __ddiv_rn(qa, q), bb = __ddiv_rn(qb, q), bc = __ddiv_rn(qc, q);
@@ -588,13 +605,10 @@ __global__ __launch_bounds__(256) void depth_cloud_write_kernel(const uint32_t *
                 P[c] = (float)__dadd_rn(__dadd_rn(__dmul_rn(ba, (double)A[c]), __dmul_rn(bb, (double)B[c])), __dmul_rn(bc, (double)C[c]));
                 L[c] = (float)__dadd_rn(__dadd_rn(__dmul_rn(ba, (double)LA[c]), __dmul_rn(bb, (double)LB[c])), __dmul_rn(bc, (double)LC[c]));
             }
-            // n = (B - A) x (C - A) on the camera coordinates; p = the point seen from the camera
-            const double ux = __dsub_rn(f.cam[1][0], f.cam[0][0]), uy = __dsub_rn(f.cam[1][1], f.cam[0][1]), uz = __dsub_rn(f.cam[1][2], f.cam[0][2]);
-            const double vx = __dsub_rn(f.cam[2][0], f.cam[0][0]), vy = __dsub_rn(f.cam[2][1], f.cam[0][1]), vz = __dsub_rn(f.cam[2][2], f.cam[0][2]);
-            const double nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy)), ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
-            const double nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+            double nx, ny, nz;
+            mr_normal(f, nx, ny, nz);
             const double amb = (double)im.ambient;
-            double shade = amb, p[3];
+            double shade = amb, p[3];                                     // p = the point seen from the camera
             if (pc_camera(im, P, p)) {
                 const double nn = __dadd_rn(__dadd_rn(__dmul_rn(nx, nx), __dmul_rn(ny, ny)), __dmul_rn(nz, nz));
                 const double pp = __dadd_rn(__dadd_rn(__dmul_rn(p[0], p[0]), __dmul_rn(p[1], p[1])), __dmul_rn(p[2], p[2]));
@@ -622,8 +636,8 @@ static int pc_check(const char *who, const int64_t *vseg_host, const int64_t *fs
                     int I) {
     GN_REQUIRE(M >= 0, "%s: M=%d meshes", who, M);
     for (int m = 0; m < M; ++m) {
-        GN_REQUIRE(vseg_host[m] >= 0 && vseg_host[m + 1] >= vseg_host[m], "%s: mesh %d: vseg is not a non-decreasing CSR", who, m);
-        GN_REQUIRE(fseg_host[m] >= 0 && fseg_host[m + 1] >= fseg_host[m], "%s: mesh %d: fseg is not a non-decreasing CSR", who, m);
+        const int rc = mr_check_csr(who, "mesh", vseg_host, fseg_host, m);
+        if (rc != GN_OK) return rc;
         GN_REQUIRE(fseg_host[m + 1] - fseg_host[m] < (int64_t)RD_NONE, "%s: mesh %d: a segment of %lld faces (needs fewer than 2^32 - 1)", who, m,
                    (long long)(fseg_host[m + 1] - fseg_host[m]));
     }

@@ -150,11 +150,6 @@ def distance_field(meshes, shape, backend=None):
     if backend == "numpy":
         fields = [distance_field_reference(v, f, shape) for v, f in meshes]
         return np.stack([d for d, _ in fields]), np.stack([i for _, i in fields])
-    import torch
-
     from . import ops
-    dev = torch.device("cuda", torch.cuda.current_device())
-    on_dev = [(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev),
-               torch.from_numpy(np.ascontiguousarray(np.asarray(f).reshape(-1, 3), dtype=np.int64)).to(dev)) for v, f in meshes]
-    d2, face_idx = ops.distance_field_batch(on_dev, shape)
+    d2, face_idx = ops.distance_field_batch(ops.meshes_f64(meshes), shape)
     return d2.cpu().numpy(), face_idx.cpu().numpy()

@@ -1137,6 +1137,12 @@ def _rows3_f64(t, name):
     return t
 
 
+def _rows3_f32(t, name):
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected an (N, 3) tensor, got {tuple(t.shape)}")
+    return _chk(t.contiguous(), torch.float32, name)
+
+
 def _cat_sets(tensors, name, dtype=torch.float64, width=3, dedup=True):
     """concatenate point / face sets -> (joint tensor, row offset of each entry); dedup: a tensor passed more than once is stored once (for
     the READ-ONLY sets: query rows are also output rows and must not share them)"""
@@ -1198,6 +1204,31 @@ def _faces_i32(f):
     return f
 
 
+def _mesh_sets(who, meshes, queries=None, rows3=_rows3_f64, dedup=False):
+    """the list-of-meshes work of the mesh-pair wrappers: every mesh's (verts, faces) checked (rows3: _rows3_f64, or _rows3_f32 for the entry that
+    takes fp32 and does not cast), the joint vertices and int32 faces (dedup: a mesh tensor passed more than once is stored once), the 2^31 refusal
+    under the caller's name, and the int64 device table: with `queries` (a list of row sets, one per mesh; output rows, so never shared) a pair row
+    (q0, nq, v0, nv, f0, nf) per mesh, without them the CSR rows (v0, f0) closed by the totals.  -> (joint queries or None, v, f, table, rows)"""
+    queries = None if queries is None else [_rows3_f64(q, "query") for q in queries]
+    verts = [rows3(v, "verts") for v, _ in meshes]
+    faces = [_faces_i32(f) for _, f in meshes]
+    q, qo = (None, None) if queries is None else _cat_sets(queries, "query", dedup=False)
+    v, vo = _cat_sets(verts, "verts", dtype=verts[0].dtype, dedup=dedup)
+    f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=dedup)
+    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: more than 2^31 vertices or faces")
+    if queries is None:
+        rows = [(vo[k], fo[k]) for k in range(len(meshes))] + [(v.shape[0], f.shape[0])]
+    else:
+        rows = [(qo[k], queries[k].shape[0], vo[k], verts[k].shape[0], fo[k], faces[k].shape[0]) for k in range(len(meshes))]
+    return q, v, f, _pairs_table(rows, v.device), rows
+
+
+def _raise_bad_face(flag, who):
+    if flag:
+        raise IndexError(f"{who}: a face index is out of bounds for its mesh's vertices")
+
+
 def point_mesh_sqdist_batch(queries, meshes):
     """fp64 unsigned squared distance of every query to the nearest triangle of its mesh, every (queries[k], meshes[k] = (verts, faces))
     pair in ONE launch (gn_point_mesh_sqdist_batch) -> list of (face_idx int32 [nq_k], d2 float64 [nq_k]).  libigl's
@@ -1207,25 +1238,13 @@ def point_mesh_sqdist_batch(queries, meshes):
         raise ValueError("point_mesh_sqdist_batch: one mesh per query set")
     if not queries:
         return []
-    queries = [_rows3_f64(q, "query") for q in queries]
-    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
-    faces = [_faces_i32(f) for _, f in meshes]
-    dev = queries[0].device
-    q, qo = _cat_sets(queries, "query", dedup=False)
-    v, vo = _cat_sets(verts, "verts")
-    f, fo = _cat_sets(faces, "faces", dtype=_i32)
-    if v.shape[0] >= 2 ** 31 or (f is not None and f.shape[0] >= 2 ** 31):
-        raise ValueError("point_mesh_sqdist_batch: more than 2^31 vertices or faces")
-    rows = [(qo[k], queries[k].shape[0], vo[k], verts[k].shape[0], fo[k], faces[k].shape[0]) for k in range(len(queries))]
-    pairs = _pairs_table(rows, dev)
-    max_nq = max(r[1] for r in rows)
-    face_idx = torch.empty(q.shape[0], dtype=_i32, device=dev)
-    d2 = torch.empty(q.shape[0], dtype=torch.float64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    _lib.call("gn_point_mesh_sqdist_batch", _p(q), _p(v), _p(f) if f is not None else None, _p(pairs), len(rows), max_nq, _p(face_idx), _p(d2),
-              _p(bad), _stream())
-    if int(bad.item()):
-        raise IndexError("point_mesh_sqdist: a face index is out of bounds for its mesh's vertices")
+    q, v, f, pairs, rows = _mesh_sets("point_mesh_sqdist_batch", meshes, queries, dedup=True)
+    face_idx = torch.empty(q.shape[0], dtype=_i32, device=q.device)
+    d2 = torch.empty(q.shape[0], dtype=torch.float64, device=q.device)
+    bad = torch.zeros(1, dtype=torch.int64, device=q.device)
+    _lib.call("gn_point_mesh_sqdist_batch", _p(q), _p(v), _p(f), _p(pairs), len(rows), max(r[1] for r in rows), _p(face_idx), _p(d2), _p(bad),
+              _stream())
+    _raise_bad_face(bad.item(), "point_mesh_sqdist")
     return [(face_idx[r[0]:r[0] + r[1]], d2[r[0]:r[0] + r[1]]) for r in rows]
 
 
@@ -1243,23 +1262,11 @@ def winding_number_batch(queries, meshes):
         raise ValueError("winding_number_batch: one mesh per query set")
     if not queries:
         return []
-    queries = [_rows3_f64(q, "query") for q in queries]
-    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
-    faces = [_faces_i32(f) for _, f in meshes]
-    dev = queries[0].device
-    q, qo = _cat_sets(queries, "query", dedup=False)
-    v, vo = _cat_sets(verts, "verts")
-    f, fo = _cat_sets(faces, "faces", dtype=_i32)
-    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
-        raise ValueError("winding_number_batch: more than 2^31 vertices or faces")
-    rows = [(qo[k], queries[k].shape[0], vo[k], verts[k].shape[0], fo[k], faces[k].shape[0]) for k in range(len(queries))]
-    pairs = _pairs_table(rows, dev)
-    max_nq = max(r[1] for r in rows)
-    out = torch.empty(q.shape[0], dtype=torch.float64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    _lib.call("gn_winding_number_batch", _p(q), _p(v), _p(f), _p(pairs), len(rows), max_nq, _p(out), _p(bad), _stream())
-    if int(bad.item()):
-        raise IndexError("winding_number: a face index is out of bounds for its mesh's vertices")
+    q, v, f, pairs, rows = _mesh_sets("winding_number_batch", meshes, queries, dedup=True)
+    out = torch.empty(q.shape[0], dtype=torch.float64, device=q.device)
+    bad = torch.zeros(1, dtype=torch.int64, device=q.device)
+    _lib.call("gn_winding_number_batch", _p(q), _p(v), _p(f), _p(pairs), len(rows), max(r[1] for r in rows), _p(out), _p(bad), _stream())
+    _raise_bad_face(bad.item(), "winding_number")
     return [out[r[0]:r[0] + r[1]] for r in rows]
 
 
@@ -1276,19 +1283,11 @@ def winding_field_batch(meshes, shape):
     D, H, W = (int(n) for n in shape)
     if not meshes:
         raise ValueError("winding_field_batch: no meshes")
-    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
-    faces = [_faces_i32(f) for _, f in meshes]
-    dev = verts[0].device
-    v, vo = _cat_sets(verts, "verts", dedup=False)
-    f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
-    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
-        raise ValueError("winding_field_batch: more than 2^31 vertices or faces")
-    csr = _pairs_table([(vo[k], fo[k]) for k in range(len(meshes))] + [(v.shape[0], f.shape[0])], dev)
-    out = torch.empty((len(meshes), D, H, W), dtype=torch.float32, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _, v, f, csr, _ = _mesh_sets("winding_field_batch", meshes)
+    out = torch.empty((len(meshes), D, H, W), dtype=torch.float32, device=v.device)
+    bad = torch.zeros(1, dtype=torch.int64, device=v.device)
     _lib.call("gn_winding_field_batch", _p(v), _p(f), _p(csr), len(meshes), D, H, W, _p(out), _p(bad), _stream())
-    if int(bad.item()):
-        raise IndexError("winding_field: a face index is out of bounds for its mesh's vertices")
+    _raise_bad_face(bad.item(), "winding_field")
     return out
 
 
@@ -1302,20 +1301,12 @@ def distance_field_batch(meshes, shape):
         raise ValueError("distance_field_batch: no meshes")
     if min(D, H, W) < 2 or D * H * W >= 2 ** 31 - 1:        # the limits of the entry, refused here before the outputs are allocated
         raise ValueError(f"gn_distance_field_batch: lattice {(D, H, W)}: every axis needs >= 2 nodes and D*H*W < 2^31")
-    verts = [_rows3_f64(v, "verts") for v, _ in meshes]
-    faces = [_faces_i32(f) for _, f in meshes]
-    dev = verts[0].device
-    v, vo = _cat_sets(verts, "verts", dedup=False)
-    f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
-    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
-        raise ValueError("distance_field_batch: more than 2^31 vertices or faces")
-    csr = _pairs_table([(vo[k], fo[k]) for k in range(len(meshes))] + [(v.shape[0], f.shape[0])], dev)
-    face_idx = torch.empty((len(meshes), D, H, W), dtype=_i32, device=dev)
-    d2 = torch.empty((len(meshes), D, H, W), dtype=torch.float64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _, v, f, csr, _ = _mesh_sets("distance_field_batch", meshes)
+    face_idx = torch.empty((len(meshes), D, H, W), dtype=_i32, device=v.device)
+    d2 = torch.empty((len(meshes), D, H, W), dtype=torch.float64, device=v.device)
+    bad = torch.zeros(1, dtype=torch.int64, device=v.device)
     _lib.call("gn_distance_field_batch", _p(v), _p(f), _p(csr), len(meshes), D, H, W, _p(face_idx), _p(d2), _p(bad), _stream())
-    if int(bad.item()):
-        raise IndexError("distance_field: a face index is out of bounds for its mesh's vertices")
+    _raise_bad_face(bad.item(), "distance_field")
     return d2, face_idx
 
 
@@ -1329,8 +1320,7 @@ def _qt_bad(bad, who):
     index, short = (int(v) for v in bad.tolist())                    # one host synchronisation
     if short:
         raise _lib.GarmentNetsHipError(f"{who}: a mesh has more faces than the max_nf the workspace was sized for")
-    if index:
-        raise IndexError(f"{who}: a face index is out of bounds for its mesh's vertices")
+    _raise_bad_face(index, who)
 
 
 def query_targets_batch(queries, meshes, kind, tsdf_clip_value=None, absolute=False, return_fp64=False):
@@ -1353,18 +1343,8 @@ def query_targets_batch(queries, meshes, kind, tsdf_clip_value=None, absolute=Fa
     d2 = torch.empty((B, M), dtype=torch.float64, device=dev) if return_fp64 and need_d else None
     face_idx = torch.empty((B, M), dtype=_i32, device=dev) if return_fp64 and need_d else None
     if B:
-        verts = []
-        for v, _ in meshes:
-            if v.dim() != 2 or v.shape[1] != 3:
-                raise ValueError(f"verts: expected an (N, 3) tensor, got {tuple(v.shape)}")
-            verts.append(_chk(v.contiguous(), torch.float32, "verts"))
-        faces = [_faces_i32(f) for _, f in meshes]
-        v, vo = _cat_sets(verts, "verts", dtype=torch.float32, dedup=False)
-        f, fo = _cat_sets(faces, "faces", dtype=_i32, dedup=False)
-        if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
-            raise ValueError("query_targets_batch: more than 2^31 vertices or faces")
-        csr = _pairs_table([(vo[k], fo[k]) for k in range(B)] + [(v.shape[0], f.shape[0])], dev)
-        max_nf = max(int(x.shape[0]) for x in faces)
+        _, v, f, csr, _ = _mesh_sets("query_targets_batch", meshes, rows3=_rows3_f32)
+        max_nf = max(int(x.shape[0]) for _, x in meshes)
         nbytes = _lib.load().gn_query_targets_workspace_bytes(B, M, max_nf, code)
         ws = _ws(nbytes, dev)
         bad = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -1383,6 +1363,11 @@ def _check_sets(n):
 
 def _table(cls, rows):
     return (cls * len(rows))(*[cls(*r) for r in rows])
+
+
+def _table_dev(tab, device):
+    """a host ctypes table -> its bytes as a uint8 tensor on the device (a copy: the host table may be reused or freed)"""
+    return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device)
 
 
 def nocs_bin_metrics(sets, bins, mirror_axis=None):
@@ -2151,36 +2136,68 @@ def color_idx_batch(idx_img, images, colors=None, values=None):
         e.num_overlays = len(overlays)
         for o, (xyz, rgba, k) in zip(e.overlay, overlays):
             o.xyz[:], o.rgba[:], o.kernel_size = [float(v) for v in xyz], [float(v) for v in rgba], int(k)
-    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    tab_dev = _table_dev(tab, dev)
     _lib.call("gn_color_idx_batch", _p(idx_img), ctypes.cast(tab, ctypes.c_void_p), _p(tab_dev), _p(colors), _p(values), n, S, _p(out), _stream())
     return out
 
 
+# ------------------------------------------------------------------------------------------------ lists of meshes -> the device
+def meshes_f64(meshes, device=None):
+    """[(verts, faces)] numpy arrays -> [(fp64 (V, 3), int64 (F, 3))] on the device (default: the current one): what the field entries take"""
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    return [(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev),
+             torch.from_numpy(np.ascontiguousarray(np.asarray(f).reshape(-1, 3), dtype=np.int64)).to(dev)) for v, f in meshes]
+
+
+def pack_meshes(meshes, extra_widths=(), device=None):
+    """[(verts, faces, *per-vertex extras)], numpy arrays or torch tensors on the host or the device -> (verts (V, 3) fp32, faces (F, 3) int32,
+    *extras (V, width) fp32, vseg, fseg): the meshes back to back on the device (arrays go to `device`, default the current one; tensors stay where
+    they are) with their host CSRs, as the segmented-mesh entries take them"""
+    def dev(a, dtype, width):
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.int32 if dtype == _i32 else np.float32)).to(device or "cuda")
+        return a.detach().to(dtype).reshape(-1, width)
+
+    columns = [[dev(m[k], _i32 if k == 1 else torch.float32, w) for m in meshes] for k, w in enumerate((3, 3) + tuple(extra_widths))]
+    vseg, fseg = (np.concatenate([[0], np.cumsum([t.shape[0] for t in col])]).astype(np.int64) for col in columns[:2])
+    return tuple(torch.cat(col).contiguous() for col in columns) + (vseg, fseg)
+
+
 # ------------------------------------------------------------------------------------------------ mesh images
-def _mesh_args(who, verts, faces, vseg, fseg, sides, ambients, default_colors):
-    """the checked tensors, the two host CSRs and the GnMeshImage table (host, device) of the mesh entries.  What only sizes an access is refused
-    here (a segment beyond its tensor); sides, ambients and the CSRs' order are the entry's to refuse, in its words"""
+def _segmented_meshes(who, verts, faces, vseg, fseg, entries):
+    """the shared head of _mesh_args / _depth_args: the checked tensors and the two host CSRs.  entries(M by vseg, M by fseg) refuses the caller's own
+    per-image lists in between; then what only sizes an access is refused (a segment beyond its tensor).  The CSRs' order is the entry's to refuse"""
     verts, faces = _chk(verts, torch.float32, "verts"), _chk(faces, _i32, "faces")
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
         raise ValueError(f"{who}: expected (V, 3) fp32 verts and (F, 3) int32 faces on one device, got {tuple(verts.shape)}, {tuple(faces.shape)}")
     vseg = np.ascontiguousarray(np.asarray(vseg, dtype=np.int64).reshape(-1))
     fseg = np.ascontiguousarray(np.asarray(fseg, dtype=np.int64).reshape(-1))
-    n = vseg.shape[0] - 1
-    side = [_side(s) for s in sides]
-    ambients = [0.35] * n if ambients is None else list(ambients)
-    default_colors = [(1.0, 1.0, 1.0, 0.0)] * n if default_colors is None else list(default_colors)
-    if n < 0 or fseg.shape[0] != n + 1 or len(side) != n or len(ambients) != n or len(default_colors) != n:
-        raise ValueError(f"{who}: vseg and fseg hold I + 1 entries for I sides, ambients and default colours")
-    if n and (vseg.max() > verts.shape[0] or fseg.max() > faces.shape[0]):
+    entries(vseg.shape[0] - 1, fseg.shape[0] - 1)
+    if vseg.shape[0] > 1 and (vseg.max() > verts.shape[0] or fseg.max() > faces.shape[0]):
         raise ValueError(f"{who}: a segment ends beyond its tensor ({verts.shape[0]} verts, {faces.shape[0]} faces)")
+    return verts, faces, vseg, fseg
+
+
+def _mesh_args(who, verts, faces, vseg, fseg, sides, ambients, default_colors):
+    """_segmented_meshes and the GnMeshImage table (host, device) of the mesh entries; sides and ambients are the entry's to refuse, in its words"""
+    def entries(n, nf):
+        nonlocal side, ambients, default_colors
+        side = [_side(s) for s in sides]
+        ambients = [0.35] * n if ambients is None else list(ambients)
+        default_colors = [(1.0, 1.0, 1.0, 0.0)] * n if default_colors is None else list(default_colors)
+        if n < 0 or nf != n or len(side) != n or len(ambients) != n or len(default_colors) != n:
+            raise ValueError(f"{who}: vseg and fseg hold I + 1 entries for I sides, ambients and default colours")
+
+    side = None
+    verts, faces, vseg, fseg = _segmented_meshes(who, verts, faces, vseg, fseg, entries)
+    n = len(side)
     tab = (_lib.MeshImage * max(n, 1))()
     for i in range(n):
         e = tab[i]
         e.vert_begin, e.vert_end, e.face_begin, e.face_end = int(vseg[i]), int(vseg[i + 1]), int(fseg[i]), int(fseg[i + 1])
         e.side, e.ambient = side[i], float(ambients[i])
         e.default_color[:] = [float(v) for v in default_colors[i]]
-    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(verts.device)
-    return verts, faces, vseg, fseg, tab, tab_dev, n
+    return verts, faces, vseg, fseg, tab, _table_dev(tab, verts.device), n
 
 
 def render_mesh_batch(verts, faces, vseg, fseg, sides, img_size):
@@ -2224,25 +2241,22 @@ def color_mesh_batch(idx_img, verts, faces, colors, vseg, fseg, sides, ambients=
 
 # ------------------------------------------------------------------------------------------------ point clouds from meshes
 def _depth_args(who, verts, faces, vseg, fseg, mesh_of, cameras, ambients, base_colors):
-    """the checked tensors, the meshes' host CSRs, the images' mesh numbers and the GnDepthImage table (host, device).  cameras: one record per image
-    ({"R" (3, 3), "t" (3,), "f", "c", "near"}; point_cloud.camera_ring builds them).  What only sizes an access is refused here (a segment beyond its
-    tensor, a mesh number outside the CSRs); cameras, ambients and the CSRs' order are the entry's to refuse, in its words"""
-    verts, faces = _chk(verts, torch.float32, "verts"), _chk(faces, _i32, "faces")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
-        raise ValueError(f"{who}: expected (V, 3) fp32 verts and (F, 3) int32 faces on one device, got {tuple(verts.shape)}, {tuple(faces.shape)}")
-    vseg = np.ascontiguousarray(np.asarray(vseg, dtype=np.int64).reshape(-1))
-    fseg = np.ascontiguousarray(np.asarray(fseg, dtype=np.int64).reshape(-1))
-    mesh_of = np.ascontiguousarray(np.asarray(mesh_of, dtype=np.int32).reshape(-1))
+    """_segmented_meshes, the images' mesh numbers and the GnDepthImage table (host, device).  cameras: one record per image ({"R" (3, 3), "t" (3,),
+    "f", "c", "near"}; point_cloud.camera_ring builds them).  A mesh number outside the CSRs would size an access too and is refused here; cameras
+    and ambients are the entry's to refuse, in its words"""
+    def entries(m, mf):
+        nonlocal mesh_of, cameras, ambients, base_colors
+        mesh_of = np.ascontiguousarray(np.asarray(mesh_of, dtype=np.int32).reshape(-1))
+        n, cameras = mesh_of.shape[0], list(cameras)
+        ambients = [0.35] * n if ambients is None else list(ambients)
+        base_colors = [(0.5, 0.5, 0.5)] * n if base_colors is None else list(base_colors)
+        if m < 0 or mf != m or len(cameras) != n or len(ambients) != n or len(base_colors) != n:
+            raise ValueError(f"{who}: vseg and fseg hold M + 1 entries for M meshes; mesh_of, cameras, ambients and base colours one entry per image")
+        if n and (m == 0 or mesh_of.min() < 0 or mesh_of.max() >= m):
+            raise ValueError(f"{who}: an image's mesh number is outside [0, M={m})")
+
+    verts, faces, vseg, fseg = _segmented_meshes(who, verts, faces, vseg, fseg, entries)
     m, n = vseg.shape[0] - 1, mesh_of.shape[0]
-    cameras = list(cameras)
-    ambients = [0.35] * n if ambients is None else list(ambients)
-    base_colors = [(0.5, 0.5, 0.5)] * n if base_colors is None else list(base_colors)
-    if m < 0 or fseg.shape[0] != m + 1 or len(cameras) != n or len(ambients) != n or len(base_colors) != n:
-        raise ValueError(f"{who}: vseg and fseg hold M + 1 entries for M meshes; mesh_of, cameras, ambients and base colours one entry per image")
-    if n and (m == 0 or mesh_of.min() < 0 or mesh_of.max() >= m):
-        raise ValueError(f"{who}: an image's mesh number is outside [0, M={m})")
-    if m and (vseg.max() > verts.shape[0] or fseg.max() > faces.shape[0]):
-        raise ValueError(f"{who}: a segment ends beyond its tensor ({verts.shape[0]} verts, {faces.shape[0]} faces)")
     tab = (_lib.DepthImage * max(n, 1))()
     for i in range(n):
         e, cam, g = tab[i], cameras[i], int(mesh_of[i])
@@ -2251,8 +2265,7 @@ def _depth_args(who, verts, faces, vseg, fseg, mesh_of, cameras, ambients, base_
         e.t[:] = [float(v) for v in np.asarray(cam["t"], dtype=np.float64).reshape(3)]
         e.f, e.c, e.znear, e.ambient = float(cam["f"]), float(cam["c"]), float(cam["near"]), float(ambients[i])
         e.base_color[:] = [float(v) for v in base_colors[i]]
-    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(verts.device)
-    return verts, faces, vseg, fseg, mesh_of, tab, tab_dev, m, n
+    return verts, faces, vseg, fseg, mesh_of, tab, _table_dev(tab, verts.device), m, n
 
 
 def depth_render_batch(verts, faces, vseg, fseg, mesh_of, cameras, img_size):
@@ -2313,7 +2326,7 @@ def grad_pack_table(rows, device):
         entries.append((ptr or None, int(off), int(numel), blk))
         blk += -(-int(numel) // _lib.ADAM_CHUNK)
     host = _table(_lib.PackEntry, entries)
-    return torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device), blk
+    return _table_dev(host, device), blk
 
 
 def grad_pack(table, n_entries, n_blocks, flat, world=1, flat_numel=None):

@@ -139,7 +139,7 @@ class FusedAdam(torch.optim.Optimizer):
         cached = self._tables.get(bi)
         if cached is None or cached[0] != key:
             host = (_lib.AdamEntry * len(entries))(*[_lib.AdamEntry(*e) for e in entries])
-            table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+            table = ops._table_dev(host, dev)
             cached = self._tables[bi] = (key, table)
         hy = (_lib.AdamHyper * len(used))()
         for h, i in used.items():

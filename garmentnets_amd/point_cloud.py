@@ -7,13 +7,17 @@ depth and labels, and the covered pixels of every view, in raster order, as the 
   render_point_clouds(meshes, cameras, S, ...)   every garment of a call times every view in one launch set (ops.depth_render_batch, ops.depth_cloud),
                                                  or, backend="numpy", the restatement below: the same operations in the same order, bit for bit
 
-The restatement spells every sum whose order the definition fixes; it uses neither `@` nor einsum there (a BLAS may fuse or reorder).
+The restatement spells every sum whose order the definition fixes; it uses neither `@` nor einsum there (a BLAS may fuse or reorder).  The coverage
+rules, the drawn faces, the index image and the winner's weights live in raster.py, shared with visualize.py; this module brings its pinhole, the
+near plane, the inverse depth, the mixes and the headlight.
 """
 import math
 
 import numpy as np
 
-from .visualize import DEFAULT_AMBIENT, DEFAULT_IDX, MESH_COORD_LIMIT, MESH_SUBPIXEL, _edge, _host, _mesh_weights
+from . import raster
+from .raster import _host
+from .visualize import DEFAULT_AMBIENT
 
 DEFAULT_FOV, DEFAULT_ELEVATION = 45.0, 20.0     # degrees; a look, not a measurement: how much of a view the garment fills, and from how high it is seen
 DEFAULT_BASE_COLOR = (0.5, 0.5, 0.5)            # a look as well: the grey the headlight shades
@@ -67,26 +71,13 @@ def to_camera(points, cam):
 
 
 def _depth_faces(verts, faces, cam):
-    """the drawn faces in positive orientation -> (index [D] int64, vertex indices [D, 3] after the swap, fx, fy [D, 3] int64, cam [D, 3, 3] fp64)"""
-    v = _host(verts).reshape(-1, 3)
-    f = _host(faces, np.int64).reshape(-1, 3)
-    keep = np.flatnonzero(((f >= 0) & (f < len(v))).all(axis=1))
-    f = f[keep]
+    """raster.drawn_faces behind the pinhole: screen = (f * x) / z + c, a vertex nearer than the near plane is not seen"""
     fl, c, near = np.float64(cam["f"]), np.float64(cam["c"]), np.float64(cam["near"])
-    with np.errstate(all="ignore"):
-        pc = to_camera(v, cam)[f]                                                       # (D, 3 corners, 3 coordinates)
-        ok = np.isfinite(v).all(axis=1)[f].all(axis=1) & (pc[:, :, 2] >= near).all(axis=1)
-        fx = np.rint(((fl * pc[:, :, 0]) / pc[:, :, 2] + c) * np.float64(MESH_SUBPIXEL))    # half to even
-        fy = np.rint(((fl * pc[:, :, 1]) / pc[:, :, 2] + c) * np.float64(MESH_SUBPIXEL))
-        ok &= (np.abs(fx) <= MESH_COORD_LIMIT).all(axis=1) & (np.abs(fy) <= MESH_COORD_LIMIT).all(axis=1)
-    keep, f, pc = keep[ok], f[ok], pc[ok]
-    fx, fy = fx[ok].astype(np.int64), fy[ok].astype(np.int64)
-    area2 = _edge(fx[:, 0], fy[:, 0], fx[:, 1], fy[:, 1], fx[:, 2], fy[:, 2])
-    drawn = area2 != 0
-    keep, f, pc, fx, fy, area2 = keep[drawn], f[drawn], pc[drawn], fx[drawn], fy[drawn], area2[drawn]
-    order = np.where((area2 < 0)[:, None], np.array([0, 2, 1]), np.array([0, 1, 2]))    # two-sided: b and c swap, with everything they carry
-    rows = np.arange(len(keep))[:, None]
-    return keep, f[rows, order], fx[rows, order], fy[rows, order], pc[rows, order]
+
+    def project(v):
+        pc = to_camera(v, cam)
+        return pc, (fl * pc[:, 0]) / pc[:, 2] + c, (fl * pc[:, 1]) / pc[:, 2] + c, pc[:, 2] >= near
+    return raster.drawn_faces(verts, faces, project)
 
 
 def _inverse_depth(wa, wb, wc, z):
@@ -97,32 +88,9 @@ def _inverse_depth(wa, wb, wc, z):
 
 def render_depth_idx_numpy(verts, faces, cam, S):
     """-> the index image (S, S) uint32: per pixel the covering face with the largest inv = q / double(area2), the lowest index among equal ones"""
-    img = np.full((S, S), DEFAULT_IDX, dtype=np.uint32)
     index, _, fx, fy, pc = _depth_faces(verts, faces, cam)
-    if not len(index):
-        return img
-    half = MESH_SUBPIXEL // 2                                                           # the pixels whose samples lie in the face's box, within the image
-    xlo = np.maximum(-((-(fx.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
-    xhi = np.minimum((fx.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
-    ylo = np.maximum(-((-(fy.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
-    yhi = np.minimum((fy.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
-    wd, ht = np.maximum(xhi - xlo + 1, 0), np.maximum(yhi - ylo + 1, 0)
-    n = wd * ht
-    if n.sum() == 0:
-        return img
-    face = np.repeat(np.arange(len(index)), n)                                          # every (face, pixel of its box) pair
-    local = np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n)
-    X, Y = xlo[face] + local % wd[face], ylo[face] + local // wd[face]
-    wa, wb, wc, covered = _mesh_weights(fx[face], fy[face], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
-    face, X, Y, wa, wb, wc = face[covered], X[covered], Y[covered], wa[covered], wb[covered], wc[covered]
-    q = _inverse_depth(wa, wb, wc, pc[face][:, :, 2])[3]
-    inv = q / (wa + wb + wc).astype(np.float64)
-    pixel = Y * S + X
-    order = np.lexsort((index[face], -inv, pixel))                                      # per pixel: the largest inv, then the lowest index
-    first = np.ones(order.size, dtype=bool)
-    first[1:] = pixel[order][1:] != pixel[order][:-1]
-    img.reshape(-1)[pixel[order][first]] = index[face][order][first].astype(np.uint32)
-    return img
+    return raster.raster_idx(index, fx, fy, S, lambda face, wa, wb, wc: _inverse_depth(wa, wb, wc, pc[face][:, :, 2])[3] /
+                             (wa + wb + wc).astype(np.float64), largest=True)[0]
 
 
 def _mix(ba, bb, bc, corners):
@@ -135,22 +103,16 @@ def depth_cloud_numpy(idx_img, verts, nocs, faces, cam, ambient=DEFAULT_AMBIENT,
     """the covered pixels of one index image in raster order -> (point (P, 3) fp32, nocs (P, 3) fp32, rgb (P, 3) uint8).  screen_linear: mix with the
     screen-space weights w_k / area2 instead of the perspective-correct ones -- NOT the definition; the tests show what it breaks"""
     index, f, fx, fy, pc = _depth_faces(verts, faces, cam)
-    Y, X = np.nonzero(idx_img != DEFAULT_IDX)                                           # raster order: Y, then X
+    Y, _, row, wa, wb, wc = raster.winner_weights(idx_img, index, fx, fy)
     if len(Y) == 0:
         return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
-    row = np.searchsorted(index, idx_img[Y, X].astype(np.int64))                        # the winner is a drawn face: recompute its weights
-    half = MESH_SUBPIXEL // 2
-    wa, wb, wc, covered = _mesh_weights(fx[row], fy[row], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
-    assert covered.all() and np.array_equal(index[row], idx_img[Y, X])
     qa, qb, qc, q = _inverse_depth(wa, wb, wc, pc[row][:, :, 2])
     if screen_linear:
         qa, qb, qc, q = wa.astype(np.float64), wb.astype(np.float64), wc.astype(np.float64), (wa + wb + wc).astype(np.float64)
     ba, bb, bc = qa / q, qb / q, qc / q
     point = _mix(ba, bb, bc, _host(verts).reshape(-1, 3)[f[row]])
     label = _mix(ba, bb, bc, _host(nocs).reshape(-1, 3)[f[row]])
-    A, B, C = pc[row][:, 0], pc[row][:, 1], pc[row][:, 2]
-    u, w = B - A, C - A
-    nx, ny, nz = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+    nx, ny, nz = raster.face_normals(pc[row])
     amb = np.float64(np.float32(ambient))
     with np.errstate(all="ignore"):
         p = to_camera(point, cam)
@@ -199,20 +161,9 @@ def render_point_clouds(meshes, cameras, img_size=256, base_color=DEFAULT_BASE_C
                 rows.append(depth_cloud_numpy(render_depth_idx_numpy(v, f, cam, S), v, n, f, cam, ambient, base_color))
                 sizes.append(len(rows[-1][0]))
         return _split([np.concatenate([r[k] for r in rows]) for k in range(3)], sizes, nv)
-    import torch
-
     from . import ops
 
-    def dev(a, dtype):
-        if not torch.is_tensor(a):
-            a = torch.from_numpy(_host(a, np.int32 if dtype == torch.int32 else np.float32)).to(device or "cuda")
-        return a.detach().to(dtype).reshape(-1, 3)
-
-    verts, nocs = [dev(m[0], torch.float32) for m in meshes], [dev(m[1], torch.float32) for m in meshes]
-    faces = [dev(m[2], torch.int32) for m in meshes]
-    vseg = np.concatenate([[0], np.cumsum([v.shape[0] for v in verts])]).astype(np.int64)
-    fseg = np.concatenate([[0], np.cumsum([f.shape[0] for f in faces])]).astype(np.int64)
-    verts, nocs, faces = torch.cat(verts).contiguous(), torch.cat(nocs).contiguous(), torch.cat(faces).contiguous()
+    verts, faces, nocs, vseg, fseg = ops.pack_meshes([(v, f, n) for v, n, f in meshes], (3,), device)
     mesh_of = np.repeat(np.arange(len(meshes), dtype=np.int32), nv)
     cams = cameras * len(meshes)
     idx = ops.depth_render_batch(verts, faces, vseg, fseg, mesh_of, cams, S)

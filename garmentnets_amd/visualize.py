@@ -19,7 +19,9 @@ training) are not provided.
 
 Mesh images (the evaluation's visualisation; DESIGN.md, "Mesh images") are described by `mesh_spec` (vertices, faces, a colour row per vertex, side,
 ambient) and rendered by `render_mesh_batch`, again on the device (ops.render_mesh_batch + ops.color_mesh_batch, one launch pair for all of them) or
-by the numpy restatement: a z-buffered, two-sided, shaded triangle rasteriser whose coverage is decided in integers.
+by the numpy restatement: a z-buffered, two-sided, shaded triangle rasteriser whose coverage is decided in integers.  The coverage rules, the drawn
+faces, the index image and the winner's weights live in raster.py, shared with point_cloud.py; this module brings its axis cameras, the depth, the
+colour mix and the shade.
 """
 import os
 import re
@@ -28,7 +30,9 @@ import zlib
 
 import numpy as np
 
-DEFAULT_IDX = np.uint32(0xFFFFFFFF)
+from . import raster
+from .raster import DEFAULT_IDX, MESH_COORD_LIMIT, MESH_SUBPIXEL, _host  # noqa: F401  (the constants are this module's public names too)
+
 # side -> per camera coordinate (axis of the point, sign, offset): the reference's get_extrinsic, each row one signed unit vector plus a translation
 SIDES = {"front": ((0, 1.0, 0.0), (2, -1.0, 1.0), (1, 1.0, 0.0)),
          "top": ((0, 1.0, 0.0), (1, -1.0, 1.0), (2, -1.0, 1.0)),
@@ -48,12 +52,6 @@ def viridis_lut():
             raise ValueError(f"csrc/viridis_lut.h: expected 768 entries, found {bits.shape[0]}")
         _LUT = np.concatenate([bits.view(np.float32).reshape(256, 3), np.ones((256, 1), np.float32)], axis=1)
     return _LUT
-
-
-def _host(a, dtype=np.float32):
-    if hasattr(a, "detach"):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a), dtype=dtype)
 
 
 # ------------------------------------------------------------------------------------------------ the numpy restatement
@@ -240,53 +238,16 @@ def render_idx_batch(points, sides, kernel_sizes, img_size=256, backend="device"
 
 # ------------------------------------------------------------------------------------------------ mesh images
 # DESIGN.md "Mesh images": a z-buffered, two-sided, shaded triangle rasteriser behind the same camera.  Coverage is decided in integers on 1/256-pixel
-# fixed-point coordinates, so the numpy restatement below and csrc/render.hip agree bit for bit.
-MESH_SUBPIXEL = 256
-MESH_COORD_LIMIT = 2 ** 24
+# fixed-point coordinates (raster.py), so the numpy restatement below and csrc/render.hip agree bit for bit.
 DEFAULT_AMBIENT = 0.35                          # a look, not a measurement: how dark a face seen edge-on gets
 
 
-def _edge(px, py, qx, qy, rx, ry):
-    """E(p, q, r) = (qx - px)(ry - py) - (qy - py)(rx - px) in int64"""
-    return (qx - px) * (ry - py) - (qy - py) * (rx - px)
-
-
-def _owns(px, py, qx, qy):
-    """the directed edge p -> q owns the samples on it: dy > 0 or (dy == 0 and dx < 0)"""
-    dx, dy = qx - px, qy - py
-    return (dy > 0) | ((dy == 0) & (dx < 0))
-
-
 def _mesh_faces(verts, faces, side, S):
-    """the drawn faces in positive orientation -> (index [D] int64, vertex indices [D, 3] after the swap, fx, fy [D, 3] int64, cam [D, 3, 3] fp64)"""
-    v = _host(verts).reshape(-1, 3)
-    f = _host(faces, np.int64).reshape(-1, 3)
-    ok = ((f >= 0) & (f < len(v))).all(axis=1)
-    keep = np.flatnonzero(ok)
-    f = f[keep]
-    with np.errstate(invalid="ignore", over="ignore"):
-        cam = to_camera(v, side)[f]                                                     # (D, 3 corners, 3 coordinates)
-        fin = np.isfinite(v).all(axis=1)[f].all(axis=1)
-        fx = np.rint(cam[:, :, 0] * np.float64(S - 1) * np.float64(MESH_SUBPIXEL))      # half to even
-        fy = np.rint(cam[:, :, 1] * np.float64(S - 1) * np.float64(MESH_SUBPIXEL))
-        fin &= (np.abs(fx) <= MESH_COORD_LIMIT).all(axis=1) & (np.abs(fy) <= MESH_COORD_LIMIT).all(axis=1)
-    keep, f, cam = keep[fin], f[fin], cam[fin]
-    fx, fy = fx[fin].astype(np.int64), fy[fin].astype(np.int64)
-    area2 = _edge(fx[:, 0], fy[:, 0], fx[:, 1], fy[:, 1], fx[:, 2], fy[:, 2])
-    drawn = area2 != 0
-    keep, f, cam, fx, fy, area2 = keep[drawn], f[drawn], cam[drawn], fx[drawn], fy[drawn], area2[drawn]
-    order = np.where((area2 < 0)[:, None], np.array([0, 2, 1]), np.array([0, 1, 2]))    # two-sided: b and c swap, with everything they carry
-    rows = np.arange(len(keep))[:, None]
-    return keep, f[rows, order], fx[rows, order], fy[rows, order], cam[rows, order]
-
-
-def _mesh_weights(fx, fy, px, py):
-    """-> (w_a, w_b, w_c, covered) of the samples (px, py) in the faces (fx, fy) [.., 3], all int64"""
-    ax, ay, bx, by, cx, cy = fx[..., 0], fy[..., 0], fx[..., 1], fy[..., 1], fx[..., 2], fy[..., 2]
-    wa, wb, wc = _edge(bx, by, cx, cy, px, py), _edge(cx, cy, ax, ay, px, py), _edge(ax, ay, bx, by, px, py)
-    covered = ((wa > 0) | ((wa == 0) & _owns(bx, by, cx, cy))) & ((wb > 0) | ((wb == 0) & _owns(cx, cy, ax, ay))) & \
-        ((wc > 0) | ((wc == 0) & _owns(ax, ay, bx, by)))
-    return wa, wb, wc, covered
+    """raster.drawn_faces behind the axis camera of `side`: screen = cam * (S - 1), nothing culled"""
+    def project(v):
+        cam = to_camera(v, side)
+        return cam, cam[:, 0] * np.float64(S - 1), cam[:, 1] * np.float64(S - 1), np.ones(len(v), dtype=bool)
+    return raster.drawn_faces(verts, faces, project)
 
 
 def _render_mesh_idx_numpy(verts, faces, side, S):
@@ -295,33 +256,12 @@ def _render_mesh_idx_numpy(verts, faces, side, S):
 
 def _render_mesh_numpy(verts, faces, side, S):
     """-> (index image (S, S) uint32, the winners' depths (S, S) fp64, +inf where nobody covers)"""
-    img = np.full((S, S), DEFAULT_IDX, dtype=np.uint32)
-    zimg = np.full((S, S), np.inf)
     index, _, fx, fy, cam = _mesh_faces(verts, faces, side, S)
-    # the pixels whose samples 256 X + 128 lie in the face's bounding box, within the image
-    half = MESH_SUBPIXEL // 2
-    xlo = np.maximum(-((-(fx.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
-    xhi = np.minimum((fx.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
-    ylo = np.maximum(-((-(fy.min(axis=1) - half)) // MESH_SUBPIXEL), 0)
-    yhi = np.minimum((fy.max(axis=1) - half) // MESH_SUBPIXEL, S - 1)
-    wd, ht = np.maximum(xhi - xlo + 1, 0), np.maximum(yhi - ylo + 1, 0)
-    n = wd * ht
-    if n.sum() == 0:
-        return img, zimg
-    face = np.repeat(np.arange(len(index)), n)                                          # every (face, pixel of its box) pair
-    local = np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n)
-    X, Y = xlo[face] + local % wd[face], ylo[face] + local // wd[face]
-    wa, wb, wc, covered = _mesh_weights(fx[face], fy[face], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
-    face, X, Y, wa, wb, wc = face[covered], X[covered], Y[covered], wa[covered], wb[covered], wc[covered]
-    z = cam[face][:, :, 2]
-    depth = ((wa.astype(np.float64) * z[:, 0] + wb.astype(np.float64) * z[:, 1]) + wc.astype(np.float64) * z[:, 2]) / (wa + wb + wc).astype(np.float64)
-    pixel = Y * S + X
-    order = np.lexsort((index[face], depth, pixel))                                     # per pixel: the smallest depth, then the lowest index
-    first = np.ones(order.size, dtype=bool)
-    first[1:] = pixel[order][1:] != pixel[order][:-1]
-    img.reshape(-1)[pixel[order][first]] = index[face][order][first].astype(np.uint32)
-    zimg.reshape(-1)[pixel[order][first]] = depth[order][first]
-    return img, zimg
+
+    def depth(face, wa, wb, wc):
+        z = cam[face][:, :, 2]
+        return ((wa.astype(np.float64) * z[:, 0] + wb.astype(np.float64) * z[:, 1]) + wc.astype(np.float64) * z[:, 2]) / (wa + wb + wc).astype(np.float64)
+    return raster.raster_idx(index, fx, fy, S, depth, largest=False)
 
 
 def _color_mesh_numpy(idx_img, verts, faces, colors, side, ambient, default_color):
@@ -329,20 +269,14 @@ def _color_mesh_numpy(idx_img, verts, faces, colors, side, ambient, default_colo
     img = np.empty((S, S, 4), dtype=np.float32)
     img[:, :] = np.asarray(default_color, dtype=np.float32)
     index, f, fx, fy, cam = _mesh_faces(verts, faces, side, S)
-    Y, X = np.nonzero(idx_img != DEFAULT_IDX)
+    Y, X, row, wa, wb, wc = raster.winner_weights(idx_img, index, fx, fy)
     if len(Y) == 0:
         return img
-    row = np.searchsorted(index, idx_img[Y, X].astype(np.int64))                        # the winner is a drawn face: recompute its weights
-    half = MESH_SUBPIXEL // 2
-    wa, wb, wc, covered = _mesh_weights(fx[row], fy[row], MESH_SUBPIXEL * X + half, MESH_SUBPIXEL * Y + half)
-    assert covered.all() and np.array_equal(index[row], idx_img[Y, X])
     area2 = (wa + wb + wc).astype(np.float64)
     beta = [(w.astype(np.float64) / area2).astype(np.float32) for w in (wa, wb, wc)]
     c = _host(colors).reshape(-1, 4)[f[row]]                                            # (P, 3 corners, 4)
     rgb = (beta[0][:, None] * c[:, 0, :3] + beta[1][:, None] * c[:, 1, :3]) + beta[2][:, None] * c[:, 2, :3]
-    A, B, C = cam[row][:, 0], cam[row][:, 1], cam[row][:, 2]
-    u, w = B - A, C - A
-    nx, ny, nz = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+    nx, ny, nz = raster.face_normals(cam[row])
     amb = np.float64(np.float32(ambient))
     with np.errstate(all="ignore"):
         length = np.sqrt((nx * nx + ny * ny) + nz * nz)
@@ -366,19 +300,8 @@ def mesh_spec(verts, faces, colors, side="front", ambient=DEFAULT_AMBIENT, defau
 
 
 def _mesh_device_args(specs, device):
-    import torch
-
-    def dev(a, dtype, width):
-        if not torch.is_tensor(a):
-            a = torch.from_numpy(_host(a, np.int32 if dtype == torch.int32 else np.float32)).to(device or "cuda")
-        return a.detach().to(dtype).reshape(-1, width)
-
-    verts = [dev(s["verts"], torch.float32, 3) for s in specs]
-    faces = [dev(s["faces"], torch.int32, 3) for s in specs]
-    colors = [dev(s["colors"], torch.float32, 4) for s in specs]
-    vseg = np.concatenate([[0], np.cumsum([v.shape[0] for v in verts])]).astype(np.int64)
-    fseg = np.concatenate([[0], np.cumsum([f.shape[0] for f in faces])]).astype(np.int64)
-    return torch.cat(verts).contiguous(), torch.cat(faces).contiguous(), torch.cat(colors).contiguous(), vseg, fseg
+    from . import ops
+    return ops.pack_meshes([(s["verts"], s["faces"], s["colors"]) for s in specs], (4,), device)
 
 
 def render_mesh_idx_batch(specs, img_size=256, backend="device", device=None):

@@ -97,12 +97,8 @@ def winding_field(meshes, shape, backend=None):
     differs (DESIGN.md, "Winding numbers")."""
     shape = tuple(int(n) for n in shape)
     if backend in (None, "hip"):
-        import torch
-
         from . import ops
-        dev = torch.device("cuda", torch.cuda.current_device())
-        on_dev = [(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev),
-                   torch.from_numpy(np.ascontiguousarray(np.asarray(f).reshape(-1, 3), dtype=np.int64)).to(dev)) for v, f in meshes]
+        on_dev = ops.meshes_f64(meshes)
         if not on_dev:
             return np.zeros((0,) + shape, dtype=np.float32)
         return ops.winding_field_batch(on_dev, shape).cpu().numpy()
