@@ -160,6 +160,7 @@ PROTOTYPES = {
     "gn_depth_render_batch": [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "gn_depth_cloud_offsets": [_vp, _i32, _i32, _vp, _vp, _vp],
     "gn_depth_cloud_write": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
+    "gn_cloth_simulate_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -230,6 +231,9 @@ class ResidentStore(ctypes.Structure):
     """GnResidentStore (host struct of the gn_resident_* calls: device pointers of the resident arrays, NULL for the ones a store does not hold)"""
     _fields_ = [(k, _vp) for k in RESIDENT_ARRAYS] + [("n", _i32), ("D", _i32), ("H", _i32), ("W", _i32)]
 
+
+CLOTH_MAX_LDS = 160 * 1024                      # CL_MAX_LDS
+CLOTH_MAX_BLOCK = 1024                          # CL_MAX_BLOCK
 
 RENDER_MAX_SIZE = 4096                          # GN_RENDER_MAX_SIZE
 RENDER_MAX_OVERLAYS = 3                         # GN_RENDER_MAX_OVERLAYS

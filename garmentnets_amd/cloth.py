@@ -1,0 +1,297 @@
+"""The hanging garment: a cloth of point masses and distance constraints under gravity, held at one vertex, stepped with small-step XPBD.  It makes
+mesh/cloth_verts of a dataset store from the canonical mesh (mesh/cloth_nocs_verts, mesh/cloth_faces_tri): the one array every derived group starts from.
+
+Definition (normative, this package's own; csrc/cloth.hip follows it operation for operation, DESIGN.md "Hanging garments").  All fp64, every operation
+rounded on its own (numpy never contracts to fma; the kernel uses _rn intrinsics), so the device gives the bits of simulate_reference below.
+
+  rest shape   X = (cloth_nocs_verts - 0.5) * rest_scale, rest_scale the longest edge of summary/cloth_canonical_aabb_union
+  frame        the gripper frame of the dataset: grip vertex g at the origin, z up, gravity along -z.  Start pose: x = X - X[g], v = 0.  Rest lengths
+               are measured in this pose with the expression of `len` below, so a garment at rest has len == l0 to the bit and, without gravity, stays
+               where it is
+  particles    m_i = density * (sum of the rest areas of the faces at i) / 3, w_i = 1 / m_i; w_g = 0; a vertex of no face (m_i = 0) has w_i = 0
+  constraints  distance constraints (i, j, l0, alpha) in ONE list: stretch -- one per unique mesh edge, i < j, sorted lexicographically,
+               l0 = |x_i - x_j| in the start pose, alpha_stretch -- then bend -- for every edge of exactly two faces the two opposite vertices
+               (k, l), k < l, sorted lexicographically, l0 alike, alpha_bend.  An edge of one face, or of more than two, gets no bend constraint
+  colouring    greedy first fit in list order: a constraint takes the smallest colour that no earlier constraint sharing a vertex with it has; the list
+               is then grouped by colour with a stable sort.  The colouring fixes the result, so it is part of the definition
+  constants    h, inv_h = 1 / h, hg = h * gravity (3), damp = max(0, 1 - h * damping), alpha_t = alpha / (h * h): computed ONCE on the host (step_constants)
+               and read by both sides
+  substep      for every vertex with w > 0:   v = (v + hg) * damp;  x_prev = x;  p = x + h * v
+               for each colour, ascending, for each constraint of it:
+                   d = p_i - p_j;  len = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z);  s = (w_i + w_j) + alpha_t
+                   len == 0 or s == 0: nothing.  Otherwise dl = -(len - l0) / s;  n = d / len;  p_i += (w_i * dl) * n;  p_j -= (w_j * dl) * n
+               for every vertex with w > 0:   v = (p - x_prev) * inv_h;  x = p
+               (one projection sweep per substep and the multipliers reset every substep, so none is stored; no two constraints of a colour share a
+               vertex, so the order inside a colour cannot matter and a colour is one vectorised numpy statement)
+
+NOT modelled: self-collision, collision with anything else, aerodynamic forces, strain limiting, dihedral bending, a random start orientation, moving
+grippers.  The result is a hanging garment that may pass through itself.
+"""
+import dataclasses
+import hashlib
+
+import numpy as np
+
+# "a look", chosen from runs of simulate_reference (DESIGN.md "Hanging garments"); no test depends on them
+DEFAULT_GRAVITY = 9.81                 # m / s^2 along -z
+DEFAULT_H = 1.0 / 2400.0               # seconds per substep
+DEFAULT_DURATION = 3.0                 # seconds simulated
+DEFAULT_DAMPING = 4.0                  # 1 / s: v *= 1 - h * damping every substep
+DEFAULT_ALPHA_STRETCH = 0.0            # m / N: as stiff as the substep count makes it
+DEFAULT_ALPHA_BEND = 0.1               # m / N
+DEFAULT_DENSITY = 0.2                  # kg / m^2
+
+
+@dataclasses.dataclass(frozen=True)
+class ClothParams:
+    gravity: float = DEFAULT_GRAVITY
+    h: float = DEFAULT_H
+    damping: float = DEFAULT_DAMPING
+    alpha_stretch: float = DEFAULT_ALPHA_STRETCH
+    alpha_bend: float = DEFAULT_ALPHA_BEND
+    density: float = DEFAULT_DENSITY
+
+    def __post_init__(self):
+        vals = dataclasses.asdict(self)
+        if not all(np.isfinite(v) for v in vals.values()):
+            raise ValueError(f"cloth parameters must be finite, got {vals}")
+        if not self.h > 0 or not self.density > 0 or self.damping < 0 or self.alpha_stretch < 0 or self.alpha_bend < 0:
+            raise ValueError(f"cloth parameters: h and density must be positive, damping and the compliances not negative, got {vals}")
+
+
+def step_constants(params):
+    """the per-step numbers both sides read -> dict of python floats (fp64): h, inv_h, hg (3), damp, alpha_t_stretch, alpha_t_bend"""
+    h = np.float64(params.h)
+    g = np.array([0.0, 0.0, -float(params.gravity)], dtype=np.float64)
+    return {"h": float(h), "inv_h": float(np.float64(1.0) / h), "hg": [float(c) for c in h * g],
+            "damp": float(max(np.float64(0.0), np.float64(1.0) - h * np.float64(params.damping))),
+            "alpha_t_stretch": float(np.float64(params.alpha_stretch) / (h * h)), "alpha_t_bend": float(np.float64(params.alpha_bend) / (h * h))}
+
+
+def substeps_of(duration, h):
+    return int(round(float(duration) / float(h)))
+
+
+# ------------------------------------------------------------------------------------------------ topology
+def _faces(faces):
+    faces = np.asarray(faces)
+    if faces.size == 0:
+        return np.zeros((0, 3), dtype=np.int64)
+    if faces.dtype.kind not in "iu":
+        raise TypeError(f"faces: expected an integer array, got {faces.dtype}")
+    if faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected an (F, 3) array, got {faces.shape}")
+    return faces.astype(np.int64)
+
+
+def constraint_pairs(faces):
+    """-> (stretch (Ns, 2), bend (Nb, 2)) int64 in the list order of the definition.  Reads no vertex, so an index outside the mesh passes through."""
+    faces = _faces(faces)
+    corners = np.stack([faces[:, [0, 1, 2]], faces[:, [1, 2, 0]], faces[:, [2, 0, 1]]], axis=1).reshape(-1, 3)     # (edge a, edge b, opposite)
+    corners = corners[corners[:, 0] != corners[:, 1]]                                     # a face that names a vertex twice has no edge there
+    if len(corners) == 0:
+        return np.zeros((0, 2), np.int64), np.zeros((0, 2), np.int64)
+    edges = np.sort(corners[:, :2], axis=1)
+    stretch, inverse, count = np.unique(edges, axis=0, return_inverse=True, return_counts=True)       # rows sorted lexicographically
+    inverse = inverse.reshape(-1)
+    order = np.argsort(inverse, kind="stable")
+    first = np.concatenate([[0], np.cumsum(count)[:-1]])[count == 2]
+    opp = np.sort(np.stack([corners[order[first], 2], corners[order[first + 1], 2]], axis=1), axis=1)
+    opp = opp[opp[:, 0] != opp[:, 1]]                                                     # the same face twice: no pair
+    bend = opp[np.lexsort((opp[:, 1], opp[:, 0]))] if len(opp) else np.zeros((0, 2), np.int64)
+    return stretch.astype(np.int64), bend.astype(np.int64)
+
+
+def first_fit_colours(pairs):
+    """greedy first fit in list order -> (C,) int64"""
+    used = {}
+    out = np.zeros(len(pairs), dtype=np.int64)
+    for c, (i, j) in enumerate(pairs.tolist()):
+        taken = used.get(i, 0) | used.get(j, 0)
+        free = ~taken & (taken + 1)                    # the lowest clear bit
+        out[c] = free.bit_length() - 1
+        used[i] = used.get(i, 0) | free
+        used[j] = used.get(j, 0) | free
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class Topology:
+    pairs: np.ndarray            # (C, 2) int64, grouped by colour
+    is_bend: np.ndarray          # (C,) bool
+    colour_off: np.ndarray       # (K + 1,) int64: colour k owns pairs[colour_off[k] : colour_off[k + 1]]
+    n_stretch: int
+    n_bend: int
+
+
+_TOPOLOGY_CACHE = {}
+_TOPOLOGY_CACHE_MAX = 64
+
+
+def topology(faces):
+    """the coloured constraint list of a faces array, built once per array (garments of one template share it)"""
+    faces = np.ascontiguousarray(_faces(faces))
+    key = (faces.shape[0], hashlib.sha1(faces.tobytes()).hexdigest())
+    hit = _TOPOLOGY_CACHE.get(key)
+    if hit is not None:
+        return hit
+    stretch, bend = constraint_pairs(faces)
+    pairs = np.concatenate([stretch, bend])
+    is_bend = np.arange(len(pairs)) >= len(stretch)
+    colour = first_fit_colours(pairs)
+    order = np.argsort(colour, kind="stable")
+    k = int(colour.max()) + 1 if len(colour) else 0
+    off = np.concatenate([[0], np.cumsum(np.bincount(colour, minlength=k))]).astype(np.int64)
+    topo = Topology(pairs[order], is_bend[order], off, len(stretch), len(bend))
+    for a in (topo.pairs, topo.is_bend, topo.colour_off):
+        a.setflags(write=False)
+    if len(_TOPOLOGY_CACHE) >= _TOPOLOGY_CACHE_MAX:
+        _TOPOLOGY_CACHE.pop(next(iter(_TOPOLOGY_CACHE)))
+    _TOPOLOGY_CACHE[key] = topo
+    return topo
+
+
+# ------------------------------------------------------------------------------------------------ a garment
+def _norm3(d):
+    return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def rest_scale_of(canonical_aabb):
+    """the longest edge of summary/cloth_canonical_aabb_union"""
+    box = np.asarray(canonical_aabb, dtype=np.float64)
+    return float((box[1] - box[0]).max())
+
+
+def rest_shape(nocs_verts, rest_scale):
+    return (np.asarray(nocs_verts, dtype=np.float64) - 0.5) * np.float64(rest_scale)
+
+
+@dataclasses.dataclass
+class Garment:
+    """what one garment's simulation reads: everything fp64 / int64 numpy"""
+    x0: np.ndarray               # (V, 3) start pose: the rest shape with the grip vertex at the origin
+    w: np.ndarray                # (V,) inverse masses
+    pairs: np.ndarray            # (C, 2), grouped by colour
+    is_bend: np.ndarray          # (C,) bool
+    l0: np.ndarray               # (C,)
+    alpha_t: np.ndarray          # (C,)
+    colour_off: np.ndarray       # (K + 1,)
+    consts: dict                 # step_constants
+    grip: int
+    n_massless: int              # vertices of no face (the grip vertex is not counted)
+    n_stretch: int
+    n_bend: int
+    bad_index: bool              # a face names a vertex outside [0, V): only a garment built with check=False carries one
+
+
+def garment(X, faces, grip, params, check=True):
+    """the Garment of a rest shape X (V, 3), its faces and the grip vertex.  check=False lets a face index outside [0, V) through (its rest lengths and
+    areas are then read at a clipped index and mean nothing): the device entry flags such an index itself and never dereferences it."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError(f"verts: expected a (V, 3) array, got {X.shape}")
+    if not np.isfinite(X).all():
+        raise ValueError("cloth: a rest-shape vertex is not finite")
+    V = len(X)
+    grip = int(grip)
+    if not 0 <= grip < V:
+        raise ValueError(f"cloth: grip vertex {grip} outside [0, {V})")
+    faces = _faces(faces)
+    bad = bool(len(faces) and (faces.min() < 0 or faces.max() >= V))
+    if bad and check:
+        raise IndexError("cloth: a face index is out of bounds for its mesh's vertices")
+    topo = topology(faces)
+    safe = np.clip(faces, 0, V - 1)
+    a, b, c = X[safe[:, 0]], X[safe[:, 1]], X[safe[:, 2]]
+    area = 0.5 * _norm3(np.cross(b - a, c - a))
+    mass = np.zeros(V, dtype=np.float64)
+    for k in range(3):
+        np.add.at(mass, safe[:, k], area)              # unbuffered: face order, one addition after the other
+    mass = np.float64(params.density) * mass / 3.0
+    w = np.zeros(V, dtype=np.float64)
+    np.divide(1.0, mass, out=w, where=mass > 0)
+    n_massless = int((mass == 0).sum()) - int(mass[grip] == 0)
+    w[grip] = 0.0
+    if not np.isfinite(w).all():
+        raise ValueError("cloth: an inverse mass is not finite (a face of vanishing area)")
+    consts = step_constants(params)
+    x0 = X - X[grip]
+    ij = np.clip(topo.pairs, 0, V - 1)
+    l0 = _norm3(x0[ij[:, 0]] - x0[ij[:, 1]]) if len(ij) else np.zeros(0)      # measured in the start pose, as the sweep measures len
+    alpha_t = np.where(topo.is_bend, consts["alpha_t_bend"], consts["alpha_t_stretch"]).astype(np.float64)
+    return Garment(x0, w, topo.pairs, topo.is_bend, l0, alpha_t, topo.colour_off, consts, grip, n_massless, topo.n_stretch, topo.n_bend, bad)
+
+
+def garment_from_nocs(nocs_verts, faces, grip, rest_scale, params, check=True):
+    return garment(rest_shape(nocs_verts, rest_scale), faces, grip, params, check=check)
+
+
+def state_arrays(g, x, v, who="cloth"):
+    """(x, v) float64 (V, 3) copies of a state (None: the start pose / rest), refused when not finite"""
+    x = np.array(g.x0 if x is None else x, dtype=np.float64)
+    v = np.zeros_like(g.x0) if v is None else np.array(v, dtype=np.float64)
+    if x.shape != g.x0.shape or v.shape != g.x0.shape:
+        raise ValueError(f"{who}: x and v must be {g.x0.shape}, got {x.shape} and {v.shape}")
+    if not (np.isfinite(x).all() and np.isfinite(v).all()):
+        raise ValueError(f"{who}: a position or velocity is not finite")
+    return x, v
+
+
+# ------------------------------------------------------------------------------------------------ the restatement
+def project_colour(p, w, i, j, l0, alpha_t):
+    """one colour of the sweep, in place on p: the constraints (i, j, l0, alpha_t) share no vertex"""
+    pi, pj = p[i], p[j]
+    d = pi - pj
+    length = _norm3(d)
+    wi, wj = w[i], w[j]
+    s = (wi + wj) + alpha_t
+    act = (length != 0) & (s != 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dl = -(length - l0) / s
+        n = d / length[:, None]
+        new_i = pi + (wi * dl)[:, None] * n
+        new_j = pj - (wj * dl)[:, None] * n
+    p[i[act]] = new_i[act]
+    p[j[act]] = new_j[act]
+
+
+def substep(g, x, v):
+    """one substep of the definition, in place on x and v"""
+    c = g.consts
+    h, inv_h, damp, hg = np.float64(c["h"]), np.float64(c["inv_h"]), np.float64(c["damp"]), np.array(c["hg"], dtype=np.float64)
+    live = g.w > 0
+    v[live] = (v[live] + hg) * damp
+    x_prev = x.copy()
+    p = x.copy()
+    p[live] = x[live] + h * v[live]
+    off = g.colour_off
+    for k in range(len(off) - 1):
+        sl = slice(off[k], off[k + 1])
+        project_colour(p, g.w, g.pairs[sl, 0], g.pairs[sl, 1], g.l0[sl], g.alpha_t[sl])
+    v[live] = (p[live] - x_prev[live]) * inv_h
+    x[live] = p[live]
+
+
+def simulate_reference(g, substeps, x=None, v=None):
+    """`substeps` substeps from (x, v) (None: the start pose at rest) -> (x, v) float64 (V, 3), new arrays"""
+    if g.bad_index:
+        raise IndexError("cloth: a face index is out of bounds for its mesh's vertices")
+    x, v = state_arrays(g, x, v, "simulate_reference")
+    for _ in range(int(substeps)):
+        substep(g, x, v)
+    return x, v
+
+
+# ------------------------------------------------------------------------------------------------ diagnostics
+def diagnostics(g, x, v):
+    """-> {"kinetic_energy": sum m |v|^2 / 2 over the moving vertices, "max_stretch_strain": max |len / l0 - 1| over the stretch constraints,
+    "massless_vertices": count}"""
+    x, v = np.asarray(x, np.float64), np.asarray(v, np.float64)
+    live = g.w > 0
+    ke = float(0.5 * ((v[live] ** 2).sum(axis=1) / g.w[live]).sum())
+    stretch = ~g.is_bend & (g.l0 > 0)
+    strain = 0.0
+    if stretch.any():
+        i, j = g.pairs[stretch, 0], g.pairs[stretch, 1]
+        strain = float(np.abs(_norm3(x[i] - x[j]) / g.l0[stretch] - 1.0).max())
+    return {"kinetic_energy": ke, "max_stretch_strain": strain, "massless_vertices": int(g.n_massless)}

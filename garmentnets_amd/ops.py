@@ -2315,6 +2315,89 @@ def depth_cloud(idx_img, verts, nocs, faces, vseg, fseg, mesh_of, cameras, ambie
     return point, label, rgb, sizes
 
 
+# ------------------------------------------------------------------------------------------------ the hanging garment (cloth.py)
+CLOTH_SUBSTEPS_PER_LAUNCH = 256        # a launch of the solver stays in the milliseconds on a shared machine
+
+
+def cloth_device_tables(garments, states, dev):
+    """the device arguments of gn_cloth_simulate_batch for `garments` and their (x, v) `states` (numpy) -> dict: x, v (fresh copies: the entry
+    writes them), w, pairs, l0, alpha_t, colour_off, csr tensors, consts (ctypes double[6]), v_off (numpy), totals"""
+    v_off = np.concatenate([[0], np.cumsum([len(g.w) for g in garments])])
+    c_off = np.concatenate([[0], np.cumsum([len(g.l0) for g in garments])])
+    k_off = np.concatenate([[0], np.cumsum([len(g.colour_off) for g in garments])])
+    if v_off[-1] >= 2 ** 31 - 1 or c_off[-1] >= 2 ** 31 - 1:
+        raise ValueError("cloth_simulate_batch: more than 2^31 vertices or constraints")
+
+    def up(parts, dtype, width=None):
+        a = np.concatenate([np.asarray(p).reshape((-1,) if width is None else (-1, width)) for p in parts]).astype(dtype)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = {"x": up([s[0] for s in states], np.float64, 3), "v": up([s[1] for s in states], np.float64, 3), "w": up([g.w for g in garments], np.float64),
+         # an index that does not fit int32 is out of range: keep it so
+         "pairs": up([np.clip(g.pairs, -1, 2 ** 31 - 1) for g in garments], np.int32, 2),
+         "l0": up([g.l0 for g in garments], np.float64), "alpha_t": up([g.alpha_t for g in garments], np.float64),
+         "colour_off": up([g.colour_off for g in garments], np.int64),
+         "csr": torch.from_numpy(np.stack([v_off, c_off, k_off], axis=1).astype(np.int64)).to(dev), "v_off": v_off,
+         "total_verts": int(v_off[-1]), "total_constraints": int(c_off[-1])}
+    if not (torch.isfinite(t["w"]).all() and torch.isfinite(t["l0"]).all() and torch.isfinite(t["alpha_t"]).all()):
+        raise ValueError("cloth_simulate_batch: an inverse mass, rest length or compliance is not finite")
+    c = garments[0].consts
+    t["consts"] = (ctypes.c_double * 6)(c["h"], c["inv_h"], c["hg"][0], c["hg"][1], c["hg"][2], c["damp"])
+    return t
+
+
+def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_budget=None, max_substeps_per_launch=CLOTH_SUBSTEPS_PER_LAUNCH,
+                         block=None, device=None):
+    """`substeps` substeps of cloth.py's definition on every cloth.Garment of `garments`, all of them in the same launches (gn_cloth_simulate_batch: one
+    workgroup per garment) -> [(x, v)] float64 (V, 3) tensors, on the device (backend "hip") or on the host (backend "numpy": cloth.simulate_reference).
+    states: None or one (x, v) / None per garment (None: the start pose at rest); the inputs are not written.  The device gives the restatement's bits
+    whatever the batch, `block` (threads per workgroup, a multiple of 64 up to 1024), lds_budget (bytes: a garment whose positions, 24 bytes per vertex,
+    fit it keeps them in LDS, any other in global memory; default all 160 KiB) and max_substeps_per_launch (a longer run is several launches).  The
+    garments must share their step constants.  A face index outside [0, V) raises IndexError (after the launch, nothing is read or written through
+    it); a state that is not finite, a bad budget / block / substep count raise ValueError before it."""
+    from . import cloth
+    if backend not in ("hip", "numpy"):
+        raise ValueError(f"backend {backend!r}: expected 'hip' or 'numpy'")
+    substeps = int(substeps)
+    if substeps < 0 or int(max_substeps_per_launch) < 1:
+        raise ValueError(f"cloth_simulate_batch: substeps={substeps}, max_substeps_per_launch={max_substeps_per_launch}")
+    states = [None] * len(garments) if states is None else list(states)
+    if len(states) != len(garments):
+        raise ValueError("cloth_simulate_batch: one state per garment")
+    states = [cloth.state_arrays(g, *(s if s is not None else (None, None)), who="cloth_simulate_batch") for g, s in zip(garments, states)]
+    if not garments:
+        return []
+    if any(g.consts != garments[0].consts for g in garments):
+        raise ValueError("cloth_simulate_batch: the garments of one call must share their step constants (h, gravity, damping, compliances)")
+    if backend == "numpy":
+        return [tuple(torch.from_numpy(a) for a in cloth.simulate_reference(g, substeps, x, v)) for g, (x, v) in zip(garments, states)]
+    budget = _lib.CLOTH_MAX_LDS if lds_budget is None else int(lds_budget)
+    if not 0 <= budget <= _lib.CLOTH_MAX_LDS:
+        raise ValueError(f"cloth_simulate_batch: lds_budget={budget} outside [0, {_lib.CLOTH_MAX_LDS}]")
+    nv = [len(g.w) for g in garments]
+    if block is None:
+        block = 256 if max(len(g.l0) for g in garments) <= 4096 else _lib.CLOTH_MAX_BLOCK
+    block = int(block)
+    if block % 64 or not 64 <= block <= _lib.CLOTH_MAX_BLOCK:
+        raise ValueError(f"cloth_simulate_batch: block={block}: a multiple of 64 in [64, {_lib.CLOTH_MAX_BLOCK}]")
+    if len(garments) > 65535:
+        raise ValueError(f"cloth_simulate_batch: at most 65535 garments per call, got {len(garments)}")
+    lds = max([24 * n for n in nv if 24 * n <= budget], default=0)            # the LDS the launch asks for: its largest garment that fits the budget
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    t = cloth_device_tables(garments, states, dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _lib.call("gn_cloth_simulate_batch", _p(t["x"]), _p(t["v"]), _p(t["w"]), _p(t["pairs"]), _p(t["l0"]), _p(t["alpha_t"]), _p(t["csr"]),
+              _p(t["colour_off"]), len(garments), t["total_verts"], t["total_constraints"], substeps, int(max_substeps_per_launch),
+              ctypes.cast(t["consts"], ctypes.c_void_p), lds, block, _p(bad), _stream())
+    _raise_bad_face(bad.item(), "cloth_simulate")
+    return [(t["x"][a:b], t["v"][a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
+
+
+def cloth_storage_path(garment, lds_budget=None):
+    """"lds" or "global": where cloth_simulate_batch keeps the working positions of `garment` under `lds_budget`"""
+    budget = _lib.CLOTH_MAX_LDS if lds_budget is None else int(lds_budget)
+    return "lds" if 24 * len(garment.w) <= budget else "global"
+
+
 # ------------------------------------------------------------------------------------------------ gradient pack (data-parallel training)
 def grad_pack_table(rows, device):
     """the device table of gn_grad_pack.  rows: [(source pointer or None, dst_off, numel)] in the order of their workgroups; dst_off a multiple of 4

@@ -1,0 +1,134 @@
+"""python -m garmentnets_amd.simulate: hang the garments of a dataset store from their grip vertices (cloth.py) and write mesh/cloth_verts.
+
+Reads, per sample, mesh/{cloth_nocs_verts, cloth_faces_tri}, the attribute grip_vertex_idx (drawn with RandomState(seed + dataset index) and written
+back where it is absent) and summary/cloth_canonical_aabb_union (whose longest edge is the rest scale; --rest_scale where the store has none), and
+writes through io.zarr_store, with default_compressor():
+
+  samples/<key>/mesh/cloth_verts       float32 (V, 3): the garment after --duration seconds of cloth.py's solver in the gripper frame (grip vertex at the
+                                       origin, z up); the mesh group's attributes get {"cloth_simulation": the parameters, the substep count and the
+                                       diagnostics of the final state (kinetic energy, largest stretch strain, massless vertices)}
+  summary/cloth_aabb_union             float32 (2, 3): the union box of every cloth_verts of the store, when the store has none or with --update_summary
+
+An existing cloth_verts is kept unless --overwrite is given.  --backend hip runs --batch_size garments per call of ops.cloth_simulate_batch (one workgroup
+each); --backend numpy runs the restatement, which gives the same bits.  After this command `prepare` can build every other group: simulate -> prepare ->
+train -> predict -> evaluate runs from canonical meshes alone.
+"""
+import argparse
+import dataclasses
+import json
+import time
+
+import numpy as np
+
+from . import cloth
+from .io import zarr_store
+
+MESH_INPUTS = ("cloth_nocs_verts", "cloth_faces_tri")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="hang the garments of a garmentnets dataset store: mesh/cloth_verts from the canonical meshes")
+    ap.add_argument("--zarr_in", required=True, help="garmentnets dataset store (Zarr v2); completed in place")
+    ap.add_argument("--overwrite", action="store_true", help="simulate samples that already hold mesh/cloth_verts again")
+    ap.add_argument("--update_summary", action="store_true", help="rewrite summary/cloth_aabb_union from the store's cloth_verts")
+    ap.add_argument("--batch_size", type=int, default=16, help="garments per call (one workgroup each)")
+    ap.add_argument("--backend", default="hip", choices=("hip", "numpy"))
+    ap.add_argument("--seed", type=int, default=0, help="a missing grip_vertex_idx is drawn with RandomState(seed + dataset index)")
+    ap.add_argument("--rest_scale", type=float, default=None, help="rest shape = (nocs - 0.5) * rest_scale, for a store without "
+                                                                    "summary/cloth_canonical_aabb_union")
+    ap.add_argument("--gravity", type=float, default=cloth.DEFAULT_GRAVITY, help="m / s^2 along -z")
+    ap.add_argument("--h", type=float, default=cloth.DEFAULT_H, help="seconds per substep")
+    ap.add_argument("--duration", type=float, default=cloth.DEFAULT_DURATION, help="seconds simulated")
+    ap.add_argument("--damping", type=float, default=cloth.DEFAULT_DAMPING, help="1 / s")
+    ap.add_argument("--alpha_stretch", type=float, default=cloth.DEFAULT_ALPHA_STRETCH, help="stretch compliance, m / N")
+    ap.add_argument("--alpha_bend", type=float, default=cloth.DEFAULT_ALPHA_BEND, help="bend compliance, m / N")
+    ap.add_argument("--density", type=float, default=cloth.DEFAULT_DENSITY, help="kg / m^2")
+    return ap
+
+
+def grip_index(sample_group, dataset_idx, num_verts, seed):
+    """the sample's grip_vertex_idx; where absent, drawn with RandomState(seed + dataset index) and written back"""
+    attrs = sample_group.attrs
+    if "grip_vertex_idx" in attrs:
+        return int(attrs["grip_vertex_idx"])
+    grip = int(np.random.RandomState(int(seed) + int(dataset_idx)).randint(0, num_verts))
+    sample_group.put_attrs({"grip_vertex_idx": grip})
+    return grip
+
+
+def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_scale=None, batch_size=16, overwrite=False, update_summary=False,
+                   backend="hip", seed=0, log=print):
+    """-> summary dict {"samples", "written", "substeps", "seconds"}; log gets one dict per sample"""
+    params = cloth.ClothParams() if params is None else params
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size} < 1")
+    substeps = cloth.substeps_of(duration, params.h)
+    if substeps < 0:
+        raise ValueError(f"duration {duration} < 0")
+    root = zarr_store.open_group(zarr_in, create=False)
+    if "samples" not in root:
+        raise ValueError(f"{zarr_in}: no samples group")
+    if "summary/cloth_canonical_aabb_union" in root:
+        scale = cloth.rest_scale_of(root["summary"]["cloth_canonical_aabb_union"][:])
+    elif rest_scale is not None:
+        scale = float(rest_scale)
+    else:
+        raise ValueError(f"{zarr_in}: no summary/cloth_canonical_aabb_union to take the rest scale from: give --rest_scale")
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"rest scale {scale}: expected a positive number")
+    samples = root["samples"]
+    keys = sorted(samples.keys())
+    for k in keys:
+        missing = [a for a in MESH_INPUTS if f"mesh/{a}" not in samples[k]]
+        if missing:
+            raise ValueError(f"{zarr_in}: sample {k} has no mesh/{missing[0]}: the garment is simulated from its canonical mesh")
+    todo = [(i, k) for i, k in enumerate(keys) if overwrite or "mesh/cloth_verts" not in samples[k]]
+    comp = zarr_store.default_compressor()
+    record = dict(dataclasses.asdict(params), duration=float(duration), substeps=substeps, rest_scale=scale)
+    t_all = time.perf_counter()
+    for s in range(0, len(todo), batch_size):
+        chunk = todo[s:s + batch_size]
+        t0 = time.perf_counter()
+        garments = []
+        for i, k in chunk:
+            mesh = samples[k]["mesh"]
+            nocs = mesh["cloth_nocs_verts"][:]
+            garments.append(cloth.garment_from_nocs(nocs, mesh["cloth_faces_tri"][:], grip_index(samples[k], i, len(nocs), seed), scale, params))
+        if backend == "numpy":
+            states = [cloth.simulate_reference(g, substeps) for g in garments]
+        else:
+            from . import ops
+            states = [(x.cpu().numpy(), v.cpu().numpy()) for x, v in ops.cloth_simulate_batch(garments, substeps)]
+        dt = time.perf_counter() - t0
+        for (i, k), g, (x, v) in zip(chunk, garments, states):
+            diag = cloth.diagnostics(g, x, v)
+            mesh = samples[k].require_group("mesh")
+            mesh.array("cloth_verts", x.astype(np.float32), compressor=comp)
+            mesh.put_attrs({"cloth_simulation": dict(record, grip_vertex_idx=g.grip, **diag)})
+            log(dict({"sample": k, "seconds": dt / len(chunk)}, **diag))
+    wrote_summary = False
+    if keys and (update_summary or "summary/cloth_aabb_union" not in root) and all("mesh/cloth_verts" in samples[k] for k in keys):
+        lo = np.min([samples[k]["mesh"]["cloth_verts"][:].min(axis=0) for k in keys], axis=0)
+        hi = np.max([samples[k]["mesh"]["cloth_verts"][:].max(axis=0) for k in keys], axis=0)
+        root.require_group("summary").array("cloth_aabb_union", np.stack([lo, hi]).astype(np.float32))
+        wrote_summary = True
+    summary = {"samples": len(keys), "written": len(todo), "substeps": substeps, "summary_written": wrote_summary,
+               "seconds": time.perf_counter() - t_all}
+    log(summary)
+    return summary
+
+
+def main(argv=None):
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    try:
+        params = cloth.ClothParams(gravity=a.gravity, h=a.h, damping=a.damping, alpha_stretch=a.alpha_stretch, alpha_bend=a.alpha_bend,
+                                   density=a.density)
+        return simulate_store(a.zarr_in, params, a.duration, a.rest_scale, a.batch_size, a.overwrite, a.update_summary, a.backend, a.seed,
+                              log=lambda row: print(json.dumps(row)))
+    except ValueError as e:
+        ap.error(str(e))
+
+
+if __name__ == "__main__":
+    main()

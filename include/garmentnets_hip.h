@@ -15,7 +15,7 @@
  *   - dense float tensors are fp32, row-major with an explicit leading dimension (ld*) in elements.  Exception: the two
  *     evaluation distances (gn_nearest_neighbor_f64_batch, gn_point_mesh_sqdist_batch) take and return fp64 tensors, and the two
  *     winding-number calls (gn_winding_number_batch, gn_winding_field_batch) take fp64 vertices; gn_distance_field_batch takes fp64
- *     vertices and returns fp64 squared distances.
+ *     vertices and returns fp64 squared distances; gn_cloth_simulate_batch is fp64 throughout.
  *   - volumes are CHANNEL-LAST: [B][D][H][W][C]  (the reference's NCDHW is a host-side view of this).
  *   - indices: point / vertex indices int32 on device (int64 only where the reference API exposes them).
  */
@@ -1057,6 +1057,21 @@ int gn_depth_cloud_offsets(const uint32_t *idx_img, int I, int S, int64_t *row_o
 int gn_depth_cloud_write(const uint32_t *idx_img, const float *verts, const float *nocs, const int32_t *faces, const int64_t *vseg_host,
                          const int64_t *fseg_host, int M, const int32_t *mesh_host, const GnDepthImage *tab_host, const GnDepthImage *tab,
                          const int64_t *row_off, int I, int S, int64_t N, float *point, float *nocs_out, uint8_t *rgb, void *stream);
+
+/* The hanging garment (garmentnets_amd/cloth.py has the definition, DESIGN.md "Hanging garments"): `substeps` substeps of small-step XPBD on each of B
+ * ragged garments, fp64, bit for bit cloth.simulate_reference.  ONE workgroup of `block` threads (a multiple of 64 in [64, 1024]) owns one garment, so the
+ * result is a pure function of (garment, constants, substeps): independent of the batch, of `block`, of lds_bytes and of max_substeps_per_launch.
+ * x, v [*][3] fp64, in and out (carried in global memory between the launches of one call: at most max_substeps_per_launch substeps per launch);
+ * w [*] inverse masses (0: held or massless, never moved); pairs [*][2] int32 vertex indices relative to the garment's first vertex, grouped by colour
+ * (no two constraints of a colour share a vertex); l0, alpha_t [*] per constraint.  csr [B + 1][3] int64 on the device = {v_off, c_off, k_off}, closed by
+ * the totals: garment b owns the vertex rows v_off[b] .. v_off[b+1] - 1, the constraint rows c_off[b] .. c_off[b+1] - 1 and the entries
+ * k_off[b] .. k_off[b+1] - 1 of colour_off (K_b + 1 of them for K_b colours, relative to c_off[b]).  consts_host [6] = {h, 1/h, h*g.x, h*g.y, h*g.z,
+ * damp}.  A garment whose positions fit lds_bytes (24 bytes per vertex, at most 160 KiB) keeps them in LDS, any other in its rows of x.  An index of
+ * `pairs` outside [0, V_b) sets *bad = 1 (caller zeroes it) and is never dereferenced.  Refused by name: B > 65535, 2^31 or more vertices or
+ * constraints in all, a bad block / lds_bytes / substep count, a step constant that is not finite, null pointers. */
+int gn_cloth_simulate_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0, const double *alpha_t, const int64_t *csr,
+                            const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints, int64_t substeps,
+                            int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block, int64_t *bad, void *stream);
 
 #ifdef __cplusplus
 }
