@@ -18,6 +18,9 @@
 #error "libgarmentnets_hip.so needs the ROCm 7 hipcc (clang >= 20: __builtin_elementwise_maximum)"
 #endif
 
+// gn_grid_scatter's reduce codes (include/garmentnets_hip.h)
+enum { GN_REDUCE_MAX = 0, GN_REDUCE_MEAN = 1, GN_REDUCE_SUM = 2, GN_REDUCE_MIN = 3, GN_REDUCE_MUL = 4 };
+
 void gn_set_error(const char *fmt, ...);
 
 #define GN_REQUIRE(cond, ...)            \

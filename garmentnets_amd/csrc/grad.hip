@@ -9,64 +9,12 @@
 //    ascending element index -- and ONE wavefront per destination adds its terms in that order: identical calls give identical bits, no float atomics.
 //    (The integer atomics that count and hand out ranges only decide WHERE a range lives, never the order inside it.)
 #include "common.h"
+#include "inv_lists.h"
 #include <limits.h>
-
-// gn_grid_scatter's reduce codes (include/garmentnets_hip.h)
-enum { GN_REDUCE_MAX = 0, GN_REDUCE_MEAN = 1, GN_REDUCE_SUM = 2, GN_REDUCE_MIN = 3, GN_REDUCE_MUL = 4 };
 
 __device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) && a == a; }
 
-// ------------------------------------------------------------------------------------------------ inverse lists
-struct InvWs {
-    int32_t *cnt, *start, *cursor, *total, *lst, *sorted;
-};
-static size_t inv_ws_bytes(int64_t nkeys, int64_t n) { return (size_t)(3 * nkeys + 1 + 2 * n) * sizeof(int32_t); }
-static InvWs inv_ws(void *ws, int64_t nkeys, int64_t n) {
-    int32_t *w = reinterpret_cast<int32_t *>(ws);
-    return InvWs{w, w + nkeys, w + 2 * nkeys, w + 3 * nkeys, w + 3 * nkeys + 1, w + 3 * nkeys + 1 + n};
-}
-
-// keys[e] outside [0, nkeys): the element belongs to no destination (an empty slot, a corner beyond the border)
-__global__ __launch_bounds__(256) void inv_count_kernel(const int32_t *__restrict__ keys, int64_t n, int64_t nkeys, InvWs w) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int k = keys[e];
-    if (k >= 0 && k < nkeys) atomicAdd(&w.cnt[k], 1);
-}
-__global__ __launch_bounds__(256) void inv_start_kernel(int64_t nkeys, InvWs w) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nkeys || w.cnt[k] == 0) return;
-    w.start[k] = atomicAdd(w.total, w.cnt[k]);
-}
-__global__ __launch_bounds__(256) void inv_list_kernel(const int32_t *__restrict__ keys, int64_t n, int64_t nkeys, InvWs w) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int k = keys[e];
-    if (k >= 0 && k < nkeys) w.lst[w.start[k] + atomicAdd(&w.cursor[k], 1)] = (int)e;
-}
-// every element finds its rank in its destination's range (how many of the range's elements have a lower index: O(range) per element)
-__global__ __launch_bounds__(256) void inv_rank_kernel(const int32_t *__restrict__ keys, int64_t n, int64_t nkeys, InvWs w) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int k = keys[e];
-    if (k < 0 || k >= nkeys) return;
-    const int base = w.start[k], c = w.cnt[k];
-    int rank = 0;
-    for (int i = 0; i < c; ++i) rank += w.lst[base + i] < (int)e;
-    w.sorted[base + rank] = (int)e;
-}
-
-static int inv_build(const int32_t *keys, int64_t n, int64_t nkeys, InvWs w, hipStream_t st, const char *who) {
-    GN_HIP(hipMemsetAsync(w.cnt, 0, (size_t)(3 * nkeys + 1) * sizeof(int32_t), st), who);
-    if (n == 0) return GN_OK;
-    const dim3 block(256), ge((unsigned)gn_cdiv(n, 256)), gk((unsigned)gn_cdiv(nkeys, 256));
-    hipLaunchKernelGGL(inv_count_kernel, ge, block, 0, st, keys, n, nkeys, w);
-    hipLaunchKernelGGL(inv_start_kernel, gk, block, 0, st, nkeys, w);
-    hipLaunchKernelGGL(inv_list_kernel, ge, block, 0, st, keys, n, nkeys, w);
-    hipLaunchKernelGGL(inv_rank_kernel, ge, block, 0, st, keys, n, nkeys, w);
-    return GN_OK;
-}
-
+// ------------------------------------------------------------------------------------------------ ordered sums over the inverse lists (inv_lists.h)
 // one wavefront per destination, channels over its lanes: out[key][ch] = sum over the range, ascending, of coef[e] * g[e / div][ch]  (coef NULL: 1).
 // A destination nobody reads gets 0: the kernel writes every row of out.
 __global__ __launch_bounds__(256) void ordered_sum_kernel(InvWs w, int64_t nkeys, const float *__restrict__ coef, int div, const float *__restrict__ g,
@@ -96,16 +44,6 @@ static int ordered_sum(InvWs w, int64_t nkeys, const float *coef, int div, const
 // max / min: every occupied cell gets an owner point (which one only decides where the cell's winner row lives), every point whose value is bit-equal
 // to the cell's stored value bids its index for (owner, channel) with an integer atomicMin -- order-independent -- and the gather hands the cell's
 // gradient to the point that holds the bid.
-__global__ __launch_bounds__(256) void gsb_owner_kernel(const int32_t *__restrict__ flat_idx, int64_t N, int64_t cells, int32_t *__restrict__ count,
-                                                        int32_t *__restrict__ owner_of) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const int64_t cell = flat_idx[p];
-    if (cell < 0 || cell >= cells) { owner_of[p] = -1; return; }
-    const int old = atomicCAS(&count[cell], 0, (int)p + 1);
-    owner_of[p] = old == 0 ? (int)p : old - 1;
-}
-
 __global__ __launch_bounds__(256) void gsb_bid_kernel(const float *__restrict__ src, int lds, const float *__restrict__ vol, const int32_t *__restrict__ flat_idx,
                                                       int64_t N, int C, int c_real, const int32_t *__restrict__ owner_of, int32_t *__restrict__ win) {
     const int lane = threadIdx.x & 63;
@@ -175,7 +113,7 @@ extern "C" int gn_grid_scatter_bwd(const float *grad_vol, const float *vol, cons
         int32_t *owner_of = count + cells, *win = owner_of + N;
         GN_HIP(hipMemsetAsync(count, 0, (size_t)cells * sizeof(int32_t), st), "gn_grid_scatter_bwd(memset count)");
         GN_HIP(hipMemsetAsync(win, 0x7f, (size_t)N * C * sizeof(int32_t), st), "gn_grid_scatter_bwd(memset bids)");   // 0x7f7f7f7f > any point index
-        hipLaunchKernelGGL(gsb_owner_kernel, pts, block, 0, st, flat_idx, N, cells, count, owner_of);
+        hipLaunchKernelGGL(cell_owner_kernel<true>, pts, block, 0, st, flat_idx, N, cells, count, owner_of, (int32_t *)nullptr);
         hipLaunchKernelGGL(gsb_bid_kernel, grid, block, 0, st, src, lds, vol, flat_idx, N, C, c_real, owner_of, win);
         hipLaunchKernelGGL(gsb_select_kernel, grid, block, 0, st, grad_vol, flat_idx, N, C, c_real, owner_of, win, grad_src, ldg);
     } else {

@@ -2,9 +2,7 @@
 // channel-last feature volume.  Reference: networks/conv_implicit_wnf.py:43-100,
 // components/gridding.py:161-256 (VirtualGrid index maths, fp32, truncation toward zero).
 #include "common.h"
-
-// gn_grid_scatter's reduce codes (include/garmentnets_hip.h)
-enum { GN_REDUCE_MAX = 0, GN_REDUCE_MEAN = 1, GN_REDUCE_SUM = 2, GN_REDUCE_MIN = 3, GN_REDUCE_MUL = 4 };
+#include "inv_lists.h"
 
 struct GridParams {
     float lower[3], upper[3];
@@ -106,23 +104,12 @@ __global__ __launch_bounds__(256) void scatter_max_finalize_kernel(const int32_t
 
 // mean: DETERMINISTIC.  A float atomicAdd into the volume would make the sum depend on the arrival order of a cell's points (with
 // seeded synthetic weights a cell collects > 1000 points; the run-to-run spread, amplified by the GroupNorm of a > 99 % empty
-// volume, reached 4e-5 on the WNF).  Instead every occupied cell gets an OWNER point (first atomicCAS on the zeroed count
-// workspace; which point wins only decides where the partial sums live), the cell's points add their channels into the owner's
+// volume, reached 4e-5 on the WNF).  Instead every occupied cell gets an OWNER point (cell_owner_kernel, inv_lists.h; which point
+// wins only decides where the partial sums live), the cell's points add their channels into the owner's
 // row of an fp64 scratch [N][C] with fp64 atomics -- sums of <= 2^13 fp32 values are exact in fp64 unless their exponents span
 // more than 2^16, so the result does not depend on the order -- and the owner stores fp32(sum) / count: for one or two points
 // per cell (the realistic case: 6000 points over 128^3 cells) bit-identical to a sequential fp32 sum, closer to the exact mean
 // than it otherwise.
-__global__ __launch_bounds__(256) void scatter_mean_owner_kernel(const int32_t *__restrict__ flat_idx, int64_t N, int32_t *__restrict__ count,
-                                                                 int32_t *__restrict__ owner_of, int32_t *__restrict__ npts) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const int64_t cell = flat_idx[p];
-    const int old = atomicCAS(&count[cell], 0, (int)p + 1);
-    const int owner = old == 0 ? (int)p : old - 1;
-    owner_of[p] = owner;
-    atomicAdd(&npts[owner], 1);
-}
-
 __global__ __launch_bounds__(256) void scatter_mean_accum_kernel(const float *__restrict__ src, int lds, int64_t N, int C,
                                                                  const int32_t *__restrict__ owner_of, double *__restrict__ acc) {
     const int lane = threadIdx.x & 63;
@@ -149,37 +136,14 @@ __global__ __launch_bounds__(256) void scatter_mean_finalize_kernel(const int32_
 }
 
 // mul: the product of a cell's points in ascending point index -- the order of torch_scatter's CPU loop; a float atomic product would depend on the
-// arrival order.  Owners as for mean; each owner gets a range of a point list (counting sort keyed by the owner: a range per owner from one counter,
-// then the points in arrival order), every point finds its rank in its cell's range (how many of the cell's points have a lower index: O(k) per point,
-// k = the cell's points) and moves to that slot of a second list, and the owner multiplies its cell's rows in that order, starting from the identity 1.
+// arrival order.  Owners as for mean; the ordered inverse lists of inv_lists.h keyed by the owner (its npts are the counts) give every owner its cell's
+// points in ascending index, and the owner multiplies its cell's rows in that order, starting from the identity 1.
 struct MulWs {
     int32_t *owner_of, *npts, *start, *cursor, *lst, *sorted, *total;
 };
 __host__ __device__ inline MulWs mul_ws(void *ws, int64_t N) {
     int32_t *w = reinterpret_cast<int32_t *>(ws);
     return MulWs{w, w + N, w + 2 * N, w + 3 * N, w + 4 * N, w + 5 * N, w + 6 * N};
-}
-
-__global__ __launch_bounds__(256) void scatter_mul_start_kernel(int64_t N, MulWs w) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N || w.owner_of[p] != (int)p) return;
-    w.start[p] = atomicAdd(w.total, w.npts[p]);
-}
-
-__global__ __launch_bounds__(256) void scatter_mul_list_kernel(int64_t N, MulWs w) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const int o = w.owner_of[p];
-    w.lst[w.start[o] + atomicAdd(&w.cursor[o], 1)] = (int)p;
-}
-
-__global__ __launch_bounds__(256) void scatter_mul_rank_kernel(int64_t N, MulWs w) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N) return;
-    const int o = w.owner_of[p], base = w.start[o], k = w.npts[o];
-    int rank = 0;
-    for (int i = 0; i < k; ++i) rank += w.lst[base + i] < (int)p;
-    w.sorted[base + rank] = (int)p;
 }
 
 // every cell: 1 on the real channels (the identity an empty cell keeps), 0 on the pads [c_real, C)
@@ -245,16 +209,14 @@ extern "C" int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat
     } else if (reduce == GN_REDUCE_MUL) {
         const MulWs w = mul_ws(ws, N);
         GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
-        hipLaunchKernelGGL(scatter_mean_owner_kernel, pts, block, 0, st, flat_idx, N, count_ws, w.owner_of, w.npts);
-        hipLaunchKernelGGL(scatter_mul_start_kernel, pts, block, 0, st, N, w);
-        hipLaunchKernelGGL(scatter_mul_list_kernel, pts, block, 0, st, N, w);
-        hipLaunchKernelGGL(scatter_mul_rank_kernel, pts, block, 0, st, N, w);
+        hipLaunchKernelGGL(cell_owner_kernel<false>, pts, block, 0, st, flat_idx, N, cells, count_ws, w.owner_of, w.npts);
+        inv_build_counted(w.owner_of, N, N, InvWs{w.npts, w.start, w.cursor, w.total, w.lst, w.sorted}, st);
         hipLaunchKernelGGL(scatter_mul_finalize_kernel, grid, block, 0, st, src, lds, flat_idx, N, C, w, vol, count_ws);
     } else {
         double *acc = reinterpret_cast<double *>(ws);
         int32_t *owner_of = reinterpret_cast<int32_t *>(acc + (size_t)N * C), *npts = owner_of + N;
         GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
-        hipLaunchKernelGGL(scatter_mean_owner_kernel, pts, block, 0, st, flat_idx, N, count_ws, owner_of, npts);
+        hipLaunchKernelGGL(cell_owner_kernel<false>, pts, block, 0, st, flat_idx, N, cells, count_ws, owner_of, npts);
         hipLaunchKernelGGL(scatter_mean_accum_kernel, grid, block, 0, st, src, lds, N, C, owner_of, acc);
         if (reduce == GN_REDUCE_MEAN)
             hipLaunchKernelGGL(scatter_mean_finalize_kernel<true>, grid, block, 0, st, flat_idx, N, C, owner_of, npts, acc, vol, count_ws);

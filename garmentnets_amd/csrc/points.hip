@@ -79,6 +79,31 @@ __device__ __forceinline__ float fps_min(float a, float b) {
     return o;
 }
 
+// The workgroup's arg-max of step k from every lane's (bv, bi): largest value, ties to the lowest index; `gv` receives the value.  pv / pi are
+// the [2][WAVES] exchange buffers (by step parity: one barrier per step).  BALLOT reads the wave's index from the one lane a ballot names and
+// falls back to the DPP min of the indices on exact ties; without it the DPP min runs every step.
+template <int WAVES, bool BALLOT>
+__device__ __forceinline__ int fps_pick(float bv, int bi, int k, float *pv, int *pi, int lane, int wave, float &gv) {
+    const float wv = gn_wave_max(bv);
+    int wi;
+    if (BALLOT) {
+        const unsigned long long hit = __ballot(bv == wv);
+        if (__builtin_popcountll(hit) == 1) wi = __builtin_amdgcn_readlane(bi, __builtin_ctzll(hit));
+        else wi = gn_wave_min(bv == wv ? bi : INT_MAX);
+    } else {
+        wi = gn_wave_min(bv == wv ? bi : INT_MAX);
+    }
+    const int par = (k & 1) * WAVES;
+    if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
+    __syncthreads();
+    // lanes 0..WAVES-1 (replicated over the 16-lane DPP row) of every wave reduce the partials
+    float fv = pv[par + (lane & (WAVES - 1))];
+    int fi = pi[par + (lane & (WAVES - 1))];
+    gv = gn_row_max<WAVES>(fv);
+    fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
+    return __builtin_amdgcn_readfirstlane(fi);
+}
+
 template <int PPT, bool LDS_POS, int THREADS>
 __global__ __launch_bounds__(THREADS) void fps_kernel(const float *__restrict__ pos, const int32_t *__restrict__ ptr,
                                                       const int32_t *__restrict__ out_ptr, const int32_t *__restrict__ start_idx,
@@ -151,43 +176,37 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(const float *__restrict__ 
             }
         }
         const int bi = bv >= 0.f ? tid + bj * THREADS : INT_MAX;   // (a lane whose slots are all past the end holds -1)
-        const float wv = gn_wave_max(bv);
-        // the lanes that hold the wave's maximum: one lane in all but exact ties -> its index is read directly; ties take the DPP min
-        const unsigned long long hit = __ballot(bv == wv);
-        int wi;
-        if (__builtin_popcountll(hit) == 1) wi = __builtin_amdgcn_readlane(bi, __builtin_ctzll(hit));
-        else wi = gn_wave_min(bv == wv ? bi : INT_MAX);
-        const int par = (k & 1) * WAVES;
-        if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
-        __syncthreads();
-        // lanes 0..WAVES-1 (replicated over the 16-lane DPP row) of every wave reduce the partials
-        float fv = pv[par + (lane & (WAVES - 1))];
-        int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = gn_row_max<WAVES>(fv);
-        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
-        last = __builtin_amdgcn_readfirstlane(fi);
+        float gv;
+        last = fps_pick<WAVES, true>(bv, bi, k, pv, pi, lane, wave, gv);
         gmin = fps_min(gmin, gv);
         if (tid == 0) out_idx[o0 + k] = s + last;
     }
     if (gap_out && tid == 0) gap_out[b] = gmin;
 }
 
-// Large examples (more points than the register-resident kernel's 16 per lane x 1024 lanes): the running distances live in LDS (one float per point, up to
-// FPS_LDS_MAX points = 144 KB), the coordinates are re-read from global memory every step (L2-resident).  Same arithmetic, same tie rule (a thread walks its
-// points in ascending index and keeps the first maximum; wave and workgroup reductions as above), so the index lists are the oracle's for any size; the price is
-// ~n / 1024 dependent LDS round trips per step instead of a register update -- a correctness path for clouds the reference's fps (no limit,
-// components/pointnet2.py:26) would take, not a tuned one.
+// Large examples (more points than the register-resident kernel's 16 per lane x 1024 lanes).  Same arithmetic, same tie rule (a thread walks its
+// points in ascending index and keeps the first maximum; wave and workgroup reductions as above), so the index lists are the oracle's for any size --
+// a correctness path for clouds the reference's fps (no limit, components/pointnet2.py:26) would take, not a tuned one.  The running distances live
+//   * in LDS up to FPS_LDS_MAX points (one float per point = 144 KB), the coordinates re-read from global memory every step (L2-resident): ~n / 1024
+//     dependent LDS round trips per step instead of a register update;
+//   * IN_WS, beyond that, in a device workspace: one 16-byte record (x, y, z, d) per point written once at the start, so that a step is one dwordx4
+//     load and one dword store per point (L2-resident: 1.6 MB per 100 000 points).  Every thread reads and writes only its own records (points tid,
+//     tid + FPS_THREADS, ...), so the workspace needs no barrier.
+// One workgroup per example either way -- never one example over several workgroups, which would pay a device-scope fence and a spin barrier per step.
 #define FPS_LDS_MAX (36 * 1024)
-__global__ __launch_bounds__(FPS_THREADS) void fps_lds_kernel(const float *__restrict__ pos, const int32_t *__restrict__ ptr, const int32_t *__restrict__ out_ptr,
-                                                             const int32_t *__restrict__ start_idx, int32_t *__restrict__ out_idx, float *__restrict__ gap_out,
-                                                             const float *__restrict__ nested_gap) {
+template <bool IN_WS>
+__global__ __launch_bounds__(FPS_THREADS) void fps_large_kernel(const float *__restrict__ pos, const int32_t *__restrict__ ptr, const int32_t *__restrict__ out_ptr,
+                                                               const int32_t *__restrict__ start_idx, int32_t *__restrict__ out_idx, float *__restrict__ gap_out,
+                                                               const float *__restrict__ nested_gap, float4 *__restrict__ ws, int max_points) {
     constexpr int WAVES = FPS_WAVES;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x;
     const int s = ptr[b], n = ptr[b + 1] - s;
     const int o0 = out_ptr[b], m = out_ptr[b + 1] - o0;
     if (n <= 0 || m <= 0) return;
+    if (IN_WS && n > max_points) return;   // (an example larger than the caller's max_points would run past its workspace rows)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the nested prefix and the start clamp as in fps_kernel, written out in both: as inlined helpers they change fps_kernel's instruction stream
     if (nested_gap && nested_gap[b] > 0.f && m <= n) {
         for (int k = tid; k < m; k += FPS_THREADS) out_idx[o0 + k] = s + k;
         if (gap_out && tid == 0) gap_out[b] = nested_gap[b];
@@ -195,10 +214,14 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_lds_kernel(const float *__res
     }
     float *pv = smem;
     int *pi = (int *)(smem + 2 * WAVES);
-    float *dd = smem + 4 * WAVES;
+    float *dd = smem + 4 * WAVES;                                    // [n] (LDS form)
+    float4 *rec = IN_WS ? ws + (size_t)b * max_points : nullptr;     // [n] (workspace form)
     const float *gp = pos + 3 * (size_t)s;
-    for (int i = tid; i < n; i += FPS_THREADS) dd[i] = 3.0e38f;
-    __syncthreads();
+    for (int i = tid; i < n; i += FPS_THREADS) {
+        if (IN_WS) rec[i] = make_float4(gp[3 * i], gp[3 * i + 1], gp[3 * i + 2], 3.0e38f);
+        else dd[i] = 3.0e38f;
+    }
+    if (!IN_WS) __syncthreads();
     float gmin = 3.0e38f;
     int last = start_idx ? start_idx[b] : 0;
     if (last < 0 || last >= n) last = 0;
@@ -208,37 +231,52 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_lds_kernel(const float *__res
         float bv = -1.f;
         int bi = INT_MAX;
         for (int i = tid; i < n; i += FPS_THREADS) {
-            const float d = fps_min(dd[i], gn_sqdist3(gp[3 * i], gp[3 * i + 1], gp[3 * i + 2], qx, qy, qz));
-            dd[i] = d;
+            float d;
+            if (IN_WS) {
+                const float4 r = rec[i];
+                d = fps_min(r.w, gn_sqdist3(r.x, r.y, r.z, qx, qy, qz));
+                reinterpret_cast<float *>(rec + i)[3] = d;
+            } else {
+                d = fps_min(dd[i], gn_sqdist3(gp[3 * i], gp[3 * i + 1], gp[3 * i + 2], qx, qy, qz));
+                dd[i] = d;
+            }
             if (d > bv) { bv = d; bi = i; }          // ascending index: ties keep the lowest
         }
-        const float wv = gn_wave_max(bv);
-        const int wi = gn_wave_min(bv == wv ? bi : INT_MAX);
-        const int par = (k & 1) * WAVES;
-        if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
-        __syncthreads();
-        float fv = pv[par + (lane & (WAVES - 1))];
-        int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = gn_row_max<WAVES>(fv);
-        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
-        last = __builtin_amdgcn_readfirstlane(fi);
+        float gv;
+        last = fps_pick<WAVES, false>(bv, bi, k, pv, pi, lane, wave, gv);
         gmin = fps_min(gmin, gv);
         if (tid == 0) out_idx[o0 + k] = s + last;
     }
     if (gap_out && tid == 0) gap_out[b] = gmin;
 }
 
-extern "C" int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
-                             int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *stream) {
-    GN_REQUIRE(B >= 0 && max_points_per_example >= 0, "gn_fps: bad sizes");
+extern "C" size_t gn_fps_workspace_bytes(int B, int max_points_per_example) {
+    if (B <= 0 || max_points_per_example <= FPS_LDS_MAX) return 0;
+    return (size_t)B * (size_t)max_points_per_example * sizeof(float4);
+}
+
+// the checks and the kernel choice of the three entries; `takes_ws`: the entry has workspace arguments (gn_fps_nested_ws)
+static int fps_checked_launch(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B, int n, int32_t *out_idx,
+                              float *gap_out, const float *nested_gap, bool takes_ws, void *ws, size_t ws_bytes, void *stream) {
+    GN_REQUIRE(B >= 0 && n >= 0, "gn_fps: bad sizes");
     GN_REQUIRE(nested_gap == nullptr || start_idx == nullptr, "gn_fps_nested: a nested sample starts at the example's first point (start_idx must be NULL)");
-    if (B == 0 || max_points_per_example == 0) return GN_OK;
-    const int n = max_points_per_example;
-    GN_REQUIRE(n <= FPS_LDS_MAX, "gn_fps: more than %d points per example needs a workspace: gn_fps_nested_ws (got %d)", FPS_LDS_MAX, n);
-    if (n > 16 * FPS_THREADS) {                     // beyond the register-resident kernels: running distances in LDS (fps_lds_kernel)
+    if (B == 0 || n == 0) return GN_OK;
+    if (n > FPS_LDS_MAX) {
+        GN_REQUIRE(takes_ws, "gn_fps: more than %d points per example needs a workspace: gn_fps_nested_ws (got %d)", FPS_LDS_MAX, n);
+        const size_t need = gn_fps_workspace_bytes(B, n);
+        GN_REQUIRE(ws != nullptr && ws_bytes >= need, "gn_fps_nested_ws: %d points per example need a workspace of %zu bytes (gn_fps_workspace_bytes), got %zu",
+                   n, need, ws ? ws_bytes : (size_t)0);
+        GN_REQUIRE(((uintptr_t)ws & 15) == 0, "gn_fps_nested_ws: the workspace must be 16-byte aligned");
+        hipLaunchKernelGGL(fps_large_kernel<true>, dim3(B), dim3(FPS_THREADS), sizeof(float) * 4 * FPS_WAVES, gn_stream(stream), pos, ptr, out_ptr, start_idx,
+                           out_idx, gap_out, nested_gap, reinterpret_cast<float4 *>(ws), n);
+        GN_LAUNCH_CHECK("gn_fps");
+        return GN_OK;
+    }
+    if (n > 16 * FPS_THREADS) {                     // beyond the register-resident kernels
         const size_t shl = sizeof(float) * (4 * FPS_WAVES + (size_t)n);
-        GN_HIP(hipFuncSetAttribute((const void *)fps_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shl), "gn_fps");
-        hipLaunchKernelGGL(fps_lds_kernel, dim3(B), dim3(FPS_THREADS), shl, gn_stream(stream), pos, ptr, out_ptr, start_idx, out_idx, gap_out, nested_gap);
+        GN_HIP(hipFuncSetAttribute((const void *)fps_large_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shl), "gn_fps");
+        hipLaunchKernelGGL(fps_large_kernel<false>, dim3(B), dim3(FPS_THREADS), shl, gn_stream(stream), pos, ptr, out_ptr, start_idx, out_idx, gap_out,
+                           nested_gap, (float4 *)nullptr, 0);
         GN_LAUNCH_CHECK("gn_fps");
         return GN_OK;
     }
@@ -276,86 +314,20 @@ extern "C" int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t
     return GN_OK;
 }
 
-// Examples of more points than fps_lds_kernel holds: the running distances live in a device workspace, one 16-byte record (x, y, z, d) per point written
-// once at the start, so that a step is one dwordx4 load and one dword store per point (L2-resident: 1.6 MB per 100 000 points).  One workgroup per example as
-// above -- never one example over several workgroups, which would pay a device-scope fence and a spin barrier per step.  Every thread reads and writes only
-// its own records (points tid, tid + FPS_THREADS, ...), so the workspace needs no barrier; same arithmetic, same walk in ascending index and the same
-// reductions as fps_lds_kernel, hence the same index list.  A correctness path for the clouds the reference takes without limit, not a tuned one.
-__global__ __launch_bounds__(FPS_THREADS) void fps_ws_kernel(const float *__restrict__ pos, const int32_t *__restrict__ ptr, const int32_t *__restrict__ out_ptr,
-                                                            const int32_t *__restrict__ start_idx, int32_t *__restrict__ out_idx, float *__restrict__ gap_out,
-                                                            const float *__restrict__ nested_gap, float4 *__restrict__ ws, int max_points) {
-    constexpr int WAVES = FPS_WAVES;
-    __shared__ float pv[2 * WAVES];
-    __shared__ int pi[2 * WAVES];
-    const int b = blockIdx.x;
-    const int s = ptr[b], n = ptr[b + 1] - s;
-    const int o0 = out_ptr[b], m = out_ptr[b + 1] - o0;
-    if (n <= 0 || m <= 0 || n > max_points) return;   // (an example larger than the caller's max_points would run past its workspace rows)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (nested_gap && nested_gap[b] > 0.f && m <= n) {
-        for (int k = tid; k < m; k += FPS_THREADS) out_idx[o0 + k] = s + k;
-        if (gap_out && tid == 0) gap_out[b] = nested_gap[b];
-        return;
-    }
-    const float *gp = pos + 3 * (size_t)s;
-    float4 *rec = ws + (size_t)b * max_points;
-    for (int i = tid; i < n; i += FPS_THREADS) rec[i] = make_float4(gp[3 * i], gp[3 * i + 1], gp[3 * i + 2], 3.0e38f);
-    float gmin = 3.0e38f;
-    int last = start_idx ? start_idx[b] : 0;
-    if (last < 0 || last >= n) last = 0;
-    if (tid == 0) out_idx[o0] = s + last;
-    for (int k = 1; k < m; ++k) {
-        const float qx = gp[3 * last], qy = gp[3 * last + 1], qz = gp[3 * last + 2];
-        float bv = -1.f;
-        int bi = INT_MAX;
-        for (int i = tid; i < n; i += FPS_THREADS) {
-            const float4 r = rec[i];
-            const float d = fps_min(r.w, gn_sqdist3(r.x, r.y, r.z, qx, qy, qz));
-            reinterpret_cast<float *>(rec + i)[3] = d;
-            if (d > bv) { bv = d; bi = i; }          // ascending index: ties keep the lowest
-        }
-        const float wv = gn_wave_max(bv);
-        const int wi = gn_wave_min(bv == wv ? bi : INT_MAX);
-        const int par = (k & 1) * WAVES;
-        if (lane == 0) { pv[par + wave] = wv; pi[par + wave] = wi; }
-        __syncthreads();
-        float fv = pv[par + (lane & (WAVES - 1))];
-        int fi = pi[par + (lane & (WAVES - 1))];
-        const float gv = gn_row_max<WAVES>(fv);
-        fi = gn_row_min<WAVES>(fv == gv ? fi : INT_MAX);
-        last = __builtin_amdgcn_readfirstlane(fi);
-        gmin = fps_min(gmin, gv);
-        if (tid == 0) out_idx[o0 + k] = s + last;
-    }
-    if (gap_out && tid == 0) gap_out[b] = gmin;
+extern "C" int gn_fps(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
+                      int max_points_per_example, int32_t *out_idx, void *stream) {
+    return fps_checked_launch(pos, ptr, out_ptr, start_idx, B, max_points_per_example, out_idx, nullptr, nullptr, false, nullptr, 0, stream);
 }
 
-extern "C" size_t gn_fps_workspace_bytes(int B, int max_points_per_example) {
-    if (B <= 0 || max_points_per_example <= FPS_LDS_MAX) return 0;
-    return (size_t)B * (size_t)max_points_per_example * sizeof(float4);
+extern "C" int gn_fps_nested(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
+                             int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *stream) {
+    return fps_checked_launch(pos, ptr, out_ptr, start_idx, B, max_points_per_example, out_idx, gap_out, nested_gap, false, nullptr, 0, stream);
 }
 
 extern "C" int gn_fps_nested_ws(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
                                 int max_points_per_example, int32_t *out_idx, float *gap_out, const float *nested_gap, void *ws, size_t ws_bytes,
                                 void *stream) {
-    GN_REQUIRE(B >= 0 && max_points_per_example >= 0, "gn_fps: bad sizes");
-    GN_REQUIRE(nested_gap == nullptr || start_idx == nullptr, "gn_fps_nested: a nested sample starts at the example's first point (start_idx must be NULL)");
-    const int n = max_points_per_example;
-    if (B == 0 || n == 0 || n <= FPS_LDS_MAX)
-        return gn_fps_nested(pos, ptr, out_ptr, start_idx, B, n, out_idx, gap_out, nested_gap, stream);
-    const size_t need = gn_fps_workspace_bytes(B, n);
-    GN_REQUIRE(ws != nullptr && ws_bytes >= need, "gn_fps_nested_ws: %d points per example need a workspace of %zu bytes (gn_fps_workspace_bytes), got %zu",
-               n, need, ws ? ws_bytes : (size_t)0);
-    GN_REQUIRE(((uintptr_t)ws & 15) == 0, "gn_fps_nested_ws: the workspace must be 16-byte aligned");
-    hipLaunchKernelGGL(fps_ws_kernel, dim3(B), dim3(FPS_THREADS), 0, gn_stream(stream), pos, ptr, out_ptr, start_idx, out_idx, gap_out, nested_gap,
-                       reinterpret_cast<float4 *>(ws), n);
-    GN_LAUNCH_CHECK("gn_fps");
-    return GN_OK;
-}
-
-extern "C" int gn_fps(const float *pos, const int32_t *ptr, const int32_t *out_ptr, const int32_t *start_idx, int B,
-                      int max_points_per_example, int32_t *out_idx, void *stream) {
-    return gn_fps_nested(pos, ptr, out_ptr, start_idx, B, max_points_per_example, out_idx, nullptr, nullptr, stream);
+    return fps_checked_launch(pos, ptr, out_ptr, start_idx, B, max_points_per_example, out_idx, gap_out, nested_gap, true, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ ball query

@@ -8,8 +8,9 @@
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------------ channel stats
-// grid (chunks, B).  Thread t owns channel t % C (C | 256) or channels t, t+256, ... (256 | C) and walks the
-// chunk's voxels; per-thread fp32 partials over <= 64 voxels, then fp64 atomics into [B][C].
+// grid (chunks, B).  C <= 256: floor(256 / C) voxel groups of C threads, thread t owns channel t % C of group t / C and walks the chunk's
+// voxels of its group (the threads past the last whole group idle: none when C | 256); per-thread fp32 partials over <= 32 voxels, then
+// fp64 atomics into [B][C].  C > 256: thread t owns channels t, t+256, ... over the whole chunk.
 #define STATS_VOX_PER_BLOCK 512
 __global__ __launch_bounds__(256) void channel_stats_kernel(const float *__restrict__ x, int64_t V, int C,
                                                             double *__restrict__ sum, double *__restrict__ sumsq) {
@@ -20,6 +21,7 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float *__restr
     const float *xb = x + (int64_t)b * V * C;
     if (C <= 256) {
         const int c = threadIdx.x % C, g = threadIdx.x / C, ng = 256 / C;
+        if (g >= ng) return;
         double s = 0.0, q = 0.0;
         float fs = 0.f, fq = 0.f;
         int cnt = 0;
@@ -46,79 +48,57 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float *__restr
     }
 }
 
+static int channel_stats_launch(const char *name, const float *x, int B, int64_t V, int C, double *sum, double *sumsq, void *stream) {
+    hipStream_t st = gn_stream(stream);
+    GN_HIP(gn_zero_stats(sum, sumsq, (size_t)B * C, st), name);
+    if (B == 0 || V == 0) return GN_OK;
+    hipLaunchKernelGGL(channel_stats_kernel, dim3((unsigned)gn_cdiv(V, STATS_VOX_PER_BLOCK), B), dim3(256), 0, st, x, V, C, sum, sumsq);
+    GN_LAUNCH_CHECK(name);
+    return GN_OK;
+}
+
 extern "C" int gn_channel_stats(const float *x, int B, int64_t V, int C, double *sum, double *sumsq, void *stream) {
     GN_REQUIRE(B >= 0 && V >= 0 && C > 0, "gn_channel_stats: bad sizes");
     GN_REQUIRE((C <= 256 && 256 % C == 0) || (C % 256 == 0), "gn_channel_stats: C=%d must divide 256 or be a multiple of it", C);
-    hipStream_t st = gn_stream(stream);
-    GN_HIP(gn_zero_stats(sum, sumsq, (size_t)B * C, st), "gn_channel_stats");
-    if (B == 0 || V == 0) return GN_OK;
-    hipLaunchKernelGGL(channel_stats_kernel, dim3((unsigned)gn_cdiv(V, STATS_VOX_PER_BLOCK), B), dim3(256), 0, st, x, V, C, sum, sumsq);
-    GN_LAUNCH_CHECK("gn_channel_stats");
-    return GN_OK;
+    return channel_stats_launch("gn_channel_stats", x, B, V, C, sum, sumsq, stream);
 }
 
-// The channel counts channel_stats_kernel's thread layout does not cover below 256 (C does not divide 256: 96, 160, 192, 224 -- the UNet's
-// channel-padded widths): floor(256 / C) voxel groups of C threads, the remaining threads idle; otherwise its C <= 256 branch, same order.
-__global__ __launch_bounds__(256) void channel_stats_rows_kernel(const float *__restrict__ x, int64_t V, int C, double *__restrict__ sum,
-                                                                 double *__restrict__ sumsq) {
-    const int b = blockIdx.y, ng = 256 / C, c = threadIdx.x % C, g = threadIdx.x / C;
-    if (g >= ng) return;
-    const int64_t v0 = (int64_t)blockIdx.x * STATS_VOX_PER_BLOCK;
-    int64_t v1 = v0 + STATS_VOX_PER_BLOCK;
-    if (v1 > V) v1 = V;
-    const float *xb = x + (int64_t)b * V * C;
-    double s = 0.0, q = 0.0;
-    float fs = 0.f, fq = 0.f;
-    int cnt = 0;
-    for (int64_t v = v0 + g; v < v1; v += ng) {
-        float t = xb[v * C + c];
-        fs += t;
-        fq = fmaf(t, t, fq);
-        if (++cnt == 32) { s += fs; q += fq; fs = fq = 0.f; cnt = 0; }
-    }
-    s += fs; q += fq;
-    atomicAdd(&sum[(int64_t)b * C + c], s);
-    atomicAdd(&sumsq[(int64_t)b * C + c], q);
-}
-
-// gn_channel_stats for any C % 4 == 0.  The counts gn_channel_stats takes run its code unchanged; C > 256 takes channel_stats_kernel's
-// thread-per-channel branch, which never needed 256 | C; C < 256 the strided rows above.
+// gn_channel_stats for any C % 4 == 0 (96, 160, 192, 224: the UNet's channel-padded widths).
 extern "C" int gn_channel_stats_any(const float *x, int B, int64_t V, int C, double *sum, double *sumsq, void *stream) {
     GN_REQUIRE(B >= 0 && V >= 0 && C > 0 && C % 4 == 0, "gn_channel_stats_any: bad sizes (C=%d must be a positive multiple of 4)", C);
-    if ((C <= 256 && 256 % C == 0) || C % 256 == 0) return gn_channel_stats(x, B, V, C, sum, sumsq, stream);
-    hipStream_t st = gn_stream(stream);
-    GN_HIP(gn_zero_stats(sum, sumsq, (size_t)B * C, st), "gn_channel_stats_any");
-    if (B == 0 || V == 0) return GN_OK;
-    const dim3 grid((unsigned)gn_cdiv(V, STATS_VOX_PER_BLOCK), B);
-    if (C > 256) hipLaunchKernelGGL(channel_stats_kernel, grid, dim3(256), 0, st, x, V, C, sum, sumsq);
-    else hipLaunchKernelGGL(channel_stats_rows_kernel, grid, dim3(256), 0, st, x, V, C, sum, sumsq);
-    GN_LAUNCH_CHECK("gn_channel_stats_any");
-    return GN_OK;
+    return channel_stats_launch("gn_channel_stats_any", x, B, V, C, sum, sumsq, stream);
 }
 
-// one block per sample, one thread per group.  With `act_inv_scale` (split-operand convs): the affine of the whole sample is multiplied
+// GroupNorm statistics -> per-(sample, channel) affine y = a x + d.  One block per sample.  Source k holds Ck REAL channels in rows of
+// Sk >= Ck stored ones ([B][Sk] statistics: the UNet stores a layer of c channels as round_up(c, 32), the conv kernels need Cout % 32 == 0);
+// the groups are formed over the C0 + C1 real channels (gamma / beta [C0 + C1]); a / d are written in the stored layout [B][S0 + S1], pad
+// channels a = d = 0 (the convolutions then see exact zeros there whatever the pads hold).  A padded layout gives the unpadded layout's
+// bits on its real channels: the pads add nothing to a group sum and their rms is 0.
+// With `act_inv_scale` (split-operand convs): the affine of the whole sample is multiplied
 // by a power of two 2^k chosen from the statistics so that the largest per-channel rms of the normalised activations
 // y_c = a_c x + d_c (E[y^2] = a^2 E[x^2] + 2 a d E[x] + d^2, all known here) lands in [1, 2); act_inv_scale[b] = 2^-k undoes it exactly
 // in the conv epilogue.  fp16's narrow exponent then never matters: a channel's values are bounded by rms * sqrt(V) <= 2 * 2^14.5
 // < 65504 for any V < 2^29 voxels (no overflow by construction, whatever the checkpoint), and values down to 1/8 of the typical
 // magnitude keep a normal second plane (residual <= 2^-22 |x|; below that the residual is absolute, 2^-25 of the sample's scale).
-// Round 6: the statistics of the sample are first brought into LDS by all threads (coalesced), the per-GROUP sums are then formed by one thread per group
-// in ascending channel order -- the summation order of the round-1 kernel, bit for bit -- and everything per CHANNEL (a, d, the rms) runs one thread per
-// channel.  The thread-per-group form walked up to 48 channels through dependent global loads: 40 us for the 384-channel decoder layer, 12 us typical.
+// The statistics of the sample are first brought into LDS by all threads (coalesced), the per-GROUP sums are then formed by one thread per group
+// in ascending channel order -- the pinned summation order -- and everything per CHANNEL (a, d, the rms) runs one thread per channel.  A thread
+// per group walking its channels through dependent global loads took 40 us for the 384-channel decoder layer, 12 us typical.
+// Per-channel and per-group tables in dynamic LDS: 16 B per channel + 8 B per group (~6-10k channels in 160 KB).
 #define GNA_THREADS 256
-#define GNA_MAXC 1024
-__global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_kernel(const double *__restrict__ sum0, const double *__restrict__ sq0, int C0, int64_t V0,
-                                        const double *__restrict__ sum1, const double *__restrict__ sq1, int C1, int64_t V1,
-                                        int rep1, int B, int groups, float eps, const float *__restrict__ gamma,
-                                        const float *__restrict__ beta, float *__restrict__ a, float *__restrict__ d,
-                                        float *__restrict__ act_inv_scale) {
-    __shared__ double ls[GNA_MAXC], lq[GNA_MAXC];           // per-channel sum / sum of squares (source 1 already times rep1)
-    __shared__ float grstd[GNA_MAXC], gmean[GNA_MAXC];      // per group
-    __shared__ float gmax[GNA_THREADS / 64];
-    const int b = blockIdx.x, C = C0 + C1, cpg = C / groups, tid = threadIdx.x;
+__global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_kernel(const double *__restrict__ sum0, const double *__restrict__ sq0, int C0, int S0,
+                                        int64_t V0, const double *__restrict__ sum1, const double *__restrict__ sq1, int C1, int S1, int rep1,
+                                        int groups, float eps, const float *__restrict__ gamma, const float *__restrict__ beta, float *__restrict__ a,
+                                        float *__restrict__ d, float *__restrict__ act_inv_scale) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gna_smem[];
+    const int b = blockIdx.x, C = C0 + C1, S = S0 + S1, cpg = C / groups, tid = threadIdx.x;
+    double *ls = reinterpret_cast<double *>(gna_smem), *lq = ls + C;   // per-channel sum / sum of squares (source 1 already times rep1)
+    float *grstd = reinterpret_cast<float *>(lq + C), *gmean = grstd + groups, *gmax = gmean + groups;   // per group; per wave
     for (int c = tid; c < C; c += GNA_THREADS) {
-        if (c < C0) { ls[c] = sum0[(int64_t)b * C0 + c]; lq[c] = sq0[(int64_t)b * C0 + c]; }
-        else { ls[c] = rep1 * sum1[(int64_t)b * C1 + c - C0]; lq[c] = rep1 * sq1[(int64_t)b * C1 + c - C0]; }
+        if (c < C0) { ls[c] = sum0[(int64_t)b * S0 + c]; lq[c] = sq0[(int64_t)b * S0 + c]; }
+        else { ls[c] = rep1 * sum1[(int64_t)b * S1 + c - C0]; lq[c] = rep1 * sq1[(int64_t)b * S1 + c - C0]; }
+    }
+    for (int j = tid; j < S; j += GNA_THREADS) {                 // pad channels (stored positions C0..S0-1 and S0+C1..S-1)
+        if ((j >= C0 && j < S0) || j >= S0 + C1) { a[(int64_t)b * S + j] = 0.f; d[(int64_t)b * S + j] = 0.f; }
     }
     __syncthreads();
     for (int g = tid; g < groups; g += GNA_THREADS) {
@@ -135,10 +115,11 @@ __global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_kernel(const dou
     float my_max = 0.f;
     for (int c = tid; c < C; c += GNA_THREADS) {
         const int g = c / cpg;
+        const int64_t o = (int64_t)b * S + (c < C0 ? c : S0 + c - C0);
         const float ga = gamma[c] * grstd[g];
         const float dd = beta[c] - gmean[g] * ga;
-        a[(int64_t)b * C + c] = ga;
-        d[(int64_t)b * C + c] = dd;
+        a[o] = ga;
+        d[o] = dd;
         if (act_inv_scale) {
             const double ex = ls[c] / (double)V0, ex2 = lq[c] / (double)V0;
             const double ey2 = (double)ga * ga * ex2 + 2.0 * (double)ga * dd * ex + (double)dd * dd;
@@ -161,88 +142,7 @@ __global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_kernel(const dou
         sc = ldexpf(1.f, e);
         inv = ldexpf(1.f, -e);
     }
-    for (int c = tid; c < C; c += GNA_THREADS) { a[(int64_t)b * C + c] *= sc; d[(int64_t)b * C + c] *= sc; }      // (each thread rescales what it wrote)
-    if (tid == 0) act_inv_scale[b] = inv;
-}
-
-extern "C" int gn_groupnorm_affine(const double *sum0, const double *sq0, int C0, int64_t V0, const double *sum1, const double *sq1,
-                                   int C1, int64_t V1, int rep1, int B, int groups, float eps, const float *gamma,
-                                   const float *beta, float *a, float *d, float *act_inv_scale, void *stream) {
-    GN_REQUIRE(B >= 0 && groups > 0 && C0 > 0 && C1 >= 0 && (C0 + C1) % groups == 0, "gn_groupnorm_affine: bad sizes");
-    GN_REQUIRE(C0 + C1 <= GNA_MAXC, "gn_groupnorm_affine: at most %d channels (got %d)", GNA_MAXC, C0 + C1);
-    GN_REQUIRE(C1 == 0 || V1 * rep1 == V0, "gn_groupnorm_affine: source 1 must cover the same voxels after replication");
-    if (B == 0) return GN_OK;
-    hipLaunchKernelGGL(groupnorm_affine_kernel, dim3((unsigned)B), dim3(GNA_THREADS), 0, gn_stream(stream), sum0, sq0, C0, V0, sum1,
-                       sq1, C1, V1, rep1, B, groups, eps, gamma, beta, a, d, act_inv_scale);
-    GN_LAUNCH_CHECK("gn_groupnorm_affine");
-    return GN_OK;
-}
-
-// The same affine for any channel count and for channel-padded storage (the UNet stores a layer of c channels as round_up(c, 32): csrc
-// conv kernels need Cout % 32 == 0).  Source k holds Ck REAL channels in rows of Sk >= Ck stored ones ([B][Sk] statistics); the groups
-// are formed over the C0 + C1 real channels (gamma / beta [C0 + C1]); a / d are written in the stored layout [B][S0 + S1], pad channels
-// a = d = 0 (the convolutions then see exact zeros there whatever the pads hold).  Per-channel and per-group tables in dynamic LDS (16 B
-// per channel + 8 B per group: ~6-10k channels in 160 KB).  Same summation order and scale pick as groupnorm_affine_kernel: with no
-// padding and C0 + C1 <= GNA_MAXC the two kernels give the same bits, and a padded layout gives the unpadded layout's bits on its real
-// channels (the pads add nothing to a group sum and their rms is 0).
-__global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_map_kernel(const double *__restrict__ sum0, const double *__restrict__ sq0, int C0, int S0,
-                                        int64_t V0, const double *__restrict__ sum1, const double *__restrict__ sq1, int C1, int S1, int rep1,
-                                        int groups, float eps, const float *__restrict__ gamma, const float *__restrict__ beta, float *__restrict__ a,
-                                        float *__restrict__ d, float *__restrict__ act_inv_scale) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gna_smem[];
-    const int b = blockIdx.x, C = C0 + C1, S = S0 + S1, cpg = C / groups, tid = threadIdx.x;
-    double *ls = reinterpret_cast<double *>(gna_smem), *lq = ls + C;
-    float *grstd = reinterpret_cast<float *>(lq + C), *gmean = grstd + groups, *gmax = gmean + groups;
-    for (int c = tid; c < C; c += GNA_THREADS) {
-        if (c < C0) { ls[c] = sum0[(int64_t)b * S0 + c]; lq[c] = sq0[(int64_t)b * S0 + c]; }
-        else { ls[c] = rep1 * sum1[(int64_t)b * S1 + c - C0]; lq[c] = rep1 * sq1[(int64_t)b * S1 + c - C0]; }
-    }
-    for (int j = tid; j < S; j += GNA_THREADS) {                 // pad channels (stored positions C0..S0-1 and S0+C1..S-1)
-        if ((j >= C0 && j < S0) || j >= S0 + C1) { a[(int64_t)b * S + j] = 0.f; d[(int64_t)b * S + j] = 0.f; }
-    }
-    __syncthreads();
-    for (int g = tid; g < groups; g += GNA_THREADS) {
-        double s = 0.0, q = 0.0;
-        for (int c = g * cpg; c < (g + 1) * cpg; ++c) { s += ls[c]; q += lq[c]; }
-        const double n = (double)cpg * (double)V0;
-        const double mean = s / n;
-        double var = q / n - mean * mean;
-        if (var < 0) var = 0;
-        grstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-        gmean[g] = (float)mean;
-    }
-    __syncthreads();
-    float my_max = 0.f;
-    for (int c = tid; c < C; c += GNA_THREADS) {
-        const int g = c / cpg;
-        const int64_t o = (int64_t)b * S + (c < C0 ? c : S0 + c - C0);
-        const float ga = gamma[c] * grstd[g];
-        const float dd = beta[c] - gmean[g] * ga;
-        a[o] = ga;
-        d[o] = dd;
-        if (act_inv_scale) {
-            const double ex = ls[c] / (double)V0, ex2 = lq[c] / (double)V0;
-            const double ey2 = (double)ga * ga * ex2 + 2.0 * (double)ga * dd * ex + (double)dd * dd;
-            const float rms = ey2 > 0 ? (float)sqrt(ey2) : 0.f;
-            if (rms > my_max) my_max = rms;
-        }
-    }
-    if (!act_inv_scale) return;
-    for (int off = 32; off >= 1; off >>= 1) my_max = fmaxf(my_max, __shfl_xor(my_max, off));
-    if ((tid & 63) == 0) gmax[tid >> 6] = my_max;
-    __syncthreads();
-    const float m = fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));
-    int e = 0;
-    float sc = 1.f, inv = 1.f;
-    if (m > 0.f && m < INFINITY) {
-        (void)frexpf(m, &e);
-        e = 1 - e;
-        if (e > 100) e = 100;
-        if (e < -100) e = -100;
-        sc = ldexpf(1.f, e);
-        inv = ldexpf(1.f, -e);
-    }
-    for (int c = tid; c < C; c += GNA_THREADS) {
+    for (int c = tid; c < C; c += GNA_THREADS) {                 // (each thread rescales what it wrote)
         const int64_t o = (int64_t)b * S + (c < C0 ? c : S0 + c - C0);
         a[o] *= sc;
         d[o] *= sc;
@@ -250,26 +150,51 @@ __global__ __launch_bounds__(GNA_THREADS) void groupnorm_affine_map_kernel(const
     if (tid == 0) act_inv_scale[b] = inv;
 }
 
-#define GNA_MAP_MAX_LDS (160 * 1024)
-static size_t gna_map_lds_bytes(int C, int groups) {
+#define GNA_MAX_LDS (160 * 1024)
+#define GNA_PLAIN_LDS (64 * 1024)       // the dynamic LDS a launch gets without raising the kernel's MaxDynamicSharedMemorySize
+static size_t gna_lds_bytes(int C, int groups) {
     return ((size_t)16 * C + (size_t)8 * groups + 4 * sizeof(float) + 15) & ~(size_t)15;
 }
 
+static int groupnorm_affine_launch(const char *name, const double *sum0, const double *sq0, int C0, int S0, int64_t V0, const double *sum1,
+                                   const double *sq1, int C1, int S1, int rep1, int B, int groups, float eps, const float *gamma,
+                                   const float *beta, float *a, float *d, float *act_inv_scale, void *stream) {
+    if (B == 0) return GN_OK;
+    const size_t lds = gna_lds_bytes(C0 + C1, groups);
+    hipStream_t st = gn_stream(stream);
+    if (lds > GNA_PLAIN_LDS)
+        GN_HIP(hipFuncSetAttribute((const void *)groupnorm_affine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
+    hipLaunchKernelGGL(groupnorm_affine_kernel, dim3((unsigned)B), dim3(GNA_THREADS), lds, st, sum0, sq0, C0, S0, V0, sum1, sq1, C1, S1, rep1, groups,
+                       eps, gamma, beta, a, d, act_inv_scale);
+    GN_LAUNCH_CHECK(name);
+    return GN_OK;
+}
+
+// Unpadded storage (S0 = C0, S1 = C1).  GNA_MAXC is this entry's contract, not an LDS limit: its tables stay under GNA_PLAIN_LDS, so the
+// inference path's once-per-conv-layer call never pays for a function attribute.
+#define GNA_MAXC 1024
+extern "C" int gn_groupnorm_affine(const double *sum0, const double *sq0, int C0, int64_t V0, const double *sum1, const double *sq1,
+                                   int C1, int64_t V1, int rep1, int B, int groups, float eps, const float *gamma,
+                                   const float *beta, float *a, float *d, float *act_inv_scale, void *stream) {
+    GN_REQUIRE(B >= 0 && groups > 0 && C0 > 0 && C1 >= 0 && (C0 + C1) % groups == 0, "gn_groupnorm_affine: bad sizes");
+    GN_REQUIRE(C0 + C1 <= GNA_MAXC, "gn_groupnorm_affine: at most %d channels (got %d)", GNA_MAXC, C0 + C1);
+    GN_REQUIRE(C1 == 0 || V1 * rep1 == V0, "gn_groupnorm_affine: source 1 must cover the same voxels after replication");
+    return groupnorm_affine_launch("gn_groupnorm_affine", sum0, sq0, C0, C0, V0, sum1, sq1, C1, C1, rep1, B, groups, eps, gamma, beta, a, d,
+                                   act_inv_scale, stream);
+}
+
+// Any channel count the LDS tables hold, channel-padded storage.
 extern "C" int gn_groupnorm_affine_map(const double *sum0, const double *sq0, int C0, int S0, int64_t V0, const double *sum1, const double *sq1,
                                        int C1, int S1, int64_t V1, int rep1, int B, int groups, float eps, const float *gamma,
                                        const float *beta, float *a, float *d, float *act_inv_scale, void *stream) {
     GN_REQUIRE(B >= 0 && groups > 0 && C0 > 0 && C1 >= 0 && S0 >= C0 && S1 >= C1 && (C0 + C1) % groups == 0, "gn_groupnorm_affine_map: bad sizes");
     GN_REQUIRE(C1 == 0 || (V1 * rep1 == V0 && rep1 > 0), "gn_groupnorm_affine_map: source 1 must cover the same voxels after replication");
     GN_REQUIRE((int64_t)S0 + S1 <= (int64_t)1 << 30, "gn_groupnorm_affine_map: bad sizes");
-    const size_t lds = gna_map_lds_bytes(C0 + C1, groups);
-    GN_REQUIRE(lds <= GNA_MAP_MAX_LDS, "gn_groupnorm_affine_map: %d channels in %d groups need %zu bytes of LDS (at most %d)", C0 + C1, groups, lds,
-               GNA_MAP_MAX_LDS);
-    if (B == 0) return GN_OK;
-    GN_HIP(hipFuncSetAttribute((const void *)groupnorm_affine_map_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "gn_groupnorm_affine_map");
-    hipLaunchKernelGGL(groupnorm_affine_map_kernel, dim3((unsigned)B), dim3(GNA_THREADS), lds, gn_stream(stream), sum0, sq0, C0, S0, V0, sum1, sq1, C1,
-                       S1, rep1, groups, eps, gamma, beta, a, d, act_inv_scale);
-    GN_LAUNCH_CHECK("gn_groupnorm_affine_map");
-    return GN_OK;
+    const size_t lds = gna_lds_bytes(C0 + C1, groups);
+    GN_REQUIRE(lds <= GNA_MAX_LDS, "gn_groupnorm_affine_map: %d channels in %d groups need %zu bytes of LDS (at most %d)", C0 + C1, groups, lds,
+               GNA_MAX_LDS);
+    return groupnorm_affine_launch("gn_groupnorm_affine_map", sum0, sq0, C0, S0, V0, sum1, sq1, C1, S1, rep1, B, groups, eps, gamma, beta, a, d,
+                                   act_inv_scale, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ conv3d 'gcr'

@@ -90,24 +90,14 @@ def fps(pos, ptr, out_ptr, max_points, m_total, start_idx=None, gap_out=None, ne
     _chk(pos, torch.float32, "pos")
     idx = torch.empty(m_total, dtype=_i32, device=pos.device)
     B = ptr.numel() - 1
+    for t, name in ((gap_out, "gap_out"), (nested_gap, "nested_gap")):
+        if t is not None:
+            _chk(t, torch.float32, name)
+    # more points per example than the LDS-resident kernels hold: running distances in a device workspace
     nbytes = _lib.load().gn_fps_workspace_bytes(B, int(max_points))
-    if nbytes:
-        # more points per example than the LDS-resident kernels hold: running distances in a device workspace (gn_fps_nested_ws)
-        for t, name in ((gap_out, "gap_out"), (nested_gap, "nested_gap")):
-            if t is not None:
-                _chk(t, torch.float32, name)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
-        _lib.call("gn_fps_nested_ws", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), B, int(max_points), _p(idx), _p(gap_out), _p(nested_gap),
-                  _p(ws), nbytes, _stream())
-    elif gap_out is None and nested_gap is None:
-        _lib.call("gn_fps", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), ptr.numel() - 1, int(max_points), _p(idx), _stream())
-    else:
-        if gap_out is not None:
-            _chk(gap_out, torch.float32, "gap_out")
-        if nested_gap is not None:
-            _chk(nested_gap, torch.float32, "nested_gap")
-        _lib.call("gn_fps_nested", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), ptr.numel() - 1, int(max_points), _p(idx), _p(gap_out), _p(nested_gap),
-                  _stream())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pos.device) if nbytes else None
+    _lib.call("gn_fps_nested_ws", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), B, int(max_points), _p(idx), _p(gap_out), _p(nested_gap),
+              _p(ws), nbytes, _stream())
     return idx
 
 
@@ -346,7 +336,7 @@ def groupnorm_affine(st0, st1, groups, eps, gamma, beta, with_act_scale=False, r
     return (a, d, inv) if with_act_scale else (a, d)
 
 
-GNA_MAXC = 1024        # gn_groupnorm_affine's channel limit (static LDS tables); gn_groupnorm_affine_map sizes its tables from C
+GNA_MAXC = 1024        # gn_groupnorm_affine's channel limit; gn_groupnorm_affine_map takes what fits 160 KB of LDS
 
 
 def pack_conv_weight(w):

@@ -202,7 +202,7 @@ int gn_grid_stats(const float *vol, const int32_t *flat_idx, int64_t N, int C, i
  * First half of nn.GroupNorm -- components/unet3d.py:66. */
 int gn_channel_stats(const float *x, int B, int64_t V, int C, double *sum, double *sumsq, void *stream);
 
-/* gn_channel_stats for any C % 4 == 0 (gn_channel_stats: C divides 256 or is a multiple of it -- the counts it takes run its code). */
+/* gn_channel_stats for any C % 4 == 0 (gn_channel_stats: C divides 256 or is a multiple of it).  One kernel serves both entries. */
 int gn_channel_stats_any(const float *x, int B, int64_t V, int C, double *sum, double *sumsq, void *stream);
 
 /* GroupNorm statistics -> per-(sample, channel) affine  y = x*a + d  for the concatenation of up to two
@@ -218,7 +218,7 @@ int gn_groupnorm_affine(const double *sum0, const double *sq0, int C0, int64_t V
 /* gn_groupnorm_affine for any channel count (up to the 160 KB of LDS a workgroup has: 16 B per channel + 8 B per group) and for
  * channel-padded storage: source k holds Ck real channels in rows of Sk >= Ck stored ones (sum / sq [B][Sk]); the groups are formed over
  * the C0 + C1 real channels (gamma / beta [C0 + C1]); a, d [B][S0 + S1] in the stored layout with a = d = 0 on the pad channels.
- * Same summation order and sample scale as gn_groupnorm_affine: with S0 == C0, S1 == C1 and C0 + C1 <= 1024 the same bits, and
+ * gn_groupnorm_affine is this call with S0 == C0, S1 == C1 and its own limit of 1024 channels: one kernel serves both, and
  * padded storage gives the unpadded bits on the real channels. */
 int gn_groupnorm_affine_map(const double *sum0, const double *sq0, int C0, int S0, int64_t V0, const double *sum1, const double *sq1,
                             int C1, int S1, int64_t V1, int rep1, int B, int groups, float eps, const float *gamma,

@@ -69,9 +69,10 @@ def test_fps_past_the_lds_limit_bit_exact(sizes, ratio):
     assert np.array_equal(got, ref)
 
 
-def test_fps_past_the_lds_limit_ties_keep_the_lowest_index():
-    """40 000 points on a coarse integer lattice: exact ties of the running distance inside a thread, a wave and across waves"""
-    n = 40000
+@pytest.mark.parametrize("n", [40000, 17000])
+def test_fps_large_cloud_ties_keep_the_lowest_index(n):
+    """n points on a coarse integer lattice: exact ties of the running distance inside a thread, a wave and across waves; running distances in the
+    workspace (40 000) and in LDS (17 000)"""
     g = torch.Generator().manual_seed(11)
     pos = torch.randint(0, 9, (n, 3), generator=g).float() * 0.125
     ref, _ = O.fps(pos.numpy(), np.array([0, n], np.int64), 0.25)
@@ -79,19 +80,19 @@ def test_fps_past_the_lds_limit_ties_keep_the_lowest_index():
     assert np.array_equal(got, ref)
 
 
-def test_fps_past_the_lds_limit_start_index():
-    sizes = [40000, 37000]
+@pytest.mark.parametrize("sizes,starts", [([40000, 37000], [12345, 36999]), ([17000, 16385], [12345, 16384])])
+def test_fps_large_cloud_start_index(sizes, starts):
     _, pos, _ = _ragged_cloud(sizes, 8)
     ratio = 0.02
     m = [ops.fps_count(n, ratio) for n in sizes]
     # the restatement is the oracle's loop: held to it from the first point
     ref0, _ = O.fps(pos[:sizes[0]].numpy(), np.array([0, sizes[0]], np.int64), ratio)
     assert np.array_equal(_fps_np(pos[:sizes[0]].numpy(), 0, m[0]), ref0)
-    start = torch.tensor([12345, 36999], dtype=torch.int32, device=DEV)
+    start = torch.tensor(starts, dtype=torch.int32, device=DEV)
     got, _ = _fps_gpu(pos, sizes, ratio, start)
     off = 0
     for b, n in enumerate(sizes):
-        want = _fps_np(pos[off:off + n].numpy(), int(start[b]), m[b]) + off
+        want = _fps_np(pos[off:off + n].numpy(), starts[b], m[b]) + off
         assert np.array_equal(got[sum(m[:b]):sum(m[:b + 1])], want), ("example", b)
         off += n
 

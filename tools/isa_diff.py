@@ -5,7 +5,7 @@
 
 Every .hip file of both directories is compiled to device assembly with the Makefile's flags (the directories must sit two levels below
 an include/ folder, as garmentnets_amd/csrc does).  A kernel is the text between its `_Z...:` label and the next one; comment lines and
-.file/.ident/.loc lines are ignored.  Prints one line per kernel that differs (instruction counts and the five resource values of its
+.file/.ident/.loc lines are ignored, and so is the function number in local labels (.LBB12_3: adding or removing a kernel renumbers those below it).  Prints one line per kernel that differs (instruction counts and the five resource values of its
 metadata, old -> new) and a summary; the exit status is 1 when any kernel differs, was added or was removed.  For a kernel with matrix
 instructions the line also says whether the two streams are equal up to and including the kernel's last v_mfma: "main loop equal" means that
 only the epilogue behind it was re-scheduled, "main loop DIFFERS" that the change reached the loop itself.
@@ -36,7 +36,7 @@ def kernels(path):
         elif s.startswith(".type") or s.startswith(".section"):  # the next symbol, or the end of the text
             cur = None
         elif cur and s and not re.match(r"\.(file|ident|loc)\b", s):
-            body[cur].append(s)
+            body[cur].append(re.sub(r"\.L([A-Za-z]+)\d+_", r".L\1_", s))  # local labels carry the function's number within its file
     res = {}
     for blk in re.split(r"\n  - \.agpr_count:", text)[1:]:
         blk = ".agpr_count:" + blk
