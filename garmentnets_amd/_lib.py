@@ -161,6 +161,11 @@ PROTOTYPES = {
     "gn_depth_cloud_offsets": [_vp, _i32, _i32, _vp, _vp, _vp],
     "gn_depth_cloud_write": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
     "gn_cloth_simulate_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp],
+    "gn_cloth_contact_buckets": [_i32],
+    "gn_cloth_contact_workspace_bytes": [_i64, _i32, _i32],
+    "gn_cloth_contact_lists": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_cloth_simulate_contacts_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                         _i32, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -169,7 +174,7 @@ _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes
              "gn_trilinear_sample_bwd_workspace_bytes": _sz, "gn_conv3d_bwd_weight_workspace_bytes": _sz, "gn_conv3d_bwd_weight_split_workspace_bytes": _sz, "gn_relu_mask_max_workspace_bytes": _sz, "gn_groupnorm_bwd_stats_workspace_bytes": _sz,
              "gn_linear_act_bwd_workspace_bytes": _sz, "gn_linear_bwd_weight_workspace_bytes": _sz,
              "gn_col_moments_workspace_bytes": _sz, "gn_col_dots_workspace_bytes": _sz, "gn_bn_train_bwd_workspace_bytes": _sz,
-             "gn_query_targets_workspace_bytes": _sz}
+             "gn_query_targets_workspace_bytes": _sz, "gn_cloth_contact_workspace_bytes": _sz}
 
 LINEAR_BWD_CHUNK_ROWS = 512                     # GN_LINEAR_BWD_CHUNK_ROWS
 LINEAR_ACT_CHUNK_ROWS = 1024                    # GN_LINEAR_ACT_CHUNK_ROWS (gn_linear_act_bwd, gn_col_moments, gn_col_dots, gn_bn_train_bwd)
@@ -234,6 +239,8 @@ class ResidentStore(ctypes.Structure):
 
 CLOTH_MAX_LDS = 160 * 1024                      # CL_MAX_LDS
 CLOTH_MAX_BLOCK = 1024                          # CL_MAX_BLOCK
+CLOTH_MAX_LIST = 64                             # CL_MAX_LIST
+CLOTH_LISTS_TRAVEL, CLOTH_LISTS_BUILD = 1, 2    # CL_LISTS_*: the flags of gn_cloth_contact_lists
 
 RENDER_MAX_SIZE = 4096                          # GN_RENDER_MAX_SIZE
 RENDER_MAX_OVERLAYS = 3                         # GN_RENDER_MAX_OVERLAYS

@@ -24,8 +24,33 @@ rounded on its own (numpy never contracts to fma; the kernel uses _rn intrinsics
                (one projection sweep per substep and the multipliers reset every substep, so none is stored; no two constraints of a colour share a
                vertex, so the order inside a colour cannot matter and a colour is one vectorised numpy statement)
 
-NOT modelled: self-collision, collision with anything else, aerodynamic forces, strain limiting, dihedral bending, a random start orientation, moving
-grippers.  The result is a hanging garment that may pass through itself.
+Self-collision (OFF by default: collision_thickness = 0, and then every array, attribute and bit is what it is without this section).  Vertex-vertex
+contacts found through contact lists that are rebuilt every few substeps, applied by a Jacobi gather once a substep:
+
+  parameters   collision_thickness t (metres; 0: off), collision_margin (> 0 when on), collision_rebuild R (substeps, >= 1), collision_max_list K
+               (in [1, 64]), collision_relax (in (0, 1])
+  constants    t2 = t * t, r = t + margin, r2 = r * r: computed ONCE on the host (collision_constants), kept in Garment.collision, read by both sides
+  pair         sq(a, b) = (dx*dx + dy*dy) + dz*dz of d = a - b;  rest2_ij = sq(x0_i, x0_j) on the garment's START POSE Garment.x0 (not the state a call
+               starts from);  tm2_ij = min(t2, rest2_ij): vertices closer than t at rest are only kept from coming closer than they were, so mesh
+               neighbours need no exclusion rule and t may exceed an edge length
+  contact list of vertex i at a rebuild, from the positions x at the start of that substep: all j != i with sq(x_i, x_j) <= r2 and tm2_ij > 0, in
+               ascending j, cut to the first K; an entry is (j, tm2_ij); the entries cut off are counted as overflow.  Every vertex has a list, those
+               with w = 0 too (they are read only as partners).  Rebuilds happen at the substeps s of a call with s % R == 0, s counted from the call's
+               first substep: a run split into calls equals one call only when every call but the last is a multiple of R long.  The list is DEFINED
+               by brute force over all pairs (contact_lists_reference); a search structure must return exactly this set
+  contact pass once a substep, after the last colour and before the velocity pass, on the positions p as the sweep left them.  For every i with
+               w_i > 0:  corr = (0, 0, 0);  for each entry in list order:  d = p_i - p_j;  d2 = sq;  active iff d2 < tm2 and d2 > 0 (both strict);
+               active:  len = sqrt(d2);  tmin = sqrt(tm2);  s = w_i + w_j;  dl = (tmin - len) / s;  n = d / len;  corr += (w_i * dl) * n (per
+               component).  When all vertices have read:  p_i = p_i + relax * corr.  One writer per position, no atomics, an order fixed by the list.
+               A garment at rest has no active entry (d2 == rest2 >= tm2), so without gravity nothing moves, to the bit
+  diagnostics  per garment and call: contact_overflow (the sum of overflow over the rebuilds), contact_max_list (the longest uncut list),
+               contact_travel (the largest, over rebuild intervals and vertices, of sqrt(sq(x_i, x_i at the last rebuild)) / (margin / 2), taken at every
+               rebuild after the first and at the end of the call: above 1 a contact may have been missed), contact_active (active entries summed over
+               the substeps)
+
+NOT modelled: vertex-face and edge-edge contacts, continuous collision detection, friction, collision with anything else, aerodynamic forces, strain
+limiting, dihedral bending, a random start orientation, moving grippers.  With contacts off the result is a hanging garment that may pass through
+itself; with them on, its vertices keep their distance but a vertex can still pass through the middle of a face larger than the thickness.
 """
 import dataclasses
 import hashlib
@@ -40,6 +65,14 @@ DEFAULT_DAMPING = 4.0                  # 1 / s: v *= 1 - h * damping every subst
 DEFAULT_ALPHA_STRETCH = 0.0            # m / N: as stiff as the substep count makes it
 DEFAULT_ALPHA_BEND = 0.1               # m / N
 DEFAULT_DENSITY = 0.2                  # kg / m^2
+# self-collision, used by `simulate --self_collision` only (ClothParams has contacts off by default)
+DEFAULT_COLLISION_THICKNESS_FACTOR = 1.5     # thickness = factor * the mean stretch rest length of the garment (mean_stretch_rest_length)
+DEFAULT_COLLISION_MARGIN_FACTOR = 1.0        # margin = factor * thickness
+DEFAULT_COLLISION_REBUILD = 4                # substeps between two list builds
+DEFAULT_COLLISION_MAX_LIST = 64
+DEFAULT_COLLISION_RELAX = 1.0
+COLLISION_MAX_LIST_CAP = 64                  # CL_MAX_LIST of csrc/cloth.hip
+COLLISION_FIELDS = ("collision_thickness", "collision_margin", "collision_rebuild", "collision_max_list", "collision_relax")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -50,6 +83,11 @@ class ClothParams:
     alpha_stretch: float = DEFAULT_ALPHA_STRETCH
     alpha_bend: float = DEFAULT_ALPHA_BEND
     density: float = DEFAULT_DENSITY
+    collision_thickness: float = 0.0       # metres; 0: no contacts
+    collision_margin: float = 0.0          # metres; > 0 when contacts are on
+    collision_rebuild: int = 1             # substeps between two list builds
+    collision_max_list: int = DEFAULT_COLLISION_MAX_LIST
+    collision_relax: float = DEFAULT_COLLISION_RELAX
 
     def __post_init__(self):
         vals = dataclasses.asdict(self)
@@ -57,6 +95,20 @@ class ClothParams:
             raise ValueError(f"cloth parameters must be finite, got {vals}")
         if not self.h > 0 or not self.density > 0 or self.damping < 0 or self.alpha_stretch < 0 or self.alpha_bend < 0:
             raise ValueError(f"cloth parameters: h and density must be positive, damping and the compliances not negative, got {vals}")
+        if self.collision_thickness < 0 or self.collision_margin < 0:
+            raise ValueError(f"cloth parameters: collision_thickness and collision_margin must not be negative, got {vals}")
+        if self.collision_thickness > 0 and not self.collision_margin > 0:
+            raise ValueError(f"cloth parameters: collision_margin must be positive when collision_thickness is, got {vals}")
+        if int(self.collision_rebuild) != self.collision_rebuild or self.collision_rebuild < 1:
+            raise ValueError(f"cloth parameters: collision_rebuild must be a whole number >= 1, got {self.collision_rebuild}")
+        if int(self.collision_max_list) != self.collision_max_list or not 1 <= self.collision_max_list <= COLLISION_MAX_LIST_CAP:
+            raise ValueError(f"cloth parameters: collision_max_list must be a whole number in [1, {COLLISION_MAX_LIST_CAP}], got {self.collision_max_list}")
+        if not 0 < self.collision_relax <= 1:
+            raise ValueError(f"cloth parameters: collision_relax must lie in (0, 1], got {self.collision_relax}")
+
+    @property
+    def contacts(self):
+        return self.collision_thickness > 0
 
 
 def step_constants(params):
@@ -66,6 +118,16 @@ def step_constants(params):
     return {"h": float(h), "inv_h": float(np.float64(1.0) / h), "hg": [float(c) for c in h * g],
             "damp": float(max(np.float64(0.0), np.float64(1.0) - h * np.float64(params.damping))),
             "alpha_t_stretch": float(np.float64(params.alpha_stretch) / (h * h)), "alpha_t_bend": float(np.float64(params.alpha_bend) / (h * h))}
+
+
+def collision_constants(params):
+    """the contact numbers both sides read -> None with contacts off, else a dict: t2, r, r2, half_margin, relax (python floats, fp64), K, R (ints)"""
+    if not params.contacts:
+        return None
+    t, m = np.float64(params.collision_thickness), np.float64(params.collision_margin)
+    r = t + m
+    return {"t2": float(t * t), "r": float(r), "r2": float(r * r), "half_margin": float(m / np.float64(2.0)), "relax": float(params.collision_relax),
+            "K": int(params.collision_max_list), "R": int(params.collision_rebuild)}
 
 
 def substeps_of(duration, h):
@@ -182,6 +244,7 @@ class Garment:
     n_stretch: int
     n_bend: int
     bad_index: bool              # a face names a vertex outside [0, V): only a garment built with check=False carries one
+    collision: dict = None       # collision_constants: None with contacts off
 
 
 def garment(X, faces, grip, params, check=True):
@@ -219,7 +282,8 @@ def garment(X, faces, grip, params, check=True):
     ij = np.clip(topo.pairs, 0, V - 1)
     l0 = _norm3(x0[ij[:, 0]] - x0[ij[:, 1]]) if len(ij) else np.zeros(0)      # measured in the start pose, as the sweep measures len
     alpha_t = np.where(topo.is_bend, consts["alpha_t_bend"], consts["alpha_t_stretch"]).astype(np.float64)
-    return Garment(x0, w, topo.pairs, topo.is_bend, l0, alpha_t, topo.colour_off, consts, grip, n_massless, topo.n_stretch, topo.n_bend, bad)
+    return Garment(x0, w, topo.pairs, topo.is_bend, l0, alpha_t, topo.colour_off, consts, grip, n_massless, topo.n_stretch, topo.n_bend, bad,
+                   collision_constants(params))
 
 
 def garment_from_nocs(nocs_verts, faces, grip, rest_scale, params, check=True):
@@ -255,8 +319,77 @@ def project_colour(p, w, i, j, l0, alpha_t):
     p[j[act]] = new_j[act]
 
 
-def substep(g, x, v):
-    """one substep of the definition, in place on x and v"""
+def _sq3(d):
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def contact_lists_reference(g, x, chunk=256):
+    """the contact lists of the definition for the positions x, by brute force over all pairs (`chunk` rows at a time, so V x V is never held at once)
+    -> ((idx (V, K) int32, tm2 (V, K) float64), counts (V,) int64, overflow (V,) int64): row i holds its first counts[i] entries in ascending j, the
+    rest of the row is (-1, 0); overflow[i] entries were cut off, so counts + overflow is the uncut length"""
+    c = g.collision
+    if c is None:
+        raise ValueError("contact_lists_reference: the garment has contacts off (collision_thickness = 0)")
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape != g.x0.shape:
+        raise ValueError(f"contact_lists_reference: x must be {g.x0.shape}, got {x.shape}")
+    V, K = len(x), c["K"]
+    t2, r2 = np.float64(c["t2"]), np.float64(c["r2"])
+    idx = np.full((V, K), -1, dtype=np.int32)
+    tm2 = np.zeros((V, K), dtype=np.float64)
+    counts = np.zeros(V, dtype=np.int64)
+    overflow = np.zeros(V, dtype=np.int64)
+    cols = np.arange(V)
+    for a in range(0, V, int(chunk)):
+        rows = np.arange(a, min(a + int(chunk), V))
+        rest2 = _sq3(g.x0[rows, None, :] - g.x0[None, :, :])
+        near = (_sq3(x[rows, None, :] - x[None, :, :]) <= r2) & (np.minimum(t2, rest2) > 0) & (rows[:, None] != cols[None, :])
+        rank = np.cumsum(near, axis=1) - 1                    # the place of j among the row's partners, ascending j
+        total = near.sum(axis=1)
+        n, j = np.nonzero(near & (rank < K))
+        idx[rows[n], rank[n, j]] = j
+        tm2[rows[n], rank[n, j]] = np.minimum(t2, rest2[n, j])
+        counts[rows] = np.minimum(total, K)
+        overflow[rows] = total - counts[rows]
+    return (idx, tm2), counts, overflow
+
+
+def contact_entries(g, lists, counts):
+    """the list entries the contact pass reads, flat and in its order (vertex by vertex, list order inside a vertex), of the vertices with w > 0
+    -> (i, j, tm2)"""
+    idx, tm2 = lists
+    keep = (np.arange(idx.shape[1])[None, :] < np.asarray(counts)[:, None]) & (g.w > 0)[:, None]
+    i, k = np.nonzero(keep)                                   # row-major: the order of the definition
+    return i, idx[i, k].astype(np.int64), tm2[i, k]
+
+
+def contact_pass(p, w, entries, relax):
+    """the contact pass of the definition, in place on p -> the number of active entries"""
+    i, j, tm2 = entries
+    d = p[i] - p[j]
+    d2 = _sq3(d)
+    act = (d2 < tm2) & (d2 > 0)
+    i, j, d, d2, tm2 = i[act], j[act], d[act], d2[act], tm2[act]
+    length = np.sqrt(d2)
+    wi = w[i]
+    dl = (np.sqrt(tm2) - length) / (wi + w[j])
+    n = d / length[:, None]
+    corr = np.zeros_like(p)
+    np.add.at(corr, i, (wi * dl)[:, None] * n)                # unbuffered: entry after entry, so list order inside a vertex
+    live = w > 0
+    p[live] = p[live] + np.float64(relax) * corr[live]
+    return int(act.sum())
+
+
+def contact_travel(g, x, x_ref):
+    """sqrt(the largest sq(x_i, x_ref_i)) / (margin / 2): sqrt and the division are monotone, so this is the largest of the definition's quotients"""
+    if len(x) == 0:
+        return 0.0
+    return float(np.sqrt(_sq3(x - x_ref).max()) / np.float64(g.collision["half_margin"]))
+
+
+def substep(g, x, v, entries=None):
+    """one substep of the definition, in place on x and v; entries: contact_entries of the current lists (None: no contact pass) -> active entries"""
     c = g.consts
     h, inv_h, damp, hg = np.float64(c["h"]), np.float64(c["inv_h"]), np.float64(c["damp"]), np.array(c["hg"], dtype=np.float64)
     live = g.w > 0
@@ -268,18 +401,50 @@ def substep(g, x, v):
     for k in range(len(off) - 1):
         sl = slice(off[k], off[k + 1])
         project_colour(p, g.w, g.pairs[sl, 0], g.pairs[sl, 1], g.l0[sl], g.alpha_t[sl])
+    active = 0 if entries is None else contact_pass(p, g.w, entries, g.collision["relax"])
     v[live] = (p[live] - x_prev[live]) * inv_h
     x[live] = p[live]
+    return active
 
 
-def simulate_reference(g, substeps, x=None, v=None):
-    """`substeps` substeps from (x, v) (None: the start pose at rest) -> (x, v) float64 (V, 3), new arrays"""
+CONTACT_STATS = ("contact_overflow", "contact_max_list", "contact_travel", "contact_active")
+
+
+def simulate_reference(g, substeps, x=None, v=None, stats=False, observe=None):
+    """`substeps` substeps from (x, v) (None: the start pose at rest) -> (x, v) float64 (V, 3), new arrays; stats=True: (x, v, the contact diagnostics
+    of the definition as a dict, all 0 with contacts off).  With contacts on the lists are rebuilt at the substeps s with s % R == 0.  observe: called
+    as observe(s, x, v) after every substep s (the arrays are the run's own: read, do not write)."""
     if g.bad_index:
         raise IndexError("cloth: a face index is out of bounds for its mesh's vertices")
     x, v = state_arrays(g, x, v, "simulate_reference")
-    for _ in range(int(substeps)):
-        substep(g, x, v)
-    return x, v
+    out = {"contact_overflow": 0, "contact_max_list": 0, "contact_travel": 0.0, "contact_active": 0}
+    if g.collision is None:
+        for s in range(int(substeps)):
+            substep(g, x, v)
+            if observe is not None:
+                observe(s, x, v)
+        return (x, v, out) if stats else (x, v)
+    entries = x_ref = None
+    for s in range(int(substeps)):
+        if s % g.collision["R"] == 0:
+            if x_ref is not None:
+                out["contact_travel"] = max(out["contact_travel"], contact_travel(g, x, x_ref))
+            lists, counts, overflow = contact_lists_reference(g, x)
+            out["contact_overflow"] += int(overflow.sum())
+            out["contact_max_list"] = max(out["contact_max_list"], int((counts + overflow).max(initial=0)))
+            entries, x_ref = contact_entries(g, lists, counts), x.copy()
+        out["contact_active"] += substep(g, x, v, entries)
+        if observe is not None:
+            observe(s, x, v)
+    if x_ref is not None:
+        out["contact_travel"] = max(out["contact_travel"], contact_travel(g, x, x_ref))
+    return (x, v, out) if stats else (x, v)
+
+
+def mean_stretch_rest_length(g):
+    """the mean rest length of the stretch constraints: (sum of l0 over them) / their number, 0 for a garment without one"""
+    stretch = ~g.is_bend
+    return float(g.l0[stretch].sum() / stretch.sum()) if stretch.any() else 0.0
 
 
 # ------------------------------------------------------------------------------------------------ diagnostics

@@ -1,22 +1,38 @@
 // cloth.hip -- the hanging garment: small-step XPBD over point masses and distance constraints, fp64, no fma: mesh/cloth_verts built on the device.
 //
-//   gn_cloth_simulate_batch   B ragged garments, `substeps` substeps each, in launches of at most max_substeps_per_launch
+//   gn_cloth_simulate_batch            B ragged garments, `substeps` substeps each, in launches of at most max_substeps_per_launch
+//   gn_cloth_contact_lists             the vertex-vertex contact lists of B garments through a hashed uniform grid (and contact_travel)
+//   gn_cloth_simulate_contacts_batch   gn_cloth_simulate_batch with the contact pass of those lists after the last colour
 //
 // The definition is garmentnets_amd/cloth.py's ("Hanging garments"); cloth_substeps below is its substep, operation for operation: the
 // library is built with -ffp-contract=off and every operation is an explicit _rn intrinsic, so x and v are the bits of cloth.simulate_reference.
 //
 // Shape: ONE workgroup owns ONE garment for the whole launch, so nothing is ever handed to another workgroup and there is no device-scope
-// synchronisation.  A thread owns the vertices tid, tid + T, ... in the two per-vertex passes and the constraints c0 + tid, c0 + tid + T, ... of a
+// synchronisation.  A thread owns the vertices tid, tid + T, ... in the per-vertex passes and the constraints c0 + tid, c0 + tid + T, ... of a
 // colour.  No two constraints of a colour share a vertex (the host's colouring), so inside a colour every position has one reader-writer: no atomics,
 // and which thread projects which constraint cannot change a bit.  Barriers: one after the prediction pass and one after every colour; every thread
 // reaches every one of them -- each loop bound is a launch argument or a table entry that the whole workgroup reads alike, and nothing returns early.
 // (The velocity pass of a substep and the prediction pass of the next touch only the thread's own vertices: no barrier between them.)
+//
+// Contacts (cloth_substeps<true>): after the last colour's barrier a thread gathers, for its own vertices, the corrections of its list entries from
+// the positions the sweep left (reads of any vertex, a write to the thread's own row of the corr workspace only), ONE more barrier says "all reads
+// done", and the thread adds relax * corr to its own vertices.  The velocity pass that follows reads only what the same thread wrote, and the next
+// reader of a foreign position is the next substep's first colour, behind the prediction pass's barrier: the second barrier the plan allowed for
+// ("writes done") is that one.  A Jacobi gather: one writer per position, no atomics, the order of the additions fixed by the list.
+//
+// Contact lists (cl_contact_* below): many workgroups per garment; a uniform grid of cells of edge `cell` (a little above r) hashed into `buckets`
+// buckets per garment, filled by count, scan, fill (a thread per vertex); the query (a wave per vertex) scans the 27 neighbouring cells, keeps the
+// candidates that really lie in the scanned cell (so two cells that share a bucket only cost time), applies the predicate of the definition and
+// places every partner by its rank among those found.  The result is the brute-force set of cloth.contact_lists_reference: DESIGN.md argues the
+// cell edge.
 //
 // Storage: the working positions p of a garment live in LDS when 24 V bytes fit the launch's dynamic LDS (the wrapper's budget), otherwise in the
 // garment's rows of x in global memory (L2-resident at these sizes; the waves of a workgroup share their CU's L1, and __syncthreads() is the
 // workgroup-scope release / acquire between a colour's stores and the next colour's loads).  x_prev needs no storage of its own: v is dead between the
 // prediction pass and the velocity pass, so its rows hold x_prev meanwhile.  Both paths run the same cloth_substeps and give the same bits, as does
 // every workgroup size: the result is a pure function of (garment, constants, substeps).
+#include <type_traits>
+
 #include "common.h"
 
 #define CL_MAX_BLOCK 1024
@@ -34,11 +50,47 @@ struct ClothArgs {
     int substeps, lds_bytes;
 };
 
-// P: the working positions of the garment (LDS or global), vb: its rows of v.  Called by the whole workgroup (it holds barriers).
+#define CL_MAX_LIST 64                      // the longest contact list a vertex can have (cloth.COLLISION_MAX_LIST_CAP)
+#define CL_GATHER 8                         // list entries the contact pass fetches at a time
+#define CL_DIAG 4                           // int64 per garment: {contact_overflow, contact_max_list, contact_active, bits of the largest travel^2}
+
+// what the contact pass reads beside ClothArgs: the lists of gn_cloth_contact_lists
+struct ClothArgsContacts : ClothArgs {
+    const int32_t *list_j;                  // [*][K] partner indices relative to the garment's first vertex, ascending
+    const double *list_tm2;                 // [*][K] min(t2, rest2) of the entry
+    const int32_t *list_n;                  // [*] entries of the row
+    double *corr;                           // [*][3] workspace: a vertex's correction between the gather and its application
+    int64_t *diag;                          // [B][CL_DIAG]
+    double relax;
+    int K;
+};
+template <bool CONTACTS>
+using ClothArgsOf = std::conditional_t<CONTACTS, ClothArgsContacts, ClothArgs>;
+
+__device__ __forceinline__ double cl_sq(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+__device__ __forceinline__ long long cl_wave_sum(long long v) {
+    for (int m = GN_WAVE / 2; m; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ unsigned long long cl_wave_max(unsigned long long v) {
+    for (int m = GN_WAVE / 2; m; m >>= 1) {
+        const unsigned long long o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// P: the working positions of the garment (LDS or global), vb: its rows of v.  Called by the whole workgroup (it holds barriers).  CONTACTS: v_off is
+// the garment's first row of the lists and of corr, diag its CL_DIAG counters.
+template <bool CONTACTS>
 __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const double *__restrict__ w, const int32_t *__restrict__ ij,
                                                const double *__restrict__ l0, const double *__restrict__ at, const int64_t *__restrict__ coff, int ncol,
-                                               int V, const ClothArgs &a) {
+                                               int V, const ClothArgsOf<CONTACTS> &a, int64_t v_off = 0, int64_t *diag = nullptr) {
     const int T = blockDim.x;
+    long long active = 0;
     for (int s = 0; s < a.substeps; ++s) {
         for (int i = threadIdx.x; i < V; i += T) {
             if (!(w[i] > 0.0)) continue;                     // held or massless: stays where it is
@@ -70,6 +122,56 @@ __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const doub
             }
             __syncthreads();
         }
+        if constexpr (CONTACTS) {
+            const int32_t *lj = a.list_j + v_off * a.K, *ln = a.list_n + v_off;
+            const double *lt = a.list_tm2 + v_off * a.K;
+            double *corr = a.corr + 3 * v_off;
+            for (int i = threadIdx.x; i < V; i += T) {       // gather: reads any vertex, writes the thread's own rows of corr
+                const double wi = w[i];
+                if (!(wi > 0.0)) continue;
+                const double *p = P + 3 * (int64_t)i;
+                const double px = p[0], py = p[1], pz = p[2];
+                int n = ln[i];
+                n = n < 0 ? 0 : (n > a.K ? a.K : n);
+                double cx = 0.0, cy = 0.0, cz = 0.0;
+                for (int k0 = 0; k0 < n; k0 += CL_GATHER) {  // CL_GATHER entries fetched together: a row is read in a few round trips, not n
+                    int32_t js[CL_GATHER];
+                    double ts[CL_GATHER];
+#pragma unroll
+                    for (int u = 0; u < CL_GATHER; ++u) {
+                        const int k = min(k0 + u, n - 1);
+                        js[u] = lj[(int64_t)i * a.K + k]; ts[u] = lt[(int64_t)i * a.K + k];
+                    }
+#pragma unroll
+                    for (int u = 0; u < CL_GATHER; ++u) {      // in list order
+                        if (k0 + u >= n) break;
+                        const int32_t j = js[u];
+                        if (j < 0 || j >= V) { *a.bad = 1; continue; }                         // flagged, never dereferenced
+                        const double *q = P + 3 * (int64_t)j;
+                        const double dx = __dsub_rn(px, q[0]), dy = __dsub_rn(py, q[1]), dz = __dsub_rn(pz, q[2]);
+                        const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+                        const double tm2 = ts[u];
+                        if (!(d2 < tm2 && d2 > 0.0)) continue;
+                        const double len = __dsqrt_rn(d2), tmin = __dsqrt_rn(tm2);
+                        const double dl = __ddiv_rn(__dsub_rn(tmin, len), __dadd_rn(wi, w[j]));
+                        const double ai = __dmul_rn(wi, dl);
+                        cx = __dadd_rn(cx, __dmul_rn(ai, __ddiv_rn(dx, len)));
+                        cy = __dadd_rn(cy, __dmul_rn(ai, __ddiv_rn(dy, len)));
+                        cz = __dadd_rn(cz, __dmul_rn(ai, __ddiv_rn(dz, len)));
+                        ++active;
+                    }
+                }
+                corr[3 * (int64_t)i] = cx; corr[3 * (int64_t)i + 1] = cy; corr[3 * (int64_t)i + 2] = cz;
+            }
+            __syncthreads();                                 // all reads done
+            for (int i = threadIdx.x; i < V; i += T) {
+                if (!(w[i] > 0.0)) continue;
+                double *p = P + 3 * (int64_t)i;
+                const double *c = corr + 3 * (int64_t)i;
+                p[0] = __dadd_rn(p[0], __dmul_rn(a.relax, c[0])); p[1] = __dadd_rn(p[1], __dmul_rn(a.relax, c[1]));
+                p[2] = __dadd_rn(p[2], __dmul_rn(a.relax, c[2]));
+            }
+        }
         for (int i = threadIdx.x; i < V; i += T) {
             if (!(w[i] > 0.0)) continue;
             const double *p = P + 3 * (int64_t)i;
@@ -78,9 +180,14 @@ __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const doub
             q[2] = __dmul_rn(__dsub_rn(p[2], q[2]), a.inv_h);
         }
     }
+    if constexpr (CONTACTS) {
+        active = cl_wave_sum(active);                        // every lane is here: nothing above returns
+        if ((threadIdx.x & (GN_WAVE - 1)) == 0 && active) atomicAdd((unsigned long long *)(diag + 2), (unsigned long long)active);
+    }
 }
 
-__global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(ClothArgs a) {
+template <bool CONTACTS>
+__global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(ClothArgsOf<CONTACTS> a) {
     extern __shared__ __attribute__((aligned(16))) double cl_pos[];
     const int64_t *m = a.csr + 3 * (int64_t)blockIdx.x;
     const int64_t v_off = m[0], c_off = m[1], k_off = m[2];
@@ -90,52 +197,327 @@ __global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(Clot
     const int64_t *coff = a.colour_off + k_off;
     double *xb = a.x + 3 * v_off, *vb = a.v + 3 * v_off;
     const double *w = a.w + v_off;
+    int64_t *diag = nullptr;
+    if constexpr (CONTACTS) diag = a.diag + CL_DIAG * (int64_t)blockIdx.x;
     // every index of the table is checked whatever the substep count: the wrapper raises on the flag
     for (int64_t c = threadIdx.x; c < 2 * C; c += blockDim.x)
         if (ij[c] < 0 || ij[c] >= V) *a.bad = 1;
     if ((int64_t)V * 24 <= (int64_t)a.lds_bytes) {           // workgroup-uniform: V and lds_bytes are the same for every thread
         for (int i = threadIdx.x; i < 3 * V; i += blockDim.x) cl_pos[i] = xb[i];
         __syncthreads();
-        cloth_substeps(cl_pos, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a);
+        cloth_substeps<CONTACTS>(cl_pos, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag);
         __syncthreads();
         for (int i = threadIdx.x; i < 3 * V; i += blockDim.x) xb[i] = cl_pos[i];
     } else {
-        cloth_substeps(xb, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a);
+        cloth_substeps<CONTACTS>(xb, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag);
     }
+}
+
+// the checks and launches both solver entries share; `name` is the entry's for the messages
+template <bool CONTACTS>
+static int cloth_launch(const char *name, ClothArgsOf<CONTACTS> &a, int B, int64_t total_verts, int64_t total_constraints, int64_t substeps,
+                        int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block, void *stream) {
+    GN_REQUIRE(B >= 0 && B <= 65535, "%s: B=%d outside [0, 65535]", name, B);
+    GN_REQUIRE(total_verts >= 0 && total_verts < INT32_MAX && total_constraints >= 0 && total_constraints < INT32_MAX,
+               "%s: %lld vertices, %lld constraints: each table must stay below 2^31 rows", name, (long long)total_verts, (long long)total_constraints);
+    GN_REQUIRE(substeps >= 0 && max_substeps_per_launch >= 1, "%s: substeps=%lld, max_substeps_per_launch=%d", name, (long long)substeps,
+               max_substeps_per_launch);
+    GN_REQUIRE(block >= GN_WAVE && block <= CL_MAX_BLOCK && block % GN_WAVE == 0, "%s: block=%d: a multiple of %d in [%d, %d]", name, block, GN_WAVE,
+               GN_WAVE, CL_MAX_BLOCK);
+    GN_REQUIRE(lds_bytes >= 0 && lds_bytes <= CL_MAX_LDS, "%s: lds_bytes=%d outside [0, %d]", name, lds_bytes, CL_MAX_LDS);
+    if (B == 0) return GN_OK;
+    GN_REQUIRE(a.csr && a.colour_off && a.bad && consts_host, "%s: null pointer", name);
+    GN_REQUIRE(total_verts == 0 || (a.x && a.v && a.w), "%s: null x / v / w", name);
+    GN_REQUIRE(total_constraints == 0 || (a.pairs && a.l0 && a.alpha_t), "%s: null constraint table", name);
+    for (int k = 0; k < 6; ++k)
+        GN_REQUIRE(consts_host[k] == consts_host[k] && fabs(consts_host[k]) <= 1.7976931348623157e308, "%s: step constant %d is not finite", name, k);
+    a.h = consts_host[0]; a.inv_h = consts_host[1]; a.hgx = consts_host[2]; a.hgy = consts_host[3]; a.hgz = consts_host[4]; a.damp = consts_host[5];
+    a.lds_bytes = lds_bytes;
+    GN_HIP(hipFuncSetAttribute((const void *)cloth_simulate_batch_kernel<CONTACTS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), name);
+    // a launch with substeps == 0 still checks the table
+    int64_t left = substeps;
+    do {
+        a.substeps = (int)(left < max_substeps_per_launch ? left : max_substeps_per_launch);
+        hipLaunchKernelGGL(cloth_simulate_batch_kernel<CONTACTS>, dim3((unsigned)B), dim3((unsigned)block), (size_t)lds_bytes, gn_stream(stream), a);
+        GN_LAUNCH_CHECK(name);
+        left -= a.substeps;
+    } while (left > 0);
+    return GN_OK;
 }
 
 extern "C" int gn_cloth_simulate_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0, const double *alpha_t,
                                        const int64_t *csr, const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints,
                                        int64_t substeps, int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block,
                                        int64_t *bad, void *stream) {
-    GN_REQUIRE(B >= 0 && B <= 65535, "gn_cloth_simulate_batch: B=%d outside [0, 65535]", B);
-    GN_REQUIRE(total_verts >= 0 && total_verts < INT32_MAX && total_constraints >= 0 && total_constraints < INT32_MAX,
-               "gn_cloth_simulate_batch: %lld vertices, %lld constraints: each table must stay below 2^31 rows", (long long)total_verts,
-               (long long)total_constraints);
-    GN_REQUIRE(substeps >= 0 && max_substeps_per_launch >= 1, "gn_cloth_simulate_batch: substeps=%lld, max_substeps_per_launch=%d",
-               (long long)substeps, max_substeps_per_launch);
-    GN_REQUIRE(block >= GN_WAVE && block <= CL_MAX_BLOCK && block % GN_WAVE == 0, "gn_cloth_simulate_batch: block=%d: a multiple of %d in [%d, %d]",
-               block, GN_WAVE, GN_WAVE, CL_MAX_BLOCK);
-    GN_REQUIRE(lds_bytes >= 0 && lds_bytes <= CL_MAX_LDS, "gn_cloth_simulate_batch: lds_bytes=%d outside [0, %d]", lds_bytes, CL_MAX_LDS);
-    if (B == 0) return GN_OK;
-    GN_REQUIRE(csr && colour_off && bad && consts_host, "gn_cloth_simulate_batch: null pointer");
-    GN_REQUIRE(total_verts == 0 || (x && v && w), "gn_cloth_simulate_batch: null x / v / w");
-    GN_REQUIRE(total_constraints == 0 || (pairs && l0 && alpha_t), "gn_cloth_simulate_batch: null constraint table");
-    for (int k = 0; k < 6; ++k) GN_REQUIRE(consts_host[k] == consts_host[k] && fabs(consts_host[k]) <= 1.7976931348623157e308,
-                                           "gn_cloth_simulate_batch: step constant %d is not finite", k);
     ClothArgs a;
     a.x = x; a.v = v; a.w = w; a.pairs = pairs; a.l0 = l0; a.alpha_t = alpha_t; a.csr = csr; a.colour_off = colour_off; a.bad = bad;
-    a.h = consts_host[0]; a.inv_h = consts_host[1]; a.hgx = consts_host[2]; a.hgy = consts_host[3]; a.hgz = consts_host[4]; a.damp = consts_host[5];
-    a.lds_bytes = lds_bytes;
-    GN_HIP(hipFuncSetAttribute((const void *)cloth_simulate_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-           "gn_cloth_simulate_batch");
-    // a launch with substeps == 0 still checks the table
-    int64_t left = substeps;
-    do {
-        a.substeps = (int)(left < max_substeps_per_launch ? left : max_substeps_per_launch);
-        hipLaunchKernelGGL(cloth_simulate_batch_kernel, dim3((unsigned)B), dim3((unsigned)block), (size_t)lds_bytes, gn_stream(stream), a);
-        GN_LAUNCH_CHECK("gn_cloth_simulate_batch");
-        left -= a.substeps;
-    } while (left > 0);
+    return cloth_launch<false>("gn_cloth_simulate_batch", a, B, total_verts, total_constraints, substeps, max_substeps_per_launch, consts_host,
+                               lds_bytes, block, stream);
+}
+
+static bool cl_finite(double v) { return v == v && fabs(v) <= 1.7976931348623157e308; }
+
+extern "C" int gn_cloth_simulate_contacts_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0, const double *alpha_t,
+                                                const int64_t *csr, const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints,
+                                                int64_t substeps, int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block,
+                                                int64_t *bad, const int32_t *list_j, const double *list_tm2, const int32_t *list_n, int K,
+                                                const double *collision_host, double *corr, int64_t *diag, void *stream) {
+    const char *name = "gn_cloth_simulate_contacts_batch";
+    GN_REQUIRE(K >= 1 && K <= CL_MAX_LIST, "%s: K=%d outside [1, %d]", name, K, CL_MAX_LIST);
+    GN_REQUIRE(collision_host, "%s: null collision constants", name);
+    GN_REQUIRE(cl_finite(collision_host[3]) && collision_host[3] > 0.0 && collision_host[3] <= 1.0, "%s: collision constant 3 (relax) is not in (0, 1]",
+               name);
+    GN_REQUIRE(B == 0 || diag, "%s: null diag", name);
+    GN_REQUIRE(B == 0 || total_verts == 0 || (list_j && list_tm2 && list_n && corr), "%s: null list / corr", name);
+    ClothArgsContacts a;
+    a.x = x; a.v = v; a.w = w; a.pairs = pairs; a.l0 = l0; a.alpha_t = alpha_t; a.csr = csr; a.colour_off = colour_off; a.bad = bad;
+    a.list_j = list_j; a.list_tm2 = list_tm2; a.list_n = list_n; a.corr = corr; a.diag = diag; a.relax = collision_host[3]; a.K = K;
+    return cloth_launch<true>(name, a, B, total_verts, total_constraints, substeps, max_substeps_per_launch, consts_host, lds_bytes, block, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ contact lists
+#define CL_CELL_CLAMP 1073741824.0          // 2^30: a cell index and its neighbours fit int32; clamping is monotone, so it never separates neighbours
+#define CL_BIN_BLOCK 256
+#define CL_QUERY_BLOCK GN_WAVE
+#define CL_QUERY_CAP 256                    // partners of a vertex the query holds in LDS
+#define CL_SCAN_BLOCK 1024
+enum { CL_LISTS_TRAVEL = 1, CL_LISTS_BUILD = 2 };
+
+struct ContactArgs {
+    const double *x, *x0;                   // [*][3] positions now, start pose
+    double *x_ref;                          // [*][3] positions at the last build
+    const int64_t *csr;                     // the solver's [B + 1][3]; only v_off is read
+    int32_t *cell;                          // [*][4] per vertex: its cell and its bucket
+    int32_t *count, *start, *cursor;        // [B][buckets]
+    int32_t *items;                         // [*] the vertices of a garment grouped by bucket
+    int32_t *list_j, *list_n, *list_total;
+    double *list_tm2;
+    int64_t *diag;
+    double t2, r2, edge;
+    int K, buckets, flags;
+};
+
+__device__ __forceinline__ int cl_cell_of(double x, double edge) {
+    double q = __ddiv_rn(x, edge);
+    q = fmin(fmax(q, -CL_CELL_CLAMP), CL_CELL_CLAMP);        // a NaN lands on -2^30: still a cell
+    return (int)floor(q);
+}
+__device__ __forceinline__ int cl_bucket_of(int cx, int cy, int cz, int buckets) {
+    return (int)((((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u) ^ ((uint32_t)cz * 83492791u)) & (uint32_t)(buckets - 1));
+}
+
+// grid (chunks of the largest garment, B).  Travel against x_ref, then x_ref = x, the vertex's cell and the bucket counts.
+__global__ __launch_bounds__(CL_BIN_BLOCK) void cl_contact_bin_kernel(ContactArgs a) {
+    const int b = blockIdx.y;
+    const int64_t v_off = a.csr[3 * (int64_t)b];
+    const int V = (int)(a.csr[3 * (int64_t)(b + 1)] - v_off);
+    const int i = blockIdx.x * CL_BIN_BLOCK + threadIdx.x;
+    unsigned long long far = 0;                              // bits of a double >= 0: ordered as the doubles are
+    if (i < V) {
+        const int64_t g = v_off + i;
+        const double px = a.x[3 * g], py = a.x[3 * g + 1], pz = a.x[3 * g + 2];
+        if (a.flags & CL_LISTS_TRAVEL) far = (unsigned long long)__double_as_longlong(cl_sq(px, py, pz, a.x_ref[3 * g], a.x_ref[3 * g + 1], a.x_ref[3 * g + 2]));
+        if (a.flags & CL_LISTS_BUILD) {
+            a.x_ref[3 * g] = px; a.x_ref[3 * g + 1] = py; a.x_ref[3 * g + 2] = pz;
+            const int cx = cl_cell_of(px, a.edge), cy = cl_cell_of(py, a.edge), cz = cl_cell_of(pz, a.edge);
+            const int bk = cl_bucket_of(cx, cy, cz, a.buckets);
+            a.cell[4 * g] = cx; a.cell[4 * g + 1] = cy; a.cell[4 * g + 2] = cz; a.cell[4 * g + 3] = bk;
+            atomicAdd(a.count + (int64_t)b * a.buckets + bk, 1);
+        }
+    }
+    if (a.flags & CL_LISTS_TRAVEL) {                         // every lane: the flag is the launch's
+        far = cl_wave_max(far);
+        if ((threadIdx.x & (GN_WAVE - 1)) == 0 && far) atomicMax((unsigned long long *)(a.diag + CL_DIAG * (int64_t)b + 3), far);
+    }
+}
+
+// grid B: the exclusive scan of a garment's bucket counts -> start and cursor
+__global__ __launch_bounds__(CL_SCAN_BLOCK) void cl_contact_scan_kernel(ContactArgs a) {
+    __shared__ int part[2][CL_SCAN_BLOCK];
+    const int64_t base = (int64_t)blockIdx.x * a.buckets;
+    const int per = (a.buckets + CL_SCAN_BLOCK - 1) / CL_SCAN_BLOCK;
+    const int k0 = min(threadIdx.x * per, a.buckets), k1 = min(k0 + per, a.buckets);
+    int sum = 0;
+    for (int k = k0; k < k1; ++k) sum += a.count[base + k];
+    int cur = 0;
+    part[0][threadIdx.x] = sum;
+    __syncthreads();
+    for (int step = 1; step < CL_SCAN_BLOCK; step <<= 1) {   // inclusive scan, ping-pong
+        const int val = part[cur][threadIdx.x] + (threadIdx.x >= step ? part[cur][threadIdx.x - step] : 0);
+        part[cur ^ 1][threadIdx.x] = val;
+        cur ^= 1;
+        __syncthreads();
+    }
+    int run = part[cur][threadIdx.x] - sum;
+    for (int k = k0; k < k1; ++k) {
+        a.start[base + k] = run;
+        a.cursor[base + k] = run;
+        run += a.count[base + k];
+    }
+}
+
+// grid as the bin kernel: the vertices of a garment grouped by bucket (the order inside a bucket does not reach the result: the lists are sorted)
+__global__ __launch_bounds__(CL_BIN_BLOCK) void cl_contact_fill_kernel(ContactArgs a) {
+    const int b = blockIdx.y;
+    const int64_t v_off = a.csr[3 * (int64_t)b];
+    const int V = (int)(a.csr[3 * (int64_t)(b + 1)] - v_off);
+    const int i = blockIdx.x * CL_BIN_BLOCK + threadIdx.x;
+    if (i >= V) return;
+    const int pos = atomicAdd(a.cursor + (int64_t)b * a.buckets + a.cell[4 * (v_off + i) + 3], 1);
+    if (pos >= 0 && pos < V) a.items[v_off + pos] = i;
+}
+
+// slot s of the bucket of cell (ex, ey, ez), scanned for vertex i: the index of the vertex there when it is a partner of the definition, else -1
+struct ContactQuery {
+    int i, V;
+    int64_t v_off;
+    double px, py, pz, rx, ry, rz;                          // x_i and x0_i
+};
+__device__ __forceinline__ int cl_partner(const ContactArgs &a, const ContactQuery &q, int s, int s1, int ex, int ey, int ez) {
+    if (s >= s1) return -1;
+    const int j = a.items[q.v_off + s];
+    if (j == q.i || j < 0 || j >= q.V) return -1;
+    const int32_t *cj = a.cell + 4 * (q.v_off + j);
+    if (cj[0] != ex || cj[1] != ey || cj[2] != ez) return -1;                              // another cell of the same bucket
+    const double *p = a.x + 3 * (q.v_off + j);
+    if (!(cl_sq(q.px, q.py, q.pz, p[0], p[1], p[2]) <= a.r2)) return -1;
+    const double *p0 = a.x0 + 3 * (q.v_off + j);
+    if (!(cl_sq(q.rx, q.ry, q.rz, p0[0], p0[1], p0[2]) > 0.0)) return -1;                  // tm2 = min(t2, rest2) > 0 iff rest2 > 0 (t2 > 0)
+    return j;
+}
+__device__ __forceinline__ void cl_write_entry(const ContactArgs &a, const ContactQuery &q, int k, int j) {
+    const double *p0 = a.x0 + 3 * (q.v_off + j);
+    a.list_j[(q.v_off + q.i) * a.K + k] = j;
+    a.list_tm2[(q.v_off + q.i) * a.K + k] = fmin(a.t2, cl_sq(q.rx, q.ry, q.rz, p0[0], p0[1], p0[2]));
+}
+
+// grid (the most vertices of a garment, B), ONE wave per vertex: the lanes share the slots of the 27 buckets, the partners found go to LDS, and an
+// entry's place in the list is its rank among them (the indices are distinct).  More than CL_QUERY_CAP partners: the K smallest are drawn one after
+// the other by scanning the buckets again -- slow, exact, and only for a vertex with hundreds of vertices within r.
+__global__ __launch_bounds__(CL_QUERY_BLOCK) void cl_contact_query_kernel(ContactArgs a) {
+    __shared__ int32_t found[CL_QUERY_CAP];
+    const int b = blockIdx.y, lane = threadIdx.x;
+    ContactQuery q;
+    q.v_off = a.csr[3 * (int64_t)b];
+    q.V = (int)(a.csr[3 * (int64_t)(b + 1)] - q.v_off);
+    q.i = blockIdx.x;
+    if (q.i >= q.V) return;                                  // the whole workgroup: nobody is left waiting at the barrier below
+    const int64_t g = q.v_off + q.i;
+    q.px = a.x[3 * g]; q.py = a.x[3 * g + 1]; q.pz = a.x[3 * g + 2];
+    q.rx = a.x0[3 * g]; q.ry = a.x0[3 * g + 1]; q.rz = a.x0[3 * g + 2];
+    int ex = 0, ey = 0, ez = 0, s0 = 0, s1 = 0;              // lane c < 27: cell c of the neighbourhood and the slots of its bucket
+    if (lane < 27) {
+        ex = a.cell[4 * g] + lane % 3 - 1; ey = a.cell[4 * g + 1] + (lane / 3) % 3 - 1; ez = a.cell[4 * g + 2] + lane / 9 - 1;
+        const int64_t at = (int64_t)b * a.buckets + cl_bucket_of(ex, ey, ez, a.buckets);
+        s0 = max(a.start[at], 0); s1 = min(a.cursor[at], q.V);
+    }
+    const int K = a.K;
+    int total = 0;
+    for (int c = 0; c < 27; ++c) {
+        const int c0 = __shfl(s0, c), c1 = __shfl(s1, c), fx = __shfl(ex, c), fy = __shfl(ey, c), fz = __shfl(ez, c);
+        for (int s = c0; s < c1; s += GN_WAVE) {             // wave-uniform bounds
+            const int j = cl_partner(a, q, s + lane, c1, fx, fy, fz);
+            const unsigned long long hit = __ballot(j >= 0);
+            const int at = total + __popcll(hit & ((1ull << lane) - 1ull));
+            if (j >= 0 && at < CL_QUERY_CAP) found[at] = j;
+            total += __popcll(hit);
+        }
+    }
+    const int n = min(total, K);
+    __syncthreads();                                         // one wave: the hand-over of `found` from the lanes that wrote it
+    if (total <= CL_QUERY_CAP) {
+        for (int e = lane; e < total; e += GN_WAVE) {
+            const int j = found[e];
+            int rank = 0;
+            for (int o = 0; o < total; ++o) rank += found[o] < j;
+            if (rank < K) cl_write_entry(a, q, rank, j);
+        }
+    } else {
+        int prev = -1;
+        for (int k = 0; k < n; ++k) {                        // the smallest partner above the last one drawn
+            int best = INT32_MAX;
+            for (int c = 0; c < 27; ++c) {
+                const int c0 = __shfl(s0, c), c1 = __shfl(s1, c), fx = __shfl(ex, c), fy = __shfl(ey, c), fz = __shfl(ez, c);
+                for (int s = c0; s < c1; s += GN_WAVE) {
+                    const int j = cl_partner(a, q, s + lane, c1, fx, fy, fz);
+                    if (j > prev && j < best) best = j;
+                }
+            }
+            best = gn_wave_min(best);
+            if (lane == 0 && best < q.V) cl_write_entry(a, q, k, best);
+            prev = best;
+        }
+    }
+    for (int k = n + lane; k < K; k += GN_WAVE) {
+        a.list_j[g * K + k] = -1;
+        a.list_tm2[g * K + k] = 0.0;
+    }
+    if (lane == 0) {
+        a.list_n[g] = n;
+        a.list_total[g] = total;
+        int64_t *d = a.diag + CL_DIAG * (int64_t)b;
+        if (total > n) atomicAdd((unsigned long long *)d, (unsigned long long)(total - n));
+        if ((int64_t)total > d[1]) atomicMax((unsigned long long *)(d + 1), (unsigned long long)total);     // d[1] only grows: a stale read costs an atomic
+    }
+}
+
+extern "C" int gn_cloth_contact_buckets(int max_verts) {
+    int64_t nb = 64;
+    while (nb < 2 * (int64_t)max_verts) nb <<= 1;
+    return max_verts < 0 || nb > (1 << 30) ? 0 : (int)nb;
+}
+
+// cell [*][4] int32, items [*] int32, x_ref [*][3] fp64, count / start / cursor [B][buckets] int32, each part on a 256-byte boundary
+static size_t cl_align(size_t n) { return (n + 255) & ~(size_t)255; }
+extern "C" size_t gn_cloth_contact_workspace_bytes(int64_t total_verts, int B, int buckets) {
+    if (total_verts < 0 || B < 0 || buckets < 0) return 0;
+    return cl_align(16 * (size_t)total_verts) + cl_align(4 * (size_t)total_verts) + cl_align(24 * (size_t)total_verts) +
+           3 * cl_align(4 * (size_t)B * (size_t)buckets);
+}
+
+extern "C" int gn_cloth_contact_lists(const double *x, const double *x0, const int64_t *csr, int B, int64_t total_verts, int max_verts, int buckets,
+                                      const double *collision_host, int K, int flags, void *workspace, size_t workspace_bytes, int32_t *list_j,
+                                      double *list_tm2, int32_t *list_n, int32_t *list_total, int64_t *diag, void *stream) {
+    const char *name = "gn_cloth_contact_lists";
+    GN_REQUIRE(B >= 0 && B <= 65535, "%s: B=%d outside [0, 65535]", name, B);
+    GN_REQUIRE(total_verts >= 0 && total_verts < INT32_MAX / CL_MAX_LIST, "%s: %lld vertices: the lists must stay below 2^31 entries", name,
+               (long long)total_verts);
+    GN_REQUIRE(max_verts >= 0 && max_verts <= total_verts, "%s: max_verts=%d outside [0, %lld]", name, max_verts, (long long)total_verts);
+    GN_REQUIRE(K >= 1 && K <= CL_MAX_LIST, "%s: K=%d outside [1, %d]", name, K, CL_MAX_LIST);
+    GN_REQUIRE(flags >= 1 && flags <= 3, "%s: flags=%d: 1 (travel), 2 (build) or 3", name, flags);
+    GN_REQUIRE(buckets >= 64 && (buckets & (buckets - 1)) == 0 && buckets >= gn_cloth_contact_buckets(max_verts) && gn_cloth_contact_buckets(max_verts),
+               "%s: buckets=%d: a power of two of at least max(64, 2 max_verts)", name, buckets);
+    GN_REQUIRE(collision_host, "%s: null collision constants", name);
+    for (int k = 0; k < 3; ++k)
+        GN_REQUIRE(cl_finite(collision_host[k]) && collision_host[k] > 0.0, "%s: collision constant %d is not finite and positive", name, k);
+    GN_REQUIRE(collision_host[2] * collision_host[2] > collision_host[1], "%s: the cell edge %g does not exceed r = sqrt(%g)", name, collision_host[2],
+               collision_host[1]);
+    if (B == 0 || total_verts == 0) return GN_OK;
+    GN_REQUIRE(x && x0 && csr && diag && workspace, "%s: null pointer", name);
+    GN_REQUIRE(!(flags & CL_LISTS_BUILD) || (list_j && list_tm2 && list_n && list_total), "%s: null list", name);
+    GN_REQUIRE(workspace_bytes >= gn_cloth_contact_workspace_bytes(total_verts, B, buckets), "%s: workspace of %zu bytes, %zu needed", name,
+               workspace_bytes, gn_cloth_contact_workspace_bytes(total_verts, B, buckets));
+    ContactArgs a;
+    a.x = x; a.x0 = x0; a.csr = csr; a.list_j = list_j; a.list_tm2 = list_tm2; a.list_n = list_n; a.list_total = list_total; a.diag = diag;
+    a.t2 = collision_host[0]; a.r2 = collision_host[1]; a.edge = collision_host[2]; a.K = K; a.buckets = buckets; a.flags = flags;
+    char *ws = (char *)workspace;
+    const size_t per_table = cl_align(4 * (size_t)B * (size_t)buckets);
+    a.cell = (int32_t *)ws; ws += cl_align(16 * (size_t)total_verts);
+    a.items = (int32_t *)ws; ws += cl_align(4 * (size_t)total_verts);
+    a.x_ref = (double *)ws; ws += cl_align(24 * (size_t)total_verts);
+    a.count = (int32_t *)ws; a.start = (int32_t *)(ws + per_table); a.cursor = (int32_t *)(ws + 2 * per_table);
+    hipStream_t st = gn_stream(stream);
+    const dim3 per_vertex((unsigned)gn_cdiv(max_verts, CL_BIN_BLOCK), (unsigned)B);
+    if (max_verts == 0) return GN_OK;
+    if (flags & CL_LISTS_BUILD) GN_HIP(hipMemsetAsync(a.count, 0, 4 * (size_t)B * (size_t)buckets, st), name);
+    hipLaunchKernelGGL(cl_contact_bin_kernel, per_vertex, dim3(CL_BIN_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
+    if (!(flags & CL_LISTS_BUILD)) return GN_OK;
+    hipLaunchKernelGGL(cl_contact_scan_kernel, dim3((unsigned)B), dim3(CL_SCAN_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(cl_contact_fill_kernel, per_vertex, dim3(CL_BIN_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(cl_contact_query_kernel, dim3((unsigned)max_verts, (unsigned)B), dim3(CL_QUERY_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
     return GN_OK;
 }

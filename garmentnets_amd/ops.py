@@ -2335,15 +2335,108 @@ def cloth_device_tables(garments, states, dev):
     return t
 
 
+CLOTH_CELL_SLACK = 2.0 ** -10          # the grid's cell edge is r * (1 + CLOTH_CELL_SLACK): DESIGN.md "Hanging garments" argues why that admits every pair
+
+
+def cloth_collision_constants(garments, who):
+    """the collision record the garments of one call share (cloth.collision_constants) -> None with contacts off, else the record with "cell" (the grid's
+    cell edge) and "host" (ctypes double[4] = t2, r2, cell, relax) added.  Refused by name: records that differ, a constant that is not finite or not
+    positive, K outside [1, 64], R < 1, relax outside (0, 1]."""
+    col = garments[0].collision
+    if any(g.collision != col for g in garments):
+        raise ValueError(f"{who}: the garments of one call must share their collision constants (thickness, margin, rebuild, max_list, relax)")
+    if col is None:
+        return None
+    for k in ("t2", "r", "r2", "half_margin", "relax"):
+        if not (np.isfinite(col[k]) and col[k] > 0):
+            raise ValueError(f"{who}: collision constant {k}={col[k]} is not finite and positive")
+    if int(col["K"]) != col["K"] or not 1 <= col["K"] <= _lib.CLOTH_MAX_LIST:
+        raise ValueError(f"{who}: collision_max_list K={col['K']} outside [1, {_lib.CLOTH_MAX_LIST}]")
+    if int(col["R"]) != col["R"] or col["R"] < 1:
+        raise ValueError(f"{who}: collision_rebuild R={col['R']} < 1")
+    if not col["relax"] <= 1:
+        raise ValueError(f"{who}: collision_relax={col['relax']} outside (0, 1]")
+    cell = float(np.float64(col["r"]) * (np.float64(1.0) + np.float64(CLOTH_CELL_SLACK)))
+    return dict(col, cell=cell, host=(ctypes.c_double * 4)(col["t2"], col["r2"], cell, col["relax"]))
+
+
+def cloth_contact_buffers(garments, t, col, dev):
+    """what the two contact entries need beside cloth_device_tables' `t`: x0, the lists (rows of stride K), corr, diag and the grid's workspace"""
+    n, B, K = t["total_verts"], len(garments), col["K"]
+    max_verts = max(len(g.w) for g in garments)
+    buckets = int(_lib.load().gn_cloth_contact_buckets(max_verts))
+    if n >= (2 ** 31 - 1) // _lib.CLOTH_MAX_LIST or buckets <= 0:
+        raise ValueError("cloth contacts: the lists must stay below 2^31 entries")
+    ws_bytes = int(_lib.load().gn_cloth_contact_workspace_bytes(n, B, buckets))
+    return {"x0": torch.from_numpy(np.ascontiguousarray(np.concatenate([g.x0 for g in garments]).reshape(-1, 3))).to(dev),
+            "list_j": torch.full((n, K), -1, dtype=torch.int32, device=dev), "list_tm2": torch.zeros((n, K), dtype=torch.float64, device=dev),
+            "list_n": torch.zeros(n, dtype=torch.int32, device=dev), "list_total": torch.zeros(n, dtype=torch.int32, device=dev),
+            "corr": torch.zeros((n, 3), dtype=torch.float64, device=dev), "diag": torch.zeros((B, 4), dtype=torch.int64, device=dev),
+            "workspace": torch.zeros(max(ws_bytes, 1), dtype=torch.uint8, device=dev), "workspace_bytes": ws_bytes, "max_verts": max_verts,
+            "buckets": buckets}
+
+
+def _cloth_lists_call(t, c, col, B, flags):
+    _lib.call("gn_cloth_contact_lists", _p(t["x"]), _p(c["x0"]), _p(t["csr"]), B, t["total_verts"], c["max_verts"], c["buckets"],
+              ctypes.cast(col["host"], ctypes.c_void_p), col["K"], flags, _p(c["workspace"]), c["workspace_bytes"], _p(c["list_j"]), _p(c["list_tm2"]),
+              _p(c["list_n"]), _p(c["list_total"]), _p(c["diag"]), _stream())
+
+
+def cloth_contact_stats(diag, col):
+    """the rows of the device's diag table -> one dict of the definition's four diagnostics per garment"""
+    d = diag.cpu().numpy()
+    travel = np.sqrt(np.ascontiguousarray(d[:, 3]).view(np.float64)) / np.float64(col["half_margin"])
+    return [{"contact_overflow": int(r[0]), "contact_max_list": int(r[1]), "contact_travel": float(tr), "contact_active": int(r[2])}
+            for r, tr in zip(d, travel)]
+
+
+def cloth_contact_lists(garments, states=None, backend="hip", device=None):
+    """the contact lists of cloth.py's definition for every garment at the positions of `states` (None: the start pose), all garments in the same
+    launches (gn_cloth_contact_lists: a hashed uniform grid, many workgroups per garment) -> [((idx (V, K) int32, tm2 (V, K) float64), counts (V,)
+    int64, overflow (V,) int64)] tensors: bit for bit cloth.contact_lists_reference (backend "numpy").  The garments must have contacts on and share
+    their collision constants."""
+    from . import cloth
+    if backend not in ("hip", "numpy"):
+        raise ValueError(f"backend {backend!r}: expected 'hip' or 'numpy'")
+    states = [None] * len(garments) if states is None else list(states)
+    if len(states) != len(garments):
+        raise ValueError("cloth_contact_lists: one state per garment")
+    states = [cloth.state_arrays(g, *(s if s is not None else (None, None)), who="cloth_contact_lists") for g, s in zip(garments, states)]
+    if not garments:
+        return []
+    col = cloth_collision_constants(garments, "cloth_contact_lists")
+    if col is None:
+        raise ValueError("cloth_contact_lists: the garments have contacts off (collision_thickness = 0)")
+    if backend == "numpy":
+        out = []
+        for g, (x, _) in zip(garments, states):
+            (idx, tm2), counts, overflow = cloth.contact_lists_reference(g, x)
+            out.append(((torch.from_numpy(idx), torch.from_numpy(tm2)), torch.from_numpy(counts), torch.from_numpy(overflow)))
+        return out
+    if len(garments) > 65535:
+        raise ValueError(f"cloth_contact_lists: at most 65535 garments per call, got {len(garments)}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    t = cloth_device_tables(garments, states, dev)
+    c = cloth_contact_buffers(garments, t, col, dev)
+    _cloth_lists_call(t, c, col, len(garments), _lib.CLOTH_LISTS_BUILD)
+    counts, total = c["list_n"].to(torch.int64), c["list_total"].to(torch.int64)
+    return [((c["list_j"][a:b], c["list_tm2"][a:b]), counts[a:b], total[a:b] - counts[a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
+
+
 def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_budget=None, max_substeps_per_launch=CLOTH_SUBSTEPS_PER_LAUNCH,
-                         block=None, device=None):
+                         block=None, device=None, stats=False):
     """`substeps` substeps of cloth.py's definition on every cloth.Garment of `garments`, all of them in the same launches (gn_cloth_simulate_batch: one
     workgroup per garment) -> [(x, v)] float64 (V, 3) tensors, on the device (backend "hip") or on the host (backend "numpy": cloth.simulate_reference).
     states: None or one (x, v) / None per garment (None: the start pose at rest); the inputs are not written.  The device gives the restatement's bits
     whatever the batch, `block` (threads per workgroup, a multiple of 64 up to 1024), lds_budget (bytes: a garment whose positions, 24 bytes per vertex,
     fit it keeps them in LDS, any other in global memory; default all 160 KiB) and max_substeps_per_launch (a longer run is several launches).  The
     garments must share their step constants.  A face index outside [0, V) raises IndexError (after the launch, nothing is read or written through
-    it); a state that is not finite, a bad budget / block / substep count raise ValueError before it."""
+    it); a state that is not finite, a bad budget / block / substep count raise ValueError before it.
+
+    Garments with contacts on (ClothParams.collision_thickness > 0; the garments of one call share their collision constants) run the contact pass of
+    the definition: the wrapper alternates gn_cloth_contact_lists (every collision_rebuild substeps, counted from the call's first) and
+    gn_cloth_simulate_contacts_batch on one stream, without a host synchronisation between them.  stats=True returns (states, [the four contact
+    diagnostics of the definition per garment]) (all 0 with contacts off); without it the return value is what it always was."""
     from . import cloth
     if backend not in ("hip", "numpy"):
         raise ValueError(f"backend {backend!r}: expected 'hip' or 'numpy'")
@@ -2358,8 +2451,11 @@ def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_bud
         return []
     if any(g.consts != garments[0].consts for g in garments):
         raise ValueError("cloth_simulate_batch: the garments of one call must share their step constants (h, gravity, damping, compliances)")
+    col = cloth_collision_constants(garments, "cloth_simulate_batch")
     if backend == "numpy":
-        return [tuple(torch.from_numpy(a) for a in cloth.simulate_reference(g, substeps, x, v)) for g, (x, v) in zip(garments, states)]
+        ref = [cloth.simulate_reference(g, substeps, x, v, stats=True) for g, (x, v) in zip(garments, states)]
+        out = [tuple(torch.from_numpy(a) for a in r[:2]) for r in ref]
+        return (out, [r[2] for r in ref]) if stats else out
     budget = _lib.CLOTH_MAX_LDS if lds_budget is None else int(lds_budget)
     if not 0 <= budget <= _lib.CLOTH_MAX_LDS:
         raise ValueError(f"cloth_simulate_batch: lds_budget={budget} outside [0, {_lib.CLOTH_MAX_LDS}]")
@@ -2375,11 +2471,31 @@ def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_bud
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     t = cloth_device_tables(garments, states, dev)
     bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    _lib.call("gn_cloth_simulate_batch", _p(t["x"]), _p(t["v"]), _p(t["w"]), _p(t["pairs"]), _p(t["l0"]), _p(t["alpha_t"]), _p(t["csr"]),
-              _p(t["colour_off"]), len(garments), t["total_verts"], t["total_constraints"], substeps, int(max_substeps_per_launch),
-              ctypes.cast(t["consts"], ctypes.c_void_p), lds, block, _p(bad), _stream())
+    solver = (_p(t["x"]), _p(t["v"]), _p(t["w"]), _p(t["pairs"]), _p(t["l0"]), _p(t["alpha_t"]), _p(t["csr"]), _p(t["colour_off"]), len(garments),
+              t["total_verts"], t["total_constraints"])
+    tail = (int(max_substeps_per_launch), ctypes.cast(t["consts"], ctypes.c_void_p), lds, block, _p(bad))
+    if col is None:
+        _lib.call("gn_cloth_simulate_batch", *solver, substeps, *tail, _stream())
+        contact_stats = [{"contact_overflow": 0, "contact_max_list": 0, "contact_travel": 0.0, "contact_active": 0} for _ in garments]
+    else:
+        c = cloth_contact_buffers(garments, t, col, dev)
+        lists = (_p(c["list_j"]), _p(c["list_tm2"]), _p(c["list_n"]), col["K"], ctypes.cast(col["host"], ctypes.c_void_p), _p(c["corr"]),
+                 _p(c["diag"]))
+        done = 0
+        while True:                                                           # one pass with substeps == 0: the table is still checked
+            n = min(col["R"], substeps - done)
+            if n > 0:
+                _cloth_lists_call(t, c, col, len(garments), _lib.CLOTH_LISTS_BUILD | (_lib.CLOTH_LISTS_TRAVEL if done else 0))
+            _lib.call("gn_cloth_simulate_contacts_batch", *solver, n, *tail, *lists, _stream())
+            done += n
+            if done >= substeps:
+                break
+        if substeps > 0:
+            _cloth_lists_call(t, c, col, len(garments), _lib.CLOTH_LISTS_TRAVEL)
+        contact_stats = cloth_contact_stats(c["diag"], col) if stats else None
     _raise_bad_face(bad.item(), "cloth_simulate")
-    return [(t["x"][a:b], t["v"][a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
+    out = [(t["x"][a:b], t["v"][a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
+    return (out, contact_stats) if stats else out
 
 
 def cloth_storage_path(garment, lds_budget=None):

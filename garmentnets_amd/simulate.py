@@ -9,6 +9,12 @@ writes through io.zarr_store, with default_compressor():
                                        diagnostics of the final state (kinetic energy, largest stretch strain, massless vertices)}
   summary/cloth_aabb_union             float32 (2, 3): the union box of every cloth_verts of the store, when the store has none or with --update_summary
 
+--self_collision turns the vertex-vertex contacts of cloth.py on: --collision_thickness (default: cloth.DEFAULT_COLLISION_THICKNESS_FACTOR times the
+garment's mean stretch rest length, cloth.mean_stretch_rest_length, so it differs from garment to garment), --collision_margin (default: the thickness),
+--collision_rebuild, --collision_max_list, --collision_relax.  The five parameters and the four contact diagnostics of the sample then join
+"cloth_simulation", and a sample with contact_overflow > 0 or contact_travel > 1 is named in a printed warning (a contact may have been cut off or
+missed).  Without the flag the store is byte for byte what it was.
+
 An existing cloth_verts is kept unless --overwrite is given.  --backend hip runs --batch_size garments per call of ops.cloth_simulate_batch (one workgroup
 each); --backend numpy runs the restatement, which gives the same bits.  After this command `prepare` can build every other group: simulate -> prepare ->
 train -> predict -> evaluate runs from canonical meshes alone.
@@ -43,6 +49,14 @@ def build_parser():
     ap.add_argument("--alpha_stretch", type=float, default=cloth.DEFAULT_ALPHA_STRETCH, help="stretch compliance, m / N")
     ap.add_argument("--alpha_bend", type=float, default=cloth.DEFAULT_ALPHA_BEND, help="bend compliance, m / N")
     ap.add_argument("--density", type=float, default=cloth.DEFAULT_DENSITY, help="kg / m^2")
+    ap.add_argument("--self_collision", action="store_true", help="vertex-vertex self-collision (cloth.py); off by default")
+    ap.add_argument("--collision_thickness", type=float, default=None,
+                    help=f"metres; default {cloth.DEFAULT_COLLISION_THICKNESS_FACTOR} x the garment's mean stretch rest length")
+    ap.add_argument("--collision_margin", type=float, default=None,
+                    help=f"metres beyond the thickness at which a pair enters a contact list; default {cloth.DEFAULT_COLLISION_MARGIN_FACTOR} x the thickness")
+    ap.add_argument("--collision_rebuild", type=int, default=cloth.DEFAULT_COLLISION_REBUILD, help="substeps between two contact-list builds")
+    ap.add_argument("--collision_max_list", type=int, default=cloth.DEFAULT_COLLISION_MAX_LIST, help="entries a contact list can hold, at most 64")
+    ap.add_argument("--collision_relax", type=float, default=cloth.DEFAULT_COLLISION_RELAX, help="in (0, 1]: the share of a contact correction applied")
     return ap
 
 
@@ -56,10 +70,47 @@ def grip_index(sample_group, dataset_idx, num_verts, seed):
     return grip
 
 
+def collision_params(params, g, collision):
+    """`params` with the contacts of `collision` ({"thickness", "margin" (None: the defaults from the garment g), "rebuild", "max_list", "relax"}) on"""
+    t = collision.get("thickness")
+    if t is None:
+        t = cloth.DEFAULT_COLLISION_THICKNESS_FACTOR * cloth.mean_stretch_rest_length(g)
+    m = collision.get("margin")
+    if m is None:
+        m = cloth.DEFAULT_COLLISION_MARGIN_FACTOR * t
+    if not t > 0:
+        raise ValueError(f"collision thickness {t}: expected a positive number (a garment without a stretch constraint has no default)")
+    return dataclasses.replace(params, collision_thickness=float(t), collision_margin=float(m), collision_rebuild=int(collision["rebuild"]),
+                               collision_max_list=int(collision["max_list"]), collision_relax=float(collision["relax"]))
+
+
+def run_batch(garments, substeps, backend):
+    """-> ([(x, v)] numpy, [the contact diagnostics]) of `garments`, those that share their collision constants in one call each"""
+    groups = {}
+    for n, g in enumerate(garments):
+        groups.setdefault(json.dumps(g.collision, sort_keys=True), []).append(n)
+    states, stats = [None] * len(garments), [None] * len(garments)
+    for idx in groups.values():
+        gs = [garments[n] for n in idx]
+        if backend == "numpy":
+            res = [cloth.simulate_reference(g, substeps, stats=True) for g in gs]
+            got, st = [r[:2] for r in res], [r[2] for r in res]
+        else:
+            from . import ops
+            got, st = ops.cloth_simulate_batch(gs, substeps, stats=True)
+            got = [(x.cpu().numpy(), v.cpu().numpy()) for x, v in got]
+        for n, state, d in zip(idx, got, st):
+            states[n], stats[n] = state, d
+    return states, stats
+
+
 def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_scale=None, batch_size=16, overwrite=False, update_summary=False,
-                   backend="hip", seed=0, log=print):
-    """-> summary dict {"samples", "written", "substeps", "seconds"}; log gets one dict per sample"""
+                   backend="hip", seed=0, log=print, collision=None):
+    """-> summary dict {"samples", "written", "substeps", "seconds"}; log gets one dict per sample.  collision: None (no contacts; `params` must then
+    have them off too) or the dict collision_params reads"""
     params = cloth.ClothParams() if params is None else params
+    if params.contacts:
+        raise ValueError("simulate_store: give the contacts through `collision`, not through params")
     if batch_size < 1:
         raise ValueError(f"batch_size {batch_size} < 1")
     substeps = cloth.substeps_of(duration, params.h)
@@ -84,24 +135,34 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
             raise ValueError(f"{zarr_in}: sample {k} has no mesh/{missing[0]}: the garment is simulated from its canonical mesh")
     todo = [(i, k) for i, k in enumerate(keys) if overwrite or "mesh/cloth_verts" not in samples[k]]
     comp = zarr_store.default_compressor()
-    record = dict(dataclasses.asdict(params), duration=float(duration), substeps=substeps, rest_scale=scale)
+    record = dict({k: v for k, v in dataclasses.asdict(params).items() if k not in cloth.COLLISION_FIELDS}, duration=float(duration),
+                  substeps=substeps, rest_scale=scale)
+    warned = []
     t_all = time.perf_counter()
     for s in range(0, len(todo), batch_size):
         chunk = todo[s:s + batch_size]
         t0 = time.perf_counter()
-        garments = []
+        garments, extra = [], []
         for i, k in chunk:
             mesh = samples[k]["mesh"]
             nocs = mesh["cloth_nocs_verts"][:]
-            garments.append(cloth.garment_from_nocs(nocs, mesh["cloth_faces_tri"][:], grip_index(samples[k], i, len(nocs), seed), scale, params))
-        if backend == "numpy":
-            states = [cloth.simulate_reference(g, substeps) for g in garments]
-        else:
-            from . import ops
-            states = [(x.cpu().numpy(), v.cpu().numpy()) for x, v in ops.cloth_simulate_batch(garments, substeps)]
+            g = cloth.garment_from_nocs(nocs, mesh["cloth_faces_tri"][:], grip_index(samples[k], i, len(nocs), seed), scale, params)
+            if collision is not None:
+                on = collision_params(params, g, collision)
+                g = dataclasses.replace(g, collision=cloth.collision_constants(on))
+                extra.append({f: getattr(on, f) for f in cloth.COLLISION_FIELDS})
+            garments.append(g)
+        states, stats = run_batch(garments, substeps, backend)
         dt = time.perf_counter() - t0
-        for (i, k), g, (x, v) in zip(chunk, garments, states):
+        for n, ((i, k), g, (x, v)) in enumerate(zip(chunk, garments, states)):
             diag = cloth.diagnostics(g, x, v)
+            if collision is not None:
+                diag = dict(diag, **extra[n], **stats[n])
+                if stats[n]["contact_overflow"] > 0 or stats[n]["contact_travel"] > 1:
+                    warned.append(k)
+                    log({"warning": f"sample {k}: contact_overflow {stats[n]['contact_overflow']}, contact_travel {stats[n]['contact_travel']:.3g}: "
+                                    "a contact may have been cut off or missed (raise --collision_max_list or --collision_margin, or lower "
+                                    "--collision_rebuild)"})
             mesh = samples[k].require_group("mesh")
             mesh.array("cloth_verts", x.astype(np.float32), compressor=comp)
             mesh.put_attrs({"cloth_simulation": dict(record, grip_vertex_idx=g.grip, **diag)})
@@ -114,6 +175,8 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
         wrote_summary = True
     summary = {"samples": len(keys), "written": len(todo), "substeps": substeps, "summary_written": wrote_summary,
                "seconds": time.perf_counter() - t_all}
+    if collision is not None:
+        summary["contact_warnings"] = warned
     log(summary)
     return summary
 
@@ -124,8 +187,12 @@ def main(argv=None):
     try:
         params = cloth.ClothParams(gravity=a.gravity, h=a.h, damping=a.damping, alpha_stretch=a.alpha_stretch, alpha_bend=a.alpha_bend,
                                    density=a.density)
+        collision = None
+        if a.self_collision:
+            collision = {"thickness": a.collision_thickness, "margin": a.collision_margin, "rebuild": a.collision_rebuild,
+                         "max_list": a.collision_max_list, "relax": a.collision_relax}
         return simulate_store(a.zarr_in, params, a.duration, a.rest_scale, a.batch_size, a.overwrite, a.update_summary, a.backend, a.seed,
-                              log=lambda row: print(json.dumps(row)))
+                              log=lambda row: print(json.dumps(row)), collision=collision)
     except ValueError as e:
         ap.error(str(e))
 

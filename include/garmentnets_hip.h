@@ -1073,6 +1073,33 @@ int gn_cloth_simulate_batch(double *x, double *v, const double *w, const int32_t
                             const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints, int64_t substeps,
                             int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block, int64_t *bad, void *stream);
 
+/* Self-collision of the hanging garment (cloth.py "Self-collision"; DESIGN.md "Hanging garments").  The vertex-vertex contact lists of B ragged garments
+ * for the positions x [*][3] fp64 and the start poses x0 [*][3], through a uniform grid of cells hashed into `buckets` buckets per garment
+ * (gn_cloth_contact_buckets(max_verts) or any larger power of two; max_verts: the most vertices a garment of the batch has) -- bit for bit the
+ * brute-force lists of cloth.contact_lists_reference.  csr: the solver's table (only v_off is read).  collision_host [4] = {t2, r2, cell edge (> r),
+ * relax}.  flags: 1 = measure the travel against the positions stored at the last build, 2 = build the lists (and store the positions), 3 = both, the
+ * travel first.  A build writes, per vertex row, list_j [*][K] (ascending partner indices relative to the garment's first vertex, -1 beyond the row's
+ * entries), list_tm2 [*][K] (min(t2, rest2) of the entry, 0 beyond), list_n [*] (entries, at most K) and list_total [*] (the uncut length), and
+ * accumulates into diag [B][4] int64 (caller zeroes it once per run) {sum of list_total - list_n, largest list_total, -- (the solver's active entries),
+ * the bits of the largest squared travel as a double}.  workspace: gn_cloth_contact_workspace_bytes(total_verts, B, buckets) bytes, kept by the caller
+ * between the calls of one run (it holds the stored positions).  Refused by name: B > 65535, 2^31 / 64 or more vertices, K outside [1, 64], bad flags
+ * or buckets, a constant that is not finite and positive, a cell edge that does not exceed r, a short workspace, null pointers. */
+int gn_cloth_contact_buckets(int max_verts);
+size_t gn_cloth_contact_workspace_bytes(int64_t total_verts, int B, int buckets);
+int gn_cloth_contact_lists(const double *x, const double *x0, const int64_t *csr, int B, int64_t total_verts, int max_verts, int buckets,
+                           const double *collision_host, int K, int flags, void *workspace, size_t workspace_bytes, int32_t *list_j, double *list_tm2,
+                           int32_t *list_n, int32_t *list_total, int64_t *diag, void *stream);
+
+/* gn_cloth_simulate_batch with the contact pass of the definition after the last colour of every substep: the lists of gn_cloth_contact_lists (list_j,
+ * list_tm2, list_n, rows of stride K), corr [*][3] fp64 workspace, diag as above (diag[b][2] += the active entries).  The caller runs at most the
+ * substeps up to the next rebuild per call and alternates the two entries on one stream.  A list index outside [0, V_b) sets *bad and is never
+ * dereferenced.  Refused by name, beside gn_cloth_simulate_batch's refusals: K outside [1, 64], relax (collision_host[3]) outside (0, 1], null lists. */
+int gn_cloth_simulate_contacts_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0, const double *alpha_t,
+                                     const int64_t *csr, const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints,
+                                     int64_t substeps, int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block, int64_t *bad,
+                                     const int32_t *list_j, const double *list_tm2, const int32_t *list_n, int K, const double *collision_host,
+                                     double *corr, int64_t *diag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
