@@ -468,11 +468,21 @@ extern "C" int gn_cloth_contact_buckets(int max_verts) {
 }
 
 // cell [*][4] int32, items [*] int32, x_ref [*][3] fp64, count / start / cursor [B][buckets] int32, each part on a 256-byte boundary
-static size_t cl_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// (the last one padded to it as well)
+static void cl_contact_ws(GnCarve &c, int64_t total_verts, int B, int buckets, ContactArgs &a) {
+    const size_t nv = (size_t)total_verts, table = (size_t)B * (size_t)buckets;
+    a.cell = c.take<int32_t>(4 * nv, 256);
+    a.items = c.take<int32_t>(nv, 256);
+    a.x_ref = c.take<double>(3 * nv, 256);
+    a.count = c.take<int32_t>(table, 256);
+    a.start = c.take<int32_t>(table, 256);
+    a.cursor = c.take<int32_t>(table, 256);
+    c.align(256);
+}
+
 extern "C" size_t gn_cloth_contact_workspace_bytes(int64_t total_verts, int B, int buckets) {
-    if (total_verts < 0 || B < 0 || buckets < 0) return 0;
-    return cl_align(16 * (size_t)total_verts) + cl_align(4 * (size_t)total_verts) + cl_align(24 * (size_t)total_verts) +
-           3 * cl_align(4 * (size_t)B * (size_t)buckets);
+    ContactArgs a;
+    return (total_verts < 0 || B < 0 || buckets < 0) ? 0 : gn_carve_bytes(cl_contact_ws, total_verts, B, buckets, a);
 }
 
 extern "C" int gn_cloth_contact_lists(const double *x, const double *x0, const int64_t *csr, int B, int64_t total_verts, int max_verts, int buckets,
@@ -495,17 +505,12 @@ extern "C" int gn_cloth_contact_lists(const double *x, const double *x0, const i
     if (B == 0 || total_verts == 0) return GN_OK;
     GN_REQUIRE(x && x0 && csr && diag && workspace, "%s: null pointer", name);
     GN_REQUIRE(!(flags & CL_LISTS_BUILD) || (list_j && list_tm2 && list_n && list_total), "%s: null list", name);
-    GN_REQUIRE(workspace_bytes >= gn_cloth_contact_workspace_bytes(total_verts, B, buckets), "%s: workspace of %zu bytes, %zu needed", name,
-               workspace_bytes, gn_cloth_contact_workspace_bytes(total_verts, B, buckets));
     ContactArgs a;
+    GnCarve c(workspace);
+    cl_contact_ws(c, total_verts, B, buckets, a);
+    GN_REQUIRE(workspace_bytes >= c.off, "%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, c.off);
     a.x = x; a.x0 = x0; a.csr = csr; a.list_j = list_j; a.list_tm2 = list_tm2; a.list_n = list_n; a.list_total = list_total; a.diag = diag;
     a.t2 = collision_host[0]; a.r2 = collision_host[1]; a.edge = collision_host[2]; a.K = K; a.buckets = buckets; a.flags = flags;
-    char *ws = (char *)workspace;
-    const size_t per_table = cl_align(4 * (size_t)B * (size_t)buckets);
-    a.cell = (int32_t *)ws; ws += cl_align(16 * (size_t)total_verts);
-    a.items = (int32_t *)ws; ws += cl_align(4 * (size_t)total_verts);
-    a.x_ref = (double *)ws; ws += cl_align(24 * (size_t)total_verts);
-    a.count = (int32_t *)ws; a.start = (int32_t *)(ws + per_table); a.cursor = (int32_t *)(ws + 2 * per_table);
     hipStream_t st = gn_stream(stream);
     const dim3 per_vertex((unsigned)gn_cdiv(max_verts, CL_BIN_BLOCK), (unsigned)B);
     if (max_verts == 0) return GN_OK;

@@ -64,6 +64,29 @@ static inline hipError_t gn_zero_stats(double *sum, double *sumsq, size_t n, hip
     return e != hipSuccess ? e : hipMemsetAsync(sumsq, 0, n * sizeof(double), st);
 }
 
+// A workspace layout is written ONCE, as a function over this cursor that returns the parts in order (a braced list evaluates left to right).  Host
+// only.  With a null base the walk only measures (every part comes back null) -- that is the gn_*_workspace_bytes entry; with the caller's pointer it
+// hands out the parts.  Either way `off` ends as the byte count.  Alignments are of the OFFSET: the base is expected on the layout's largest one.
+struct GnCarve {
+    char *base;
+    size_t off = 0;
+    explicit GnCarve(void *ws = nullptr) : base(static_cast<char *>(ws)) {}
+    void align(size_t a) { off = (off + a - 1) / a * a; }
+    void pad(size_t bytes) { off += bytes; }                // slack behind the parts that a size has always included
+    template <class T> T *take(size_t n, size_t a = alignof(T)) {
+        align(a);
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+};
+// the byte count of a layout: its carve function walked on a null base
+template <class F, class... A> static size_t gn_carve_bytes(F carve, A &&...shape) {
+    GnCarve c;
+    carve(c, shape...);
+    return c.off;
+}
+
 // squared distance in the pinned operation order ((dx*dx + dy*dy) + dz*dz), fp32, no FMA contraction
 // (the library is compiled with -ffp-contract=off; the intrinsics make it explicit).
 __device__ __forceinline__ float gn_sqdist3(float ax, float ay, float az, float bx, float by, float bz) {

@@ -192,6 +192,16 @@ extern "C" size_t gn_conv_affine_pack_wino_bytes(int B, int Cin, int Cout) {
     return ((size_t)B * (Cin / 16) * 36 + CPREP_WINO_PAD) * step;
 }
 
+// the workspace of both entries: mconst [B][Cin] fp64 (first: on 8 bytes), wfac [B][Cin], rowscale [B][Cout]
+struct CprepWs { double *mconst; float *wfac, *rowscale; };
+static CprepWs cprep_ws(GnCarve &c, int B, int Cin, int Cout) {
+    return {c.take<double>((size_t)B * Cin), c.take<float>((size_t)B * Cin), c.take<float>((size_t)B * Cout)};
+}
+
+extern "C" size_t gn_conv_affine_pack_workspace_bytes(int B, int Cin, int Cout) {
+    return (B < 0 || Cin <= 0 || Cout <= 0 || Cin % 16 || Cout % 32) ? 0 : gn_carve_bytes(cprep_ws, B, Cin, Cout);
+}
+
 static int conv_affine_pack_impl(const float *w, int Cin, int Cout, const float *a, const float *d, const double *sum, const double *sumsq,
                                  int64_t V, const float *coff, int B, void *pack, size_t pack_bytes, float *stage_a, float *stage_d,
                                  float *out_scale, float *kbias, void *ws, size_t ws_bytes, void *stream, bool wino) {
@@ -199,13 +209,11 @@ static int conv_affine_pack_impl(const float *w, int Cin, int Cout, const float 
     if (B == 0) return GN_OK;
     GN_REQUIRE(w && a && d && sum && sumsq && pack && stage_a && stage_d && out_scale && kbias && ws, "gn_conv_affine_pack: null pointer");
     GN_REQUIRE(pack_bytes >= (wino ? gn_conv_affine_pack_wino_bytes(B, Cin, Cout) : gn_conv_affine_pack_bytes(B, Cin, Cout)), "gn_conv_affine_pack: pack buffer too small");
-    const size_t need = (size_t)B * Cin * (4 + 8) + (size_t)B * Cout * 4;
-    GN_REQUIRE(ws_bytes >= need, "gn_conv_affine_pack: workspace too small (%zu < %zu)", ws_bytes, need);
+    GnCarve c(ws);
+    const auto [mconst, wfac, rowscale] = cprep_ws(c, B, Cin, Cout);
+    GN_REQUIRE(ws_bytes >= c.off, "gn_conv_affine_pack: workspace too small (%zu < %zu)", ws_bytes, c.off);
     GN_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)pack & 15) == 0, "gn_conv_affine_pack: ws must be 8-byte aligned, pack 16-byte aligned");
     hipStream_t st = gn_stream(stream);
-    double *mconst = (double *)ws;                                          // [B][Cin] (8-byte aligned first)
-    float *wfac = (float *)(mconst + (size_t)B * Cin);                      // [B][Cin]
-    float *rowscale = wfac + (size_t)B * Cin;                               // [B][Cout]
     const int nsteps = wino ? 36 : 27;
     const size_t step = (size_t)(Cout / 32) * 2 * 1024, per_sample = (size_t)(Cin / 16) * nsteps * step;
     GN_HIP(hipMemsetAsync((char *)pack + (size_t)B * per_sample, 0, (wino ? CPREP_WINO_PAD : 8) * step, st), "gn_conv_affine_pack");

@@ -87,11 +87,15 @@ __global__ __launch_bounds__(256) void gsb_spread_kernel(const float *__restrict
     for (int ch = lane; ch < C; ch += 64) grad_src[p * ldg + ch] = (in && ch < c_real) ? __fdiv_rn(g[ch], c) : 0.f;
 }
 
+// count [cells] (max / min / mean), owner_of [N] and the bids win [N][C] (max / min); sum needs nothing
+struct GsbWs { int32_t *count, *owner_of, *win; };
+static GsbWs gsb_ws(GnCarve &c, int64_t N, int C, int64_t cells, int reduce) {
+    const bool sel = reduce == GN_REDUCE_MAX || reduce == GN_REDUCE_MIN;
+    return {c.take<int32_t>(sel || reduce == GN_REDUCE_MEAN ? (size_t)cells : 0), c.take<int32_t>(sel ? (size_t)N : 0), c.take<int32_t>(sel ? (size_t)N * C : 0)};
+}
+
 extern "C" size_t gn_grid_scatter_bwd_workspace_bytes(int64_t N, int C, int64_t cells, int reduce) {
-    if (N <= 0) return 0;
-    if (reduce == GN_REDUCE_MAX || reduce == GN_REDUCE_MIN) return ((size_t)cells + (size_t)N + (size_t)N * C) * sizeof(int32_t);
-    if (reduce == GN_REDUCE_MEAN) return (size_t)cells * sizeof(int32_t);
-    return 0;
+    return N <= 0 ? 0 : gn_carve_bytes(gsb_ws, N, C, cells, reduce);
 }
 
 extern "C" int gn_grid_scatter_bwd(const float *grad_vol, const float *vol, const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int c_real,
@@ -101,16 +105,15 @@ extern "C" int gn_grid_scatter_bwd(const float *grad_vol, const float *vol, cons
     GN_REQUIRE(N >= 0 && C > 0 && cells >= 0 && ldg >= C, "gn_grid_scatter_bwd: bad sizes");
     GN_REQUIRE(c_real > 0 && c_real <= C, "gn_grid_scatter_bwd: c_real must be in [1, C]");
     GN_REQUIRE(N < (int64_t)0x7fffffff, "gn_grid_scatter_bwd: more than 2^31-2 points");
-    const size_t need = gn_grid_scatter_bwd_workspace_bytes(N, C, cells, reduce);
-    GN_REQUIRE(ws_bytes >= need && (ws || !need), "gn_grid_scatter_bwd: workspace too small (gn_grid_scatter_bwd_workspace_bytes)");
-    if (N == 0) return GN_OK;
+    if (N == 0) return GN_OK;                       // (needs no workspace)
+    GnCarve c(ws);
+    const auto [count, owner_of, win] = gsb_ws(c, N, C, cells, reduce);
+    GN_REQUIRE(c.off <= ws_bytes && (ws || !c.off), "gn_grid_scatter_bwd: workspace too small (gn_grid_scatter_bwd_workspace_bytes)");
     const bool sel = reduce == GN_REDUCE_MAX || reduce == GN_REDUCE_MIN;
     GN_REQUIRE(grad_vol && flat_idx && grad_src && (!sel || (vol && src && lds >= c_real)), "gn_grid_scatter_bwd: null pointer");
     hipStream_t st = gn_stream(stream);
     const dim3 grid((unsigned)gn_cdiv(N, 4)), block(256), pts((unsigned)gn_cdiv(N, 256));
-    int32_t *count = reinterpret_cast<int32_t *>(ws);
     if (sel) {
-        int32_t *owner_of = count + cells, *win = owner_of + N;
         GN_HIP(hipMemsetAsync(count, 0, (size_t)cells * sizeof(int32_t), st), "gn_grid_scatter_bwd(memset count)");
         GN_HIP(hipMemsetAsync(win, 0x7f, (size_t)N * C * sizeof(int32_t), st), "gn_grid_scatter_bwd(memset bids)");   // 0x7f7f7f7f > any point index
         hipLaunchKernelGGL(cell_owner_kernel<true>, pts, block, 0, st, flat_idx, N, cells, count, owner_of, (int32_t *)nullptr);
@@ -196,17 +199,18 @@ extern "C" int gn_global_max_pool_bwd(const float *grad_out, int ldg, const floa
 // ------------------------------------------------------------------------------------------------ SA gather
 // grad_x[j] = the sum of the feature part of the edge rows whose source is j (slot_src: gn_sa_gather's record of every row's source after the
 // self-loop rule, -1 = an empty slot), in ascending row index.  Positions are data: no gradient.
-extern "C" size_t gn_sa_gather_bwd_workspace_bytes(int64_t rows, int64_t n_points) { return (rows < 0 || n_points <= 0) ? 0 : inv_ws_bytes(n_points, rows); }
+extern "C" size_t gn_sa_gather_bwd_workspace_bytes(int64_t rows, int64_t n_points) { return (rows < 0 || n_points <= 0) ? 0 : gn_carve_bytes(inv_ws, n_points, rows); }
 
 extern "C" int gn_sa_gather_bwd(const float *grad_edge, int lde, const int32_t *slot_src, int64_t rows, int C, int64_t n_points, void *ws, size_t ws_bytes,
                                 float *grad_x, int ldgx, void *stream) {
     GN_REQUIRE(rows >= 0 && rows < (int64_t)0x7fffffff && n_points >= 0 && n_points < (int64_t)0x7fffffff && C > 0 && lde >= C && ldgx >= C,
                "gn_sa_gather_bwd: bad sizes");
     if (n_points == 0) return GN_OK;
-    GN_REQUIRE(ws && ws_bytes >= gn_sa_gather_bwd_workspace_bytes(rows, n_points), "gn_sa_gather_bwd: workspace too small (gn_sa_gather_bwd_workspace_bytes)");
+    GnCarve c(ws);
+    const InvWs w = inv_ws(c, n_points, rows);
+    GN_REQUIRE(ws && c.off <= ws_bytes, "gn_sa_gather_bwd: workspace too small (gn_sa_gather_bwd_workspace_bytes)");
     GN_REQUIRE(grad_x && (rows == 0 || (grad_edge && slot_src)), "gn_sa_gather_bwd: null pointer");
     hipStream_t st = gn_stream(stream);
-    const InvWs w = inv_ws(ws, n_points, rows);
     const int rc = inv_build(slot_src, rows, n_points, w, st, "gn_sa_gather_bwd");
     if (rc != GN_OK) return rc;
     ordered_sum(w, n_points, nullptr, 1, grad_edge, lde, C, grad_x, ldgx, st);
@@ -270,20 +274,24 @@ __global__ __launch_bounds__(256) void knn_coef_kernel(const int32_t *__restrict
         coef[(size_t)q * k + r] = nbr[(size_t)q * k + r] >= 0 ? __fdiv_rn(__fdiv_rn(1.0f, fmaxf(d2[(size_t)q * k + r], 1e-16f)), wsum) : 0.f;
 }
 
+// the inverse lists over the Nq k neighbour slots, keyed by the source, then coef [Nq][k]
+struct KnnBwdWs { InvWs inv; float *coef; };
+static KnnBwdWs knn_bwd_ws(GnCarve &c, int64_t Nq, int k, int64_t Ns) { return {inv_ws(c, Ns, Nq * k), c.take<float>((size_t)(Nq * k))}; }
+
 extern "C" size_t gn_knn_interpolate_bwd_workspace_bytes(int64_t Nq, int k, int64_t Ns) {
-    return (Nq < 0 || k < 1 || Ns <= 0) ? 0 : inv_ws_bytes(Ns, Nq * k) + (size_t)Nq * k * sizeof(float);
+    return (Nq < 0 || k < 1 || Ns <= 0) ? 0 : gn_carve_bytes(knn_bwd_ws, Nq, k, Ns);
 }
 
 extern "C" int gn_knn_interpolate_bwd(const int32_t *nbr, const float *d2, int Nq, int k, const float *grad_y, int ldg, int Ns, int C, void *ws, size_t ws_bytes,
                                       float *grad_xs, int ldgx, void *stream) {
     GN_REQUIRE(k >= 1 && Nq >= 0 && Ns >= 0 && C > 0 && ldg >= C && ldgx >= C && (int64_t)Nq * k < (int64_t)0x7fffffff, "gn_knn_interpolate_bwd: bad sizes");
     if (Ns == 0) return GN_OK;
-    GN_REQUIRE(ws && ws_bytes >= gn_knn_interpolate_bwd_workspace_bytes(Nq, k, Ns), "gn_knn_interpolate_bwd: workspace too small (gn_knn_interpolate_bwd_workspace_bytes)");
+    GnCarve c(ws);
+    const auto [w, coef] = knn_bwd_ws(c, Nq, k, Ns);
+    GN_REQUIRE(ws && c.off <= ws_bytes, "gn_knn_interpolate_bwd: workspace too small (gn_knn_interpolate_bwd_workspace_bytes)");
     GN_REQUIRE(grad_xs && (Nq == 0 || (nbr && d2 && grad_y)), "gn_knn_interpolate_bwd: null pointer");
     hipStream_t st = gn_stream(stream);
     const int64_t n = (int64_t)Nq * k;
-    const InvWs w = inv_ws(ws, Ns, n);
-    float *coef = reinterpret_cast<float *>(w.sorted + n);
     if (Nq > 0) hipLaunchKernelGGL(knn_coef_kernel, dim3((unsigned)gn_cdiv(Nq, 256)), dim3(256), 0, st, nbr, d2, Nq, k, coef);
     const int rc = inv_build(nbr, n, Ns, w, st, "gn_knn_interpolate_bwd");
     if (rc != GN_OK) return rc;
@@ -362,9 +370,13 @@ __global__ __launch_bounds__(256) void tri_grad_query_kernel(const float *__rest
     }
 }
 
+// the inverse lists over the n = 8 B M corner elements, keyed by the voxel, then the elements' keys [n] and weights [n]
+struct TriBwdWs { InvWs inv; int32_t *keys; float *wgt; };
+static TriBwdWs tri_bwd_ws(GnCarve &c, int64_t n, int64_t vox) { return {inv_ws(c, vox, n), c.take<int32_t>((size_t)n), c.take<float>((size_t)n)}; }
+
 extern "C" size_t gn_trilinear_sample_bwd_workspace_bytes(int B, int64_t M, int D, int H, int W) {
     const int64_t n = (int64_t)B * M * 8, vox = (int64_t)B * D * H * W;
-    return (B <= 0 || M < 0 || vox <= 0) ? 0 : inv_ws_bytes(vox, n) + (size_t)n * (sizeof(int32_t) + sizeof(float));
+    return (B <= 0 || M < 0 || vox <= 0) ? 0 : gn_carve_bytes(tri_bwd_ws, n, vox);
 }
 
 // grad_rows: (B M) rows of ldg floats; vol / grad_vol: B dense channel-last volumes (D, H, W, C); grad_vol or grad_query may be NULL (not asked for)
@@ -377,11 +389,10 @@ extern "C" int gn_trilinear_sample_bwd(const float *grad_rows, int ldg, const fl
     GN_REQUIRE(BM == 0 || (grad_rows && query), "gn_trilinear_sample_bwd: null pointer");
     hipStream_t st = gn_stream(stream);
     if (grad_vol) {
-        GN_REQUIRE(ws && ws_bytes >= gn_trilinear_sample_bwd_workspace_bytes(B, M, D, H, W), "gn_trilinear_sample_bwd: workspace too small (gn_trilinear_sample_bwd_workspace_bytes)");
         const int64_t n = BM * 8;
-        const InvWs w = inv_ws(ws, vox, n);
-        int32_t *keys = w.sorted + n;
-        float *wgt = reinterpret_cast<float *>(keys + n);
+        GnCarve c(ws);
+        const auto [w, keys, wgt] = tri_bwd_ws(c, n, vox);
+        GN_REQUIRE(ws && c.off <= ws_bytes, "gn_trilinear_sample_bwd: workspace too small (gn_trilinear_sample_bwd_workspace_bytes)");
         if (BM > 0) hipLaunchKernelGGL(tri_elements_kernel, dim3((unsigned)gn_cdiv(BM, 256)), dim3(256), 0, st, query, BM, M, D, H, W, keys, wgt);
         const int rc = inv_build(keys, n, vox, w, st, "gn_trilinear_sample_bwd");
         if (rc != GN_OK) return rc;

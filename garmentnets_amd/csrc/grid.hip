@@ -141,10 +141,12 @@ __global__ __launch_bounds__(256) void scatter_mean_finalize_kernel(const int32_
 struct MulWs {
     int32_t *owner_of, *npts, *start, *cursor, *lst, *sorted, *total;
 };
-__host__ __device__ inline MulWs mul_ws(void *ws, int64_t N) {
-    int32_t *w = reinterpret_cast<int32_t *>(ws);
-    return MulWs{w, w + N, w + 2 * N, w + 3 * N, w + 4 * N, w + 5 * N, w + 6 * N};
+static MulWs mul_ws(GnCarve &c, int64_t N) {                // [N] x 6, [1]
+    return {c.take<int32_t>(N), c.take<int32_t>(N), c.take<int32_t>(N), c.take<int32_t>(N), c.take<int32_t>(N), c.take<int32_t>(N), c.take<int32_t>(1)};
 }
+// mean / sum: the owners' fp64 sums acc [N][C], then owner_of [N] and npts [N]
+struct MeanWs { double *acc; int32_t *owner_of, *npts; };
+static MeanWs mean_ws(GnCarve &c, int64_t N, int C) { return {c.take<double>((size_t)N * C), c.take<int32_t>(N), c.take<int32_t>(N)}; }
 
 // every cell: 1 on the real channels (the identity an empty cell keeps), 0 on the pads [c_real, C)
 __global__ __launch_bounds__(256) void scatter_mul_fill_kernel(int64_t n, int C, int c_real, float *__restrict__ vol) {
@@ -172,9 +174,8 @@ __global__ __launch_bounds__(256) void scatter_mul_finalize_kernel(const float *
 
 extern "C" size_t gn_grid_scatter_workspace_bytes(int64_t N, int C, int reduce) {
     if (N <= 0) return 0;
-    if (reduce == GN_REDUCE_MEAN || reduce == GN_REDUCE_SUM) return (size_t)N * C * sizeof(double) + 2 * (size_t)N * sizeof(int32_t);
-    if (reduce == GN_REDUCE_MUL) return (6 * (size_t)N + 1) * sizeof(int32_t);
-    return 0;
+    if (reduce == GN_REDUCE_MEAN || reduce == GN_REDUCE_SUM) return gn_carve_bytes(mean_ws, N, C);
+    return reduce == GN_REDUCE_MUL ? gn_carve_bytes(mul_ws, N) : 0;
 }
 
 extern "C" int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat_idx, int64_t N, int C, int c_real, int64_t cells, int reduce,
@@ -182,8 +183,9 @@ extern "C" int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat
     GN_REQUIRE(N >= 0 && C > 0 && cells >= 0 && reduce >= GN_REDUCE_MAX && reduce <= GN_REDUCE_MUL, "gn_grid_scatter: bad arguments");
     GN_REQUIRE(c_real > 0 && c_real <= C, "gn_grid_scatter: c_real must be in [1, C]");
     GN_REQUIRE(N < (int64_t)0x7fffffff, "gn_grid_scatter: more than 2^31-2 points");
-    GN_REQUIRE(ws_bytes >= gn_grid_scatter_workspace_bytes(N, C, reduce) && (ws || !gn_grid_scatter_workspace_bytes(N, C, reduce)),
-               "gn_grid_scatter: workspace too small (gn_grid_scatter_workspace_bytes)");
+    const size_t need = gn_grid_scatter_workspace_bytes(N, C, reduce);
+    GN_REQUIRE(ws_bytes >= need && (ws || !need), "gn_grid_scatter: workspace too small (gn_grid_scatter_workspace_bytes)");
+    GnCarve c(ws);
     hipStream_t st = gn_stream(stream);
     if (!vol_is_zeroed) {       // (the caller may have zeroed both ahead of time, e.g. on a side stream next to the serial FPS kernels)
         if (reduce != GN_REDUCE_MUL) GN_HIP(hipMemsetAsync(vol, 0, sizeof(float) * (size_t)cells * C, st), "gn_grid_scatter(memset vol)");
@@ -207,15 +209,14 @@ extern "C" int gn_grid_scatter_ex(const float *src, int lds, const int32_t *flat
             hipLaunchKernelGGL(scatter_max_finalize_kernel<true>, grid, block, 0, st, flat_idx, N, C, vol, count_ws);
         }
     } else if (reduce == GN_REDUCE_MUL) {
-        const MulWs w = mul_ws(ws, N);
-        GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
+        const MulWs w = mul_ws(c, N);
+        GN_HIP(hipMemsetAsync(ws, 0, c.off, st), "gn_grid_scatter(memset ws)");
         hipLaunchKernelGGL(cell_owner_kernel<false>, pts, block, 0, st, flat_idx, N, cells, count_ws, w.owner_of, w.npts);
         inv_build_counted(w.owner_of, N, N, InvWs{w.npts, w.start, w.cursor, w.total, w.lst, w.sorted}, st);
         hipLaunchKernelGGL(scatter_mul_finalize_kernel, grid, block, 0, st, src, lds, flat_idx, N, C, w, vol, count_ws);
     } else {
-        double *acc = reinterpret_cast<double *>(ws);
-        int32_t *owner_of = reinterpret_cast<int32_t *>(acc + (size_t)N * C), *npts = owner_of + N;
-        GN_HIP(hipMemsetAsync(ws, 0, gn_grid_scatter_workspace_bytes(N, C, reduce), st), "gn_grid_scatter(memset ws)");
+        const auto [acc, owner_of, npts] = mean_ws(c, N, C);
+        GN_HIP(hipMemsetAsync(ws, 0, c.off, st), "gn_grid_scatter(memset ws)");
         hipLaunchKernelGGL(cell_owner_kernel<false>, pts, block, 0, st, flat_idx, N, cells, count_ws, owner_of, npts);
         hipLaunchKernelGGL(scatter_mean_accum_kernel, grid, block, 0, st, src, lds, N, C, owner_of, acc);
         if (reduce == GN_REDUCE_MEAN)

@@ -9,10 +9,9 @@
 struct InvWs {
     int32_t *cnt, *start, *cursor, *total, *lst, *sorted;      // [nkeys] x 3, [1], [n] x 2
 };
-static size_t inv_ws_bytes(int64_t nkeys, int64_t n) { return (size_t)(3 * nkeys + 1 + 2 * n) * sizeof(int32_t); }
-static InvWs inv_ws(void *ws, int64_t nkeys, int64_t n) {
-    int32_t *w = reinterpret_cast<int32_t *>(ws);
-    return InvWs{w, w + nkeys, w + 2 * nkeys, w + 3 * nkeys, w + 3 * nkeys + 1, w + 3 * nkeys + 1 + n};
+// (cnt, start, cursor and total stay back to back: inv_build zeroes them with one fill)
+static InvWs inv_ws(GnCarve &c, int64_t nkeys, int64_t n) {
+    return {c.take<int32_t>(nkeys), c.take<int32_t>(nkeys), c.take<int32_t>(nkeys), c.take<int32_t>(1), c.take<int32_t>(n), c.take<int32_t>(n)};
 }
 
 // keys[e] outside [0, nkeys): the element belongs to no destination (an empty slot, a corner beyond the border)

@@ -1061,23 +1061,39 @@ __global__ void mc_counts_kernel(const unsigned long long *__restrict__ total, i
     counts_dev[1] = (int64_t)(*total & 0xffffffffull);
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t mc33_ws_one(int n0, int n1, int n2) {
-    const size_t ncells = (size_t)(n0 - 1) * (n1 - 1) * (n2 - 1), nvox = (size_t)n0 * n1 * n2;
-    const size_t nb = (ncells + SCAN_ELEMS - 1) / SCAN_ELEMS;
-    return align256(ncells * 4) + align256(ncells) + align256(nvox * 16) + align256((nb + 1) * 8);
+static McDims mc_dims(int n0, int n1, int n2) {
+    McDims d;
+    d.n0 = n0; d.n1 = n1; d.n2 = n2; d.c0 = n0 - 1; d.c1 = n1 - 1; d.c2 = n2 - 1;
+    d.ncells = (int64_t)d.c0 * d.c1 * d.c2;
+    d.nvox = (int64_t)n0 * n1 * n2;
+    d.s_cinfo = d.s_cnt = d.s_edge = d.s_bsum = d.s_verts = d.s_faces = 0;
+    return d;
 }
 
-extern "C" size_t gn_mc33_workspace_bytes(int n0, int n1, int n2) {
-    if (n0 < 2 || n1 < 2 || n2 < 2) return 0;
-    return mc33_ws_one(n0, n1, n2) + 256;
+// one array per volume, every volume's on a 256-byte boundary: the pointer to the first, and the elements from one volume's to the next
+template <class T> static T *mc_per_volume(GnCarve &c, int batch, int64_t n, int64_t &stride) {
+    stride = (int64_t)(((size_t)n * sizeof(T) + 255) / 256 * 256 / sizeof(T));
+    return c.take<T>((size_t)batch * (size_t)stride, 256);
+}
+
+// the workspace, array by array (mc33_batch_impl says what each holds); fills the strides of d.  256 bytes of slack at the end.
+struct McWs { int32_t *cinfo; unsigned char *cnt8; int32_t *edge_vid; unsigned long long *bsum; };
+static McWs mc33_ws(GnCarve &c, int batch, McDims &d) {
+    const int64_t nb = gn_cdiv(d.ncells, SCAN_ELEMS);
+    const McWs w = {mc_per_volume<int32_t>(c, batch, d.ncells, d.s_cinfo), mc_per_volume<unsigned char>(c, batch, d.ncells, d.s_cnt),
+                    mc_per_volume<int32_t>(c, batch, 4 * d.nvox, d.s_edge),
+                    mc_per_volume<unsigned long long>(c, batch, nb + 1, d.s_bsum)};     // a volume's nb block sums, then its total
+    c.pad(256);
+    return w;
 }
 
 extern "C" size_t gn_mc33_batch_workspace_bytes(int batch, int n0, int n1, int n2) {
     if (n0 < 2 || n1 < 2 || n2 < 2 || batch < 1) return 0;
-    return (size_t)batch * mc33_ws_one(n0, n1, n2) + 256;
+    McDims d = mc_dims(n0, n1, n2);
+    return gn_carve_bytes(mc33_ws, batch, d);
 }
+
+extern "C" size_t gn_mc33_workspace_bytes(int n0, int n1, int n2) { return gn_mc33_batch_workspace_bytes(1, n0, n1, n2); }
 
 // `batch` volumes of the same shape and level in one set of launches (blockIdx.y = volume): vol [batch][n0][n1][n2], verts / normals
 // [batch][cap_v][3], faces [batch][cap_f][3], values [batch][cap_v], counts_dev [batch][2].  Workspace, array by array: [batch] tiling rows
@@ -1092,24 +1108,14 @@ static int mc33_batch_impl(const float *vol, int batch, int n0, int n1, int n2, 
     GN_REQUIRE(n0 >= 2 && n1 >= 2 && n2 >= 2, "gn_mc33: input volume must be at least 2x2x2");
     GN_REQUIRE(batch >= 0 && batch <= 65535, "gn_mc33_batch: bad batch");
     if (batch == 0) return GN_OK;
-    GN_REQUIRE(ws != nullptr && ws_bytes >= gn_mc33_batch_workspace_bytes(batch, n0, n1, n2), "gn_mc33: workspace too small");
+    McDims d = mc_dims(n0, n1, n2);
+    GnCarve c(ws);
+    const auto [cinfo, cnt8, edge_vid, bsum] = mc33_ws(c, batch, d);
+    GN_REQUIRE(ws != nullptr && ws_bytes >= c.off, "gn_mc33: workspace too small");
     GN_REQUIRE(cap_v >= 0 && cap_f >= 0, "gn_mc33: bad capacities");
-    McDims d;
-    d.n0 = n0; d.n1 = n1; d.n2 = n2; d.c0 = n0 - 1; d.c1 = n1 - 1; d.c2 = n2 - 1;
-    d.ncells = (int64_t)d.c0 * d.c1 * d.c2;
-    d.nvox = (int64_t)n0 * n1 * n2;
     const int64_t nb = gn_cdiv(d.ncells, SCAN_ELEMS);
-    d.s_cinfo = (int64_t)(align256(d.ncells * 4) / 4);
-    d.s_cnt = (int64_t)align256(d.ncells);
-    d.s_edge = (int64_t)(align256(d.nvox * 16) / 4);
-    d.s_bsum = (int64_t)(align256((nb + 1) * 8) / 8);
     d.s_verts = cap_v * 3;
     d.s_faces = cap_f * 3;
-    char *p = (char *)ws;
-    int32_t *cinfo = (int32_t *)p; p += (size_t)batch * d.s_cinfo * 4;
-    unsigned char *cnt8 = (unsigned char *)p; p += (size_t)batch * d.s_cnt;
-    int32_t *edge_vid = (int32_t *)p; p += (size_t)batch * d.s_edge * 4;
-    unsigned long long *bsum = (unsigned long long *)p;
     unsigned long long *total = bsum + nb;
     hipStream_t st = gn_stream(stream);
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1257,15 +1263,24 @@ __global__ void unpack_counts_kernel(const unsigned long long *__restrict__ tota
     counts[2] = (int64_t)*bad;
 }
 
-extern "C" size_t gn_mesh_compact_workspace_bytes(int64_t V, int64_t F) {
+// n = max(V, F): flags [n], their exclusive scan ex [n], the scan's block sums and total, the bad flag (cleared as 8 bytes) and 8 bytes of slack
+struct CompactWs { unsigned long long *flags, *ex, *bsum, *total; unsigned *bad; };
+static CompactWs compact_ws(GnCarve &c, int64_t V, int64_t F) {
     const size_t n = (size_t)(V > F ? V : F), nb = (n + SCAN_ELEMS - 1) / SCAN_ELEMS;
-    return sizeof(unsigned long long) * (2 * n + nb + 3);
+    const CompactWs w = {c.take<unsigned long long>(n), c.take<unsigned long long>(n), c.take<unsigned long long>(nb), c.take<unsigned long long>(1),
+                         c.take<unsigned>(2)};
+    c.pad(8);
+    return w;
 }
+
+extern "C" size_t gn_mesh_compact_workspace_bytes(int64_t V, int64_t F) { return gn_carve_bytes(compact_ws, V, F); }
 
 extern "C" int gn_mesh_compact(const void *verts, int vert_bytes, const int32_t *faces, const unsigned char *on_surface, int64_t V, int64_t F,
                                void *ws, size_t ws_bytes, void *out_verts, int32_t *out_faces, int64_t *counts, void *stream) {
     GN_REQUIRE(V >= 0 && F >= 0 && V < (1ll << 31) && F < (1ll << 31) && vert_bytes > 0 && vert_bytes % 4 == 0, "gn_mesh_compact: bad sizes");
-    GN_REQUIRE(ws_bytes >= gn_mesh_compact_workspace_bytes(V, F), "gn_mesh_compact: workspace too small");
+    GnCarve c(ws);
+    const auto [flags, ex, bsum, total, bad] = compact_ws(c, V, F);
+    GN_REQUIRE(ws_bytes >= c.off, "gn_mesh_compact: workspace too small");
     hipStream_t st = gn_stream(stream);
     const int64_t n = V > F ? V : F;
     if (n == 0 || F == 0) {                         // (V == 0 with faces: every index is out of range -> the bad flag below)
@@ -1273,8 +1288,6 @@ extern "C" int gn_mesh_compact(const void *verts, int vert_bytes, const int32_t 
         return GN_OK;
     }
     const int64_t nb = gn_cdiv(n, SCAN_ELEMS);
-    unsigned long long *flags = reinterpret_cast<unsigned long long *>(ws), *ex = flags + n, *bsum = ex + n, *total = bsum + nb;
-    unsigned *bad = reinterpret_cast<unsigned *>(total + 1);
     GN_HIP(hipMemsetAsync(flags, 0, sizeof(unsigned long long) * (size_t)n, st), "gn_mesh_compact");
     GN_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned long long), st), "gn_mesh_compact");
     hipLaunchKernelGGL(compact_mark_kernel, dim3((unsigned)gn_cdiv(F, 256)), dim3(256), 0, st, faces, on_surface, V, F, flags, bad);

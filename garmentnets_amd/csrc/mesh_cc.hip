@@ -89,8 +89,16 @@ __global__ void cc_mask_kernel(int *__restrict__ parent, int64_t V, const unsign
     mask[i] = (x == win) ? 1 : 0;
 }
 
+// parent [V], count [V], then 64 bytes that hold the best key (on 16 bytes) and the bad flag
+struct CcWs { int *parent, *count; unsigned long long *best; int *bad; };
+static CcWs cc_ws(GnCarve &c, int64_t V) {
+    const CcWs w = {c.take<int>(V), c.take<int>(V), c.take<unsigned long long>(1, 16), c.take<int>(1)};
+    c.pad((size_t)V * 8 + 64 - c.off);
+    return w;
+}
+
 extern "C" size_t gn_mesh_largest_component_workspace_bytes(int64_t V) {
-    return V < 0 ? 0 : (size_t)V * 8 + 64;                                 // parent + count, best key, bad flag
+    return V < 0 ? 0 : gn_carve_bytes(cc_ws, V);
 }
 
 extern "C" int gn_mesh_largest_component(const int32_t *faces, int64_t F, int64_t V, void *ws, size_t ws_bytes, unsigned char *mask, int32_t *label,
@@ -108,10 +116,9 @@ extern "C" int gn_mesh_largest_component(const int32_t *faces, int64_t F, int64_
         return GN_OK;
     }
     GN_REQUIRE((faces || F == 0) && mask && ws, "gn_mesh_largest_component: null pointer");
-    GN_REQUIRE(ws_bytes >= gn_mesh_largest_component_workspace_bytes(V), "gn_mesh_largest_component: workspace too small");
-    int *parent = (int *)ws, *count = parent + V;
-    unsigned long long *best = (unsigned long long *)(((uintptr_t)(count + V) + 15) & ~(uintptr_t)15);
-    int *bad = (int *)(best + 1);
+    GnCarve c(ws);
+    const auto [parent, count, best, bad] = cc_ws(c, V);
+    GN_REQUIRE(ws_bytes >= c.off, "gn_mesh_largest_component: workspace too small");
     const unsigned gv = (unsigned)gn_cdiv(V, 256), gf = (unsigned)gn_cdiv(F, 256);
     hipLaunchKernelGGL(cc_init_kernel, dim3(gv), dim3(256), 0, st, parent, count, V, best, bad);
     if (F > 0) hipLaunchKernelGGL(cc_hook_kernel, dim3(gf), dim3(256), 0, st, faces, F, V, parent, bad);

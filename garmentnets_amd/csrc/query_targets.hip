@@ -201,20 +201,26 @@ static bool qt_host_needs_d(int kind) { return kind == GN_QT_DISTANCE || kind ==
 
 extern "C" int gn_query_targets_face_chunk(void) { return QT_FACE_CHUNK; }
 
-extern "C" size_t gn_query_targets_workspace_bytes(int B, int64_t M, int64_t max_nf, int kind) {
-    if (B <= 0 || M <= 0 || max_nf < 0 || !qt_kind_ok(kind)) return 0;
-    const size_t per = (qt_host_needs_w(kind) ? 8 : 0) + (qt_host_needs_d(kind) ? 12 : 0);
-    return (size_t)B * (size_t)qt_chunks(max_nf) * (size_t)M * per;
+// the partials, [B][chunks][M] each: d2 and face for the kinds that fold a distance, w for those that fold a winding number (the doubles first, the
+// int32 face numbers last: every part aligned).  A part the kind does not need is empty; the kernels never touch its pointer.
+struct QtWs { double *d2, *w; int32_t *face; };
+static QtWs qt_ws(GnCarve &c, int B, int64_t M, int64_t max_nf, int kind) {
+    const size_t n = (size_t)B * (size_t)qt_chunks(max_nf) * (size_t)M;
+    return {c.take<double>(qt_host_needs_d(kind) ? n : 0), c.take<double>(qt_host_needs_w(kind) ? n : 0), c.take<int32_t>(qt_host_needs_d(kind) ? n : 0)};
 }
 
-// the two launches of both entries (every argument checked by the caller)
+extern "C" size_t gn_query_targets_workspace_bytes(int B, int64_t M, int64_t max_nf, int kind) {
+    return (B <= 0 || M <= 0 || max_nf < 0 || !qt_kind_ok(kind)) ? 0 : gn_carve_bytes(qt_ws, B, M, max_nf, kind);
+}
+
+// the workspace check and the two launches of both entries (every other argument checked by the caller)
 static int qt_launch(const char *who, const QtMeshes &ms, const float *query, int B, int64_t M, int64_t max_nf, int kind, int use_clip, float tsdf_clip,
-                     int absolute, void *ws, float *target, double *w, double *d2, int32_t *face_idx, int64_t *bad, void *stream) {
-    const int64_t C = qt_chunks(max_nf), n = (int64_t)B * C * M;
+                     int absolute, void *ws, size_t ws_bytes, float *target, double *w, double *d2, int32_t *face_idx, int64_t *bad, void *stream) {
+    GnCarve c(ws);
+    const auto [ws_d2, ws_w, ws_face] = qt_ws(c, B, M, max_nf, kind);
+    GN_REQUIRE(c.off == 0 || (ws && ws_bytes >= c.off), "%s: short workspace (%zu bytes, %zu needed)", who, ws ? ws_bytes : (size_t)0, c.off);
+    const int64_t C = qt_chunks(max_nf);
     const bool need_w = qt_host_needs_w(kind), need_d = qt_host_needs_d(kind);
-    double *ws_d2 = (double *)ws;                                     // [B][C][M] doubles first, the int32 face numbers last: every part aligned
-    double *ws_w = ws_d2 + (need_d ? n : 0);
-    int32_t *ws_face = (int32_t *)(ws_w + (need_w ? n : 0));
     const dim3 grid((unsigned)(M > 0 ? gn_cdiv(M, QT_SPAN) : 1), (unsigned)C, (unsigned)B);
     hipStream_t st = gn_stream(stream);
     if (need_w && need_d)
@@ -242,10 +248,8 @@ extern "C" int gn_query_targets_batch(const float *query, const float *verts, co
     GN_REQUIRE(mesh_csr && bad, "gn_query_targets_batch: null pointer (mesh_csr / bad)");
     GN_REQUIRE(max_nf == 0 || (verts && faces), "gn_query_targets_batch: null pointer (verts / faces with max_nf=%lld)", (long long)max_nf);
     GN_REQUIRE(M == 0 || (query && target), "gn_query_targets_batch: null pointer (query / target with M=%lld)", (long long)M);
-    const size_t need = gn_query_targets_workspace_bytes(B, M, max_nf, kind);
-    GN_REQUIRE(need == 0 || (ws && ws_bytes >= need), "gn_query_targets_batch: short workspace (%zu bytes, %zu needed)", ws ? ws_bytes : (size_t)0, need);
     const QtMeshes ms = {verts, faces, mesh_csr, nullptr, nullptr, 0, 0};
-    return qt_launch("gn_query_targets_batch", ms, query, B, M, max_nf, kind, use_clip, tsdf_clip, absolute, ws, target, w, d2, face_idx, bad, stream);
+    return qt_launch("gn_query_targets_batch", ms, query, B, M, max_nf, kind, use_clip, tsdf_clip, absolute, ws, ws_bytes, target, w, d2, face_idx, bad, stream);
 }
 
 extern "C" int gn_resident_query_targets(const GnResidentStore *store, const int32_t *slots, int B, int64_t M, int task_space, int64_t total_verts,
@@ -257,8 +261,6 @@ extern "C" int gn_resident_query_targets(const GnResidentStore *store, const int
     GN_REQUIRE(store->meta && store->faces && slots && query && value && bad, "gn_resident_query_targets: null pointer");
     const float *verts = task_space ? store->task_verts : store->nocs_verts;
     GN_REQUIRE(verts != nullptr, "gn_resident_query_targets: the store holds no %s vertices", task_space ? "task-space" : "NOCS");
-    const size_t need = gn_query_targets_workspace_bytes(B, M, max_nf, kind);
-    GN_REQUIRE(ws && ws_bytes >= need, "gn_resident_query_targets: short workspace (%zu bytes, %zu needed)", ws ? ws_bytes : (size_t)0, need);
     const QtMeshes ms = {verts, store->faces, nullptr, store->meta, slots, total_verts, store->n};
-    return qt_launch("gn_resident_query_targets", ms, query, B, M, max_nf, kind, use_clip, tsdf_clip, absolute, ws, value, nullptr, nullptr, nullptr, bad, stream);
+    return qt_launch("gn_resident_query_targets", ms, query, B, M, max_nf, kind, use_clip, tsdf_clip, absolute, ws, ws_bytes, value, nullptr, nullptr, nullptr, bad, stream);
 }

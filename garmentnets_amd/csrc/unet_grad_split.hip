@@ -137,7 +137,11 @@ struct BwsArgs {
     int tiles_z, tiles_y, tiles_x, ntiles, per_chain;
 };
 
-static int64_t bws_header_bytes(int B) { return gn_cdiv((int64_t)16 + 4 * (int64_t)B, 256) * 256; }
+// the workspace: the header's 4 + B floats on 16 bytes, then from the next 256-byte boundary one partial [27][Cin32][Cout] per chain
+struct BwsWs { float *hdr, *part; };
+static BwsWs bws_ws(GnCarve &c, int B, int chains, int Cin, int Cout) {
+    return {c.take<float>(4 + (size_t)B, 16), c.take<float>((size_t)chains * 27 * (size_t)(gn_cdiv(Cin, BWS_CI) * BWS_CI) * Cout, 256)};
+}
 
 static int bws_chains(int B, int D, int H, int W, int Cin, int Cout, int *per_chain) {
     const int64_t ntiles = (int64_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX);
@@ -327,8 +331,7 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_split_fold_kernel(const
 
 extern "C" size_t gn_conv3d_bwd_weight_split_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 32 != 0) return 0;
-    const int chains = bws_chains(B, D, H, W, Cin, Cout, nullptr);
-    return (size_t)bws_header_bytes(B) + (size_t)chains * 27 * (size_t)(gn_cdiv(Cin, BWS_CI) * BWS_CI) * Cout * sizeof(float);
+    return gn_carve_bytes(bws_ws, B, bws_chains(B, D, H, W, Cin, Cout, nullptr), Cin, Cout);
 }
 
 extern "C" int gn_conv3d_bwd_weight_split(const float *src0, int C0, const float *src1, int C1, const float *a, const float *d, const float *x_inv,
@@ -350,15 +353,16 @@ extern "C" int gn_conv3d_bwd_weight_split(const float *src0, int C0, const float
     }
     GN_REQUIRE(src0 && a && d && dy && gmax && dw && ws && (C1 == 0 || src1), "gn_conv3d_bwd_weight_split: null pointer");
     GN_REQUIRE(((uintptr_t)ws & 15) == 0, "gn_conv3d_bwd_weight_split: the workspace must be 16-byte aligned");
-    float *hdr = (float *)ws;
+    BwsArgs p;
+    const int chains = bws_chains(B, D, H, W, Cin, Cout, &p.per_chain);
+    GnCarve c(ws);
+    const auto [hdr, part] = bws_ws(c, B, chains, Cin, Cout);
     hipLaunchKernelGGL(bws_scales_kernel, dim3(1), dim3(64), 0, st, x_inv, gmax, B, hdr);
     GN_LAUNCH_CHECK("gn_conv3d_bwd_weight_split");
-    BwsArgs p;
-    p.src0 = src0; p.src1 = src1; p.a = a; p.d = d; p.y = y; p.dy = dy; p.hdr = hdr; p.part = (float *)((char *)ws + bws_header_bytes(B));
+    p.src0 = src0; p.src1 = src1; p.a = a; p.d = d; p.y = y; p.dy = dy; p.hdr = hdr; p.part = part;
     p.C0 = C0; p.C1 = C1; p.B = B; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.Cin32 = (int)gn_cdiv(Cin, BWS_CI) * BWS_CI;
     p.tiles_z = (int)gn_cdiv(D, GN_CONV_TZ); p.tiles_y = (int)gn_cdiv(H, GN_CONV_TY); p.tiles_x = (int)gn_cdiv(W, GN_CONV_TX);
     p.ntiles = B * p.tiles_z * p.tiles_y * p.tiles_x;
-    const int chains = bws_chains(B, D, H, W, Cin, Cout, &p.per_chain);
     const int nco = Cout % 64 == 0 ? 2 : 1;
     const size_t lds = (size_t)2 * BWS_HALO_BYTES + (size_t)2 * nco * BWS_G_BYTES;
     const dim3 grid((unsigned)((p.Cin32 / BWS_CI) * (Cout / (32 * nco))), (unsigned)chains);

@@ -842,9 +842,14 @@ __global__ __launch_bounds__(256) void conv_fill_inactive_kernel(SplitArgs p, co
     }
 }
 
+// the occupancy-aware launch's workspace: 16 ints that open with the number of active tiles, then the list of them (at most every 4 x 8 x 8 tile)
+struct OccWs { int *count, *list; };
+static OccWs occ_ws_parts(GnCarve &c, int B, int D, int H, int W) {
+    return {c.take<int>(16), c.take<int>((size_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX))};
+}
+
 extern "C" size_t gn_conv3d_occupancy_workspace_bytes(int B, int D, int H, int W) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    return ((size_t)B * gn_cdiv(D, GN_CONV_TZ) * gn_cdiv(H, GN_CONV_TY) * gn_cdiv(W, GN_CONV_TX) + 16) * sizeof(int);
+    return (B < 0 || D <= 0 || H <= 0 || W <= 0) ? 0 : gn_carve_bytes(occ_ws_parts, B, D, H, W);
 }
 
 // The direct variants: kernel, block size, tile depth (4: 4 x 8 x 8 tiles, 8: the x-strip kernel's 8 x 8 x 8), output channels per workgroup and the name
@@ -925,11 +930,12 @@ static int conv3d_gcr_split_impl(const float *src0, int C0, const float *src1, i
                "gn_conv3d_gcr_split: the occupancy-aware launch needs a two-plane mode, kreach 1 or 2 and dims > 2 kreach");
     if (tile_active) {
         // the active tiles as a compact list at the chosen kernel's tile granularity + the inactive tiles' constants (and their statistics)
-        GN_REQUIRE(occ_ws && occ_ws_bytes >= gn_conv3d_occupancy_workspace_bytes(B, D, H, W) && ((uintptr_t)occ_ws & 3) == 0,
+        GnCarve c(occ_ws);
+        const auto [count, list] = occ_ws_parts(c, B, D, H, W);
+        GN_REQUIRE(occ_ws && occ_ws_bytes >= c.off && ((uintptr_t)occ_ws & 3) == 0,
                    "gn_conv3d_gcr_split: the occupancy-aware launch needs gn_conv3d_occupancy_workspace_bytes(B, D, H, W) bytes of workspace");
         GN_REQUIRE(Cout % 4 == 0 && Cout <= 1024, "gn_conv3d_gcr_split: the occupancy-aware launch needs Cout <= 1024");
         const int pair = (strip || wino32) ? 2 : 1;
-        int *count = (int *)occ_ws, *list = count + 16;
         hipLaunchKernelGGL(occ_compact_kernel, dim3(1), dim3(1024), 0, st, tile_active, B, tz, p.tiles_y * p.tiles_x, pair, list, count);
         hipLaunchKernelGGL(conv_fill_inactive_kernel, dim3(p.tiles_y * p.tiles_x, B), dim3(256), 0, st, p, tile_active, pair);
         p.active_list = list;

@@ -95,7 +95,7 @@ def fps(pos, ptr, out_ptr, max_points, m_total, start_idx=None, gap_out=None, ne
             _chk(t, torch.float32, name)
     # more points per example than the LDS-resident kernels hold: running distances in a device workspace
     nbytes = _lib.load().gn_fps_workspace_bytes(B, int(max_points))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pos.device) if nbytes else None
+    ws = _ws(nbytes, pos.device) if nbytes else None
     _lib.call("gn_fps_nested_ws", _p(pos), _p(ptr), _p(out_ptr), _p(start_idx), B, int(max_points), _p(idx), _p(gap_out), _p(nested_gap),
               _p(ws), nbytes, _stream())
     return idx
@@ -287,7 +287,7 @@ def grid_scatter(src, flat_idx, B, grid_shape, reduce, with_stats=False, prezero
         cnt = torch.empty(cells, dtype=_i32, device=src.device)
     code = REDUCE_CODES[reduce]
     nbytes = _lib.load().gn_grid_scatter_workspace_bytes(N, C, code)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if nbytes else None
+    ws = _ws(nbytes, src.device) if nbytes else None
     _lib.call("gn_grid_scatter_ex", _p(src), rows_view(src)[1], _p(flat_idx), N, C, C if c_real is None else int(c_real), cells, code, _p(vol), _p(cnt),
               _p(ws), nbytes, 0 if prezeroed is None else 1, _stream())
     if not with_stats:
@@ -535,7 +535,8 @@ def pack_conv_weight_split_device(w, mode, c_lo=0, c_n=None):
         raise ValueError(f"unknown split mode {mode}")
     w, cout, cin, c_lo, c_n = _device_pack_args("pack_conv_weight_split_device", w, c_lo, c_n)
     planes = 2 if mode == SPLIT_F16X2 else int(mode)
-    pk = torch.empty((c_n // 16 * 27 + 8, cout // 32 * planes * 512), dtype=torch.int16, device=w.device)
+    nbytes = _lib.load().gn_weight_pack_split_bytes(c_n, cout, int(mode))
+    pk = torch.empty((nbytes // 2,), dtype=torch.int16, device=w.device).view(-1, cout // 32 * planes * 512)      # one row per (slice, tap) step
     scale = torch.empty((cout,), dtype=torch.float32, device=w.device)
     _lib.call("gn_weight_pack_split", _p(w), cout, cin, c_lo, c_n, int(mode), _p(pk), pk.numel() * 2, _p(scale), _stream())
     return SplitPack(pk, mode, scale)
@@ -544,7 +545,8 @@ def pack_conv_weight_split_device(w, mode, c_lo=0, c_n=None):
 def pack_conv_weight_split_wino_device(w, c_lo=0, c_n=None):
     """pack_conv_weight_split_wino(w[:, c_lo:c_lo + c_n]) built on the device (csrc/weight_pack.hip); as pack_conv_weight_split_device"""
     w, cout, cin, c_lo, c_n = _device_pack_args("pack_conv_weight_split_wino_device", w, c_lo, c_n)
-    pk = torch.empty((c_n // 16 * 36 + 6, cout // 32 * 2 * 512), dtype=torch.int16, device=w.device)
+    nbytes = _lib.load().gn_weight_pack_split_wino_bytes(c_n, cout)
+    pk = torch.empty((nbytes // 2,), dtype=torch.int16, device=w.device).view(-1, cout // 32 * 2 * 512)
     scale = torch.empty((cout,), dtype=torch.float32, device=w.device)
     _lib.call("gn_weight_pack_split_wino", _p(w), cout, cin, c_lo, c_n, _p(pk), pk.numel() * 2, _p(scale), _stream())
     return SplitPack(pk, SPLIT_F16X2, scale)
@@ -556,7 +558,7 @@ def pack_upconv_weight_device(w, c0, mode):
     if mode not in (SPLIT_BF16X2, SPLIT_F16X2):
         raise ValueError("gn_upconv_partial runs the two-plane modes only")
     w, cout, cin, c0, c1 = _device_pack_args("pack_upconv_weight_device", w, c0, None)
-    pk = torch.empty((c1 // 16 * 64 * (cout // 32) * 2 * 512,), dtype=torch.int16, device=w.device)
+    pk = torch.empty((_lib.load().gn_weight_pack_upconv_bytes(c1, cout) // 2,), dtype=torch.int16, device=w.device)
     scale = torch.empty((8 * cout,), dtype=torch.float32, device=w.device)
     _lib.call("gn_weight_pack_upconv", _p(w), cout, cin, c0, int(mode), _p(pk), pk.numel() * 2, _p(scale), _stream())
     return SplitPack(pk, mode, scale)
@@ -610,9 +612,11 @@ def conv_affine_pack(weight, a, d, stats, rest=None, wino=False):
     r.stage_d = torch.empty((B, cin), dtype=torch.float32, device=dev)
     r.out_scale = torch.empty((B, cout), dtype=torch.float32, device=dev)
     r.kbias = torch.empty((B, 64, cout), dtype=torch.float32, device=dev)
-    ws = torch.empty((B * cin * 12 + B * cout * 4 + 16,), dtype=torch.uint8, device=dev)
+    # (16 bytes more than the entry asks for, as this wrapper has always passed: the recorded launch traces of the UNet hold that scalar)
+    ws_bytes = _lib.load().gn_conv_affine_pack_workspace_bytes(B, cin, cout) + 16
+    ws = _ws(ws_bytes, dev)
     _lib.call("gn_conv_affine_pack" + sfx, _p(w), cin, cout, _p(a), _p(d), _p(stats[0]), _p(stats[1]), int(stats[2]), _p(rest), B, _p(r.pack), nbytes,
-              _p(r.stage_a), _p(r.stage_d), _p(r.out_scale), _p(r.kbias), _p(ws), ws.numel(), _stream())
+              _p(r.stage_a), _p(r.stage_d), _p(r.out_scale), _p(r.kbias), _p(ws), ws_bytes, _stream())
     return r
 
 
@@ -635,7 +639,7 @@ def _occupancy_ws(tile_active, B, D, H, W, device):
     if tile_active is None:
         return None, 0
     n = _lib.load().gn_conv3d_occupancy_workspace_bytes(B, D, H, W)
-    return torch.empty((n,), dtype=torch.uint8, device=device), n
+    return _ws(n, device), n
 
 
 def _conv_outputs(src, cout, with_stats, tile_active):
@@ -948,7 +952,7 @@ def ggm3d_batch_range(vols, sigma, accum_bits=64):
     out = torch.empty_like(vols)
     rng = torch.empty((B, 2), dtype=torch.float32, device=vols.device)
     nws = _lib.load().gn_ggm3d_range_workspace_bytes(B, n0, n1, n2)             # a (min, max) pair per wave of the fused launch; scratch
-    ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=vols.device)
+    ws = _ws(nws, vols.device)
     _lib.call("gn_ggm3d_batch_ex", _p(vols), B, n0, n1, n2, float(sigma), _p(tmp), _p(out), int(accum_bits), _p(rng), _p(ws), nws, _stream())
     return out, rng
 
@@ -970,7 +974,7 @@ def mc33_batch(vols, level, cap_v, cap_f):
     B, n0, n1, n2 = vols.shape
     dev = vols.device
     nbytes = _lib.load().gn_mc33_batch_workspace_bytes(B, n0, n1, n2)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     verts = torch.zeros((B, cap_v, 3), dtype=torch.float32, device=dev)      # rows past a volume's vertex count stay finite (padded consumers)
     faces = torch.empty((B, cap_f, 3), dtype=_i32, device=dev)
     normals = torch.empty((B, cap_v, 3), dtype=torch.float32, device=dev)
@@ -992,7 +996,7 @@ def mc33_batch_profiled(vols, level, cap_v=None):
     cap_f = 2 * cap_v + 64
     while True:
         nbytes = _lib.load().gn_mc33_batch_workspace_bytes(B, n0, n1, n2)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _ws(nbytes, dev)
         verts = torch.empty((B, cap_v, 3), dtype=torch.float32, device=dev)
         faces = torch.empty((B, cap_f, 3), dtype=_i32, device=dev)
         normals = torch.empty((B, cap_v, 3), dtype=torch.float32, device=dev)
@@ -1019,7 +1023,7 @@ def mc33(vol, level, cap_v, cap_f):
     n0, n1, n2 = vol.shape
     dev = vol.device
     nbytes = _lib.load().gn_mc33_workspace_bytes(n0, n1, n2)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     verts = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
     faces = torch.empty((cap_f, 3), dtype=_i32, device=dev)
     normals = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
@@ -1069,7 +1073,7 @@ def mesh_compact(verts, faces, on_surface):
     if flag.numel() != V:
         raise ValueError("is_vert_on_surface must have one entry per vertex")
     nbytes = _lib.load().gn_mesh_compact_workspace_bytes(V, F)
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=verts.device)
+    ws = _ws(nbytes, verts.device)
     out_v, out_f = torch.empty_like(verts), torch.empty_like(faces)
     counts = torch.empty(3, dtype=torch.int64, device=verts.device)
     _lib.call("gn_mesh_compact", _p(verts), verts.element_size() * 3, _p(faces), _p(flag), V, F, _p(ws), nbytes, _p(out_v), _p(out_f), _p(counts), _stream())
@@ -1094,7 +1098,7 @@ def mesh_largest_component(faces, num_verts, with_labels=False):
     faces = _chk(faces.to(torch.int32).contiguous(), torch.int32, "faces")
     dev = faces.device
     nbytes = _lib.load().gn_mesh_largest_component_workspace_bytes(V)
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     mask = torch.empty(V, dtype=torch.uint8, device=dev)
     label = torch.empty(V, dtype=_i32, device=dev) if with_labels else None
     info = torch.empty(4, dtype=torch.int64, device=dev)
@@ -1380,7 +1384,7 @@ def nocs_bin_metrics(sets, bins, mirror_axis=None):
     tab = _table(_lib.NocsBinSet, rows)
     dev = keep[0][1].device
     nws = _lib.load().gn_nocs_bin_metrics_workspace_bytes(tab, len(rows))
-    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
+    ws = _ws(max(nws, 8), dev)
     out = torch.empty((len(rows), 4), dtype=torch.float64, device=dev)
     _lib.call("gn_nocs_bin_metrics", tab, len(rows), int(bins), -1 if mirror_axis is None else int(mirror_axis), _p(ws), nws, _p(out), _stream())
     return out
@@ -1411,7 +1415,7 @@ def value_losses(segments):
     tab = _table(_lib.LossSegment, rows)
     dev = keep[0][0].device
     nws = _lib.load().gn_value_losses_workspace_bytes(tab, len(rows))
-    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
+    ws = _ws(max(nws, 8), dev)
     out = torch.empty((len(rows), 2), dtype=torch.float64, device=dev)
     _lib.call("gn_value_losses", tab, len(rows), _p(ws), nws, _p(out), _stream())
     return out
@@ -1483,8 +1487,10 @@ def value_losses_bwd(segments, sums, weights, upstream):
 
 
 # ------------------------------------------------------------------------------------------------ operator gradients (csrc/grad.hip)
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+def _ws(nbytes, device, zero=False):
+    """THE workspace allocation of every wrapper: nbytes bytes as a size entry of the library gave them (at least one, so that the pointer is
+    never null), zero-filled on request"""
+    return (torch.zeros if zero else torch.empty)(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
 def fp32_rows(t, name, rows=None, cols=None):
@@ -2372,7 +2378,7 @@ def cloth_contact_buffers(garments, t, col, dev):
             "list_j": torch.full((n, K), -1, dtype=torch.int32, device=dev), "list_tm2": torch.zeros((n, K), dtype=torch.float64, device=dev),
             "list_n": torch.zeros(n, dtype=torch.int32, device=dev), "list_total": torch.zeros(n, dtype=torch.int32, device=dev),
             "corr": torch.zeros((n, 3), dtype=torch.float64, device=dev), "diag": torch.zeros((B, 4), dtype=torch.int64, device=dev),
-            "workspace": torch.zeros(max(ws_bytes, 1), dtype=torch.uint8, device=dev), "workspace_bytes": ws_bytes, "max_verts": max_verts,
+            "workspace": _ws(ws_bytes, dev, zero=True), "workspace_bytes": ws_bytes, "max_verts": max_verts,
             "buckets": buckets}
 
 

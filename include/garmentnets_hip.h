@@ -283,9 +283,10 @@ int gn_conv3d_gcr_split(const float *src0, int C0, const float *src1, int C1, co
  *                                gn_conv_affine_pack_bytes(B, Cin, Cout) bytes
  *     out_scale [B][Cout]        exact powers of two undoing the row scales
  *     kbias [B][64][Cout]        class = (mz * 4 + my) * 4 + mx, m = (voxel has a previous neighbour on the axis) | (a next one) << 1
- * ws: B * Cin * 12 + B * Cout * 4 bytes.  gn_conv3d_gcr_split_persample runs the layer from them (GN_SPLIT_F16X2 arithmetic, one source;
+ * ws: gn_conv_affine_pack_workspace_bytes(B, Cin, Cout) bytes (both entries), on 8 bytes.  gn_conv3d_gcr_split_persample runs the layer from them (GN_SPLIT_F16X2 arithmetic, one source;
  * tile_active / kconst / kreach / partial / occ_ws as gn_conv3d_gcr_split). */
 size_t gn_conv_affine_pack_bytes(int B, int Cin, int Cout);
+size_t gn_conv_affine_pack_workspace_bytes(int B, int Cin, int Cout);
 int gn_conv_affine_pack(const float *w, int Cin, int Cout, const float *a, const float *d, const double *sum, const double *sumsq, int64_t V,
                         const float *coff, int B, void *pack, size_t pack_bytes, float *stage_a, float *stage_d, float *out_scale,
                         float *kbias, void *ws, size_t ws_bytes, void *stream);
