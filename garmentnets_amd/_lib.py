@@ -167,6 +167,10 @@ PROTOTYPES = {
     "gn_cloth_contact_lists": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "gn_cloth_simulate_contacts_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                          _i32, _vp, _vp, _vp, _vp],
+    "gn_cloth_face_contact_lists": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
+                                    _vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "gn_cloth_simulate_face_contacts_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                              _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"gn_weight_pack_split_bytes": _sz, "gn_weight_pack_split_wino_bytes": _sz, "gn_weight_pack_upconv_bytes": _sz,
              "gn_conv_affine_pack_bytes": _sz, "gn_conv_affine_pack_workspace_bytes": _sz, "gn_conv_affine_pack_wino_bytes": _sz, "gn_conv3d_occupancy_workspace_bytes": _sz, "gn_mc33_workspace_bytes": _sz, "gn_ggm3d_range_workspace_bytes": _sz, "gn_mc33_batch_workspace_bytes": _sz, "gn_grid_scatter_workspace_bytes": _sz, "gn_fps_workspace_bytes": _sz, "gn_mesh_compact_workspace_bytes": _sz, "gn_mesh_largest_component_workspace_bytes": _sz,
@@ -242,6 +246,9 @@ CLOTH_MAX_LDS = 160 * 1024                      # CL_MAX_LDS
 CLOTH_MAX_BLOCK = 1024                          # CL_MAX_BLOCK
 CLOTH_MAX_LIST = 64                             # CL_MAX_LIST
 CLOTH_LISTS_TRAVEL, CLOTH_LISTS_BUILD = 1, 2    # CL_LISTS_*: the flags of gn_cloth_contact_lists
+CLOTH_FACE_MAX_LIST = 32                        # CL_FACE_MAX_LIST
+CLOTH_FACE_MAX_CHUNKS = 1024                    # CL_FACE_MAX_CHUNKS
+CLOTH_FACE_BLOCK = 256                          # CL_FACE_BLOCK: vertices per workgroup of the face-list kernels
 
 RENDER_MAX_SIZE = 4096                          # GN_RENDER_MAX_SIZE
 RENDER_MAX_OVERLAYS = 3                         # GN_RENDER_MAX_OVERLAYS

@@ -48,9 +48,39 @@ contacts found through contact lists that are rebuilt every few substeps, applie
                rebuild after the first and at the end of the call: above 1 a contact may have been missed), contact_active (active entries summed over
                the substeps)
 
-NOT modelled: vertex-face and edge-edge contacts, continuous collision detection, friction, collision with anything else, aerodynamic forces, strain
-limiting, dihedral bending, a random start orientation, moving grippers.  With contacts off the result is a hanging garment that may pass through
-itself; with them on, its vertices keep their distance but a vertex can still pass through the middle of a face larger than the thickness.
+Vertex-face contacts (OFF by default: face_thickness = 0, and then every array, attribute, diagnostic and bit is what it is without this section).  A
+vertex is kept off the faces it is no corner of, through face-contact lists built where the vertex lists are built and applied in the same Jacobi gather:
+
+  parameters   face_thickness t_f (metres; 0: off; not negative; positive only with collision_thickness > 0), face_max_list K_f (a whole number in
+               [1, 32], FACE_MAX_LIST_CAP); collision_margin, collision_rebuild and collision_relax are shared with the vertex contacts
+  constants    tf2 = t_f * t_f, rf = t_f + margin, rf2 = rf * rf, Kf: computed ONCE on the host (face_collision_constants), kept in
+               Garment.face_collision, read by both sides
+  closest point  point_triangle(q, a, b, c) -> (d2, r, bary): the arithmetic of distance.py's d2, operation for operation (e0, e1, e2, the Gram entries,
+               the four reciprocals-or-zero, the clamped segment distances s0, s1, s2, the plane projection (s, t, plane, inside)), which in addition
+               names the winner: inside and plane <= min(s0, s1, s2): the plane, r = (w - s*e0) - t*e1, bary = ((1 - s) - t, s, t); otherwise the
+               first of s0, s1, s2 equal to the minimum, r the residual that segment squares, u its clamped parameter, bary = (1-u, u, 0) on v0->v1,
+               (1-u, 0, u) on v0->v2, (0, 1-u, u) on v1->v2.  d2 is the winner's value: the d2 of distance.point_mesh_sqdist_reference, to the bit
+  face list    of vertex i at a rebuild, from the positions x at the start of that substep: every face f with i no corner of f (by index: the squared
+               distance of a corner to its own face can be a tiny positive number, l2 * (1 / l2) may be below 1), d2(x_i, tri_f(x)) <= rf2 and
+               tm2_if = min(tf2, d2(x0_i, tri_f(x0))) > 0, in ascending f, cut to the first K_f; an entry is (f, tm2_if); the entries cut off are
+               counted as overflow.  DEFINED by brute force over all (vertex, face) pairs (face_contact_lists_reference).  Rebuilds at the substeps of
+               the vertex lists, s % R == 0.  The travel diagnostic covers these lists too: if no vertex moves more than margin / 2, no
+               point-triangle distance changes by more than margin
+  contact pass the gather of the vertex pass and its corr.  For i with w_i > 0 the vertex entries come first, in list order (unchanged), then the
+               face entries in list order, both on the positions p as the sweep left them.  Entry (f, tm2), (a, b, c) = faces[f]:
+               d2, r, bary = point_triangle(p_i, p_a, p_b, p_c);  active iff d2 < tm2 and d2 > 0 (both strict);  active:  len = sqrt(d2);
+               tmin = sqrt(tm2);  n = r / len;  s = (w_i + ((b0*b0)*w_a + (b1*b1)*w_b)) + (b2*b2)*w_c;  dl = (tmin - len) / s;
+               corr += (w_i * dl) * n.  Then the single p_i = p_i + relax * corr.  The vertex takes its mass-weighted share; THE FACE'S CORNERS DO NOT
+               RECEIVE THE REACTION (one writer per position, no atomics: a reaction needs reverse lists with a fixed order, the step after this
+               one), so this pass does not conserve momentum and a light face in front of a heavy vertex resolves slowly.  A garment at rest has no
+               active entry (d2 == rest d2 >= tm2): without gravity nothing moves, to the bit
+  diagnostics  face_contact_overflow, face_contact_max_list, face_contact_active (FACE_CONTACT_STATS): the meaning of their vertex namesakes; they
+               join the stats dict only when face contacts are on
+
+NOT modelled: edge-edge contacts, the reaction of a vertex-face contact on the face, continuous collision detection, friction, collision with anything
+else, aerodynamic forces, strain limiting, dihedral bending, a random start orientation, moving grippers.  With contacts off the result is a hanging
+garment that may pass through itself; with the vertex contacts on, its vertices keep their distance but a vertex can still pass through the middle
+of a face larger than the thickness; with the face contacts on as well a vertex is kept off the faces, while two edges can still cross.
 """
 import dataclasses
 import hashlib
@@ -73,6 +103,11 @@ DEFAULT_COLLISION_MAX_LIST = 64
 DEFAULT_COLLISION_RELAX = 1.0
 COLLISION_MAX_LIST_CAP = 64                  # CL_MAX_LIST of csrc/cloth.hip
 COLLISION_FIELDS = ("collision_thickness", "collision_margin", "collision_rebuild", "collision_max_list", "collision_relax")
+# vertex-face contacts, used by `simulate --face_contacts` only
+DEFAULT_FACE_THICKNESS_FACTOR = 0.5          # face thickness = factor * the mean stretch rest length of the garment
+DEFAULT_FACE_MAX_LIST = 32
+FACE_MAX_LIST_CAP = 32                       # CL_FACE_MAX_LIST of csrc/cloth.hip
+FACE_COLLISION_FIELDS = ("face_thickness", "face_max_list")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -88,6 +123,8 @@ class ClothParams:
     collision_rebuild: int = 1             # substeps between two list builds
     collision_max_list: int = DEFAULT_COLLISION_MAX_LIST
     collision_relax: float = DEFAULT_COLLISION_RELAX
+    face_thickness: float = 0.0            # metres; 0: no vertex-face contacts
+    face_max_list: int = DEFAULT_FACE_MAX_LIST
 
     def __post_init__(self):
         vals = dataclasses.asdict(self)
@@ -105,10 +142,21 @@ class ClothParams:
             raise ValueError(f"cloth parameters: collision_max_list must be a whole number in [1, {COLLISION_MAX_LIST_CAP}], got {self.collision_max_list}")
         if not 0 < self.collision_relax <= 1:
             raise ValueError(f"cloth parameters: collision_relax must lie in (0, 1], got {self.collision_relax}")
+        if self.face_thickness < 0:
+            raise ValueError(f"cloth parameters: face_thickness must not be negative, got {self.face_thickness}")
+        if self.face_thickness > 0 and not self.collision_thickness > 0:
+            raise ValueError(f"cloth parameters: face_thickness > 0 needs collision_thickness > 0 (the face contacts share the vertex contacts' margin, "
+                             f"rebuild and relax), got {vals}")
+        if int(self.face_max_list) != self.face_max_list or not 1 <= self.face_max_list <= FACE_MAX_LIST_CAP:
+            raise ValueError(f"cloth parameters: face_max_list must be a whole number in [1, {FACE_MAX_LIST_CAP}], got {self.face_max_list}")
 
     @property
     def contacts(self):
         return self.collision_thickness > 0
+
+    @property
+    def face_contacts(self):
+        return self.face_thickness > 0
 
 
 def step_constants(params):
@@ -128,6 +176,15 @@ def collision_constants(params):
     r = t + m
     return {"t2": float(t * t), "r": float(r), "r2": float(r * r), "half_margin": float(m / np.float64(2.0)), "relax": float(params.collision_relax),
             "K": int(params.collision_max_list), "R": int(params.collision_rebuild)}
+
+
+def face_collision_constants(params):
+    """the face-contact numbers both sides read -> None with face contacts off, else a dict: tf2, rf, rf2 (python floats, fp64), Kf (int)"""
+    if not params.face_contacts:
+        return None
+    t, m = np.float64(params.face_thickness), np.float64(params.collision_margin)
+    rf = t + m
+    return {"tf2": float(t * t), "rf": float(rf), "rf2": float(rf * rf), "Kf": int(params.face_max_list)}
 
 
 def substeps_of(duration, h):
@@ -245,6 +302,8 @@ class Garment:
     n_bend: int
     bad_index: bool              # a face names a vertex outside [0, V): only a garment built with check=False carries one
     collision: dict = None       # collision_constants: None with contacts off
+    faces: np.ndarray = None     # (F, 3) int64, the mesh's faces in their order (garment() always fills it)
+    face_collision: dict = None  # face_collision_constants: None with face contacts off
 
 
 def garment(X, faces, grip, params, check=True):
@@ -283,7 +342,7 @@ def garment(X, faces, grip, params, check=True):
     l0 = _norm3(x0[ij[:, 0]] - x0[ij[:, 1]]) if len(ij) else np.zeros(0)      # measured in the start pose, as the sweep measures len
     alpha_t = np.where(topo.is_bend, consts["alpha_t_bend"], consts["alpha_t_stretch"]).astype(np.float64)
     return Garment(x0, w, topo.pairs, topo.is_bend, l0, alpha_t, topo.colour_off, consts, grip, n_massless, topo.n_stretch, topo.n_bend, bad,
-                   collision_constants(params))
+                   collision_constants(params), faces, face_collision_constants(params))
 
 
 def garment_from_nocs(nocs_verts, faces, grip, rest_scale, params, check=True):
@@ -363,8 +422,9 @@ def contact_entries(g, lists, counts):
     return i, idx[i, k].astype(np.int64), tm2[i, k]
 
 
-def contact_pass(p, w, entries, relax):
-    """the contact pass of the definition, in place on p -> the number of active entries"""
+def contact_pass(p, w, entries, relax, face=None):
+    """the contact pass of the definition, in place on p -> (active vertex entries, active face entries); face: None (no face entries: the second
+    count is 0) or (faces (F, 3), face_contact_entries): the face entries follow the vertex entries in the same corr"""
     i, j, tm2 = entries
     d = p[i] - p[j]
     d2 = _sq3(d)
@@ -376,8 +436,126 @@ def contact_pass(p, w, entries, relax):
     n = d / length[:, None]
     corr = np.zeros_like(p)
     np.add.at(corr, i, (wi * dl)[:, None] * n)                # unbuffered: entry after entry, so list order inside a vertex
+    face_active = 0 if face is None else face_contact_gather(corr, p, w, face[0], face[1])
     live = w > 0
     p[live] = p[live] + np.float64(relax) * corr[live]
+    return int(act.sum()), face_active
+
+
+def _dot3(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _rcp_or_zero(x):
+    return np.where(x > 0.0, 1.0 / np.where(x > 0.0, x, 1.0), 0.0)
+
+
+def _seg_closest(w, e, wd, inv):
+    """distance.py's _seg, which also returns what it squares: (r.r, r (3 components), the clamped parameter)"""
+    u = np.fmin(np.fmax(wd * inv, 0.0), 1.0)
+    r = [w[k] - u * e[k] for k in range(3)]
+    return _dot3(r, r), r, u
+
+
+def point_triangle(q, a, b, c):
+    """the closest point of the triangle (a, b, c) to q, all (..., 3) and broadcast against each other -> (d2 (...), r (..., 3), bary (..., 3)): d2 the
+    squared distance of distance.point_mesh_sqdist_reference to the bit, r = q - the closest point as the winner of the definition computes it, bary
+    the closest point's weights on (a, b, c)"""
+    q, a, b, c = np.broadcast_arrays(*(np.asarray(p, dtype=np.float64) for p in (q, a, b, c)))
+    q, v0, v1, v2 = ([p[..., k] for k in range(3)] for p in (q, a, b, c))
+    with np.errstate(all="ignore"):
+        e0, e1, e2 = ([i[k] - j[k] for k in range(3)] for i, j in ((v1, v0), (v2, v0), (v2, v1)))
+        ga, gb, gc, l2 = _dot3(e0, e0), _dot3(e0, e1), _dot3(e1, e1), _dot3(e2, e2)
+        idet, ia, ic, ie2 = _rcp_or_zero(ga * gc - gb * gb), _rcp_or_zero(ga), _rcp_or_zero(gc), _rcp_or_zero(l2)
+        w = [q[k] - v0[k] for k in range(3)]
+        d0, d1 = _dot3(w, e0), _dot3(w, e1)
+        s0, r0, u0 = _seg_closest(w, e0, d0, ia)
+        s1, r1, u1 = _seg_closest(w, e1, d1, ic)
+        u = [q[k] - v1[k] for k in range(3)]
+        s2, r2, u2 = _seg_closest(u, e2, _dot3(u, e2), ie2)
+        s, t = (gc * d0 - gb * d1) * idet, (ga * d1 - gb * d0) * idet
+        rp = [(w[k] - s * e0[k]) - t * e1[k] for k in range(3)]
+        plane = _dot3(rp, rp)
+        inside = (idet > 0.0) & (s >= 0.0) & (t >= 0.0) & (s + t <= 1.0)
+        seg = np.fmin(np.fmin(s0, s1), s2)
+        win_p = inside & (plane <= seg)
+        win_0 = ~win_p & (s0 == seg)
+        win_1 = ~win_p & ~win_0 & (s1 == seg)
+        one, zero = np.ones_like(seg), np.zeros_like(seg)
+        d2 = np.where(win_p, plane, seg)
+        r = np.stack([np.where(win_p, rp[k], np.where(win_0, r0[k], np.where(win_1, r1[k], r2[k]))) for k in range(3)], axis=-1)
+        b0 = np.where(win_p, (one - s) - t, np.where(win_0, one - u0, np.where(win_1, one - u1, zero)))
+        b1 = np.where(win_p, s, np.where(win_0, u0, np.where(win_1, zero, one - u2)))
+        b2 = np.where(win_p, t, np.where(win_0, zero, np.where(win_1, u1, u2)))
+    return d2, r, np.stack([b0, b1, b2], axis=-1)
+
+
+def _face_corners(g):
+    if g.faces is None:
+        raise ValueError("cloth face contacts: the garment carries no faces (build it with cloth.garment)")
+    return np.asarray(g.faces, dtype=np.int64).reshape(-1, 3)
+
+
+def face_contact_lists_reference(g, x, chunk=256):
+    """the face-contact lists of the definition for the positions x, by brute force over all (vertex, face) pairs (`chunk` vertices at a time)
+    -> ((idx (V, Kf) int32, tm2 (V, Kf) float64), counts (V,) int64, overflow (V,) int64): row i holds its first counts[i] entries in ascending f,
+    the rest of the row is (-1, 0); overflow[i] entries were cut off"""
+    c = g.face_collision
+    if c is None:
+        raise ValueError("face_contact_lists_reference: the garment has face contacts off (face_thickness = 0)")
+    if g.bad_index:
+        raise IndexError("cloth: a face index is out of bounds for its mesh's vertices")
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape != g.x0.shape:
+        raise ValueError(f"face_contact_lists_reference: x must be {g.x0.shape}, got {x.shape}")
+    faces = _face_corners(g)
+    V, F, K = len(x), len(faces), c["Kf"]
+    tf2, rf2 = np.float64(c["tf2"]), np.float64(c["rf2"])
+    idx = np.full((V, K), -1, dtype=np.int32)
+    tm2 = np.zeros((V, K), dtype=np.float64)
+    counts = np.zeros(V, dtype=np.int64)
+    overflow = np.zeros(V, dtype=np.int64)
+    if F == 0:
+        return (idx, tm2), counts, overflow
+    fa, fb, fc = faces[:, 0], faces[:, 1], faces[:, 2]
+    for a in range(0, V, int(chunk)):
+        rows = np.arange(a, min(a + int(chunk), V))
+        now = point_triangle(x[rows, None, :], x[None, fa, :], x[None, fb, :], x[None, fc, :])[0]
+        rest = np.minimum(tf2, point_triangle(g.x0[rows, None, :], g.x0[None, fa, :], g.x0[None, fb, :], g.x0[None, fc, :])[0])
+        corner = (rows[:, None] == fa[None, :]) | (rows[:, None] == fb[None, :]) | (rows[:, None] == fc[None, :])
+        near = (now <= rf2) & (rest > 0) & ~corner
+        rank = np.cumsum(near, axis=1) - 1
+        total = near.sum(axis=1)
+        n, f = np.nonzero(near & (rank < K))
+        idx[rows[n], rank[n, f]] = f
+        tm2[rows[n], rank[n, f]] = rest[n, f]
+        counts[rows] = np.minimum(total, K)
+        overflow[rows] = total - counts[rows]
+    return (idx, tm2), counts, overflow
+
+
+def face_contact_entries(g, lists, counts):
+    """the face-list entries the contact pass reads, flat and in its order, of the vertices with w > 0 -> (i, f, tm2)"""
+    return contact_entries(g, lists, counts)
+
+
+def face_contact_gather(corr, p, w, faces, entries):
+    """the face entries (i, f, tm2) of the contact pass, added to corr in place entry after entry (after the vertex entries: corr carries their sum)
+    -> the number of active entries; p is read only"""
+    i, f, tm2 = entries
+    if len(i) == 0:
+        return 0
+    ca, cb, cc = faces[f, 0], faces[f, 1], faces[f, 2]
+    d2, r, bary = point_triangle(p[i], p[ca], p[cb], p[cc])
+    act = (d2 < tm2) & (d2 > 0)
+    i, d2, r, bary, tm2, ca, cb, cc = i[act], d2[act], r[act], bary[act], tm2[act], ca[act], cb[act], cc[act]
+    length = np.sqrt(d2)
+    wi = w[i]
+    b0, b1, b2 = bary[:, 0], bary[:, 1], bary[:, 2]
+    s = (wi + ((b0 * b0) * w[ca] + (b1 * b1) * w[cb])) + (b2 * b2) * w[cc]
+    dl = (np.sqrt(tm2) - length) / s
+    n = r / length[:, None]
+    np.add.at(corr, i, (wi * dl)[:, None] * n)                # unbuffered: entry after entry, so list order inside a vertex
     return int(act.sum())
 
 
@@ -388,8 +566,9 @@ def contact_travel(g, x, x_ref):
     return float(np.sqrt(_sq3(x - x_ref).max()) / np.float64(g.collision["half_margin"]))
 
 
-def substep(g, x, v, entries=None):
-    """one substep of the definition, in place on x and v; entries: contact_entries of the current lists (None: no contact pass) -> active entries"""
+def substep(g, x, v, entries=None, face_entries=None):
+    """one substep of the definition, in place on x and v -> (active vertex entries, active face entries); entries: contact_entries of the current
+    lists (None: no contact pass); face_entries: face_contact_entries of the current face lists (None: no face entries; they need `entries`)"""
     c = g.consts
     h, inv_h, damp, hg = np.float64(c["h"]), np.float64(c["inv_h"]), np.float64(c["damp"]), np.array(c["hg"], dtype=np.float64)
     live = g.w > 0
@@ -401,30 +580,39 @@ def substep(g, x, v, entries=None):
     for k in range(len(off) - 1):
         sl = slice(off[k], off[k + 1])
         project_colour(p, g.w, g.pairs[sl, 0], g.pairs[sl, 1], g.l0[sl], g.alpha_t[sl])
-    active = 0 if entries is None else contact_pass(p, g.w, entries, g.collision["relax"])
+    active = (0, 0)
+    if entries is not None:
+        face = None if face_entries is None else (_face_corners(g), face_entries)
+        active = contact_pass(p, g.w, entries, g.collision["relax"], face=face)
     v[live] = (p[live] - x_prev[live]) * inv_h
     x[live] = p[live]
     return active
 
 
 CONTACT_STATS = ("contact_overflow", "contact_max_list", "contact_travel", "contact_active")
+FACE_CONTACT_STATS = ("face_contact_overflow", "face_contact_max_list", "face_contact_active")
 
 
 def simulate_reference(g, substeps, x=None, v=None, stats=False, observe=None):
     """`substeps` substeps from (x, v) (None: the start pose at rest) -> (x, v) float64 (V, 3), new arrays; stats=True: (x, v, the contact diagnostics
-    of the definition as a dict, all 0 with contacts off).  With contacts on the lists are rebuilt at the substeps s with s % R == 0.  observe: called
-    as observe(s, x, v) after every substep s (the arrays are the run's own: read, do not write)."""
+    of the definition as a dict, all 0 with contacts off; with face contacts on FACE_CONTACT_STATS join it).  With contacts on the lists are rebuilt at
+    the substeps s with s % R == 0.  observe: called as observe(s, x, v) after every substep s (the arrays are the run's own: read, do not write)."""
     if g.bad_index:
         raise IndexError("cloth: a face index is out of bounds for its mesh's vertices")
     x, v = state_arrays(g, x, v, "simulate_reference")
     out = {"contact_overflow": 0, "contact_max_list": 0, "contact_travel": 0.0, "contact_active": 0}
+    if g.face_collision is not None and g.collision is None:
+        raise ValueError("simulate_reference: face contacts need the vertex contacts on (collision_thickness > 0)")
     if g.collision is None:
         for s in range(int(substeps)):
             substep(g, x, v)
             if observe is not None:
                 observe(s, x, v)
         return (x, v, out) if stats else (x, v)
-    entries = x_ref = None
+    entries = face_entries = x_ref = None
+    faces_on = g.face_collision is not None
+    if faces_on:
+        out.update({k: 0 for k in FACE_CONTACT_STATS})
     for s in range(int(substeps)):
         if s % g.collision["R"] == 0:
             if x_ref is not None:
@@ -433,7 +621,15 @@ def simulate_reference(g, substeps, x=None, v=None, stats=False, observe=None):
             out["contact_overflow"] += int(overflow.sum())
             out["contact_max_list"] = max(out["contact_max_list"], int((counts + overflow).max(initial=0)))
             entries, x_ref = contact_entries(g, lists, counts), x.copy()
-        out["contact_active"] += substep(g, x, v, entries)
+            if faces_on:
+                lists, counts, overflow = face_contact_lists_reference(g, x)
+                out["face_contact_overflow"] += int(overflow.sum())
+                out["face_contact_max_list"] = max(out["face_contact_max_list"], int((counts + overflow).max(initial=0)))
+                face_entries = face_contact_entries(g, lists, counts)
+        active, face_active = substep(g, x, v, entries, face_entries)
+        out["contact_active"] += active
+        if faces_on:
+            out["face_contact_active"] += face_active
         if observe is not None:
             observe(s, x, v)
     if x_ref is not None:

@@ -3,6 +3,8 @@
 //   gn_cloth_simulate_batch            B ragged garments, `substeps` substeps each, in launches of at most max_substeps_per_launch
 //   gn_cloth_contact_lists             the vertex-vertex contact lists of B garments through a hashed uniform grid (and contact_travel)
 //   gn_cloth_simulate_contacts_batch   gn_cloth_simulate_batch with the contact pass of those lists after the last colour
+//   gn_cloth_face_contact_lists        the vertex-face contact lists of B garments over all (vertex, face) pairs (at the end of this file)
+//   gn_cloth_simulate_face_contacts_batch   gn_cloth_simulate_contacts_batch with the face entries of those lists inside the same gather
 //
 // The definition is garmentnets_amd/cloth.py's ("Hanging garments"); cloth_substeps below is its substep, operation for operation: the
 // library is built with -ffp-contract=off and every operation is an explicit _rn intrinsic, so x and v are the bits of cloth.simulate_reference.
@@ -19,6 +21,9 @@
 // done", and the thread adds relax * corr to its own vertices.  The velocity pass that follows reads only what the same thread wrote, and the next
 // reader of a foreign position is the next substep's first colour, behind the prediction pass's barrier: the second barrier the plan allowed for
 // ("writes done") is that one.  A Jacobi gather: one writer per position, no atomics, the order of the additions fixed by the list.
+// Face entries (cloth_substeps<true, true>): in the same gather, after the vertex entries of the vertex and into the same sum, the entries of its
+// face list: the triangle's constants from P (pm_tri_of), the closest point (pm_closest), the vertex's mass-weighted share; the face's corners get
+// no reaction, so the one-writer rule and the barriers are those of the vertex entries.
 //
 // Contact lists (cl_contact_* below): many workgroups per garment; a uniform grid of cells of edge `cell` (a little above r) hashed into `buckets`
 // buckets per garment, filled by count, scan, fill (a thread per vertex); the query (a wave per vertex) scans the 27 neighbouring cells, keeps the
@@ -34,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mesh_pair.h"
 
 #define CL_MAX_BLOCK 1024
 #define CL_MAX_LDS (160 * 1024)
@@ -64,8 +70,21 @@ struct ClothArgsContacts : ClothArgs {
     double relax;
     int K;
 };
-template <bool CONTACTS>
-using ClothArgsOf = std::conditional_t<CONTACTS, ClothArgsContacts, ClothArgs>;
+#define CL_FACE_MAX_LIST 32                 // the longest face-contact list a vertex can have (cloth.FACE_MAX_LIST_CAP)
+#define CL_FACE_DIAG 3                      // int64 per garment: {face_contact_overflow, face_contact_max_list, face_contact_active}
+
+// what the face entries of the contact pass read beside ClothArgsContacts: the lists of gn_cloth_face_contact_lists
+struct ClothArgsFaces : ClothArgsContacts {
+    const int32_t *faces;                   // [*][3] vertex indices relative to the garment's first vertex
+    const int64_t *fcsr;                    // [B + 1] the garment's first face
+    const int32_t *flist_f;                 // [*][Kf] face indices relative to the garment's first face, ascending
+    const double *flist_tm2;                // [*][Kf] min(tf2, the rest d2) of the entry
+    const int32_t *flist_n;                 // [*] entries of the row
+    int64_t *fdiag;                         // [B][CL_FACE_DIAG]
+    int Kf;
+};
+template <bool CONTACTS, bool FACES = false>
+using ClothArgsOf = std::conditional_t<FACES, ClothArgsFaces, std::conditional_t<CONTACTS, ClothArgsContacts, ClothArgs>>;
 
 __device__ __forceinline__ double cl_sq(double ax, double ay, double az, double bx, double by, double bz) {
     const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
@@ -84,13 +103,15 @@ __device__ __forceinline__ unsigned long long cl_wave_max(unsigned long long v) 
 }
 
 // P: the working positions of the garment (LDS or global), vb: its rows of v.  Called by the whole workgroup (it holds barriers).  CONTACTS: v_off is
-// the garment's first row of the lists and of corr, diag its CL_DIAG counters.
-template <bool CONTACTS>
+// the garment's first row of the lists and of corr, diag its CL_DIAG counters.  FACES (with CONTACTS): b is the garment, the face entries follow the
+// vertex entries of a vertex in the same corr.
+template <bool CONTACTS, bool FACES = false>
 __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const double *__restrict__ w, const int32_t *__restrict__ ij,
                                                const double *__restrict__ l0, const double *__restrict__ at, const int64_t *__restrict__ coff, int ncol,
-                                               int V, const ClothArgsOf<CONTACTS> &a, int64_t v_off = 0, int64_t *diag = nullptr) {
+                                               int V, const ClothArgsOf<CONTACTS, FACES> &a, int64_t v_off = 0, int64_t *diag = nullptr, int b = 0) {
     const int T = blockDim.x;
     long long active = 0;
+    [[maybe_unused]] long long face_active = 0;
     for (int s = 0; s < a.substeps; ++s) {
         for (int i = threadIdx.x; i < V; i += T) {
             if (!(w[i] > 0.0)) continue;                     // held or massless: stays where it is
@@ -161,6 +182,38 @@ __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const doub
                         ++active;
                     }
                 }
+                if constexpr (FACES) {                       // the face entries, after the vertex entries and in list order
+                    const int64_t f_off = a.fcsr[b];
+                    const int F = (int)(a.fcsr[b + 1] - f_off);
+                    const int32_t *fc = a.faces + 3 * f_off;
+                    const int32_t *ff = a.flist_f + (v_off + i) * a.Kf;
+                    const double *ft = a.flist_tm2 + (v_off + i) * a.Kf;
+                    int nf = a.flist_n[v_off + i];
+                    nf = nf < 0 ? 0 : (nf > a.Kf ? a.Kf : nf);
+                    for (int k = 0; k < nf; ++k) {
+                        const int32_t f = ff[k];
+                        const double tm2 = ft[k];
+                        if (f < 0 || f >= F) { *a.bad = 1; continue; }                             // flagged, never dereferenced
+                        const int32_t ia = fc[3 * (int64_t)f], ib = fc[3 * (int64_t)f + 1], ic = fc[3 * (int64_t)f + 2];
+                        if (ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) { *a.bad = 1; continue; }
+                        const double *qa = P + 3 * (int64_t)ia, *qb = P + 3 * (int64_t)ib, *qc = P + 3 * (int64_t)ic;
+                        const double p0[3] = {qa[0], qa[1], qa[2]}, p1[3] = {qb[0], qb[1], qb[2]}, p2[3] = {qc[0], qc[1], qc[2]};
+                        const PmTri tri = pm_tri_of(p0, p1, p2);
+                        double r[3], bary[3];
+                        const double d2 = pm_closest(tri, px, py, pz, r, bary);
+                        if (!(d2 < tm2 && d2 > 0.0)) continue;
+                        const double len = __dsqrt_rn(d2), tmin = __dsqrt_rn(tm2);
+                        const double sum = __dadd_rn(__dadd_rn(wi, __dadd_rn(__dmul_rn(__dmul_rn(bary[0], bary[0]), w[ia]),
+                                                                             __dmul_rn(__dmul_rn(bary[1], bary[1]), w[ib]))),
+                                                     __dmul_rn(__dmul_rn(bary[2], bary[2]), w[ic]));
+                        const double dl = __ddiv_rn(__dsub_rn(tmin, len), sum);
+                        const double ai = __dmul_rn(wi, dl);
+                        cx = __dadd_rn(cx, __dmul_rn(ai, __ddiv_rn(r[0], len)));
+                        cy = __dadd_rn(cy, __dmul_rn(ai, __ddiv_rn(r[1], len)));
+                        cz = __dadd_rn(cz, __dmul_rn(ai, __ddiv_rn(r[2], len)));
+                        ++face_active;
+                    }
+                }
                 corr[3 * (int64_t)i] = cx; corr[3 * (int64_t)i + 1] = cy; corr[3 * (int64_t)i + 2] = cz;
             }
             __syncthreads();                                 // all reads done
@@ -184,10 +237,15 @@ __device__ __forceinline__ void cloth_substeps(double *P, double *vb, const doub
         active = cl_wave_sum(active);                        // every lane is here: nothing above returns
         if ((threadIdx.x & (GN_WAVE - 1)) == 0 && active) atomicAdd((unsigned long long *)(diag + 2), (unsigned long long)active);
     }
+    if constexpr (FACES) {
+        face_active = cl_wave_sum(face_active);
+        if ((threadIdx.x & (GN_WAVE - 1)) == 0 && face_active)
+            atomicAdd((unsigned long long *)(a.fdiag + CL_FACE_DIAG * (int64_t)b + 2), (unsigned long long)face_active);
+    }
 }
 
-template <bool CONTACTS>
-__global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(ClothArgsOf<CONTACTS> a) {
+template <bool CONTACTS, bool FACES = false>
+__global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(ClothArgsOf<CONTACTS, FACES> a) {
     extern __shared__ __attribute__((aligned(16))) double cl_pos[];
     const int64_t *m = a.csr + 3 * (int64_t)blockIdx.x;
     const int64_t v_off = m[0], c_off = m[1], k_off = m[2];
@@ -202,20 +260,25 @@ __global__ __launch_bounds__(CL_MAX_BLOCK) void cloth_simulate_batch_kernel(Clot
     // every index of the table is checked whatever the substep count: the wrapper raises on the flag
     for (int64_t c = threadIdx.x; c < 2 * C; c += blockDim.x)
         if (ij[c] < 0 || ij[c] >= V) *a.bad = 1;
+    if constexpr (FACES) {
+        const int64_t f_off = a.fcsr[blockIdx.x], F = a.fcsr[blockIdx.x + 1] - f_off;
+        for (int64_t c = threadIdx.x; c < 3 * F; c += blockDim.x)
+            if (a.faces[3 * f_off + c] < 0 || a.faces[3 * f_off + c] >= V) *a.bad = 1;
+    }
     if ((int64_t)V * 24 <= (int64_t)a.lds_bytes) {           // workgroup-uniform: V and lds_bytes are the same for every thread
         for (int i = threadIdx.x; i < 3 * V; i += blockDim.x) cl_pos[i] = xb[i];
         __syncthreads();
-        cloth_substeps<CONTACTS>(cl_pos, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag);
+        cloth_substeps<CONTACTS, FACES>(cl_pos, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag, (int)blockIdx.x);
         __syncthreads();
         for (int i = threadIdx.x; i < 3 * V; i += blockDim.x) xb[i] = cl_pos[i];
     } else {
-        cloth_substeps<CONTACTS>(xb, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag);
+        cloth_substeps<CONTACTS, FACES>(xb, vb, w, ij, a.l0 + c_off, a.alpha_t + c_off, coff, ncol, V, a, v_off, diag, (int)blockIdx.x);
     }
 }
 
 // the checks and launches both solver entries share; `name` is the entry's for the messages
-template <bool CONTACTS>
-static int cloth_launch(const char *name, ClothArgsOf<CONTACTS> &a, int B, int64_t total_verts, int64_t total_constraints, int64_t substeps,
+template <bool CONTACTS, bool FACES = false>
+static int cloth_launch(const char *name, ClothArgsOf<CONTACTS, FACES> &a, int B, int64_t total_verts, int64_t total_constraints, int64_t substeps,
                         int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block, void *stream) {
     GN_REQUIRE(B >= 0 && B <= 65535, "%s: B=%d outside [0, 65535]", name, B);
     GN_REQUIRE(total_verts >= 0 && total_verts < INT32_MAX && total_constraints >= 0 && total_constraints < INT32_MAX,
@@ -233,12 +296,12 @@ static int cloth_launch(const char *name, ClothArgsOf<CONTACTS> &a, int B, int64
         GN_REQUIRE(consts_host[k] == consts_host[k] && fabs(consts_host[k]) <= 1.7976931348623157e308, "%s: step constant %d is not finite", name, k);
     a.h = consts_host[0]; a.inv_h = consts_host[1]; a.hgx = consts_host[2]; a.hgy = consts_host[3]; a.hgz = consts_host[4]; a.damp = consts_host[5];
     a.lds_bytes = lds_bytes;
-    GN_HIP(hipFuncSetAttribute((const void *)cloth_simulate_batch_kernel<CONTACTS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), name);
+    GN_HIP(hipFuncSetAttribute((const void *)cloth_simulate_batch_kernel<CONTACTS, FACES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), name);
     // a launch with substeps == 0 still checks the table
     int64_t left = substeps;
     do {
         a.substeps = (int)(left < max_substeps_per_launch ? left : max_substeps_per_launch);
-        hipLaunchKernelGGL(cloth_simulate_batch_kernel<CONTACTS>, dim3((unsigned)B), dim3((unsigned)block), (size_t)lds_bytes, gn_stream(stream), a);
+        hipLaunchKernelGGL((cloth_simulate_batch_kernel<CONTACTS, FACES>), dim3((unsigned)B), dim3((unsigned)block), (size_t)lds_bytes, gn_stream(stream), a);
         GN_LAUNCH_CHECK(name);
         left -= a.substeps;
     } while (left > 0);
@@ -525,4 +588,183 @@ extern "C" int gn_cloth_contact_lists(const double *x, const double *x0, const i
     hipLaunchKernelGGL(cl_contact_query_kernel, dim3((unsigned)max_verts, (unsigned)B), dim3(CL_QUERY_BLOCK), 0, st, a);
     GN_LAUNCH_CHECK(name);
     return GN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ vertex-face contacts
+// Face-contact lists (cloth.py "Vertex-face contacts"): all (vertex, face) pairs of a garment, no search structure.  cl_face_hits_kernel: grid
+// (blocks of CL_FACE_BLOCK vertices, face chunks, B); a workgroup stages the triangle constants of its chunk's faces from the CURRENT x in LDS tiles
+// (pm_stage_tile) and every thread walks them for its one vertex, so inside a chunk a vertex meets the faces in ascending order; a face within rf
+// that the vertex is no corner of has its tm2 evaluated from x0 and, when that is positive, becomes a hit: the first Kf hits of the (vertex, chunk)
+// are kept, all are counted.  cl_face_concat_kernel (a thread per vertex) strings the chunks' hits together in chunk order -- ascending f -- cuts
+// at Kf and counts the rest.  The chunks only spread one garment over the machine: the lists do not depend on their number.
+#define CL_FACE_BLOCK ED_BLOCK              // pm_stage_tile's workgroup
+#define CL_FACE_MAX_CHUNKS 1024
+
+struct FaceListArgs {
+    const double *x, *x0;                   // [*][3] positions now, start pose
+    const int64_t *csr;                     // the solver's [B + 1][3]; only v_off is read
+    const int32_t *faces;                   // [*][3]
+    const int64_t *fcsr;                    // [B + 1]
+    int32_t *hit_f, *hit_n;                 // [*][chunks][Kf], [*][chunks]
+    double *hit_tm2;                        // [*][chunks][Kf]
+    int32_t *list_f, *list_n, *list_total;
+    double *list_tm2;
+    int64_t *fdiag, *bad;
+    double tf2, rf2;
+    int Kf, chunks;
+};
+
+__global__ __launch_bounds__(CL_FACE_BLOCK) void cl_face_hits_kernel(FaceListArgs a) {
+    __shared__ double tri[PM_NCONST][PM_TILE];
+    const int b = blockIdx.z, chunk = blockIdx.y;
+    const int64_t v_off = a.csr[3 * (int64_t)b], f_off = a.fcsr[b];
+    const int V = (int)(a.csr[3 * (int64_t)(b + 1)] - v_off);
+    const int64_t F = a.fcsr[b + 1] - f_off;
+    if ((int64_t)blockIdx.x * CL_FACE_BLOCK >= V) return;    // the whole workgroup: nobody is left waiting at a barrier below
+    const int64_t per = (F + a.chunks - 1) / a.chunks;       // faces per chunk of this garment
+    const int64_t f0 = chunk * per, f1 = f0 + per < F ? f0 + per : F;
+    const int i = blockIdx.x * CL_FACE_BLOCK + threadIdx.x;
+    const bool own = i < V;
+    const double *xb = a.x + 3 * v_off, *x0b = a.x0 + 3 * v_off;
+    const int32_t *fc = a.faces + 3 * f_off;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (own) { qx = xb[3 * (int64_t)i]; qy = xb[3 * (int64_t)i + 1]; qz = xb[3 * (int64_t)i + 2]; }
+    const int64_t slot = (v_off + i) * a.chunks + chunk;     // read only when own
+    int n = 0;
+    for (int64_t t0 = f0; t0 < f1; t0 += PM_TILE) {          // workgroup-uniform bounds
+        const int m = (int)(f1 - t0 < PM_TILE ? f1 - t0 : PM_TILE);
+        __syncthreads();
+        pm_stage_tile(tri, xb, (int64_t)V, fc, t0, m, a.bad);
+        __syncthreads();
+        if (!own) continue;
+        for (int j = 0; j < m; ++j) {
+            const PmTri T = pm_load(tri, j);
+            if (!(pm_sqdist(T, qx, qy, qz) <= a.rf2)) continue;
+            const int64_t f = t0 + j;
+            const int32_t ia = fc[3 * f], ib = fc[3 * f + 1], ic = fc[3 * f + 2];
+            if (ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) continue;     // flagged by the staging, never dereferenced
+            if (ia == i || ib == i || ic == i) continue;                                   // a corner of the face, by index
+            double p[3][3];
+            const int32_t cs[3] = {ia, ib, ic};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) p[k][c] = x0b[3 * (int64_t)cs[k] + c];
+            const PmTri R = pm_tri_of(p[0], p[1], p[2]);
+            const double tm2 = fmin(a.tf2, pm_sqdist(R, x0b[3 * (int64_t)i], x0b[3 * (int64_t)i + 1], x0b[3 * (int64_t)i + 2]));
+            if (!(tm2 > 0.0)) continue;
+            if (n < a.Kf) {
+                a.hit_f[slot * a.Kf + n] = (int32_t)f;
+                a.hit_tm2[slot * a.Kf + n] = tm2;
+            }
+            ++n;
+        }
+    }
+    if (own) a.hit_n[slot] = n;
+}
+
+// grid (blocks of CL_FACE_BLOCK vertices, B): a thread per vertex
+__global__ __launch_bounds__(CL_FACE_BLOCK) void cl_face_concat_kernel(FaceListArgs a) {
+    const int b = blockIdx.y;
+    const int64_t v_off = a.csr[3 * (int64_t)b];
+    const int V = (int)(a.csr[3 * (int64_t)(b + 1)] - v_off);
+    const int i = blockIdx.x * CL_FACE_BLOCK + threadIdx.x;
+    if (i >= V) return;
+    const int64_t g = v_off + i;
+    const int Kf = a.Kf;
+    int n = 0;
+    long long total = 0;
+    for (int c = 0; c < a.chunks; ++c) {
+        const int64_t slot = g * a.chunks + c;
+        int h = a.hit_n[slot];
+        h = h < 0 ? 0 : h;
+        total += h;
+        const int kept = h < Kf ? h : Kf;
+        for (int k = 0; k < kept && n < Kf; ++k, ++n) {
+            a.list_f[g * Kf + n] = a.hit_f[slot * Kf + k];
+            a.list_tm2[g * Kf + n] = a.hit_tm2[slot * Kf + k];
+        }
+    }
+    for (int k = n; k < Kf; ++k) {
+        a.list_f[g * Kf + k] = -1;
+        a.list_tm2[g * Kf + k] = 0.0;
+    }
+    a.list_n[g] = n;
+    a.list_total[g] = (int32_t)(total < INT32_MAX ? total : INT32_MAX);
+    int64_t *d = a.fdiag + CL_FACE_DIAG * (int64_t)b;        // integer sums and maxima: the order of the atomics cannot reach the result
+    if (total > n) atomicAdd((unsigned long long *)d, (unsigned long long)(total - n));
+    if (total > d[1]) atomicMax((unsigned long long *)(d + 1), (unsigned long long)total);
+}
+
+static int cl_face_constants(const char *name, const double *face_host, const double *collision_host, int Kf) {
+    GN_REQUIRE(Kf >= 1 && Kf <= CL_FACE_MAX_LIST, "%s: Kf=%d outside [1, %d]", name, Kf, CL_FACE_MAX_LIST);
+    GN_REQUIRE(face_host, "%s: null face constants", name);
+    for (int k = 0; k < 2; ++k)
+        GN_REQUIRE(cl_finite(face_host[k]) && face_host[k] > 0.0, "%s: face constant %d is not finite and positive", name, k);
+    GN_REQUIRE(collision_host, "%s: face constants need the vertex contacts' constants (null collision constants)", name);
+    return GN_OK;
+}
+
+extern "C" int gn_cloth_face_contact_lists(const double *x, const double *x0, const int64_t *csr, const int32_t *faces, const int64_t *fcsr, int B,
+                                           int64_t total_verts, int64_t total_faces, int max_verts, const double *face_host,
+                                           const double *collision_host, int Kf, int chunks, int32_t *hit_f, double *hit_tm2, int64_t hit_entries,
+                                           int32_t *hit_n, int64_t hit_rows, int32_t *list_f, double *list_tm2, int64_t list_entries, int32_t *list_n,
+                                           int32_t *list_total, int64_t list_rows, int64_t *fdiag, int64_t fdiag_rows, int64_t *bad, void *stream) {
+    const char *name = "gn_cloth_face_contact_lists";
+    GN_REQUIRE(B >= 0 && B <= 65535, "%s: B=%d outside [0, 65535]", name, B);
+    GN_REQUIRE(chunks >= 1 && chunks <= CL_FACE_MAX_CHUNKS, "%s: chunks=%d outside [1, %d]", name, chunks, CL_FACE_MAX_CHUNKS);
+    if (int rc = cl_face_constants(name, face_host, collision_host, Kf)) return rc;
+    GN_REQUIRE(total_verts >= 0 && total_verts < INT32_MAX / CL_MAX_LIST && total_faces >= 0 && total_faces < INT32_MAX / 3,
+               "%s: %lld vertices, %lld faces: the tables must stay below 2^31 entries", name, (long long)total_verts, (long long)total_faces);
+    GN_REQUIRE(max_verts >= 0 && max_verts <= total_verts, "%s: max_verts=%d outside [0, %lld]", name, max_verts, (long long)total_verts);
+    GN_REQUIRE(hit_entries >= total_verts * chunks * Kf && hit_rows >= total_verts * chunks,
+               "%s: hit buffers of %lld entries and %lld rows, %lld and %lld needed", name, (long long)hit_entries, (long long)hit_rows,
+               (long long)(total_verts * chunks * Kf), (long long)(total_verts * chunks));
+    GN_REQUIRE(list_entries >= total_verts * Kf && list_rows >= total_verts, "%s: lists of %lld entries and %lld rows, %lld and %lld needed", name,
+               (long long)list_entries, (long long)list_rows, (long long)(total_verts * Kf), (long long)total_verts);
+    GN_REQUIRE(fdiag_rows >= B, "%s: fdiag of %lld rows, %d needed", name, (long long)fdiag_rows, B);
+    if (B == 0 || total_verts == 0 || max_verts == 0) return GN_OK;
+    GN_REQUIRE(x && x0 && csr && fcsr && fdiag && bad && (total_faces == 0 || faces), "%s: null pointer", name);
+    GN_REQUIRE(hit_f && hit_tm2 && hit_n && list_f && list_tm2 && list_n && list_total, "%s: null list", name);
+    FaceListArgs a;
+    a.x = x; a.x0 = x0; a.csr = csr; a.faces = faces; a.fcsr = fcsr; a.hit_f = hit_f; a.hit_tm2 = hit_tm2; a.hit_n = hit_n; a.list_f = list_f;
+    a.list_tm2 = list_tm2; a.list_n = list_n; a.list_total = list_total; a.fdiag = fdiag; a.bad = bad; a.tf2 = face_host[0]; a.rf2 = face_host[1];
+    a.Kf = Kf; a.chunks = chunks;
+    hipStream_t st = gn_stream(stream);
+    const unsigned vb = (unsigned)gn_cdiv(max_verts, CL_FACE_BLOCK);
+    hipLaunchKernelGGL(cl_face_hits_kernel, dim3(vb, (unsigned)chunks, (unsigned)B), dim3(CL_FACE_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(cl_face_concat_kernel, dim3(vb, (unsigned)B), dim3(CL_FACE_BLOCK), 0, st, a);
+    GN_LAUNCH_CHECK(name);
+    return GN_OK;
+}
+
+extern "C" int gn_cloth_simulate_face_contacts_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0,
+                                                     const double *alpha_t, const int64_t *csr, const int64_t *colour_off, int B, int64_t total_verts,
+                                                     int64_t total_constraints, int64_t substeps, int max_substeps_per_launch,
+                                                     const double *consts_host, int lds_bytes, int block, int64_t *bad, const int32_t *list_j,
+                                                     const double *list_tm2, const int32_t *list_n, int K, const double *collision_host, double *corr,
+                                                     int64_t *diag, const int32_t *faces, const int64_t *fcsr, int64_t total_faces,
+                                                     const int32_t *flist_f, const double *flist_tm2, int64_t flist_entries, const int32_t *flist_n,
+                                                     int64_t flist_rows, int Kf, const double *face_host, int64_t *fdiag, int64_t fdiag_rows,
+                                                     void *stream) {
+    const char *name = "gn_cloth_simulate_face_contacts_batch";
+    GN_REQUIRE(K >= 1 && K <= CL_MAX_LIST, "%s: K=%d outside [1, %d]", name, K, CL_MAX_LIST);
+    if (int rc = cl_face_constants(name, face_host, collision_host, Kf)) return rc;
+    GN_REQUIRE(cl_finite(collision_host[3]) && collision_host[3] > 0.0 && collision_host[3] <= 1.0, "%s: collision constant 3 (relax) is not in (0, 1]",
+               name);
+    GN_REQUIRE(total_faces >= 0 && total_faces < INT32_MAX / 3, "%s: %lld faces: the table must stay below 2^31 entries", name, (long long)total_faces);
+    GN_REQUIRE(total_verts < 0 || (flist_entries >= total_verts * Kf && flist_rows >= total_verts),
+               "%s: face lists of %lld entries and %lld rows, %lld and %lld needed", name, (long long)flist_entries, (long long)flist_rows,
+               (long long)(total_verts * Kf), (long long)total_verts);
+    GN_REQUIRE(fdiag_rows >= B, "%s: fdiag of %lld rows, %d needed", name, (long long)fdiag_rows, B);
+    GN_REQUIRE(B == 0 || (diag && fdiag && fcsr), "%s: null diag / fdiag / fcsr", name);
+    GN_REQUIRE(B == 0 || total_verts == 0 || (list_j && list_tm2 && list_n && corr && flist_f && flist_tm2 && flist_n), "%s: null list / corr", name);
+    GN_REQUIRE(B == 0 || total_faces == 0 || faces, "%s: null faces", name);
+    ClothArgsFaces a;
+    a.x = x; a.v = v; a.w = w; a.pairs = pairs; a.l0 = l0; a.alpha_t = alpha_t; a.csr = csr; a.colour_off = colour_off; a.bad = bad;
+    a.list_j = list_j; a.list_tm2 = list_tm2; a.list_n = list_n; a.corr = corr; a.diag = diag; a.relax = collision_host[3]; a.K = K;
+    a.faces = faces; a.fcsr = fcsr; a.flist_f = flist_f; a.flist_tm2 = flist_tm2; a.flist_n = flist_n; a.fdiag = fdiag; a.Kf = Kf;
+    return cloth_launch<true, true>(name, a, B, total_verts, total_constraints, substeps, max_substeps_per_launch, consts_host, lds_bytes, block,
+                                    stream);
 }

@@ -1,6 +1,7 @@
 // mesh_pair.h -- the per-(query, face) device cores of the all-pairs mesh kernels, fp64, no fma: the solid angle of winding.hip (wn_*) and the squared
-// point-to-triangle distance of eval_dist.hip (pm_*).  winding.hip, eval_dist.hip and query_targets.hip include this file, so that one definition serves
-// every kernel that is held to garmentnets_amd/winding.py and garmentnets_amd/distance.py.  The vertex type is a template parameter: the dataset
+// point-to-triangle distance of eval_dist.hip (pm_*).  winding.hip, eval_dist.hip, query_targets.hip and cloth.hip (pm_closest, the vertex-face contacts
+// of garmentnets_amd/cloth.py) include this file, so that one definition serves every kernel that is held to garmentnets_amd/winding.py and
+// garmentnets_amd/distance.py.  The vertex type is a template parameter: the dataset
 // preparation entries read fp64 vertices, the training-target entries the stored fp32 ones, widened exactly.
 #pragma once
 #include <math.h>
@@ -167,4 +168,73 @@ __device__ __forceinline__ double pm_sqdist(const PmTri &T, double qx, double qy
     // noise, `plane` is then only an upper bound and an edge can be closer
     const double seg = fmin(fmin(s0, s1), s2);
     return inside ? fmin(plane, seg) : seg;
+}
+
+// the PM_NCONST constants of the triangle (p0, p1, p2) in registers: pm_stage_tile's expressions, for a kernel that meets a triangle once
+__device__ __forceinline__ PmTri pm_tri_of(const double (&p0)[3], const double (&p1)[3], const double (&p2)[3]) {
+    PmTri T;
+    const double e0x = __dsub_rn(p1[0], p0[0]), e0y = __dsub_rn(p1[1], p0[1]), e0z = __dsub_rn(p1[2], p0[2]);
+    const double e1x = __dsub_rn(p2[0], p0[0]), e1y = __dsub_rn(p2[1], p0[1]), e1z = __dsub_rn(p2[2], p0[2]);
+    const double e2x = __dsub_rn(p2[0], p1[0]), e2y = __dsub_rn(p2[1], p1[1]), e2z = __dsub_rn(p2[2], p1[2]);
+    const double a = ed_dot3(e0x, e0y, e0z, e0x, e0y, e0z), b = ed_dot3(e0x, e0y, e0z, e1x, e1y, e1z);
+    const double c = ed_dot3(e1x, e1y, e1z, e1x, e1y, e1z), l2 = ed_dot3(e2x, e2y, e2z, e2x, e2y, e2z);
+    const double det = __dsub_rn(__dmul_rn(a, c), __dmul_rn(b, b));
+    T.k[PM_V0X] = p0[0]; T.k[PM_V0Y] = p0[1]; T.k[PM_V0Z] = p0[2];
+    T.k[PM_E0X] = e0x; T.k[PM_E0Y] = e0y; T.k[PM_E0Z] = e0z;
+    T.k[PM_E1X] = e1x; T.k[PM_E1Y] = e1y; T.k[PM_E1Z] = e1z;
+    T.k[PM_V1X] = p1[0]; T.k[PM_V1Y] = p1[1]; T.k[PM_V1Z] = p1[2];
+    T.k[PM_E2X] = e2x; T.k[PM_E2Y] = e2y; T.k[PM_E2Z] = e2z;
+    T.k[PM_A] = a; T.k[PM_B] = b; T.k[PM_C] = c;
+    T.k[PM_IDET] = pm_rcp_or_zero(det);
+    T.k[PM_IA] = pm_rcp_or_zero(a); T.k[PM_IC] = pm_rcp_or_zero(c); T.k[PM_IE2] = pm_rcp_or_zero(l2);
+    return T;
+}
+
+// pm_seg, which also returns what it squares (r) and the clamped parameter
+__device__ __forceinline__ double pm_seg_closest(double wx, double wy, double wz, double dx, double dy, double dz, double wd, double inv_len2,
+                                                 double (&r)[3], double &u) {
+    u = fmin(fmax(__dmul_rn(wd, inv_len2), 0.0), 1.0);
+    r[0] = __dsub_rn(wx, __dmul_rn(u, dx)); r[1] = __dsub_rn(wy, __dmul_rn(u, dy)); r[2] = __dsub_rn(wz, __dmul_rn(u, dz));
+    return ed_dot3(r[0], r[1], r[2], r[0], r[1], r[2]);
+}
+
+// pm_sqdist, which also names the winner (cloth.py "Vertex-face contacts", point_triangle): the squared distance (the bits of pm_sqdist), r = q - the
+// closest point as the winner computes it, bary the closest point's weights on (v0, v1, v2).  The plane wins when the projection is inside and
+// plane <= min(s0, s1, s2); otherwise the first of s0, s1, s2 that equals the minimum.
+__device__ __forceinline__ double pm_closest(const PmTri &T, double qx, double qy, double qz, double (&r)[3], double (&bary)[3]) {
+    const double wx = __dsub_rn(qx, T.k[PM_V0X]), wy = __dsub_rn(qy, T.k[PM_V0Y]), wz = __dsub_rn(qz, T.k[PM_V0Z]);
+    const double e0x = T.k[PM_E0X], e0y = T.k[PM_E0Y], e0z = T.k[PM_E0Z];
+    const double e1x = T.k[PM_E1X], e1y = T.k[PM_E1Y], e1z = T.k[PM_E1Z];
+    const double d0 = ed_dot3(wx, wy, wz, e0x, e0y, e0z), d1 = ed_dot3(wx, wy, wz, e1x, e1y, e1z);
+    double r0[3], r1[3], r2[3], u0, u1, u2;
+    const double s0 = pm_seg_closest(wx, wy, wz, e0x, e0y, e0z, d0, T.k[PM_IA], r0, u0);
+    const double s1 = pm_seg_closest(wx, wy, wz, e1x, e1y, e1z, d1, T.k[PM_IC], r1, u1);
+    const double ux = __dsub_rn(qx, T.k[PM_V1X]), uy = __dsub_rn(qy, T.k[PM_V1Y]), uz = __dsub_rn(qz, T.k[PM_V1Z]);
+    const double e2x = T.k[PM_E2X], e2y = T.k[PM_E2Y], e2z = T.k[PM_E2Z];
+    const double s2 = pm_seg_closest(ux, uy, uz, e2x, e2y, e2z, ed_dot3(ux, uy, uz, e2x, e2y, e2z), T.k[PM_IE2], r2, u2);
+    const double a = T.k[PM_A], b = T.k[PM_B], c = T.k[PM_C], idet = T.k[PM_IDET];
+    const double s = __dmul_rn(__dsub_rn(__dmul_rn(c, d0), __dmul_rn(b, d1)), idet);
+    const double t = __dmul_rn(__dsub_rn(__dmul_rn(a, d1), __dmul_rn(b, d0)), idet);
+    const double rx = __dsub_rn(__dsub_rn(wx, __dmul_rn(s, e0x)), __dmul_rn(t, e1x));
+    const double ry = __dsub_rn(__dsub_rn(wy, __dmul_rn(s, e0y)), __dmul_rn(t, e1y));
+    const double rz = __dsub_rn(__dsub_rn(wz, __dmul_rn(s, e0z)), __dmul_rn(t, e1z));
+    const double plane = ed_dot3(rx, ry, rz, rx, ry, rz);
+    const bool inside = idet > 0.0 && s >= 0.0 && t >= 0.0 && __dadd_rn(s, t) <= 1.0;
+    const double seg = fmin(fmin(s0, s1), s2);
+    if (inside && plane <= seg) {
+        r[0] = rx; r[1] = ry; r[2] = rz;
+        bary[0] = __dsub_rn(__dsub_rn(1.0, s), t); bary[1] = s; bary[2] = t;
+        return plane;
+    }
+    if (s0 == seg) {
+        r[0] = r0[0]; r[1] = r0[1]; r[2] = r0[2];
+        bary[0] = __dsub_rn(1.0, u0); bary[1] = u0; bary[2] = 0.0;
+    } else if (s1 == seg) {
+        r[0] = r1[0]; r[1] = r1[1]; r[2] = r1[2];
+        bary[0] = __dsub_rn(1.0, u1); bary[1] = 0.0; bary[2] = u1;
+    } else {
+        r[0] = r2[0]; r[1] = r2[1]; r[2] = r2[2];
+        bary[0] = 0.0; bary[1] = __dsub_rn(1.0, u2); bary[2] = u2;
+    }
+    return seg;
 }

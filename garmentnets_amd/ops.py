@@ -2396,6 +2396,112 @@ def cloth_contact_stats(diag, col):
             for r, tr in zip(d, travel)]
 
 
+def cloth_face_collision_constants(garments, who):
+    """the face-contact record the garments of one call share (cloth.face_collision_constants) -> None with face contacts off, else the record with
+    "host" (ctypes double[2] = tf2, rf2) added.  Refused by name: records that differ, a record with the vertex contacts off, a constant that is not
+    finite or not positive, Kf outside [1, 32]."""
+    fcol = garments[0].face_collision
+    if any(g.face_collision != fcol for g in garments):
+        raise ValueError(f"{who}: the garments of one call must share their face-contact constants (face_thickness, margin, face_max_list)")
+    if fcol is None:
+        return None
+    if any(g.collision is None for g in garments):
+        raise ValueError(f"{who}: face-contact constants are set but the vertex contacts are off (collision_thickness = 0)")
+    for k in ("tf2", "rf", "rf2"):
+        if not (np.isfinite(fcol[k]) and fcol[k] > 0):
+            raise ValueError(f"{who}: face-contact constant {k}={fcol[k]} is not finite and positive")
+    if int(fcol["Kf"]) != fcol["Kf"] or not 1 <= fcol["Kf"] <= _lib.CLOTH_FACE_MAX_LIST:
+        raise ValueError(f"{who}: face_max_list Kf={fcol['Kf']} outside [1, {_lib.CLOTH_FACE_MAX_LIST}]")
+    return dict(fcol, host=(ctypes.c_double * 2)(fcol["tf2"], fcol["rf2"]))
+
+
+CLOTH_FACE_HIT_BYTES = 256 << 20       # the most the per-chunk hit buffers of a face-list build may take: fewer chunks beyond it
+
+
+def cloth_face_chunks(n_garments, max_verts, max_faces, total_verts, Kf):
+    """the face chunks of a face-list build: enough workgroups (vertex blocks x chunks x garments) for about two per compute unit, no chunk below one
+    tile of 128 faces, the hit buffers within CLOTH_FACE_HIT_BYTES.  The lists do not depend on it."""
+    blocks = max(1, n_garments * -(-max_verts // _lib.CLOTH_FACE_BLOCK))
+    chunks = max(1, min(-(-512 // blocks), -(-max_faces // 128), 64))
+    while chunks > 1 and total_verts * chunks * Kf * 12 > CLOTH_FACE_HIT_BYTES:
+        chunks //= 2
+    return chunks
+
+
+def cloth_face_buffers(garments, t, fcol, dev, chunks=None, x0=None):
+    """what the two face-contact entries need beside cloth_device_tables' `t`: x0 (or the tensor cloth_contact_buffers made), faces and their CSR, the
+    per-chunk hit buffers, the lists (rows of stride Kf) and fdiag, each a tensor of its own"""
+    n, B, Kf = t["total_verts"], len(garments), fcol["Kf"]
+    faces = [np.clip(np.asarray(g.faces, dtype=np.int64).reshape(-1, 3), -1, 2 ** 31 - 1) for g in garments]      # an index beyond int32 stays out of range
+    f_off = np.concatenate([[0], np.cumsum([len(f) for f in faces])])
+    max_verts, max_faces = max(len(g.w) for g in garments), max(len(f) for f in faces)
+    if f_off[-1] >= (2 ** 31 - 1) // 3 or n >= (2 ** 31 - 1) // _lib.CLOTH_MAX_LIST:
+        raise ValueError("cloth face contacts: the tables must stay below 2^31 entries")
+    chunks = cloth_face_chunks(B, max_verts, max_faces, n, Kf) if chunks is None else int(chunks)
+    if not 1 <= chunks <= _lib.CLOTH_FACE_MAX_CHUNKS:
+        raise ValueError(f"cloth face contacts: chunks={chunks} outside [1, {_lib.CLOTH_FACE_MAX_CHUNKS}]")
+    if x0 is None:
+        x0 = torch.from_numpy(np.ascontiguousarray(np.concatenate([g.x0 for g in garments]).reshape(-1, 3))).to(dev)
+    return {"x0": x0,
+            "faces": torch.from_numpy(np.ascontiguousarray(np.concatenate(faces).astype(np.int32))).to(dev),
+            "fcsr": torch.from_numpy(f_off.astype(np.int64)).to(dev), "total_faces": int(f_off[-1]), "max_verts": max_verts, "chunks": chunks,
+            "hit_f": torch.empty((n, chunks, Kf), dtype=torch.int32, device=dev), "hit_tm2": torch.empty((n, chunks, Kf), dtype=torch.float64, device=dev),
+            "hit_n": torch.zeros((n, chunks), dtype=torch.int32, device=dev),
+            "list_f": torch.full((n, Kf), -1, dtype=torch.int32, device=dev), "list_tm2": torch.zeros((n, Kf), dtype=torch.float64, device=dev),
+            "list_n": torch.zeros(n, dtype=torch.int32, device=dev), "list_total": torch.zeros(n, dtype=torch.int32, device=dev),
+            "fdiag": torch.zeros((B, 3), dtype=torch.int64, device=dev)}
+
+
+def _cloth_face_lists_call(t, fc, col, fcol, B, bad):
+    _lib.call("gn_cloth_face_contact_lists", _p(t["x"]), _p(fc["x0"]), _p(t["csr"]), _p(fc["faces"]), _p(fc["fcsr"]), B, t["total_verts"],
+              fc["total_faces"], fc["max_verts"], ctypes.cast(fcol["host"], ctypes.c_void_p), ctypes.cast(col["host"], ctypes.c_void_p), fcol["Kf"],
+              fc["chunks"], _p(fc["hit_f"]), _p(fc["hit_tm2"]), fc["hit_f"].numel(), _p(fc["hit_n"]), fc["hit_n"].numel(), _p(fc["list_f"]),
+              _p(fc["list_tm2"]), fc["list_f"].numel(), _p(fc["list_n"]), _p(fc["list_total"]), fc["list_n"].numel(), _p(fc["fdiag"]),
+              fc["fdiag"].shape[0], _p(bad), _stream())
+
+
+def cloth_face_contact_stats(fdiag):
+    """the rows of the device's fdiag table -> one dict of the definition's three face diagnostics per garment"""
+    return [{"face_contact_overflow": int(r[0]), "face_contact_max_list": int(r[1]), "face_contact_active": int(r[2])} for r in fdiag.cpu().numpy()]
+
+
+def cloth_face_contact_lists(garments, states=None, backend="hip", device=None, chunks=None):
+    """the face-contact lists of cloth.py's definition for every garment at the positions of `states` (None: the start pose), all garments in the same
+    launches (gn_cloth_face_contact_lists: all (vertex, face) pairs, the faces of a garment spread over `chunks` workgroups per block of vertices; None:
+    cloth_face_chunks) -> [((idx (V, Kf) int32, tm2 (V, Kf) float64), counts (V,) int64, overflow (V,) int64)] tensors: bit for bit
+    cloth.face_contact_lists_reference (backend "numpy"), whatever `chunks`.  The garments must have face contacts on and share their constants.  A face
+    index outside [0, V) raises IndexError (after the launch; nothing is read or written through it)."""
+    from . import cloth
+    if backend not in ("hip", "numpy"):
+        raise ValueError(f"backend {backend!r}: expected 'hip' or 'numpy'")
+    states = [None] * len(garments) if states is None else list(states)
+    if len(states) != len(garments):
+        raise ValueError("cloth_face_contact_lists: one state per garment")
+    states = [cloth.state_arrays(g, *(s if s is not None else (None, None)), who="cloth_face_contact_lists") for g, s in zip(garments, states)]
+    if not garments:
+        return []
+    col = cloth_collision_constants(garments, "cloth_face_contact_lists")
+    fcol = cloth_face_collision_constants(garments, "cloth_face_contact_lists")
+    if fcol is None:
+        raise ValueError("cloth_face_contact_lists: the garments have face contacts off (face_thickness = 0)")
+    if backend == "numpy":
+        out = []
+        for g, (x, _) in zip(garments, states):
+            (idx, tm2), counts, overflow = cloth.face_contact_lists_reference(g, x)
+            out.append(((torch.from_numpy(idx), torch.from_numpy(tm2)), torch.from_numpy(counts), torch.from_numpy(overflow)))
+        return out
+    if len(garments) > 65535:
+        raise ValueError(f"cloth_face_contact_lists: at most 65535 garments per call, got {len(garments)}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    t = cloth_device_tables(garments, states, dev)
+    fc = cloth_face_buffers(garments, t, fcol, dev, chunks)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _cloth_face_lists_call(t, fc, col, fcol, len(garments), bad)
+    _raise_bad_face(bad.item(), "cloth_face_contact_lists")
+    counts, total = fc["list_n"].to(torch.int64), fc["list_total"].to(torch.int64)
+    return [((fc["list_f"][a:b], fc["list_tm2"][a:b]), counts[a:b], total[a:b] - counts[a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
+
+
 def cloth_contact_lists(garments, states=None, backend="hip", device=None):
     """the contact lists of cloth.py's definition for every garment at the positions of `states` (None: the start pose), all garments in the same
     launches (gn_cloth_contact_lists: a hashed uniform grid, many workgroups per garment) -> [((idx (V, K) int32, tm2 (V, K) float64), counts (V,)
@@ -2442,7 +2548,11 @@ def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_bud
     Garments with contacts on (ClothParams.collision_thickness > 0; the garments of one call share their collision constants) run the contact pass of
     the definition: the wrapper alternates gn_cloth_contact_lists (every collision_rebuild substeps, counted from the call's first) and
     gn_cloth_simulate_contacts_batch on one stream, without a host synchronisation between them.  stats=True returns (states, [the four contact
-    diagnostics of the definition per garment]) (all 0 with contacts off); without it the return value is what it always was."""
+    diagnostics of the definition per garment]) (all 0 with contacts off); without it the return value is what it always was.
+
+    Garments with face contacts on as well (ClothParams.face_thickness > 0, Garment.face_collision; shared by the garments of one call) run the
+    face entries of the definition: gn_cloth_face_contact_lists follows every gn_cloth_contact_lists build on the same stream and the solver is
+    gn_cloth_simulate_face_contacts_batch; stats=True then carries the three face diagnostics too.  With face contacts off nothing changes."""
     from . import cloth
     if backend not in ("hip", "numpy"):
         raise ValueError(f"backend {backend!r}: expected 'hip' or 'numpy'")
@@ -2458,6 +2568,7 @@ def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_bud
     if any(g.consts != garments[0].consts for g in garments):
         raise ValueError("cloth_simulate_batch: the garments of one call must share their step constants (h, gravity, damping, compliances)")
     col = cloth_collision_constants(garments, "cloth_simulate_batch")
+    fcol = cloth_face_collision_constants(garments, "cloth_simulate_batch")
     if backend == "numpy":
         ref = [cloth.simulate_reference(g, substeps, x, v, stats=True) for g, (x, v) in zip(garments, states)]
         out = [tuple(torch.from_numpy(a) for a in r[:2]) for r in ref]
@@ -2487,18 +2598,28 @@ def cloth_simulate_batch(garments, substeps, states=None, backend="hip", lds_bud
         c = cloth_contact_buffers(garments, t, col, dev)
         lists = (_p(c["list_j"]), _p(c["list_tm2"]), _p(c["list_n"]), col["K"], ctypes.cast(col["host"], ctypes.c_void_p), _p(c["corr"]),
                  _p(c["diag"]))
+        entry = "gn_cloth_simulate_contacts_batch"
+        if fcol is not None:
+            fc = cloth_face_buffers(garments, t, fcol, dev, x0=c["x0"])
+            entry = "gn_cloth_simulate_face_contacts_batch"
+            lists += (_p(fc["faces"]), _p(fc["fcsr"]), fc["total_faces"], _p(fc["list_f"]), _p(fc["list_tm2"]), fc["list_f"].numel(), _p(fc["list_n"]),
+                      fc["list_n"].numel(), fcol["Kf"], ctypes.cast(fcol["host"], ctypes.c_void_p), _p(fc["fdiag"]), fc["fdiag"].shape[0])
         done = 0
         while True:                                                           # one pass with substeps == 0: the table is still checked
             n = min(col["R"], substeps - done)
             if n > 0:
                 _cloth_lists_call(t, c, col, len(garments), _lib.CLOTH_LISTS_BUILD | (_lib.CLOTH_LISTS_TRAVEL if done else 0))
-            _lib.call("gn_cloth_simulate_contacts_batch", *solver, n, *tail, *lists, _stream())
+                if fcol is not None:
+                    _cloth_face_lists_call(t, fc, col, fcol, len(garments), bad)
+            _lib.call(entry, *solver, n, *tail, *lists, _stream())
             done += n
             if done >= substeps:
                 break
         if substeps > 0:
             _cloth_lists_call(t, c, col, len(garments), _lib.CLOTH_LISTS_TRAVEL)
         contact_stats = cloth_contact_stats(c["diag"], col) if stats else None
+        if stats and fcol is not None:
+            contact_stats = [dict(a, **b) for a, b in zip(contact_stats, cloth_face_contact_stats(fc["fdiag"]))]
     _raise_bad_face(bad.item(), "cloth_simulate")
     out = [(t["x"][a:b], t["v"][a:b]) for a, b in zip(t["v_off"][:-1], t["v_off"][1:])]
     return (out, contact_stats) if stats else out

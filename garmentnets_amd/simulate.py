@@ -15,6 +15,10 @@ garment's mean stretch rest length, cloth.mean_stretch_rest_length, so it differ
 "cloth_simulation", and a sample with contact_overflow > 0 or contact_travel > 1 is named in a printed warning (a contact may have been cut off or
 missed).  Without the flag the store is byte for byte what it was.
 
+--face_contacts (only with --self_collision) turns the vertex-face contacts of cloth.py on as well: --face_thickness (default:
+cloth.DEFAULT_FACE_THICKNESS_FACTOR times the garment's mean stretch rest length), --face_max_list.  The two parameters and the three face-contact
+diagnostics then join "cloth_simulation", and face_contact_overflow > 0 joins the warning.  Without the flag nothing changes.
+
 An existing cloth_verts is kept unless --overwrite is given.  --backend hip runs --batch_size garments per call of ops.cloth_simulate_batch (one workgroup
 each); --backend numpy runs the restatement, which gives the same bits.  After this command `prepare` can build every other group: simulate -> prepare ->
 train -> predict -> evaluate runs from canonical meshes alone.
@@ -57,6 +61,10 @@ def build_parser():
     ap.add_argument("--collision_rebuild", type=int, default=cloth.DEFAULT_COLLISION_REBUILD, help="substeps between two contact-list builds")
     ap.add_argument("--collision_max_list", type=int, default=cloth.DEFAULT_COLLISION_MAX_LIST, help="entries a contact list can hold, at most 64")
     ap.add_argument("--collision_relax", type=float, default=cloth.DEFAULT_COLLISION_RELAX, help="in (0, 1]: the share of a contact correction applied")
+    ap.add_argument("--face_contacts", action="store_true", help="vertex-face contacts (cloth.py) beside the vertex-vertex ones; needs --self_collision")
+    ap.add_argument("--face_thickness", type=float, default=None,
+                    help=f"metres; default {cloth.DEFAULT_FACE_THICKNESS_FACTOR} x the garment's mean stretch rest length")
+    ap.add_argument("--face_max_list", type=int, default=cloth.DEFAULT_FACE_MAX_LIST, help="entries a face-contact list can hold, at most 32")
     return ap
 
 
@@ -71,7 +79,8 @@ def grip_index(sample_group, dataset_idx, num_verts, seed):
 
 
 def collision_params(params, g, collision):
-    """`params` with the contacts of `collision` ({"thickness", "margin" (None: the defaults from the garment g), "rebuild", "max_list", "relax"}) on"""
+    """`params` with the contacts of `collision` ({"thickness", "margin" (None: the defaults from the garment g), "rebuild", "max_list", "relax"}) on;
+    with the key "face" ({"thickness" (None: the default from g), "max_list"}) the vertex-face contacts too"""
     t = collision.get("thickness")
     if t is None:
         t = cloth.DEFAULT_COLLISION_THICKNESS_FACTOR * cloth.mean_stretch_rest_length(g)
@@ -80,15 +89,24 @@ def collision_params(params, g, collision):
         m = cloth.DEFAULT_COLLISION_MARGIN_FACTOR * t
     if not t > 0:
         raise ValueError(f"collision thickness {t}: expected a positive number (a garment without a stretch constraint has no default)")
-    return dataclasses.replace(params, collision_thickness=float(t), collision_margin=float(m), collision_rebuild=int(collision["rebuild"]),
-                               collision_max_list=int(collision["max_list"]), collision_relax=float(collision["relax"]))
+    on = dataclasses.replace(params, collision_thickness=float(t), collision_margin=float(m), collision_rebuild=int(collision["rebuild"]),
+                             collision_max_list=int(collision["max_list"]), collision_relax=float(collision["relax"]))
+    face = collision.get("face")
+    if face is None:
+        return on
+    tf = face.get("thickness")
+    if tf is None:
+        tf = cloth.DEFAULT_FACE_THICKNESS_FACTOR * cloth.mean_stretch_rest_length(g)
+    if not tf > 0:
+        raise ValueError(f"face thickness {tf}: expected a positive number (a garment without a stretch constraint has no default)")
+    return dataclasses.replace(on, face_thickness=float(tf), face_max_list=int(face["max_list"]))
 
 
 def run_batch(garments, substeps, backend):
-    """-> ([(x, v)] numpy, [the contact diagnostics]) of `garments`, those that share their collision constants in one call each"""
+    """-> ([(x, v)] numpy, [the contact diagnostics]) of `garments`, those that share their collision and face-contact constants in one call each"""
     groups = {}
     for n, g in enumerate(garments):
-        groups.setdefault(json.dumps(g.collision, sort_keys=True), []).append(n)
+        groups.setdefault(json.dumps([g.collision, g.face_collision], sort_keys=True), []).append(n)
     states, stats = [None] * len(garments), [None] * len(garments)
     for idx in groups.values():
         gs = [garments[n] for n in idx]
@@ -135,7 +153,8 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
             raise ValueError(f"{zarr_in}: sample {k} has no mesh/{missing[0]}: the garment is simulated from its canonical mesh")
     todo = [(i, k) for i, k in enumerate(keys) if overwrite or "mesh/cloth_verts" not in samples[k]]
     comp = zarr_store.default_compressor()
-    record = dict({k: v for k, v in dataclasses.asdict(params).items() if k not in cloth.COLLISION_FIELDS}, duration=float(duration),
+    record = dict({k: v for k, v in dataclasses.asdict(params).items() if k not in cloth.COLLISION_FIELDS + cloth.FACE_COLLISION_FIELDS},
+                  duration=float(duration),
                   substeps=substeps, rest_scale=scale)
     warned = []
     t_all = time.perf_counter()
@@ -149,8 +168,8 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
             g = cloth.garment_from_nocs(nocs, mesh["cloth_faces_tri"][:], grip_index(samples[k], i, len(nocs), seed), scale, params)
             if collision is not None:
                 on = collision_params(params, g, collision)
-                g = dataclasses.replace(g, collision=cloth.collision_constants(on))
-                extra.append({f: getattr(on, f) for f in cloth.COLLISION_FIELDS})
+                g = dataclasses.replace(g, collision=cloth.collision_constants(on), face_collision=cloth.face_collision_constants(on))
+                extra.append({f: getattr(on, f) for f in cloth.COLLISION_FIELDS + (cloth.FACE_COLLISION_FIELDS if on.face_contacts else ())})
             garments.append(g)
         states, stats = run_batch(garments, substeps, backend)
         dt = time.perf_counter() - t0
@@ -158,11 +177,14 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
             diag = cloth.diagnostics(g, x, v)
             if collision is not None:
                 diag = dict(diag, **extra[n], **stats[n])
-                if stats[n]["contact_overflow"] > 0 or stats[n]["contact_travel"] > 1:
+                face_cut = stats[n].get("face_contact_overflow", 0)
+                if stats[n]["contact_overflow"] > 0 or stats[n]["contact_travel"] > 1 or face_cut > 0:
                     warned.append(k)
-                    log({"warning": f"sample {k}: contact_overflow {stats[n]['contact_overflow']}, contact_travel {stats[n]['contact_travel']:.3g}: "
-                                    "a contact may have been cut off or missed (raise --collision_max_list or --collision_margin, or lower "
-                                    "--collision_rebuild)"})
+                    face_note = f", face_contact_overflow {face_cut}" if "face_contact_overflow" in stats[n] else ""
+                    face_hint = "; for the face lists raise --face_max_list or lower --collision_margin" if face_cut > 0 else ""
+                    log({"warning": f"sample {k}: contact_overflow {stats[n]['contact_overflow']}, contact_travel {stats[n]['contact_travel']:.3g}"
+                                    f"{face_note}: a contact may have been cut off or missed (raise --collision_max_list or "
+                                    f"--collision_margin, or lower --collision_rebuild{face_hint})"})
             mesh = samples[k].require_group("mesh")
             mesh.array("cloth_verts", x.astype(np.float32), compressor=comp)
             mesh.put_attrs({"cloth_simulation": dict(record, grip_vertex_idx=g.grip, **diag)})
@@ -184,6 +206,8 @@ def simulate_store(zarr_in, params=None, duration=cloth.DEFAULT_DURATION, rest_s
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.face_contacts and not a.self_collision:
+        ap.error("--face_contacts needs --self_collision: the face contacts share the vertex contacts' margin, rebuild interval and relaxation")
     try:
         params = cloth.ClothParams(gravity=a.gravity, h=a.h, damping=a.damping, alpha_stretch=a.alpha_stretch, alpha_bend=a.alpha_bend,
                                    density=a.density)
@@ -191,6 +215,8 @@ def main(argv=None):
         if a.self_collision:
             collision = {"thickness": a.collision_thickness, "margin": a.collision_margin, "rebuild": a.collision_rebuild,
                          "max_list": a.collision_max_list, "relax": a.collision_relax}
+            if a.face_contacts:
+                collision["face"] = {"thickness": a.face_thickness, "max_list": a.face_max_list}
         return simulate_store(a.zarr_in, params, a.duration, a.rest_scale, a.batch_size, a.overwrite, a.update_summary, a.backend, a.seed,
                               log=lambda row: print(json.dumps(row)), collision=collision)
     except ValueError as e:

@@ -1101,6 +1101,38 @@ int gn_cloth_simulate_contacts_batch(double *x, double *v, const double *w, cons
                                      const int32_t *list_j, const double *list_tm2, const int32_t *list_n, int K, const double *collision_host,
                                      double *corr, int64_t *diag, void *stream);
 
+/* Vertex-face contacts of the hanging garment (cloth.py "Vertex-face contacts"; DESIGN.md "Hanging garments").  The face-contact lists of B ragged
+ * garments for the positions x and the start poses x0, over ALL (vertex, face) pairs -- bit for bit cloth.face_contact_lists_reference.  csr: the
+ * solver's table (only v_off is read); faces [*][3] int32 vertex indices relative to the garment's first vertex; fcsr [B + 1] int64 the garments'
+ * first faces.  face_host [2] = {tf2, rf2}; collision_host: the vertex contacts' constants (must be given: face contacts need them on; not read
+ * further).  `chunks` in [1, 1024] spreads the faces of a garment over that many workgroups per block of 256 vertices (the lists do not depend on
+ * it); hit_f / hit_tm2 [total_verts][chunks][Kf] (hit_entries entries each) and hit_n [total_verts][chunks] (hit_rows rows) hold the per-chunk hits
+ * between the two kernels.  Written per vertex row: list_f [*][Kf] (ascending face indices relative to the garment's first face, -1 beyond the row's
+ * entries), list_tm2 [*][Kf] (min(tf2, the rest squared distance), 0 beyond), list_n [*] (entries, at most Kf), list_total [*] (the uncut length);
+ * list_entries / list_rows are the sizes the caller allocated.  fdiag [fdiag_rows >= B][3] int64 (caller zeroes it once per run) accumulates {sum of
+ * list_total - list_n, largest list_total, -- (the solver's active face entries)}.  A face index outside [0, V_b) sets *bad (caller zeroes it) and
+ * is never dereferenced.  Refused by name: B > 65535, chunks outside [1, 1024], Kf outside [1, 32], a face constant that is not finite and positive,
+ * null collision constants, too many vertices / faces, short hit buffers / lists / fdiag, null pointers. */
+int gn_cloth_face_contact_lists(const double *x, const double *x0, const int64_t *csr, const int32_t *faces, const int64_t *fcsr, int B,
+                                int64_t total_verts, int64_t total_faces, int max_verts, const double *face_host, const double *collision_host, int Kf,
+                                int chunks, int32_t *hit_f, double *hit_tm2, int64_t hit_entries, int32_t *hit_n, int64_t hit_rows, int32_t *list_f,
+                                double *list_tm2, int64_t list_entries, int32_t *list_n, int32_t *list_total, int64_t list_rows, int64_t *fdiag,
+                                int64_t fdiag_rows, int64_t *bad, void *stream);
+
+/* gn_cloth_simulate_contacts_batch with the face entries of the definition inside the same gather: for a vertex its vertex entries first, then its
+ * face entries (flist_f, flist_tm2, flist_n: the lists of gn_cloth_face_contact_lists, rows of stride Kf), both into one corr, before the single
+ * p += relax * corr.  fdiag[b][2] += the active face entries.  A face-list index outside [0, F_b) or a face corner outside [0, V_b) sets *bad and is
+ * never dereferenced.  Refused by name, beside gn_cloth_simulate_contacts_batch's refusals: Kf outside [1, 32], a face constant that is not finite
+ * and positive, null collision constants, short face lists / fdiag, null faces / fcsr / lists. */
+int gn_cloth_simulate_face_contacts_batch(double *x, double *v, const double *w, const int32_t *pairs, const double *l0, const double *alpha_t,
+                                          const int64_t *csr, const int64_t *colour_off, int B, int64_t total_verts, int64_t total_constraints,
+                                          int64_t substeps, int max_substeps_per_launch, const double *consts_host, int lds_bytes, int block,
+                                          int64_t *bad, const int32_t *list_j, const double *list_tm2, const int32_t *list_n, int K,
+                                          const double *collision_host, double *corr, int64_t *diag, const int32_t *faces, const int64_t *fcsr,
+                                          int64_t total_faces, const int32_t *flist_f, const double *flist_tm2, int64_t flist_entries,
+                                          const int32_t *flist_n, int64_t flist_rows, int Kf, const double *face_host, int64_t *fdiag,
+                                          int64_t fdiag_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
