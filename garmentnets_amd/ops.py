@@ -565,11 +565,31 @@ def pack_upconv_weight_device(w, c0, mode):
 
 
 def upconv_partial(src1, a1, d1, pack, cout, act_inv=None):
-    """coarse source [B][Dc][Hc][Wc][C1] -> polyphase partial sums [B][Dc][Hc][Wc][8 * cout] (csrc/upconv.hip)"""
+    """coarse source [B][Dc][Hc][Wc][C1] -> polyphase partial sums [B][Dc][Hc][Wc][8 * cout] (csrc/upconv.hip).  a1, d1 [B][C1]: the GroupNorm affine of
+    THESE channels (the layer's a[:, c0:], not its full-width rows); act_inv [B] or None; pack: pack_upconv_weight[_device] of the same C1 and cout.
+    TypeError / ValueError, before any launch: the kernel reads every one of them by the strides these shapes imply"""
+    _chk(src1, torch.float32, "src1")
+    if src1.dim() != 5:
+        raise ValueError(f"src1: expected [B][Dc][Hc][Wc][C1], got {tuple(src1.shape)}")
     B, Dc, Hc, Wc, C1 = src1.shape
+    cout = int(cout)
+    for t, name in ((a1, "a"), (d1, "d")):
+        if tuple(_chk(t, torch.float32, name).shape) != (B, C1):
+            raise ValueError(f"{name}: expected [B][C1] = {(B, C1)} (the affine of the upsampled channels alone), got {tuple(t.shape)}")
+    if act_inv is not None and tuple(_chk(act_inv, torch.float32, "act_inv").shape) != (B,):
+        raise ValueError(f"act_inv: expected [B] = {(B,)}, got {tuple(act_inv.shape)}")
+    if pack.mode not in (SPLIT_BF16X2, SPLIT_F16X2):
+        raise ValueError("gn_upconv_partial runs the two-plane modes only")
+    # (widths the entry refuses have no pack size: the entry names them)
+    need = _lib.load().gn_weight_pack_upconv_bytes(C1, cout)
+    have = _chk(pack.tensor, pack.tensor.dtype, "pack").numel() * pack.tensor.element_size()
+    if need and have != need:
+        raise ValueError(f"pack: {have} bytes, the polyphase pack of C1 = {C1}, cout = {cout} has {need} (pack_upconv_weight)")
+    if tuple(_chk(pack.out_scale, torch.float32, "pack.out_scale").shape) != (8 * cout,):
+        raise ValueError(f"pack.out_scale: expected [8 * cout] = {(8 * cout,)}, got {tuple(pack.out_scale.shape)}")
     part = torch.empty((B, Dc, Hc, Wc, 8 * cout), dtype=torch.float32, device=src1.device)
-    _lib.call("gn_upconv_partial", _p(src1), C1, _p(_chk(a1, torch.float32, "a")), _p(_chk(d1, torch.float32, "d")), _p(pack.tensor), pack.mode,
-              _p(pack.out_scale), _p(act_inv), B, Dc, Hc, Wc, cout, _p(part), _stream())
+    _lib.call("gn_upconv_partial", _p(src1), C1, _p(a1), _p(d1), _p(pack.tensor), pack.mode, _p(pack.out_scale), _p(act_inv), B, Dc, Hc, Wc, cout,
+              _p(part), _stream())
     return part
 
 

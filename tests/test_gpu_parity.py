@@ -1660,7 +1660,9 @@ def test_polyphase_decoder_conv_with_the_skip_connection_at_rest():
 
 # ------------------------------------------------------------------------------------------------ polyphase decoder convolutions
 @pytest.mark.parametrize("C0,C1,Cout,dims,B", [(32, 64, 32, (16, 16, 16), 1), (64, 128, 64, (8, 16, 8), 2), (128, 256, 128, (8, 8, 8), 1),
-                                               (32, 64, 32, (64, 64, 64), 2), (16, 32, 64, (4, 6, 10), 1)])
+                                               (32, 64, 32, (64, 64, 64), 2), (16, 32, 64, (4, 6, 10), 1),
+                                               # the 32-wide template of csrc/upconv.hip on a ragged, odd coarse volume; three column blocks
+                                               (16, 32, 32, (6, 10, 18), 1), (16, 16, 96, (2, 6, 10), 2)])
 @pytest.mark.parametrize("mode", [4, 2])
 def test_polyphase_upsampled_conv_equals_literal_form(C0, C1, Cout, dims, B, mode):
     """SingleConv on cat((skip, upsample_nearest(x))) (components/unet3d.py:291,330): the polyphase form (upsampled channels as a
